@@ -6,7 +6,9 @@
 A step = one pass of the hot path over one batch of 64 synthetic 256x256 crops per GPU (BASELINE.json configs[2]: full
 TokenHMR = ViT-H + token decoder + VQ lookup/decode + SMPL LBS, batch 64 per GPU, fp32 in / fp32 out like the reference's
 inference).  `--workload vit` times configs[1] (ViT-H encoder only).  Inputs are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line with the driver's fields plus `roofline`, `cpu_baseline` and `parity`.
+Rank 0 prints ONE JSON line with the driver's fields; `--full` adds `roofline`, `cpu_baseline`, `parity` and the untimed extras
+below (without it they are null or absent, and the run does nothing beyond setup, warm-up and the timed steps).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (inputs and weights are seeded: identical run to run).
 
 Which arithmetic `value` is measured in (round 5: the ENGINE'S DEFAULT — the same mode load_tokenhmr() / thmr_create deliver to a caller
 who passes no mode; bench.py does not touch the switch unless --vit-gemm is given).  The engine has two modes for the four ViT GEMM classes, both fp32 in / fp32 out with
@@ -61,9 +63,18 @@ def parse(argv=None):
                          "products; below 3 crops per GPU it runs the exact-fp32 kernels and the line says f32).  f32: thmr_set_vit_gemm(0), "
                          "the fp32 MFMA pipe.  The other mode is measured after the timed region and reported beside it "
                          "(`exact_f32_mode` / `split3_mode`)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: the fc1 roofline (HIP events in the timed region), the "
+                         "per-step event times, the untimed extras (class split, LBS at B=512, parity, facade, pipeline, batch sweep, "
+                         "the other ViT GEMM mode), the cross-rank check and per-rank local rates at N > 1, and the CPU baseline.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; "
+                         "an output above 16 MB is replaced by a fixed seeded sample of its elements, <name>_sample.npy, with the "
+                         "flat indices of the sample in <name>_sample_index.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-gather", action="store_true", help="skip the per-step packed all-gather at N>1")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras (class split, LBS at B=512, parity)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extras (class split, LBS at B=512, parity)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--fake-engine", action="store_true", help="CPU dry run of the N-rank orchestration (with --backend gloo)")
     ap.add_argument("--self-launch", action="store_true", help="re-exec under torch.distributed.run even at --gpus 1")
@@ -72,6 +83,39 @@ def parse(argv=None):
                          "rank 0 loads, broadcast, receivers finalize, sharded forward, gather, cross-rank check — runs with real "
                          "engines on a one-GPU box; `value` is meaningless (the ranks time-slice one GPU)")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 16 << 20         # per output; larger ones are sampled (at most 64 MB in all)
+DUMP_SAMPLE = 1 << 20             # elements in the sample of a large output
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as float32 DIR/<name>.npy; an array above DUMP_MAX_BYTES as a fixed seeded sample of DUMP_SAMPLE
+    elements (the same indices in every run, so two builds compare element for element) plus those flat indices."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in sorted(arrays.items()):
+        if t is None:
+            continue
+        x = t.detach().float().cpu().numpy() if hasattr(t, "detach") else np.asarray(t, dtype=np.float32)
+        if x.nbytes > DUMP_MAX_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, DUMP_SAMPLE, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            np.save(os.path.join(out_dir, f"{name}_sample.npy"), x.reshape(-1)[idx])
+        else:
+            np.save(os.path.join(out_dir, f"{name}.npy"), x)
+
+
+def library_current(G) -> bool:
+    """Read-only check that G.LIB exists and that the manifest build() wrote beside it says it was linked from the sources as they
+    are now (G.source_hash()).  A stale or missing library, or no readable manifest, means build() has work to do.  The library's
+    own build info is checked against the same hash once it is loaded."""
+    try:
+        with open(G.MANIFEST) as f:
+            manifest = json.load(f)
+    except (OSError, ValueError):
+        return False
+    return os.path.exists(G.LIB) and manifest.get("__lib__") == G.source_hash()
 
 
 def _free_port():
@@ -346,7 +390,7 @@ def lbs_at_b512(dev, smpl):
             "unit": "GB/s", "frac": round(by / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4), "bytes": by}
 
 
-def pipeline_bench(eng, dev, B, steps, warmup, fwd_ms=None):
+def pipeline_bench(eng, dev, B, steps, warmup, fwd_ms=None, extras=True, keep=None):
     """The rows AROUND the path and the pipeline they exist for, measured end to end:
 
         decoded uint8 1080p frames on the HOST (pinned)  --H2D-->  thmr_cropper_run (blur + warp + normalise, csrc/crop.hip)
@@ -355,7 +399,9 @@ def pipeline_bench(eng, dev, B, steps, warmup, fwd_ms=None):
     = what tokenhmr/eval.py:124,144-149 does per batch with a 4-worker cv2 DataLoader, recursive_to, model(batch), evaluator(out, batch).
     Two streams: the copies and crops of batch i + 1 run on a side stream while batch i is in forward / eval on the launch stream
     (double-buffered frames and crops), and nothing synchronises with the host inside the loop (the evaluator accumulates on the device).
-    8 frames x B / 8 people per batch; boxes of 250-900 px (the larger ones take the anti-alias blur of vitdet_dataset.py:62-68)."""
+    8 frames x B / 8 people per batch; boxes of 250-900 px (the larger ones take the anti-alias blur of vitdet_dataset.py:62-68).
+    `extras` False: the timed loop only (no forward-only, per-stage or encoder timings).  `keep`: a dict that receives copies of what
+    the last timed batch computed (the forward's outputs and the device-side metric sums)."""
     import numpy as np
     import torch
     from tokenhmr_amd.preprocess import Cropper, gen_trans_from_patch_cv, expand_to_aspect_ratio
@@ -432,6 +478,12 @@ def pipeline_bench(eng, dev, B, steps, warmup, fwd_ms=None):
     run(steps, timed=True)
     torch.cuda.synchronize()
     pipe_ms = (time.perf_counter() - t0) / steps * 1e3
+    if keep is not None:
+        keep.update({k: v.clone() for k, v in outs.items()}, metric_sums=acc.clone())
+    if not extras:
+        cropper.close()
+        return {"crops_per_s": round(B / (pipe_ms * 1e-3), 2), "ms_per_batch": round(pipe_ms, 3), "frames_per_batch": F,
+                "people_per_frame": P, "steps": steps}
     h2d_ms = sorted(e0.elapsed_time(e1) for e0, e1 in h2d_ev)
     # forward only, same engine, crops resident (the bench's own timed region when it is handed over)
     if fwd_ms is None:
@@ -554,9 +606,11 @@ def main():
         eng = FakeEngine(rank)
     else:
         # ALWAYS bring the library up to date first (incremental by content hash; verifies the loaded .so reports the hash of
-        # the current sources).  Rank 0 builds, the others wait, so N ranks never race on the object files.
+        # the current sources).  Rank 0 builds, the others wait, so N ranks never race on the object files.  A library that build()
+        # already linked from the current sources is only read, never rebuilt: the bench then writes nothing into the tree, which
+        # may be read-only to the user who runs it.
         import __graft_entry__
-        if rank == 0:
+        if rank == 0 and not library_current(__graft_entry__):
             __graft_entry__.build()
         if use_dist:
             dist.barrier()
@@ -611,8 +665,11 @@ def main():
     if a.workload == "pipeline":
         if cpu_dry or world != 1:
             sys.exit("--workload pipeline runs on one GPU with a real engine")
-        res = pipeline_bench(eng, dev, B, a.steps, a.warmup)
+        kept = {} if a.dump_outputs else None
+        res = pipeline_bench(eng, dev, B, a.steps, a.warmup, extras=a.full, keep=kept)
         eng.status()
+        if kept is not None:
+            dump_outputs(a.dump_outputs, kept)
         print(json.dumps({"metric": "crops_per_sec", "value": res["crops_per_s"], "unit": "crops/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
                           "ms_per_step": res["ms_per_batch"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                           "dtype": "f32 (ViT GEMM operands as 3 x bf16 pieces)" if split_mode else "f32", "data": "synthetic",
@@ -680,13 +737,14 @@ def main():
         step()
     join()
     sync()
-    # HIP events around the DOMINANT kernel only (fc1: the GEMM class with the largest share of every step), every 4th of its 32
+    # --full: HIP events around the DOMINANT kernel only (fc1: the GEMM class with the largest share of every step), every 4th of its 32
     # launches per call (one shape): an event pair costs ~2-3 us of stream time — instrumenting the four GEMM classes (round 2)
     # cost 0.75 % of a B = 64 step and 20 % of a B = 1 call.  Its roofline is measured live in the timed region; the other classes
-    # come from a separate untimed pass below.
-    eng.prof_enable("fc1")
+    # come from a separate untimed pass below.  A plain run times the steps without any of these events.
+    if a.full:
+        eng.prof_enable("fc1")
     gw["on"] = True
-    ev = [] if cpu_dry else [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+    ev = [] if (cpu_dry or not a.full) else [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
     if use_dist:
         dist.barrier()
     sync()
@@ -706,12 +764,18 @@ def main():
     gw["on"] = False
     step_ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(a.steps)) if ev else []
     gather_wait_ms = (sum(e0.elapsed_time(e1) for e0, e1 in gw["ev"]) if gw["ev"] else gw["host_s"] * 1e3) / max(1, a.steps)
-    eng.prof_enable(False)
-    prof = eng.prof_collect()
+    prof = {}
+    if a.full:
+        eng.prof_enable(False)
+        prof = eng.prof_collect()
     if not cpu_dry:
         eng.status()            # no asynchronous device-side error in the timed region (bounded grid barrier of the decoder kernel)
+    if a.dump_outputs and rank == 0:
+        # what the timed path handed its caller in the last timed step (rank 0's shard at N > 1), before anything else runs on the engine
+        dump_outputs(a.dump_outputs, {"vit_features": feats} if a.workload == "vit" else last.get("out", {}))
+    extras = a.full and not a.no_extras
     prof_all, breakdown_steps = {}, 0
-    if not a.no_extras and not cpu_dry:
+    if extras and not cpu_dry:
         breakdown_steps = min(2, a.steps)
         eng.prof_enable(True)                       # untimed: every kernel class instrumented, for classes_ms_per_step
         for _ in range(breakdown_steps):
@@ -729,7 +793,7 @@ def main():
         t = torch.tensor([1.0 if gathered_ok else 0.0], device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         gathered_ok = bool(t.item() == 1.0)
-        if rank == 0 and world > 1 and not a.no_extras:
+        if rank == 0 and world > 1 and extras:
             # ... and the OTHER ranks' rows must be what a correctly loaded model computes: rank 0 (which read the checkpoint)
             # regenerates each rank's seeded crops, runs them through its own engine and compares the gathered rows bit for bit —
             # same kernels, same arithmetic, another GPU.  This is the check that catches a receiver whose broadcast arena was
@@ -750,7 +814,7 @@ def main():
     # what N GPUs deliver if the gather and the barriers cost nothing at THIS shard size (`multi_gpu.expected`), so a poor first 8-GPU curve
     # separates "small shards run slower per crop" (see batch_sweep: 4 crops per GPU = 0.63 of the 64-crop rate) from "the gather / broadcast hurts"
     local_rate = None
-    if use_dist and not cpu_dry and a.workload == "full":
+    if use_dist and not cpu_dry and a.workload == "full" and a.full:
         def local():
             n_loc = max(3, min(a.steps, 10))
             for _ in range(2):
@@ -858,7 +922,7 @@ def main():
                     if world == 1:
                         roof["lbs_hbm_b512"] = lbs_at_b512(dev, smpl)
         par, facade = None, None
-        if not a.no_extras and not cpu_dry and "out" in last:
+        if extras and not cpu_dry and "out" in last:
             par = parity_vs_golden(last["out"], B, cfg, a.workload)
             if world == 1:
                 # the drop-in's own rate: `model(batch)` through the facade (tokenhmr_amd/model.py) allocates its output tensors per
@@ -881,13 +945,13 @@ def main():
                                    "the timed region ran — by default the engine's creation default, i.e. what load_tokenhmr() without a mode "
                                    "argument delivers (tests/test_gpu_checkpoint_files.py asserts that on the reference's file formats)")}
         pipeline = None
-        if world == 1 and not a.no_extras and not cpu_dry and a.workload == "full":
+        if world == 1 and extras and not cpu_dry and a.workload == "full":
             try:
                 pipeline = {a.vit_gemm: pipeline_bench(eng, dev, B, max(5, min(a.steps, 20)), 2, elapsed / a.steps * 1e3)}
             except Exception as ex:      # an extra must never cost the headline line
                 pipeline = {"error": f"{type(ex).__name__}: {ex}"}
         sweep = None
-        if world == 1 and not a.no_extras and not cpu_dry and a.workload == "full" and B >= 32:
+        if world == 1 and extras and not cpu_dry and a.workload == "full" and B >= 32:
             # The reference's OWN batch sizes through the same engine in the timed mode (untimed extra): 1 crop (BASELINE configs[0], a
             # single detection), 8 (demo.py:70 DataLoader batch_size), 32 (README.md:316 eval batch) — and the timed batch again, by the
             # same method, so the ratios are same-process, same-box.  HIP events on the launch stream, pre-allocated outputs.
@@ -928,7 +992,7 @@ def main():
             except Exception as ex:      # an extra must never cost the headline line
                 sweep = {"error": f"{type(ex).__name__}: {ex}"}
         other, other_name = None, ("exact_f32_mode" if split_mode else "split3_mode")
-        if world == 1 and not a.no_extras and not cpu_dry and B >= 3:
+        if world == 1 and extras and not cpu_dry and B >= 3:
             # SECOND measurement, not `value`: the same K steps with the ViT GEMMs in the engine's OTHER mode (thmr_set_vit_gemm), so one
             # line from one process on one box carries both: the exact-fp32 MFMA path beside the split3 one.  Each with its own parity
             # block against the reference golden, its own class split and its dominant kernel's roofline.
@@ -983,13 +1047,13 @@ def main():
                     eng.set_vit_gemm(a.vit_gemm)
                 except Exception:
                     pass
-        if par is not None and world == 1 and not a.no_extras and not cpu_dry and a.workload == "full" and B == 64 and cfg.vit_depth == 32:
+        if par is not None and world == 1 and extras and not cpu_dry and a.workload == "full" and B == 64 and cfg.vit_depth == 32:
             try:
                 par["set"] = parity_set(cfg, dev, a.vit_gemm, par)
             except Exception as ex:
                 par["set"] = {"error": f"{type(ex).__name__}: {ex}"}
         cpu = None
-        if world == 1 and not a.no_cpu_baseline and not cpu_dry:
+        if world == 1 and a.full and not a.no_cpu_baseline and not cpu_dry:
             cpu = cpu_baseline(cfg, sd, tok, smpl, a.workload)
         line = {
             "metric": "crops_per_sec", "value": round(value, 2), "unit": "crops/s", "n_gpus": world, "steps": a.steps,

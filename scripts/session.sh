@@ -7,7 +7,7 @@
 # Steps (each prints a short summary; the full logs stay in the output directory):
 #   tests[=<pytest -k expression>]      the -m gpu suite (or the selected tests)
 #   smoke                               __graft_entry__.smoke()
-#   bench[=<bench.py arguments>]        one bench line -> bench<n>.json (+ a parsed summary)
+#   bench[=<bench.py arguments>]        one bench.py --full line -> bench<n>.json (+ a parsed summary)
 #   classprof=<B,B,...>                 per-class ms of one call at each batch size (default mode), scripts/small_batch_prof.py
 #   ab=<libA>:<batch>[:<extra args>]    scripts/ab_same_box.py <libA> vs the in-tree library at that batch size
 #   abexp=<batch>:<A-env>:<B-env>       two knob settings of the experiments build against each other (env lists comma-separated K=V)
@@ -38,7 +38,7 @@ for step in "$@"; do
     smoke)
       timeout 400 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke$n.log 2>&1; echo "smoke rc=$?"; grep smoke $O/smoke$n.log | tail -13 | cut -c1-140 ;;
     bench)
-      timeout 1700 python bench.py $arg > $O/bench$n.json 2> $O/bench$n.err; echo "bench rc=$?"; tail -2 $O/bench$n.err
+      timeout 1700 python bench.py --full $arg > $O/bench$n.json 2> $O/bench$n.err; echo "bench rc=$?"; tail -2 $O/bench$n.err
       python - $O/bench$n.json <<'PY'
 import json, sys
 try:

@@ -29,7 +29,7 @@ def _line(r):
 
 
 def test_gpus2_self_launches_two_gloo_ranks():
-    j = _line(_run(["--gpus", "2", "--backend", "gloo", "--fake-engine", "--steps", "3", "--warmup", "1", "--batch", "4"]))
+    j = _line(_run(["--gpus", "2", "--backend", "gloo", "--fake-engine", "--steps", "3", "--warmup", "1", "--batch", "4", "--full"]))
     assert j["n_gpus"] == 2 and j["config"]["ranks"] == 2 and j["config"]["backend"] == "gloo"
     assert j["config"]["global_batch"] == 8 and j["config"]["batch_per_gpu"] == 4 and j["config"]["parallelism"] == "dp2"
     assert j["config"]["allgather_outputs"] is True and j["gathered_records_ok"] is True
@@ -55,15 +55,72 @@ def test_gpus8_dry_run_global_batch_512_and_ragged_509():
     per-step async packed all-gather joined one step later, per-rank diagnostics, cross-rank check, one JSON line) runs here on
     gloo / CPU tensors, weak-scaled at 64 crops per rank (global 512, BASELINE configs[3]) and with ONE ragged global batch of
     509 crops dealt 64,64,64,64,64,63,63,63."""
-    j = _line(_run(["--gpus", "8", "--backend", "gloo", "--fake-engine", "--steps", "3", "--warmup", "1"], timeout=900))
+    j = _line(_run(["--gpus", "8", "--backend", "gloo", "--fake-engine", "--steps", "3", "--warmup", "1", "--full"], timeout=900))
     assert j["n_gpus"] == 8 and j["config"]["ranks"] == 8 and j["config"]["global_batch"] == 512 and j["config"]["batch_per_gpu"] == 64
     assert j["scaling"] == "weak" and j["config"]["parallelism"] == "dp8"
     assert abs(j["value"] - 512 * 3 / (j["ms_per_step"] * 3e-3)) / j["value"] < 1e-3
     _check_multi_gpu_block(j, 8, [64] * 8)
-    j = _line(_run(["--gpus", "8", "--backend", "gloo", "--fake-engine", "--steps", "2", "--warmup", "1", "--global-batch", "509"], timeout=900))
+    j = _line(_run(["--gpus", "8", "--backend", "gloo", "--fake-engine", "--steps", "2", "--warmup", "1", "--global-batch", "509", "--full"],
+                   timeout=900))
     assert j["config"]["global_batch"] == 509 and j["config"]["batch_per_gpu"] == [64, 64, 64, 64, 64, 63, 63, 63] and j["scaling"] == "strong"
     assert abs(j["value"] - 509 * 2 / (j["ms_per_step"] * 2e-3)) / j["value"] < 1e-3
     _check_multi_gpu_block(j, 8, [64, 64, 64, 64, 64, 63, 63, 63])
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline only (no cross-rank check, no per-step events, no extras); --dump-outputs writes
+    rank 0's outputs of the last timed step, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        j = _line(_run(["--gpus", "2", "--backend", "gloo", "--fake-engine", "--steps", "2", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(d)]))
+        assert j["steps"] == 2 and j["ms_per_step"] > 0 and abs(j["value"] - 8 * 2 / (j["ms_per_step"] * 2e-3)) / j["value"] < 1e-3
+        assert j["gathered_records_ok"] is True and j["multi_gpu"]["cross_rank_check"] is None and "step_ms" not in j
+        assert j["roofline"] is None and j["cpu_baseline"] is None and j["parity"] is None
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    assert "pred_vertices.npy" in dumps[0] and "token_idx.npy" in dumps[0]
+    assert dumps[0]["pred_vertices.npy"].shape == (4, 6890, 3) and dumps[0]["pred_vertices.npy"].dtype == np.float32
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
+def test_bench_reads_a_current_library_without_building(built_lib, monkeypatch, tmp_path):
+    """bench.py calls build() only when the library is missing or stale: after build() the check says current (so a run in a tree
+    that is read-only to its user writes nothing there); another source hash or no manifest says build() has work to do."""
+    import __graft_entry__ as G
+    import bench
+    assert bench.library_current(G)
+    with monkeypatch.context() as m:
+        m.setattr(G, "source_hash", lambda: "0" * 16)
+        assert not bench.library_current(G)
+    monkeypatch.setattr(G, "MANIFEST", str(tmp_path / "no_manifest.json"))
+    assert not bench.library_current(G)
+
+
+@pytest.mark.gpu
+def test_plain_run_in_a_read_only_tree(built_lib, cuda_dev, tmp_path):
+    """A plain run in a copy of the built tree that its user cannot write to (the library is current, so nothing is rebuilt)."""
+    import shutil
+    tree = tmp_path / "tree"
+    tree.mkdir()
+    for f in ("bench.py", "__graft_entry__.py"):
+        shutil.copy2(os.path.join(ROOT, f), tree / f)
+    shutil.copytree(os.path.join(ROOT, "include"), tree / "include")
+    shutil.copytree(os.path.join(ROOT, "tokenhmr_amd"), tree / "tokenhmr_amd", ignore=shutil.ignore_patterns("*.o", "__pycache__"))
+    dirs = [tree] + [p for p in tree.rglob("*") if p.is_dir()]
+    for d in dirs:
+        d.chmod(0o555)
+    try:
+        env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+        env["PYTHONDONTWRITEBYTECODE"] = "1"
+        r = subprocess.run([sys.executable, str(tree / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--vit-depth", "2",
+                            "--batch", "4"], capture_output=True, text=True, env=env, timeout=600, cwd=str(tree))
+        j = _line(r)
+        assert j["steps"] == 2 and j["ms_per_step"] > 0 and "src:" in j["build"]
+    finally:
+        for d in dirs:
+            d.chmod(0o755)
 
 
 def test_global_batch_smaller_than_world_is_refused():
@@ -92,7 +149,7 @@ def test_self_launch_on_rccl_world1(built_lib, cuda_dev):
     """`--gpus 1 --self-launch`: the N-rank code path (torch.distributed.run, nccl backend, broadcast, per-step all-gather)
     with one rank, at a reduced depth so it takes seconds."""
     j = _line(_run(["--gpus", "1", "--self-launch", "--vit-depth", "2", "--steps", "4", "--warmup", "1", "--batch", "8",
-                    "--no-cpu-baseline", "--no-extras"], {"HSA_ENABLE_IPC_MODE_LEGACY": "0"}))
+                    "--no-cpu-baseline", "--no-extras", "--full"], {"HSA_ENABLE_IPC_MODE_LEGACY": "0"}))
     assert j["n_gpus"] == 1 and j["config"]["ranks"] == 1 and j["config"]["backend"] == "nccl"
     assert j["config"]["allgather_outputs"] is True and j["gathered_records_ok"] is True
     assert j["roofline"]["frac"] > 0 and "src:" in j["build"]
@@ -150,7 +207,7 @@ def test_two_ranks_with_real_engines_on_one_gpu(built_lib, cuda_dev, extra):
     split = not extra                     # bench.py's default with real engines and >= 3 crops per GPU is the split3 mode
     n = 16 if split else 5
     j = _line(_run(["--gpus", "2", "--backend", "gloo", "--single-device", "--vit-depth", "2", "--batch", str(n), "--steps", "3", "--warmup", "1",
-                    "--no-cpu-baseline"] + extra, timeout=900))
+                    "--no-cpu-baseline", "--full"] + extra, timeout=900))
     assert j["n_gpus"] == 2 and j["config"]["ranks"] == 2 and "single-device" in j["dry_run"]
     m = j["multi_gpu"]
     assert m["checkpoint_readers"] == [0] and j["gathered_records_ok"] is True

@@ -1,39 +1,20 @@
-"""Drop-in conformance by static analysis (runs where /root/reference exists, i.e. in the build container; no GPU needed).
+"""Drop-in conformance by static analysis (no GPU needed).
 
-The reference's CLIs can be executed against the facade nowhere: the reference tree exists only here (no GPU), the GPU box has no
-reference tree, and the product has no CPU path.  What CAN be checked here is that everything those scripts DO with the model is
-served by the facade: every keyword they pass to load_tokenhmr, every attribute they touch on the returned model, every key they
-read from the output dict — collected from the reference's own sources with `ast`, compared with what tokenhmr_amd.model
+The reference's CLIs cannot be executed against the facade on a GPU box (the product has no CPU path).  What CAN be checked is that
+everything those scripts DO with the model is served by the facade: every keyword they pass to load_tokenhmr, every attribute they
+touch on the returned model, every key they read from the output dict — collected from the reference's own sources with `ast` by
+oracle/gen_golden_call_sites.py and frozen in tests/golden/reference_call_sites.json, compared here with what tokenhmr_amd.model
 declares (its signature, its class, the dict literal of TokenHMR._pack).  The loop bodies themselves run on the GPU box in
 tests/test_gpu_pipeline.py."""
 import ast
 import inspect
+import json
 import os
 
-import pytest
+from conftest import GOLDEN_DIR
 
-REF = "/root/reference/tokenhmr"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box): static call-site check runs in the build container")
-
-
-def _parse(rel):
-    with open(os.path.join(REF, rel)) as f:
-        return ast.parse(f.read())
-
-
-def _subscript_keys(tree, names):
-    """string keys k of `name[k]` loads for name in names"""
-    keys = set()
-    for n in ast.walk(tree):
-        if isinstance(n, ast.Subscript) and isinstance(n.value, ast.Name) and n.value.id in names:
-            s = n.slice
-            if isinstance(s, ast.Constant) and isinstance(s.value, str):
-                keys.add(s.value)
-    return keys
-
-
-def _attrs(tree, name):
-    return {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == name}
+with open(os.path.join(GOLDEN_DIR, "reference_call_sites.json")) as _f:
+    REF = json.load(_f)
 
 
 def _facade_output_keys():
@@ -54,19 +35,15 @@ def _facade_output_keys():
 def test_load_tokenhmr_accepts_every_keyword_the_reference_passes():
     from tokenhmr_amd.model import load_tokenhmr
     params = set(inspect.signature(load_tokenhmr).parameters)
-    ref_sig = None
-    for n in ast.walk(_parse("lib/models/__init__.py")):
-        if isinstance(n, ast.FunctionDef) and n.name == "load_tokenhmr":
-            ref_sig = [a.arg for a in n.args.args]
+    ref_sig = REF["load_tokenhmr_params"]
     assert ref_sig, "reference load_tokenhmr not found"
     assert set(ref_sig) <= params, (ref_sig, params)                       # same names (lib/models/__init__.py:3)
     assert list(inspect.signature(load_tokenhmr).parameters)[:len(ref_sig)] == ref_sig      # same positional order
     used = set()
-    for script in ("eval.py", "demo.py", "track.py"):
-        for n in ast.walk(_parse(script)):
-            if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "load_tokenhmr":
-                assert not n.args, f"{script}: positional call"          # the scripts call it by keyword
-                used |= {k.arg for k in n.keywords}
+    for c in REF["load_tokenhmr_calls"]:
+        assert c["positional_args"] == 0, f"{c['script']}: positional call"          # the scripts call it by keyword
+        used |= set(c["keywords"])
+    assert {c["script"] for c in REF["load_tokenhmr_calls"]} == {"eval.py", "demo.py", "track.py"}
     assert used and used <= params, (used, params)
 
 
@@ -75,38 +52,25 @@ def test_every_model_attribute_the_scripts_touch_exists_on_the_facade():
     init = ast.parse(inspect.getsource(TokenHMR))
     inst_attrs = {n.attr for n in ast.walk(init) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "self"}
     have = set(dir(TokenHMR)) | inst_attrs
-    touched = set()
-    for script in ("eval.py", "demo.py", "track.py"):
-        touched |= _attrs(_parse(script), "model")
+    touched = set(REF["model_attrs"])
     # track.py wraps the model in a PHALP predictor class; what it calls on it is forward(batch) through __call__
     assert touched, "no model.<attr> use found in the reference scripts"
     missing = {a for a in touched if a not in have}
     assert not missing, f"the reference scripts use model.{missing}, the facade has no such attribute"
     # model.smpl.faces (demo.py:52)
-    assert any(isinstance(n, ast.Attribute) and n.attr == "faces" and isinstance(n.value, ast.Attribute) and n.value.attr == "smpl"
-               for n in ast.walk(_parse("demo.py")))
+    assert REF["demo_reads_model_smpl_faces"]
     from tokenhmr_amd.model import _SmplHandle
     assert "faces" in {n.attr for n in ast.walk(ast.parse(inspect.getsource(_SmplHandle))) if isinstance(n, ast.Attribute)}
 
 
 def test_every_output_key_the_reference_reads_is_produced():
     keys, nested = _facade_output_keys()
-    read = set()
-    read |= _subscript_keys(_parse("demo.py"), {"out"})
-    read |= _subscript_keys(_parse("eval.py"), {"out"})
-    read |= _subscript_keys(_parse("track.py"), {"model_out"})
-    read |= _subscript_keys(_parse("lib/utils/pose_utils.py"), {"output"})          # Evaluator.__call__(output, batch)
+    read = set(REF["output_keys_read"])            # demo.py / eval.py `out[...]`, track.py `model_out[...]`, Evaluator.__call__ `output[...]`
     assert {"pred_vertices", "pred_keypoints_3d", "pred_cam", "pred_cam_t"} <= read, read
     missing = read - keys
     assert not missing, f"the reference reads output keys {missing} that TokenHMR._pack does not produce"
     # the output dict of the reference's forward_step (tokenhmr.py:156-188): every key it sets at inference is produced too
-    fs = next(n for n in ast.walk(_parse("lib/models/tokenhmr.py")) if isinstance(n, ast.FunctionDef) and n.name == "forward_step")
-    set_keys = set()
-    for n in ast.walk(fs):
-        if isinstance(n, ast.Assign):
-            for t in n.targets:
-                if isinstance(t, ast.Subscript) and isinstance(t.value, ast.Name) and t.value.id == "output" and isinstance(t.slice, ast.Constant):
-                    set_keys.add(t.slice.value)
+    set_keys = set(REF["forward_step_output_keys"])
     assert set_keys, "no output[...] assignment found in forward_step"
     assert set_keys <= keys, (set_keys - keys)
     assert nested.get("pred_smpl_params") == {"global_orient", "body_pose", "betas"}
@@ -117,29 +81,20 @@ def test_tokenizer_dropins_keep_the_reference_constructors_and_call_sites():
     defaults (vanilla_pose_vqvae.py:258-262, :304-307), and the one place the reference instantiates and calls DecodeTokens
     (heads/token_classifier.py: Proxy) passes nothing the drop-in does not take."""
     from tokenhmr_amd import tokenizer as T
-    tok_src = os.path.join(os.path.dirname(REF), "tokenization", "models", "vanilla_pose_vqvae.py")
-    with open(tok_src) as f:
-        tree = ast.parse(f.read())
     for cls_name in ("DecodeTokens", "EncodeTokens"):
-        cls = next(n for n in ast.walk(tree) if isinstance(n, ast.ClassDef) and n.name == cls_name)
-        init = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == "__init__")
-        ref_args = [a.arg for a in init.args.args][1:]
-        ref_defaults = [ast.literal_eval(d) for d in init.args.defaults]
+        ref = REF["tokenizer_classes"][cls_name]
+        ref_args, ref_defaults = ref["init_params"], ref["init_defaults"]
         mine = inspect.signature(getattr(T, cls_name).__init__)
         names = list(mine.parameters)[1:]
         assert names[:len(ref_args)] == ref_args, (cls_name, names, ref_args)
         assert [mine.parameters[a].default for a in ref_args] == ref_defaults, cls_name
-        fwd = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == "forward")
-        assert len(fwd.args.args) == 2 and len(inspect.signature(getattr(T, cls_name).forward).parameters) == 2      # (self, x)
+        assert ref["forward_params"] == 2 and len(inspect.signature(getattr(T, cls_name).forward).parameters) == 2      # (self, x)
     # the reference's own call site (token_classifier.py:85): eval('VanillaDecodeTokens')(tokenizer_checkpoint_path), handed to Proxy, which
     # moves it with .to(x.device) and calls it with the token probabilities (:12-20)
-    tc = _parse("lib/models/heads/token_classifier.py")
-    calls = [n for n in ast.walk(tc) if isinstance(n, ast.Call) and isinstance(n.func, ast.Call) and isinstance(n.func.func, ast.Name)
-             and n.func.func.id == "eval"]
+    calls = REF["token_classifier_eval_calls"]
     assert calls, "the reference no longer instantiates the tokenizer through eval(...)(ckpt_path) in token_classifier.py?"
     ok = set(inspect.signature(T.DecodeTokens.__init__).parameters)
     for c in calls:
-        assert len(c.args) == 1 and all(k.arg in ok for k in c.keywords), ast.dump(c)
-    proxy = next(n for n in ast.walk(tc) if isinstance(n, ast.ClassDef) and n.name == "Proxy")
-    used = {n.attr for n in ast.walk(proxy) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Attribute) and n.value.attr == "tokenizer"}
+        assert c["positional_args"] == 1 and all(k in ok for k in c["keywords"]), c
+    used = set(REF["proxy_tokenizer_attrs"])
     assert used <= {"to"} and all(hasattr(T.DecodeTokens, a) for a in used | {"__call__"}), used
