@@ -319,6 +319,63 @@ int  thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int3
                       const thmr_crop_desc* crops_host, int32_t n, int32_t patch, int32_t swap_rb, const float* mean_host,
                       const float* std_host, float* out_dev, void* stream);
 
+/* Mesh renderer: the reference's pyrender scenes (tokenhmr/lib/utils/renderer.py) rasterised on the device
+ * (csrc/render.hip).  The kernels know no presets: the host scene builder (tokenhmr_amd/render.py) fills the descriptor.
+ *   camera frame   x right, y down, z forward (the frame of perspective_projection); per mesh m
+ *                  translate_first = 0: p = R v + t_m   (Renderer.__call__: R = the side-view rotation)
+ *                  translate_first = 1: p = R (v + t_m) (vertices_to_trimesh / render_rgba*: R = the rot_axis / rot_angle rotation)
+ *   projection     u = fx X/Z + cx, v = fy Y/Z + cy; pixel (row i, col j) covers [j, j+1) x [i, i+1)
+ *   coverage       1 sample (pixel centre) or 4 (rotated grid (0.375,0.125) (0.875,0.375) (0.125,0.625) (0.625,0.875)); vertices
+ *                  snapped to 1/256 px, exact integer edge functions, top-left rule; back faces (clockwise in the image frame, i.e.
+ *                  GL's clockwise-in-window after the y flip) and degenerate faces culled; a face with a vertex at Z < znear or
+ *                  projecting beyond 2^21 px is rejected (no clipping)
+ *   visibility     per sample the smallest (fp32 depth, mesh, face); deterministic
+ *   shading        glTF metallic-roughness, smooth angle-weighted normals, once per (pixel, distinct winning face) at the centre
+ *   output         rgb = (sum shaded + (S - k) bg) / S, alpha = k / S, each rounded to 8 bits; (n_img, H, W, out_channels) fp32
+ *   mode           THMR_RENDER_PER_IMAGE: N images, image m holds mesh m; THMR_RENDER_ONE_IMAGE: one image holding all N meshes
+ * Lights are in the camera frame: a directional light's vec is the direction it travels, a point light's vec its position
+ * (radiance color * intensity / distance^2).  thmr_renderer_run arguments: verts_dev (N, V, 3) and cam_t_dev (N, 3) fp32 device;
+ * bg_dev NULL, or (n_img, 3, H, W) normalised images composited as Renderer.__call__ does (out = rgb a + (1 - a) (x std + mean),
+ * out_channels 3); out_dev (n_img, H, W, out_channels).  The handle grows device scratch at a new, larger size (and synchronises the
+ * stream then); otherwise a call allocates nothing and does not synchronise. */
+#define THMR_RENDER_MAX_LIGHTS 16
+#define THMR_RENDER_PER_IMAGE 0
+#define THMR_RENDER_ONE_IMAGE 1
+#define THMR_LIGHT_DIRECTIONAL 0
+#define THMR_LIGHT_POINT 1
+typedef struct thmr_render_light {
+    int32_t type;               /* THMR_LIGHT_DIRECTIONAL / THMR_LIGHT_POINT */
+    float vec[3];               /* direction of travel / position, camera frame */
+    float color[3];
+    float intensity;
+} thmr_render_light;
+typedef struct thmr_render_desc {
+    int32_t width, height;      /* 1 ... 8192 */
+    float fx, fy, cx, cy;
+    float znear;                /* > 0 */
+    int32_t samples;            /* 1 or 4 */
+    int32_t mode;               /* THMR_RENDER_PER_IMAGE / THMR_RENDER_ONE_IMAGE */
+    int32_t translate_first;
+    float rot[9];               /* R, row-major */
+    float base_color[3];        /* every mesh's base colour ... */
+    const float* mesh_colors;   /* ... or per mesh: host (N, 3), NULL = base_color */
+    float bg_color[3];          /* background, alpha 0 */
+    float metallic, roughness;
+    float ambient[3];           /* ambient light; the shaded colour gains ambient * base */
+    int32_t n_lights;           /* 0 ... THMR_RENDER_MAX_LIGHTS */
+    thmr_render_light lights[THMR_RENDER_MAX_LIGHTS];
+    int32_t out_channels;       /* 3 or 4 */
+    float img_mean[3], img_std[3];   /* de-normalisation of bg_dev */
+    uint32_t* ids_dev;          /* optional (n_img, H, W, samples) device: winning mesh * F + face per sample, 0xFFFFFFFF = none */
+} thmr_render_desc;
+typedef struct thmr_renderer thmr_renderer;
+/* faces_host (F, 3) int32, every index in [0, V); builds the vertex -> face lists once (needs the device) */
+int  thmr_renderer_create(int32_t device, const int32_t* faces_host, int32_t F, int32_t V, thmr_renderer** out);
+void thmr_renderer_destroy(thmr_renderer* r);
+const char* thmr_renderer_last_error(const thmr_renderer* r);
+int  thmr_renderer_run(thmr_renderer* r, const thmr_render_desc* desc, const float* verts_dev, const float* cam_t_dev, int32_t N,
+                       const float* bg_dev, float* out_dev, void* stream);
+
 /* ---- data-parallel collectives for hosts without torch.distributed ----
  * The reference has no collective on this path (inference is single-device, tokenhmr/eval.py:52-54).  Crops shard with NO data-path
  * collective; two collectives surround the path: ONE broadcast of the packed weight arena at start-up (only rank `root` read the

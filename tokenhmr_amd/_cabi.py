@@ -52,6 +52,25 @@ class CropDesc(C.Structure):
     _fields_ = [("M", C.c_double * 6), ("sigma", C.c_double), ("truncate", C.c_double)]
 
 
+RENDER_MAX_LIGHTS = 16
+# thmr_render_desc.mode / thmr_render_light.type (header: THMR_RENDER_* / THMR_LIGHT_*)
+RENDER_PER_IMAGE, RENDER_ONE_IMAGE = 0, 1
+LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1
+
+
+class RenderLight(C.Structure):
+    _fields_ = [("type", C.c_int32), ("vec", C.c_float * 3), ("color", C.c_float * 3), ("intensity", C.c_float)]
+
+
+class RenderDesc(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("znear", C.c_float), ("samples", C.c_int32), ("mode", C.c_int32), ("translate_first", C.c_int32),
+                ("rot", C.c_float * 9), ("base_color", C.c_float * 3), ("mesh_colors", C.POINTER(C.c_float)), ("bg_color", C.c_float * 3),
+                ("metallic", C.c_float), ("roughness", C.c_float), ("ambient", C.c_float * 3), ("n_lights", C.c_int32),
+                ("lights", RenderLight * RENDER_MAX_LIGHTS), ("out_channels", C.c_int32), ("img_mean", C.c_float * 3),
+                ("img_std", C.c_float * 3), ("ids_dev", C.c_void_p)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
@@ -150,6 +169,12 @@ def load(exp=None):
     lib.thmr_cropper_last_error.argtypes = [vp]
     lib.thmr_cropper_last_error.restype = C.c_char_p
     lib.thmr_cropper_run.argtypes = [vp, vp, i32, i32, i64, C.POINTER(CropDesc), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
+    lib.thmr_renderer_create.argtypes = [i32, vp, i32, i32, C.POINTER(vp)]
+    lib.thmr_renderer_destroy.argtypes = [vp]
+    lib.thmr_renderer_destroy.restype = None
+    lib.thmr_renderer_last_error.argtypes = [vp]
+    lib.thmr_renderer_last_error.restype = C.c_char_p
+    lib.thmr_renderer_run.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, i32, vp, vp, vp]
     lib.thmr_pack_records.argtypes = [C.POINTER(Outputs), i32, vp, vp]
     lib.thmr_bcast_weights.argtypes = [vp, vp, i32, vp]
     lib.thmr_allgather_records.argtypes = [vp, vp, i32, vp, vp]
@@ -163,7 +188,8 @@ def load(exp=None):
             continue
         fn = getattr(lib, name)
         if name not in ("thmr_build_info", "thmr_last_error", "thmr_destroy", "thmr_smpl_destroy", "thmr_cropper_destroy",
-                        "thmr_cropper_last_error", "thmr_collective_last_error"):
+                        "thmr_cropper_last_error", "thmr_collective_last_error", "thmr_renderer_destroy",
+                        "thmr_renderer_last_error"):
             fn.restype = C.c_int
     if lib.thmr_abi_version() != ABI_VERSION and not older:
         raise RuntimeError("libtokenhmr_hip.so ABI version mismatch")

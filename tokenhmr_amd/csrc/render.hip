@@ -1,0 +1,565 @@
+// Mesh renderer: the GPU restatement of the reference's pyrender scenes (tokenhmr/lib/utils/renderer.py) —
+// crop overlays and side views (B images, one mesh each) and the all-people frame (one image, N meshes) in one code path.
+//
+// Pipeline, all asynchronous on the caller's stream:
+//   1. render_vertex_kernel    camera-frame transform p = R v + t (or R (v + t)), projection u = fx X/Z + cx, snap to 1/256 px
+//   2. render_normal_kernel    angle-weighted smooth vertex normals, gathered through a vertex -> face CSR (no float atomics)
+//   3. render_setup_kernel     cull (back face, degenerate, znear, off screen), per-face record (snapped corners, 1/Z plane),
+//                              count the 16x16 tiles a small face's box touches; faces spanning > 4 tiles go to a per-image list
+//   4. render_scan_kernel      exclusive scan of the tile counts (one workgroup)
+//   5. render_fill_kernel      small faces into their tiles' bins
+//   6. render_raster_kernel    one workgroup per (image, tile), one lane per pixel: exact integer coverage at 1 or 4 samples,
+//                              nearest key (fp32 depth, mesh, face) per sample in registers, face records streamed through LDS;
+//                              then shade once per (pixel, distinct winning face), resolve, 8-bit round, composite, store.
+//
+// Determinism: coverage is integer arithmetic; the per-sample winner is the minimum of a total order, so the bin order the
+// atomics produce cannot change any pixel.  The only atomics are the bin counters and cursors.
+//
+// Compiled contract-off: the vertex transform and projection are fp32 operations in a fixed order, which the NumPy restatement
+// (tests/render_numpy.py) repeats bit for bit — that is what makes its coverage (and alpha) exact.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <climits>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/tokenhmr_hip.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int TILE = 16;
+constexpr int SMALL_TILES = 4;                 // faces whose pixel box spans more tiles than this go to the per-image list
+constexpr float GUARD_PX = 2097152.f;          // 2^21 px: snapped coordinates stay below 2^29, edge products below 2^61
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+constexpr float PI_F = 3.14159265358979f;
+
+struct FaceRec {                               // 48 B; corners oriented so that the image-frame doubled area is positive
+    int32_t x0, y0, x1, y1, x2, y2;            // snapped corners, 1/256 px
+    float za, zb, zc;                          // 1/Z = za + zb (x - x0) + zc (y - y0), x / y in 1/256 px
+    uint32_t id;                               // mesh * F + face, NONE = rejected
+    int32_t bx, by;                            // pixel box: x0 | x1 << 16, y0 | y1 << 16
+};
+
+struct Light {
+    int32_t type;
+    float v[3], c[3];
+};
+
+struct Params {
+    int32_t W, H, S, mode, tr_first, N, V, F, n_img, tiles_x, tiles_y, ch, has_colors, has_img;
+    float fx, fy, cx, cy, znear;
+    float R[9];
+    float base[3], bg[3], amb[3], mean[3], stdv[3];
+    float metallic, roughness;
+    int32_t n_lights;
+    Light L[THMR_RENDER_MAX_LIGHTS];
+};
+
+struct Scratch {
+    float* pos = nullptr;          // (N, V, 3) camera frame
+    int2* fix = nullptr;           // (N, V) snapped u, v; x = INT_MIN: vertex unusable
+    float* nrm = nullptr;          // (N, V, 3)
+    FaceRec* rec = nullptr;        // (N, F)
+    uint32_t* cnt = nullptr;       // (T) tile counts, then (T + 1) offsets, (T) cursors, (n_img) large counts
+    uint32_t* off = nullptr;
+    uint32_t* cur = nullptr;
+    uint32_t* lcnt = nullptr;
+    uint32_t* bins = nullptr;      // (N F SMALL_TILES)
+    uint32_t* large = nullptr;     // (N F)
+    float* colors = nullptr;       // (N, 3)
+};
+
+std::string g_render_err;
+
+int rfail(int code, const std::string& m) { g_render_err = m; return code; }
+
+__device__ __forceinline__ int64_t edge(int32_t ax, int32_t ay, int32_t bx, int32_t by, int32_t px, int32_t py) {
+    return (int64_t)(bx - ax) * (int64_t)(py - ay) - (int64_t)(by - ay) * (int64_t)(px - ax);
+}
+
+// top-left rule in the image frame (x right, y down) for a positively oriented triangle: an edge a -> b owns the samples that
+// lie exactly on it when it is a top edge (dy == 0, dx > 0) or a left edge (dy < 0)
+__device__ __forceinline__ bool inside(int64_t e, int32_t dx, int32_t dy) {
+    return e > 0 || (e == 0 && (dy < 0 || (dy == 0 && dx > 0)));
+}
+
+__global__ void render_vertex_kernel(Params p, const float* __restrict__ verts, const float* __restrict__ cam_t, float* __restrict__ pos,
+                                     int2* __restrict__ fix) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)p.N * p.V) return;
+    const int m = (int)(i / p.V);
+    float x = verts[i * 3], y = verts[i * 3 + 1], z = verts[i * 3 + 2];
+    const float tx = cam_t[m * 3], ty = cam_t[m * 3 + 1], tz = cam_t[m * 3 + 2];
+    if (p.tr_first) { x = x + tx; y = y + ty; z = z + tz; }
+    float X = p.R[0] * x + p.R[1] * y + p.R[2] * z;
+    float Y = p.R[3] * x + p.R[4] * y + p.R[5] * z;
+    float Z = p.R[6] * x + p.R[7] * y + p.R[8] * z;
+    if (!p.tr_first) { X = X + tx; Y = Y + ty; Z = Z + tz; }
+    pos[i * 3] = X; pos[i * 3 + 1] = Y; pos[i * 3 + 2] = Z;
+    const float u = X / Z * p.fx + p.cx, v = Y / Z * p.fy + p.cy;
+    int2 f = make_int2(INT_MIN, INT_MIN);
+    if (Z >= p.znear && fabsf(u) <= GUARD_PX && fabsf(v) <= GUARD_PX)       // false for NaN as well
+        f = make_int2((int)rintf(u * 256.f), (int)rintf(v * 256.f));
+    fix[i] = f;
+}
+
+__global__ void render_normal_kernel(Params p, const int32_t* __restrict__ faces, const int32_t* __restrict__ csr_off,
+                                     const int32_t* __restrict__ csr, const float* __restrict__ pos, float* __restrict__ nrm) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)p.N * p.V) return;
+    const int m = (int)(i / p.V), v = (int)(i - (int64_t)m * p.V);
+    const float* P = pos + (int64_t)m * p.V * 3;
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    for (int k = csr_off[v]; k < csr_off[v + 1]; ++k) {
+        const int f = csr[k] >> 2, c = csr[k] & 3;
+        const int32_t* fv = faces + (int64_t)f * 3;
+        const float* a = P + (int64_t)fv[0] * 3;
+        const float* b = P + (int64_t)fv[1] * 3;
+        const float* d = P + (int64_t)fv[2] * 3;
+        const float e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2];
+        const float e2x = d[0] - a[0], e2y = d[1] - a[1], e2z = d[2] - a[2];
+        float fnx = e1y * e2z - e1z * e2y, fny = e1z * e2x - e1x * e2z, fnz = e1x * e2y - e1y * e2x;
+        const float fl = sqrtf(fnx * fnx + fny * fny + fnz * fnz);
+        if (!(fl > 0.f) || !isfinite(fl)) continue;                  // degenerate face: no normal, no weight
+        fnx = fnx / fl; fny = fny / fl; fnz = fnz / fl;
+        const float* o = P + (int64_t)fv[c] * 3;                      // interior angle at this corner
+        const float* q = P + (int64_t)fv[(c + 1) % 3] * 3;
+        const float* r = P + (int64_t)fv[(c + 2) % 3] * 3;
+        const float ax = q[0] - o[0], ay = q[1] - o[1], az = q[2] - o[2];
+        const float bx = r[0] - o[0], by = r[1] - o[1], bz = r[2] - o[2];
+        const float la = sqrtf(ax * ax + ay * ay + az * az), lb = sqrtf(bx * bx + by * by + bz * bz);
+        if (!(la > 0.f) || !(lb > 0.f)) continue;
+        const float cs = fminf(fmaxf((ax * bx + ay * by + az * bz) / (la * lb), -1.f), 1.f);
+        const float w = acosf(cs);
+        nx = nx + w * fnx; ny = ny + w * fny; nz = nz + w * fnz;
+    }
+    const float l = sqrtf(nx * nx + ny * ny + nz * nz);
+    if (l > 0.f) { nx = nx / l; ny = ny / l; nz = nz / l; }
+    nrm[i * 3] = nx; nrm[i * 3 + 1] = ny; nrm[i * 3 + 2] = nz;
+}
+
+__device__ __forceinline__ void face_tiles(const FaceRec& r, int& tx0, int& tx1, int& ty0, int& ty1) {
+    tx0 = (r.bx & 0xFFFF) / TILE; tx1 = (r.bx >> 16) / TILE;
+    ty0 = (r.by & 0xFFFF) / TILE; ty1 = (r.by >> 16) / TILE;
+}
+
+__global__ void render_setup_kernel(Params p, const int32_t* __restrict__ faces, const float* __restrict__ pos, const int2* __restrict__ fix,
+                                    FaceRec* __restrict__ rec, uint32_t* __restrict__ cnt, uint32_t* __restrict__ lcnt,
+                                    uint32_t* __restrict__ large) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)p.N * p.F) return;
+    const int m = (int)(i / p.F), f = (int)(i - (int64_t)m * p.F);
+    FaceRec r;
+    r.id = NONE; r.bx = r.by = 0;
+    r.x0 = r.y0 = r.x1 = r.y1 = r.x2 = r.y2 = 0; r.za = r.zb = r.zc = 0.f;
+    const int32_t* fv = faces + (int64_t)f * 3;
+    const int64_t base = (int64_t)m * p.V;
+    int2 a = fix[base + fv[0]], b = fix[base + fv[1]], c = fix[base + fv[2]];
+    double Za = pos[(base + fv[0]) * 3 + 2], Zb = pos[(base + fv[1]) * 3 + 2], Zc = pos[(base + fv[2]) * 3 + 2];
+    const int64_t area = edge(a.x, a.y, b.x, b.y, c.x, c.y);
+    // front faces are counter-clockwise in GL window coordinates (y up), i.e. negative doubled area in the image frame
+    if (a.x != INT_MIN && b.x != INT_MIN && c.x != INT_MIN && area < 0) {
+        { int2 t = b; b = c; c = t; double tz = Zb; Zb = Zc; Zc = tz; }   // orient positively
+        const int px0 = min(a.x, min(b.x, c.x)) >> 8, px1 = max(a.x, max(b.x, c.x)) >> 8;
+        const int py0 = min(a.y, min(b.y, c.y)) >> 8, py1 = max(a.y, max(b.y, c.y)) >> 8;
+        if (px1 >= 0 && py1 >= 0 && px0 < p.W && py0 < p.H) {
+            r.x0 = a.x; r.y0 = a.y; r.x1 = b.x; r.y1 = b.y; r.x2 = c.x; r.y2 = c.y;
+            r.bx = max(px0, 0) | (min(px1, p.W - 1) << 16);
+            r.by = max(py0, 0) | (min(py1, p.H - 1) << 16);
+            // 1/Z plane over the snapped corners, in double, relative to corner 0
+            const double i0 = 1.0 / Za, i1 = 1.0 / Zb, i2 = 1.0 / Zc;
+            const double d1x = (double)(b.x - a.x), d1y = (double)(b.y - a.y), d2x = (double)(c.x - a.x), d2y = (double)(c.y - a.y);
+            const double det = d1x * d2y - d2x * d1y;
+            r.za = (float)i0;
+            r.zb = (float)(((i1 - i0) * d2y - (i2 - i0) * d1y) / det);
+            r.zc = (float)(((i2 - i0) * d1x - (i1 - i0) * d2x) / det);
+            r.id = (uint32_t)i;
+            const int img = p.mode ? 0 : m;
+            int tx0, tx1, ty0, ty1;
+            face_tiles(r, tx0, tx1, ty0, ty1);
+            if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) <= SMALL_TILES) {
+                for (int ty = ty0; ty <= ty1; ++ty)
+                    for (int tx = tx0; tx <= tx1; ++tx)
+                        atomicAdd(&cnt[((int64_t)img * p.tiles_y + ty) * p.tiles_x + tx], 1u);
+            } else {
+                const int64_t cap = p.mode ? (int64_t)p.N * p.F : p.F;
+                const uint32_t slot = atomicAdd(&lcnt[img], 1u);
+                large[img * cap + slot] = (uint32_t)i;
+            }
+        }
+    }
+    rec[i] = r;
+}
+
+__global__ void __launch_bounds__(1024) render_scan_kernel(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
+                                                           uint32_t* __restrict__ cur, int64_t T) {
+    __shared__ uint32_t part[1024];
+    const int t = threadIdx.x;
+    const int64_t chunk = (T + 1023) / 1024, lo = min<int64_t>(T, t * chunk), hi = min<int64_t>(T, lo + chunk);
+    uint32_t s = 0;
+    for (int64_t k = lo; k < hi; ++k) s += cnt[k];
+    part[t] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {                             // Hillis-Steele inclusive scan of the 1024 chunk sums
+        const uint32_t v = t >= d ? part[t - d] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - s;
+    for (int64_t k = lo; k < hi; ++k) { off[k] = run; cur[k] = run; run += cnt[k]; }
+    if (t == 1023) off[T] = part[1023];
+}
+
+__global__ void render_fill_kernel(Params p, const FaceRec* __restrict__ rec, uint32_t* __restrict__ cur, uint32_t* __restrict__ bins) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)p.N * p.F) return;
+    const FaceRec r = rec[i];
+    if (r.id == NONE) return;
+    int tx0, tx1, ty0, ty1;
+    face_tiles(r, tx0, tx1, ty0, ty1);
+    if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) > SMALL_TILES) return;
+    const int img = p.mode ? 0 : (int)(i / p.F);
+    for (int ty = ty0; ty <= ty1; ++ty)
+        for (int tx = tx0; tx <= tx1; ++tx) {
+            const uint32_t slot = atomicAdd(&cur[((int64_t)img * p.tiles_y + ty) * p.tiles_x + tx], 1u);
+            bins[slot] = (uint32_t)i;
+        }
+}
+
+__device__ __forceinline__ float3 shade(const Params& p, uint32_t id, int px, int py, const int32_t* __restrict__ faces,
+                                        const float* __restrict__ pos, const int2* __restrict__ fix, const float* __restrict__ nrm,
+                                        const float* __restrict__ colors) {
+    const int m = (int)(id / (uint32_t)p.F), f = (int)(id - (uint32_t)m * (uint32_t)p.F);
+    const int32_t* fv = faces + (int64_t)f * 3;
+    const int64_t base = (int64_t)m * p.V;
+    const int2 a = fix[base + fv[0]], b = fix[base + fv[1]], c = fix[base + fv[2]];
+    // screen-space barycentrics at the pixel centre (may lie outside the face: no centroid sampling, as in GL), then
+    // perspective-correct weights
+    const int32_t sx = px * 256 + 128, sy = py * 256 + 128;
+    const double area = (double)edge(a.x, a.y, b.x, b.y, c.x, c.y);
+    const double l0 = (double)edge(b.x, b.y, c.x, c.y, sx, sy) / area, l1 = (double)edge(c.x, c.y, a.x, a.y, sx, sy) / area;
+    const double l2 = 1.0 - l0 - l1;
+    const float* P0 = pos + (base + fv[0]) * 3;
+    const float* P1 = pos + (base + fv[1]) * 3;
+    const float* P2 = pos + (base + fv[2]) * 3;
+    double w0 = l0 / P0[2], w1 = l1 / P1[2], w2 = l2 / P2[2];
+    const double ws = w0 + w1 + w2;
+    w0 /= ws; w1 /= ws; w2 /= ws;
+    const float* N0 = nrm + (base + fv[0]) * 3;
+    const float* N1 = nrm + (base + fv[1]) * 3;
+    const float* N2 = nrm + (base + fv[2]) * 3;
+    float P[3], N[3];
+    for (int k = 0; k < 3; ++k) {
+        P[k] = (float)(w0 * P0[k] + w1 * P1[k] + w2 * P2[k]);
+        N[k] = (float)(w0 * N0[k] + w1 * N1[k] + w2 * N2[k]);
+    }
+    float nl = sqrtf(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]);
+    nl = nl > 0.f ? nl : 1.f;
+    N[0] /= nl; N[1] /= nl; N[2] /= nl;
+    float V[3] = {-P[0], -P[1], -P[2]};
+    float vl = sqrtf(V[0] * V[0] + V[1] * V[1] + V[2] * V[2]);
+    vl = vl > 0.f ? vl : 1.f;
+    V[0] /= vl; V[1] /= vl; V[2] /= vl;
+    float base_c[3];
+    for (int k = 0; k < 3; ++k) base_c[k] = p.has_colors ? colors[m * 3 + k] : p.base[k];
+    // glTF metallic-roughness (pyrender's mesh shader, restated — DESIGN.md §3.6)
+    const float met = p.metallic, alpha = p.roughness * p.roughness, a2 = alpha * alpha;
+    float cdiff[3], f0[3];
+    for (int k = 0; k < 3; ++k) {
+        cdiff[k] = base_c[k] * (1.f - 0.04f) * (1.f - met);
+        f0[k] = 0.04f * (1.f - met) + base_c[k] * met;
+    }
+    const float f90 = fminf(fmaxf(fmaxf(f0[0], fmaxf(f0[1], f0[2])) * 25.f, 0.f), 1.f);
+    const float ndv = fminf(fmaxf(fabsf(N[0] * V[0] + N[1] * V[1] + N[2] * V[2]), 0.001f), 1.f);
+    float col[3] = {p.amb[0] * base_c[0], p.amb[1] * base_c[1], p.amb[2] * base_c[2]};
+    for (int li = 0; li < p.n_lights; ++li) {
+        const Light& L = p.L[li];
+        float l[3], att = 1.f;
+        if (L.type == 0) {
+            l[0] = -L.v[0]; l[1] = -L.v[1]; l[2] = -L.v[2];
+        } else {
+            l[0] = L.v[0] - P[0]; l[1] = L.v[1] - P[1]; l[2] = L.v[2] - P[2];
+            const float d2 = l[0] * l[0] + l[1] * l[1] + l[2] * l[2];
+            att = 1.f / d2;
+        }
+        const float ll = sqrtf(l[0] * l[0] + l[1] * l[1] + l[2] * l[2]);
+        if (!(ll > 0.f)) continue;
+        l[0] /= ll; l[1] /= ll; l[2] /= ll;
+        float h[3] = {l[0] + V[0], l[1] + V[1], l[2] + V[2]};
+        float hl = sqrtf(h[0] * h[0] + h[1] * h[1] + h[2] * h[2]);
+        hl = hl > 0.f ? hl : 1.f;
+        h[0] /= hl; h[1] /= hl; h[2] /= hl;
+        const float ndl = fminf(fmaxf(N[0] * l[0] + N[1] * l[1] + N[2] * l[2], 0.001f), 1.f);
+        const float ndh = fminf(fmaxf(N[0] * h[0] + N[1] * h[1] + N[2] * h[2], 0.f), 1.f);
+        const float vdh = fminf(fmaxf(V[0] * h[0] + V[1] * h[1] + V[2] * h[2], 0.f), 1.f);
+        const float fs = powf(1.f - vdh, 5.f);
+        const float G = (2.f * ndl / (ndl + sqrtf(a2 + (1.f - a2) * ndl * ndl))) * (2.f * ndv / (ndv + sqrtf(a2 + (1.f - a2) * ndv * ndv)));
+        const float dd = ndh * ndh * (a2 - 1.f) + 1.f;
+        const float D = a2 / (PI_F * dd * dd);
+        for (int k = 0; k < 3; ++k) {
+            const float F = f0[k] + (f90 - f0[k]) * fs;
+            const float diff = (1.f - F) * cdiff[k] / PI_F;
+            const float spec = F * G * D / (4.f * ndl * ndv);
+            col[k] += att * L.c[k] * ndl * (diff + spec);
+        }
+    }
+    float3 o;
+    o.x = fminf(fmaxf(powf(fmaxf(col[0], 0.f), 1.f / 2.2f), 0.f), 1.f);
+    o.y = fminf(fmaxf(powf(fmaxf(col[1], 0.f), 1.f / 2.2f), 0.f), 1.f);
+    o.z = fminf(fmaxf(powf(fmaxf(col[2], 0.f), 1.f / 2.2f), 0.f), 1.f);
+    return o;
+}
+
+__device__ __forceinline__ float to8(float v) { return rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f) / 255.0f; }
+
+template <int S>
+__global__ void __launch_bounds__(256) render_raster_kernel(Params p, const int32_t* __restrict__ faces, const float* __restrict__ pos,
+                                                            const int2* __restrict__ fix, const float* __restrict__ nrm,
+                                                            const float* __restrict__ colors, const FaceRec* __restrict__ rec,
+                                                            const uint32_t* __restrict__ off, const uint32_t* __restrict__ bins,
+                                                            const uint32_t* __restrict__ lcnt, const uint32_t* __restrict__ large,
+                                                            const float* __restrict__ img_in, float* __restrict__ out,
+                                                            uint32_t* __restrict__ ids_out) {
+    __shared__ FaceRec lds[256];
+    const int lane = threadIdx.x, img = blockIdx.y;
+    const int tile = blockIdx.x, tx = tile % p.tiles_x, ty = tile / p.tiles_x;
+    const int px = tx * TILE + (lane & 15), py = ty * TILE + (lane >> 4);
+    // the standard 4x rotated-grid positions in 1/256 px; one sample = the pixel centre
+    const int ox[4] = {96, 224, 32, 160}, oy[4] = {32, 96, 160, 224};
+    int32_t sxs[S], sys[S];
+    uint32_t bz[S], bid[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        sxs[s] = px * 256 + (S == 1 ? 128 : ox[s]);
+        sys[s] = py * 256 + (S == 1 ? 128 : oy[s]);
+        bz[s] = NONE; bid[s] = NONE;
+    }
+    const int64_t t = ((int64_t)img * p.tiles_y + ty) * p.tiles_x + tx;
+    const int64_t lcap = p.mode ? (int64_t)p.N * p.F : p.F;
+    for (int list = 0; list < 2; ++list) {
+        const uint32_t* ids = list == 0 ? bins + off[t] : large + img * lcap;
+        const uint32_t n = list == 0 ? off[t + 1] - off[t] : lcnt[img];
+        for (uint32_t b0 = 0; b0 < n; b0 += 256) {
+            if (b0 + lane < n) lds[lane] = rec[ids[b0 + lane]];
+            __syncthreads();
+            const uint32_t cnt = min(256u, n - b0);
+            for (uint32_t k = 0; k < cnt; ++k) {
+                const FaceRec& r = lds[k];
+                if (px < (r.bx & 0xFFFF) || px > (r.bx >> 16) || py < (r.by & 0xFFFF) || py > (r.by >> 16)) continue;
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    const int32_t sx = sxs[s], sy = sys[s];
+                    if (!inside(edge(r.x1, r.y1, r.x2, r.y2, sx, sy), r.x2 - r.x1, r.y2 - r.y1)) continue;
+                    if (!inside(edge(r.x2, r.y2, r.x0, r.y0, sx, sy), r.x0 - r.x2, r.y0 - r.y2)) continue;
+                    if (!inside(edge(r.x0, r.y0, r.x1, r.y1, sx, sy), r.x1 - r.x0, r.y1 - r.y0)) continue;
+                    const float iz = r.za + r.zb * (float)(sx - r.x0) + r.zc * (float)(sy - r.y0);
+                    const uint32_t z = iz > 0.f ? __float_as_uint(1.f / iz) : 0x7F800000u;
+                    if (z < bz[s] || (z == bz[s] && r.id < bid[s])) { bz[s] = z; bid[s] = r.id; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (px >= p.W || py >= p.H) return;
+    // resolve: shade once per distinct winning face (MSAA), average with the background over the uncovered samples
+    float sum[3] = {0.f, 0.f, 0.f};
+    int k = 0;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        if (bid[s] == NONE) continue;
+        ++k;
+        bool seen = false;
+#pragma unroll
+        for (int q = 0; q < s; ++q) seen = seen || bid[q] == bid[s];
+        if (seen) continue;
+        int mult = 0;
+#pragma unroll
+        for (int q = s; q < S; ++q) mult += bid[q] == bid[s];
+        const float3 c = shade(p, bid[s], px, py, faces, pos, fix, nrm, colors);
+        sum[0] += (float)mult * c.x; sum[1] += (float)mult * c.y; sum[2] += (float)mult * c.z;
+    }
+    const float unc = (float)(S - k), inv = 1.f / (float)S;
+    float rgb[3];
+    for (int c = 0; c < 3; ++c) rgb[c] = to8((sum[c] + unc * p.bg[c]) * inv);
+    const float a = to8((float)k * inv);
+    const int64_t pix = ((int64_t)img * p.H + py) * p.W + px;
+    float* o = out + pix * p.ch;
+    if (p.has_img) {                       // Renderer.__call__: color * valid_mask + (1 - valid_mask) * image, in fp32
+        const int64_t plane = (int64_t)p.H * p.W;
+        const float* src = img_in + (int64_t)img * 3 * plane + (int64_t)py * p.W + px;
+        for (int c = 0; c < 3; ++c) {
+            const float im = src[c * plane] * p.stdv[c] + p.mean[c];
+            o[c] = rgb[c] * a + (1.f - a) * im;
+        }
+    } else {
+        for (int c = 0; c < 3; ++c) o[c] = rgb[c];
+        if (p.ch == 4) o[3] = a;
+    }
+    if (ids_out)
+#pragma unroll
+        for (int s = 0; s < S; ++s) ids_out[pix * S + s] = bid[s];
+}
+
+template <typename T>
+hipError_t grow(T*& ptr, size_t& cap, size_t n) {
+    if (n <= cap) return hipSuccess;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr; cap = 0;
+    hipError_t e = hipMalloc(&ptr, sizeof(T) * n);
+    if (e == hipSuccess) cap = n;
+    return e;
+}
+
+}  // namespace
+
+struct thmr_renderer {
+    int device = 0;
+    int32_t F = 0, V = 0;
+    int32_t* faces = nullptr;      // (F, 3) device
+    int32_t* csr_off = nullptr;    // (V + 1)
+    int32_t* csr = nullptr;        // (3F) face << 2 | corner, by vertex, face-ascending
+    Scratch s;
+    size_t cap_pos = 0, cap_fix = 0, cap_nrm = 0, cap_rec = 0, cap_cnt = 0, cap_off = 0, cap_cur = 0, cap_lcnt = 0, cap_bins = 0,
+           cap_large = 0, cap_colors = 0;
+    std::string err;
+};
+
+extern "C" {
+
+const char* thmr_renderer_last_error(const thmr_renderer* r) { return r ? r->err.c_str() : g_render_err.c_str(); }
+
+int thmr_renderer_create(int32_t device, const int32_t* faces_host, int32_t F, int32_t V, thmr_renderer** out) {
+    if (!out) return rfail(THMR_ERR_INVALID, "null out");
+    *out = nullptr;
+    if (!faces_host) return rfail(THMR_ERR_INVALID, "null faces");
+    if (F <= 0 || V <= 0 || V > (1 << 28) || F > (1 << 28)) return rfail(THMR_ERR_INVALID, "bad face / vertex count");
+    std::vector<int32_t> cnt((size_t)V + 1, 0);
+    for (int64_t k = 0; k < (int64_t)F * 3; ++k) {
+        const int32_t v = faces_host[k];
+        if (v < 0 || v >= V) return rfail(THMR_ERR_INVALID, "face " + std::to_string(k / 3) + " indexes vertex " + std::to_string(v) +
+                                                            " outside [0, " + std::to_string(V) + ")");
+        ++cnt[v + 1];
+    }
+    for (int32_t v = 0; v < V; ++v) cnt[v + 1] += cnt[v];
+    std::vector<int32_t> csr((size_t)F * 3), fill(cnt.begin(), cnt.end() - 1);
+    for (int32_t f = 0; f < F; ++f)
+        for (int c = 0; c < 3; ++c) csr[fill[faces_host[(int64_t)f * 3 + c]]++] = (f << 2) | c;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+        (void)hipGetLastError();
+        return rfail(THMR_ERR_HIP, "no such HIP device (the render kernels have no CPU fallback)");
+    }
+    if (hipSetDevice(device) != hipSuccess) return rfail(THMR_ERR_HIP, "hipSetDevice failed");
+    thmr_renderer* r = new thmr_renderer();
+    r->device = device; r->F = F; r->V = V;
+    hipError_t e = hipMalloc(&r->faces, sizeof(int32_t) * (size_t)F * 3);
+    if (e == hipSuccess) e = hipMalloc(&r->csr_off, sizeof(int32_t) * ((size_t)V + 1));
+    if (e == hipSuccess) e = hipMalloc(&r->csr, sizeof(int32_t) * (size_t)F * 3);
+    if (e == hipSuccess) e = hipMemcpy(r->faces, faces_host, sizeof(int32_t) * (size_t)F * 3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(r->csr_off, cnt.data(), sizeof(int32_t) * ((size_t)V + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(r->csr, csr.data(), sizeof(int32_t) * (size_t)F * 3, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        const std::string m = std::string("renderer setup: ") + hipGetErrorString(e);
+        thmr_renderer_destroy(r);
+        return rfail(THMR_ERR_HIP, m);
+    }
+    *out = r;
+    return 0;
+}
+
+void thmr_renderer_destroy(thmr_renderer* r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    void* bufs[] = {r->faces, r->csr_off, r->csr, r->s.pos, r->s.fix, r->s.nrm, r->s.rec, r->s.cnt, r->s.off, r->s.cur, r->s.lcnt,
+                    r->s.bins, r->s.large, r->s.colors};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    delete r;
+}
+
+int thmr_renderer_run(thmr_renderer* r, const thmr_render_desc* d, const float* verts_dev, const float* cam_t_dev, int32_t N,
+                      const float* bg_dev, float* out_dev, void* stream) {
+    if (!r) return rfail(THMR_ERR_INVALID, "null renderer");
+    auto bad = [&](const std::string& m) { r->err = m; g_render_err = m; return THMR_ERR_INVALID; };
+    if (!d || !verts_dev || !cam_t_dev || !out_dev) return bad("null descriptor or buffer");
+    if (d->width < 1 || d->height < 1 || d->width > 8192 || d->height > 8192) return bad("image size must be 1 ... 8192 per side");
+    if (d->samples != 1 && d->samples != 4) return bad("samples must be 1 or 4");
+    if (N < 1) return bad("N must be >= 1");
+    if (d->mode != THMR_RENDER_PER_IMAGE && d->mode != THMR_RENDER_ONE_IMAGE) return bad("mode must be THMR_RENDER_PER_IMAGE or THMR_RENDER_ONE_IMAGE");
+    if (d->out_channels != 3 && d->out_channels != 4) return bad("out_channels must be 3 or 4");
+    if (bg_dev && d->out_channels != 3) return bad("compositing over background images writes 3 channels");
+    if (d->n_lights < 0 || d->n_lights > THMR_RENDER_MAX_LIGHTS) return bad("n_lights must be 0 ... THMR_RENDER_MAX_LIGHTS");
+    if ((int64_t)N * r->F * SMALL_TILES >= (int64_t)NONE || (int64_t)N * r->V * 3 >= ((int64_t)1 << 40)) return bad("too many meshes");
+    const float fl[] = {d->fx, d->fy, d->cx, d->cy};
+    for (float v : fl)
+        if (!std::isfinite(v)) return bad("non-finite intrinsics");
+    if (!(d->znear > 0.f) || !std::isfinite(d->znear)) return bad("znear must be a positive number");
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(d->rot[k])) return bad("non-finite rotation");
+    for (int i = 0; i < d->n_lights; ++i)
+        if (d->lights[i].type != THMR_LIGHT_DIRECTIONAL && d->lights[i].type != THMR_LIGHT_POINT) return bad("light " + std::to_string(i) + ": unknown type");
+
+    Params p{};
+    p.W = d->width; p.H = d->height; p.S = d->samples; p.mode = d->mode; p.tr_first = d->translate_first ? 1 : 0;
+    p.N = N; p.V = r->V; p.F = r->F; p.n_img = d->mode == THMR_RENDER_ONE_IMAGE ? 1 : N;
+    p.tiles_x = (p.W + TILE - 1) / TILE; p.tiles_y = (p.H + TILE - 1) / TILE;
+    p.ch = d->out_channels; p.has_colors = d->mesh_colors ? 1 : 0; p.has_img = bg_dev ? 1 : 0;
+    p.fx = d->fx; p.fy = d->fy; p.cx = d->cx; p.cy = d->cy; p.znear = d->znear;
+    for (int k = 0; k < 9; ++k) p.R[k] = d->rot[k];
+    for (int k = 0; k < 3; ++k) {
+        p.base[k] = d->base_color[k]; p.bg[k] = d->bg_color[k]; p.amb[k] = d->ambient[k];
+        p.mean[k] = d->img_mean[k]; p.stdv[k] = d->img_std[k];
+    }
+    p.metallic = d->metallic; p.roughness = d->roughness; p.n_lights = d->n_lights;
+    for (int i = 0; i < d->n_lights; ++i) {
+        const thmr_render_light& L = d->lights[i];
+        p.L[i].type = L.type;
+        for (int k = 0; k < 3; ++k) { p.L[i].v[k] = L.vec[k]; p.L[i].c[k] = L.color[k] * L.intensity; }
+    }
+    const int64_t T = (int64_t)p.n_img * p.tiles_x * p.tiles_y;
+    const size_t NV = (size_t)N * r->V, NF = (size_t)N * r->F;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipSetDevice(r->device) != hipSuccess) return bad("hipSetDevice failed");
+    auto hip_bad = [&](const char* what, hipError_t e) { r->err = std::string(what) + ": " + hipGetErrorString(e); g_render_err = r->err; return THMR_ERR_HIP; };
+    hipError_t e;
+    Scratch& s = r->s;
+    // grow-only scratch; growing synchronises the stream first (earlier launches may still use the old buffers)
+    if (NV * 3 > r->cap_pos || NV > r->cap_fix || NF > r->cap_rec || (size_t)T > r->cap_cnt || (size_t)T + 1 > r->cap_off ||
+        (size_t)p.n_img > r->cap_lcnt || NF * SMALL_TILES > r->cap_bins || (size_t)N * 3 > r->cap_colors) {
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_bad("hipStreamSynchronize", e);
+        if ((e = grow(s.pos, r->cap_pos, NV * 3)) != hipSuccess || (e = grow(s.nrm, r->cap_nrm, NV * 3)) != hipSuccess ||
+            (e = grow(s.fix, r->cap_fix, NV)) != hipSuccess || (e = grow(s.rec, r->cap_rec, NF)) != hipSuccess ||
+            (e = grow(s.cnt, r->cap_cnt, (size_t)T)) != hipSuccess || (e = grow(s.off, r->cap_off, (size_t)T + 1)) != hipSuccess ||
+            (e = grow(s.cur, r->cap_cur, (size_t)T)) != hipSuccess || (e = grow(s.lcnt, r->cap_lcnt, (size_t)p.n_img)) != hipSuccess ||
+            (e = grow(s.bins, r->cap_bins, NF * SMALL_TILES)) != hipSuccess || (e = grow(s.large, r->cap_large, NF)) != hipSuccess ||
+            (e = grow(s.colors, r->cap_colors, (size_t)N * 3)) != hipSuccess)
+            return hip_bad("hipMalloc(render scratch)", e);
+    }
+    if (d->mesh_colors &&
+        (e = hipMemcpyAsync(s.colors, d->mesh_colors, sizeof(float) * (size_t)N * 3, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return hip_bad("hipMemcpyAsync(mesh colours)", e);
+    if ((e = hipMemsetAsync(s.cnt, 0, sizeof(uint32_t) * (size_t)T, st)) != hipSuccess) return hip_bad("hipMemsetAsync", e);
+    if ((e = hipMemsetAsync(s.lcnt, 0, sizeof(uint32_t) * (size_t)p.n_img, st)) != hipSuccess) return hip_bad("hipMemsetAsync", e);
+    const unsigned gv = (unsigned)((NV + 255) / 256), gf = (unsigned)((NF + 255) / 256);
+    hipLaunchKernelGGL(render_vertex_kernel, dim3(gv), dim3(256), 0, st, p, verts_dev, cam_t_dev, s.pos, s.fix);
+    hipLaunchKernelGGL(render_normal_kernel, dim3(gv), dim3(256), 0, st, p, r->faces, r->csr_off, r->csr, s.pos, s.nrm);
+    hipLaunchKernelGGL(render_setup_kernel, dim3(gf), dim3(256), 0, st, p, r->faces, s.pos, s.fix, s.rec, s.cnt, s.lcnt, s.large);
+    hipLaunchKernelGGL(render_scan_kernel, dim3(1), dim3(1024), 0, st, s.cnt, s.off, s.cur, T);
+    hipLaunchKernelGGL(render_fill_kernel, dim3(gf), dim3(256), 0, st, p, s.rec, s.cur, s.bins);
+    const dim3 grid((unsigned)(p.tiles_x * p.tiles_y), (unsigned)p.n_img);
+    if (p.S == 4)
+        hipLaunchKernelGGL(render_raster_kernel<4>, grid, dim3(256), 0, st, p, r->faces, s.pos, s.fix, s.nrm, s.colors, s.rec, s.off,
+                           s.bins, s.lcnt, s.large, bg_dev, out_dev, d->ids_dev);
+    else
+        hipLaunchKernelGGL(render_raster_kernel<1>, grid, dim3(256), 0, st, p, r->faces, s.pos, s.fix, s.nrm, s.colors, s.rec, s.off,
+                           s.bins, s.lcnt, s.large, bg_dev, out_dev, d->ids_dev);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_bad("render kernel launch", e);
+    return 0;
+}
+
+}  // extern "C"
