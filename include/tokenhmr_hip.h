@@ -376,6 +376,45 @@ const char* thmr_renderer_last_error(const thmr_renderer* r);
 int  thmr_renderer_run(thmr_renderer* r, const thmr_render_desc* desc, const float* verts_dev, const float* cam_t_dev, int32_t N,
                        const float* bg_dev, float* out_dev, void* stream);
 
+/* Contact sheet: the reference's MeshRenderer.visualize / visualize_tensorboard (tokenhmr/lib/utils/mesh_renderer.py,
+ * render_openpose.py) as one canvas, in two launches on `stream`.  Per person the tiles are, in this order, those requested in
+ * `panels` (the image; the front and the side render under the hard mask out = alpha > 0.8 ? rgb : bg, bg = the image / ones) and one
+ * skeleton panel per keypoint set given (predicted, then ground truth).  Tiles are laid out as torchvision's make_grid(nrow, padding)
+ * does, pad value 0: xmaps = min(nrow, tiles), ymaps = ceil(tiles / xmaps), canvas (3, ymaps (H + padding) + padding,
+ * xmaps (W + padding) + padding) fp32 planes, tile k at row padding + (k / xmaps)(H + padding), column padding + (k % xmaps)(W + padding).
+ *   images_dev   (n, 3, H, W) fp32, values in 0 ... 1           front_dev / side_dev   (n, H, W, 4) fp32 RGBA of thmr_renderer_run
+ *   pred_kp_dev  (n, 44, 2) fp32 or NULL: normalised keypoints, confidence 1; pixel = img_res (k + 0.5) in fp32; body keypoints 1 ... 14
+ *                take the matching ones of the 19 extra keypoints
+ *   gt_kp_dev    (n, 44, 3) fp32 or NULL: x, y, confidence; scaled the same way and remapped where the extra keypoint has confidence > 0
+ *                and the body one confidence 0 — IN PLACE, as the reference does on its caller's array
+ *   records_dev  ((pred ? n : 0) + (gt ? n : 0), THMR_SHEET_RECORDS, THMR_SHEET_RECORD_WORDS) int32, 16-byte aligned; required with
+ *                keypoints.  The draw list of render_openpose per skeleton, in draw order: 24 limbs, then 25 joints; a record is
+ *                {kind (0 = not drawn, 1 = line, 2 = circle), x0, y0, x1, y1, radius, thickness, colour index, box x0, y0, x1, y1}.
+ *                Written by the first launch, read by the second; the caller may read it back.
+ * A draw-list entry is what render_openpose passes to cv2 (same integer points, radius, thickness, colour, order), except that an
+ * entry with a coordinate beyond +-16384 (or non-finite) is not drawn.  Coverage: integer point (x, y) is the centre of pixel column x,
+ * row y; a line of thickness t covers the pixels within t / 2 of the closed segment; a circle of radius r and thickness k > 0 the
+ * pixels at distance d with (2r - k)^2 <= 4 d^2 <= (2r + k)^2 (no lower bound when 2r <= k), k < 0 the disc d <= r; later entries
+ * overwrite earlier ones.  A covered pixel is colour / 255, any other fl(fl(255 x) / 255) of the image.
+ * Nothing is allocated and nothing synchronises; two calls give identical bits. */
+#define THMR_SHEET_IMAGE 1
+#define THMR_SHEET_FRONT 2
+#define THMR_SHEET_SIDE 4
+#define THMR_SHEET_KEYPOINTS 44
+#define THMR_SHEET_RECORDS 49
+#define THMR_SHEET_RECORD_WORDS 12
+typedef struct thmr_sheet_desc {
+    int32_t n;                  /* people, >= 1 */
+    int32_t width, height;      /* of every image and render, 1 ... 8192 */
+    int32_t img_res;            /* keypoint scale (MODEL.IMAGE_SIZE), 1 ... 8192 */
+    int32_t panels;             /* THMR_SHEET_IMAGE | THMR_SHEET_FRONT | THMR_SHEET_SIDE */
+    int32_t nrow, padding;      /* make_grid's */
+    int32_t canvas_width, canvas_height;   /* of canvas_dev; must equal the size stated above */
+} thmr_sheet_desc;
+int  thmr_renderer_sheet(thmr_renderer* r, const thmr_sheet_desc* desc, const float* images_dev, const float* front_dev,
+                         const float* side_dev, const float* pred_kp_dev, float* gt_kp_dev, int32_t* records_dev, float* canvas_dev,
+                         void* stream);
+
 /* ---- data-parallel collectives for hosts without torch.distributed ----
  * The reference has no collective on this path (inference is single-device, tokenhmr/eval.py:52-54).  Crops shard with NO data-path
  * collective; two collectives surround the path: ONE broadcast of the packed weight arena at start-up (only rank `root` read the

@@ -71,6 +71,16 @@ class RenderDesc(C.Structure):
                 ("img_std", C.c_float * 3), ("ids_dev", C.c_void_p)]
 
 
+# thmr_sheet_desc.panels, and the draw-list records of thmr_renderer_sheet (header: THMR_SHEET_*)
+SHEET_IMAGE, SHEET_FRONT, SHEET_SIDE = 1, 2, 4
+SHEET_KEYPOINTS, SHEET_RECORDS, SHEET_RECORD_WORDS = 44, 49, 12
+
+
+class SheetDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("img_res", C.c_int32), ("panels", C.c_int32),
+                ("nrow", C.c_int32), ("padding", C.c_int32), ("canvas_width", C.c_int32), ("canvas_height", C.c_int32)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
@@ -118,7 +128,9 @@ def load(exp=None):
         pass
     lib = C.CDLL(path)
     older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
-    missing = [s for s in declared_symbols() if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))]
+    # a build loaded by path may also predate thmr_renderer_sheet (added without an ABI change: a new symbol, no layout touched)
+    missing = [s for s in declared_symbols() if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
+               and not (isinstance(exp, str) and s == "thmr_renderer_sheet")]
     if missing:
         raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -175,6 +187,8 @@ def load(exp=None):
     lib.thmr_renderer_last_error.argtypes = [vp]
     lib.thmr_renderer_last_error.restype = C.c_char_p
     lib.thmr_renderer_run.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, i32, vp, vp, vp]
+    if hasattr(lib, "thmr_renderer_sheet"):
+        lib.thmr_renderer_sheet.argtypes = [vp, C.POINTER(SheetDesc), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.thmr_pack_records.argtypes = [C.POINTER(Outputs), i32, vp, vp]
     lib.thmr_bcast_weights.argtypes = [vp, vp, i32, vp]
     lib.thmr_allgather_records.argtypes = [vp, vp, i32, vp, vp]

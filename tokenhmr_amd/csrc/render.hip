@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <string>
@@ -559,6 +560,256 @@ int thmr_renderer_run(thmr_renderer* r, const thmr_render_desc* d, const float* 
         hipLaunchKernelGGL(render_raster_kernel<1>, grid, dim3(256), 0, st, p, r->faces, s.pos, s.fix, s.nrm, s.colors, s.rec, s.off,
                            s.bins, s.lcnt, s.large, bg_dev, out_dev, d->ids_dev);
     if ((e = hipGetLastError()) != hipSuccess) return hip_bad("render kernel launch", e);
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ contact sheet
+// MeshRenderer.visualize / visualize_tensorboard (tokenhmr/lib/utils/mesh_renderer.py) in two launches on the caller's stream:
+//   sheet_build_kernel   one wave per skeleton: the keypoints -> pixels scaling, visualize_tensorboard's keypoint remap, the
+//                        rectangle / thickness arithmetic of render_openpose and its draw list as THMR_SHEET_RECORDS records
+//   sheet_kernel         the whole make_grid canvas: padding, image panels, hard-mask mesh panels (alpha > 0.8) and skeleton
+//                        panels (records walked last to first per pixel, first hit wins: the painter's order without hazards)
+// No atomics, no allocation, no synchronisation; every value is integer or single-rounded fp32 arithmetic, which the NumPy
+// restatement (tests/overlay_numpy.py) repeats bit for bit.
+namespace {
+
+constexpr int SK_REC = THMR_SHEET_RECORDS;
+constexpr int SK_WORDS = THMR_SHEET_RECORD_WORDS;
+constexpr int SK_KP = THMR_SHEET_KEYPOINTS;
+constexpr int SK_BODY = 25;
+constexpr int SK_LIMBS = 24;
+constexpr float SK_RANGE = 16385.f;            // |trunc(v)| <= 16384  <=>  |v| < 16385; NaN and inf fail the comparison
+enum { PANEL_IMAGE = 0, PANEL_FRONT = 1, PANEL_SIDE = 2, PANEL_PRED = 3, PANEL_GT = 4 };
+enum { REC_KIND = 0, REC_X0, REC_Y0, REC_X1, REC_Y1, REC_RADIUS, REC_THICK, REC_COLOR, REC_BX0, REC_BY0, REC_BX1, REC_BY1 };
+
+// OpenPose BODY_25: the limbs it renders (pairs of keypoint indices; a limb takes the colour of its second keypoint) and its palette
+__constant__ uint8_t SK_LIMB[SK_LIMBS][2] = {{1, 8},   {1, 2},   {1, 5},   {2, 3},   {3, 4},   {5, 6},   {6, 7},   {8, 9},
+                                             {9, 10},  {10, 11}, {8, 12},  {12, 13}, {13, 14}, {1, 0},   {0, 15},  {15, 17},
+                                             {0, 16},  {16, 18}, {14, 19}, {19, 20}, {14, 21}, {11, 22}, {22, 23}, {11, 24}};
+__constant__ uint8_t SK_COLOR[SK_BODY][3] = {{255, 0, 85},  {255, 0, 0},   {255, 85, 0},  {255, 170, 0}, {255, 255, 0}, {170, 255, 0}, {85, 255, 0},
+                                             {0, 255, 0},   {255, 0, 0},   {0, 255, 85},  {0, 255, 170}, {0, 255, 255}, {0, 170, 255}, {0, 85, 255},
+                                             {0, 0, 255},   {255, 0, 170}, {170, 0, 255}, {255, 0, 255}, {85, 0, 255},  {0, 0, 255},   {0, 0, 255},
+                                             {0, 0, 255},   {0, 255, 255}, {0, 255, 255}, {0, 255, 255}};
+// visualize_tensorboard's keypoint_matches: body keypoint i takes extra keypoint SK_REMAP[i] (the 19 after the 25), -1 = keeps its own
+__constant__ int8_t SK_REMAP[SK_BODY] = {-1, 12, 8, 7, 6, 9, 10, 11, 14, 2, 1, 0, 3, 4, 5, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+
+struct SheetParams {
+    int32_t B, W, H, img_res, n_panels, xmaps, ymaps, pad, Wg, Hg, vec, has_pred, has_gt;
+    int32_t kind[5];
+    double thick;                              // sqrt(area) * thickness_circle_ratio = sqrt(3 W) / 75, rounded as the host rounds it
+};
+
+__device__ __forceinline__ void sk_store(int32_t* rec, int slot, int kind, int x0, int y0, int x1, int y1, int radius, int thick, int color,
+                                         int ext, int W, int H) {
+    int4 a = make_int4(0, 0, 0, 0), b = a, c = a;
+    if (kind) {
+        a = make_int4(kind, x0, y0, x1);
+        b = make_int4(y1, radius, thick, color);
+        c = make_int4(max(min(x0, x1) - ext, 0), max(min(y0, y1) - ext, 0), min(max(x0, x1) + ext, W - 1), min(max(y0, y1) + ext, H - 1));
+    }
+    int4* o = reinterpret_cast<int4*>(rec + slot * SK_WORDS);
+    o[0] = a; o[1] = b; o[2] = c;
+}
+
+__global__ void __launch_bounds__(64) sheet_build_kernel(SheetParams p, const float* __restrict__ pred, float* gt, int32_t* __restrict__ rec) {
+    const int s = blockIdx.x, l = threadIdx.x;                     // skeleton s: the B predicted ones first, then the B ground-truth ones
+    const bool is_gt = !p.has_pred || s >= p.B;
+    const int b = (is_gt && p.has_pred) ? s - p.B : s;
+    const float res = (float)p.img_res;
+    float x = 0.f, y = 0.f, c = 0.f;
+    float* g = is_gt ? gt + ((int64_t)b * SK_KP + l) * 3 : nullptr;
+    if (l < SK_KP) {
+        const float* k = is_gt ? g : pred + ((int64_t)b * SK_KP + l) * 2;
+        x = __fmul_rn(res, __fadd_rn(k[0], 0.5f));                // img_res * (k + 0.5) in fp32
+        y = __fmul_rn(res, __fadd_rn(k[1], 0.5f));
+        c = is_gt ? k[2] : 1.f;                                    // predicted keypoints get confidence 1
+    }
+    const int src = l < SK_BODY ? SK_REMAP[l] : -1;
+    const int from = SK_BODY + (src < 0 ? 0 : src);
+    const float ex = __shfl(x, from), ey = __shfl(y, from), ec = __shfl(c, from);
+    if (src >= 0 && (!is_gt || (ec > 0.f && c == 0.f))) { x = ex; y = ey; c = ec; }      // unconditional for predictions
+    if (is_gt) {
+        __syncthreads();                                           // every lane's loads are back before a keypoint is overwritten
+        if (l < SK_KP) { g[0] = x; g[1] = y; g[2] = c; }           // the reference scales and remaps the caller's array in place
+    }
+    // get_keypoints_rectangle over the body keypoints above 0.1; numpy's max / min carry a NaN, which leaves area > 0 false
+    const bool body = l < SK_BODY, vr = body && c > 0.1f;
+    const bool has_nan = __ballot(vr && (x != x || y != y)) != 0;
+    float mxx = vr ? x : -INFINITY, mnx = vr ? x : INFINITY, mxy = vr ? y : -INFINITY, mny = vr ? y : INFINITY;
+    for (int o = 32; o; o >>= 1) {
+        mxx = fmaxf(mxx, __shfl_xor(mxx, o)); mnx = fminf(mnx, __shfl_xor(mnx, o));
+        mxy = fmaxf(mxy, __shfl_xor(mxy, o)); mny = fminf(mny, __shfl_xor(mny, o));
+    }
+    bool draw = false;
+    int t_line = 0, t_circle = 0, radius = 0;
+    if (__ballot(vr) != 0 && !has_nan) {
+        const float pw = __fsub_rn(mxx, mnx), ph = __fsub_rn(mxy, mny), area = __fmul_rn(pw, ph);
+        if (area > 0.f) {
+            // the reference reads width, height = img.shape[1], img.shape[2] of an HWC image: "height" is the 3 channels
+            const float rw = __fdiv_rn(pw, (float)p.W), rh = __fdiv_rn(ph, 3.f);
+            const float m = rh > rw ? rh : rw, ratio = m < 1.f ? m : 1.f;
+            const double tr = fmax(rint(p.thick * (double)ratio), 2.0);            // np.round: half to even
+            t_circle = (int)(ratio > 0.05f ? tr : 1.0);                               // maximum(1, -1) = 1 on the other branch
+            t_line = (int)fmax(1.0, rint(tr * 0.75));
+            radius = (int)rint(tr * 0.5);
+            draw = true;                                                              // W <= 8192: tr = 2, so all three are <= 2
+        }
+    }
+    rec += (int64_t)s * SK_REC * SK_WORDS;
+    const int i1 = l < SK_LIMBS ? SK_LIMB[l][0] : 0, i2 = l < SK_LIMBS ? SK_LIMB[l][1] : 0;
+    const float ax = __shfl(x, i1), ay = __shfl(y, i1), ac = __shfl(c, i1), bx = __shfl(x, i2), by = __shfl(y, i2), bc = __shfl(c, i2);
+    if (l < SK_LIMBS) {
+        const bool ok = draw && ac > 0.1f && bc > 0.1f && fabsf(ax) < SK_RANGE && fabsf(ay) < SK_RANGE && fabsf(bx) < SK_RANGE && fabsf(by) < SK_RANGE;
+        sk_store(rec, l, ok ? 1 : 0, (int)ax, (int)ay, (int)bx, (int)by, 0, t_line, i2, (t_line + 1) >> 1, p.W, p.H);
+    }
+    if (body) {
+        const bool ok = draw && c > 0.1f && fabsf(x) < SK_RANGE && fabsf(y) < SK_RANGE;
+        sk_store(rec, SK_LIMBS + l, ok ? 2 : 0, (int)x, (int)y, (int)x, (int)y, radius, t_circle, l, radius + ((t_circle + 1) >> 1), p.W, p.H);
+    }
+}
+
+// Does the primitive cover the pixel whose centre is the integer point (px, py)?  Exact in int64: |coordinate| <= 16384 and
+// 0 <= px, py < 8192 keep every difference below 2^15 + 2^13 and |b - a|^2 <= 2^31; radius and thickness are <= 2 from the builder
+// (any value below 2^14 would do).  So dot, cross < 2^31.2, cross^2 < 2^62.4 and t^2 |ab|^2 <= 2^33 fit — whereas 4 cross^2 could
+// reach 2^64, hence the comparison against (t^2 |ab|^2) >> 2, which is the same predicate because cross^2 is an integer.
+__device__ __forceinline__ bool sk_covers(const int32_t* R, int px, int py) {
+    const int64_t t = R[REC_THICK], wx = px - R[REC_X0], wy = py - R[REC_Y0], d2 = wx * wx + wy * wy;
+    if (R[REC_KIND] == 1) {                    // capsule: distance to the closed segment <= t / 2
+        const int64_t dx = R[REC_X1] - R[REC_X0], dy = R[REC_Y1] - R[REC_Y0], len2 = dx * dx + dy * dy, dot = wx * dx + wy * dy;
+        if (dot <= 0) return 4 * d2 <= t * t;                      // before a, and a == b
+        if (dot >= len2) {
+            const int64_t ux = px - R[REC_X1], uy = py - R[REC_Y1];
+            return 4 * (ux * ux + uy * uy) <= t * t;
+        }
+        const int64_t cr = wx * dy - wy * dx;
+        return cr * cr <= ((t * t * len2) >> 2);
+    }
+    const int64_t r = R[REC_RADIUS];           // ring of width k about radius r; k < 0: the filled disc
+    if (t < 0) return d2 <= r * r;
+    const int64_t lo = 2 * r - t, hi = 2 * r + t;
+    return 4 * d2 <= hi * hi && (lo <= 0 || lo * lo <= 4 * d2);
+}
+
+// One workgroup works inside one grid cell (a tile with the padding above and left of it; the last column / row of cells also own
+// the canvas's right / bottom padding), so it stages at most one skeleton.  A lane owns 4 consecutive canvas x, aligned to 16 B in the
+// canvas row: with Wg % 4 == 0 every run inside the cell is one dwordx4 store per plane.
+__global__ void __launch_bounds__(256) sheet_kernel(SheetParams p, const float* __restrict__ images, const float* __restrict__ front,
+                                                    const float* __restrict__ side, const int32_t* __restrict__ rec, float* __restrict__ canvas) {
+    __shared__ int32_t srec[SK_REC * SK_WORDS];
+    const int cell = blockIdx.y, cxi = cell % p.xmaps, cyi = cell / p.xmaps;
+    const int cw = p.W + p.pad, ch = p.H + p.pad;
+    const int X0 = cxi * cw, X1 = cxi == p.xmaps - 1 ? p.Wg : X0 + cw;
+    const int Y0 = cyi * ch, Y1 = cyi == p.ymaps - 1 ? p.Hg : Y0 + ch;
+    const int person = cell / p.n_panels;
+    const int kind = person < p.B ? p.kind[cell % p.n_panels] : -1;                 // make_grid leaves the cells past the last tile at 0
+    const bool skel = kind == PANEL_PRED || kind == PANEL_GT;
+    if (skel) {
+        const int32_t* src = rec + (int64_t)((kind == PANEL_GT && p.has_pred ? p.B : 0) + person) * SK_REC * SK_WORDS;
+        for (int i = threadIdx.x; i < SK_REC * SK_WORDS; i += 256) srec[i] = src[i];
+    }
+    __syncthreads();
+    const int q0 = X0 >> 2, nq = ((X1 + 3) >> 2) - q0;
+    const int item = blockIdx.x * 256 + threadIdx.x, row = item / nq;
+    if (row >= Y1 - Y0) return;
+    const int xs = (q0 + item % nq) * 4, y = Y0 + row, ly = y - Y0 - p.pad, lx0 = xs - X0 - p.pad;
+    const bool row_in = kind >= 0 && ly >= 0 && ly < p.H;
+    unsigned own = 0, inside = 0;
+    for (int j = 0; j < 4; ++j) {
+        if (xs + j >= X0 && xs + j < X1) own |= 1u << j;
+        if (row_in && lx0 + j >= 0 && lx0 + j < p.W) inside |= 1u << j;
+    }
+    int col[4] = {-1, -1, -1, -1};
+    if (skel) {
+        unsigned pending = inside;
+        for (int r = SK_REC - 1; r >= 0 && pending; --r) {
+            const int32_t* R = srec + r * SK_WORDS;
+            if (R[REC_KIND] == 0 || ly < R[REC_BY0] || ly > R[REC_BY1] || lx0 + 3 < R[REC_BX0] || lx0 > R[REC_BX1]) continue;
+            for (int j = 0; j < 4; ++j)
+                if ((pending >> j & 1) && sk_covers(R, lx0 + j, ly)) { col[j] = R[REC_COLOR]; pending &= ~(1u << j); }
+        }
+    }
+    const int64_t plane = (int64_t)p.H * p.W;
+    float v[3][4];
+    for (int j = 0; j < 4; ++j) {
+        v[0][j] = v[1][j] = v[2][j] = 0.f;
+        if (!(inside >> j & 1)) continue;
+        const int64_t pix = (int64_t)ly * p.W + lx0 + j;
+        const float* im = images + (int64_t)person * 3 * plane + pix;
+        if (kind == PANEL_IMAGE) {
+            for (int c = 0; c < 3; ++c) v[c][j] = im[c * plane];
+        } else if (skel) {
+            for (int c = 0; c < 3; ++c)                            // render_openpose(255 * img) / 255: two roundings where nothing is drawn
+                v[c][j] = col[j] >= 0 ? __fdiv_rn((float)SK_COLOR[col[j]][c], 255.f) : __fdiv_rn(__fmul_rn(255.f, im[c * plane]), 255.f);
+        } else {                                                   // color * valid_mask + (1 - valid_mask) * bg, valid = alpha > 0.8
+            const float4 px = reinterpret_cast<const float4*>(kind == PANEL_FRONT ? front : side)[(int64_t)person * plane + pix];
+            const bool valid = px.w > 0.8f;
+            v[0][j] = valid ? px.x : (kind == PANEL_FRONT ? im[0] : 1.f);
+            v[1][j] = valid ? px.y : (kind == PANEL_FRONT ? im[plane] : 1.f);
+            v[2][j] = valid ? px.z : (kind == PANEL_FRONT ? im[2 * plane] : 1.f);
+        }
+    }
+    const int64_t gplane = (int64_t)p.Hg * p.Wg;
+    float* dst = canvas + (int64_t)y * p.Wg + xs;
+    for (int c = 0; c < 3; ++c, dst += gplane) {
+        if (p.vec && own == 15u) {
+            *reinterpret_cast<float4*>(dst) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (own >> j & 1) dst[j] = v[c][j];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int thmr_renderer_sheet(thmr_renderer* r, const thmr_sheet_desc* d, const float* images_dev, const float* front_dev, const float* side_dev,
+                        const float* pred_kp_dev, float* gt_kp_dev, int32_t* records_dev, float* canvas_dev, void* stream) {
+    if (!r) return rfail(THMR_ERR_INVALID, "null renderer");
+    auto bad = [&](const std::string& m) { r->err = m; g_render_err = m; return THMR_ERR_INVALID; };
+    if (!d || !images_dev || !canvas_dev) return bad("null descriptor or buffer");
+    if (d->n < 1 || d->n > (1 << 20)) return bad("n must be 1 ... 2^20 people");
+    if (d->width < 1 || d->height < 1 || d->width > 8192 || d->height > 8192) return bad("image size must be 1 ... 8192 per side");
+    if (d->img_res < 1 || d->img_res > 8192) return bad("img_res must be 1 ... 8192");
+    if (d->nrow < 1 || d->padding < 0 || d->padding > 4096) return bad("nrow must be >= 1 and padding 0 ... 4096");
+    if (d->panels & ~(THMR_SHEET_IMAGE | THMR_SHEET_FRONT | THMR_SHEET_SIDE)) return bad("unknown panel bit");
+    if (((d->panels & THMR_SHEET_FRONT) && !front_dev) || ((d->panels & THMR_SHEET_SIDE) && !side_dev)) return bad("a requested mesh panel has no render");
+    if ((pred_kp_dev || gt_kp_dev) && !records_dev) return bad("skeleton panels need the records buffer");
+    if (reinterpret_cast<uintptr_t>(records_dev) % 16 || reinterpret_cast<uintptr_t>(front_dev) % 16 || reinterpret_cast<uintptr_t>(side_dev) % 16)
+        return bad("records and RGBA buffers must be 16-byte aligned");
+    SheetParams p{};
+    p.B = d->n; p.W = d->width; p.H = d->height; p.img_res = d->img_res; p.pad = d->padding;
+    p.has_pred = pred_kp_dev ? 1 : 0; p.has_gt = gt_kp_dev ? 1 : 0;
+    if (d->panels & THMR_SHEET_IMAGE) p.kind[p.n_panels++] = PANEL_IMAGE;
+    if (d->panels & THMR_SHEET_FRONT) p.kind[p.n_panels++] = PANEL_FRONT;
+    if (d->panels & THMR_SHEET_SIDE) p.kind[p.n_panels++] = PANEL_SIDE;
+    if (p.has_pred) p.kind[p.n_panels++] = PANEL_PRED;
+    if (p.has_gt) p.kind[p.n_panels++] = PANEL_GT;
+    if (!p.n_panels) return bad("no panel requested");
+    // torchvision.utils.make_grid(list, nrow, padding), pad value 0
+    const int64_t tiles = (int64_t)p.B * p.n_panels;
+    const int64_t xmaps = std::min<int64_t>(d->nrow, tiles), ymaps = (tiles + xmaps - 1) / xmaps;
+    const int64_t Wg = xmaps * (p.W + p.pad) + p.pad, Hg = ymaps * (p.H + p.pad) + p.pad;
+    if (Wg > (1 << 24) || Hg > (1 << 24)) return bad("canvas beyond 2^24 per side");
+    if (d->canvas_width != Wg || d->canvas_height != Hg)
+        return bad("canvas must be " + std::to_string(Hg) + " x " + std::to_string(Wg) + " for these tiles");
+    p.xmaps = (int32_t)xmaps; p.ymaps = (int32_t)ymaps; p.Wg = (int32_t)Wg; p.Hg = (int32_t)Hg;
+    p.vec = (Wg % 4 == 0 && reinterpret_cast<uintptr_t>(canvas_dev) % 16 == 0) ? 1 : 0;
+    p.thick = std::sqrt((double)((int64_t)p.W * 3)) * (1.0 / 75.0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipSetDevice(r->device) != hipSuccess) return bad("hipSetDevice failed");
+    const int n_skel = (p.has_pred + p.has_gt) * p.B;
+    if (n_skel) hipLaunchKernelGGL(sheet_build_kernel, dim3((unsigned)n_skel), dim3(64), 0, st, p, pred_kp_dev, gt_kp_dev, records_dev);
+    const int64_t items = (int64_t)(((p.W + 2 * p.pad + 3) >> 2) + 1) * (p.H + 2 * p.pad);
+    const int64_t cells = xmaps * ymaps;
+    if (cells > 65535) return bad("more than 65535 grid cells");
+    hipLaunchKernelGGL(sheet_kernel, dim3((unsigned)((items + 255) / 256), (unsigned)cells), dim3(256), 0, st, p, images_dev, front_dev, side_dev,
+                       records_dev, canvas_dev);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { r->err = std::string("sheet kernel launch: ") + hipGetErrorString(e); g_render_err = r->err; return THMR_ERR_HIP; }
     return 0;
 }
 

@@ -9,6 +9,13 @@ The reference's scenes are reduced here, on the host, to one camera frame (x rig
 perspective_projection), a light list and a material, written into a thmr_render_desc; rasterisation, visibility, shading,
 resolve and compositing run in csrc/render.hip.  The batched device entry points the per-person calls wrap are
 `Renderer.render_batch` (B crops / side views in one launch) and `Renderer.render_scene` (one frame holding N meshes).
+
+    from tokenhmr_amd.render import MeshRenderer                      # instead of lib.utils (eval.py:19)
+    mesh_renderer = MeshRenderer(model_cfg, faces=smpl.faces)         # eval.py --render
+
+`MeshRenderer` is the drop-in for lib/utils/mesh_renderer.py: its contact sheets (the image, the mesh from the front and from the side,
+the predicted and the ground-truth OpenPose skeleton per person, tiled as make_grid tiles them) are two RGBA renders plus
+thmr_renderer_sheet, which builds the skeletons' draw lists and writes the whole canvas on the device.
 There is no CPU fallback.
 """
 import ctypes as C
@@ -383,3 +390,156 @@ class Renderer:
         t = np.stack([np.asarray(x, dtype=np.float32).reshape(3) for x in cam_t])
         out = self.render_scene(v, t, render_res[0], render_res[1], focal_length, rot_axis, rot_angle, mesh_base_color, scene_bg_color)
         return out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------ the contact sheets of eval.py --render
+def sheet_geometry(n_tiles, nrow, padding, height, width):
+    """torchvision.utils.make_grid(list of n_tiles (3, height, width) tensors, nrow, padding): (xmaps, ymaps, canvas height,
+    canvas width).  Tile k starts at row padding + (k // xmaps) (height + padding), column padding + (k % xmaps) (width + padding)."""
+    xmaps = min(int(nrow), int(n_tiles))
+    ymaps = -(-int(n_tiles) // xmaps)
+    return xmaps, ymaps, ymaps * (height + padding) + padding, xmaps * (width + padding) + padding
+
+
+def side_translation(cam_t):
+    """The translation the reference's side view sees in visualize*: __call__ negates camera_translation[i][0] in place on both of
+    its calls, so the second one (the side view) runs on (-tx, ty, tz) in this project's frame and leaves the caller's array restored."""
+    if torch.is_tensor(cam_t):
+        return torch.cat([-cam_t[..., :1], cam_t[..., 1:]], dim=-1)
+    return np.asarray(cam_t) * np.array([-1.0, 1.0, 1.0], dtype=np.asarray(cam_t).dtype)
+
+
+class MeshRenderer:
+    """lib/utils/mesh_renderer.py:44-157 on the GPU: same constructor, __call__, visualize and visualize_tensorboard.  The arguments
+    are the reference's NumPy arrays or torch tensors already on the device (all of one kind); the sheets come back as a
+    (3, Hg, Wg) float32 tensor on the device, __call__ as a NumPy (H, W, 3) image.  With device tensors nothing is copied to the
+    host and nothing synchronises."""
+
+    def __init__(self, cfg, faces=None, device="cuda:0", samples=4):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("MeshRenderer needs a GPU device: the render kernels have no CPU fallback")
+        if samples not in (1, 4):
+            raise ValueError("samples must be 1 or 4")
+        self.cfg = cfg
+        self.focal_length = _get(cfg, "EXTRA", "FOCAL_LENGTH")
+        self.img_res = _get(cfg, "MODEL", "IMAGE_SIZE")
+        self.camera_center = [self.img_res // 2, self.img_res // 2]
+        self.faces = faces
+        self._device, self._samples = dev, samples
+        self._renderer = None
+
+    @property
+    def renderer(self):
+        """The Renderer that owns the device handle; faces=None is accepted at construction, as in the reference, and fails here."""
+        if self._renderer is None:
+            if self.faces is None:
+                raise ValueError("MeshRenderer was constructed without faces: nothing to render")
+            self._renderer = Renderer(self.cfg, self.faces, self._device, self._samples)
+        return self._renderer
+
+    def close(self):
+        if self._renderer is not None:
+            self._renderer.close()
+
+    def scene(self, width, height, focal_length, side_view=False, rot_angle=90, baseColorFactor=(1.0, 1.0, 0.9, 1.0)):
+        """mesh_renderer.py:109-146 in the camera frame: Renderer.__call__'s scene with a transparent black background."""
+        return build_scene("call", width, height, focal_length, np.zeros(3), side_view, rot_angle,
+                           mesh_base_color=tuple(baseColorFactor)[:3], scene_bg_color=(0, 0, 0))
+
+    def _sheet(self, n_verts, images, front, side, panels, pred=None, gt=None, nrow=1, padding=0):
+        """thmr_renderer_sheet on device tensors; returns (canvas, records or None)."""
+        r = self.renderer
+        B, _, H, W = images.shape
+        n_skel = (pred is not None) + (gt is not None)
+        n_panels = bin(panels).count("1") + n_skel
+        _, _, Hg, Wg = sheet_geometry(B * n_panels, nrow, padding, H, W)
+        canvas = torch.empty(3, Hg, Wg, device=r.device, dtype=torch.float32)
+        records = torch.empty(n_skel * B, _cabi.SHEET_RECORDS, _cabi.SHEET_RECORD_WORDS, device=r.device, dtype=torch.int32) if n_skel else None
+        d = _cabi.SheetDesc(B, W, H, int(self.img_res), panels, int(nrow), int(padding), Wg, Hg)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(r.device):
+            stream = torch.cuda.current_stream(r.device).cuda_stream
+            h = r._handle(n_verts)                     # the handle the two renders ran on
+            rc = r.lib.thmr_renderer_sheet(h, C.byref(d), images.data_ptr(), ptr(front), ptr(side), ptr(pred), ptr(gt), ptr(records),
+                                           canvas.data_ptr(), stream)
+        if rc != 0:
+            raise _cabi.EngineError(f"thmr_renderer_sheet: {r.lib.thmr_renderer_last_error(h).decode()}")
+        return canvas, records
+
+    def __call__(self, vertices, camera_translation, image, focal_length=5000, text=None, resize=None, side_view=False,
+                 baseColorFactor=(1.0, 1.0, 0.9, 1.0), rot_angle=90):
+        """One person over one (H, W, 3) image with values in 0 ... 1 (the side view over ones): the mesh where all samples of a pixel
+        are covered (alpha > 0.8), the background elsewhere.  `text` is unused, as in the reference."""
+        if resize is not None:
+            raise NotImplementedError("resize= needs cv2.resize, which this renderer does not restate; resize the returned image")
+        img = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"image must be (H, W, 3), got {img.shape}")
+        v = vertices.detach().cpu().numpy() if torch.is_tensor(vertices) else np.asarray(vertices)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError(f"vertices must be (V, 3), got {v.shape}")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        check_size(W, H)
+        r = self.renderer
+        t = np.array(camera_translation, dtype=np.float64).reshape(3)
+        check_meshes(v[None], t[None], r._max_index)
+        camera_translation[0] *= -1.                  # mesh_renderer.py:118 — in place, on the caller's array
+        rgba = r._run(self.scene(W, H, focal_length, side_view, rot_angle, baseColorFactor), v[None].astype(np.float32), t[None],
+                      _cabi.RENDER_PER_IMAGE, 4)
+        images = torch.as_tensor(np.ascontiguousarray(img.transpose(2, 0, 1)[None], dtype=np.float32)).to(r.device)
+        canvas, _ = self._sheet(v.shape[0], images, None if side_view else rgba, rgba if side_view else None,
+                                _cabi.SHEET_SIDE if side_view else _cabi.SHEET_FRONT)
+        return np.ascontiguousarray(canvas.permute(1, 2, 0).cpu().numpy())
+
+    def _sheet_arguments(self, vertices, camera_translation, images, pred_keypoints=None, gt_keypoints=None):
+        """Every check of visualize / visualize_tensorboard, before any device work.  Returns on_device."""
+        args = [a for a in (vertices, camera_translation, images, pred_keypoints, gt_keypoints) if a is not None]
+        tensors = [a for a in args if torch.is_tensor(a)]
+        if tensors and (len(tensors) != len(args) or any(a.device != self.renderer.device for a in tensors)):
+            raise ValueError("pass every argument as a NumPy array, or every argument as a tensor on the renderer's device")
+        check_meshes(vertices, camera_translation, self.renderer._max_index)
+        B = int(vertices.shape[0])
+        if len(images.shape) != 4 or tuple(images.shape[:2]) != (B, 3):
+            raise ValueError(f"images must be ({B}, 3, H, W), got {tuple(images.shape)}")
+        check_size(images.shape[3], images.shape[2])
+        if pred_keypoints is not None and tuple(pred_keypoints.shape) != (B, _cabi.SHEET_KEYPOINTS, 2):
+            raise ValueError(f"pred_keypoints must be ({B}, {_cabi.SHEET_KEYPOINTS}, 2), got {tuple(pred_keypoints.shape)}")
+        if gt_keypoints is not None:
+            if tuple(gt_keypoints.shape) != (B, _cabi.SHEET_KEYPOINTS, 3):
+                raise ValueError(f"gt_keypoints must be ({B}, {_cabi.SHEET_KEYPOINTS}, 3), got {tuple(gt_keypoints.shape)}")
+            floating = gt_keypoints.dtype.is_floating_point if tensors else np.issubdtype(gt_keypoints.dtype, np.floating)
+            if not floating:
+                raise ValueError("gt_keypoints are scaled in place: they must be a floating-point array")
+        return bool(tensors)
+
+    def _sheets(self, vertices, camera_translation, images, pred_keypoints, gt_keypoints, nrow, padding):
+        on_device = self._sheet_arguments(vertices, camera_translation, images, pred_keypoints, gt_keypoints)
+        if int(nrow) < 1 or int(padding) < 0:
+            raise ValueError("nrow must be >= 1 and padding >= 0")
+        r = self.renderer
+        dev = lambda a: None if a is None else torch.as_tensor(a).detach().to(r.device, torch.float32).contiguous()
+        v, t, img, pred, gt = dev(vertices), dev(camera_translation), dev(images), dev(pred_keypoints), dev(gt_keypoints)
+        H, W = int(img.shape[2]), int(img.shape[3])
+        # the reference calls __call__ twice on the same camera_translation[i], which it negates in place each time: the front view
+        # sees t, the side view (-tx, ty, tz), and the caller's array ends up as it was.  visualize* ignore their focal_length.
+        front = r._run(self.scene(W, H, self.focal_length), v, t, _cabi.RENDER_PER_IMAGE, 4)
+        side = r._run(self.scene(W, H, self.focal_length, side_view=True), v, side_translation(t), _cabi.RENDER_PER_IMAGE, 4)
+        canvas, _ = self._sheet(int(v.shape[1]), img, front, side, _cabi.SHEET_IMAGE | _cabi.SHEET_FRONT | _cabi.SHEET_SIDE, pred, gt, nrow, padding)
+        if gt_keypoints is not None:                   # scaled and remapped in place, like the reference's caller array
+            if not on_device:
+                gt_keypoints[...] = gt.cpu().numpy()
+            elif gt.data_ptr() != gt_keypoints.data_ptr():
+                gt_keypoints.copy_(gt)
+        return canvas
+
+    def visualize(self, vertices, camera_translation, images, focal_length=None, nrow=3, padding=2):
+        """mesh_renderer.py:57-68: per person the image, the front and the side view, tiled nrow to a row."""
+        return self._sheets(vertices, camera_translation, images, None, None, nrow, padding)
+
+    def visualize_tensorboard(self, vertices, camera_translation, images, pred_keypoints, gt_keypoints, focal_length=None, nrow=5, padding=2):
+        """mesh_renderer.py:70-107: visualize's tiles plus the predicted and the ground-truth OpenPose skeleton over the image; nrow
+        shrinks by one for each keypoint set that is None.  gt_keypoints is scaled to pixels and remapped in place."""
+        nrow = nrow - 1 if gt_keypoints is None else nrow
+        nrow = nrow - 1 if pred_keypoints is None else nrow
+        return self._sheets(vertices, camera_translation, images, pred_keypoints, gt_keypoints, nrow, padding)
