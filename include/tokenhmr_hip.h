@@ -144,7 +144,9 @@ int thmr_arena_bytes(const thmr_config* cfg, size_t* weight_bytes, size_t* scrat
 
 /* Device memory the engine allocates ITSELF, outside the two arenas, for `vit_gemm_mode` (0 / 1, see thmr_set_vit_gemm): the split3 copies
  * of the ViT weights (shared by all engines of this process that were created on the same weight_arena_dev), the split3 activation operands
- * of max_batch crops, the hand-over workspace of the persistent GEMM.  All 0 for mode 0 and for max_batch < 3.  No GPU needed. */
+ * of max_batch crops, the hand-over workspace of the persistent GEMM.  All 0 for mode 0 and for max_batch < 3.  workspace_bytes is an
+ * UPPER BOUND: the workspace is allocated on devices with 256 compute units only, elsewhere the engine allocates none (0 bytes) and
+ * runs the per-tile kernels.  No GPU needed. */
 int thmr_mode_bytes(const thmr_config* cfg, int32_t vit_gemm_mode, size_t* split_weight_bytes, size_t* split_act_bytes, size_t* workspace_bytes);
 
 /* Enumerate the checkpoint contract the engine expects (name + element count), index = 0..count-1.
@@ -185,6 +187,40 @@ int thmr_engine_status(thmr_engine* e, void* stream);
 /* Diagnostics: with THMR_DEC_TIMELINE=1 in the environment at thmr_finalize_weights, workgroup 0 of the persistent decoder kernel
  * stamps the 100 MHz wall clock after every step and barrier of the last call; this copies up to max_stamps (<= 240) of them. */
 int thmr_debug_decoder_timeline(thmr_engine* e, uint64_t* stamps_host, int32_t max_stamps, void* stream);
+
+/* Diagnostics: which kernel and which K split every ViT GEMM (and the decoder's to_kv GEMM) of a B-crop call runs with — the very
+ * function the engine evaluates at the top of each call (csrc/vit_plan.h), for an engine of this config in `vit_gemm_mode` (0 / 1) whose
+ * weights are finalized.  streams_available: non-zero = the device has 256 CUs, the config has no THMR_CFG_NO_PERSISTENT and no hand-over
+ * timeout was recovered (the tile streams exist); the flag in cfg turns it off by itself.  The SPLIT FACTORS (ksplit of proj / fc2) fix
+ * the association of the K sums, i.e. the bits, and depend on mode and B only; the KINDS are decompositions of the same sums (time only).
+ * B outside [1, max_batch], a bad mode or a null `out`: THMR_ERR_INVALID.  No GPU needed. */
+typedef enum {
+    THMR_GEMM_F32_TILE = 0,         /* exact-fp32 MFMA, one workgroup per tile (launch_gemm's cost model picks the tile) */
+    THMR_GEMM_F32_TILE_SPLITK,      /* ... K split `ksplit` ways into partial planes, summed by the residual + LayerNorm kernel */
+    THMR_GEMM_F32_RING,             /* 64x64 tiles on the LDS-DMA ring (few crops), `ksplit` ways */
+    THMR_GEMM_F32_RING16,           /* 64x48 tiles of 16x16x4 MFMAs (qkv of one and two crops) */
+    THMR_GEMM_S3_TILE,              /* split3 on the bf16 matrix pipe, one workgroup per tile (incl. the launcher's mixed grid with half tiles) */
+    THMR_GEMM_S3_TILE_SPLITK,       /* ... `ksplit` copies of the grid writing partial planes */
+    THMR_GEMM_S3_STREAM_WIDE,       /* 256 persistent workgroups over the 128 x 256 tile stream */
+    THMR_GEMM_S3_STREAM_NARROW,     /* ... over the 128 x 128 tile stream (three-stage ring) */
+    THMR_GEMM_S3_SPLITK_STREAM,     /* split K with (tile, K slice) units through the 128 x 128 stream */
+    THMR_GEMM_S3_RING               /* experiments library only: the ring kernel on split3 operands */
+} thmr_gemm_kind;
+enum { THMR_VIT_PATH_F32 = 0, THMR_VIT_PATH_SPLIT3 = 1, THMR_VIT_PATH_SPLIT3_SMALL = 2 /* experiments library only */ };
+enum { THMR_ATTN_F32 = 0, THMR_ATTN_F32_KEYSPLIT = 1, THMR_ATTN_F32_SPLIT3_OUT = 2, THMR_ATTN_B16 = 3 };
+typedef struct thmr_gemm_choice {
+    int32_t kind;               /* thmr_gemm_kind */
+    int32_t ksplit;             /* 1 = unsplit */
+} thmr_gemm_choice;
+typedef struct thmr_vit_plan_desc {
+    int32_t path;               /* THMR_VIT_PATH_*: which block loop runs (buffers and LayerNorm kernels differ) */
+    thmr_gemm_choice patch, qkv, proj, fc1, fc2, to_kv;
+    int32_t attn;               /* THMR_ATTN_* */
+    int32_t bs_blk;             /* 1: fc1 writes fc2's operand in the row-blocked form (fc2 on the 128 x 256 stream) */
+    int32_t part2_in_scratch;   /* 1: fc2's partial planes live in the scratch arena (3-4 crops), 0: behind the engine's operand buffers */
+    int32_t tile_opts;          /* GemmArgs::tile_opts of the split3 GEMMs (0 in the shipped library) */
+} thmr_vit_plan_desc;
+int thmr_debug_vit_plan(const thmr_config* cfg, int32_t vit_gemm_mode, int32_t B, int32_t streams_available, thmr_vit_plan_desc* out);
 
 /* Sub-paths (configs 2 of BASELINE.json and unit parity). */
 int thmr_vit_forward(thmr_engine* e, const float* img_dev, int32_t B, float* feats_dev /*(B,192,1280)*/, void* stream);

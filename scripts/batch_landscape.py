@@ -1,5 +1,6 @@
 """Full path at EVERY batch size of a range, one engine, default mode: ms per call, crops/s and the per-class profile of one call — where the
-tile / round quantisation of the GEMMs still shows (round 6: which sizes take which decomposition is in csrc/engine.hip, vit_forward).
+tile / round quantisation of the GEMMs still shows (round 6: which sizes take which decomposition is decided by plan_vit in csrc/vit_plan.h;
+thmr_debug_vit_plan reports it without a GPU).
     python scripts/batch_landscape.py [lo=1] [hi=40] [iters=10]      (THMR_LIB=exp + knobs for an A/B of a rule)"""
 import json
 import os

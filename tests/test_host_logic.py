@@ -677,3 +677,101 @@ def test_split3_handover_epoch_protocol_model():
 
     assert sum(run("flags01", s) for s in range(20)) > 0          # the model reproduces round 4's hazard ...
     assert all(run("epoch", s) == 0 for s in range(200))          # ... and an epoch flag cannot admit a slab of another launch
+
+
+# ---- the ViT's per-batch GEMM dispatch (csrc/vit_plan.h) through thmr_debug_vit_plan: no GPU needed ----
+def _vit_plan(lib, mode, B, streams=1, max_batch=128, flags=0):
+    cc = _cabi.Config(abi_version=_cabi.ABI_VERSION, vit_depth=32, dec_depth=6, max_batch=max_batch, device=0, flags=flags)
+    d = _cabi.VitPlanDesc()
+    assert lib.thmr_debug_vit_plan(C.byref(cc), mode, B, streams, C.byref(d)) == 0, lib.thmr_last_error(None)
+    return d
+
+
+def _kind(choice):
+    return _cabi.GEMM_KINDS[choice.kind]
+
+
+def test_vit_plan_split_factors_are_one_per_batch_range(built_lib):
+    """The split factors of proj / fc2 fix the association of the K sums, i.e. the bits: ONE factor per range of batch sizes (the ranges of
+    tests/test_gpu_model.py::test_batch_regimes_agree and its REGIME_BATCHES comment), whatever decomposition runs them — so they may not
+    depend on whether the tile streams are available, nor on THMR_CFG_NO_PERSISTENT."""
+    def split3_expected(B):      # (path, proj, fc2): 1-2 exact-fp32 path | 3-4 | 5-15 | 16-31 | >= 32
+        return ("f32", 4, 4) if B <= 2 else ("split3", 4, 4) if B <= 4 else ("split3", 2, 2) if B <= 15 else ("split3", 1, 2) if B <= 31 else ("split3", 1, 1)
+
+    def f32_expected(B):         # 1-6 ring kernel 4 / 4 | 7-16 big tiles 2 / 2 | >= 17 unsplit
+        return ("f32", 4, 4) if B <= 6 else ("f32", 2, 2) if B <= 16 else ("f32", 1, 1)
+    for B in range(1, 129):
+        for streams, flags in ((1, 0), (0, 0), (1, _cabi.CFG_NO_PERSISTENT)):
+            d = _vit_plan(built_lib, 1, B, streams, flags=flags)
+            assert (_cabi.VIT_PATHS[d.path], d.proj.ksplit, d.fc2.ksplit) == split3_expected(B), (B, streams, flags)
+            assert d.qkv.ksplit == 1 and d.fc1.ksplit == 1 and d.patch.ksplit == 1 and d.to_kv.ksplit == 1
+            assert d.part2_in_scratch == (1 if 3 <= B <= 4 else 0), B
+            f = _vit_plan(built_lib, 0, B, streams, flags=flags)
+            assert (_cabi.VIT_PATHS[f.path], f.proj.ksplit, f.fc2.ksplit) == f32_expected(B), (B, streams, flags)
+            # the kernels of the exact-fp32 path belong to its regimes too (their K sums / key sums are associated differently); one and two
+            # crops run them in either mode
+            for p in (f, d) if B <= 2 else (f,):
+                assert _kind(p.proj) == _kind(p.fc2) == ("f32_ring" if B <= 6 else "f32_tile_splitk" if B <= 16 else "f32_tile"), B
+                assert _kind(p.qkv) == ("f32_ring16" if B <= 2 else "f32_tile") and _kind(p.fc1) == ("f32_ring" if B <= 2 else "f32_tile"), B
+                assert _cabi.ATTN_KINDS[p.attn] == ("f32_keysplit" if B <= 2 else "f32"), B
+                assert _kind(p.patch) == _kind(p.to_kv) == "f32_tile" and p.bs_blk == 0
+            if B >= 3:
+                assert _cabi.ATTN_KINDS[d.attn] == "b16" and _kind(d.patch) == "s3_tile" and _kind(d.to_kv) == "s3_tile", B
+    # an engine that can never reach the mode (max_batch < 3) builds nothing for it: every size on the exact-fp32 path
+    assert _cabi.VIT_PATHS[_vit_plan(built_lib, 1, 2, max_batch=2).path] == "f32"
+
+
+def test_vit_plan_decompositions_are_the_measured_ones(built_lib):
+    """The decompositions decide only time; the cases are the ones DESIGN §3.1 names with their measurements (256 CUs, streams available,
+    default knobs).  Without the streams every split3 GEMM runs one workgroup per tile and fc1 -> fc2's operand stays row-major."""
+    plan = {B: _vit_plan(built_lib, 1, B) for B in range(3, 129)}
+    # qkv: the 128 x 128 stream at 6 / 8 / 12 / 13 crops (it loses at 10: wide rounds 88 % full; and at 64), the 128 x 256 stream at 14 / 16 / 24
+    assert [_kind(plan[B].qkv) for B in (6, 8, 12, 13)] == ["s3_stream_narrow"] * 4
+    assert [_kind(plan[B].qkv) for B in (10, 64)] == ["s3_tile"] * 2
+    assert [_kind(plan[B].qkv) for B in (14, 16, 24)] == ["s3_stream_wide"] * 3
+    # fc1: the 128 x 128 stream at 5 / 6 / 9 / 10 (loses at 8: 94 % full), the 128 x 256 stream above two badly filled rounds (17 / 18; 12: +0.16)
+    assert [_kind(plan[B].fc1) for B in (5, 6, 9, 10)] == ["s3_stream_narrow"] * 4
+    assert [_kind(plan[B].fc1) for B in (17, 18)] == ["s3_stream_wide"] * 2
+    assert [_kind(plan[B].fc1) for B in (8, 12, 64)] == ["s3_tile"] * 3
+    # split K through the stream: proj / fc2 at 9 / 10 crops, fc2 at 18 / 20
+    assert [(_kind(plan[B].proj), _kind(plan[B].fc2)) for B in (9, 10)] == [("s3_splitk_stream", "s3_splitk_stream")] * 2
+    assert [_kind(plan[B].fc2) for B in (18, 20)] == ["s3_splitk_stream"] * 2
+    # fc2 on the 128 x 256 stream with the row-blocked operand, ragged M included (35, 39); 32 crops (240 tiles: under one round) per tile
+    assert [(_kind(plan[B].fc2), plan[B].bs_blk) for B in (35, 39, 64)] == [("s3_stream_wide", 1)] * 3
+    assert (_kind(plan[32].fc2), plan[32].bs_blk) == ("s3_tile", 0)
+    for B, d in plan.items():
+        assert _kind(d.proj) in ("s3_tile", "s3_tile_splitk", "s3_splitk_stream"), B
+        assert d.proj.ksplit > 1 or _kind(d.proj) == "s3_tile", B                 # never on a stream when unsplit
+        assert d.bs_blk == (1 if _kind(d.fc2) == "s3_stream_wide" else 0), B
+        for streams, flags in ((0, 0), (1, _cabi.CFG_NO_PERSISTENT)):
+            n = _vit_plan(built_lib, 1, B, streams, flags=flags)
+            assert {_kind(c) for c in (n.patch, n.qkv, n.proj, n.fc1, n.fc2, n.to_kv)} <= {"s3_tile", "s3_tile_splitk"} and n.bs_blk == 0, (B, streams, flags)
+
+
+def test_vit_plan_rejects_bad_arguments(built_lib):
+    cc = _cabi.Config(abi_version=_cabi.ABI_VERSION, vit_depth=32, dec_depth=6, max_batch=8, device=0)
+    d = _cabi.VitPlanDesc()
+    for mode, B, out in ((1, 0, C.byref(d)), (1, 9, C.byref(d)), (1, -1, C.byref(d)), (2, 4, C.byref(d)), (-1, 4, C.byref(d)), (1, 4, None)):
+        assert built_lib.thmr_debug_vit_plan(C.byref(cc), mode, B, 1, out) == -1, (mode, B)
+        assert built_lib.thmr_last_error(None)
+    cc.abi_version = 99
+    assert built_lib.thmr_debug_vit_plan(C.byref(cc), 1, 4, 1, C.byref(d)) == -1
+    assert built_lib.thmr_debug_vit_plan(None, 1, 4, 1, C.byref(d)) == -1
+
+
+def test_vit_plan_query_and_knobs_share_one_function(built_lib, monkeypatch):
+    """The experiments library reads its knobs when the query is called (as thmr_create does for an engine): THMR_SPLIT3_PN_MASK=0 turns
+    the 128 x 128-stream cases per-tile — except qkv at 12 / 13 crops, whose 270 / 300 tiles of 128 x 256 (53 / 59 % of two rounds) then meet
+    DESIGN §3.1's next rule, "the 128 x 256 stream where its grid is >= 256 tiles and <= 72 % full", exactly as the rules did before they
+    moved into vit_plan.h.  The shipped library ignores the variable."""
+    exp = _cabi.load(exp=True)
+    cases = [("qkv", B) for B in (6, 8, 12, 13)] + [("fc1", B) for B in (5, 6, 9, 10)]
+    for name, B in cases:
+        assert _kind(getattr(_vit_plan(exp, 1, B), name)) == "s3_stream_narrow", (name, B)
+    monkeypatch.setenv("THMR_SPLIT3_PN_MASK", "0")
+    for name, B in cases:
+        assert _kind(getattr(_vit_plan(exp, 1, B), name)) == ("s3_stream_wide" if (name, B) in (("qkv", 12), ("qkv", 13)) else "s3_tile"), (name, B)
+        assert _kind(getattr(_vit_plan(built_lib, 1, B), name)) == "s3_stream_narrow", (name, B)
+    for B in (9, 10):      # mask bit 3: split K through the stream
+        assert _kind(_vit_plan(exp, 1, B).fc2) == "s3_tile_splitk" and _kind(_vit_plan(built_lib, 1, B).fc2) == "s3_splitk_stream"
+        assert _vit_plan(exp, 1, B).fc2.ksplit == 2

@@ -81,6 +81,22 @@ class SheetDesc(C.Structure):
                 ("nrow", C.c_int32), ("padding", C.c_int32), ("canvas_width", C.c_int32), ("canvas_height", C.c_int32)]
 
 
+class GemmChoice(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("ksplit", C.c_int32)]
+
+
+# thmr_gemm_choice.kind / thmr_vit_plan_desc.path / .attn (header: THMR_GEMM_*, THMR_VIT_PATH_*, THMR_ATTN_*)
+GEMM_KINDS = ["f32_tile", "f32_tile_splitk", "f32_ring", "f32_ring16", "s3_tile", "s3_tile_splitk", "s3_stream_wide", "s3_stream_narrow",
+              "s3_splitk_stream", "s3_ring"]
+VIT_PATHS = ["f32", "split3", "split3_small"]
+ATTN_KINDS = ["f32", "f32_keysplit", "f32_split3_out", "b16"]
+
+
+class VitPlanDesc(C.Structure):
+    _fields_ = [("path", C.c_int32)] + [(n, GemmChoice) for n in ("patch", "qkv", "proj", "fc1", "fc2", "to_kv")] + \
+               [("attn", C.c_int32), ("bs_blk", C.c_int32), ("part2_in_scratch", C.c_int32), ("tile_opts", C.c_int32)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
@@ -128,9 +144,9 @@ def load(exp=None):
         pass
     lib = C.CDLL(path)
     older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
-    # a build loaded by path may also predate thmr_renderer_sheet (added without an ABI change: a new symbol, no layout touched)
+    # a build loaded by path may also predate thmr_renderer_sheet / thmr_debug_vit_plan (added without an ABI change: new symbols, no layout touched)
     missing = [s for s in declared_symbols() if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
-               and not (isinstance(exp, str) and s == "thmr_renderer_sheet")]
+               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan"))]
     if missing:
         raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -152,6 +168,8 @@ def load(exp=None):
     lib.thmr_forward.argtypes = [vp, vp, i32, C.POINTER(Outputs), vp]
     lib.thmr_engine_status.argtypes = [vp, vp]
     lib.thmr_debug_decoder_timeline.argtypes = [vp, C.POINTER(C.c_uint64), i32, vp]
+    if hasattr(lib, "thmr_debug_vit_plan"):
+        lib.thmr_debug_vit_plan.argtypes = [C.POINTER(Config), i32, i32, i32, C.POINTER(VitPlanDesc)]
     lib.thmr_vit_forward.argtypes = [vp, vp, i32, vp, vp]
     lib.thmr_head_forward.argtypes = [vp, vp, i32, C.POINTER(Outputs), vp]
     lib.thmr_lbs_forward.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]

@@ -380,7 +380,7 @@ int launch_gemm_split3_splitk(const GemmArgs& a, int ksplit, float* part, hipStr
 // accumulators handed over through `ws`; bit-identical to launch_gemm_split3).  mode 0 = fp32 C; 1 / 2 = split3 output (a.c_split) through the
 // LDS transposition / through swapped operand roles.  ws: gemm_split3_persist_ws_bytes() of device memory zeroed once, one launch at a time.
 size_t gemm_split3_persist_ws_bytes();
-bool gemm_split3_persist_ok(const GemmArgs& a);        // shape served by the persistent kernel (M % 128, N % 256, >= 256 tiles, no split-K)
+bool gemm_split3_persist_ok(const GemmArgs& a);        // shape served by the persistent kernel (M % 32, N % 256, >= 256 tiles, no split-K)
 int launch_gemm_split3_persist(const GemmArgs& a, int epi, int mode, void* ws, hipStream_t s);
 // round 6: the same stream over 128 x 128 tiles with the three-stage K ring (few crops: 257 ... kPersistNarrowMaxTiles tiles of 128 x 128)
 bool gemm_split3_persist_narrow_ok(const GemmArgs& a);   // N % 128, >= 256 tiles of 128 x 128 (M may be ragged), row-major A, no split-K

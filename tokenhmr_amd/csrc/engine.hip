@@ -23,43 +23,18 @@
 
 #include "../../include/tokenhmr_hip.h"
 #include "common.h"
+#include "vit_plan.h"
 
 namespace {
 
-constexpr int TOK = 192, DIM = 1280, HEADS = 16, MLP = 5120;
-constexpr int E = 1024, INNER = 512, DEC_MLP = 1024;
+constexpr int HEADS = 16;                              // TOK, DIM, MLP, INNER: vit_plan.h
+constexpr int E = 1024, DEC_MLP = 1024;
 constexpr int TN = 160, NCLS = 2048, HID = 64, HID_INTER = 256, TOK_INTER = 64, MIX = 4;
 constexpr int CODE = 256, VQW = 512, VQJ = 21;
 constexpr int NV = 6890, NJ = 24, NB = 10, NP = 207;
 constexpr float VIT_EPS = 1e-6f, LN_EPS = 1e-5f;
 constexpr float FOCAL = 5000.0f, IMG = 256.0f;
-// small-batch ViT path (gemm_ring_kernel): used while M = 192*B <= kSmallM; crossovers measured in profiles/r1_small_gemm_variants.log
-constexpr int kSmallM = 1152, kSplitKMax = 4;     // B <= 6
-constexpr int kKeysplitMaxB = 2;                  // key-split attention kernel: one and two crops
-constexpr bool kAttnB16 = true;                   // split3 mode's attention: true = attention_b16.hip (the mode's arithmetic: three bf16 pieces per operand on the bf16
-                                                  // matrix pipe; 4.03 -> 3.48 ms per 64-crop step, profiles/r4r_engine_b64_attention_b16_ab.log), false = the fp32-MFMA kernels with split3 output
-// mid-size batches: from 7 to 16 crops proj / fc2 (N = 1280: 110-240 output tiles of 128x128 on 512 resident slots) run split-K 2
-// on the big LDS-DMA tiles (measured per batch size and per GEMM, profiles/r3d_mid_batch_splitk_sweep.log, r3f_mid_batch_forced_tile.log:
-// -10 % per call at 9 and 10 crops, -2.5 ... -3.7 % at 11 ... 16, -2 % at 7 and 8 with the 64x128 tile; from 17 on the unsplit launch
-// is the faster one, and 4 ways never beats 2).  That range is its own regime of the K sum.
-constexpr int kMidLoM = 7 * 192, kMidHiM = 16 * 192, kMidSplit = 2;
-// thmr_set_vit_gemm(1): the split3 mode serves calls of kSplit3LowMinB (3) crops and more, in ranges.  From THIS many crops on the
-// N = 1280 GEMM proj runs with its K sum unsplit (128 x 256 tiles, one workgroup per CU); below it proj / fc2 split K (next constants)
-constexpr int kSplit3MinB = 16;
-// ... and 5 ... 15 crops run them with proj / fc2 split K two ways (60-120 tiles of 128 x 256 otherwise): the mode's own mid regime
-constexpr int kSplit3MidMinB = 5, kSplit3MidSplit = 2;
-// ... and 3 and 4 crops four ways (100-120 workgroups of 128 x 128 otherwise: fc2 3.3 vs 2.0 ms per call for the exact-fp32 ring kernel);
-// with them 5 / 6 crops run at 447 / 478 crops/s against 413 / 423 (profiles/r3am_split3_mid_regime_3_to_6_crops.log).  One and two
-// crops (2-3 row tiles of 128) stay with the exact-fp32 kernels.
-constexpr int kSplit3LowMinB = 3, kSplit3LowSplit = 4;
-// fc2 (K = 5120) splits K two ways up to 31 crops: 128 x 256 tiles of K = 5120 are ~400 us blocks, and halving them shortens the ragged
-// last round — op level 198 vs 229 us at 16 crops, 547 vs 666 at 40, 596 vs 741 at 48 incl. the reduce
-// (profiles/r3af_split3_n1280_tile_splitk_sweep.log); per call 702 vs 658 crops/s at 16 crops, 756 vs 707 at 48 — but 773 vs 784 at 32 and
-// 775 vs 784 at 64, whose 240 / 480 tiles fill the rounds anyway and where the LayerNorm kernel then reads two partial planes for nothing
-// (profiles/r3ag_split3_fc2_splitk_all_batches.log).  One factor per RANGE (batch invariance): split up to 31 crops, unsplit from 32 on —
-// the boundary keeps the reference README's batch of 32 at its best (784) and gives up the 7 % at 40-48 crops.
-// proj (K = 1280) splits only up to 15 crops.
-constexpr int kSplit3Fc2Split = 2, kSplit3Fc2MaxB = 31;
+// (the ViT's batch-size regimes — kSmallM, kMid*, kSplit3* — and every kernel choice that follows from them: vit_plan.h)
 // decoder + mixer stack: the persistent decoder kernel and the one-workgroup-per-crop mixer kernel win while the work is
 // latency-bound (B = 1: 0.96 vs 1.01 ms, B = 64: 1.58 vs 1.93 ms per head); from a few hundred crops on the same products are
 // real GEMMs (M = B and M = 160 B rows) and the tiled MFMA kernels win (B = 512: 6.7 vs 7.5 ms) — profiles/r2e_head_fused_vs_chain.log
@@ -107,10 +82,6 @@ struct thmr_engine {
     bool legacy_head = false;         // THMR_LEGACY_HEAD=1: force the chain-of-GEMMs head at every batch size (A/B only)
     bool mixer_cluster = true;        // THMR_MIXER_CLUSTER=0: always run the mixer stack as its own one-workgroup-per-crop kernel (A/B only)
     bool tiny_gemm = true;            // THMR_TINY_GEMM=0: the VQ decoder's GEMMs stay on the ring kernel in the small-batch regime (A/B only)
-    bool qkv_ring16 = true;           // THMR_QKV_RING16=0: one and two crops keep the 64x64 ring kernel for qkv (A/B only)
-    bool attn_keysplit = true;        // THMR_ATTN_KEYSPLIT=0: one and two crops keep the 64-query attention workgroups (A/B only)
-    bool attn_b16 = kAttnB16;         // split3 mode: the attention on the bf16 matrix pipe too (csrc/attention_b16.hip); THMR_ATTN_B16=0 / 1: A/B only
-    int mid_split_force[2] = {-1, -1};   // THMR_MID_SPLIT=<p><f> (digits 0|2|4): force the split factors of proj and fc2 above 6 crops where the partial-sum buffer allows (A/B only)
     bool smpl_loaded = false, finalized = false;
     // 1 (the DEFAULT since round 5 / ABI 4: what thmr_forward, the facade and bench.py's `value` all run): the four ViT GEMMs, the attention
     // and the decoder's to_kv GEMM of batches of at least kSplit3LowMinB (3) crops run on the bf16 matrix pipe with fp32 operands carried as
@@ -118,37 +89,14 @@ struct thmr_engine {
     // the ViT weights (1.5 x their fp32 size) and the split3 activation operands (M x (1280 + 5120) x 6 bytes).  thmr_set_vit_gemm(0) = the
     // opt-out: exact-fp32 MFMA everywhere.  An engine whose max_batch is below 3 never runs the mode and builds nothing for it.
     int vit_gemm_mode = 1;
-    bool split3_small = false;        // THMR_SPLIT3_SMALL=1: the split3 mode also serves up to six crops (ring kernel on split3 operands) — measured SLOWER, A/B only
-    int split3_fc2_split = 2;         // THMR_SPLIT3_FC2_SPLIT=1: fc2 of the split3 mode unsplit from 16 crops on (A/B only)
-    // round 6: qkv (bit 0), fc1 (bit 1) and proj (bit 2) of few-crop calls as 256 persistent workgroups over the 128 x 128 tile stream (three-stage ring) when
-    // that grid is more than one round, at most s3_pn_max tiles, and the 128 x 256 grid would fill its rounds to at most s3_pn_fill per cent (gemm_split16.hip launch_split16_persist narrow); bit-identical to the
-    // per-tile kernels.  THMR_SPLIT3_PN_MASK / THMR_SPLIT3_PN_MAX (experiments build)
-    // fc1 takes the 128 x 256 stream where its grid is MORE than two rounds and at most s3_pw_fill per cent full (17 / 18 crops: 520 / 540
-    // tiles = three rounds of time for 2.03 / 2.1 of work: fc1 -0.43 / -0.75 ms per call, profiles/r6z_*); below two rounds its GELU + split3
-    // epilogue (spills in the persistent form) loses what the rounds gain (12 crops: +0.16).  THMR_SPLIT3_PW_FC1=0: off (A/B)
-    int s3_pw_fc1 = 1;
-    int s3_pw_fill = 72;              // the 128 x 256 stream for qkv when its per-tile grid fills its rounds to at most this many per cent (THMR_SPLIT3_PW_FILL)
-    int s3_pn_fill_proj = 60;     // (proj: mask bit 2, OFF — 36-40 crops: proj -0.46 ... -0.59 ms per call, the call as a whole equal: profiles/r6x_*)
-    int s3_pn_mask = 11, s3_pn_max = 600, s3_pn_fill = 72, s3_pk_max = 1000;      // mask bit 3: split-K launches (proj / fc2 partial sums) as (tile, K slice) units, up to s3_pk_max units      // s3_pn_fill: use the stream when the 128 x 256 grid fills its rounds to at most this many per cent
-    int s3_tile_opts = 0;             // GemmArgs::tile_opts of the split3 GEMMs (THMR_SPLIT3_NARROW8=1 -> 1, THMR_SPLIT3_TAIL8=1 -> 2; A/B only)
-    int split3_min_b = 0;             // THMR_SPLIT3_MIN_B=<n>: A/B knob for the smallest batch the split3 mode serves (0 = kSplit3LowMinB)
+    VitKnobs knobs;                   // everything an A/B knob can change about the ViT / to_kv dispatch (vit_plan.h; read_knobs below)
     char* split_w = nullptr;          // split3 weight copies: shared, reference-counted, among the engines of one weight arena (split_share())
     bool split_w_counted = false;     // this engine holds a reference in split_share()
     char* split_act = nullptr;
-    // persistent split3 GEMM (csrc/gemm_split_persist.hip; bit-identical to the one-workgroup-per-tile kernel, so purely a matter of time):
-    // hand-over slabs + flags, allocated with the split3 weights on a 256-CU device.  s3_persist: 0 off / 1 on (THMR_SPLIT3_PERSIST);
-    // s3_fc1_mode: how fc1's split3 output leaves the persistent kernel — 2 swapped operand roles, 1 LDS transposition, 0 = fc1 stays on
-    // the per-tile kernel (THMR_SPLIT3_FC1_MODE)
+    // tile streams of the split3 GEMMs (csrc/gemm_split_persist.hip): hand-over slabs + flags, allocated with the split3 weights on a
+    // 256-CU device; s3_persist: run-time state, 1 until a hand-over timeout was recovered (then the per-tile kernels, same results)
     void* s3_ws = nullptr;
-    int s3_persist = 1, s3_fc1_mode = 2;
-    // Which GEMMs run the persistent decomposition: bit 0 qkv, 1 proj, 2 fc1, 3 fc2, 4 the decoder's to_kv.  It pays per tile boundary
-    // (hand-over slabs, segment bookkeeping, register spills around its epilogue) and wins the ragged last round: with the 16x16x32
-    // kernel it is the faster one for fc2 (K = 5120: 671 vs 715 us) and ties or loses at K = 1280 (qkv 518 vs 515, proj 199 vs 187,
-    // fc1 with split3 output 728 vs 702; profiles/r4k_split3_gemm_b64_mfma16.jsonl; whole path 834 vs 822 crops/s with all four,
-    // profiles/r4l_engine_b64_persist_min_k_ab.log).  Round 5, same-box interleaved, the whole path at 64 crops (profiles/r5j_ab_mask8_vs_*):
-    // + proj +0.33 ms per step (a build whose proj instantiation had NO scratch access in its K loop), + qkv +0.96 ms: at 40 K tiles per
-    // tile the hand-over costs more than the ragged round's 6 %.  Same bits either way.  THMR_SPLIT3_PERSIST_MASK (experiments build).
-    int s3_persist_mask = 8;
+    int s3_persist = 1;
     bool s3_forced_once = false;      // experiments build: THMR_SPLIT3_FORCE_TIMEOUT=1 was honoured already
     struct SplitW { const char *qkv, *proj, *fc1, *fc2; };
     std::vector<SplitW> vitw_s;
@@ -463,152 +411,86 @@ GemmArgs mk(const float* A, int64_t lda, const float* W, int64_t ldw, const floa
     return a;
 }
 
-int launch_decoder_serialised(thmr_engine* e, const DecParams& d, hipStream_t st);   // below (turnstile of the persistent kernels)
-int launch_split3_persist_serialised(thmr_engine* e, const GemmArgs& a, int epi, int mode, hipStream_t st);
+// the call's plan (vit_plan.h): a few dozen integer operations, evaluated per call — s3_persist changes at run time (a recovered timeout)
+VitPlan plan_of(const thmr_engine* e, int B) {
+    VitPlanIn in{};
+    in.mode = e->vit_gemm_mode; in.B = B; in.dec_depth = e->dec_depth;
+    in.split_ready = e->split_w && e->split_act && e->pe_s && e->kv_s;
+    in.streams = e->s3_ws != nullptr && e->s3_persist;
+    in.part_floats = e->so.part_floats;
+    return plan_vit(e->knobs, in);
+}
+
+// one GEMM as the plan chose it; `part`: the partial planes of a split-K choice
+int run_gemm(thmr_engine* e, GemmChoice c, const GemmArgs& a, int epi, float* part, hipStream_t st) {
+    switch (c.kind) {
+        case THMR_GEMM_F32_TILE: return launch_gemm(a, epi, -1, st);
+        case THMR_GEMM_F32_TILE_SPLITK: return launch_gemm_splitk(a, -1, c.ksplit, part, st);
+        case THMR_GEMM_F32_RING: return launch_gemm_ring(a, epi, 4, c.ksplit, c.ksplit > 1 ? part : nullptr, st);
+        case THMR_GEMM_F32_RING16: return launch_gemm_ring16(a, epi, st);
+        case THMR_GEMM_S3_TILE: return launch_gemm_split3(a, epi, -1, st);
+        case THMR_GEMM_S3_TILE_SPLITK: return launch_gemm_split3_splitk(a, c.ksplit, part, st);
+        case THMR_GEMM_S3_STREAM_WIDE: return launch_gemm_split3_persist(a, epi, a.c_split ? 2 : 0, e->s3_ws, st);   // split3 output: swapped operand roles
+        case THMR_GEMM_S3_STREAM_NARROW: return launch_gemm_split3_persist_narrow(a, epi, e->s3_ws, st);
+        case THMR_GEMM_S3_SPLITK_STREAM: return launch_gemm_split3_splitk_stream(a, c.ksplit, part, e->s3_ws, st);
+#ifdef THMR_EXPERIMENTS
+        case THMR_GEMM_S3_RING: return launch_gemm_split3_ring(a, epi, c.ksplit, c.ksplit > 1 ? part : nullptr, st);
+#endif
+    }
+    return -1;
+}
 
 // ---------------------------------------------------------------------------------------------- ViT-H
 int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipStream_t st) {
     const int M = B * TOK;
+    const VitPlan plan = plan_of(e, B);
     float* x = e->S(e->so.x);
     float* h = e->S(e->so.h);
     float* big = e->S(e->so.big);
-    const bool s3_on = e->vit_gemm_mode == 1 && B >= (e->split3_min_b > 0 ? e->split3_min_b : kSplit3LowMinB) && e->split_w && e->split_act;
+    float* part = e->S(e->so.part);      // split-K partial sums of proj / fc2, reduced inside the residual + LayerNorm kernel that follows them anyway
     {   // patch embed: crop + pad + im2col, then GEMM (+bias, +pos_embed)   vit.py:341,170-176,327
         ProfScope ps(e, st, THMR_PROF_PATCH, 2.0 * M * 768.0 * DIM,
                      4.0 * (B * 3.0 * 256 * 192 + (double)M * DIM + 768.0 * DIM));
-        if (s3_on && e->pe_s) {
+        if (plan.path == THMR_VIT_PATH_SPLIT3) {
             // default mode: the im2col operand written as three bf16 pieces (into the idle fc1 -> fc2 operand buffer) and the Conv2d as a
             // split3 product on the bf16 matrix pipe with the same bias + pos_embed epilogue (0.23 -> ~0.13 ms at 64 crops)
             char* ims = e->split_act + (size_t)M * DIM * 6;
             LAUNCH_OK(launch_im2col_patch_split3(img, ims, B, st));
             GemmArgs a = mk(reinterpret_cast<const float*>(ims), 768, reinterpret_cast<const float*>(e->pe_s), 768, e->hot.pe_b, e->hot.pos, 0, x, DIM, M, DIM, 768);
-            a.tile_opts = e->s3_tile_opts;
-            LAUNCH_OK(launch_gemm_split3(a, EPI_BIAS_POS, -1, st));
+            a.tile_opts = plan.tile_opts;
+            LAUNCH_OK(run_gemm(e, plan.patch, a, EPI_BIAS_POS, nullptr, st));
         } else {
             LAUNCH_OK(launch_im2col_patch(img, big, B, st));
             GemmArgs a = mk(big, 768, e->hot.pe_w, 768, e->hot.pe_b, e->hot.pos, 0, x, DIM, M, DIM, 768);
-            LAUNCH_OK(launch_gemm(a, EPI_BIAS_POS, -1, st));
+            LAUNCH_OK(run_gemm(e, plan.patch, a, EPI_BIAS_POS, nullptr, st));
         }
     }
     const float qscale = 1.0f / sqrtf(80.0f);   // head_dim ** -0.5  (vit.py:101)
-    // Few crops (M <= kSmallM): the N = 1280 GEMMs run split-K on the 64x64 ring kernel and their partial sums are reduced
-    // inside the residual + LayerNorm kernel that follows them anyway; qkv / fc1 use the ring kernel up to M = 384.
-    const bool small = M <= kSmallM, ring_wide = M <= 384;
-    // one split factor for the whole regime, so a crop's result does not depend on how many crops share its batch (B <= 6)
-    const int ks_proj = kSplitKMax, ks_fc2 = kSplitKMax;
-    float* part = e->S(e->so.part);
-    // mid-size batches (7 ... 16 crops): proj / fc2 split K two ways on the big tiles, reduced by the same residual + LayerNorm
-    // kernel; ONE factor for the whole range and both GEMMs, so a crop's result does not depend on the batch it rides in within it
-    auto pick = [&](int forced, int rule) {
-        int sp = small ? 1 : forced >= 0 ? (forced > 1 ? forced : 1) : rule;
-        if ((size_t)sp * M * DIM > e->so.part_floats) sp = 1;      // only reachable with the A/B knob
-        return sp;
-    };
-    const int rule = (M >= kMidLoM && M <= kMidHiM) ? kMidSplit : 1;
-    const int mid_proj = pick(e->mid_split_force[0], rule), mid_fc2 = pick(e->mid_split_force[1], rule);
-    // x += Linear(A) + bias;  y = LayerNorm(x)      (vit.py:149 / :150 followed by the next norm)
-    auto resid_linear_ln = [&](int cls, const float* A, int K, const float* Wt, const float* bias, int ks, int mid_split, const float* g,
-                               const float* bt, float* y) -> int {
-        const double fl = 2.0 * M * DIM * (double)K, by = 4.0 * ((double)M * K + (double)DIM * K + 2.0 * M * DIM);
-        if (small) {
-            {
-                ProfScope ps(e, st, cls, fl, by);
-                GemmArgs a = mk(A, K, Wt, K, nullptr, nullptr, 0, x, DIM, M, DIM, K);
-                LAUNCH_OK(launch_gemm_ring(a, EPI_NONE, 4, ks, part, st));
-            }
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks + 3.0) * M * DIM);
-            LAUNCH_OK(launch_splitk_resid_ln(part, ks, M, DIM, bias, x, x, g, bt, y, VIT_EPS, st));
-        } else if (mid_split > 1) {
-            {
-                ProfScope ps(e, st, cls, fl, by);
-                GemmArgs a = mk(A, K, Wt, K, nullptr, nullptr, 0, x, DIM, M, DIM, K);
-                LAUNCH_OK(launch_gemm_splitk(a, -1, mid_split, part, st));
-            }
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (mid_split + 3.0) * M * DIM);
-            LAUNCH_OK(launch_splitk_resid_ln(part, mid_split, M, DIM, bias, x, x, g, bt, y, VIT_EPS, st));
-        } else {
-            {
-                ProfScope ps(e, st, cls, fl, by);
-                GemmArgs a = mk(A, K, Wt, K, bias, x, DIM, x, DIM, M, DIM, K);
-                LAUNCH_OK(launch_gemm(a, EPI_BIAS_RESID, -1, st));
-            }
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 8.0 * M * DIM);
-            LAUNCH_OK(launch_layernorm(x, g, bt, y, M, DIM, VIT_EPS, 0, st));
-        }
-        return 0;
-    };
     const float* lastn_w = e->hot.lastn_w;
     const float* lastn_b = e->hot.lastn_b;
-    if (s3_on) {
-        // 3 ... 4 / 5 ... 15 crops: proj / fc2 split K four / two ways into `part`, reduced (in a fixed order) by the residual + LayerNorm kernel,
-        // as in the exact-fp32 path's regimes; 16 ... 31: only fc2 (two ways); 32 and more: unsplit.  One factor per range: a crop's result is
-        // batch-independent within it.
-        const bool s3_low = B < kSplit3MidMinB;                  // 3 and 4 crops: both N = 1280 GEMMs four ways
-        const int s3_split = s3_low ? kSplit3LowSplit : B < kSplit3MinB ? kSplit3MidSplit : 1;
-        const int s3_fc2 = s3_low ? kSplit3LowSplit : B <= kSplit3Fc2MaxB ? e->split3_fc2_split : 1;
-        // fc2's partial sums: the engine-owned planes behind the operand buffers (two planes for any batch size); the four planes of
-        // 3 and 4 crops fit the scratch arena's `part` (4 x 1152 rows)
-        float* part2 = s3_low ? part : reinterpret_cast<float*>(e->split_act + (size_t)e->max_batch * TOK * (DIM + MLP) * 6);
+    if (plan.path == THMR_VIT_PATH_SPLIT3) {
+        const int ks_proj = plan.proj.ksplit, ks_fc2 = plan.fc2.ksplit;
+        float* part2 = plan.part2_in_scratch ? part : reinterpret_cast<float*>(e->split_act + (size_t)e->max_batch * TOK * (DIM + MLP) * 6);
         // The four GEMMs as split3 products on the bf16 matrix pipe (csrc/gemm_split.hip); everything else — patch embed, attention,
         // LayerNorm arithmetic, epilogues — is the fp32 path's.  A operands: the LayerNorms, the attention kernel and fc1's GELU epilogue
         // write their results directly as three bf16 pieces (hs, bs): no conversion pass, no fp32 copy of those activations.
         char* hs = e->split_act;                                    // [M][1280] split3: LayerNorm / attention output
         char* bs = e->split_act + (size_t)M * DIM * 6;              // [M][5120] split3: GELU output
-        // fc1's output = fc2's A in the ROW-BLOCKED form (common.h GemmArgs::a_blk) when fc2 runs the persistent kernel: the epilogue (one output
-        // row per lane) then writes 256-512 contiguous bytes per 16-32 lanes instead of a different line per lane (same box: 830-832 -> 846-848
-        // crops/s at 64 crops, profiles/r4h_row_blocked_ab_same_box_b64.log; with the 16x16x32 kernel fc1 718 -> 702 us and fc2 677 -> 671,
-        // r4k_split3_gemm_b64_mfma16.jsonl).  A per-tile fc2 measured SLOWER with a blocked A (778 vs 715 us) and keeps the row-major form
-        // (fewer than 32 crops, odd batches).  Same values either way.
-        int bs_blk = 0;
-        {
-            GemmArgs t1 = mk(nullptr, DIM, nullptr, DIM, nullptr, nullptr, 0, nullptr, 0, M, MLP, DIM), t2 = mk(nullptr, MLP, nullptr, MLP, nullptr, nullptr, 0, nullptr, 0, M, DIM, MLP);
-            (void)t1;
-            bs_blk = (e->s3_ws && e->s3_persist && s3_fc2 <= 1 && (e->s3_persist_mask & 8) && gemm_split3_persist_ok(t2)) ? 1 : 0;      // fc2 runs the persistent kernel
-            static const bool no_blk = [] { const char* k = thmr_knob("THMR_SPLIT3_BS_BLK"); return k && k[0] == '0'; }();      // A/B (experiments build)
-            if (no_blk) bs_blk = 0;
-        }
-        // The 128 x 128 grid is more than one round of 256 workgroups, and the 128 x 256 grid it would otherwise run fills its rounds badly:
-        // then the stream over 128 x 128 tiles wins (a K tile costs it ~1.3 us + ~10 us per launch, against 2.15 us per wide K tile and whole
-        // rounds).  Measured per class, same box (profiles/r6k_*): qkv at 6 / 12 crops (135 / 270 wide tiles, rounds 53 % full) 2.75 -> 2.13 and
-        // 4.87 -> 3.64 ms per call, fc1 at 6 / 10 crops (70 % / 59 %) 2.92 -> 2.63 and 5.10 -> 3.94; at 8 crops qkv (70 %) 2.70 -> 2.62; it
-        // LOSES where the wide rounds are full (fc1 at 8 crops, 94 %: +0.26; qkv at 10, 88 %: +0.34) and from ~700 tiles on (qkv at 16: +0.25).
-        auto narrow_stream = [&](const GemmArgs& a, int fill = 0) {
-            const long rows = (a.M + 127) / 128, t128 = rows * ((a.N + 127) / 128), wide = rows * ((a.N + 255) / 256);
-            const long rounds = (wide + 255) / 256;
-            return e->s3_ws && e->s3_persist && t128 > 256 && t128 <= e->s3_pn_max && 100 * wide <= (fill ? fill : e->s3_pn_fill) * 256 * rounds &&
-                   gemm_split3_persist_narrow_ok(a);
-        };
-        // ... and the stream over 128 x 256 tiles (round 4's persistent kernel; until round 6 fc2's only, where it wins at every size) for qkv
-        // too WHEN its one-workgroup-per-tile grid fills its rounds badly and the 128 x 128 stream above does not apply: at 64 crops (94 % full)
-        // the hand-overs cost qkv +6 %; at 24 crops its 540 tiles are 2.1 rounds = three rounds of time: 7.49 -> 6.93 ms per call, at 14 crops
-        // (315 tiles, 62 %) 5.02 -> 4.45 (profiles/r6m_*).  fc1 only above two rounds (s3_pw_fc1); not proj: measured equal or slower (+0.12 at 36)
-        auto wide_stream = [&](const GemmArgs& a, long min_tiles = 256) {
-            const long wide = (long)((a.M + 127) / 128) * ((a.N + 255) / 256), rounds = (wide + 255) / 256;
-            return e->s3_ws && e->s3_persist && wide >= min_tiles && 100 * wide <= e->s3_pw_fill * 256 * rounds && gemm_split3_persist_ok(a);
-        };
-        // split-K launches (proj / fc2 below 16 / 32 crops) through the same stream: units = (tile, K slice); taken where the grid the rule would
-        // launch fills its rounds badly — e.g. fc2 at 18 crops = 270 workgroups of 128 x 256 x (K / 2) = two rounds for 1.05 rounds of work
-        auto splitk_stream = [&](const GemmArgs& a, int ks) {
-            const long rows = (a.M + 127) / 128, units = rows * ((a.N + 127) / 128) * ks, wide = rows * ((a.N + 255) / 256) * ks;
-            const long rounds = (wide + 255) / 256;
-            GemmArgs t = a;
-            t.ksplit = ks; t.bias = nullptr; t.resid = nullptr;
-            return e->s3_ws && e->s3_persist && (e->s3_pn_mask & 8) && units > 256 && units <= e->s3_pk_max && 100 * wide <= e->s3_pn_fill * 256 * rounds &&
-                   gemm_split3_persist_narrow_ok(t);
-        };
-        auto gemm_s = [&](int cls, const char* A, int K, const char* Wt, const float* bias, const float* resid, float* C, int N, int epi, int a_blk = 0) -> int {
+        // an unsplit split3 product with an fp32 result (qkv, proj, fc2)
+        auto gemm_s = [&](int cls, GemmChoice c, const char* A, int K, const char* Wt, const float* bias, const float* resid, float* C, int N, int epi, int a_blk = 0) -> int {
             ProfScope ps(e, st, cls, 2.0 * M * (double)N * K, 6.0 * ((double)M * K + (double)N * K) + 4.0 * M * N * (resid ? 2.0 : 1.0));
             GemmArgs a = mk(reinterpret_cast<const float*>(A), K, reinterpret_cast<const float*>(Wt), K, bias, resid, N, C, N, M, N, K);
             a.qscale = qscale; a.qcols = DIM;
             a.a_blk = a_blk;
-            a.tile_opts = e->s3_tile_opts;
-            const int bit = cls == THMR_PROF_GEMM_QKV ? 1 : cls == THMR_PROF_GEMM_PROJ ? 2 : cls == THMR_PROF_GEMM_FC2 ? 8 : 0;
-            if (e->s3_ws && e->s3_persist && (e->s3_persist_mask & bit) && gemm_split3_persist_ok(a)) return launch_split3_persist_serialised(e, a, epi, 0, st);
-            if (cls == THMR_PROF_GEMM_QKV && (e->s3_pn_mask & 1) && narrow_stream(a)) return launch_gemm_split3_persist_narrow(a, epi, e->s3_ws, st);
-            // proj (unsplit from 16 crops on; K = 1280, 5 wide column tiles): only where its wide rounds are at most s3_pn_fill_proj per cent full
-            if (cls == THMR_PROF_GEMM_PROJ && (e->s3_pn_mask & 4) && narrow_stream(a, e->s3_pn_fill_proj)) return launch_gemm_split3_persist_narrow(a, epi, e->s3_ws, st);
-            if (cls == THMR_PROF_GEMM_QKV && wide_stream(a)) return launch_split3_persist_serialised(e, a, epi, 0, st);
-            return launch_gemm_split3(a, epi, -1, st);
+            a.tile_opts = plan.tile_opts;
+            return run_gemm(e, c, a, epi, nullptr, st);
+        };
+        // ... and one whose K sum is split into the planes of `dst` (proj, fc2), reduced by the residual + LayerNorm kernel
+        auto gemm_s_splitk = [&](int cls, GemmChoice c, const char* A, int K, const char* Wt, float* dst) -> int {
+            ProfScope ps(e, st, cls, 2.0 * M * DIM * (double)K, 6.0 * ((double)M * K + (double)DIM * K) + 4.0 * c.ksplit * M * DIM);
+            GemmArgs a = mk(reinterpret_cast<const float*>(A), K, reinterpret_cast<const float*>(Wt), K, nullptr, nullptr, 0, x, DIM, M, DIM, K);
+            a.tile_opts = plan.tile_opts;
+            return run_gemm(e, c, a, EPI_NONE, dst, st);
         };
         {
             ProfScope ps(e, st, THMR_PROF_LN, 0, 10.0 * M * DIM);
@@ -618,24 +500,18 @@ int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipSt
             const VitBlockW& w = e->vitw[i];
             const thmr_engine::SplitW& ws = e->vitw_s[i];
             const bool last = i + 1 == e->vit_depth;
-            LAUNCH_OK(gemm_s(THMR_PROF_GEMM_QKV, hs, DIM, ws.qkv, w.qkvb, nullptr, big, 3 * DIM, EPI_BIAS_QSCALE));
+            LAUNCH_OK(gemm_s(THMR_PROF_GEMM_QKV, plan.qkv, hs, DIM, ws.qkv, w.qkvb, nullptr, big, 3 * DIM, EPI_BIAS_QSCALE));
             {   // attention, its output written directly as proj's split3 operand
                 ProfScope ps(e, st, THMR_PROF_ATTN, 4.0 * B * HEADS * 192.0 * 192.0 * 80.0, 4.0 * (3.0 * M * DIM) + 6.0 * M * DIM);
-                if (e->attn_b16) LAUNCH_OK(launch_vit_attention_b16(big, hs, B, true, 0, st));
+                if (plan.attn == THMR_ATTN_B16) LAUNCH_OK(launch_vit_attention_b16(big, hs, B, true, 0, st));
                 else LAUNCH_OK(launch_vit_attention_split3(big, hs, B, st));
             }
-            if (s3_split > 1) {
-                {
-                    ProfScope ps(e, st, THMR_PROF_GEMM_PROJ, 2.0 * M * DIM * (double)DIM, 6.0 * ((double)M * DIM + (double)DIM * DIM) + 4.0 * s3_split * M * DIM);
-                    GemmArgs a = mk(reinterpret_cast<const float*>(hs), DIM, reinterpret_cast<const float*>(ws.proj), DIM, nullptr, nullptr, 0, x, DIM, M, DIM, DIM);
-                    a.tile_opts = e->s3_tile_opts;
-                    if (splitk_stream(a, s3_split)) LAUNCH_OK(launch_gemm_split3_splitk_stream(a, s3_split, part, e->s3_ws, st));
-                    else LAUNCH_OK(launch_gemm_split3_splitk(a, s3_split, part, st));
-                }
-                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (s3_split + 2.0) * M * DIM + 6.0 * M * DIM);
-                LAUNCH_OK(launch_splitk_resid_ln(part, s3_split, M, DIM, w.pb, x, x, w.n2w, w.n2b, reinterpret_cast<float*>(hs), VIT_EPS, st, true));
+            if (ks_proj > 1) {
+                LAUNCH_OK(gemm_s_splitk(THMR_PROF_GEMM_PROJ, plan.proj, hs, DIM, ws.proj, part));
+                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks_proj + 2.0) * M * DIM + 6.0 * M * DIM);
+                LAUNCH_OK(launch_splitk_resid_ln(part, ks_proj, M, DIM, w.pb, x, x, w.n2w, w.n2b, reinterpret_cast<float*>(hs), VIT_EPS, st, true));
             } else {
-                LAUNCH_OK(gemm_s(THMR_PROF_GEMM_PROJ, hs, DIM, ws.proj, w.pb, x, x, DIM, EPI_BIAS_RESID));
+                LAUNCH_OK(gemm_s(THMR_PROF_GEMM_PROJ, plan.proj, hs, DIM, ws.proj, w.pb, x, x, DIM, EPI_BIAS_RESID));
                 ProfScope ps(e, st, THMR_PROF_LN, 0, 10.0 * M * DIM);
                 LAUNCH_OK(launch_layernorm_split3(x, w.n2w, w.n2b, hs, M, DIM, VIT_EPS, st));
             }
@@ -643,32 +519,20 @@ int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipSt
                 ProfScope ps(e, st, THMR_PROF_GEMM_FC1, 2.0 * M * DIM * (double)MLP, 6.0 * ((double)M * DIM + (double)DIM * MLP + (double)M * MLP));
                 GemmArgs a = mk(reinterpret_cast<const float*>(hs), DIM, reinterpret_cast<const float*>(ws.fc1), DIM, w.f1b, nullptr, 0, nullptr, 0, M, MLP, DIM);
                 a.c_split = bs; a.ldcs = MLP;
-                a.cs_blk = bs_blk;
-                a.tile_opts = e->s3_tile_opts;
-                if (e->s3_ws && e->s3_persist && e->s3_fc1_mode && ((e->s3_persist_mask & 4) || (e->s3_pw_fc1 && wide_stream(a, 512))) && gemm_split3_persist_ok(a))
-                    LAUNCH_OK(launch_split3_persist_serialised(e, a, EPI_BIAS_GELU, 2, st));
-                else if ((e->s3_pn_mask & 2) && narrow_stream(a))
-                    LAUNCH_OK(launch_gemm_split3_persist_narrow(a, EPI_BIAS_GELU, e->s3_ws, st));
-                else
-                    LAUNCH_OK(launch_gemm_split3(a, EPI_BIAS_GELU, -1, st));
+                a.cs_blk = plan.bs_blk;
+                a.tile_opts = plan.tile_opts;
+                LAUNCH_OK(run_gemm(e, plan.fc1, a, EPI_BIAS_GELU, nullptr, st));
             }
-            if (s3_fc2 > 1) {
-                {
-                    ProfScope ps(e, st, THMR_PROF_GEMM_FC2, 2.0 * M * DIM * (double)MLP, 6.0 * ((double)M * MLP + (double)DIM * MLP) + 4.0 * s3_fc2 * M * DIM);
-                    GemmArgs a = mk(reinterpret_cast<const float*>(bs), MLP, reinterpret_cast<const float*>(ws.fc2), MLP, nullptr, nullptr, 0, x, DIM, M, DIM, MLP);
-                    a.a_blk = bs_blk;
-                    a.tile_opts = e->s3_tile_opts;
-                    if (!a.a_blk && splitk_stream(a, s3_fc2)) LAUNCH_OK(launch_gemm_split3_splitk_stream(a, s3_fc2, part2, e->s3_ws, st));
-                    else LAUNCH_OK(launch_gemm_split3_splitk(a, s3_fc2, part2, st));
-                }
-                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (s3_fc2 + 3.0) * M * DIM);
+            if (ks_fc2 > 1) {
+                LAUNCH_OK(gemm_s_splitk(THMR_PROF_GEMM_FC2, plan.fc2, bs, MLP, ws.fc2, part2));
+                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks_fc2 + 3.0) * M * DIM);
                 if (last)
-                    LAUNCH_OK(launch_splitk_resid_ln(part2, s3_fc2, M, DIM, w.f2b, x, x, lastn_w, lastn_b, feats_out ? feats_out : h, VIT_EPS, st));
+                    LAUNCH_OK(launch_splitk_resid_ln(part2, ks_fc2, M, DIM, w.f2b, x, x, lastn_w, lastn_b, feats_out ? feats_out : h, VIT_EPS, st));
                 else
-                    LAUNCH_OK(launch_splitk_resid_ln(part2, s3_fc2, M, DIM, w.f2b, x, x, e->vitw[i + 1].n1w, e->vitw[i + 1].n1b,
+                    LAUNCH_OK(launch_splitk_resid_ln(part2, ks_fc2, M, DIM, w.f2b, x, x, e->vitw[i + 1].n1w, e->vitw[i + 1].n1b,
                                                      reinterpret_cast<float*>(hs), VIT_EPS, st, true));
             } else {
-                LAUNCH_OK(gemm_s(THMR_PROF_GEMM_FC2, bs, MLP, ws.fc2, w.f2b, x, x, DIM, EPI_BIAS_RESID, bs_blk));
+                LAUNCH_OK(gemm_s(THMR_PROF_GEMM_FC2, plan.fc2, bs, MLP, ws.fc2, w.f2b, x, x, DIM, EPI_BIAS_RESID, plan.bs_blk));
                 ProfScope ps(e, st, THMR_PROF_LN, 0, 10.0 * M * DIM);
                 if (last) LAUNCH_OK(launch_layernorm(x, lastn_w, lastn_b, feats_out ? feats_out : h, M, DIM, VIT_EPS, 0, st));
                 else LAUNCH_OK(launch_layernorm_split3(x, e->vitw[i + 1].n1w, e->vitw[i + 1].n1b, hs, M, DIM, VIT_EPS, st));
@@ -677,13 +541,14 @@ int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipSt
         return 0;
     }
 #ifdef THMR_EXPERIMENTS
-    if (e->vit_gemm_mode == 1 && small && e->split3_small) {
+    if (plan.path == THMR_VIT_PATH_SPLIT3_SMALL) {
         // EXPERIMENT (THMR_SPLIT3_SMALL=1, off by default): a small-batch regime (up to six crops) of the split3 mode — the ring kernel
         // on split3 operands (64 x 64 tiles, 4-deep LDS-DMA ring; proj / fc2 split K four ways into `part`, reduced by the residual +
         // LayerNorm kernel as in the fp32 regime), producers writing split3 operands directly.  A wave's MFMA chain per K tile shrinks from
         // 16 x 64 to 12 x 32 cycles, but the call gets SLOWER: 4.28 vs 3.89 ms at one crop, 6.88 vs 5.84 at two, 16.3 vs 14.1 at six
         // (profiles/r3y_split3_small_batch_regime_ab.log).  At these sizes the GEMMs are bound by the bytes a CU can keep in flight
         // (three 24 KB stages) against a ~4 us loaded memory round trip, not by the matrix pipe, and split3 operands are 1.5x the bytes.
+        const int ks_proj = plan.proj.ksplit, ks_fc2 = plan.fc2.ksplit;
         char* hs = e->split_act;
         char* bs = e->split_act + (size_t)M * DIM * 6;
         auto sgemm = [&](const char* A, int K, const char* Wt, const float* bias, float* C, int N) {
@@ -701,42 +566,60 @@ int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipSt
                 ProfScope ps(e, st, THMR_PROF_GEMM_QKV, 2.0 * M * DIM * 3.0 * DIM, 6.0 * ((double)M * DIM + 3.0 * DIM * DIM) + 12.0 * M * DIM);
                 GemmArgs a = sgemm(hs, DIM, ws.qkv, w.qkvb, big, 3 * DIM);
                 a.qscale = qscale; a.qcols = DIM;
-                LAUNCH_OK(launch_gemm_split3_ring(a, EPI_BIAS_QSCALE, 1, nullptr, st));
+                LAUNCH_OK(run_gemm(e, plan.qkv, a, EPI_BIAS_QSCALE, nullptr, st));
             }
             {
                 ProfScope ps(e, st, THMR_PROF_ATTN, 4.0 * B * HEADS * 192.0 * 192.0 * 80.0, 4.0 * (3.0 * M * DIM) + 6.0 * M * DIM);
                 LAUNCH_OK(launch_vit_attention_split3(big, hs, B, st));
             }
             {
-                ProfScope ps(e, st, THMR_PROF_GEMM_PROJ, 2.0 * M * DIM * (double)DIM, 6.0 * ((double)M * DIM + (double)DIM * DIM) + 4.0 * kSplitKMax * M * DIM);
+                ProfScope ps(e, st, THMR_PROF_GEMM_PROJ, 2.0 * M * DIM * (double)DIM, 6.0 * ((double)M * DIM + (double)DIM * DIM) + 4.0 * ks_proj * M * DIM);
                 GemmArgs a = sgemm(hs, DIM, ws.proj, nullptr, x, DIM);
-                LAUNCH_OK(launch_gemm_split3_ring(a, EPI_NONE, kSplitKMax, part, st));
+                LAUNCH_OK(run_gemm(e, plan.proj, a, EPI_NONE, part, st));
             }
             {
-                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (kSplitKMax + 2.0) * M * DIM + 6.0 * M * DIM);
-                LAUNCH_OK(launch_splitk_resid_ln(part, kSplitKMax, M, DIM, w.pb, x, x, w.n2w, w.n2b, reinterpret_cast<float*>(hs), VIT_EPS, st, true));
+                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks_proj + 2.0) * M * DIM + 6.0 * M * DIM);
+                LAUNCH_OK(launch_splitk_resid_ln(part, ks_proj, M, DIM, w.pb, x, x, w.n2w, w.n2b, reinterpret_cast<float*>(hs), VIT_EPS, st, true));
             }
             {
                 ProfScope ps(e, st, THMR_PROF_GEMM_FC1, 2.0 * M * DIM * (double)MLP, 6.0 * ((double)M * DIM + (double)DIM * MLP + (double)M * MLP), (i & 3) == 0);
                 GemmArgs a = sgemm(hs, DIM, ws.fc1, w.f1b, nullptr, MLP);
                 a.c_split = bs; a.ldcs = MLP;
-                LAUNCH_OK(launch_gemm_split3_ring(a, EPI_BIAS_GELU, 1, nullptr, st));
+                LAUNCH_OK(run_gemm(e, plan.fc1, a, EPI_BIAS_GELU, nullptr, st));
             }
             {
-                ProfScope ps(e, st, THMR_PROF_GEMM_FC2, 2.0 * M * DIM * (double)MLP, 6.0 * ((double)M * MLP + (double)DIM * MLP) + 4.0 * kSplitKMax * M * DIM);
+                ProfScope ps(e, st, THMR_PROF_GEMM_FC2, 2.0 * M * DIM * (double)MLP, 6.0 * ((double)M * MLP + (double)DIM * MLP) + 4.0 * ks_fc2 * M * DIM);
                 GemmArgs a = sgemm(bs, MLP, ws.fc2, nullptr, x, DIM);
-                LAUNCH_OK(launch_gemm_split3_ring(a, EPI_NONE, kSplitKMax, part, st));
+                LAUNCH_OK(run_gemm(e, plan.fc2, a, EPI_NONE, part, st));
             }
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (kSplitKMax + 3.0) * M * DIM);
+            ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks_fc2 + 3.0) * M * DIM);
             if (last)
-                LAUNCH_OK(launch_splitk_resid_ln(part, kSplitKMax, M, DIM, w.f2b, x, x, lastn_w, lastn_b, feats_out ? feats_out : h, VIT_EPS, st));
+                LAUNCH_OK(launch_splitk_resid_ln(part, ks_fc2, M, DIM, w.f2b, x, x, lastn_w, lastn_b, feats_out ? feats_out : h, VIT_EPS, st));
             else
-                LAUNCH_OK(launch_splitk_resid_ln(part, kSplitKMax, M, DIM, w.f2b, x, x, e->vitw[i + 1].n1w, e->vitw[i + 1].n1b,
+                LAUNCH_OK(launch_splitk_resid_ln(part, ks_fc2, M, DIM, w.f2b, x, x, e->vitw[i + 1].n1w, e->vitw[i + 1].n1b,
                                                  reinterpret_cast<float*>(hs), VIT_EPS, st, true));
         }
         return 0;
     }
 #endif  // THMR_EXPERIMENTS
+    // x += Linear(A) + bias;  y = LayerNorm(x)      (vit.py:149 / :150 followed by the next norm): K split into `part` (few crops on the ring
+    // kernel, the mid range on the big tiles) and reduced by the residual + LayerNorm kernel, or unsplit with the residual in the epilogue
+    auto resid_linear_ln = [&](int cls, GemmChoice c, const float* A, int K, const float* Wt, const float* bias, const float* g, const float* bt, float* y) -> int {
+        const bool split = c.ksplit > 1;
+        {
+            ProfScope ps(e, st, cls, 2.0 * M * DIM * (double)K, 4.0 * ((double)M * K + (double)DIM * K + 2.0 * M * DIM));
+            GemmArgs a = split ? mk(A, K, Wt, K, nullptr, nullptr, 0, x, DIM, M, DIM, K) : mk(A, K, Wt, K, bias, x, DIM, x, DIM, M, DIM, K);
+            LAUNCH_OK(run_gemm(e, c, a, split ? EPI_NONE : EPI_BIAS_RESID, part, st));
+        }
+        if (split) {
+            ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (c.ksplit + 3.0) * M * DIM);
+            LAUNCH_OK(launch_splitk_resid_ln(part, c.ksplit, M, DIM, bias, x, x, g, bt, y, VIT_EPS, st));
+        } else {
+            ProfScope ps(e, st, THMR_PROF_LN, 0, 8.0 * M * DIM);
+            LAUNCH_OK(launch_layernorm(x, g, bt, y, M, DIM, VIT_EPS, 0, st));
+        }
+        return 0;
+    };
     {
         ProfScope ps(e, st, THMR_PROF_LN, 0, 8.0 * M * DIM);
         LAUNCH_OK(launch_layernorm(x, e->vitw[0].n1w, e->vitw[0].n1b, h, M, DIM, VIT_EPS, 0, st));
@@ -750,37 +633,27 @@ int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipSt
             ProfScope ps(e, st, THMR_PROF_GEMM_QKV, 2.0 * M * DIM * 3.0 * DIM, 4.0 * ((double)M * DIM + 3.0 * DIM * DIM + 3.0 * M * DIM));
             GemmArgs a = mk(h, DIM, w.qkvw, DIM, w.qkvb, nullptr, 0, big, 3 * DIM, M, 3 * DIM, DIM);
             a.qscale = qscale; a.qcols = DIM;
-            // one and two crops: 64 x 48 tiles of 16x16x4 MFMAs (240 / 480 workgroups whose waves walk 12.8 us chains) instead of 64x64
-            // tiles of 32x32x2 (180 / 360 workgroups, 17.1 us chains); another order of the K sum, hence tied to that regime
-            if (B <= kKeysplitMaxB && e->qkv_ring16) LAUNCH_OK(launch_gemm_ring16(a, EPI_BIAS_QSCALE, st));
-            else if (ring_wide) LAUNCH_OK(launch_gemm_ring(a, EPI_BIAS_QSCALE, 4, 1, nullptr, st));
-            else LAUNCH_OK(launch_gemm(a, EPI_BIAS_QSCALE, -1, st));
+            LAUNCH_OK(run_gemm(e, plan.qkv, a, EPI_BIAS_QSCALE, nullptr, st));
         }
         {
             ProfScope ps(e, st, THMR_PROF_ATTN, 4.0 * B * HEADS * 192.0 * 192.0 * 80.0, 4.0 * (4.0 * M * DIM));
-            // one or two crops: keys split over the waves of a workgroup (192 / 96 workgroups per crop instead of 48, 120 / 240 instead
-            // of 480 dependent MFMAs per wave): -3.9 % per call at one crop, -1 % at two, slower from three on, where its four-fold
-            // re-reads of K / V cost more than the shorter chain saves (profiles/r3j_attention_keysplit_ab.log).  Its own association of
-            // the key sum, hence its own regime {1, 2} inside the small-batch regime.
-            if (B <= kKeysplitMaxB && e->attn_keysplit) LAUNCH_OK(launch_vit_attention_keysplit(big, h, B, st));
+            if (plan.attn == THMR_ATTN_F32_KEYSPLIT) LAUNCH_OK(launch_vit_attention_keysplit(big, h, B, st));
             else LAUNCH_OK(launch_vit_attention(big, h, B, st));
         }
         // proj + residual, then norm2 (vit.py:123,149,150)
-        if (int rc = resid_linear_ln(THMR_PROF_GEMM_PROJ, h, DIM, w.pw, w.pb, ks_proj, mid_proj, w.n2w, w.n2b, h)) return rc;
+        if (int rc = resid_linear_ln(THMR_PROF_GEMM_PROJ, plan.proj, h, DIM, w.pw, w.pb, w.n2w, w.n2b, h)) return rc;
         {   // fc1 + exact GELU (vit.py:83-84)
             ProfScope ps(e, st, THMR_PROF_GEMM_FC1, 2.0 * M * DIM * (double)MLP, 4.0 * ((double)M * DIM + (double)DIM * MLP + (double)M * MLP), (i & 3) == 0);
             GemmArgs a = mk(h, DIM, w.f1w, DIM, w.f1b, nullptr, 0, big, MLP, M, MLP, DIM);
-            if (ring_wide) LAUNCH_OK(launch_gemm_ring(a, EPI_BIAS_GELU, 4, 1, nullptr, st));
-            else LAUNCH_OK(launch_gemm(a, EPI_BIAS_GELU, -1, st));
+            LAUNCH_OK(run_gemm(e, plan.fc1, a, EPI_BIAS_GELU, nullptr, st));
         }
         // fc2 + residual (vit.py:85,150), then the next block's norm1 — or last_norm (vit.py:335), kept token-major: the
         // :337 permute is undone by token_head.py:69
-        if (int rc = resid_linear_ln(THMR_PROF_GEMM_FC2, big, MLP, w.f2w, w.f2b, ks_fc2, mid_fc2, nxt_w, nxt_b, last && feats_out ? feats_out : h))
+        if (int rc = resid_linear_ln(THMR_PROF_GEMM_FC2, plan.fc2, big, MLP, w.f2w, w.f2b, nxt_w, nxt_b, last && feats_out ? feats_out : h))
             return rc;
     }
     return 0;
 }
-
 
 
 // ---------------------------------------------------------------------------------------------- head
@@ -859,18 +732,17 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
     const int ldkv = e->dec_depth * 2 * INNER;
     {   // K8: to_kv of all decoder layers in ONE GEMM on the un-normalised context (pose_transformer.py:102,113)
         ProfScope ps(e, st, THMR_PROF_DEC_KV, 2.0 * M * DIM * (double)ldkv, 4.0 * ((double)M * DIM + (double)ldkv * DIM + (double)M * ldkv));
-        const int s3_min = e->split3_min_b > 0 ? e->split3_min_b : kSplit3LowMinB;
-        if (e->vit_gemm_mode == 1 && B >= s3_min && e->kv_s) {
+        const VitPlan plan = plan_of(e, B);
+        if (plan.to_kv.kind != THMR_GEMM_F32_TILE) {
             // split3 mode: the context (fp32: it may be a caller's buffer) converted into the ViT's idle operand buffer, then the same product
             // on the bf16 matrix pipe (1.5 -> 1.0 ms at 64 crops)
             LAUNCH_OK(launch_split3(ctx, DIM, e->split_act, DIM, M, DIM, st));
             GemmArgs a = mk(reinterpret_cast<const float*>(e->split_act), DIM, reinterpret_cast<const float*>(e->kv_s), DIM, nullptr, nullptr, 0, big, ldkv, M, ldkv, DIM);
-            a.tile_opts = e->s3_tile_opts;
-            if (e->s3_ws && e->s3_persist && (e->s3_persist_mask & 16) && gemm_split3_persist_ok(a)) LAUNCH_OK(launch_split3_persist_serialised(e, a, EPI_NONE, 0, st));
-            else LAUNCH_OK(launch_gemm_split3(a, EPI_NONE, -1, st));
+            a.tile_opts = plan.tile_opts;
+            LAUNCH_OK(run_gemm(e, plan.to_kv, a, EPI_NONE, nullptr, st));
         } else {
             GemmArgs a = mk(ctx, DIM, e->warena + e->o_kv_all, DIM, nullptr, nullptr, 0, big, ldkv, M, ldkv, DIM);
-            LAUNCH_OK(launch_gemm(a, EPI_NONE, -1, st));
+            LAUNCH_OK(run_gemm(e, plan.to_kv, a, EPI_NONE, nullptr, st));
         }
     }
     ProfScope ps_head(e, st, THMR_PROF_HEAD, 2.0 * B * (6.0 * 4.2e6 + 116.7e6 + 167.8e6 + 705.0e6), 0);
@@ -893,7 +765,7 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
         mixer_in_decoder = d.mixer_cluster != 0;
         d.mx = e->mix;
         d.mixy[0] = cf; d.mixy[1] = cf2;
-        LAUNCH_OK(launch_decoder_serialised(e, d, st));
+        LAUNCH_OK(launch_decoder_fused(d, st));            // the caller's Turn (thmr_forward / thmr_head_forward) orders engines
     } else {
     LAUNCH_OK(launch_decoder_init(e->W(T + "to_token_embedding.bias"), e->W(T + "pos_embedding"), dx, B, E, st));
     for (int l = 0; l < e->dec_depth; ++l) {
@@ -1128,15 +1000,6 @@ struct Turn {
     ~Turn() { (void)end(); }
 };
 
-int launch_decoder_serialised(thmr_engine* e, const DecParams& d, hipStream_t st) {
-    (void)e;
-    return launch_decoder_fused(d, st);                // the caller's Turn (thmr_forward / thmr_head_forward) orders engines
-}
-
-int launch_split3_persist_serialised(thmr_engine* e, const GemmArgs& a, int epi, int mode, hipStream_t st) {
-    return launch_gemm_split3_persist(a, epi, mode, e->s3_ws, st);
-}
-
 // split3 weight copies are a pure function of the weight arena's contents: engines that SHARE an arena (thmr_create with the same
 // weight_arena_dev, e.g. several engines of one process on one GPU) share ONE copy, reference-counted (round 6, ADVICE r5: eight engines on
 // one device held 30 GB of duplicates).  Every finalize still runs the conversion into it — idempotent, the same bytes.
@@ -1252,6 +1115,40 @@ static int validate_cfg(const thmr_config* cfg) {
     return 0;
 }
 
+// the plan's knobs: their defaults in the shipped library (thmr_knob is a constant nullptr there), THMR_* environment variables in the
+// experiments build
+static VitKnobs read_knobs() {
+    VitKnobs k;
+#ifdef THMR_EXPERIMENTS
+    auto off = [](const char* name) { const char* v = thmr_knob(name); return v && v[0] == '0'; };
+    auto on = [](const char* name) { const char* v = thmr_knob(name); return v && v[0] == '1'; };
+    auto num = [](const char* name, int& dst) { if (const char* v = thmr_knob(name)) dst = atoi(v); };
+    auto digit = [](const char* name, char hi, int& dst) { const char* v = thmr_knob(name); if (v && v[0] >= '0' && v[0] <= hi) dst = v[0] - '0'; };
+    k.qkv_ring16 = !off("THMR_QKV_RING16");
+    k.attn_keysplit = !off("THMR_ATTN_KEYSPLIT");
+    if (on("THMR_ATTN_B16") || off("THMR_ATTN_B16")) k.attn_b16 = on("THMR_ATTN_B16");
+    k.split3_small = on("THMR_SPLIT3_SMALL");
+    if (on("THMR_SPLIT3_FC2_SPLIT")) k.split3_fc2_split = 1;
+    num("THMR_SPLIT3_MIN_B", k.split3_min_b);
+    k.tile_opts = (on("THMR_SPLIT3_NARROW8") ? 1 : 0) | (on("THMR_SPLIT3_TAIL8") ? 2 : 0) | (off("THMR_SPLIT3_RING3") ? 4 : 0) | (off("THMR_SPLIT3_FRONT") ? 8 : 0);
+    num("THMR_SPLIT3_PN_MASK", k.pn_mask);
+    num("THMR_SPLIT3_PN_MAX", k.pn_max);
+    num("THMR_SPLIT3_PN_FILL", k.pn_fill);
+    num("THMR_SPLIT3_PK_MAX", k.pk_max);
+    num("THMR_SPLIT3_PN_FILL_PROJ", k.pn_fill_proj);
+    num("THMR_SPLIT3_PW_FILL", k.pw_fill);
+    if (off("THMR_SPLIT3_PW_FC1")) k.pw_fc1 = 0;
+    digit("THMR_SPLIT3_PERSIST", '1', k.persist);
+    digit("THMR_SPLIT3_FC1_MODE", '2', k.fc1_mode);
+    num("THMR_SPLIT3_PERSIST_MASK", k.persist_mask);
+    k.bs_blk = !off("THMR_SPLIT3_BS_BLK");
+    if (const char* ms = thmr_knob("THMR_MID_SPLIT")) {
+        if (ms[0] && ms[1]) { k.mid_split_force[0] = ms[0] - '0'; k.mid_split_force[1] = ms[1] - '0'; }
+    }
+#endif
+    return k;
+}
+
 // bytes of the engine-owned allocations of the split3 mode (build_split_weights): weight copies, activation operands + fc2's split-K planes
 static size_t split_w_bytes_of(int vit_depth, int dec_depth) {
     const size_t per_block = (size_t)DIM * (3 * DIM) + (size_t)DIM * DIM + 2 * (size_t)DIM * MLP;      // weights of one block
@@ -1329,27 +1226,8 @@ int thmr_create(const thmr_config* cfg, void* weight_arena_dev, void* scratch_ar
     { const char* lg = thmr_knob("THMR_LEGACY_HEAD"); e->legacy_head = lg && lg[0] == '1'; }
     { const char* mc = thmr_knob("THMR_MIXER_CLUSTER"); e->mixer_cluster = !(mc && mc[0] == '0'); }
     { const char* tg = thmr_knob("THMR_TINY_GEMM"); e->tiny_gemm = !(tg && tg[0] == '0'); }
-    { const char* qr = thmr_knob("THMR_QKV_RING16"); e->qkv_ring16 = !(qr && qr[0] == '0'); }
-    { const char* ak = thmr_knob("THMR_ATTN_KEYSPLIT"); e->attn_keysplit = !(ak && ak[0] == '0'); }
-    { const char* ab = thmr_knob("THMR_ATTN_B16"); if (ab && (ab[0] == '0' || ab[0] == '1')) e->attn_b16 = ab[0] == '1'; }
-    { const char* ss = thmr_knob("THMR_SPLIT3_SMALL"); e->split3_small = ss && ss[0] == '1'; }
-    { const char* fs = thmr_knob("THMR_SPLIT3_FC2_SPLIT"); e->split3_fc2_split = (fs && fs[0] == '1') ? 1 : kSplit3Fc2Split; }
-    { const char* sm = thmr_knob("THMR_SPLIT3_MIN_B"); e->split3_min_b = sm ? atoi(sm) : 0; }
-    { const char* n8 = thmr_knob("THMR_SPLIT3_NARROW8"); if (n8 && n8[0] == '1') e->s3_tile_opts |= 1; }
-    { const char* t8 = thmr_knob("THMR_SPLIT3_TAIL8"); if (t8 && t8[0] == '1') e->s3_tile_opts |= 2; }
-    { const char* r3 = thmr_knob("THMR_SPLIT3_RING3"); if (r3 && r3[0] == '0') e->s3_tile_opts |= 4; }
-    { const char* fr = thmr_knob("THMR_SPLIT3_FRONT"); if (fr && fr[0] == '0') e->s3_tile_opts |= 8; }
-    { const char* pm = thmr_knob("THMR_SPLIT3_PN_MASK"); if (pm) e->s3_pn_mask = atoi(pm); }
-    { const char* px = thmr_knob("THMR_SPLIT3_PN_MAX"); if (px) e->s3_pn_max = atoi(px); }
-    { const char* pf = thmr_knob("THMR_SPLIT3_PN_FILL"); if (pf) e->s3_pn_fill = atoi(pf); }
-    { const char* pk = thmr_knob("THMR_SPLIT3_PK_MAX"); if (pk) e->s3_pk_max = atoi(pk); }
-    { const char* pp = thmr_knob("THMR_SPLIT3_PN_FILL_PROJ"); if (pp) e->s3_pn_fill_proj = atoi(pp); }
-    { const char* pw = thmr_knob("THMR_SPLIT3_PW_FILL"); if (pw) e->s3_pw_fill = atoi(pw); }
-    { const char* p1 = thmr_knob("THMR_SPLIT3_PW_FC1"); if (p1 && p1[0] == '0') e->s3_pw_fc1 = 0; }
-    { const char* sp = thmr_knob("THMR_SPLIT3_PERSIST"); if (sp && sp[0] >= '0' && sp[0] <= '1') e->s3_persist = sp[0] - '0'; }
-    { const char* fm = thmr_knob("THMR_SPLIT3_FC1_MODE"); if (fm && fm[0] >= '0' && fm[0] <= '2') e->s3_fc1_mode = fm[0] - '0'; }
-    { const char* mk_ = thmr_knob("THMR_SPLIT3_PERSIST_MASK"); if (mk_) e->s3_persist_mask = atoi(mk_); }
-    { const char* ms = thmr_knob("THMR_MID_SPLIT"); if (ms && ms[0] && ms[1]) { e->mid_split_force[0] = ms[0] - '0'; e->mid_split_force[1] = ms[1] - '0'; } }
+    e->knobs = read_knobs();
+    e->s3_persist = e->knobs.persist;
     if (cfg->flags & THMR_CFG_VIT_GEMM_F32) e->vit_gemm_mode = 0;      // created in the opt-out mode: finalize builds nothing for split3
     if (cfg->flags & THMR_CFG_NO_PERSISTENT) {                         // no kernel that needs all its workgroups resident at once
         e->s3_persist = 0;
@@ -1733,6 +1611,22 @@ int thmr_debug_decoder_timeline(thmr_engine* e, uint64_t* stamps_host, int32_t m
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_OK(hipMemcpyAsync(stamps_host, e->sarena + e->so.sync + 16, sizeof(uint64_t) * max_stamps, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int thmr_debug_vit_plan(const thmr_config* cfg, int32_t vit_gemm_mode, int32_t B, int32_t streams_available, thmr_vit_plan_desc* out) {
+    if (int r = validate_cfg(cfg)) return r;
+    if (vit_gemm_mode != 0 && vit_gemm_mode != 1) return fail(nullptr, THMR_ERR_INVALID, "vit gemm mode must be 0 or 1");
+    if (!out || B < 1 || B > cfg->max_batch) return fail(nullptr, THMR_ERR_INVALID, "null out / batch outside [1, max_batch]");
+    thmr_engine tmp;
+    tmp.max_batch = cfg->max_batch;
+    layout_scratch(&tmp);
+    VitPlanIn in{};
+    in.mode = vit_gemm_mode; in.B = B; in.dec_depth = cfg->dec_depth;
+    in.split_ready = vit_gemm_mode == 1 && cfg->max_batch >= kSplit3LowMinB;      // what thmr_finalize_weights builds (build_split_weights)
+    in.streams = streams_available != 0 && !(cfg->flags & THMR_CFG_NO_PERSISTENT);
+    in.part_floats = tmp.so.part_floats;
+    *out = plan_vit(read_knobs(), in);
     return 0;
 }
 
