@@ -72,7 +72,23 @@ enum {
      * the head to fp32 summation order; a few per cent slower).  For a GPU SHARED WITH ANOTHER PROCESS: there the persistent kernels can starve each other until their bounded
      * waits (~0.5 s) run out — one batch of invalid outputs, an error from the next call, then this mode anyway (thmr_engine_status).  Engines
      * of ONE process are ordered by the library itself (one turn per forward-type call) and do not need the flag. */
-    THMR_CFG_NO_PERSISTENT = 2
+    THMR_CFG_NO_PERSISTENT = 2,
+    /* The engine runs the reference's OTHER SMPL head (MODEL.SMPL_HEAD.TYPE: transformer_decoder — SMPLTransformerDecoderHead,
+     * tokenhmr/lib/models/heads/smpl_head.py:10-104: the HMR2.0 regressor, the format of the 4D-Humans checkpoints) instead of the token head:
+     * the same ViT, to_kv GEMM, one-token decoder, SMPL and projection; behind token_out three Linears 1024 -> 144 / 10 / 3 (one stacked
+     * read-out in fp32 with a fixed summation order), + the mean parameters, rot6d_to_rotmat over all 24 joints.  IEF_ITERS = 1, the zero
+     * input token and JOINT_REP 6d only.  With the flag
+     *   - thmr_spec enumerates 'backbone.*' and 'smpl_head.transformer.*' as without it, then smpl_head.decpose.{weight,bias} (144 x 1024,
+     *     144), smpl_head.decshape.*, smpl_head.deccam.*, smpl_head.init_body_pose / init_betas / init_cam — no decpose_grot / decpose_hands /
+     *     decpose.mixer_* and no tokenizer tensor; thmr_load_weights needs (and accepts) none of those; the arenas are smaller;
+     *   - thmr_forward / thmr_head_forward fill every thmr_outputs field EXCEPT cls_logits_softmax, cls_logits and token_idx: a non-NULL
+     *     pointer there is THMR_ERR_INVALID (thmr_last_error names the field); thmr_vq_argmin, thmr_vq_decode and thmr_encode_tokens
+     *     likewise.  token_out is bit-identical to a token engine's for the same 'smpl_head.transformer.*' weights and context;
+     *   - the record of thmr_pack_records keeps its layout; pass token_idx = NULL and its 160 words are zero.
+     * Up to 128 crops the head behind the to_kv GEMM is two launches (the persistent decoder kernel with the read-out as its last step, and
+     * the finish); beyond that, with THMR_CFG_NO_PERSISTENT and after a recovered barrier timeout, the launch chain (equal to fp32 summation
+     * order of the read-out).  (Bit value 4 is not assigned: ABI 5 hosts were promised that it is refused, and it still is.) */
+    THMR_CFG_HEAD_HMR2 = 8
 };
 
 /* One named tensor of the reference checkpoint contract:
@@ -458,7 +474,8 @@ int  thmr_renderer_sheet(thmr_renderer* r, const thmr_sheet_desc* desc, const fl
  * per-crop records.  `nccl_comm` is an ncclComm_t the caller created (ncclCommInitRank) with the RCCL already loaded in the process;
  * the library resolves ncclBroadcast / ncclAllGather from that copy at first use (it does not link its own).  Asynchronous on `stream`.
  *   record = [pred_vertices 20670 | pred_keypoints_3d 132 | pred_keypoints_2d 88 | rotmat 216 | betas 10 | pred_cam 3 | pred_cam_t 3 |
- *             token_idx 160 (int32 bits)] = THMR_RECORD_WORDS 32-bit words per crop (85,128 B). */
+ *             token_idx 160 (int32 bits)] = THMR_RECORD_WORDS 32-bit words per crop (85,128 B).  token_idx may be NULL (an engine with
+ *             THMR_CFG_HEAD_HMR2 has none): its 160 words are then zero; every other field is required. */
 #define THMR_RECORD_WORDS 21282
 int thmr_pack_records(const thmr_outputs* out, int32_t B, float* rec_dev /*(B, THMR_RECORD_WORDS)*/, void* stream);
 int thmr_bcast_weights(thmr_engine* e, void* nccl_comm, int32_t root, void* stream);

@@ -17,7 +17,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "tokenhmr_hip.h")
 
 ABI_VERSION = 5
 # thmr_config.flags (header: THMR_CFG_*)
-CFG_VIT_GEMM_F32, CFG_NO_PERSISTENT = 1, 2
+CFG_VIT_GEMM_F32, CFG_NO_PERSISTENT, CFG_HEAD_HMR2 = 1, 2, 8
 PROF_NAMES = ["gemm_qkv", "gemm_proj", "gemm_fc1", "gemm_fc2", "attention", "layernorm", "patch_embed",
               "dec_kv", "head", "lbs"]
 

@@ -60,6 +60,14 @@ class HMRConfig:
     n_j19: int = 19
     n_out_joints: int = 44
     focal_length: float = 5000.0
+    # which SMPL head follows the decoder (build_smpl_head, tokenhmr/lib/models/heads/__init__.py:4-13): "token" =
+    # SMPLTokenDecoderHead (TYPE: token), "hmr2" = SMPLTransformerDecoderHead (TYPE: transformer_decoder, heads/smpl_head.py:10-104:
+    # the HMR2.0 regressor — three Linears on token_out, no classifier, no tokenizer)
+    head: str = "token"
+
+    def __post_init__(self):
+        if self.head not in ("token", "hmr2"):
+            raise ValueError(f"HMRConfig.head must be 'token' or 'hmr2', got {self.head!r}")
 
     @property
     def inner(self) -> int:      # decoder attention inner dim

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void pack_records_kernel(PackSrc s, float* __r
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             if (f == i && off >= s.n[i]) { off -= s.n[i]; f = i + 1; }
-        out[w] = s.p[f][(int64_t)b * s.n[f] + off];
+        out[w] = s.p[f] ? s.p[f][(int64_t)b * s.n[f] + off] : 0.f;      // a null field (token_idx of an HMR2 engine) packs as zero words
     }
 }
 
@@ -78,8 +78,8 @@ const char* thmr_collective_last_error(void) { return g_cerr.c_str(); }
 int thmr_pack_records(const thmr_outputs* o, int32_t B, float* rec_dev, void* stream) {
     if (!o || !rec_dev || B < 1) return cfail(THMR_ERR_INVALID, "bad argument");
     if (!o->pred_vertices || !o->pred_keypoints_3d || !o->pred_keypoints_2d || !o->rotmat || !o->betas || !o->pred_cam ||
-        !o->pred_cam_t || !o->token_idx)
-        return cfail(THMR_ERR_INVALID, "thmr_pack_records needs pred_vertices, pred_keypoints_3d/2d, rotmat, betas, pred_cam, pred_cam_t and token_idx");
+        !o->pred_cam_t)
+        return cfail(THMR_ERR_INVALID, "thmr_pack_records needs pred_vertices, pred_keypoints_3d/2d, rotmat, betas, pred_cam and pred_cam_t (token_idx may be null: zero words)");
     PackSrc s;
     const float* p[8] = {o->pred_vertices, o->pred_keypoints_3d, o->pred_keypoints_2d, o->rotmat, o->betas, o->pred_cam,
                          o->pred_cam_t, reinterpret_cast<const float*>(o->token_idx)};      // indices travel bit-exactly as words

@@ -356,8 +356,18 @@ struct DecParams {
     int mixer_cluster;
 };
 
-int launch_decoder_fused(const DecParams& p, hipStream_t s);
-int decoder_max_coresident_blocks(int device);      // > 0, or negative if the kernel cannot be resident at all
+// head kinds of the persistent decoder kernel (its compile-time parameter).  HMR2: ro_w / ro_b are the stacked read-out of
+// SMPLTransformerDecoderHead (THMR_HMR2_RO_ROWS rows = decpose 144 | decshape 10 | deccam 3, zero rows up to THMR_HMR2_RO_LD), ro is
+// (B, THMR_HMR2_RO_LD); mt_w / mt_b / mt / mx / mixy are unused and mixer_cluster must be 0.
+constexpr int THMR_HEAD_TOKEN = 0, THMR_HEAD_HMR2 = 1;
+constexpr int THMR_HMR2_RO_ROWS = 157, THMR_HMR2_RO_LD = 160;
+int launch_decoder_fused(const DecParams& p, hipStream_t s, int head = THMR_HEAD_TOKEN);
+int decoder_max_coresident_blocks(int device, int head = THMR_HEAD_TOKEN);      // > 0, or negative if the kernel cannot be resident at all
+// hmr2_head.hip: the finish of the HMR2 head — ro (B, ldro) + mean parameters -> pose6d, rotation matrices (geometry.py:64-84), betas,
+// camera and its translation (tokenhmr.py:165-169); pose6d / cam_t / focal may be null
+int launch_hmr2_finish(const float* ro, int ldro, const float* init_pose, const float* init_betas, const float* init_cam, float* pose6d,
+                       float* rotmat, float* betas, float* cam, float* cam_t, float* focal, float focal_length, float img_size, int B,
+                       hipStream_t s);
 
 // ---- the MLP-Mixer stack kernel (mixer_fused.hip; parameter structs above DecParams) ----
 int launch_mixer_fused(const MixerParams& p, int B, hipStream_t s);

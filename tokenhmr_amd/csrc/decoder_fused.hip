@@ -495,10 +495,16 @@ __device__ __forceinline__ bool mixer_cluster_stage(const DecParams& p, GridSync
     return true;
 }
 
+// HEAD (compile time): what consumes the decoder output.  THMR_HEAD_TOKEN: the token head's read-outs + mixer_trans tiles and the
+// distributed mixer tail (100+ KB of LDS).  THMR_HEAD_HMR2: SMPLTransformerDecoderHead's stacked read-out (smpl_head.py:82-84:
+// decpose 144 | decshape 10 | deccam 3 rows, padded with zero rows to ten 16-column tiles) as one more GEMV step — no mixer code and
+// none of its LDS.  The decoder layers in front are the same code in both: token_out is bit-identical between the two.
+template <int HEAD>
 __global__ __launch_bounds__(NWAVE * 64) void decoder_persistent_kernel(DecParams p) {
-    __shared__ __attribute__((aligned(16))) float mixY[mixer::T * mixer::LD];      // distributed mixer tail: the crop's LayerNorm-ed rows / s
-    __shared__ __attribute__((aligned(16))) float mixU[mixer::H * mixer::LD];      // token-mixing hidden activation
-    __shared__ __attribute__((aligned(16))) float mixX[80 * mixer::LD];            // residual rows of the own token tiles (up to 5)
+    constexpr bool TOKEN = HEAD == THMR_HEAD_TOKEN;
+    __shared__ __attribute__((aligned(16))) float mixY[TOKEN ? mixer::T * mixer::LD : 4];      // distributed mixer tail: the crop's LayerNorm-ed rows / s
+    __shared__ __attribute__((aligned(16))) float mixU[TOKEN ? mixer::H * mixer::LD : 4];      // token-mixing hidden activation
+    __shared__ __attribute__((aligned(16))) float mixX[TOKEN ? 80 * mixer::LD : 4];            // residual rows of the own token tiles (up to 5)
     __shared__ float mixred[mixer::NW];
     static_assert(mixer::NW == NWAVE, "the distributed mixer tail uses the decoder kernel's 8 waves");
     __shared__ __attribute__((aligned(16))) float red[NWAVE][64][4];         // 8 KB: K-slice partial tiles (also the attention weights)
@@ -573,17 +579,24 @@ __global__ __launch_bounds__(NWAVE * 64) void decoder_persistent_kernel(DecParam
         }
         THMR_STAMP();
     }
-    if (ok) {
-        // consumers of the decoder output: the four read-outs as one (31 + zero row, 1024) matrix (token_head.py:99-105) and
-        // the classifier's first Linear 1024 -> 160*64 (token_classifier.py:71-73); 2 + 640 column tiles dealt to the workgroups
-        gemv_multi(p.dx, p.ro_w, p.ro_b, p.ro, p.mt_w, p.mt_b, p.mt, 2, 2 + 640, B, red, tid, p.mixer_cluster != 0);
+    if constexpr (!TOKEN) {
+        // the stacked read-out of token_out: 160 (157 + 3 zero) rows x 1024, bias added, into ro (B, 160); the eight K slices are
+        // summed in gemv_stage's fixed order.  The finish (mean parameters, 6D -> rotation matrices, camera) is hmr2_head.hip's kernel.
+        if (ok) gemv_stage<false, 1>(p.dx, E, nullptr, nullptr, p.ro_w, E, p.ro_b, nullptr, p.ro, THMR_HMR2_RO_LD, THMR_HMR2_RO_LD, B, red, &rowstat, tid, pre);
+        THMR_STAMP();
+    } else {
+        if (ok) {
+            // consumers of the decoder output: the four read-outs as one (31 + zero row, 1024) matrix (token_head.py:99-105) and
+            // the classifier's first Linear 1024 -> 160*64 (token_classifier.py:71-73); 2 + 640 column tiles dealt to the workgroups
+            gemv_multi(p.dx, p.ro_w, p.ro_b, p.ro, p.mt_w, p.mt_b, p.mt, 2, 2 + 640, B, red, tid, p.mixer_cluster != 0);
+        }
+        THMR_STAMP();
+        if (ok && p.mixer_cluster != 0) {
+            ok = grid_barrier(gs, tid, &s_ok);                   // mixer_trans' Linear output complete
+            if (ok) ok = mixer_cluster_stage(p, gs, tid, &s_ok, mixY, mixU, mixX, mixred);
+        }
+        THMR_STAMP();
     }
-    THMR_STAMP();
-    if (ok && p.mixer_cluster != 0) {
-        ok = grid_barrier(gs, tid, &s_ok);                   // mixer_trans' Linear output complete
-        if (ok) ok = mixer_cluster_stage(p, gs, tid, &s_ok, mixY, mixU, mixX, mixred);
-    }
-    THMR_STAMP();
     // exit protocol: the LAST workgroup to leave publishes the last epoch as the next kernel's generation
     __syncthreads();
     if (tid == 0) {
@@ -598,8 +611,19 @@ __global__ __launch_bounds__(NWAVE * 64) void decoder_persistent_kernel(DecParam
 }  // namespace
 
 constexpr int kDecMinGrid = 128;    // the final gemv_multi streams 42 MB of mixer_trans weights: 128 workgroups take it 2 % faster than 64 at B <= 16 (profiles/r2y_decoder_min_grid.log)
-int launch_decoder_fused(const DecParams& p, hipStream_t s) {
+int launch_decoder_fused(const DecParams& p, hipStream_t s, int head) {
     if (p.B < 1 || p.depth < 1 || p.depth > 6) return -1;
+    if (head == THMR_HEAD_HMR2) {
+        // the widest step has 64 column tiles per 16-row sub-tile, the read-out ten: the same grid rule without the token head's floor
+        if (p.mixer_cluster != 0) return -1;
+        const int nsub = (p.B + 15) / 16;
+        int grid = NBLK * (nsub < 4 ? nsub : 4);
+        if (p.max_blocks > 0 && grid > p.max_blocks) grid = p.max_blocks;
+        if (grid > 256) grid = 256;
+        hipLaunchKernelGGL(decoder_persistent_kernel<THMR_HEAD_HMR2>, dim3(grid), dim3(NWAVE * 64), 0, s, p);
+        return hipGetLastError() == hipSuccess ? 0 : -2;
+    }
+    if (head != THMR_HEAD_TOKEN) return -1;
     // one workgroup per (column tile, 16-row sub-tile) of the widest step, up to one per CU
     // (the grid barrier needs every workgroup resident: never more workgroups than the device has CUs; any grid size works,
     // the steps deal their items round-robin)
@@ -620,19 +644,22 @@ int launch_decoder_fused(const DecParams& p, hipStream_t s) {
     if (coop) {
         DecParams pc = p;
         void* args[] = {&pc};
-        return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&decoder_persistent_kernel), dim3(grid), dim3(NWAVE * 64), args, 0, s) == hipSuccess ? 0 : -2;
+        return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&decoder_persistent_kernel<THMR_HEAD_TOKEN>), dim3(grid), dim3(NWAVE * 64), args, 0, s) == hipSuccess ? 0 : -2;
     }
 #endif
-    hipLaunchKernelGGL(decoder_persistent_kernel, dim3(grid), dim3(NWAVE * 64), 0, s, p);
+    hipLaunchKernelGGL(decoder_persistent_kernel<THMR_HEAD_TOKEN>, dim3(grid), dim3(NWAVE * 64), 0, s, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // Workgroups of the persistent decoder kernel that can be resident on the device at once (occupancy query x CUs): the grid
 // barrier needs every workgroup of a launch resident, so launch_decoder_fused never launches more than this (DecParams::max_blocks).
-int decoder_max_coresident_blocks(int device) {
+int decoder_max_coresident_blocks(int device, int head) {
     int cus = 0, per_cu = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) return -2;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decoder_persistent_kernel, NWAVE * 64, 0) != hipSuccess || per_cu < 1) return -2;
+    const hipError_t q = head == THMR_HEAD_HMR2
+        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decoder_persistent_kernel<THMR_HEAD_HMR2>, NWAVE * 64, 0)
+        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decoder_persistent_kernel<THMR_HEAD_TOKEN>, NWAVE * 64, 0);
+    if (q != hipSuccess || per_cu < 1) return -2;
     // Only "at least one per CU" is taken from the query: the API over-reports by one block per CU in some SGPR ranges on this
     // ROCm (MI355X_MICROARCH.md, correctness boundaries), and one workgroup per CU is what the step scheduling assumes anyway
     // (bytes per CU bound the steps; a second workgroup would only share the CU).

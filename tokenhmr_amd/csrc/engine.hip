@@ -78,6 +78,7 @@ struct thmr_engine {
         const float *res_w[2], *res_b[2];   // the two 1x1 convs of the ResConv blocks
     } hot{};
     bool counted = false;             // registered in the per-device engine count (decoder turnstile)
+    bool hmr2 = false;                // THMR_CFG_HEAD_HMR2: the HMR2.0 regressor head (stacked read-out + finish) instead of the token head
     bool no_persistent = false;       // THMR_CFG_NO_PERSISTENT: launch-chain head, per-tile split3 GEMMs, no hand-over workspace
     bool legacy_head = false;         // THMR_LEGACY_HEAD=1: force the chain-of-GEMMs head at every batch size (A/B only)
     bool mixer_cluster = true;        // THMR_MIXER_CLUSTER=0: always run the mixer stack as its own one-workgroup-per-crop kernel (A/B only)
@@ -172,7 +173,7 @@ int fail(thmr_engine* e, int code, const std::string& msg) {
     } while (0)
 
 // ---- the reference checkpoint contract, mirrored by tokenhmr_amd/weights.py::spec ----
-void build_spec(int vit_depth, int dec_depth, std::vector<std::pair<std::string, int64_t>>& out) {
+void build_spec(int vit_depth, int dec_depth, bool hmr2, std::vector<std::pair<std::string, int64_t>>& out) {
     auto add = [&](const std::string& n, int64_t numel) { out.emplace_back(n, numel); };
     auto lin = [&](const std::string& n, int64_t o, int64_t i, bool bias = true) {
         add(n + ".weight", o * i);
@@ -207,6 +208,17 @@ void build_spec(int vit_depth, int dec_depth, std::vector<std::pair<std::string,
         ln(p + "2.norm", E);
         lin(p + "2.fn.net.0", DEC_MLP, E);
         lin(p + "2.fn.net.3", E, DEC_MLP);
+    }
+    if (hmr2) {
+        // SMPLTransformerDecoderHead (heads/smpl_head.py:32-34,46-48): three read-outs of token_out and the mean parameters; no token
+        // classifier and no tokenizer
+        lin("smpl_head.decpose", 144, E);
+        lin("smpl_head.decshape", 10, E);
+        lin("smpl_head.deccam", 3, E);
+        add("smpl_head.init_body_pose", 144);
+        add("smpl_head.init_betas", 10);
+        add("smpl_head.init_cam", 3);
+        return;
     }
     lin("smpl_head.decpose_grot", 6, E);
     lin("smpl_head.decshape", 10, E);
@@ -268,19 +280,8 @@ const EncConv kEnc[] = {
 };
 constexpr int kEncN = 11;
 
-void layout_weights(thmr_engine* e) {
-    std::vector<std::pair<std::string, int64_t>> spec;
-    build_spec(e->vit_depth, e->dec_depth, spec);
-    size_t off = 0;
-    // contiguous groups first: to_kv of all layers -> one (dec_depth*1024, 1280) matrix; read-outs -> (31,1024)+(31)
-    e->o_kv_all = off;
-    for (int l = 0; l < e->dec_depth; ++l) {
-        const std::string n = "smpl_head.transformer.transformer.layers." + std::to_string(l) + ".1.fn.to_kv.weight";
-        e->slots[n] = Slot{off, (int64_t)2 * INNER * DIM, false};
-        off += (size_t)2 * INNER * DIM;
-    }
-    off = align64(off);
-    e->o_ro_w = off;
+// the token head's read-outs as one (31,1024) matrix + (31) biases, from `off` (= o_ro_w); returns the offset behind them
+size_t layout_readout_token(thmr_engine* e, size_t off) {
     const char* ro_names[] = {"smpl_head.decpose_grot", "smpl_head.decshape", "smpl_head.deccam", "smpl_head.decpose_hands"};
     const int ro_n[] = {6, 10, 3, 12};
     for (int i = 0; i < 4; ++i) {
@@ -294,7 +295,41 @@ void layout_weights(thmr_engine* e) {
         e->slots[std::string(ro_names[i]) + ".bias"] = Slot{off, ro_n[i], false};
         off += ro_n[i];
     }
-    off = align64(off + 1);
+    return align64(off + 1);
+}
+
+// the HMR2 head's stacked read-out: decpose 144 | decshape 10 | deccam 3 rows, then zero rows up to ten whole 16-column tiles; the biases
+// likewise.  Nothing of the token head follows: no classifier, no VQ decoder, no codebook, no resample tables, no encoder.
+size_t layout_readout_hmr2(thmr_engine* e, size_t off) {
+    const char* names[] = {"smpl_head.decpose", "smpl_head.decshape", "smpl_head.deccam"};
+    const int rows[] = {144, 10, 3};
+    for (int i = 0; i < 3; ++i) {
+        e->slots[std::string(names[i]) + ".weight"] = Slot{off, (int64_t)rows[i] * E, false};
+        off += (size_t)rows[i] * E;
+    }
+    off = align64(off + (size_t)(THMR_HMR2_RO_LD - THMR_HMR2_RO_ROWS) * E);
+    e->o_ro_b = off;
+    for (int i = 0; i < 3; ++i) {
+        e->slots[std::string(names[i]) + ".bias"] = Slot{off, rows[i], false};
+        off += rows[i];
+    }
+    return align64(off + (THMR_HMR2_RO_LD - THMR_HMR2_RO_ROWS));
+}
+
+void layout_weights(thmr_engine* e) {
+    std::vector<std::pair<std::string, int64_t>> spec;
+    build_spec(e->vit_depth, e->dec_depth, e->hmr2, spec);
+    size_t off = 0;
+    // contiguous groups first: to_kv of all layers -> one (dec_depth*1024, 1280) matrix; read-outs -> (31,1024)+(31)
+    e->o_kv_all = off;
+    for (int l = 0; l < e->dec_depth; ++l) {
+        const std::string n = "smpl_head.transformer.transformer.layers." + std::to_string(l) + ".1.fn.to_kv.weight";
+        e->slots[n] = Slot{off, (int64_t)2 * INNER * DIM, false};
+        off += (size_t)2 * INNER * DIM;
+    }
+    off = align64(off);
+    e->o_ro_w = off;
+    off = e->hmr2 ? layout_readout_hmr2(e, off) : layout_readout_token(e, off);
     for (auto& kv : spec) {
         e->required.push_back(kv.first);
         if (e->slots.count(kv.first)) continue;
@@ -302,15 +337,17 @@ void layout_weights(thmr_engine* e) {
         off = align64(off + (size_t)kv.second);
     }
     // derived regions
-    e->convp.resize(9);
-    for (int i = 0; i < 9; ++i) {
-        e->convp[i] = off;
-        off = align64(off + (size_t)kConv3Co[i] * kConv3Ci[i] * 3);
+    if (!e->hmr2) {
+        e->convp.resize(9);
+        for (int i = 0; i < 9; ++i) {
+            e->convp[i] = off;
+            off = align64(off + (size_t)kConv3Co[i] * kConv3Ci[i] * 3);
+        }
+        e->o_cbT = off;   off = align64(off + (size_t)NCLS * CODE);
+        e->o_cnorm = off; off = align64(off + NCLS);
+        e->o_idx = off;   off = align64(off + 4 * 160);
+        e->o_inv = off;   off = align64(off + 4 * 160);
     }
-    e->o_cbT = off;   off = align64(off + (size_t)NCLS * CODE);
-    e->o_cnorm = off; off = align64(off + NCLS);
-    e->o_idx = off;   off = align64(off + 4 * 160);
-    e->o_inv = off;   off = align64(off + 4 * 160);
     // SMPL constants
     e->o_smpl_vt = off;  off = align64(off + (size_t)NV * 3);
     e->o_smpl_sd = off;  off = align64(off + (size_t)NV * 30);
@@ -323,7 +360,7 @@ void layout_weights(thmr_engine* e) {
     e->o_smpl_jsd = off; off = align64(off + NJ * 30);
     e->o_smpl_dirs = off; off = align64(off + (size_t)NV * 3 * THMR_LBS_KX);   // [shapedirs | posedirs | 0]^T, derived
     // optional tokenizer encoder (tokenizer.pth 'encoder.encoder.*'): raw tensors, repacked convs, resample tables
-    for (int i = 0; i < kEncN; ++i) {
+    for (int i = 0; i < (e->hmr2 ? 0 : kEncN); ++i) {
         const std::string n = kEnc[i].name;
         e->enc_names.push_back(n + ".weight");
         e->enc_names.push_back(n + ".bias");
@@ -332,12 +369,14 @@ void layout_weights(thmr_engine* e) {
         e->slots[n + ".bias"] = Slot{off, kEnc[i].co, false};
         off = align64(off + kEnc[i].co);
     }
-    e->enc_convp.resize(kEncN);
-    for (int i = 0; i < kEncN; ++i) {
-        e->enc_convp[i] = off;
-        if (kEnc[i].ks > 1) off = align64(off + (size_t)kEnc[i].co * kEnc[i].cp * kEnc[i].ks);
+    if (!e->hmr2) {
+        e->enc_convp.resize(kEncN);
+        for (int i = 0; i < kEncN; ++i) {
+            e->enc_convp[i] = off;
+            if (kEnc[i].ks > 1) off = align64(off + (size_t)kEnc[i].co * kEnc[i].cp * kEnc[i].ks);
+        }
+        e->o_idx_enc = off; off = align64(off + 640);
     }
-    e->o_idx_enc = off; off = align64(off + 640);
     e->o_flags = off;   off = align64(off + 64);     // int32 flag words travelling with the arena (0: encoder present)
     e->wfloats = off;
 }
@@ -356,16 +395,19 @@ void layout_scratch(thmr_engine* e) {
         s.part = take(s.part_floats);
     }
     s.dx = take(B * E); s.dh = take(B * E); s.dv = take(B * INNER); s.dq = take(B * INNER); s.dca = take(B * INNER);
-    s.dff = take(B * DEC_MLP); s.ro = take(B * 32);
-    s.mt = take(B * TN * HID); s.cf = take(B * TN * HID); s.cf2 = take(B * TN * HID);
-    s.y1 = take(B * TN * HID); s.tT = take(B * HID * TN); s.u = take(B * HID * TOK_INTER); s.yt = take(B * HID * TN);
-    s.y = take(B * TN * HID); s.s = take(B * TN * HID); s.z0 = take(B * TN * HID); s.zh = take(B * TN * HID_INTER);
-    s.nl = take(B * TN * HID); s.nl2 = take(B * TN * HID);
-    s.feat = take(B * TN * CODE);
-    s.gat = take(B * 125 * 3 * VQW);                 // largest conv operand: T=125, 3*512 (> 160*768)
-    s.gat2 = take(B * 125 * 3 * VQW);                // the GEMM of conv i writes the operand of conv i+1: two buffers alternate
-    s.act0 = take(B * TN * VQW); s.act1 = take(B * TN * VQW); s.act2 = take(B * TN * VQW);
-    s.bpose = take(B * 128); s.tokidx = take(B * TN); s.sync = take(512);
+    s.dff = take(B * DEC_MLP); s.ro = take(B * (e->hmr2 ? THMR_HMR2_RO_LD : 32));
+    if (!e->hmr2) {      // the token head's classifier and VQ decoder; the HMR2 head has neither
+        s.mt = take(B * TN * HID); s.cf = take(B * TN * HID); s.cf2 = take(B * TN * HID);
+        s.y1 = take(B * TN * HID); s.tT = take(B * HID * TN); s.u = take(B * HID * TOK_INTER); s.yt = take(B * HID * TN);
+        s.y = take(B * TN * HID); s.s = take(B * TN * HID); s.z0 = take(B * TN * HID); s.zh = take(B * TN * HID_INTER);
+        s.nl = take(B * TN * HID); s.nl2 = take(B * TN * HID);
+        s.feat = take(B * TN * CODE);
+        s.gat = take(B * 125 * 3 * VQW);                 // largest conv operand: T=125, 3*512 (> 160*768)
+        s.gat2 = take(B * 125 * 3 * VQW);                // the GEMM of conv i writes the operand of conv i+1: two buffers alternate
+        s.act0 = take(B * TN * VQW); s.act1 = take(B * TN * VQW); s.act2 = take(B * TN * VQW);
+        s.bpose = take(B * 128); s.tokidx = take(B * TN);
+    }
+    s.sync = take(512);
     s.A = take(B * NJ * 12); s.pf = take(B * THMR_LBS_XF); s.Jtr = take(B * NJ * 3); s.vposed = take(B * NV * 3);
     s.rot = take(B * NJ * 9); s.betas = take(B * NB); s.cam = take(B * 3); s.camt = take(B * 3);
     s.verts = take(B * NV * 3); s.joints = take(B * 132); s.pose6d = take(B * 144);
@@ -745,7 +787,7 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
             LAUNCH_OK(run_gemm(e, plan.to_kv, a, EPI_NONE, nullptr, st));
         }
     }
-    ProfScope ps_head(e, st, THMR_PROF_HEAD, 2.0 * B * (6.0 * 4.2e6 + 116.7e6 + 167.8e6 + 705.0e6), 0);
+    ProfScope ps_head(e, st, THMR_PROF_HEAD, e->hmr2 ? 2.0 * B * (6.0 * 4.2e6 + 0.16e6) : 2.0 * B * (6.0 * 4.2e6 + 116.7e6 + 167.8e6 + 705.0e6), 0);
     float *dx = e->S(so.dx), *dh = e->S(so.dh), *dv = e->S(so.dv), *dq = e->S(so.dq), *dca = e->S(so.dca), *dff = e->S(so.dff);
     const std::string T = "smpl_head.transformer.";
     const std::string C = "smpl_head.decpose.";
@@ -758,14 +800,20 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
         // classifier's first Linear (decoder_fused.hip)
         DecParams d = e->dec;
         d.B = B;
-        // the MLP-Mixer stack runs inside the same kernel, 10 / 5 / 2 workgroups per crop while they fit one per CU (up to 25 / 51 /
-        // 128 crops on 256 CUs; decoder_fused.hip mixer_cluster_stage, bit-identical to mixer_stack_kernel's one workgroup per crop)
-        const int slots = d.max_blocks < 256 ? d.max_blocks : 256;
-        d.mixer_cluster = !e->mixer_cluster ? 0 : 10 * B <= slots ? 10 : 5 * B <= slots ? 5 : 2 * B <= slots ? 2 : 0;
-        mixer_in_decoder = d.mixer_cluster != 0;
-        d.mx = e->mix;
-        d.mixy[0] = cf; d.mixy[1] = cf2;
-        LAUNCH_OK(launch_decoder_fused(d, st));            // the caller's Turn (thmr_forward / thmr_head_forward) orders engines
+        if (e->hmr2) {
+            // the same persistent kernel with the stacked read-out as its last step (decoder_fused.hip, THMR_HEAD_HMR2)
+            d.mixer_cluster = 0;
+            LAUNCH_OK(launch_decoder_fused(d, st, THMR_HEAD_HMR2));
+        } else {
+            // the MLP-Mixer stack runs inside the same kernel, 10 / 5 / 2 workgroups per crop while they fit one per CU (up to 25 / 51 /
+            // 128 crops on 256 CUs; decoder_fused.hip mixer_cluster_stage, bit-identical to mixer_stack_kernel's one workgroup per crop)
+            const int slots = d.max_blocks < 256 ? d.max_blocks : 256;
+            d.mixer_cluster = !e->mixer_cluster ? 0 : 10 * B <= slots ? 10 : 5 * B <= slots ? 5 : 2 * B <= slots ? 2 : 0;
+            mixer_in_decoder = d.mixer_cluster != 0;
+            d.mx = e->mix;
+            d.mixy[0] = cf; d.mixy[1] = cf2;
+            LAUNCH_OK(launch_decoder_fused(d, st));            // the caller's Turn (thmr_forward / thmr_head_forward) orders engines
+        }
     } else {
     LAUNCH_OK(launch_decoder_init(e->W(T + "to_token_embedding.bias"), e->W(T + "pos_embedding"), dx, B, E, st));
     for (int l = 0; l < e->dec_depth; ++l) {
@@ -802,18 +850,35 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
             LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS_RESID, st));
         }
     }
-    // read-outs: one (31,1024) GEMV-class GEMM (token_head.py:99-105)
-    {
-        GemmArgs a = mk(dx, E, e->warena + e->o_ro_w, E, e->warena + e->o_ro_b, nullptr, 0, ro, 32, B, 31, E);
+    if (e->hmr2) {
+        // the stacked read-out of the HMR2 head (smpl_head.py:82-84): one (160, 1024) GEMV-class GEMM, zero rows included
+        GemmArgs a = mk(dx, E, e->warena + e->o_ro_w, E, e->warena + e->o_ro_b, nullptr, 0, ro, THMR_HMR2_RO_LD, B, THMR_HMR2_RO_LD, E);
         LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS, st));
+    } else {
+        // read-outs: one (31,1024) GEMV-class GEMM (token_head.py:99-105)
+        {
+            GemmArgs a = mk(dx, E, e->warena + e->o_ro_w, E, e->warena + e->o_ro_b, nullptr, 0, ro, 32, B, 31, E);
+            LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS, st));
+        }
+        // token classifier (token_classifier.py:89-104)
+        {
+            GemmArgs a = mk(dx, E, e->W(C + "mixer_trans.ff.0.weight"), E, e->W(C + "mixer_trans.ff.0.bias"), nullptr, 0, mt, TN * HID, B, TN * HID, E);
+            LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS, st));
+        }
     }
-    // token classifier (token_classifier.py:89-104)
-    {
-        GemmArgs a = mk(dx, E, e->W(C + "mixer_trans.ff.0.weight"), E, e->W(C + "mixer_trans.ff.0.bias"), nullptr, 0, mt, TN * HID, B, TN * HID, E);
-        LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS, st));
-    }
-    }
+    }   // the launch chain
     if (out && out->token_out) HIP_OK(hipMemcpyAsync(out->token_out, dx, sizeof(float) * B * E, hipMemcpyDeviceToDevice, st));
+    if (e->hmr2) {
+        // the finish: mean parameters, 6D -> rotation matrices of all 24 joints, camera (hmr2_head.hip) — the second and last launch
+        // behind the to_kv GEMM in the fused form
+        float* rot = (out && out->rotmat) ? out->rotmat : e->S(so.rot);
+        float* betas = (out && out->betas) ? out->betas : e->S(so.betas);
+        float* cam = (out && out->pred_cam) ? out->pred_cam : e->S(so.cam);
+        float* camt = (out && out->pred_cam_t) ? out->pred_cam_t : e->S(so.camt);
+        LAUNCH_OK(launch_hmr2_finish(ro, THMR_HMR2_RO_LD, e->hot.init_pose, e->hot.init_betas, e->hot.init_cam, out ? out->pose6d : nullptr,
+                                     rot, betas, cam, camt, out ? out->focal_length : nullptr, FOCAL, IMG, B, st));
+        return 0;
+    }
     const int R = B * TN;
     float *nl = e->S(so.nl), *nl2 = e->S(so.nl2);
     if (fused_head) {
@@ -921,6 +986,7 @@ void build_idx_tables(thmr_engine* e) {
 }
 constexpr int32_t kEncMagic = 0x454e4331;   // 'ENC1': arena flag word 0 = "tokenizer encoder tensors present"
 constexpr int32_t kArenaMagic = 0x54484d32; // 'THM2': arena flag word 1 = "the non-checkpoint regions below were written by a loading engine"
+constexpr int32_t kArenaMagicHmr2 = 0x48324d32; // 'H2M2': the same for an arena in the HMR2 head's layout (THMR_CFG_HEAD_HMR2)
 
 // Everything in the weight arena that is neither a checkpoint tensor nor derived from one: the resample index tables, the zero
 // padding row of the read-out matrix and the flag words.  Written by the engine that LOADS tensors, at load time — so the arena
@@ -929,6 +995,15 @@ constexpr int32_t kArenaMagic = 0x54484d32; // 'THM2': arena flag word 1 = "the 
 // receivers, which finalize with assume_all_loaded = 1, never wrote them).  Receivers validate kArenaMagic instead of writing:
 // their arena may be another engine's live one (Engine(weight_arena=...)).
 int write_arena_constants(thmr_engine* e, hipStream_t st) {
+    if (e->hmr2) {
+        // HMR2 head: the zero rows / zero biases that pad the stacked read-out to whole 16-column tiles, and the magic word
+        HIP_OK(hipMemsetAsync(e->warena + e->o_ro_w + (size_t)THMR_HMR2_RO_ROWS * E, 0, (size_t)(THMR_HMR2_RO_LD - THMR_HMR2_RO_ROWS) * E * sizeof(float), st));
+        HIP_OK(hipMemsetAsync(e->warena + e->o_ro_b + THMR_HMR2_RO_ROWS, 0, (THMR_HMR2_RO_LD - THMR_HMR2_RO_ROWS) * sizeof(float), st));
+        e->flag_host[0] = 0;
+        e->flag_host[1] = kArenaMagicHmr2;
+        HIP_OK(hipMemcpyAsync(e->warena + e->o_flags, e->flag_host, 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        return 0;
+    }
     build_idx_tables(e);
     HIP_OK(hipMemcpyAsync(e->warena + e->o_idx, e->idx_host.data(), e->idx_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(e->warena + e->o_inv, e->inv_host.data(), e->inv_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -1110,7 +1185,7 @@ static int validate_cfg(const thmr_config* cfg) {
     if (cfg->vit_depth < 1 || cfg->vit_depth > 64 || cfg->dec_depth < 1 || cfg->dec_depth > 6 || cfg->max_batch < 1 ||
         cfg->max_batch > 4096)
         return fail(nullptr, THMR_ERR_INVALID, "config out of range (vit_depth 1..64, dec_depth 1..6, max_batch 1..4096)");
-    if ((cfg->flags & ~(THMR_CFG_VIT_GEMM_F32 | THMR_CFG_NO_PERSISTENT)) != 0 || cfg->reserved[0] != 0 || cfg->reserved[1] != 0)
+    if ((cfg->flags & ~(THMR_CFG_VIT_GEMM_F32 | THMR_CFG_NO_PERSISTENT | THMR_CFG_HEAD_HMR2)) != 0 || cfg->reserved[0] != 0 || cfg->reserved[1] != 0)
         return fail(nullptr, THMR_ERR_INVALID, "unknown config flag / non-zero reserved field");
     return 0;
 }
@@ -1174,6 +1249,7 @@ int thmr_arena_bytes(const thmr_config* cfg, size_t* weight_bytes, size_t* scrat
     if (int r = validate_cfg(cfg)) return r;
     thmr_engine tmp;
     tmp.vit_depth = cfg->vit_depth; tmp.dec_depth = cfg->dec_depth; tmp.max_batch = cfg->max_batch;
+    tmp.hmr2 = (cfg->flags & THMR_CFG_HEAD_HMR2) != 0;
     layout_weights(&tmp);
     layout_scratch(&tmp);
     if (weight_bytes) *weight_bytes = tmp.wfloats * sizeof(float);
@@ -1185,7 +1261,7 @@ int thmr_spec(const thmr_config* cfg, int32_t index, const char** name, int64_t*
     if (int r = validate_cfg(cfg)) return r;
     static thread_local std::vector<std::pair<std::string, int64_t>> spec;
     spec.clear();
-    build_spec(cfg->vit_depth, cfg->dec_depth, spec);
+    build_spec(cfg->vit_depth, cfg->dec_depth, (cfg->flags & THMR_CFG_HEAD_HMR2) != 0, spec);
     if (index >= 0 && index < (int32_t)spec.size()) {
         if (name) *name = spec[index].first.c_str();
         if (numel) *numel = spec[index].second;
@@ -1200,6 +1276,7 @@ int thmr_create(const thmr_config* cfg, void* weight_arena_dev, void* scratch_ar
     thmr_engine* e = new thmr_engine();
     e->cfg = *cfg;
     e->vit_depth = cfg->vit_depth; e->dec_depth = cfg->dec_depth; e->max_batch = cfg->max_batch;
+    e->hmr2 = (cfg->flags & THMR_CFG_HEAD_HMR2) != 0;
     layout_weights(e);
     layout_scratch(e);
     auto bail = [&](int code, const std::string& m) { fail(nullptr, code, m); thmr_destroy(e); return code; };
@@ -1381,22 +1458,24 @@ int thmr_finalize_weights(thmr_engine* e, int32_t assume_all_loaded, void* strea
         if (enc_loaded != 0 && enc_loaded != e->enc_names.size())
             return fail(e, THMR_ERR_STATE, "tokenizer encoder partially loaded: " + std::to_string(enc_loaded) + " of " +
                                                std::to_string(e->enc_names.size()) + " tensors");
-        e->enc_ready = enc_loaded == e->enc_names.size();
+        e->enc_ready = !e->hmr2 && enc_loaded == e->enc_names.size();
     } else {
         // the arena was filled by someone else (a broadcast from the loading rank, or it is another engine's live arena): it must
         // carry the loader's magic word, otherwise the index tables / padding row / flags are uninitialised memory
         int32_t f[2] = {0, 0};
         HIP_OK(hipMemcpyAsync(f, flags, sizeof(f), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        if (f[1] != kArenaMagic)
+        if (f[1] != (e->hmr2 ? kArenaMagicHmr2 : kArenaMagic))
             return fail(e, THMR_ERR_STATE, "thmr_finalize_weights(assume_all_loaded=1): the weight arena does not carry a loaded model "
-                                           "(no loader magic word): was it broadcast before the root called thmr_load_weights, or never received?");
-        e->enc_ready = f[0] == kEncMagic;
+                                           "(no loader magic word of this head kind): was it broadcast before the root called thmr_load_weights, or never received?");
+        e->enc_ready = !e->hmr2 && f[0] == kEncMagic;
     }
-    for (int i = 0; i < 9; ++i)
-        LAUNCH_OK(launch_conv_repack(e->W(std::string(kConv3[i]) + ".weight"), e->warena + e->convp[i], kConv3Co[i], kConv3Ci[i], 3, st));
-    LAUNCH_OK(launch_transpose(e->W("quantizer.codebook"), e->warena + e->o_cbT, 1, NCLS, CODE, st));
-    LAUNCH_OK(launch_code_norm(e->W("quantizer.codebook"), e->warena + e->o_cnorm, NCLS, st));
+    if (!e->hmr2) {
+        for (int i = 0; i < 9; ++i)
+            LAUNCH_OK(launch_conv_repack(e->W(std::string(kConv3[i]) + ".weight"), e->warena + e->convp[i], kConv3Co[i], kConv3Ci[i], 3, st));
+        LAUNCH_OK(launch_transpose(e->W("quantizer.codebook"), e->warena + e->o_cbT, 1, NCLS, CODE, st));
+        LAUNCH_OK(launch_code_norm(e->W("quantizer.codebook"), e->warena + e->o_cnorm, NCLS, st));
+    }
     LAUNCH_OK(launch_lbs_jreg(e->warena + e->o_smpl_jr, e->warena + e->o_smpl_vt, e->warena + e->o_smpl_sd,
                               e->warena + e->o_smpl_jt, e->warena + e->o_smpl_jsd, st));
     LAUNCH_OK(launch_lbs_build_dirs(e->warena + e->o_smpl_sd, e->warena + e->o_smpl_pd, e->warena + e->o_smpl_dirs, st));
@@ -1436,7 +1515,7 @@ int thmr_finalize_weights(thmr_engine* e, int32_t assume_all_loaded, void* strea
         d.tok_bias = e->W(T + "to_token_embedding.bias"); d.pos = e->W(T + "pos_embedding");
         d.kv = e->S(e->so.big); d.ldkv = (int64_t)e->dec_depth * 2 * INNER;
         d.ro_w = e->warena + e->o_ro_w; d.ro_b = e->warena + e->o_ro_b;
-        d.mt_w = e->W("smpl_head.decpose.mixer_trans.ff.0.weight"); d.mt_b = e->W("smpl_head.decpose.mixer_trans.ff.0.bias");
+        if (!e->hmr2) { d.mt_w = e->W("smpl_head.decpose.mixer_trans.ff.0.weight"); d.mt_b = e->W("smpl_head.decpose.mixer_trans.ff.0.bias"); }
         d.dx = e->S(e->so.dx); d.dv = e->S(e->so.dv); d.dq = e->S(e->so.dq); d.dca = e->S(e->so.dca); d.dff = e->S(e->so.dff);
         d.ro = e->S(e->so.ro); d.mt = e->S(e->so.mt);
         d.sync = reinterpret_cast<unsigned*>(e->S(e->so.sync));
@@ -1448,14 +1527,14 @@ int thmr_finalize_weights(thmr_engine* e, int32_t assume_all_loaded, void* strea
         { const char* bm = thmr_knob("THMR_DEC_BARRIER"); d.barrier_a2a = bm && bm[0] == '1'; }
         {
             // never more workgroups than can be resident at once (occupancy query x CUs): the grid barrier depends on it
-            const int nb = decoder_max_coresident_blocks(e->cfg.device);
+            const int nb = decoder_max_coresident_blocks(e->cfg.device, e->hmr2 ? THMR_HEAD_HMR2 : THMR_HEAD_TOKEN);
             if (nb < 1) return fail(e, THMR_ERR_HIP, "persistent decoder kernel cannot be resident on this device (occupancy query failed)");
             d.max_blocks = nb;
             d.host_err = e->host_err;
         }
         MixerParams& m = e->mix;
         const std::string C = "smpl_head.decpose.";
-        for (int i = 0; i < MIX; ++i) {
+        for (int i = 0; i < (e->hmr2 ? 0 : MIX); ++i) {
             const std::string p = C + "mixer_head." + std::to_string(i) + ".";
             MixerLayerW& w = m.L[i];
             w.ln1w = e->W(p + "layernorm1.weight"); w.ln1b = e->W(p + "layernorm1.bias");
@@ -1465,18 +1544,20 @@ int thmr_finalize_weights(thmr_engine* e, int32_t assume_all_loaded, void* strea
             w.wc1 = e->W(p + "MLP_channel.ff.0.weight"); w.bc1 = e->W(p + "MLP_channel.ff.0.bias");
             w.wc2 = e->W(p + "MLP_channel.ff.3.weight"); w.bc2 = e->W(p + "MLP_channel.ff.3.bias");
         }
-        m.tln_w = e->W(C + "mixer_trans.ff.1.weight"); m.tln_b = e->W(C + "mixer_trans.ff.1.bias");
-        m.wn = e->W(C + "mixer_norm_layer.ff.0.weight"); m.bn = e->W(C + "mixer_norm_layer.ff.0.bias");
-        m.nln_w = e->W(C + "mixer_norm_layer.ff.1.weight"); m.nln_b = e->W(C + "mixer_norm_layer.ff.1.bias");
-        m.mt = e->S(e->so.mt); m.out = e->S(e->so.nl2);
+        if (!e->hmr2) {
+            m.tln_w = e->W(C + "mixer_trans.ff.1.weight"); m.tln_b = e->W(C + "mixer_trans.ff.1.bias");
+            m.wn = e->W(C + "mixer_norm_layer.ff.0.weight"); m.bn = e->W(C + "mixer_norm_layer.ff.0.bias");
+            m.nln_w = e->W(C + "mixer_norm_layer.ff.1.weight"); m.nln_b = e->W(C + "mixer_norm_layer.ff.1.bias");
+            m.mt = e->S(e->so.mt); m.out = e->S(e->so.nl2);
+        }
         auto& h = e->hot;
         h.pe_w = e->W("backbone.patch_embed.proj.weight"); h.pe_b = e->W("backbone.patch_embed.proj.bias");
         h.pos = e->W("backbone.pos_embed");
         h.lastn_w = e->W("backbone.last_norm.weight"); h.lastn_b = e->W("backbone.last_norm.bias");
-        h.cls_w = e->W(C + "class_pred_layer.weight"); h.cls_b = e->W(C + "class_pred_layer.bias");
+        if (!e->hmr2) { h.cls_w = e->W(C + "class_pred_layer.weight"); h.cls_b = e->W(C + "class_pred_layer.bias"); }
         h.init_pose = e->W("smpl_head.init_body_pose"); h.init_betas = e->W("smpl_head.init_betas"); h.init_cam = e->W("smpl_head.init_cam");
-        for (int i = 0; i < 9; ++i) h.conv_b[i] = e->W(std::string(kConv3[i]) + ".bias");
-        for (int b = 0; b < 2; ++b) {
+        for (int i = 0; i < (e->hmr2 ? 0 : 9); ++i) h.conv_b[i] = e->W(std::string(kConv3[i]) + ".bias");
+        for (int b = 0; b < (e->hmr2 ? 0 : 2); ++b) {
             const std::string p = "decoder.decoder.14.0.model." + std::to_string(b) + ".";
             h.res_w[b] = e->W(p + "conv2.weight"); h.res_b[b] = e->W(p + "conv2.bias");
         }
@@ -1506,8 +1587,21 @@ int thmr_set_vit_gemm(thmr_engine* e, int32_t mode, void* stream) {
 
 int thmr_get_vit_gemm(thmr_engine* e) { return e ? e->vit_gemm_mode : -1; }
 
+// an engine created with THMR_CFG_HEAD_HMR2 has no tokenizer: its entry points and the token outputs are refused by name
+static int refuse_hmr2(thmr_engine* e, const char* what) {
+    return fail(e, THMR_ERR_INVALID, std::string(what) + " does not exist on an engine created with THMR_CFG_HEAD_HMR2 (the HMR2 head has no pose tokens and no tokenizer)");
+}
+static int refuse_hmr2_outputs(thmr_engine* e, const thmr_outputs* out) {
+    if (!e->hmr2 || !out) return 0;
+    if (out->cls_logits_softmax) return refuse_hmr2(e, "thmr_outputs.cls_logits_softmax");
+    if (out->cls_logits) return refuse_hmr2(e, "thmr_outputs.cls_logits");
+    if (out->token_idx) return refuse_hmr2(e, "thmr_outputs.token_idx");
+    return 0;
+}
+
 int thmr_vq_decode(thmr_engine* e, const float* probs_dev, int32_t B, float* pose6d_dev, void* stream) {
     if (int r = check_ready(e, B)) return r;
+    if (e->hmr2) return refuse_hmr2(e, "thmr_vq_decode");
     if (!probs_dev || !pose6d_dev) return fail(e, THMR_ERR_INVALID, "null buffer");
     return vq_decode(e, probs_dev, B, pose6d_dev, static_cast<hipStream_t>(stream));
 }
@@ -1516,6 +1610,7 @@ int thmr_vq_decode(thmr_engine* e, const float* probs_dev, int32_t B, float* pos
 // (quantize_cnn.py:74-78) -> QuantizeEMAReset.quantize (:80-86).  pose (B,21,6) rot6d body pose -> idx (B,160).
 int thmr_encode_tokens(thmr_engine* e, const float* pose_dev, int32_t B, int32_t* idx_dev, float* latent_dev, void* stream) {
     if (int r = check_ready(e, B)) return r;
+    if (e->hmr2) return refuse_hmr2(e, "thmr_encode_tokens");
     if (!e->enc_ready) return fail(e, THMR_ERR_STATE, "tokenizer encoder weights ('encoder.encoder.*') were not loaded");
     if (!pose_dev || !idx_dev) return fail(e, THMR_ERR_INVALID, "null buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1661,6 +1756,7 @@ static int head_forward_call(thmr_engine* e, const float* ctx_dev, int32_t B, co
 int thmr_head_forward(thmr_engine* e, const float* ctx_dev, int32_t B, const thmr_outputs* out, void* stream) {
     if (int r = check_ready(e, B, static_cast<hipStream_t>(stream))) return r;
     if (!ctx_dev) return fail(e, THMR_ERR_INVALID, "null buffer");
+    if (int r = refuse_hmr2_outputs(e, out)) return r;
     hipStream_t st = static_cast<hipStream_t>(stream);
     THMR_TURN(turn, e, st);
     return end_turn(e, turn, head_forward_call(e, ctx_dev, B, out, st));
@@ -1689,6 +1785,7 @@ static int forward_call(thmr_engine* e, const float* img_dev, int32_t B, const t
 int thmr_forward(thmr_engine* e, const float* img_dev, int32_t B, const thmr_outputs* out, void* stream) {
     if (int r = check_ready(e, B, static_cast<hipStream_t>(stream))) return r;
     if (!img_dev || !out) return fail(e, THMR_ERR_INVALID, "null buffer");
+    if (int r = refuse_hmr2_outputs(e, out)) return r;
     hipStream_t st = static_cast<hipStream_t>(stream);
     THMR_TURN(turn, e, st);
     return end_turn(e, turn, forward_call(e, img_dev, B, out, st));
@@ -1711,6 +1808,7 @@ int thmr_lbs_forward(thmr_engine* e, const float* rotmat_dev, const float* betas
 int thmr_vq_argmin(thmr_engine* e, const float* x_dev, int32_t rows, int32_t* idx_dev, float* dist_dev, void* stream) {
     if (!e) return fail(e, THMR_ERR_INVALID, "null engine");
     if (!e->finalized) return fail(e, THMR_ERR_STATE, "weights not finalized");
+    if (e->hmr2) return refuse_hmr2(e, "thmr_vq_argmin");
     if (!x_dev || !idx_dev || rows < 1) return fail(e, THMR_ERR_INVALID, "bad argument");
     if ((size_t)rows * NCLS > (size_t)e->max_batch * TOK * 6144) return fail(e, THMR_ERR_INVALID, "rows exceed scratch capacity");
     hipStream_t st = static_cast<hipStream_t>(stream);

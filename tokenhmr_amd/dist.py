@@ -13,7 +13,8 @@ Works with backend 'nccl' (= RCCL on ROCm) on GPUs and 'gloo' on CPU tensors (te
 import torch
 import torch.distributed as dist
 
-# packed per-crop record layout (float32 words); token_idx is stored bit-exactly via view(int32)
+# packed per-crop record layout (float32 words); token_idx is stored bit-exactly via view(int32) — zero words where the output dict
+# has none (the HMR2 head)
 RECORD_FIELDS = [
     ("pred_vertices", 6890 * 3), ("pred_keypoints_3d", 44 * 3), ("pred_keypoints_2d", 44 * 2),
     ("rotmat", 24 * 9), ("betas", 10), ("pred_cam", 3), ("pred_cam_t", 3), ("token_idx", 160),
@@ -46,6 +47,8 @@ def pack_records(o):
             # thmr_pack_records reads raw 32-bit words: a forward_fn that hands back e.g. an int64 token_idx or a tensor on another
             # device must not be packed as garbage
             want = torch.int32 if name == "token_idx" else torch.float32
+            if name == "token_idx" and name not in o:
+                continue            # an HMR2 engine has no pose tokens: thmr_pack_records writes zero words for a null token_idx
             t = o[name]
             if t.device != dev:
                 raise ValueError(f"pack_records: '{name}' lives on {t.device}, 'pred_cam' on {dev}")
@@ -68,6 +71,9 @@ def pack_records(o):
         return rec
     parts = []
     for name, n in RECORD_FIELDS:
+        if name == "token_idx" and name not in o:
+            parts.append(torch.zeros(B, n, dtype=torch.float32, device=o["pred_cam"].device))
+            continue
         t = o[name]
         if name == "token_idx":
             t = t.to(torch.int32).contiguous().view(torch.float32)

@@ -49,6 +49,9 @@ class Engine:
         if os.environ.get("THMR_SHARED_GPU", "") == "1":
             persistent = False
         flags = (_cabi.CFG_VIT_GEMM_F32 if vit_gemm == "f32" else 0) | (0 if persistent else _cabi.CFG_NO_PERSISTENT)
+        # cfg.head == "hmr2": the HMR2.0 regressor head (THMR_CFG_HEAD_HMR2) — no token outputs, no tokenizer entry points
+        self.hmr2 = cfg.head == "hmr2"
+        flags |= _cabi.CFG_HEAD_HMR2 if self.hmr2 else 0
         if flags and self._abi < 5:
             raise _cabi.EngineError("this build of the library (ABI < 5) has no creation flags")
         self.persistent = bool(persistent)
@@ -99,9 +102,13 @@ class Engine:
     def load_state(self, state, tokenizer=None):
         """state: TokenHMR state_dict ('backbone.*','smpl_head.*'); tokenizer: tokenizer 'net' dict.
         Host or device fp32 tensors in the reference layouts (strict: missing/unknown keys raise)."""
+        if self.hmr2 and tokenizer:
+            raise ValueError("an HMR2 engine takes no tokenizer tensors")
         items = list(state.items()) + (list(tokenizer.items()) if tokenizer else [])
-        wanted = {n for n, *_ in W.spec(self.cfg)} | {n for n, *_ in W.tokenizer_spec(self.cfg)}
-        wanted |= {n for n, *_ in W.tokenizer_encoder_spec(self.cfg)}      # optional: enables encode_tokens()
+        wanted = {n for n, *_ in W.spec(self.cfg)}
+        if not self.hmr2:
+            wanted |= {n for n, *_ in W.tokenizer_spec(self.cfg)}
+            wanted |= {n for n, *_ in W.tokenizer_encoder_spec(self.cfg)}      # optional: enables encode_tokens()
         descs, keep = [], []
         for name, t in items:
             if name not in wanted:
@@ -155,6 +162,8 @@ class Engine:
             spec.append(("cls_logits_softmax", (B, 160, 2048)))
         if taps:
             spec += [("vit_features", (B, 192, 1280)), ("token_out", (B, 1024)), ("cls_logits", (B, 160, 2048)), ("pose6d", (B, 144))]
+        if self.hmr2:       # the HMR2 head has no pose tokens: the library refuses these three fields
+            spec = [(n, s) for n, s in spec if n not in ("token_idx", "cls_logits_softmax", "cls_logits")]
         # 80 KB ... MB per crop: own allocations, so a kept (or torch.save-d) small tensor neither pins nor serialises them.  The small
         # tensors share ONE storage: they are views — `.clone()` what is to outlive the dict cheaply or to be pickled on its own
         big = {"cls_logits_softmax", "vit_features", "cls_logits", "pred_vertices"}

@@ -40,7 +40,7 @@ class TokenHMR:
     def from_state(cls, cfg, state, tokenizer, smpl, max_batch=64, device="cuda:0", model_cfg=None, vit_gemm=None, persistent=True):
         """vit_gemm / persistent: creation-time choices of the engine (Engine.__init__): "f32" creates it in the opt-out mode, so that
         finalize builds no split3 copies at all; persistent=False for a GPU shared with another process."""
-        W.validate_state(state, cfg, tokenizer)
+        W.validate_state(state, cfg, tokenizer)      # (an HMR2 config takes tokenizer=None)
         m = cls(cfg, max_batch=max_batch, device=device, model_cfg=model_cfg, vit_gemm=vit_gemm, persistent=persistent)
         m.engine.load_state(state, tokenizer)
         m.engine.load_smpl(smpl)
@@ -102,6 +102,21 @@ class TokenHMR:
 
     def _pack(self, o):
         R = o["rotmat"]
+        if self.hmr_cfg.head == "hmr2":
+            # tokenhmr.py:157-158: 'cls_logits_softmax' exists for the token head only; there is no token index either
+            out = {
+                "pred_cam": o["pred_cam"],
+                "pred_smpl_params": {"global_orient": R[:, :1], "body_pose": R[:, 1:], "betas": o["betas"]},
+                "pred_cam_t": o["pred_cam_t"],
+                "focal_length": o["focal_length"],
+                "pred_keypoints_3d": o["pred_keypoints_3d"],
+                "pred_vertices": o["pred_vertices"],
+                "pred_keypoints_2d": o["pred_keypoints_2d"],
+            }
+            for k in ("vit_features", "token_out", "pose6d"):
+                if k in o:
+                    out[k] = o[k]
+            return out
         out = {
             "cls_logits_softmax": o["cls_logits_softmax"],
             "pred_cam": o["pred_cam"],
@@ -227,9 +242,16 @@ def read_reference_files(checkpoint_path="", model_cfg="", dataset_dir="", is_tr
     """The file-reading half of load_tokenhmr (no GPU needed): -> (HMRConfig, state, tokenizer, smpl, cfg).
     Mirrors tokenhmr/lib/models/__init__.py:3-26 (eval branch of TokenHMR.__init__, tokenhmr.py:49-53,84-85).
 
-    Reads the Lightning checkpoint ['state_dict'] (misc.py:242-256), the tokenizer checkpoint named
-    by MODEL.TOKENIZER_CHECKPOINT_PATH ['net'] + ['hparams'].ARCH (vanilla_pose_vqvae.py:265-278,299-301) and the SMPL
-    pickles named by SMPL.MODEL_PATH / SMPL.JOINT_REGRESSOR_EXTRA, and returns (model, cfg).
+    Reads the Lightning checkpoint ['state_dict'] (misc.py:242-256), the SMPL pickles named by SMPL.MODEL_PATH /
+    SMPL.JOINT_REGRESSOR_EXTRA and, for MODEL.SMPL_HEAD.TYPE 'token', the tokenizer checkpoint named by
+    MODEL.TOKENIZER_CHECKPOINT_PATH ['net'] + ['hparams'].ARCH (vanilla_pose_vqvae.py:265-278,299-301).
+
+    MODEL.SMPL_HEAD.TYPE 'transformer_decoder' (the HMR2.0 head, heads/smpl_head.py) gives HMRConfig.head == "hmr2" and tokenizer=None:
+    MODEL.TOKENIZER_CHECKPOINT_PATH is not read and may be absent.  IEF_ITERS != 1, TRANSFORMER_INPUT 'mean_shape' and JOINT_REP 'aa'
+    raise NotImplementedError naming the key; a TRANSFORMER_DECODER heads / dim_head / mlp_dim / context_dim / dim or depth the
+    engine's decoder is not built for raises ValueError naming the key ('dim' is checked with the four the token head fixes because
+    the reference passes it to TransformerDecoder too, smpl_head.py:22-31: a file that sets it to anything but 1024 asks for a
+    different decoder).
 
     Both checkpoints are un-pickled by `ckpt_io.load_checkpoint` (restricted find_class): the yacs CfgNode in tokenizer.pth
     and the config nodes under a Lightning checkpoint's 'hyper_parameters' need neither yacs, omegaconf nor
@@ -244,8 +266,22 @@ def read_reference_files(checkpoint_path="", model_cfg="", dataset_dir="", is_tr
     cfg.ckpt_path = checkpoint_path
     if getattr(cfg.MODEL.BACKBONE, "TYPE", "vit") != "vit":
         raise NotImplementedError("Backbone type is not implemented")
-    if getattr(cfg.MODEL.SMPL_HEAD, "TYPE", "token") != "token":
-        raise ValueError("Unknown SMPL head type for this engine: only 'token' (tokenhmr_release.yaml:65)")
+    head_type = getattr(cfg.MODEL.SMPL_HEAD, "TYPE", "token")
+    if head_type not in ("token", "transformer_decoder"):
+        raise ValueError(f"Unknown SMPL head type {head_type!r}: 'token' (tokenhmr_release.yaml:65) or 'transformer_decoder' "
+                         "(heads/__init__.py:4-13)")
+    head = "hmr2" if head_type == "transformer_decoder" else "token"
+    if head == "hmr2":
+        # SMPLTransformerDecoderHead (heads/smpl_head.py): what the engine's HMR2 head does NOT implement is refused by key
+        sh = cfg.MODEL.SMPL_HEAD
+        if int(sh.get("IEF_ITERS", 1)) != 1:
+            raise NotImplementedError(f"MODEL.SMPL_HEAD.IEF_ITERS = {sh.get('IEF_ITERS')}: only 1 (smpl_head.py:70; no shipped config sets it)")
+        if sh.get("TRANSFORMER_INPUT", "zero") != "zero":
+            raise NotImplementedError(f"MODEL.SMPL_HEAD.TRANSFORMER_INPUT = {sh.get('TRANSFORMER_INPUT')!r}: only 'zero' "
+                                      "(smpl_head.py:21,72-75; 'mean_shape' appears in no shipped config)")
+        if sh.get("JOINT_REP", "6d") != "6d":
+            raise NotImplementedError(f"MODEL.SMPL_HEAD.JOINT_REP = {sh.get('JOINT_REP')!r}: only '6d' (the reference raises for 'aa' "
+                                      "itself, smpl_head.py:61-62)")
     assert cfg.MODEL.IMAGE_SIZE == 256, f"MODEL.IMAGE_SIZE ({cfg.MODEL.IMAGE_SIZE}) should be 256 for ViT backbone"
     if "BBOX_SHAPE" not in cfg.MODEL:
         cfg.MODEL.BBOX_SHAPE = [192, 256]
@@ -262,9 +298,19 @@ def read_reference_files(checkpoint_path="", model_cfg="", dataset_dir="", is_tr
     blocks = {int(k.split(".")[2]) for k in full if k.startswith("backbone.blocks.")}
     if not blocks or blocks != set(range(len(blocks))):
         raise KeyError(f"checkpoint has no contiguous 'backbone.blocks.N.*' tensors (found indices {sorted(blocks)[:8]})")
-    hcfg = HMRConfig(vit_depth=len(blocks), dec_depth=int(td.get("depth", 6)))
+    hcfg = HMRConfig(vit_depth=len(blocks), dec_depth=int(td.get("depth", 6)), head=head)
+    if head == "hmr2":
+        # the decoder kernels are built for ONE architecture (the token head's, token_head.py:30-38): the file's must be that one
+        for key, want in (("heads", hcfg.dec_heads), ("dim_head", hcfg.dec_head_dim), ("mlp_dim", hcfg.dec_mlp), ("context_dim", hcfg.dim),
+                          ("dim", hcfg.dec_dim)):
+            if key in td and int(td[key]) != want:
+                raise ValueError(f"MODEL.SMPL_HEAD.TRANSFORMER_DECODER.{key} = {td[key]}: the engine's decoder is built for {want}")
+        if not 1 <= hcfg.dec_depth <= 6:
+            raise ValueError(f"MODEL.SMPL_HEAD.TRANSFORMER_DECODER.depth = {hcfg.dec_depth}: the engine's decoder runs 1 ... 6 layers")
     known = {n for n, *_ in W.spec(hcfg)}
     state = ckpt_io.select_state(full, ("backbone.", "smpl_head."), known, strict=strict, what=os.path.basename(checkpoint_path))
+    if head == "hmr2":
+        return _finish_reference_files(cfg, hcfg, state, None)      # no tokenizer: MODEL.TOKENIZER_CHECKPOINT_PATH is not read
     tck = ckpt_io.load_checkpoint(cfg.MODEL.TOKENIZER_CHECKPOINT_PATH)
     if not isinstance(tck, dict) or "net" not in tck:
         raise KeyError(f"{cfg.MODEL.TOKENIZER_CHECKPOINT_PATH}: no 'net' entry (vanilla_pose_vqvae.py:299-301)")
@@ -276,6 +322,11 @@ def read_reference_files(checkpoint_path="", model_cfg="", dataset_dir="", is_tr
     enc_names = [n for n, *_ in W.tokenizer_encoder_spec(hcfg)]
     if all(n in net for n in enc_names):        # the tokenizer's encoder half (EncodeTokens, :304-346) enables engine.encode_tokens()
         tok.update({n: net[n] for n in enc_names})
+    return _finish_reference_files(cfg, hcfg, state, tok)
+
+
+def _finish_reference_files(cfg, hcfg, state, tok):
+    """The part of read_reference_files both heads share: mean parameters, SMPL pickles, validation."""
     mean = __import__("numpy").load(cfg.SMPL.MEAN_PARAMS)
     state.setdefault("smpl_head.init_body_pose", torch.from_numpy(mean["pose"].astype("float32")).unsqueeze(0))
     state.setdefault("smpl_head.init_betas", torch.from_numpy(mean["shape"].astype("float32")).unsqueeze(0))

@@ -68,6 +68,16 @@ def spec(cfg: HMRConfig = RELEASE):
         ln(p + "2.norm", E)
         lin(p + "2.fn.net.0", cfg.dec_mlp, E)
         lin(p + "2.fn.net.3", E, cfg.dec_mlp)
+    if cfg.head == "hmr2":
+        # ---- SMPLTransformerDecoderHead (heads/smpl_head.py:32-34,46-48): three read-outs of token_out + the mean parameters ----
+        # (drawn in this order AFTER everything above, so backbone.* and smpl_head.transformer.* equal the token state's for a seed)
+        lin("smpl_head.decpose", 144, E)
+        lin("smpl_head.decshape", 10, E)
+        lin("smpl_head.deccam", 3, E)
+        S.append(("smpl_head.init_body_pose", (1, 144), "mean_pose", 0))
+        S.append(("smpl_head.init_betas", (1, 10), "zeros", 0))
+        S.append(("smpl_head.init_cam", (1, 3), "mean_cam", 0))
+        return S
     # ---- read-outs (token_head.py:40-43) ----
     lin("smpl_head.decpose_grot", 6, E)
     lin("smpl_head.decshape", 10, E)
@@ -167,8 +177,10 @@ def _fill(shape, kind, fan_in, g):
     raise ValueError(kind)
 
 
-def make_synthetic_state(cfg: HMRConfig = RELEASE, seed: int = 0, style: str = "init"):
-    """Seeded TokenHMR state_dict (reference key names).
+def make_synthetic_state(cfg: HMRConfig = RELEASE, seed: int = 0, style: str = "init", head: str = None):
+    """Seeded TokenHMR state_dict (reference key names).  `head` ("token" / "hmr2") overrides cfg.head: the HMR2 state shares the
+    generators, so its 'backbone.*' and 'smpl_head.transformer.*' tensors are bit-for-bit the token state's of the same (seed, style)
+    — the "trained" reshaping draws per tensor in spec order and the common prefix comes first; only the mean parameters differ.
 
     style "init": the default-init statistics described in the module docstring.
     style "trained": the same draw, then reshaped towards what a TRAINED ViT-H looks like (the released weights are trained,
@@ -176,6 +188,9 @@ def make_synthetic_state(cfg: HMRConfig = RELEASE, seed: int = 0, style: str = "
     tenths, ~1 % outlier output channels scaled x50 in every `attn.proj` / `mlp.fc2` weight (the "massive activation" channels
     of the residual stream), and non-trivial mean parameters (a random pose of ~0.3 rad per joint, betas, a shifted camera).
     The "init" tensors of a (cfg, seed) are bit-for-bit the same whatever styles exist (own generator for the reshaping)."""
+    if head is not None and head != cfg.head:
+        from dataclasses import replace
+        cfg = replace(cfg, head=head)
     g = torch.Generator(device="cpu").manual_seed(1000 + seed)
     sd = OrderedDict()
     for name, shape, kind, fan_in in spec(cfg):
@@ -240,6 +255,10 @@ def validate_state(sd, cfg: HMRConfig = RELEASE, tokenizer=None):
             raise KeyError(f"missing tensor '{name}' in TokenHMR state_dict")
         if tuple(sd[name].shape) != tuple(shape):
             raise ValueError(f"'{name}': expected {tuple(shape)}, got {tuple(sd[name].shape)}")
+    if cfg.head == "hmr2":
+        if tokenizer:
+            raise ValueError("the HMR2 head (HMRConfig.head == 'hmr2') has no tokenizer: pass tokenizer=None")
+        return
     if tokenizer is not None:
         for name, shape, _, _ in tokenizer_spec(cfg):
             if name not in tokenizer:
