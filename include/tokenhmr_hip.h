@@ -321,6 +321,71 @@ int thmr_op_rot6d(const float* x_dev, float* R_dev, int32_t n, void* stream);
  * ground-truth poses at tokenhmr.py:235,260,357): (n,3) -> (n,3,3) */
 int thmr_op_aa_to_rotmat(const float* aa_dev, float* R_dev, int32_t n, void* stream);
 
+/* The row, glue and head kernels around the GEMMs and the attention (csrc/rowops.hip, head.hip, hmr2_head.hip), each as the engine launches
+ * it (tests/test_gpu_rowops.py).  Every entry point checks its arguments before any HIP call: a null buffer, a count <= 0 or a constraint
+ * named below is THMR_ERR_INVALID with a message in thmr_last_error(NULL).  All buffers fp32 and contiguous unless said otherwise. */
+/* The split-K reduce of the ViT residual stream fused with the next LayerNorm (vit.py:149-150 followed by :149 / :150 / :335):
+ *   xout = resid + ((((part[0] + part[1]) + ...) + part[S-1]) + bias);  y = LayerNorm(xout; gamma, beta, eps)
+ * part (S, rows, D) slabs of rows * D floats; bias, gamma, beta (D); resid, xout (rows, D) — resid == xout (in place) is what the engine
+ * passes; y fp32 (rows, D), or with y_is_split3 the split3 operand [rows][D/8][3][8] bf16 (thmr_op_split3 of the fp32 y, bit for bit).
+ * D == 1280, S >= 1; the split3 output exists for S == 2 and 4 only. */
+int thmr_op_splitk_resid_ln(const float* part_dev, int32_t S, int32_t rows, int32_t D, const float* bias_dev, const float* resid_dev,
+                            float* xout_dev, const float* gamma_dev, const float* beta_dev, void* y_dev, float eps, int32_t y_is_split3,
+                            void* stream);
+/* MixerLayer's layernorm2(x + y) (heads/modules.py:59): s_out = x + y, z_out = LayerNorm64(s_out); all (rows, 64), gamma / beta (64). */
+int thmr_op_add_ln64(const float* x_dev, const float* y_dev, const float* gamma_dev, const float* beta_dev, float* s_out_dev,
+                     float* z_out_dev, int32_t rows, float eps, void* stream);
+/* batched transpose (Bn, R, C) -> (Bn, C, R) (MixerLayer's y.transpose(2, 1), heads/modules.py:56-58; the codebook at finalize).
+ * Bn <= 65535, R <= 32 * 65535 (grid dimensions). */
+int thmr_op_transpose(const float* in_dev, float* out_dev, int32_t Bn, int32_t R, int32_t C, void* stream);
+/* cls_logits.softmax(-1) over 2048 classes (token_classifier.py:104) and the token index argmax_k logits, LOWEST index on ties:
+ * logits (rows, 2048) -> probs (rows, 2048) and / or idx (rows) int32; either output may be null, not both. */
+int thmr_op_softmax_argmax(const float* logits_dev, float* probs_or_null, int32_t* idx_or_null, int32_t rows, void* stream);
+/* CrossAttention.forward for one query token per crop (pose_transformer.py:111-124): per (crop, head of 64) softmax((q . k_j) / 8) over
+ * the 192 context rows, times v.  q, out (B, 512); kv rows (b * 192 + j) of a (B * 192, ldkv) matrix with K of head h at column
+ * koff + 64 h and V at koff + 512 + 64 h (the engine: ldkv = 1024 * decoder depth, koff = 1024 * layer).
+ * ldkv % 4 == 0, koff % 4 == 0, koff >= 0, koff + 1024 <= ldkv. */
+int thmr_op_cross_attn(const float* q_dev, const float* kv_dev, int64_t ldkv, int32_t koff, float* out_dev, int32_t B, void* stream);
+/* The patch-embed GEMM's A operand (vit.py:341 x[:, :, :, 32:-32], then :168 Conv2d(3, 1280, k 16, s 16, p 2)): img (B, 3, 256, 256) ->
+ * A (B * 192, 768), row b * 192 + py * 12 + px, column c * 256 + ky * 16 + kx; the zero padding applies to the sliced 192-wide window.
+ * out_split = 0: A fp32; 1: the split3 operand [B*192][768/8][3][8] bf16 (thmr_op_split3 of the fp32 form, bit for bit). */
+int thmr_op_im2col_patch(const float* img_dev, void* A_dev, int32_t B, int32_t out_split, void* stream);
+/* The A operand of Conv1d(C -> *, k 3, padding = dilation = dil) on a channels-last signal, nearest-resampled through src and optionally
+ * ReLU'd first (vanilla_pose_vqvae.py:135-154, resnet.py:55-68):
+ *   out[b][t][dk * C + c] = f(in[b][src[t + (dk - 1) dil]][c])  where 0 <= t + (dk - 1) dil < Tout, else 0
+ * in (Bn, Tin, C), out (Bn, Tout, 3 C), src (Tout) int32 with values in [0, Tin) or null = identity (then Tin >= Tout).  C % 4 == 0, dil >= 1. */
+int thmr_op_conv3_gather(const float* in_dev, float* out_dev, const int32_t* src_or_null, int32_t Bn, int32_t Tin, int32_t Tout,
+                         int32_t C, int32_t dil, int32_t prerelu, void* stream);
+/* The same for the tokenizer encoder's general Conv1d(ks, stride, pad) with the channels zero-padded from C to Cp
+ * (vanilla_pose_vqvae.py:66-88):  out[b][t][kk * Cp + c] = in[b][src[tp]][c], tp = t * stride - pad + kk, where 0 <= tp < Tsrc and c < C,
+ * else 0.  in (Bn, Tin, C), out (Bn, Tout, ks * Cp), src (Tsrc) int32 or null = identity (then Tin >= Tsrc).  Cp >= C, ks >= 1,
+ * stride >= 1, pad >= 0. */
+int thmr_op_conv_gather(const float* in_dev, float* out_dev, const int32_t* src_or_null, int32_t Bn, int32_t Tin, int32_t Tsrc,
+                        int32_t Tout, int32_t C, int32_t Cp, int32_t ks, int32_t stride, int32_t pad, void* stream);
+/* The W operand that goes with those gathers: a Conv1d weight (co, ci, kk) -> (co, kk * cp), element [o][k * cp + i] = w[o][i][k] for
+ * i < ci and 0 for ci <= i < cp.  cp == ci: the plain repack; cp > ci: the zero-padded one; cp < ci is rejected. */
+int thmr_op_conv_repack(const float* w_dev, float* wp_dev, int32_t co, int32_t ci, int32_t cp, int32_t kk, void* stream);
+/* QuantizeEMAReset.quantize (quantize_cnn.py:80-86) behind the x . C^T GEMM:  dist[k] = (sum(x^2) - 2 dot[k]) + cnorm[k] and its argmin,
+ * LOWEST index on ties.  x (rows, 256), dot (rows, 2048), cnorm (2048) -> idx (rows) int32, dist (rows, 2048) optional. */
+int thmr_op_vq_argmin_rows(const float* x_dev, const float* dot_dev, const float* cnorm_dev, int32_t* idx_dev, float* dist_or_null,
+                           int32_t rows, void* stream);
+/* quantize_cnn.py:83 torch.sum(k_w ** 2, dim=0):  cb (ncode, 256) -> cn (ncode). */
+int thmr_op_code_norm(const float* cb_dev, float* cn_dev, int32_t ncode, void* stream);
+/* What follows the read-out GEMM of the SMPL head: mean parameters added, rot6d_to_rotmat (geometry.py:64-84) over the 24 joints,
+ * pred_cam_t = [cam1, cam2, 2 f / (img_size cam0 + 1e-9)] (tokenhmr.py:165-169).  ro (B, ldro).
+ *   kind 0, the token head (token_head.py:99-105,123): ro columns grot 0..5 | shape 6..15 | cam 16..18 | hands 19..30, ldro >= 31;
+ *           pose6d = [ro 0..5 | bpose (B, 126) | ro 19..30] + init_pose; bpose is required;
+ *   kind 1, the HMR2 head (smpl_head.py:56-103): ro columns pose 0..143 | shape 144..153 | cam 154..156, ldro >= 157; bpose is unused.
+ * init_pose (144), init_betas (10), init_cam (3) -> rotmat (B, 24, 3, 3), betas (B, 10), cam (B, 3); pose6d (B, 144), cam_t (B, 3) and
+ * focal (B, 2) are optional (null). */
+int thmr_op_head_finish(int32_t kind, const float* ro_dev, int32_t ldro, const float* bpose_or_null, const float* init_pose_dev,
+                        const float* init_betas_dev, const float* init_cam_dev, float* pose6d_or_null, float* rotmat_dev,
+                        float* betas_dev, float* cam_dev, float* cam_t_or_null, float* focal_or_null, float focal_length, float img_size,
+                        int32_t B, void* stream);
+/* The decoder's first token (pose_transformer.py:350-354 with the zero input token of token_head.py:91): x[b][:] = bias + pos for every
+ * crop; bias, pos (E) -> x (B, E).  B * E <= 2^30. */
+int thmr_op_decoder_init(const float* bias_dev, const float* pos_dev, float* x_dev, int32_t B, int32_t E, void* stream);
+
 /* Stand-alone SMPL model: the GT-side meshes the reference computes per sample on the CPU with
  * smplx.SMPL(gender) inside dataset workers (tokenhmr/lib/datasets/image_dataset.py:151-164,254-270, emdb_dataset.py:184-199)
  * reuse the LBS kernels with their own (male / female) constants.

@@ -253,6 +253,92 @@ def test_stateless_entry_points_reject_bad_arguments_without_a_gpu(built_lib):
     assert L.thmr_cropper_create(-1, C.byref(h)) < 0 and not h.value
 
 
+@pytest.mark.parametrize("exp", [False, True])
+def test_rowops_entry_points_reject_bad_arguments_without_a_gpu(built_lib, exp):
+    """The stateless entry points of the row, glue and head kernels (include/tokenhmr_hip.h) validate before any HIP call, in both
+    libraries: a null buffer, a count <= 0 and every constraint the header names give a negative status and a message that names the
+    operator.  (Several of the launch_* functions behind them validate nothing.)"""
+    L = _cabi.load(exp=exp)
+    null, one = C.c_void_p(0), C.c_void_p(16)      # 16: any non-null address, validation fails before it is dereferenced
+    DIM, ok = 1280, []
+
+    def bad(name, *args):
+        rc = getattr(L, "thmr_op_" + name)(*args)
+        msg = L.thmr_last_error(None)
+        assert rc < 0 and msg and name.encode() in msg, (name, args, rc, msg)
+        ok.append(name)
+
+    #                          part S rows D bias resid xout gamma beta y eps split3 stream
+    bad("splitk_resid_ln", null, 2, 4, DIM, one, one, one, one, one, one, 1e-6, 0, null)
+    bad("splitk_resid_ln", one, 2, 4, DIM, one, one, one, one, one, null, 1e-6, 0, null)
+    bad("splitk_resid_ln", one, 2, 0, DIM, one, one, one, one, one, one, 1e-6, 0, null)        # rows <= 0
+    bad("splitk_resid_ln", one, 2, 4, 1024, one, one, one, one, one, one, 1e-6, 0, null)     # D != 1280
+    bad("splitk_resid_ln", one, 0, 4, DIM, one, one, one, one, one, one, 1e-6, 0, null)        # S < 1
+    for S in (1, 3, 8):                                                                      # split3 output: S in {2, 4} only
+        bad("splitk_resid_ln", one, S, 4, DIM, one, one, one, one, one, one, 1e-6, 1, null)
+    bad("add_ln64", one, null, one, one, one, one, 4, 1e-5, null)
+    bad("add_ln64", one, one, one, one, one, null, 4, 1e-5, null)
+    bad("add_ln64", one, one, one, one, one, one, 0, 1e-5, null)
+    bad("transpose", null, one, 1, 4, 4, null)
+    bad("transpose", one, null, 1, 4, 4, null)
+    for shape in ((0, 4, 4), (1, 0, 4), (1, 4, -1), (65536, 4, 4)):
+        bad("transpose", one, one, *shape, null)
+    bad("softmax_argmax", null, one, one, 4, null)
+    bad("softmax_argmax", one, null, null, 4, null)                                          # both outputs null
+    bad("softmax_argmax", one, one, one, 0, null)
+    bad("cross_attn", null, one, 1024, 0, one, 1, null)
+    bad("cross_attn", one, null, 1024, 0, one, 1, null)
+    bad("cross_attn", one, one, 1024, 0, null, 1, null)
+    bad("cross_attn", one, one, 1024, 0, one, 0, null)
+    bad("cross_attn", one, one, 1026, 0, one, 1, null)                                       # ldkv % 4
+    bad("cross_attn", one, one, 2048, 2, one, 1, null)                                       # koff % 4
+    bad("cross_attn", one, one, 2048, 1028, one, 1, null)                                    # koff + 1024 > ldkv
+    bad("cross_attn", one, one, 1020, 0, one, 1, null)
+    bad("cross_attn", one, one, 2048, -4, one, 1, null)
+    for split in (0, 1):
+        bad("im2col_patch", null, one, 1, split, null)
+        bad("im2col_patch", one, null, 1, split, null)
+        bad("im2col_patch", one, one, 0, split, null)
+    #                       in out src Bn Tin Tout C dil prerelu
+    bad("conv3_gather", null, one, null, 1, 8, 8, 8, 1, 0, null)
+    bad("conv3_gather", one, null, null, 1, 8, 8, 8, 1, 0, null)
+    bad("conv3_gather", one, one, null, 0, 8, 8, 8, 1, 0, null)
+    bad("conv3_gather", one, one, null, 1, 8, 8, 6, 1, 0, null)                              # C % 4
+    bad("conv3_gather", one, one, null, 1, 8, 8, 8, 0, 0, null)                              # dil < 1
+    bad("conv3_gather", one, one, null, 1, 4, 8, 8, 1, 0, null)                              # identity table but Tin < Tout
+    #                      in out src Bn Tin Tsrc Tout C Cp ks stride pad
+    bad("conv_gather", null, one, null, 1, 8, 8, 8, 8, 8, 3, 1, 1, null)
+    bad("conv_gather", one, null, null, 1, 8, 8, 8, 8, 8, 3, 1, 1, null)
+    bad("conv_gather", one, one, null, 1, 8, 8, 0, 8, 8, 3, 1, 1, null)
+    bad("conv_gather", one, one, null, 1, 8, 8, 8, 8, 4, 3, 1, 1, null)                      # Cp < C
+    bad("conv_gather", one, one, null, 1, 8, 8, 8, 8, 8, 0, 1, 1, null)                      # ks < 1
+    bad("conv_gather", one, one, null, 1, 8, 8, 8, 8, 8, 3, 0, 1, null)                      # stride < 1
+    bad("conv_gather", one, one, null, 1, 8, 16, 8, 8, 8, 3, 1, 1, null)                     # identity table but Tin < Tsrc
+    bad("conv_repack", null, one, 4, 4, 4, 3, null)
+    bad("conv_repack", one, null, 4, 4, 4, 3, null)
+    bad("conv_repack", one, one, 0, 4, 4, 3, null)
+    bad("conv_repack", one, one, 4, 6, 4, 3, null)                                           # cp < ci
+    bad("vq_argmin_rows", null, one, one, one, null, 1, null)
+    bad("vq_argmin_rows", one, one, one, null, one, 1, null)                                 # idx is not optional
+    bad("vq_argmin_rows", one, one, one, one, one, 0, null)
+    bad("code_norm", null, one, 4, null)
+    bad("code_norm", one, null, 4, null)
+    bad("code_norm", one, one, 0, null)
+    #                      kind ro ldro bpose ipose ibetas icam pose6d rotmat betas cam cam_t focal f img B
+    bad("head_finish", 0, null, 32, one, one, one, one, one, one, one, one, one, one, 5000.0, 256.0, 1, null)
+    bad("head_finish", 0, one, 32, one, one, one, one, null, null, one, one, null, null, 5000.0, 256.0, 1, null)   # rotmat is not optional
+    bad("head_finish", 0, one, 32, null, one, one, one, one, one, one, one, one, one, 5000.0, 256.0, 1, null)      # token head without bpose
+    bad("head_finish", 0, one, 30, one, one, one, one, one, one, one, one, one, one, 5000.0, 256.0, 1, null)       # ldro below 31 columns
+    bad("head_finish", 1, one, 156, null, one, one, one, one, one, one, one, one, one, 5000.0, 256.0, 1, null)     # ldro below 157 columns
+    bad("head_finish", 1, one, 160, null, one, one, one, one, one, one, one, one, one, 5000.0, 256.0, 0, null)     # B <= 0
+    bad("head_finish", 2, one, 160, one, one, one, one, one, one, one, one, one, one, 5000.0, 256.0, 1, null)      # no such kind
+    bad("decoder_init", null, one, one, 1, 8, null)
+    bad("decoder_init", one, one, null, 1, 8, null)
+    bad("decoder_init", one, one, one, 0, 8, null)
+    bad("decoder_init", one, one, one, 1, 0, null)
+    assert set(ok) == {s[len("thmr_op_"):] for s in _cabi.ROWOPS_SYMBOLS}       # every one of the 13 entry points was refused at least once
+
+
 def test_gemm_k_loops_carry_no_valu_instruction(built_lib, tmp_path):
     """ISA-level regression guard (CPU): on gfx950 every VALU instruction issued between fp32 MFMAs costs matrix-pipe time
     (profiles/r1_mfma_valu_microbench.log), so the K loops of the product GEMM (128x160 tile, fc1 epilogue) and of the

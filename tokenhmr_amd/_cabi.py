@@ -111,6 +111,11 @@ def declared_symbols():
 
 _libs = {}
 
+# the stateless operators of the row / glue / head kernels: new symbols under ABI 5, which an older build loaded by path lacks
+ROWOPS_SYMBOLS = ("thmr_op_splitk_resid_ln", "thmr_op_add_ln64", "thmr_op_transpose", "thmr_op_softmax_argmax", "thmr_op_cross_attn",
+                  "thmr_op_im2col_patch", "thmr_op_conv3_gather", "thmr_op_conv_gather", "thmr_op_conv_repack", "thmr_op_vq_argmin_rows",
+                  "thmr_op_code_norm", "thmr_op_head_finish", "thmr_op_decoder_init")
+
 
 def load(exp=None):
     """The shipped library, or (exp=True, or exp=None with THMR_LIB=exp in the environment) the experiments build.
@@ -146,7 +151,7 @@ def load(exp=None):
     older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
     # a build loaded by path may also predate thmr_renderer_sheet / thmr_debug_vit_plan (added without an ABI change: new symbols, no layout touched)
     missing = [s for s in declared_symbols() if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
-               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan"))]
+               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS)]
     if missing:
         raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -187,6 +192,20 @@ def load(exp=None):
     lib.thmr_op_gemm_split3_out_split3.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, f32, i32, i32, vp]
     lib.thmr_op_rot6d.argtypes = [vp, vp, i32, vp]
     lib.thmr_op_aa_to_rotmat.argtypes = [vp, vp, i32, vp]
+    if hasattr(lib, "thmr_op_splitk_resid_ln"):          # the row / glue / head operators (added without an ABI change)
+        lib.thmr_op_splitk_resid_ln.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, i32, vp]
+        lib.thmr_op_add_ln64.argtypes = [vp, vp, vp, vp, vp, vp, i32, f32, vp]
+        lib.thmr_op_transpose.argtypes = [vp, vp, i32, i32, i32, vp]
+        lib.thmr_op_softmax_argmax.argtypes = [vp, vp, vp, i32, vp]
+        lib.thmr_op_cross_attn.argtypes = [vp, vp, i64, i32, vp, i32, vp]
+        lib.thmr_op_im2col_patch.argtypes = [vp, vp, i32, i32, vp]
+        lib.thmr_op_conv3_gather.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+        lib.thmr_op_conv_gather.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+        lib.thmr_op_conv_repack.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+        lib.thmr_op_vq_argmin_rows.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+        lib.thmr_op_code_norm.argtypes = [vp, vp, i32, vp]
+        lib.thmr_op_head_finish.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp]
+        lib.thmr_op_decoder_init.argtypes = [vp, vp, vp, i32, i32, vp]
     lib.thmr_smpl_create.argtypes = [C.POINTER(SmplDesc), i32, i32, C.POINTER(vp)]
     lib.thmr_smpl_destroy.argtypes = [vp]
     lib.thmr_smpl_destroy.restype = None

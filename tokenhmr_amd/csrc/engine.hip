@@ -2112,6 +2112,140 @@ int thmr_op_aa_to_rotmat(const float* aa, float* R, int32_t n, void* stream) {
     return 0;
 }
 
+// ---- stateless entry points of the row, glue and head kernels (tests/test_gpu_rowops.py): thin wrappers over the launch_* functions the
+// engine calls; every argument is validated here, before any HIP call, because several of those launchers validate nothing ----
+int thmr_op_splitk_resid_ln(const float* part, int32_t S, int32_t rows, int32_t D, const float* bias, const float* resid, float* xout,
+                            const float* gamma, const float* beta, void* y, float eps, int32_t y_is_split3, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!part || !bias || !resid || !xout || !gamma || !beta || !y) return fail(e, THMR_ERR_INVALID, "splitk_resid_ln: null buffer");
+    if (rows <= 0 || S < 1 || D != DIM) return fail(e, THMR_ERR_INVALID, "splitk_resid_ln: rows >= 1, S >= 1 and D == 1280 are required");
+    if (y_is_split3 && S != 2 && S != 4) return fail(e, THMR_ERR_INVALID, "splitk_resid_ln: the split3 output exists for S = 2 and 4 only");
+    LAUNCH_OK(launch_splitk_resid_ln(part, S, rows, D, bias, resid, xout, gamma, beta, static_cast<float*>(y), eps,
+                                     static_cast<hipStream_t>(stream), y_is_split3 != 0));
+    return 0;
+}
+
+int thmr_op_add_ln64(const float* x, const float* y, const float* gamma, const float* beta, float* s_out, float* z_out, int32_t rows,
+                     float eps, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!x || !y || !gamma || !beta || !s_out || !z_out) return fail(e, THMR_ERR_INVALID, "add_ln64: null buffer");
+    if (rows <= 0) return fail(e, THMR_ERR_INVALID, "add_ln64: rows >= 1 is required");
+    LAUNCH_OK(launch_add_ln64(x, y, gamma, beta, s_out, z_out, rows, eps, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_transpose(const float* in, float* out, int32_t Bn, int32_t R, int32_t C, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!in || !out) return fail(e, THMR_ERR_INVALID, "transpose: null buffer");
+    if (Bn <= 0 || R <= 0 || C <= 0 || Bn > 65535 || (R + 31) / 32 > 65535)
+        return fail(e, THMR_ERR_INVALID, "transpose: Bn, R, C >= 1, Bn <= 65535 and R <= 32 * 65535 are required (grid y / z)");
+    LAUNCH_OK(launch_transpose(in, out, Bn, R, C, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_softmax_argmax(const float* logits, float* probs, int32_t* idx, int32_t rows, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!logits) return fail(e, THMR_ERR_INVALID, "softmax_argmax: null buffer");
+    if (!probs && !idx) return fail(e, THMR_ERR_INVALID, "softmax_argmax: probs and idx are both null");
+    if (rows <= 0) return fail(e, THMR_ERR_INVALID, "softmax_argmax: rows >= 1 is required");
+    LAUNCH_OK(launch_softmax_argmax2048(logits, probs, idx, rows, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_cross_attn(const float* q, const float* kv, int64_t ldkv, int32_t koff, float* out, int32_t B, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!q || !kv || !out) return fail(e, THMR_ERR_INVALID, "cross_attn: null buffer");
+    if (B <= 0 || B > (1 << 24)) return fail(e, THMR_ERR_INVALID, "cross_attn: 1 <= B <= 2^24 is required");
+    if (ldkv <= 0 || koff < 0 || (ldkv % 4) != 0 || (koff % 4) != 0 || (int64_t)koff + 2 * INNER > ldkv)
+        return fail(e, THMR_ERR_INVALID, "cross_attn: ldkv % 4 == 0, koff % 4 == 0 and koff + 1024 <= ldkv are required");
+    LAUNCH_OK(launch_cross_attn(q, kv, ldkv, koff, out, B, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_im2col_patch(const float* img, void* A, int32_t B, int32_t out_split, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!img || !A) return fail(e, THMR_ERR_INVALID, "im2col_patch: null buffer");
+    if (B <= 0) return fail(e, THMR_ERR_INVALID, "im2col_patch: B >= 1 is required");
+    if (out_split) LAUNCH_OK(launch_im2col_patch_split3(img, A, B, static_cast<hipStream_t>(stream)));
+    else LAUNCH_OK(launch_im2col_patch(img, static_cast<float*>(A), B, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_conv3_gather(const float* in, float* out, const int32_t* src, int32_t Bn, int32_t Tin, int32_t Tout, int32_t C, int32_t dil,
+                         int32_t prerelu, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!in || !out) return fail(e, THMR_ERR_INVALID, "conv3_gather: null buffer");
+    if (Bn <= 0 || Tin <= 0 || Tout <= 0 || C <= 0 || (C % 4) != 0 || dil < 1)
+        return fail(e, THMR_ERR_INVALID, "conv3_gather: Bn, Tin, Tout >= 1, C % 4 == 0 and dil >= 1 are required");
+    if (!src && Tin < Tout) return fail(e, THMR_ERR_INVALID, "conv3_gather: without an index table Tin >= Tout is required");
+    LAUNCH_OK(launch_conv3_gather(in, out, src, Bn, Tin, Tout, C, dil, prerelu, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_conv_gather(const float* in, float* out, const int32_t* src, int32_t Bn, int32_t Tin, int32_t Tsrc, int32_t Tout, int32_t C,
+                        int32_t Cp, int32_t ks, int32_t stride, int32_t pad, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!in || !out) return fail(e, THMR_ERR_INVALID, "conv_gather: null buffer");
+    if (Bn <= 0 || Tin <= 0 || Tsrc <= 0 || Tout <= 0 || C <= 0 || Cp < C || ks < 1 || stride < 1 || pad < 0)
+        return fail(e, THMR_ERR_INVALID, "conv_gather: counts >= 1, Cp >= C, ks >= 1, stride >= 1 and pad >= 0 are required");
+    if (!src && Tin < Tsrc) return fail(e, THMR_ERR_INVALID, "conv_gather: without an index table Tin >= Tsrc is required");
+    LAUNCH_OK(launch_conv_gather_general(in, out, src, Bn, Tin, Tsrc, Tout, C, Cp, ks, stride, pad, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_conv_repack(const float* w, float* wp, int32_t co, int32_t ci, int32_t cp, int32_t kk, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!w || !wp) return fail(e, THMR_ERR_INVALID, "conv_repack: null buffer");
+    if (co <= 0 || ci <= 0 || kk <= 0 || cp < ci) return fail(e, THMR_ERR_INVALID, "conv_repack: co, ci, kk >= 1 and cp >= ci are required");
+    if (cp == ci) LAUNCH_OK(launch_conv_repack(w, wp, co, ci, kk, static_cast<hipStream_t>(stream)));
+    else LAUNCH_OK(launch_conv_repack_pad(w, wp, co, ci, cp, kk, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_vq_argmin_rows(const float* x, const float* dot, const float* cnorm, int32_t* idx, float* dist, int32_t rows, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!x || !dot || !cnorm || !idx) return fail(e, THMR_ERR_INVALID, "vq_argmin_rows: null buffer");
+    if (rows <= 0) return fail(e, THMR_ERR_INVALID, "vq_argmin_rows: rows >= 1 is required");
+    LAUNCH_OK(launch_vq_argmin_rows(x, dot, cnorm, idx, dist, rows, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_code_norm(const float* cb, float* cn, int32_t ncode, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!cb || !cn) return fail(e, THMR_ERR_INVALID, "code_norm: null buffer");
+    if (ncode <= 0) return fail(e, THMR_ERR_INVALID, "code_norm: ncode >= 1 is required");
+    LAUNCH_OK(launch_code_norm(cb, cn, ncode, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_head_finish(int32_t kind, const float* ro, int32_t ldro, const float* bpose, const float* init_pose, const float* init_betas,
+                        const float* init_cam, float* pose6d, float* rotmat, float* betas, float* cam, float* cam_t, float* focal,
+                        float focal_length, float img_size, int32_t B, void* stream) {
+    thmr_engine* e = nullptr;
+    if (kind != 0 && kind != 1) return fail(e, THMR_ERR_INVALID, "head_finish: kind is 0 (token head) or 1 (HMR2 head)");
+    if (!ro || !init_pose || !init_betas || !init_cam || !rotmat || !betas || !cam) return fail(e, THMR_ERR_INVALID, "head_finish: null buffer");
+    if (kind == 0 && !bpose) return fail(e, THMR_ERR_INVALID, "head_finish: the token head needs the VQ-decoded body pose");
+    if (B <= 0) return fail(e, THMR_ERR_INVALID, "head_finish: B >= 1 is required");
+    if (ldro < (kind == 0 ? 31 : THMR_HMR2_RO_ROWS))
+        return fail(e, THMR_ERR_INVALID, "head_finish: ldro is below the read-out's column count (31 token head, 157 HMR2 head)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (kind == 0)
+        LAUNCH_OK(launch_assemble(ro, ldro, bpose, init_pose, init_betas, init_cam, pose6d, rotmat, betas, cam, cam_t, focal, focal_length,
+                                  img_size, B, st));
+    else
+        LAUNCH_OK(launch_hmr2_finish(ro, ldro, init_pose, init_betas, init_cam, pose6d, rotmat, betas, cam, cam_t, focal, focal_length,
+                                     img_size, B, st));
+    return 0;
+}
+
+int thmr_op_decoder_init(const float* bias, const float* pos, float* x, int32_t B, int32_t E, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!bias || !pos || !x) return fail(e, THMR_ERR_INVALID, "decoder_init: null buffer");
+    if (B <= 0 || E <= 0 || (int64_t)B * E > (int64_t)1 << 30) return fail(e, THMR_ERR_INVALID, "decoder_init: B, E >= 1 and B * E <= 2^30 are required");
+    LAUNCH_OK(launch_decoder_init(bias, pos, x, B, E, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 // ---- stand-alone SMPL model ----
 struct thmr_smpl {
     float* mem = nullptr;

@@ -230,3 +230,192 @@ def aa_to_rotmat(theta):
     with torch.cuda.device(theta.device):
         _check(_L().thmr_op_aa_to_rotmat(_p(x), _p(R), n, _s(theta)))
     return R
+
+
+# ---- the row, glue and head kernels (csrc/rowops.hip, head.hip, hmr2_head.hip), each as the engine launches it ----
+def _req_i32(*ts):
+    for t in ts:
+        if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
+            raise ValueError("index tables are contiguous int32 CUDA tensors")
+
+
+def splitk_resid_ln(part, bias, resid, gamma, beta, eps, y_split3=False, inplace=False):
+    """part (S, rows, 1280) split-K partial sums -> (xout, y): xout = resid + ((((part[0] + part[1]) + ...) + bias), y = LayerNorm(xout).
+    y_split3: y as a split3 operand (int16 (rows, 160, 3, 8)) instead of fp32.  inplace: xout IS resid (what the engine passes; resid is
+    overwritten)."""
+    _req(part, bias, resid, gamma, beta)
+    S, rows, D = part.shape
+    if resid.shape != (rows, D):
+        raise ValueError("resid is (rows, D)")
+    xout = resid if inplace else torch.empty(rows, D, device=part.device, dtype=torch.float32)
+    y = (torch.empty(rows, D // 8, 3, 8, device=part.device, dtype=torch.int16) if y_split3
+         else torch.empty(rows, D, device=part.device, dtype=torch.float32))
+    with torch.cuda.device(part.device):
+        _check(_L().thmr_op_splitk_resid_ln(_p(part), S, rows, D, _p(bias), _p(resid), _p(xout), _p(gamma), _p(beta), _p(y), float(eps),
+                                            int(y_split3), _s(part)))
+    return xout, y
+
+
+def add_ln64(x, y, gamma, beta, eps):
+    """(rows, 64) x, y -> (s, z): s = x + y, z = LayerNorm64(s)."""
+    _req(x, y, gamma, beta)
+    if x.shape != y.shape or x.shape[-1] != 64:
+        raise ValueError("add_ln64 needs two (rows, 64) tensors")
+    s, z = torch.empty_like(x), torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_add_ln64(_p(x), _p(y), _p(gamma), _p(beta), _p(s), _p(z), x.numel() // 64, float(eps), _s(x)))
+    return s, z
+
+
+def transpose(x, out=None):
+    """(Bn, R, C) -> (Bn, C, R); `out`: write into this tensor (the tests pre-fill it)."""
+    _req(x, out)
+    Bn, R, Cc = x.shape
+    if out is None:
+        out = torch.empty(Bn, Cc, R, device=x.device, dtype=torch.float32)
+    elif out.shape != (Bn, Cc, R):
+        raise ValueError("out must be (Bn, C, R)")
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_transpose(_p(x), _p(out), Bn, R, Cc, _s(x)))
+    return out
+
+
+def softmax_argmax(logits, probs=True, idx=True):
+    """logits (rows, 2048) -> (probs (rows, 2048) or None, idx (rows) int32 or None): softmax and the lowest index of the row maximum."""
+    _req(logits)
+    rows = logits.shape[0]
+    if logits.shape != (rows, 2048):
+        raise ValueError("softmax_argmax needs (rows, 2048) logits")
+    p = torch.empty_like(logits) if probs else None
+    i = torch.empty(rows, device=logits.device, dtype=torch.int32) if idx else None
+    with torch.cuda.device(logits.device):
+        _check(_L().thmr_op_softmax_argmax(_p(logits), _p(p), _p(i), rows, _s(logits)))
+    return p, i
+
+
+def cross_attn(q, kv, koff=0):
+    """q (B, 512), kv (B * 192, ldkv) with K | V of this layer at columns koff ... koff + 1023 -> (B, 512)."""
+    _req(q, kv)
+    B = q.shape[0]
+    if q.shape != (B, 512) or kv.dim() != 2 or kv.shape[0] != B * 192:
+        raise ValueError("cross_attn needs q (B, 512) and kv (B * 192, ldkv)")
+    out = torch.empty(B, 512, device=q.device, dtype=torch.float32)
+    with torch.cuda.device(q.device):
+        _check(_L().thmr_op_cross_attn(_p(q), _p(kv), kv.shape[1], int(koff), _p(out), B, _s(q)))
+    return out
+
+
+def im2col_patch(img, out_split=False):
+    """img (B, 3, 256, 256) -> the patch-embed A operand (B * 192, 768) fp32, or (out_split) int16 (B * 192, 96, 3, 8)."""
+    _req(img)
+    B = img.shape[0]
+    if img.shape != (B, 3, 256, 256):
+        raise ValueError("im2col_patch needs (B, 3, 256, 256)")
+    out = (torch.empty(B * 192, 96, 3, 8, device=img.device, dtype=torch.int16) if out_split
+           else torch.empty(B * 192, 768, device=img.device, dtype=torch.float32))
+    with torch.cuda.device(img.device):
+        _check(_L().thmr_op_im2col_patch(_p(img), _p(out), B, int(out_split), _s(img)))
+    return out
+
+
+def conv3_gather(x, Tout, src=None, dil=1, prerelu=False, out=None):
+    """x (Bn, Tin, C) channels-last -> (Bn, Tout, 3 * C): the A operand of Conv1d(k 3, padding = dilation = dil) on the signal resampled
+    through `src` ((Tout) int32, None = identity).  `out`: write into this tensor."""
+    _req(x, out)
+    _req_i32(src)
+    Bn, Tin, Cc = x.shape
+    if src is not None and src.numel() != Tout:
+        raise ValueError("src holds one index per output position")
+    if out is None:
+        out = torch.empty(Bn, Tout, 3 * Cc, device=x.device, dtype=torch.float32)
+    elif out.shape != (Bn, Tout, 3 * Cc):
+        raise ValueError("out must be (Bn, Tout, 3 C)")
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_conv3_gather(_p(x), _p(out), _p(src), Bn, Tin, int(Tout), Cc, int(dil), int(prerelu), _s(x)))
+    return out
+
+
+def conv_gather(x, Tout, ks, stride, pad, Cp=None, src=None, Tsrc=None, out=None):
+    """x (Bn, Tin, C) channels-last -> (Bn, Tout, ks * Cp): the A operand of Conv1d(ks, stride, pad) with the channels zero-padded to Cp,
+    on the signal of length Tsrc (default Tin) resampled through `src` ((Tsrc) int32, None = identity)."""
+    _req(x, out)
+    _req_i32(src)
+    Bn, Tin, Cc = x.shape
+    Cp = Cc if Cp is None else int(Cp)
+    Tsrc = (Tin if src is None else src.numel()) if Tsrc is None else int(Tsrc)
+    if src is not None and src.numel() != Tsrc:
+        raise ValueError("src holds one index per resampled position")
+    if out is None:
+        out = torch.empty(Bn, Tout, ks * Cp, device=x.device, dtype=torch.float32)
+    elif out.shape != (Bn, Tout, ks * Cp):
+        raise ValueError("out must be (Bn, Tout, ks Cp)")
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_conv_gather(_p(x), _p(out), _p(src), Bn, Tin, Tsrc, int(Tout), Cc, Cp, int(ks), int(stride), int(pad), _s(x)))
+    return out
+
+
+def conv_repack(w, cp=None):
+    """Conv1d weight (co, ci, kk) -> (co, kk * cp), [o][k * cp + i] = w[o][i][k], zero for ci <= i < cp (cp defaults to ci)."""
+    _req(w)
+    co, ci, kk = w.shape
+    cp = ci if cp is None else int(cp)
+    out = torch.empty(co, kk * cp, device=w.device, dtype=torch.float32)
+    with torch.cuda.device(w.device):
+        _check(_L().thmr_op_conv_repack(_p(w), _p(out), co, ci, cp, kk, _s(w)))
+    return out
+
+
+def vq_argmin_rows(x, dot, cnorm, want_dist=True):
+    """x (rows, 256), dot = x @ codebook.T (rows, 2048), cnorm (2048) -> (idx (rows) int32, dist (rows, 2048) or None)."""
+    _req(x, dot, cnorm)
+    rows = x.shape[0]
+    if x.shape != (rows, 256) or dot.shape != (rows, 2048) or cnorm.shape != (2048,):
+        raise ValueError("vq_argmin_rows needs x (rows, 256), dot (rows, 2048), cnorm (2048)")
+    idx = torch.empty(rows, device=x.device, dtype=torch.int32)
+    dist = torch.empty(rows, 2048, device=x.device, dtype=torch.float32) if want_dist else None
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_vq_argmin_rows(_p(x), _p(dot), _p(cnorm), _p(idx), _p(dist), rows, _s(x)))
+    return idx, dist
+
+
+def code_norm(cb):
+    """codebook (ncode, 256) -> squared norms (ncode)."""
+    _req(cb)
+    n = cb.shape[0]
+    if cb.shape != (n, 256):
+        raise ValueError("code_norm needs (ncode, 256)")
+    cn = torch.empty(n, device=cb.device, dtype=torch.float32)
+    with torch.cuda.device(cb.device):
+        _check(_L().thmr_op_code_norm(_p(cb), _p(cn), n, _s(cb)))
+    return cn
+
+
+def head_finish(kind, ro, init_pose, init_betas, init_cam, bpose=None, focal_length=5000.0, img_size=256.0,
+                want_pose6d=True, want_cam_t=True, want_focal=True):
+    """The finish of the SMPL head behind the read-out GEMM.  kind "token": ro (B, ld >= 31) + bpose (B, 126); "hmr2": ro (B, ld >= 157).
+    Returns a dict: rotmat (B, 24, 3, 3), betas (B, 10), cam (B, 3) and — unless switched off, then None — pose6d (B, 144), cam_t (B, 3),
+    focal (B, 2)."""
+    _req(ro, init_pose, init_betas, init_cam, bpose)
+    B, ld = ro.shape
+    if init_pose.numel() != 144 or init_betas.numel() != 10 or init_cam.numel() != 3 or (bpose is not None and bpose.shape != (B, 126)):
+        raise ValueError("head_finish: init_pose (144), init_betas (10), init_cam (3), bpose (B, 126)")
+    new = lambda *s: torch.empty(*s, device=ro.device, dtype=torch.float32)
+    o = {"rotmat": new(B, 24, 3, 3), "betas": new(B, 10), "cam": new(B, 3), "pose6d": new(B, 144) if want_pose6d else None,
+         "cam_t": new(B, 3) if want_cam_t else None, "focal": new(B, 2) if want_focal else None}
+    with torch.cuda.device(ro.device):
+        _check(_L().thmr_op_head_finish({"token": 0, "hmr2": 1}[kind], _p(ro), ld, _p(bpose), _p(init_pose), _p(init_betas), _p(init_cam),
+                                        _p(o["pose6d"]), _p(o["rotmat"]), _p(o["betas"]), _p(o["cam"]), _p(o["cam_t"]), _p(o["focal"]),
+                                        float(focal_length), float(img_size), B, _s(ro)))
+    return o
+
+
+def decoder_init(bias, pos, B):
+    """bias, pos (E) -> x (B, E) = bias + pos for every crop."""
+    _req(bias, pos)
+    E = bias.numel()
+    if pos.numel() != E:
+        raise ValueError("bias and pos have the same length")
+    x = torch.empty(B, E, device=bias.device, dtype=torch.float32)
+    with torch.cuda.device(bias.device):
+        _check(_L().thmr_op_decoder_init(_p(bias), _p(pos), _p(x), int(B), E, _s(bias)))
+    return x
