@@ -400,8 +400,11 @@ int  thmr_smpl_forward(thmr_smpl* m, const float* pose_dev, int32_t pose2rot, co
  * Replaces compute_similarity_transform / eval_pose and the arithmetic of Evaluator.__call__
  * (tokenhmr/lib/utils/pose_utils.py:61-143, :201-275): pelvis alignment, MPJPE, PA-MPJPE (3x3 SVD Procrustes), PVE, in mm.
  *   pred_joints (B,n_joints,3); gt_joints (B,n_joints,gt_stride) (gt_stride = 4 for batch['keypoints_3d'] with its confidence column)
- *   pelvis_mode 0: joint pelvis_ind; 1: (joint1 + joint2)/2 (EMDB branch).  verts may be NULL (no PVE).
- *   pelvis_scratch (B,6) receives [pred_pelvis | gt_pelvis]. */
+ *   pelvis_mode 0: joint pelvis_ind; 1: (joint1 + joint2)/2 (EMDB branch); any other value is refused.  verts may be NULL (no PVE).
+ *   pelvis_scratch (B,6) receives [pred_pelvis | gt_pelvis].
+ *   Refused before any HIP call: a null buffer, n_kp outside [1, 64], gt_stride < 3, B < 1, n_joints < 3, pelvis_ind outside
+ *   [0, n_joints), pelvis_mode outside {0, 1}, and n_verts < 1 when pred_verts, gt_verts and pve_mm are all given (both vertex
+ *   buffers are (B,n_verts,3)).  A kp_list entry outside [0, n_joints) is never read through: that crop's mpjpe and re are NaN. */
 int thmr_eval_pose(const float* pred_joints_dev, const float* gt_joints_dev, int32_t n_joints, int32_t gt_stride,
                    const int32_t* kp_list_dev, int32_t n_kp, int32_t pelvis_ind, int32_t pelvis_mode,
                    const float* pred_verts_dev, const float* gt_verts_dev, int32_t n_verts, int32_t B,

@@ -116,3 +116,107 @@ def test_evaluator_fills_its_host_arrays_lazily(monkeypatch):
     ev2({"pred_keypoints_3d": torch.zeros(2, 44, 3), "pred_vertices": torch.zeros(2, 10, 3)},
         {"keypoints_3d": torch.zeros(2, 44, 4), "vertices": torch.zeros(2, 10, 3), "imgname": []})
     assert ev2.get_metrics_dict()["model_pve"] == 0.0 and "mode_pve" not in ev2._arrays
+
+
+def test_eval_pose_gpu_refuses_bad_arguments_on_the_host():
+    """Every shape and argument rule of eval_pose_gpu is checked before the device is, so it is testable on CPU tensors: a well-formed
+    call gets as far as the device check (RuntimeError), a malformed one never does.  eval_pve_kernel indexes both vertex tensors by
+    pred_vertices.shape[1]: a shorter gt_vertices used to be read past its end, where the reference raises a broadcast error."""
+    from tokenhmr_amd.evaluator import eval_pose_gpu
+    pj, gj, v = torch.zeros(2, 44, 3), torch.zeros(2, 44, 4), torch.zeros(2, 10, 3)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        eval_pose_gpu(pj, gj, KP, 39, 0, v, v)
+    for pv, gv in ((v, torch.zeros(2, 9, 3)), (torch.zeros(2, 9, 3), v), (v, torch.zeros(1, 10, 3)), (torch.zeros(3, 10, 3), torch.zeros(3, 10, 3)),
+                   (torch.zeros(2, 10, 4), torch.zeros(2, 10, 4)), (v, torch.zeros(2, 10, 4)), (torch.zeros(2, 0, 3), torch.zeros(2, 0, 3)),
+                   (torch.zeros(2, 30), torch.zeros(2, 30)), (torch.zeros(20, 3), torch.zeros(20, 3))):
+        with pytest.raises(ValueError, match="vertex shapes"):
+            eval_pose_gpu(pj, gj, KP, 39, 0, pv, gv)
+    for bad_pj, bad_gj in ((torch.zeros(2, 44, 2), gj), (pj, torch.zeros(2, 43, 4)), (pj, torch.zeros(3, 44, 4)), (pj, torch.zeros(2, 44, 5)),
+                           (torch.zeros(44, 3), torch.zeros(44, 4)), (torch.zeros(0, 44, 3), torch.zeros(0, 44, 4))):
+        with pytest.raises(ValueError, match="joint shapes"):
+            eval_pose_gpu(bad_pj, bad_gj, KP, 39)
+    big_p, big_g = torch.zeros(2, 70, 3), torch.zeros(2, 70, 4)
+    with pytest.raises(ValueError, match="the kernel holds 64"):
+        eval_pose_gpu(big_p, big_g, list(range(65)), 39)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):          # 64 is the kernel's size: accepted
+        eval_pose_gpu(big_p, big_g, list(range(64)), 39)
+    for mode in (2, -1, 3, 0.5, None):
+        with pytest.raises(ValueError, match="pelvis_mode"):
+            eval_pose_gpu(pj, gj, KP, 39, mode)
+    with pytest.raises(ValueError, match="joints 1 and 2"):
+        eval_pose_gpu(torch.zeros(2, 2, 3), torch.zeros(2, 2, 3), [0, 1], 0, 1)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):          # three joints are enough for mode 1
+        eval_pose_gpu(torch.zeros(2, 3, 3), torch.zeros(2, 3, 3), [0, 1], 0, 1)
+    for kpl in ([], [44], [-1, 3]):
+        with pytest.raises(IndexError):
+            eval_pose_gpu(pj, gj, kpl, 39)
+    with pytest.raises(IndexError, match="pelvis_ind"):
+        eval_pose_gpu(pj, gj, KP, 44)
+    meta = lambda *s: torch.zeros(*s, device="meta")          # noqa: E731  a second device that needs no GPU
+    for args in ((pj, meta(2, 44, 4), KP, 39), (meta(2, 44, 3), gj, KP, 39), (pj, gj, KP, 39, 0, meta(2, 10, 3), v), (pj, gj, KP, 39, 0, v, meta(2, 10, 3))):
+        with pytest.raises(ValueError, match="different devices"):
+            eval_pose_gpu(*args)
+    with pytest.raises(ValueError, match="vertex shapes"):          # shapes before devices
+        eval_pose_gpu(pj, gj, KP, 39, 0, meta(2, 9, 3), v)
+
+
+def test_regress_joints_gpu_refuses_bad_arguments_on_the_host():
+    """regress_joints_kernel reads J as (nj, verts.shape[1]): a J with another second dimension used to be read past its end (or mis-strided),
+    where torch.matmul raises.  Shapes are checked first, devices after, the GPU last."""
+    from tokenhmr_amd.evaluator import regress_joints_gpu
+    J, v = torch.zeros(24, 10), torch.zeros(2, 10, 3)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        regress_joints_gpu(J, v)
+    for bad in (torch.zeros(10), torch.zeros(1, 24, 10), torch.zeros(0, 10)):
+        with pytest.raises(ValueError, match="J must be"):
+            regress_joints_gpu(bad, v)
+    for bad in (torch.zeros(24, 9), torch.zeros(24, 11), torch.zeros(24, 30)):
+        with pytest.raises(ValueError, match="regresses from"):
+            regress_joints_gpu(bad, v)
+    for bad in (torch.zeros(10, 3), torch.zeros(2, 10, 4), torch.zeros(2, 10), torch.zeros(0, 10, 3), torch.zeros(2, 0, 3), torch.zeros(1, 2, 10, 3)):
+        with pytest.raises(ValueError, match="verts must be"):
+            regress_joints_gpu(J, bad)
+    with pytest.raises(ValueError, match="different devices"):
+        regress_joints_gpu(torch.zeros(24, 10, device="meta"), v)
+    with pytest.raises(ValueError, match="different devices"):
+        regress_joints_gpu(J, torch.zeros(2, 10, 3, device="meta"))
+    with pytest.raises(ValueError, match="regresses from"):          # shapes before devices
+        regress_joints_gpu(torch.zeros(24, 9, device="meta"), v)
+
+
+@pytest.mark.parametrize("exp", [False, True])
+def test_eval_entry_points_reject_bad_arguments_without_a_gpu(built_lib, exp):
+    """thmr_eval_pose / thmr_regress_joints validate before any HIP call, in both libraries: with dummy pointers and no GPU every refusal
+    below is a negative status and a message, never a launch.  New here: n_verts < 1 when PVE is asked for (all three vertex pointers
+    given) divided by zero, and a pelvis_mode other than 0 or 1 was silently treated as 1."""
+    import ctypes as C
+    from tokenhmr_amd import _cabi
+    L = _cabi.load(exp=exp)
+    null, one = C.c_void_p(0), C.c_void_p(16)      # 16: any non-null address, validation fails before it is dereferenced
+
+    def refused(*args, fn="thmr_eval_pose", says=None):
+        rc = getattr(L, fn)(*args)
+        msg = L.thmr_last_error(None)
+        assert rc < 0 and msg and (says is None or says in msg), (args, rc, msg)
+
+    #        pred gt nj stride kp nkp pelvis mode pv gv nv B mp re pve pelv stream
+    for nv in (0, -1):
+        refused(one, one, 44, 4, one, 14, 39, 0, one, one, nv, 2, one, one, one, one, null, says=b"n_verts")
+    for mode in (2, -1, 7):
+        refused(one, one, 44, 4, one, 14, 39, mode, null, null, 0, 2, one, one, null, one, null, says=b"pelvis_mode")
+        refused(one, one, 44, 4, one, 14, 39, mode, one, one, 10, 2, one, one, one, one, null, says=b"pelvis_mode")
+    for nkp in (0, 65):
+        refused(one, one, 44, 4, one, nkp, 39, 0, null, null, 0, 2, one, one, null, one, null, says=b"n_kp")
+    refused(one, one, 44, 2, one, 14, 39, 0, null, null, 0, 2, one, one, null, one, null)          # gt_stride < 3
+    refused(one, one, 44, 4, one, 14, 44, 0, null, null, 0, 2, one, one, null, one, null)          # pelvis_ind == n_joints
+    refused(one, one, 44, 4, one, 14, -1, 0, null, null, 0, 2, one, one, null, one, null)
+    refused(one, one, 2, 4, one, 2, 0, 0, null, null, 0, 2, one, one, null, one, null)             # n_joints < 3
+    refused(one, one, 44, 4, one, 14, 39, 0, null, null, 0, 0, one, one, null, one, null)          # B < 1
+    for hole in (0, 1, 4, 12, 13, 15):                                                             # each required buffer null in turn
+        args = [one, one, 44, 4, one, 14, 39, 0, null, null, 0, 2, one, one, null, one, null]
+        args[hole] = null
+        refused(*args, says=b"null")
+    #        J verts nj nv B out stream
+    for args in ((null, one, 24, 10, 2, one, null), (one, null, 24, 10, 2, one, null), (one, one, 24, 10, 2, null, null),
+                 (one, one, 0, 10, 2, one, null), (one, one, 24, 0, 2, one, null), (one, one, 24, 10, 0, one, null)):
+        refused(*args, fn="thmr_regress_joints")

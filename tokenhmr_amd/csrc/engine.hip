@@ -2330,6 +2330,8 @@ int thmr_eval_pose(const float* pred_j, const float* gt_j, int32_t nj, int32_t g
     if (!pred_j || !gt_j || !kp || !mpjpe || !re || !pelv) return fail(e, THMR_ERR_INVALID, "null buffer");
     if (nkp < 1 || nkp > 64 || gt_stride < 3 || B < 1 || pelvis_ind < 0 || pelvis_ind >= nj || nj < 3)
         return fail(e, THMR_ERR_INVALID, "bad evaluator arguments (1 <= n_kp <= 64, gt_stride >= 3)");
+    if (pelvis_mode != 0 && pelvis_mode != 1) return fail(e, THMR_ERR_INVALID, "bad evaluator arguments (pelvis_mode is 0 or 1)");
+    if (pred_v && gt_v && pve && nv < 1) return fail(e, THMR_ERR_INVALID, "bad evaluator arguments (PVE needs n_verts >= 1)");
     hipStream_t st = static_cast<hipStream_t>(stream);
     LAUNCH_OK(launch_eval_pose(pred_j, gt_j, nj, gt_stride, kp, nkp, pelvis_ind, pelvis_mode, mpjpe, re, pelv, B, st));
     if (pred_v && gt_v && pve) LAUNCH_OK(launch_eval_pve(pred_v, gt_v, pelv, nv, pve, B, st));

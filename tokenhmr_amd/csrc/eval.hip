@@ -55,6 +55,20 @@ __device__ void procrustes_rotation(const double Kin[3][3], double R[3][3], doub
     // a zero singular value leaves u undefined: complete it to a right-handed frame so det(U) is defined
     if (sv[smallest] == 0.0) {
         const int a = (smallest + 1) % 3, b = (smallest + 2) % 3;
+        // two of them zero (gt exactly on a line along a coordinate axis: two columns of K are 0): the second one needs a unit vector
+        // orthogonal to the only u there is, or R = V Z U^T loses that direction of pred and the error comes out too small.  Any such
+        // vector gives the same error (the gt side of that direction is 0); take u x e_m with e_m the axis u is furthest from.
+        const int big = sv[a] > 0.0 ? a : b, other = a + b - big;
+        if (sv[other] == 0.0 && sv[big] > 0.0) {
+            int m = 0;
+            if (fabs(U[1][big]) < fabs(U[m][big])) m = 1;
+            if (fabs(U[2][big]) < fabs(U[m][big])) m = 2;
+            const int m1 = (m + 1) % 3, m2 = (m + 2) % 3;
+            const double inv = 1.0 / sqrt(U[m1][big] * U[m1][big] + U[m2][big] * U[m2][big]);      // |u x e_m| >= sqrt(2/3)
+            U[m][other] = 0.0;
+            U[m1][other] = U[m2][big] * inv;
+            U[m2][other] = -U[m1][big] * inv;
+        }
         U[0][smallest] = U[1][a] * U[2][b] - U[2][a] * U[1][b];
         U[1][smallest] = U[2][a] * U[0][b] - U[0][a] * U[2][b];
         U[2][smallest] = U[0][a] * U[1][b] - U[1][a] * U[0][b];

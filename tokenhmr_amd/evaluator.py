@@ -22,22 +22,44 @@ def _p(t):
 _KP_CACHE = {}
 
 
+def _same_device(**named):
+    devs = {k: t.device for k, t in named.items() if t is not None}
+    if len(set(devs.values())) > 1:
+        raise ValueError("tensors on different devices: " + ", ".join(f"{k} on {d}" for k, d in devs.items()))
+
+
 def eval_pose_gpu(pred_joints, gt_joints, keypoint_list, pelvis_ind, pelvis_mode=0, pred_vertices=None, gt_vertices=None):
-    """Returns (mpjpe_mm, re_mm, pve_mm or None) as CUDA float32 tensors of shape (B,)."""
+    """Returns (mpjpe_mm, re_mm, pve_mm or None) as CUDA float32 tensors of shape (B,).
+    Every argument is validated on the host first, shapes before devices: the kernels index by the sizes given here and check nothing."""
+    ps, gs = tuple(pred_joints.shape), tuple(gt_joints.shape)
+    if len(ps) != 3 or len(gs) != 3 or gs[:2] != ps[:2] or ps[2] != 3 or gs[2] not in (3, 4) or ps[0] < 1:
+        raise ValueError(f"bad joint shapes {ps} / {gs}")
+    B, nj = ps[0], ps[1]
+    kpl = [int(k) for k in keypoint_list]
+    if not kpl or min(kpl) < 0 or max(kpl) >= nj:
+        # the reference indexes pred[:, keypoint_list] and raises here (pose_utils.py:225-226); the kernel must never read past nj
+        raise IndexError(f"keypoint_list indices must lie in [0, {nj}) for {nj}-joint inputs, got min {min(kpl, default=None)} max {max(kpl, default=None)}")
+    if len(kpl) > 64:
+        raise ValueError(f"{len(kpl)} keypoints: the kernel holds 64 (one per lane of its single wave)")
+    if pelvis_mode not in (0, 1):
+        raise ValueError(f"pelvis_mode {pelvis_mode!r}: 0 (joint pelvis_ind) or 1 ((joint 1 + joint 2) / 2, the EMDB branch)")
+    if pelvis_mode == 1 and nj < 3:
+        raise ValueError(f"pelvis_mode 1 reads joints 1 and 2, the inputs have {nj}")
+    if not 0 <= int(pelvis_ind) < nj:
+        raise IndexError(f"pelvis_ind {pelvis_ind} outside [0, {nj})")
+    want_pve = pred_vertices is not None and gt_vertices is not None
+    if want_pve:
+        vs, ws = tuple(pred_vertices.shape), tuple(gt_vertices.shape)
+        # the reference's (pred_vertices - pelvis) - (gt_vertices - pelvis) raises on a mismatch; eval_pve_kernel would read past the shorter one
+        if len(vs) != 3 or vs[0] != B or vs[1] < 1 or vs[2] != 3 or ws != vs:
+            raise ValueError(f"bad vertex shapes {vs} / {ws}: both must be ({B}, nv, 3) with nv >= 1")
+    _same_device(pred_joints=pred_joints, gt_joints=gt_joints, pred_vertices=pred_vertices if want_pve else None,
+                 gt_vertices=gt_vertices if want_pve else None)
     dev = pred_joints.device
     if dev.type != "cuda":
         raise RuntimeError("evaluator kernels run on the GPU only (no CPU fallback)")
     pj = pred_joints.detach().float().contiguous()
     gj = gt_joints.detach().float().contiguous()
-    B, nj = pj.shape[0], pj.shape[1]
-    if gj.shape[:2] != (B, nj) or pj.shape[2] != 3 or gj.shape[2] not in (3, 4):
-        raise ValueError(f"bad joint shapes {tuple(pj.shape)} / {tuple(gj.shape)}")
-    kpl = [int(k) for k in keypoint_list]
-    if not kpl or min(kpl) < 0 or max(kpl) >= nj:
-        # the reference indexes pred[:, keypoint_list] and raises here (pose_utils.py:225-226); the kernel must never read past nj
-        raise IndexError(f"keypoint_list indices must lie in [0, {nj}) for {nj}-joint inputs, got min {min(kpl, default=None)} max {max(kpl, default=None)}")
-    if not 0 <= int(pelvis_ind) < nj:
-        raise IndexError(f"pelvis_ind {pelvis_ind} outside [0, {nj})")
     kp = _KP_CACHE.get((tuple(kpl), dev))               # the index list lives on the device once: no H2D copy per batch
     if kp is None:
         kp = _KP_CACHE[(tuple(kpl), dev)] = torch.as_tensor(kpl, dtype=torch.int32, device=dev)
@@ -46,7 +68,7 @@ def eval_pose_gpu(pred_joints, gt_joints, keypoint_list, pelvis_ind, pelvis_mode
     pelv = torch.empty(B, 6, device=dev, dtype=torch.float32)
     pv = gv = pve = None
     nv = 0
-    if pred_vertices is not None and gt_vertices is not None:
+    if want_pve:
         pv = pred_vertices.detach().float().contiguous()
         gv = gt_vertices.detach().float().contiguous()
         nv = pv.shape[1]
@@ -60,6 +82,16 @@ def eval_pose_gpu(pred_joints, gt_joints, keypoint_list, pelvis_ind, pelvis_mode
 
 def regress_joints_gpu(J, verts):
     """(nj,nv) @ (B,nv,3) -> (B,nj,3) on the GPU."""
+    js, vs = tuple(J.shape), tuple(verts.shape)
+    if len(js) != 2 or js[0] < 1:
+        raise ValueError(f"J must be (nj, nv) with nj >= 1, got {js}")
+    if len(vs) != 3 or vs[0] < 1 or vs[1] < 1 or vs[2] != 3:
+        raise ValueError(f"verts must be (B, nv, 3) with B, nv >= 1, got {vs}")
+    if js[1] != vs[1]:
+        raise ValueError(f"J {js} regresses from {js[1]} vertices, verts {vs} has {vs[1]}")      # torch.matmul raises here too
+    _same_device(J=J, verts=verts)
+    if verts.device.type != "cuda":
+        raise RuntimeError("evaluator kernels run on the GPU only (no CPU fallback)")
     J = J.detach().float().contiguous()
     v = verts.detach().float().contiguous()
     B, nv = v.shape[0], v.shape[1]
