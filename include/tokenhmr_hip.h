@@ -197,7 +197,8 @@ int thmr_forward(thmr_engine* e, const float* img_dev, int32_t B, const thmr_out
  * timed out instead of hanging the GPU.  thmr_forward itself never synchronises; it does look at host-mapped copies of the same error words
  * on entry, so a timeout is also reported by the NEXT forward-type call.  Either way the error is returned once: the engine drains the
  * device, resets the barrier words / hand-over workspace and switches to the launch chain / per-tile kernel (no co-residency needed), so
- * re-submitting the batch works. */
+ * re-submitting the batch works.  It also returns THMR_ERR_INVALID, once, after a thmr_vq_decode_idx / thmr_tokenizer_roundtrip call met a code
+ * index outside [0, 2048) (clamped on the device; see thmr_vq_decode_idx). */
 int thmr_engine_status(thmr_engine* e, void* stream);
 
 /* Diagnostics: with THMR_DEC_TIMELINE=1 in the environment at thmr_finalize_weights, workgroup 0 of the persistent decoder kernel
@@ -257,6 +258,43 @@ int thmr_encode_tokens(thmr_engine* e, const float* pose_dev, int32_t B, int32_t
 /* DecodeTokens.forward (vanilla_pose_vqvae.py:294-297): probs (B,160,2048) @ codebook -> PoseSPDecoderV1 -> pose6d (B,21,6).
  * One-hot probs give the hard decode of code indices (QuantizeEMAReset.dequantize, quantize_cnn.py:88-90). */
 int thmr_vq_decode(thmr_engine* e, const float* probs_dev, int32_t B, float* pose6d_dev, void* stream);
+/* The hard decode of code indices (QuantizeEMAReset.dequantize = F.embedding, quantize_cnn.py:88-90, then PoseSPDecoderV1): idx (B,160)
+ * int32 -> pose6d (B,21,6).  A lookup kernel writes the decoder's first conv operand directly — no (B,160,2048) one-hot, no 2048-deep
+ * GEMM — and the rest is thmr_vq_decode's: bit-identical to thmr_vq_decode of the one-hot probabilities (a one-hot row contributes one
+ * non-zero fp32 term).  An index outside [0, 2048) is a caller error: the kernel clamps it (nothing is read out of bounds) and sets a
+ * host-mapped flag word of the engine; thmr_engine_status, or the next thmr_vq_decode_idx / thmr_tokenizer_roundtrip on the engine,
+ * then returns THMR_ERR_INVALID once and clears the flag.  The outputs of the call that carried the index are invalid. */
+int thmr_vq_decode_idx(thmr_engine* e, const int32_t* idx_dev, int32_t B, float* pose6d_dev, void* stream);
+/* The tokenizer round trip the reference evaluates (VanillaTokenizer.forward, vanilla_pose_vqvae.py:244-255, as driven by
+ * train_poseVQ.py:57-68 with EXP.EVAL_ONLY and utils/eval_poseVQ.py:70-143): PoseSPEncoderV1 -> QuantizeEMAReset.forward
+ * (quantize_cnn.py:95-130) -> PoseSPDecoderV1 -> rotation_6d_to_matrix -> matrix_to_axis_angle, the latent staying on the device.
+ * Every field is a device buffer or NULL = "not wanted":
+ *   idx          (B,160) int32      code indices (quantize_cnn.py:80-86, as thmr_encode_tokens)
+ *   latent       (B,160,256)        the encoder's output in the quantiser's (N*T, C) layout
+ *   pose6d       (B,21,6)           pred_pose_body_6d: the decoder on the STRAIGHT-THROUGH value x + (c - x) (quantize_cnn.py:124, fp32 in
+ *                                   that order — an ulp away from the code row c on ~6 % of the elements, so it differs from
+ *                                   thmr_vq_decode_idx(idx) in the last bits: the reference's own quirk)
+ *   rotmat       (B,21,3,3)         pred_pose_body_rotmat (rotation_6d_to_matrix == geometry.rot6d_to_rotmat bit for bit on this input)
+ *   aa           (B,21,3)           pred_pose_body_aa = matrix_to_axis_angle(rotmat) (see thmr_op_rotmat_to_aa)
+ *   commit_loss  1 float            F.mse_loss(x, c[idx]) over the B*160*256 elements
+ *   perplexity   1 float            exp(-sum p log(p + 1e-7)), p = code_count / sum(code_count) (with accumulate_counts: of the SUMMED counts)
+ *   code_count   (2048) int32       the code-usage histogram of this call; accumulate_counts != 0: added to what the buffer holds
+ * Needs the encoder tensors as thmr_encode_tokens does.  Allocates nothing and never synchronises the host, so a call can be captured in a
+ * hipGraph like thmr_forward; two calls give identical bits (integer atomics for the histogram, fixed-order float sums).  Encoder and
+ * statistics scratch is the engine's big time-shared buffer, the decoder's its own conv buffers: do not overlap a forward on one engine. */
+typedef struct thmr_tokenizer_out {
+    int32_t* idx;
+    float* latent;
+    float* pose6d;
+    float* rotmat;
+    float* aa;
+    float* commit_loss;
+    float* perplexity;
+    int32_t* code_count;
+    int32_t accumulate_counts;
+    int32_t reserved;
+} thmr_tokenizer_out;
+int thmr_tokenizer_roundtrip(thmr_engine* e, const float* pose6d_dev /*(B,21,6)*/, int32_t B, const thmr_tokenizer_out* out, void* stream);
 
 /* Stateless operator entry points (unit parity of individual kernels; no engine needed). */
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T) in exact fp32 (v_mfma_f32_32x32x2_f32 / 16x16x4_f32; csrc/gemm_f32.hip).  epi: 0 none, 1 +bias,
@@ -371,6 +409,18 @@ int thmr_op_vq_argmin_rows(const float* x_dev, const float* dot_dev, const float
                            int32_t rows, void* stream);
 /* quantize_cnn.py:83 torch.sum(k_w ** 2, dim=0):  cb (ncode, 256) -> cn (ncode). */
 int thmr_op_code_norm(const float* cb_dev, float* cn_dev, int32_t ncode, void* stream);
+/* What QuantizeEMAReset.forward returns beside the codes (quantize_cnn.py:38-47,118-121; csrc/tokenizer.hip), over x (rows, 256), the
+ * codebook (2048, 256) and idx (rows) int32:  code_count (2048) int32 histogram (integer atomics; accumulate = 0 overwrites, else adds to
+ * the caller's counts), commit = mean((x - codebook[idx])^2), perplexity = exp(-sum p log(p + 1e-7)) with p = code_count / sum(code_count)
+ * AFTER this call's update.  commit / perplexity: one device float each, either may be null.  partial_scratch: ceil(rows / 32) floats.
+ * Fixed-order float sums, no float atomics: two runs are bit-equal.  No host synchronisation.  An index outside [0, 2048) is clamped. */
+int thmr_op_vq_stats(const float* x_dev, const float* codebook_dev, const int32_t* idx_dev, int32_t rows, int32_t* code_count_dev,
+                     int32_t accumulate, float* partial_scratch_dev, float* commit_or_null, float* perplexity_or_null, void* stream);
+/* matrix_to_axis_angle (tokenization/models/rotation_utils.py:428-441): (n,3,3) -> (n,3), the reference's route exactly:
+ * _sqrt_positive_part of the four squared quaternion magnitudes, the candidate of the largest one (lowest index on ties) over
+ * 2 max(q_abs, 0.1), half = atan2(|q_1..3|, q_0), angle = 2 half, q_1..3 / (|angle| < 1e-6 ? 0.5 - angle^2 / 48 : sin(half) / angle) with the
+ * divisor clamped at the smallest normal float.  The quaternion is NOT standardised: q_0 < 0 gives an angle above pi, as the reference. */
+int thmr_op_rotmat_to_aa(const float* R_dev, float* aa_dev, int32_t n, void* stream);
 /* What follows the read-out GEMM of the SMPL head: mean parameters added, rot6d_to_rotmat (geometry.py:64-84) over the 24 joints,
  * pred_cam_t = [cam1, cam2, 2 f / (img_size cam0 + 1e-9)] (tokenhmr.py:165-169).  ro (B, ldro).
  *   kind 0, the token head (token_head.py:99-105,123): ro columns grot 0..5 | shape 6..15 | cam 16..18 | hands 19..30, ldro >= 31;

@@ -97,6 +97,12 @@ class VitPlanDesc(C.Structure):
                [("attn", C.c_int32), ("bs_blk", C.c_int32), ("part2_in_scratch", C.c_int32), ("tile_opts", C.c_int32)]
 
 
+class TokenizerOut(C.Structure):
+    _fields_ = [("idx", C.c_void_p), ("latent", C.c_void_p), ("pose6d", C.c_void_p), ("rotmat", C.c_void_p), ("aa", C.c_void_p),
+                ("commit_loss", C.c_void_p), ("perplexity", C.c_void_p), ("code_count", C.c_void_p), ("accumulate_counts", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
@@ -115,6 +121,9 @@ _libs = {}
 ROWOPS_SYMBOLS = ("thmr_op_splitk_resid_ln", "thmr_op_add_ln64", "thmr_op_transpose", "thmr_op_softmax_argmax", "thmr_op_cross_attn",
                   "thmr_op_im2col_patch", "thmr_op_conv3_gather", "thmr_op_conv_gather", "thmr_op_conv_repack", "thmr_op_vq_argmin_rows",
                   "thmr_op_code_norm", "thmr_op_head_finish", "thmr_op_decoder_init")
+
+# the tokenizer round trip (csrc/tokenizer.hip): new symbols under ABI 5 as well — hard decode, the round trip, and its two kernels alone
+TOKENIZER_RT_SYMBOLS = ("thmr_vq_decode_idx", "thmr_tokenizer_roundtrip", "thmr_op_vq_stats", "thmr_op_rotmat_to_aa")
 
 
 def load(exp=None):
@@ -151,7 +160,7 @@ def load(exp=None):
     older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
     # a build loaded by path may also predate thmr_renderer_sheet / thmr_debug_vit_plan (added without an ABI change: new symbols, no layout touched)
     missing = [s for s in declared_symbols() if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
-               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS)]
+               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS)]
     if missing:
         raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -206,6 +215,11 @@ def load(exp=None):
         lib.thmr_op_code_norm.argtypes = [vp, vp, i32, vp]
         lib.thmr_op_head_finish.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp]
         lib.thmr_op_decoder_init.argtypes = [vp, vp, vp, i32, i32, vp]
+    if hasattr(lib, "thmr_tokenizer_roundtrip"):         # the tokenizer round trip (added without an ABI change)
+        lib.thmr_vq_decode_idx.argtypes = [vp, vp, i32, vp, vp]
+        lib.thmr_tokenizer_roundtrip.argtypes = [vp, vp, i32, C.POINTER(TokenizerOut), vp]
+        lib.thmr_op_vq_stats.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+        lib.thmr_op_rotmat_to_aa.argtypes = [vp, vp, i32, vp]
     lib.thmr_smpl_create.argtypes = [C.POINTER(SmplDesc), i32, i32, C.POINTER(vp)]
     lib.thmr_smpl_destroy.argtypes = [vp]
     lib.thmr_smpl_destroy.restype = None

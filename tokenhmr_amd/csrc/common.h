@@ -448,6 +448,16 @@ int launch_cam_t(const float* cam, float* cam_t, float focal_length, float img_s
 int launch_vq_argmin_rows(const float* x, const float* dot, const float* cnorm, int32_t* idx, float* dist, int rows,
                           hipStream_t s);
 int launch_code_norm(const float* cb, float* cn, int ncode, hipStream_t s);
+// tokenizer.hip: the tokenizer round trip around the encoder / decoder GEMM chains
+// hard codebook lookup written as decoder.0's conv operand (B*160, 768); x = null: the code rows, else x + (c - x) (straight-through);
+// an index outside [0, 2048) is clamped and sets *bad_flag (may be null, may be host-mapped)
+int launch_vq_lookup(const int32_t* idx, const float* x, const float* cb, float* out, int B, unsigned* bad_flag, hipStream_t s);
+// histogram (overwritten, or added to with `accumulate`), commit = mean((x - cb[idx])^2), perplexity of count / sum(count); partial holds
+// vq_stats_partials(rows) floats; commit / perplexity may be null
+int vq_stats_partials(int rows);
+int launch_vq_stats(const float* x, const float* cb, const int32_t* idx, int rows, int32_t* count, int accumulate, float* partial,
+                    float* commit, float* perplexity, unsigned* bad_flag, hipStream_t s);
+int launch_rotmat_to_aa(const float* R, float* aa, int n, hipStream_t s);      // matrix_to_axis_angle (rotation_utils.py:428-441)
 // lbs.hip
 int launch_lbs_jreg(const float* Jreg, const float* vt, const float* sd, float* Jt, float* Jsd, hipStream_t s);
 // dirsT (20670 x 224): [shapedirs | posedirs | 0]^T built once by launch_lbs_build_dirs; scratch A (B,24,12),

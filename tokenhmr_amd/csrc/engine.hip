@@ -103,7 +103,7 @@ struct thmr_engine {
     std::vector<SplitW> vitw_s;
     const char* kv_s = nullptr;       // split3 copy of the decoder's stacked to_kv weights (dec_depth * 1024 rows x 1280)
     const char* pe_s = nullptr;       // split3 copy of the patch-embed Conv2d weight as a (1280, 768) matrix
-    unsigned* host_err = nullptr;     // host-mapped sticky error words (hipHostMalloc, 64 bytes): [0] the persistent decoder kernel's grid barrier, [1] the persistent split3 GEMM's hand-over
+    unsigned* host_err = nullptr;     // host-mapped sticky error words (hipHostMalloc, 64 bytes): [0] the persistent decoder kernel's grid barrier, [1] the persistent split3 GEMM's hand-over, [2] a code index out of range in the tokenizer's hard lookup / statistics
     unsigned* s3_host_err = nullptr;  // = host_err + 1; its ADDRESS is the stable source of the copy that binds it into the hand-over workspace
     std::string err;
     // derived / constant regions (float offsets in weight arena)
@@ -703,12 +703,18 @@ int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipSt
 // (quantize_cnn.py:92-93 dequantize_logits) + PoseSPDecoderV1 (:135-154).  probs (B,160,2048) -> bpose (B,21,6).
 // 12 GEMMs and nothing else: every Conv1d(k = 3) is a GEMM over an im2col operand (B*T, 3*C) that the PREVIOUS GEMM's epilogue
 // wrote (GemmArgs::cs_*: nearest-resample + taps + zero padding + the ResConv pre-activation ReLU), so no gather launch exists.
-int vq_decode(thmr_engine* e, const float* probs, int B, float* bpose, hipStream_t st) {
+// The lookup in front (soft: a GEMM, vq_decode; hard: a kernel, vq_decode_idx) writes the first operand; vq_decode_convs is the rest.
+//
+// Up to six crops (the small-batch regime, B <= kSmallM / 192) the M = 21 B ... 160 B row products of the VQ decoder run on the tiny-M kernel
+// (32x32 tiles, K split over the 8 waves of a workgroup): as 8-24 ring-kernel workgroups walking the whole K they were 13
+// dependent launches of 12-32 us, a third of the head at one crop.  One choice for the whole regime: the K association differs.
+int vq_tiny_variant(const thmr_engine* e, int B) { return (e->tiny_gemm && B * TOK <= kSmallM) ? 11 : -1; }
+
+// PoseSPDecoderV1 behind the codebook lookup: the operand of decoder.0 (B*160, 3*256) is in the scratch buffer `gat`, written by the soft
+// lookup's GEMM (vq_decode) or by the hard lookup kernel (vq_decode_idx, tokenizer_roundtrip) -> bpose (B,21,6)
+int vq_decode_convs(thmr_engine* e, int B, float* bpose, hipStream_t st) {
     auto& so = e->so;
-    // Up to six crops (the small-batch regime, B <= kSmallM / 192) these M = 21 B ... 160 B row products run on the tiny-M kernel
-    // (32x32 tiles, K split over the 8 waves of a workgroup): as 8-24 ring-kernel workgroups walking the whole K they were 13
-    // dependent launches of 12-32 us, a third of the head at one crop.  One choice for the whole regime: the K association differs.
-    const int tv = (e->tiny_gemm && B * TOK <= kSmallM) ? 11 : -1;
+    const int tv = vq_tiny_variant(e, B);
     float* G[2] = {e->S(so.gat), e->S(so.gat2)};          // conv operands, alternating
     float *x0 = e->S(so.act0), *x1 = e->S(so.act1), *hid = e->S(so.act2);
     const int32_t* inv = reinterpret_cast<const int32_t*>(e->warena + e->o_inv);
@@ -721,11 +727,6 @@ int vq_decode(thmr_engine* e, const float* probs, int B, float* bpose, hipStream
         const int ci = kConv3Ci[id], co = kConv3Co[id];
         return mk(opnd, 3 * ci, e->warena + e->convp[id], 3 * ci, bias, nullptr, 0, plain, co, B * T, co, 3 * ci);
     };
-    {   // soft codebook lookup: probs @ codebook as a GEMM against codebook^T -> operand of decoder.0 (T = 160, C = 256)
-        GemmArgs a = mk(probs, NCLS, e->warena + e->o_cbT, NCLS, nullptr, nullptr, 0, nullptr, CODE, B * TN, CODE, NCLS);
-        scatter(a, G[0], nullptr, 160, 160, 1, 0);
-        LAUNCH_OK(launch_gemm(a, EPI_NONE, tv, st));
-    }
     int cur = 0;
     {   // decoder.0: Conv1d(256 -> 512) + ReLU at T = 160 -> operand of decoder.3 on the 160 -> 125 resample
         GemmArgs a = conv(0, G[cur], 160, e->hot.conv_b[0], nullptr);
@@ -765,6 +766,21 @@ int vq_decode(thmr_engine* e, const float* probs, int B, float* bpose, hipStream
     GemmArgs a = conv(8, G[cur], Tq, e->hot.conv_b[8], bpose);    // decoder.15: Conv1d(512 -> 6): the 21 x 6D body pose
     LAUNCH_OK(launch_gemm(a, EPI_BIAS, tv, st));
     return 0;
+}
+
+int vq_decode(thmr_engine* e, const float* probs, int B, float* bpose, hipStream_t st) {
+    // soft codebook lookup: probs @ codebook as a GEMM against codebook^T -> operand of decoder.0 (T = 160, C = 256)
+    GemmArgs a = mk(probs, NCLS, e->warena + e->o_cbT, NCLS, nullptr, nullptr, 0, nullptr, CODE, B * TN, CODE, NCLS);
+    a.cs_out = e->S(e->so.gat); a.cs_inv = nullptr; a.cs_tin = 160; a.cs_tout = 160; a.cs_dil = 1; a.cs_relu = 0;
+    LAUNCH_OK(launch_gemm(a, EPI_NONE, vq_tiny_variant(e, B), st));
+    return vq_decode_convs(e, B, bpose, st);
+}
+
+// hard codebook lookup (QuantizeEMAReset.dequantize, quantize_cnn.py:88-90) -> the same operand; x = null: the code rows themselves,
+// else the straight-through value x + (c - x) of quantize_cnn.py:124.  A bad index sets the engine's host-mapped flag word [2].
+int vq_decode_idx(thmr_engine* e, const int32_t* idx, const float* x, int B, float* bpose, hipStream_t st) {
+    LAUNCH_OK(launch_vq_lookup(idx, x, e->W("quantizer.codebook"), e->S(e->so.gat), B, e->host_err ? e->host_err + 2 : nullptr, st));
+    return vq_decode_convs(e, B, bpose, st);
 }
 
 int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* out, hipStream_t st) {
@@ -1298,7 +1314,7 @@ int thmr_create(const thmr_config* cfg, void* weight_arena_dev, void* scratch_ar
     if (hipMemset(e->sarena + e->so.lcnt, 0, (size_t)e->max_batch * sizeof(float)) != hipSuccess) return bail(THMR_ERR_HIP, "hipMemset(lbs counters) failed");
     // sticky error word of the persistent decoder kernel, host-mapped so that the next call sees a timeout without a D2H copy
     if (hipHostMalloc(reinterpret_cast<void**>(&e->host_err), 64, hipHostMallocMapped) != hipSuccess) return bail(THMR_ERR_NOMEM, "hipHostMalloc(error word) failed");
-    e->host_err[0] = e->host_err[1] = 0;
+    e->host_err[0] = e->host_err[1] = e->host_err[2] = 0;
     e->s3_host_err = e->host_err + 1;
     { const char* lg = thmr_knob("THMR_LEGACY_HEAD"); e->legacy_head = lg && lg[0] == '1'; }
     { const char* mc = thmr_knob("THMR_MIXER_CLUSTER"); e->mixer_cluster = !(mc && mc[0] == '0'); }
@@ -1608,13 +1624,15 @@ int thmr_vq_decode(thmr_engine* e, const float* probs_dev, int32_t B, float* pos
 
 // EncodeTokens.forward (tokenization/models/vanilla_pose_vqvae.py:334-342): PoseSPEncoderV1 (:66-111) -> preprocess
 // (quantize_cnn.py:74-78) -> QuantizeEMAReset.quantize (:80-86).  pose (B,21,6) rot6d body pose -> idx (B,160).
-int thmr_encode_tokens(thmr_engine* e, const float* pose_dev, int32_t B, int32_t* idx_dev, float* latent_dev, void* stream) {
-    if (int r = check_ready(e, B)) return r;
-    if (e->hmr2) return refuse_hmr2(e, "thmr_encode_tokens");
-    if (!e->enc_ready) return fail(e, THMR_ERR_STATE, "tokenizer encoder weights ('encoder.encoder.*') were not loaded");
-    if (!pose_dev || !idx_dev) return fail(e, THMR_ERR_INVALID, "null buffer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // all scratch comes out of the big time-shared buffer (the encode path never overlaps a forward on one engine)
+// Scratch of the encode path, all out of the big time-shared buffer (B*192*6144 floats; the encode path never overlaps a forward on one
+// engine): [gather / distance operand B*320*1536 | a0, a1, a2: B*320*512 each | the round trip's statistics: 2048 counts, partial sums].
+// None of it is touched by the VQ decoder (gat / gat2 / act0-2 are buffers of their own), so a latent left in a2 survives until the
+// round trip's lookup has read it.
+static float* enc_scratch_a2(thmr_engine* e, int B) { return e->S(e->so.big) + (size_t)B * 320 * 1536 + 2 * (size_t)B * 320 * VQW; }
+
+// *lat_out: where the latent (B*160, 256) was written — latent_dev, or the scratch region a2
+static int encode_tokens_call(thmr_engine* e, const float* pose_dev, int B, int32_t* idx_dev, float* latent_dev, const float** lat_out,
+                              hipStream_t st) {
     float* gat = e->S(e->so.big);
     float* a0 = gat + (size_t)B * 320 * 1536;
     float* a1 = a0 + (size_t)B * 320 * VQW;
@@ -1666,6 +1684,64 @@ int thmr_encode_tokens(thmr_engine* e, const float* pose_dev, int32_t B, int32_t
     GemmArgs d = mk(lat, CODE, e->W("quantizer.codebook"), CODE, nullptr, nullptr, 0, gat, NCLS, B * 160, NCLS, CODE);
     LAUNCH_OK(launch_gemm(d, EPI_NONE, -1, st));
     LAUNCH_OK(launch_vq_argmin_rows(lat, gat, e->warena + e->o_cnorm, idx_dev, nullptr, B * 160, st));
+    if (lat_out) *lat_out = lat;
+    return 0;
+}
+
+int thmr_encode_tokens(thmr_engine* e, const float* pose_dev, int32_t B, int32_t* idx_dev, float* latent_dev, void* stream) {
+    if (int r = check_ready(e, B)) return r;
+    if (e->hmr2) return refuse_hmr2(e, "thmr_encode_tokens");
+    if (!e->enc_ready) return fail(e, THMR_ERR_STATE, "tokenizer encoder weights ('encoder.encoder.*') were not loaded");
+    if (!pose_dev || !idx_dev) return fail(e, THMR_ERR_INVALID, "null buffer");
+    return encode_tokens_call(e, pose_dev, B, idx_dev, latent_dev, nullptr, static_cast<hipStream_t>(stream));
+}
+
+// A code index outside [0, 2048) reached a lookup / statistics kernel of this engine (clamped there, never read through): the kernels set
+// the host-mapped flag word [2], and the next status read or tokenizer call reports it ONCE.  The work that carried it is invalid.
+static int report_bad_code_index(thmr_engine* e) {
+    if (!e->host_err || *static_cast<volatile unsigned*>(e->host_err + 2) == 0) return 0;
+    e->host_err[2] = 0;
+    return fail(e, THMR_ERR_INVALID, "a code index outside [0, 2048) was passed to thmr_vq_decode_idx / thmr_tokenizer_roundtrip in an earlier "
+                                     "call (clamped on the device, nothing was read out of bounds); that call's outputs are invalid");
+}
+
+int thmr_vq_decode_idx(thmr_engine* e, const int32_t* idx_dev, int32_t B, float* pose6d_dev, void* stream) {
+    if (int r = check_ready(e, B)) return r;
+    if (e->hmr2) return refuse_hmr2(e, "thmr_vq_decode_idx");
+    if (int r = report_bad_code_index(e)) return r;
+    if (!idx_dev || !pose6d_dev) return fail(e, THMR_ERR_INVALID, "null buffer");
+    return vq_decode_idx(e, idx_dev, nullptr, B, pose6d_dev, static_cast<hipStream_t>(stream));
+}
+
+// VanillaTokenizer.forward (vanilla_pose_vqvae.py:244-255): encoder -> QuantizeEMAReset.forward (quantize_cnn.py:95-130: quantize,
+// perplexity, commit loss, straight-through) -> decoder -> rotation_6d_to_matrix (-> matrix_to_axis_angle), on one stream, no allocation,
+// no host synchronisation.
+int thmr_tokenizer_roundtrip(thmr_engine* e, const float* pose6d_dev, int32_t B, const thmr_tokenizer_out* out, void* stream) {
+    if (int r = check_ready(e, B, static_cast<hipStream_t>(stream))) return r;
+    if (e->hmr2) return refuse_hmr2(e, "thmr_tokenizer_roundtrip");
+    if (!e->enc_ready) return fail(e, THMR_ERR_STATE, "tokenizer encoder weights ('encoder.encoder.*') were not loaded");
+    if (int r = report_bad_code_index(e)) return r;
+    if (!pose6d_dev || !out) return fail(e, THMR_ERR_INVALID, "null buffer");
+    if (out->accumulate_counts && !out->code_count) return fail(e, THMR_ERR_INVALID, "accumulate_counts needs a code_count buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t* idx = out->idx ? out->idx : reinterpret_cast<int32_t*>(e->S(e->so.tokidx));
+    const float* lat = nullptr;
+    if (int r = encode_tokens_call(e, pose6d_dev, B, idx, out->latent, &lat, st)) return r;
+    unsigned* flag = e->host_err ? e->host_err + 2 : nullptr;
+    const float* cb = e->W("quantizer.codebook");
+    if (out->commit_loss || out->perplexity || out->code_count) {
+        float* sc = enc_scratch_a2(e, B) + (size_t)B * 320 * VQW;      // behind a2: 2048 counts, then the partial sums
+        int32_t* cnt = out->code_count ? out->code_count : reinterpret_cast<int32_t*>(sc);
+        LAUNCH_OK(launch_vq_stats(lat, cb, idx, B * TN, cnt, out->code_count && out->accumulate_counts, sc + NCLS, out->commit_loss,
+                                  out->perplexity, flag, st));
+    }
+    float* pose = out->pose6d ? out->pose6d : e->S(e->so.bpose);
+    if (int r = vq_decode_idx(e, idx, lat, B, pose, st)) return r;
+    if (out->rotmat || out->aa) {
+        float* rot = out->rotmat ? out->rotmat : e->S(e->so.rot);      // (B,24,9) scratch holds the 21 body joints
+        LAUNCH_OK(launch_rot6d(pose, rot, B * VQJ, st));
+        if (out->aa) LAUNCH_OK(launch_rotmat_to_aa(rot, out->aa, B * VQJ, st));
+    }
     return 0;
 }
 
@@ -1683,6 +1759,7 @@ int thmr_engine_status(thmr_engine* e, void* stream) {
     HIP_OK(hipMemcpyAsync(words, e->sarena + e->so.sync, sizeof(words), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (words[3] != 0 || (e->host_err && *static_cast<volatile unsigned*>(e->host_err) != 0)) return recover_decoder_timeout(e);
+    if (int r = report_bad_code_index(e)) return r;
     if (e->s3_ws) {
         // persistent split3 GEMM: a consumer's bounded wait for a hand-over slab ran out (see recover_split3_timeout; the next forward-type
         // call reports it too, through the host-mapped copy of this word).  Reported once.
@@ -2215,6 +2292,24 @@ int thmr_op_code_norm(const float* cb, float* cn, int32_t ncode, void* stream) {
     if (!cb || !cn) return fail(e, THMR_ERR_INVALID, "code_norm: null buffer");
     if (ncode <= 0) return fail(e, THMR_ERR_INVALID, "code_norm: ncode >= 1 is required");
     LAUNCH_OK(launch_code_norm(cb, cn, ncode, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_vq_stats(const float* x, const float* codebook, const int32_t* idx, int32_t rows, int32_t* code_count, int32_t accumulate,
+                     float* partial_scratch, float* commit, float* perplexity, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!x || !codebook || !idx || !code_count || !partial_scratch) return fail(e, THMR_ERR_INVALID, "vq_stats: null buffer");
+    if (rows <= 0) return fail(e, THMR_ERR_INVALID, "vq_stats: rows >= 1 is required");
+    LAUNCH_OK(launch_vq_stats(x, codebook, idx, rows, code_count, accumulate != 0, partial_scratch, commit, perplexity, nullptr,
+                              static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_rotmat_to_aa(const float* R, float* aa, int32_t n, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!R || !aa) return fail(e, THMR_ERR_INVALID, "rotmat_to_aa: null buffer");
+    if (n <= 0) return fail(e, THMR_ERR_INVALID, "rotmat_to_aa: n >= 1 is required");
+    LAUNCH_OK(launch_rotmat_to_aa(R, aa, n, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

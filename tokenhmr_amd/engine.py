@@ -269,6 +269,57 @@ class Engine:
             self._check(self.lib.thmr_vq_decode(self.h, _ptr(probs), B, _ptr(pose), _stream_ptr(self.device)), self.h)
         return pose
 
+    def vq_decode_idx(self, idx):
+        """Hard decode (QuantizeEMAReset.dequantize + PoseSPDecoderV1): (B,160) code indices -> (B,21,6) rot6d pose, bit-identical to
+        vq_decode(one_hot(idx)) without the one-hot or its GEMM.  An index outside [0, 2048) is clamped on the device and reported by
+        the next status() (or the next hard-decode / round-trip call) as an error."""
+        idx = idx.to(self.device, torch.int32).contiguous()
+        B = idx.shape[0]
+        if idx.dim() != 2 or idx.shape[1] != 160:
+            raise ValueError(f"idx must be (B,160), got {tuple(idx.shape)}")
+        pose = torch.empty(B, 21, 6, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.thmr_vq_decode_idx(self.h, _ptr(idx), B, _ptr(pose), _stream_ptr(self.device)), self.h)
+        return pose
+
+    TOKENIZER_OUT = {"idx": ((160,), torch.int32), "latent": ((160, 256), torch.float32), "pose6d": ((21, 6), torch.float32),
+                     "rotmat": ((21, 3, 3), torch.float32), "aa": ((21, 3), torch.float32)}
+
+    def tokenizer_roundtrip(self, pose6d, want=("idx", "latent", "pose6d", "rotmat", "commit_loss", "perplexity", "code_count"),
+                            outputs=None, accumulate=False):
+        """VanillaTokenizer.forward (vanilla_pose_vqvae.py:244-255) in one call: (B,21,6) -> dict of the fields named in `want`
+        (thmr_tokenizer_out in the header: idx, latent, pose6d, rotmat, aa per pose; commit_loss, perplexity 0-dim; code_count (2048)
+        int32).  `outputs`: a dict of tensors to write into instead of fresh ones (graph capture; a `code_count` in it with
+        accumulate=True is added to).  No host synchronisation."""
+        pose6d = pose6d.to(self.device, torch.float32).contiguous()
+        B = pose6d.shape[0]
+        if tuple(pose6d.shape[1:]) != (21, 6):
+            raise ValueError(f"pose must be (B,21,6), got {tuple(pose6d.shape)}")
+        o = dict(outputs) if outputs is not None else {}
+        for k in want:
+            if k in o:
+                continue
+            if k in self.TOKENIZER_OUT:
+                shape, dt = self.TOKENIZER_OUT[k]
+                o[k] = torch.empty((B,) + shape, device=self.device, dtype=dt)
+            elif k in ("commit_loss", "perplexity"):
+                o[k] = torch.empty((), device=self.device, dtype=torch.float32)
+            elif k == "code_count":
+                if accumulate:
+                    raise ValueError("accumulate=True needs the caller's code_count in `outputs`")
+                o[k] = torch.empty(2048, device=self.device, dtype=torch.int32)
+            else:
+                raise KeyError(f"unknown round-trip output {k!r}")
+        for k, t in o.items():
+            shape, dt = self.TOKENIZER_OUT.get(k, ((2048,), torch.int32) if k == "code_count" else ((), torch.float32))
+            full = ((B,) + shape) if k in self.TOKENIZER_OUT else shape
+            if not (t.is_cuda and t.device == self.device and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == full):
+                raise ValueError(f"round-trip output {k!r} must be a contiguous {dt} tensor of shape {full} on {self.device}")
+        st = _cabi.TokenizerOut(**{k: o[k].data_ptr() for k in o}, accumulate_counts=1 if accumulate else 0)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.thmr_tokenizer_roundtrip(self.h, _ptr(pose6d), B, C.byref(st), _stream_ptr(self.device)), self.h)
+        return o
+
     def vq_argmin(self, x, want_dist=False):
         x = x.contiguous()
         rows = x.shape[0]

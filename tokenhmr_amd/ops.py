@@ -419,3 +419,36 @@ def decoder_init(bias, pos, B):
     with torch.cuda.device(bias.device):
         _check(_L().thmr_op_decoder_init(_p(bias), _p(pos), _p(x), int(B), E, _s(bias)))
     return x
+
+
+# ---- the tokenizer round trip's own kernels (csrc/tokenizer.hip) ----
+def vq_stats(x, codebook, idx, code_count=None, accumulate=False):
+    """What QuantizeEMAReset.forward returns beside the codes (quantize_cnn.py:38-47,118-121): x (rows, 256), codebook (2048, 256),
+    idx (rows) int32 -> (commit_loss, perplexity, code_count): two 0-dim device floats and the (2048) int32 histogram.  code_count given:
+    written in place — overwritten, or added to with accumulate=True (the perplexity is then that of the summed counts)."""
+    _req(x, codebook)
+    _req_i32(idx, code_count)
+    rows = x.shape[0]
+    if x.shape != (rows, 256) or codebook.shape != (2048, 256) or idx.shape != (rows,) or (code_count is not None and code_count.shape != (2048,)):
+        raise ValueError("vq_stats needs x (rows, 256), codebook (2048, 256), idx (rows), code_count (2048)")
+    if code_count is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs the caller's code_count")
+        code_count = torch.empty(2048, device=x.device, dtype=torch.int32)
+    partial = torch.empty((rows + 31) // 32, device=x.device, dtype=torch.float32)
+    out = torch.empty(2, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_vq_stats(_p(x), _p(codebook), _p(idx), rows, _p(code_count), int(bool(accumulate)), _p(partial),
+                                     C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 4), _s(x)))
+    return out[0], out[1], code_count
+
+
+def rotmat_to_aa(R):
+    """matrix_to_axis_angle (tokenization/models/rotation_utils.py:428-441): (..., 3, 3) -> (n, 3), n = the number of matrices."""
+    _req(R)
+    m = R.reshape(-1, 3, 3).contiguous()
+    n = m.shape[0]
+    aa = torch.empty(n, 3, device=R.device, dtype=torch.float32)
+    with torch.cuda.device(R.device):
+        _check(_L().thmr_op_rotmat_to_aa(_p(m), _p(aa), n, _s(R)))
+    return aa
