@@ -446,6 +446,51 @@ void thmr_smpl_destroy(thmr_smpl* m);
 int  thmr_smpl_forward(thmr_smpl* m, const float* pose_dev, int32_t pose2rot, const float* betas_dev, int32_t B,
                        float* verts_dev /*(B,6890,3)*/, float* joints_dev /*(B,44,3) or NULL*/, void* stream);
 
+/* Stand-alone SMPL-H model: the body mesh of the tokenizer workflow.  Replaces smplx.SMPLHLayer, the decoder's module-level
+ * body model (tokenization/models/vanilla_pose_vqvae.py:10-17, called :182-191 as body_model(body_pose=rotmat)), and smplx.SMPLH, the
+ * dataset's per-item CPU ground truth (tokenization/dataset/dataset_poseVQ.py:81,111-113), by one batched device call (csrc/smplh.hip).
+ * 52 chain joints (22 body + 2 x 15 hand), 459 pose features, 73 output joints = the 52 posed chain joints + the 21 vertices
+ * extra_verts picks (smplx vertex_ids['smplh'] in VertexJointSelector order).  New symbols under ABI 5: no struct or signature changed.
+ *   v_template (6890,3), shapedirs (6890,3,10), posedirs (459,20670) smplx's layout, J_regressor (52,6890), lbs_weights (6890,52),
+ *   parents[52] (parents[0] = -1, parents[i] in [0, i)), extra_verts[21] (ids in [0, 6890)); on_device: the pointers are device memory.
+ * thmr_smplh_create refuses (THMR_ERR_INVALID, message in thmr_last_error(NULL)) a null field, parents[0] != -1, a parents[i] outside
+ * [0, i) and an extra_verts id outside [0, 6890).  It also builds the FOLDED tables of the body-only path: every hand joint's weight
+ * column added into the body joint it hangs from (its wrist), and the blend-shape operand of the 21 body joints' 189 pose features. */
+typedef struct thmr_smplh_desc {
+    const float* v_template;
+    const float* shapedirs;
+    const float* posedirs;
+    const float* J_regressor;
+    const float* lbs_weights;
+    const int32_t* parents;
+    const int32_t* extra_verts;
+    int32_t on_device;
+    int32_t reserved;
+} thmr_smplh_desc;
+typedef struct thmr_smplh thmr_smplh;
+int  thmr_smplh_create(const thmr_smplh_desc* desc, int32_t max_batch, int32_t device, thmr_smplh** out);
+void thmr_smplh_destroy(thmr_smplh* m);
+/* pose2rot = 0: pose_dev holds rotation matrices; 1: axis-angle, converted by smplx batch_rodrigues (thmr_op_aa_to_rotmat's kernel).
+ * body_only = 0: 52 joints, (B,52,3,3) / (B,156).  body_only = 1: the root and the 21 body joints, (B,22,3,3) / (B,66), the hands at
+ * the identity — the tokenizer's call; runs the folded path (22-joint skinning, K = 224 blend product), same result up to rounding.
+ * betas_dev (B,10) and transl_dev (B,3) may be NULL (zeros); transl is added to vertices and joints.  joints_dev (B,73,3) may be NULL.
+ * Arguments are validated before any HIP call (a null handle / pose / verts, B outside [1, max_batch], a flag that is not 0 or 1);
+ * the call never allocates and never synchronises: three launches (four with pose2rot) on `stream`, capturable in a graph. */
+int  thmr_smplh_forward(thmr_smplh* m, const float* pose_dev, int32_t pose2rot, const float* betas_dev, const float* transl_dev,
+                        int32_t body_only, int32_t B, float* verts_dev /*(B,6890,3)*/, float* joints_dev /*(B,73,3) or NULL*/,
+                        void* stream);
+/* out_dev[0] = mean over items b < B and rows row_lo <= i < row_hi of || a[b][i] - b[b][i] ||_2, a and b (B, n_rows_per_item, 3): the three
+ * errors of the tokenizer's evaluation (tokenization/utils/eval_poseVQ.py) are this one operator —
+ *   calculate_pose_reconstruction_error :47-48   rows of the rotation matrices:  n = 63 (21 matrices x 3 rows), rows [0, 63)
+ *   calculate_mesh_reconstruction_error :50-51   vertices:                      n = 6890, rows [0, 6890)
+ *   calculate_jnts_reconstruction_error :53-55   body joints 1..21 of 73:       n = 73, rows [1, 22)
+ * Fixed-order two-stage fp32 / fp64 reduction without float atomics (two runs are bit-equal); the result stays on the device.
+ * workspace_dev: THMR_MEAN_ROW_DIST_WS floats, written before it is read in every call (needs no initialisation).
+ * Refused before any HIP call: a null buffer, B < 1, a row range outside 0 <= row_lo < row_hi <= n_rows_per_item, B * n > 2^29. */
+#define THMR_MEAN_ROW_DIST_WS 256
+int thmr_op_mean_row_dist(const float* a_dev, const float* b_dev, int32_t n_rows_per_item, int32_t row_lo, int32_t row_hi, int32_t B,
+                          float* out_dev, float* workspace_dev, void* stream);
+
 /* Evaluation metrics right after the hot path — stateless, all buffers device-side.
  * Replaces compute_similarity_transform / eval_pose and the arithmetic of Evaluator.__call__
  * (tokenhmr/lib/utils/pose_utils.py:61-143, :201-275): pelvis alignment, MPJPE, PA-MPJPE (3x3 SVD Procrustes), PVE, in mm.

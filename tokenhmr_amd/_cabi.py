@@ -39,6 +39,14 @@ class SmplDesc(C.Structure):
                 ("on_device", C.c_int32), ("update_hips", C.c_int32)]
 
 
+class SmplhDesc(C.Structure):
+    _fields_ = [("v_template", C.c_void_p), ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p), ("J_regressor", C.c_void_p),
+                ("lbs_weights", C.c_void_p), ("parents", C.c_void_p), ("extra_verts", C.c_void_p), ("on_device", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+MEAN_ROW_DIST_WS = 256      # header: THMR_MEAN_ROW_DIST_WS
+
 OUTPUT_FIELDS = ["pred_cam", "rotmat", "betas", "cls_logits_softmax", "pred_cam_t", "focal_length",
                  "pred_keypoints_3d", "pred_vertices", "pred_keypoints_2d", "token_idx",
                  "vit_features", "token_out", "cls_logits", "pose6d"]
@@ -124,6 +132,9 @@ ROWOPS_SYMBOLS = ("thmr_op_splitk_resid_ln", "thmr_op_add_ln64", "thmr_op_transp
 
 # the tokenizer round trip (csrc/tokenizer.hip): new symbols under ABI 5 as well — hard decode, the round trip, and its two kernels alone
 TOKENIZER_RT_SYMBOLS = ("thmr_vq_decode_idx", "thmr_tokenizer_roundtrip", "thmr_op_vq_stats", "thmr_op_rotmat_to_aa")
+
+# the SMPL-H body model and the tokenizer's mesh metrics (csrc/smplh.hip, eval.hip): new symbols under ABI 5 as well
+SMPLH_SYMBOLS = ("thmr_smplh_create", "thmr_smplh_destroy", "thmr_smplh_forward", "thmr_op_mean_row_dist")
 
 
 def load(exp=None):
@@ -220,6 +231,12 @@ def load(exp=None):
         lib.thmr_tokenizer_roundtrip.argtypes = [vp, vp, i32, C.POINTER(TokenizerOut), vp]
         lib.thmr_op_vq_stats.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         lib.thmr_op_rotmat_to_aa.argtypes = [vp, vp, i32, vp]
+    if hasattr(lib, "thmr_smplh_create"):                # the SMPL-H body model (added without an ABI change)
+        lib.thmr_smplh_create.argtypes = [C.POINTER(SmplhDesc), i32, i32, C.POINTER(vp)]
+        lib.thmr_smplh_destroy.argtypes = [vp]
+        lib.thmr_smplh_destroy.restype = None
+        lib.thmr_smplh_forward.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]
+        lib.thmr_op_mean_row_dist.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.thmr_smpl_create.argtypes = [C.POINTER(SmplDesc), i32, i32, C.POINTER(vp)]
     lib.thmr_smpl_destroy.argtypes = [vp]
     lib.thmr_smpl_destroy.restype = None
@@ -252,7 +269,7 @@ def load(exp=None):
         if not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
-        if name not in ("thmr_build_info", "thmr_last_error", "thmr_destroy", "thmr_smpl_destroy", "thmr_cropper_destroy",
+        if name not in ("thmr_build_info", "thmr_last_error", "thmr_destroy", "thmr_smpl_destroy", "thmr_smplh_destroy", "thmr_cropper_destroy",
                         "thmr_cropper_last_error", "thmr_collective_last_error", "thmr_renderer_destroy",
                         "thmr_renderer_last_error"):
             fn.restype = C.c_int

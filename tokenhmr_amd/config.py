@@ -89,6 +89,11 @@ RELEASE = HMRConfig()
 # smplx.SMPL kinematic tree (smplx==0.1.28, body_models.py / SMPL pkl 'kintree_table')
 SMPL_PARENTS = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21]
 
+# SMPL-H kinematic tree (kintree_table[0] of SMPLH_*.pkl): the 22 body joints of SMPL, then 15 joints per hand — index, middle, pinky,
+# ring, thumb, three each — hanging from the left wrist (20) and the right wrist (21)
+SMPLH_PARENTS = SMPL_PARENTS[:22] + [20, 22, 23, 20, 25, 26, 20, 28, 29, 20, 31, 32, 20, 34, 35] + \
+                [21, 37, 38, 21, 40, 41, 21, 43, 44, 21, 46, 47, 21, 49, 50]
+
 # smplx vertex_ids['smplh'] in VertexJointSelector order (nose, reye, leye, rear, lear,
 # LBigToe, LSmallToe, LHeel, RBigToe, RSmallToe, RHeel, l/r thumb..pinky tips)
 SMPL_EXTRA_VERTS = [332, 6260, 2800, 4071, 583,

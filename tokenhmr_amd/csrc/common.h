@@ -476,3 +476,27 @@ int launch_eval_pose(const float* pred, const float* gt, int nj, int gt_stride, 
                      int pelvis_mode, float* mpjpe, float* re, float* pelv, int B, hipStream_t s);
 int launch_eval_pve(const float* pv, const float* gv, const float* pelv, int nv, float* pve, int B, hipStream_t s);
 int launch_regress_joints(const float* J, const float* verts, int nj, int nv, float* out, int B, hipStream_t s);
+// out[0] = mean over items b < B and rows row_lo <= i < row_hi of ||a[b][i] - b[b][i]||, a and b (B, n, 3); partial: kMeanRowDistWs floats
+constexpr int kMeanRowDistWs = 256;
+int launch_mean_row_dist(const float* a, const float* b, int n, int row_lo, int row_hi, int B, float* out, float* partial, hipStream_t s);
+// smplh.hip: SMPL-H, 52 chain joints (22 body + 2 x 15 hand) and 73 output joints; the folded body-only path works on 22 joints, its weight
+// table padded to 24 columns.  dirsT (20670 x 480) = [shapedirs | posedirs (459) | 0]^T, dirsT_body (20670 x 224) = [shapedirs | the 189
+// body features | 0]^T (launch_smplh_build_dirs); scratch A (B,52,12), xf (B,480), vposed (B,20670)
+constexpr int THMR_SMPLH_NJ = 52, THMR_SMPLH_NBODY = 22, THMR_SMPLH_NBODY_PAD = 24, THMR_SMPLH_NOUT = 73, THMR_SMPLH_NP = 459;
+constexpr int THMR_SMPLH_KX = 480, THMR_SMPLH_KXB = 224;
+struct SmplhArgs {
+    const float *rotmat;              // (B,52,3,3), or (B,22,3,3) when body_only
+    const float *betas, *transl;      // (B,10) / (B,3); either may be null (zeros)
+    const float *Jt, *Jsd;            // (52,3), (52,3,10)  (launch_smplh_jreg)
+    const int32_t *parents, *fold;    // (52): parent; the body joint a joint folds into (itself below 22, else its wrist)
+    const int32_t* extra;             // (21) selected vertex ids
+    const float *vt, *dirsT, *dirsT_body, *W, *W_body;   // W (6890,52), W_body (6890,24) (launch_smplh_fold_weights)
+    float *A, *xf, *vposed;
+    float *verts, *joints;            // (B,6890,3); (B,73,3) or null
+    int B, body_only;
+};
+int launch_smplh_jreg(const float* Jreg, const float* vt, const float* sd, float* Jt, float* Jsd, hipStream_t s);
+int launch_smplh_build_dirs(const float* sd, const float* pd, float* dirsT, int body_only, hipStream_t s);
+int launch_smplh_fold_weights(const float* W, const int32_t* fold, float* Wf, hipStream_t s);
+int smplh_poses_per_workgroup(int B);
+int launch_smplh(const SmplhArgs& a, hipStream_t s);

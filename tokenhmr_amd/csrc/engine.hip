@@ -2417,6 +2417,115 @@ int thmr_smpl_forward(thmr_smpl* m, const float* pose, int32_t pose2rot, const f
     return 0;
 }
 
+// ---- stand-alone SMPL-H model (csrc/smplh.hip) ----
+struct thmr_smplh {
+    float* mem = nullptr;
+    int max_batch = 0;
+    size_t o_vt, o_sd, o_pd, o_jr, o_w, o_wb, o_int, o_jt, o_jsd, o_dirs, o_dirsb, o_A, o_xf, o_vposed, o_rot, total;
+};
+
+int thmr_smplh_create(const thmr_smplh_desc* d, int32_t max_batch, int32_t device, thmr_smplh** out) {
+    thmr_engine* e = nullptr;
+    constexpr int HJ = THMR_SMPLH_NJ, HB = THMR_SMPLH_NBODY, HP = THMR_SMPLH_NP;
+    if (!d || !out || max_batch < 1) return fail(e, THMR_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    if (!d->v_template || !d->shapedirs || !d->posedirs || !d->J_regressor || !d->lbs_weights || !d->parents || !d->extra_verts)
+        return fail(e, THMR_ERR_INVALID, "thmr_smplh_desc has a null field");
+    HIP_OK(hipSetDevice(device));
+    int32_t par[HJ], ext[21], fold[HJ];
+    if (d->on_device) {
+        HIP_OK(hipMemcpy(par, d->parents, sizeof(par), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(ext, d->extra_verts, sizeof(ext), hipMemcpyDeviceToHost));
+    } else {
+        memcpy(par, d->parents, sizeof(par));
+        memcpy(ext, d->extra_verts, sizeof(ext));
+    }
+    if (par[0] != -1) return fail(e, THMR_ERR_INVALID, "thmr_smplh_desc.parents[0] must be -1 (the root)");
+    for (int i = 1; i < HJ; ++i)
+        if (par[i] < 0 || par[i] >= i)
+            return fail(e, THMR_ERR_INVALID, "thmr_smplh_desc.parents[" + std::to_string(i) + "] = " + std::to_string(par[i]) + " is outside [0, " + std::to_string(i) + ")");
+    for (int k = 0; k < 21; ++k)
+        if (ext[k] < 0 || ext[k] >= NV)
+            return fail(e, THMR_ERR_INVALID, "thmr_smplh_desc.extra_verts[" + std::to_string(k) + "] = " + std::to_string(ext[k]) + " is outside [0, 6890)");
+    // fold[j]: the body joint whose bone matrix joint j has when every hand rotation is the identity.  parents[i] < i keeps the 22 body
+    // joints a chain of their own and gives fold[j] < 22 by induction (one ascending pass)
+    for (int j = 0; j < HJ; ++j) fold[j] = j < HB ? j : fold[par[j]];
+    thmr_smplh* m = new thmr_smplh();
+    m->max_batch = max_batch;
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
+    m->o_vt = take((size_t)NV * 3); m->o_sd = take((size_t)NV * 30); m->o_pd = take((size_t)HP * NV * 3);
+    m->o_jr = take((size_t)HJ * NV); m->o_w = take((size_t)NV * HJ); m->o_wb = take((size_t)NV * THMR_SMPLH_NBODY_PAD);
+    m->o_int = take(192); m->o_jt = take(HJ * 3); m->o_jsd = take(HJ * 30);
+    m->o_dirs = take((size_t)NV * 3 * THMR_SMPLH_KX); m->o_dirsb = take((size_t)NV * 3 * THMR_SMPLH_KXB);
+    const size_t B = (size_t)max_batch;
+    m->o_A = take(B * HJ * 12); m->o_xf = take(B * THMR_SMPLH_KX); m->o_rot = take(B * HJ * 9); m->o_vposed = take(B * NV * 3);
+    m->total = off;
+    if (hipMalloc(&m->mem, off * sizeof(float)) != hipSuccess) { delete m; return fail(e, THMR_ERR_NOMEM, "hipMalloc(smplh) failed"); }
+    const hipMemcpyKind k = d->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    auto cp = [&](size_t o, const void* src, size_t bytes) { return hipMemcpy(m->mem + o, src, bytes, k) == hipSuccess; };
+    int32_t* ints = reinterpret_cast<int32_t*>(m->mem + m->o_int);      // parents [0, 52) | extra_verts [64, 85) | fold [128, 180)
+    bool ok = cp(m->o_vt, d->v_template, sizeof(float) * NV * 3) && cp(m->o_sd, d->shapedirs, sizeof(float) * NV * 30) &&
+              cp(m->o_pd, d->posedirs, sizeof(float) * (size_t)HP * NV * 3) && cp(m->o_jr, d->J_regressor, sizeof(float) * HJ * NV) &&
+              cp(m->o_w, d->lbs_weights, sizeof(float) * NV * HJ) &&
+              hipMemcpy(ints, par, sizeof(par), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(ints + 64, ext, sizeof(ext), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(ints + 128, fold, sizeof(fold), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok || launch_smplh_jreg(m->mem + m->o_jr, m->mem + m->o_vt, m->mem + m->o_sd, m->mem + m->o_jt, m->mem + m->o_jsd, nullptr) != 0 ||
+        launch_smplh_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirs, 0, nullptr) != 0 ||
+        launch_smplh_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirsb, 1, nullptr) != 0 ||
+        launch_smplh_fold_weights(m->mem + m->o_w, ints + 128, m->mem + m->o_wb, nullptr) != 0 ||
+        hipDeviceSynchronize() != hipSuccess) {
+        thmr_smplh_destroy(m);
+        return fail(e, THMR_ERR_HIP, "SMPL-H constant upload failed");
+    }
+    *out = m;
+    return 0;
+}
+
+void thmr_smplh_destroy(thmr_smplh* m) {
+    if (!m) return;
+    if (m->mem) (void)hipFree(m->mem);
+    delete m;
+}
+
+int thmr_smplh_forward(thmr_smplh* m, const float* pose, int32_t pose2rot, const float* betas, const float* transl, int32_t body_only,
+                       int32_t B, float* verts, float* joints, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!m || !pose || !verts) return fail(e, THMR_ERR_INVALID, "smplh_forward: null argument");
+    if (B < 1 || B > m->max_batch) return fail(e, THMR_ERR_INVALID, "smplh_forward: batch outside [1, max_batch]");
+    if ((pose2rot != 0 && pose2rot != 1) || (body_only != 0 && body_only != 1))
+        return fail(e, THMR_ERR_INVALID, "smplh_forward: pose2rot and body_only are 0 or 1");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nj = body_only ? THMR_SMPLH_NBODY : THMR_SMPLH_NJ;
+    const float* rot = pose;
+    if (pose2rot) {
+        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * nj, st));
+        rot = m->mem + m->o_rot;
+    }
+    const int32_t* ints = reinterpret_cast<const int32_t*>(m->mem + m->o_int);
+    SmplhArgs a{};
+    a.rotmat = rot; a.betas = betas; a.transl = transl; a.Jt = m->mem + m->o_jt; a.Jsd = m->mem + m->o_jsd;
+    a.parents = ints; a.extra = ints + 64; a.fold = ints + 128;
+    a.vt = m->mem + m->o_vt; a.dirsT = m->mem + m->o_dirs; a.dirsT_body = m->mem + m->o_dirsb; a.W = m->mem + m->o_w; a.W_body = m->mem + m->o_wb;
+    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_xf; a.vposed = m->mem + m->o_vposed;
+    a.verts = verts; a.joints = joints; a.B = B; a.body_only = body_only;
+    LAUNCH_OK(launch_smplh(a, st));
+    return 0;
+}
+
+int thmr_op_mean_row_dist(const float* a, const float* b, int32_t n_rows_per_item, int32_t row_lo, int32_t row_hi, int32_t B, float* out,
+                          float* workspace, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!a || !b || !out || !workspace) return fail(e, THMR_ERR_INVALID, "mean_row_dist: null buffer");
+    if (B < 1 || n_rows_per_item < 1 || row_lo < 0 || row_hi <= row_lo || row_hi > n_rows_per_item)
+        return fail(e, THMR_ERR_INVALID, "mean_row_dist: B >= 1 and 0 <= row_lo < row_hi <= n_rows_per_item are required");
+    if ((int64_t)B * n_rows_per_item > ((int64_t)1 << 29))
+        return fail(e, THMR_ERR_INVALID, "mean_row_dist: B * n_rows_per_item <= 2^29 is required");
+    LAUNCH_OK(launch_mean_row_dist(a, b, n_rows_per_item, row_lo, row_hi, B, out, workspace, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 // ---- evaluation metrics (stateless) ----
 int thmr_eval_pose(const float* pred_j, const float* gt_j, int32_t nj, int32_t gt_stride, const int32_t* kp, int32_t nkp,
                    int32_t pelvis_ind, int32_t pelvis_mode, const float* pred_v, const float* gt_v, int32_t nv, int32_t B,

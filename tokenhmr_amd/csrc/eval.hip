@@ -205,7 +205,53 @@ __global__ __launch_bounds__(256) void regress_joints_kernel(const float* __rest
     if (t < 3) out[((int64_t)b * nj + j) * 3 + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
 }
 
+// The tokenizer's three reconstruction errors (tokenization/utils/eval_poseVQ.py:47-55) are one formula, mean_i ||a_i - b_i||_2 over
+// rows of 3: the rows of the rotation matrices, the vertices, joints 1..21 of 73.  a, b (B, n, 3); rows [lo, lo + nr) of every item.
+// Two stages, both in a fixed order and without float atomics, so two runs give identical bits: workgroup g adds the rows
+// g*256 + t, + gridDim*256, ... per lane, the lanes across the wave by xor-shuffles, the four waves in order -> partial[g]; one
+// workgroup then adds the partial sums in fp64 by a fixed tree.  Every word of `partial` that the second stage reads was written by the
+// first stage of the same call: no counter, nothing to zero, and a captured call replays like the eager one.
+__global__ __launch_bounds__(256) void mean_row_dist_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, int n,
+                                                                    int lo, int nr, int total, float* __restrict__ partial) {
+    __shared__ float red[4];
+    const int t = threadIdx.x;
+    float acc = 0.f;
+    for (int r = blockIdx.x * 256 + t; r < total; r += gridDim.x * 256) {
+        const int64_t o = ((int64_t)(r / nr) * n + lo + r % nr) * 3;
+        const float dx = a[o + 0] - b[o + 0], dy = a[o + 1] - b[o + 1], dz = a[o + 2] - b[o + 2];
+        acc += sqrtf(dx * dx + dy * dy + dz * dz);
+    }
+    const float s = wave_sum(acc);
+    if ((t & 63) == 0) red[t >> 6] = s;
+    __syncthreads();
+    if (t == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void mean_row_dist_final_kernel(const float* __restrict__ partial, int nblk, int total,
+                                                                  float* __restrict__ out) {
+    __shared__ double sh[256];
+    const int t = threadIdx.x;
+    sh[t] = t < nblk ? (double)partial[t] : 0.0;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    if (t == 0) out[0] = (float)(sh[0] / (double)total);
+}
+
 }  // namespace
+
+int launch_mean_row_dist(const float* a, const float* b, int n, int row_lo, int row_hi, int B, float* out, float* partial, hipStream_t s) {
+    if (!a || !b || !out || !partial || B < 1 || n < 1 || row_lo < 0 || row_hi <= row_lo || row_hi > n) return -1;
+    if ((int64_t)B * n * 3 >= ((int64_t)1 << 31) - 256 * kMeanRowDistWs) return -1;      // row counters are 32-bit
+    const int nr = row_hi - row_lo, total = B * nr;
+    const int nblk = (total + 255) / 256 < kMeanRowDistWs ? (total + 255) / 256 : kMeanRowDistWs;
+    hipLaunchKernelGGL(mean_row_dist_partial_kernel, dim3(nblk), dim3(256), 0, s, a, b, n, row_lo, nr, total, partial);
+    if (hipGetLastError() != hipSuccess) return -2;
+    hipLaunchKernelGGL(mean_row_dist_final_kernel, dim3(1), dim3(256), 0, s, partial, nblk, total, out);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 
 int launch_eval_pose(const float* pred, const float* gt, int nj, int gt_stride, const int32_t* kp, int nkp, int pelvis_ind,
                      int pelvis_mode, float* mpjpe, float* re, float* pelv, int B, hipStream_t s) {

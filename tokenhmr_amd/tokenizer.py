@@ -161,10 +161,11 @@ class VanillaTokenizer(_TokenizerModule):
     histogram, and the commit loss is the rows-weighted mean of the chunks' means (equal to the single mean up to fp32 rounding).
     `code_count` ((2048) int32, the last forward's histogram) is kept for codebook-usage reports.
 
-    The body mesh ('pred_body_mesh', 'pred_body_vertices', 'pred_body_joints', vanilla_pose_vqvae.py:182-191) needs an SMPL-H layer.
-    This package's LBS kernels are built for SMPL's 24 joints and no SMPL-H asset ships with it, so mesh_inference=True produces the
-    axis-angle output and — only when a `body_model=` callable is given, called as body_model(body_pose=rotmat) like the reference's
-    module-level layer — the three mesh keys; without it they are absent.
+    The body mesh ('pred_body_mesh', 'pred_body_vertices', 'pred_body_joints', vanilla_pose_vqvae.py:182-191) needs an SMPL-H layer, and
+    no SMPL-H asset ships with this package: mesh_inference=True produces the axis-angle output and — only when `body_model=` is given —
+    the three mesh keys; without it they are absent.  `body_model` is a directory or file holding SMPLH_NEUTRAL.pkl, or a constants dict
+    (smpl_assets.load_smplh_pkl / make_synthetic_smplh): the module then builds a `tokenhmr_amd.smplh.SMPLHLayer` on its device, which
+    runs the folded 22-joint kernels; or any callable, called as body_model(body_pose=rotmat) like the reference's module-level layer.
 
     encode(x) -> (B,160) int64 does what EncodeTokens does (encoder, `preprocess`, argmin).  The reference's own
     VanillaTokenizer.encode RAISES ("mat1 and mat2 shapes cannot be multiplied (768x160 and 256x2048)"): it skips `preprocess`
@@ -188,6 +189,7 @@ class VanillaTokenizer(_TokenizerModule):
                 raise ValueError(f"tokenizer architecture differs from the engine's: ARCH.NB_JOINTS = {joints!r}, the HIP kernels are built for 21")
         self.mesh_inference = bool(mesh_inference)
         self.body_model = body_model
+        self._own_body_model = body_model is not None and not callable(body_model)       # a model path or a constants dict
         self.code_count = None
         self._own_engine = engine is None
         tok = None
@@ -197,6 +199,19 @@ class VanillaTokenizer(_TokenizerModule):
         self.device = torch.device(device) if engine is None else engine.device
         self.max_batch = max_batch if engine is None else engine.max_batch
         self.engine = engine if engine is not None else (_engine_from_tensors(tok, self.device, max_batch) if tok is not None else None)
+        if self._own_body_model:
+            from .smplh import SMPLHLayer
+            self.body_model = SMPLHLayer(body_model, num_betas=10, ext="pkl", max_batch=self.max_batch, device=self.device)
+
+    def _body_mesh(self, rot):
+        """body_model(body_pose=rotmat), vanilla_pose_vqvae.py:184.  The layer this module built itself holds max_batch poses per call,
+        like the engine: more are chunked and the pieces joined."""
+        if not self._own_body_model or rot.shape[0] <= self.max_batch:
+            return self.body_model(body_pose=rot)
+        import types
+        parts = [self.body_model(body_pose=c) for c in self._chunks(rot)]
+        return types.SimpleNamespace(**{k: torch.cat([getattr(p, k) for p in parts], 0)
+                                        for k in ("vertices", "joints", "full_pose", "betas", "body_pose", "global_orient")}, transl=None)
 
     def load_state_dict(self, net, strict=True):
         """ckpt['net'] as train_poseVQ.py:63-66 passes it; 'body_model.*' keys (the reference module's SMPL-H layer) are ignored.
@@ -253,7 +268,7 @@ class VanillaTokenizer(_TokenizerModule):
         if self.mesh_inference:
             output["pred_pose_body_aa"] = cat("aa").reshape(B, 63)
             if self.body_model is not None:
-                mesh = self.body_model(body_pose=rot)
+                mesh = self._body_mesh(rot)
                 output.update({"pred_body_mesh": mesh, "pred_body_vertices": mesh.vertices, "pred_body_joints": mesh.joints})
         return output, commit, perp
 
