@@ -491,6 +491,83 @@ int  thmr_smplh_forward(thmr_smplh* m, const float* pose_dev, int32_t pose2rot, 
 int thmr_op_mean_row_dist(const float* a_dev, const float* b_dev, int32_t n_rows_per_item, int32_t row_lo, int32_t row_hi, int32_t B,
                           float* out_dev, float* workspace_dev, void* stream);
 
+/* The forward value of the reference's loss (csrc/loss.hip): TokenHMR.compute_loss (tokenhmr/lib/models/tokenhmr.py:190-277)
+ * with its loss modules (losses.py:36-228) for B items, as validation_step runs it straight after forward_step (:421-440).  Stateless, all
+ * buffers fp32 device memory and contiguous.  New symbols under ABI 5: no existing struct or signature changed.
+ *   mode THMR_VAL_LOSS_PLAIN  the `else` branch (:250-262), what validation runs:
+ *        2D   sum conf |pred - gt|                                        (Keypoint2DLoss, L1)
+ *        3D   sum conf |(pred - pred[pelvis]) - (gt - gt[pelvis])|          (Keypoint3DLoss)
+ *        global_orient / body_pose / betas   sum has (pred - gt)^2 over 9 / 23 x 9 / 10 values per item   (ParameterLoss)
+ *   mode THMR_VAL_LOSS_LOOSE  the LOOSE_SUP branch (:214-249), the threshold-adaptive loss with the *PCKT modules:
+ *        kp2d_err = conf sum_xy (pred - gt)^2;  valid2d = kp2d_err > kp2d_thresh;  weak2d = conf (1 - valid2d);  the 2D loss uses
+ *        conf valid2d, plus loose_weight x the same sum under weak2d;  the 3D confidence becomes conf3d [(valid_3d + conf valid2d) > 0.5];
+ *        angle_err = |matrix_to_axis_angle(R_pred R_gt^T)| per joint (losses.py:22-33; thmr_op_rotmat_to_aa's device function);
+ *        valid_rot = ((angle_err > angle_thresh) has + valid_3d) != 0;  weak_rot = (1 - valid_rot) has;  the pose terms are
+ *        sum valid_rot sum_9 (.)^2 plus loose_weight x the same under weak_rot;  betas uses has_betas x valid_3d and the plain form.
+ * The ground-truth pose is (B,72) axis-angle, converted by aa_to_rotmat (thmr_op_aa_to_rotmat's arithmetic, line for line; :235,260), or — with
+ * gt_pose_is_rotmat — (B,24,3,3) matrices; joint 0 is global_orient on both sides, so pred_rotmat is exactly thmr_outputs.rotmat.
+ * ONE DELIBERATE DEPARTURE: the reference writes into the batch (:223, :227, :240); this call writes into no input.  The values it would
+ * have written are the optional outputs conf2d_used, conf3d_used and has_betas_used (loose mode only).
+ * Two launches on `stream`, no host synchronisation, no allocation, no float atomics: one wave per item writes five partial sums, one
+ * workgroup adds them in fp64 in a fixed order.  Two runs are bit-equal and a captured call replays like the eager one.
+ * workspace_dev: THMR_VAL_LOSS_WS_PER_ITEM x B floats, written before they are read in every call (no initialisation needed).
+ * Refused before any HIP call (THMR_ERR_INVALID, message in thmr_last_error(NULL)): a null descriptor / input / output struct, a null
+ * required input, B outside [1, 2^24], a mode that is not 0 or 1, loose mode without valid_3d, kp2d_thresh or angle_thresh, pelvis_id
+ * outside [0, 44), a gt_pose_is_rotmat that is not 0 or 1, a null workspace, gt_keypoints_3d not 16-byte or pred_keypoints_2d not 8-byte
+ * aligned (their rows are read as float4 / float2), a `running` that is not 8-byte aligned. */
+#define THMR_VAL_LOSS_PLAIN 0
+#define THMR_VAL_LOSS_LOOSE 1
+#define THMR_VAL_LOSS_WS_PER_ITEM 5
+typedef struct thmr_val_loss_desc {
+    double w_keypoints_2d, w_keypoints_3d, w_global_orient, w_body_pose, w_betas;   /* cfg.LOSS_WEIGHTS */
+    double loose_weight;                                                            /* cfg.MODEL.LOOSE_WEIGHT */
+    int32_t pelvis_id;                /* 39 in the reference (25 + 14, :228,253) */
+    int32_t mode;                     /* THMR_VAL_LOSS_* */
+    int32_t gt_pose_is_rotmat;        /* 0: gt_pose (B,72) axis-angle; 1: (B,24,3,3) rotation matrices */
+    int32_t reserved;
+} thmr_val_loss_desc;
+typedef struct thmr_val_loss_in {
+    const float* pred_keypoints_2d;   /* (B,44,2) */
+    const float* pred_keypoints_3d;   /* (B,44,3) */
+    const float* pred_rotmat;         /* (B,24,3,3) */
+    const float* pred_betas;          /* (B,10) */
+    const float* gt_keypoints_2d;     /* (B,44,3), confidence last */
+    const float* gt_keypoints_3d;     /* (B,44,4), confidence last */
+    const float* gt_pose;             /* see gt_pose_is_rotmat */
+    const float* gt_betas;            /* (B,10) */
+    const float* has_global_orient;   /* (B) */
+    const float* has_body_pose;       /* (B) */
+    const float* has_betas;           /* (B) */
+    const float* valid_3d;            /* (B); loose mode only */
+    const float* kp2d_thresh;         /* (44); loose mode only */
+    const float* angle_thresh;        /* (24), [0] = global_orient; loose mode only */
+} thmr_val_loss_in;
+typedef struct thmr_val_loss_out {   /* every pointer may be NULL */
+    float* losses;                    /* (6): loss, loss_keypoints_2d, loss_keypoints_3d, loss_global_orient, loss_body_pose, loss_betas */
+    float* per_item;                  /* (B,5): the five unweighted terms of every item, in the order of losses[1..5] */
+    float* kp2d_err;                  /* (B,44)  loose mode only, like the seven below */
+    float* angle_err;                 /* (B,24) */
+    float* valid2d;                   /* (B,44) 0 / 1 */
+    float* weak2d;                    /* (B,44) */
+    float* valid_rot;                 /* (B,24) 0 / 1 */
+    float* weak_rot;                  /* (B,24) */
+    float* conf2d_used;               /* (B,44) */
+    float* conf3d_used;               /* (B,44) */
+    float* has_betas_used;            /* (B) */
+    double* running;                  /* (7): += the six losses of this call (their fp32 values), [6] += 1 */
+} thmr_val_loss_out;
+int thmr_val_loss(const thmr_val_loss_desc* desc, const thmr_val_loss_in* in, int32_t B, const thmr_val_loss_out* out,
+                  float* workspace_dev, void* stream);
+/* TokenLoss (losses.py:230-252): CrossEntropyLoss in mean reduction over the rows of an fp32 (rows, 2048) matrix,
+ *   out_dev[0] = mean_r (log sum_k exp(x[r][k] - max_r) + max_r - x[r][target[r]]),
+ * applied to whatever it is handed — the reference passes the softmax output cls_logits_softmax (rows = B x 160); raw logits work too.
+ * target_dev: int32 (rows).  A target outside [0, 2048) is never read through: that row's loss is NaN and so is the mean.
+ * One wave per row reads it once (8 float4 per lane); the row losses go to workspace_dev (THMR_TOKEN_CE_WS_PER_ROW x rows floats, written
+ * before they are read), one workgroup adds them in fp64 in a fixed order.  Bit-equal between runs, capturable, no host synchronisation.
+ * Refused before any HIP call: a null buffer, rows < 1, x_dev not 16-byte aligned. */
+#define THMR_TOKEN_CE_WS_PER_ROW 1
+int thmr_op_token_ce(const float* x_dev, const int32_t* target_dev, int32_t rows, float* out_dev, float* workspace_dev, void* stream);
+
 /* Evaluation metrics right after the hot path — stateless, all buffers device-side.
  * Replaces compute_similarity_transform / eval_pose and the arithmetic of Evaluator.__call__
  * (tokenhmr/lib/utils/pose_utils.py:61-143, :201-275): pelvis alignment, MPJPE, PA-MPJPE (3x3 SVD Procrustes), PVE, in mm.

@@ -46,6 +46,27 @@ class SmplhDesc(C.Structure):
 
 
 MEAN_ROW_DIST_WS = 256      # header: THMR_MEAN_ROW_DIST_WS
+# thmr_val_loss / thmr_op_token_ce (header: THMR_VAL_LOSS_*, THMR_TOKEN_CE_WS_PER_ROW): modes and workspace floats per item / per row
+VAL_LOSS_PLAIN, VAL_LOSS_LOOSE = 0, 1
+VAL_LOSS_WS_PER_ITEM, TOKEN_CE_WS_PER_ROW = 5, 1
+VAL_LOSS_IN_FIELDS = ["pred_keypoints_2d", "pred_keypoints_3d", "pred_rotmat", "pred_betas", "gt_keypoints_2d", "gt_keypoints_3d", "gt_pose",
+                      "gt_betas", "has_global_orient", "has_body_pose", "has_betas", "valid_3d", "kp2d_thresh", "angle_thresh"]
+VAL_LOSS_OUT_FIELDS = ["losses", "per_item", "kp2d_err", "angle_err", "valid2d", "weak2d", "valid_rot", "weak_rot", "conf2d_used",
+                       "conf3d_used", "has_betas_used", "running"]
+
+
+class ValLossDesc(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("w_keypoints_2d", "w_keypoints_3d", "w_global_orient", "w_body_pose", "w_betas", "loose_weight")] + \
+               [(n, C.c_int32) for n in ("pelvis_id", "mode", "gt_pose_is_rotmat", "reserved")]
+
+
+class ValLossIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in VAL_LOSS_IN_FIELDS]
+
+
+class ValLossOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in VAL_LOSS_OUT_FIELDS]
+
 
 OUTPUT_FIELDS = ["pred_cam", "rotmat", "betas", "cls_logits_softmax", "pred_cam_t", "focal_length",
                  "pred_keypoints_3d", "pred_vertices", "pred_keypoints_2d", "token_idx",
@@ -135,6 +156,9 @@ TOKENIZER_RT_SYMBOLS = ("thmr_vq_decode_idx", "thmr_tokenizer_roundtrip", "thmr_
 
 # the SMPL-H body model and the tokenizer's mesh metrics (csrc/smplh.hip, eval.hip): new symbols under ABI 5 as well
 SMPLH_SYMBOLS = ("thmr_smplh_create", "thmr_smplh_destroy", "thmr_smplh_forward", "thmr_op_mean_row_dist")
+
+# the forward value of the loss (csrc/loss.hip): new symbols under ABI 5 as well
+LOSS_SYMBOLS = ("thmr_val_loss", "thmr_op_token_ce")
 
 
 def load(exp=None):
@@ -237,6 +261,9 @@ def load(exp=None):
         lib.thmr_smplh_destroy.restype = None
         lib.thmr_smplh_forward.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]
         lib.thmr_op_mean_row_dist.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    if hasattr(lib, "thmr_val_loss"):                    # the forward value of the loss (added without an ABI change)
+        lib.thmr_val_loss.argtypes = [C.POINTER(ValLossDesc), C.POINTER(ValLossIn), i32, C.POINTER(ValLossOut), vp, vp]
+        lib.thmr_op_token_ce.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.thmr_smpl_create.argtypes = [C.POINTER(SmplDesc), i32, i32, C.POINTER(vp)]
     lib.thmr_smpl_destroy.argtypes = [vp]
     lib.thmr_smpl_destroy.restype = None

@@ -479,6 +479,24 @@ int launch_regress_joints(const float* J, const float* verts, int nj, int nv, fl
 // out[0] = mean over items b < B and rows row_lo <= i < row_hi of ||a[b][i] - b[b][i]||, a and b (B, n, 3); partial: kMeanRowDistWs floats
 constexpr int kMeanRowDistWs = 256;
 int launch_mean_row_dist(const float* a, const float* b, int n, int row_lo, int row_hi, int B, float* out, float* partial, hipStream_t s);
+// loss.hip: the forward value of compute_loss (tokenhmr.py:190-277) and TokenLoss (losses.py:230-252).  Every output pointer may be null.
+struct ValLossArgs {
+    const float *pred_kp2d, *pred_kp3d, *pred_rotmat, *pred_betas;        // (B,44,2) (B,44,3) (B,24,3,3) (B,10)
+    const float *gt_kp2d, *gt_kp3d, *gt_pose, *gt_betas;                  // (B,44,3) (B,44,4) (B,72) or (B,24,3,3), (B,10)
+    const float *has_global_orient, *has_body_pose, *has_betas;           // (B)
+    const float *valid_3d, *kp2d_thresh, *angle_thresh;                   // loose mode: (B), (44), (24)
+    float *losses, *per_item, *kp2d_err, *angle_err;                      // (6) (B,5) (B,44) (B,24)
+    float *valid2d, *weak2d, *valid_rot, *weak_rot;                       // (B,44) x 2, (B,24) x 2, 0 / 1
+    float *conf2d_used, *conf3d_used, *has_betas_used;                    // (B,44) x 2, (B): what the reference writes into the batch
+    double* running;                                                      // (7): six sums and a batch count
+    float* partial;                                                       // (B,5) workspace
+    double w[5];                                                          // LOSS_WEIGHTS: 2D, 3D, global_orient, body_pose, betas
+    float loose_weight;
+    int B, pelvis_id, mode, gt_pose_is_rotmat;
+};
+int launch_val_loss(const ValLossArgs& a, hipStream_t s);
+// out[0] = mean over rows of logsumexp(x_r) - x_r[target_r], x (rows, 2048); row_loss: rows floats of workspace
+int launch_token_ce(const float* x, const int32_t* target, int rows, float* out, float* row_loss, hipStream_t s);
 // smplh.hip: SMPL-H, 52 chain joints (22 body + 2 x 15 hand) and 73 output joints; the folded body-only path works on 22 joints, its weight
 // table padded to 24 columns.  dirsT (20670 x 480) = [shapedirs | posedirs (459) | 0]^T, dirsT_body (20670 x 224) = [shapedirs | the 189
 // body features | 0]^T (launch_smplh_build_dirs); scratch A (B,52,12), xf (B,480), vposed (B,20670)

@@ -2526,6 +2526,53 @@ int thmr_op_mean_row_dist(const float* a, const float* b, int32_t n_rows_per_ite
     return 0;
 }
 
+// ---- the forward value of the loss (stateless; csrc/loss.hip) ----
+int thmr_val_loss(const thmr_val_loss_desc* d, const thmr_val_loss_in* in, int32_t B, const thmr_val_loss_out* out, float* workspace,
+                  void* stream) {
+    thmr_engine* e = nullptr;
+    if (!d || !in || !out) return fail(e, THMR_ERR_INVALID, "val_loss: null descriptor, input or output struct");
+    if (!in->pred_keypoints_2d || !in->pred_keypoints_3d || !in->pred_rotmat || !in->pred_betas || !in->gt_keypoints_2d ||
+        !in->gt_keypoints_3d || !in->gt_pose || !in->gt_betas || !in->has_global_orient || !in->has_body_pose || !in->has_betas)
+        return fail(e, THMR_ERR_INVALID, "val_loss: null input buffer");
+    if (B < 1 || B > (1 << 24)) return fail(e, THMR_ERR_INVALID, "val_loss: 1 <= B <= 2^24 is required");
+    if (d->mode != THMR_VAL_LOSS_PLAIN && d->mode != THMR_VAL_LOSS_LOOSE)
+        return fail(e, THMR_ERR_INVALID, "val_loss: mode is THMR_VAL_LOSS_PLAIN (0) or THMR_VAL_LOSS_LOOSE (1)");
+    if (d->mode == THMR_VAL_LOSS_LOOSE && (!in->valid_3d || !in->kp2d_thresh || !in->angle_thresh))
+        return fail(e, THMR_ERR_INVALID, "val_loss: the loose mode needs valid_3d, kp2d_thresh and angle_thresh");
+    if (d->pelvis_id < 0 || d->pelvis_id >= 44) return fail(e, THMR_ERR_INVALID, "val_loss: pelvis_id outside [0, 44)");
+    if (d->gt_pose_is_rotmat != 0 && d->gt_pose_is_rotmat != 1) return fail(e, THMR_ERR_INVALID, "val_loss: gt_pose_is_rotmat is 0 or 1");
+    if (!workspace) return fail(e, THMR_ERR_INVALID, "val_loss: null workspace");
+    if (reinterpret_cast<uintptr_t>(in->gt_keypoints_3d) % 16 != 0 || reinterpret_cast<uintptr_t>(in->pred_keypoints_2d) % 8 != 0)
+        return fail(e, THMR_ERR_INVALID, "val_loss: gt_keypoints_3d must be 16-byte and pred_keypoints_2d 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->running) % 8 != 0) return fail(e, THMR_ERR_INVALID, "val_loss: running (7 doubles) must be 8-byte aligned");
+    ValLossArgs a{};
+    a.pred_kp2d = in->pred_keypoints_2d; a.pred_kp3d = in->pred_keypoints_3d; a.pred_rotmat = in->pred_rotmat; a.pred_betas = in->pred_betas;
+    a.gt_kp2d = in->gt_keypoints_2d; a.gt_kp3d = in->gt_keypoints_3d; a.gt_pose = in->gt_pose; a.gt_betas = in->gt_betas;
+    a.has_global_orient = in->has_global_orient; a.has_body_pose = in->has_body_pose; a.has_betas = in->has_betas;
+    a.valid_3d = in->valid_3d; a.kp2d_thresh = in->kp2d_thresh; a.angle_thresh = in->angle_thresh;
+    a.losses = out->losses; a.per_item = out->per_item; a.running = out->running;
+    if (d->mode == THMR_VAL_LOSS_LOOSE) {
+        a.kp2d_err = out->kp2d_err; a.angle_err = out->angle_err; a.valid2d = out->valid2d; a.weak2d = out->weak2d;
+        a.valid_rot = out->valid_rot; a.weak_rot = out->weak_rot; a.conf2d_used = out->conf2d_used; a.conf3d_used = out->conf3d_used;
+        a.has_betas_used = out->has_betas_used;
+    }
+    a.partial = workspace;
+    a.w[0] = d->w_keypoints_2d; a.w[1] = d->w_keypoints_3d; a.w[2] = d->w_global_orient; a.w[3] = d->w_body_pose; a.w[4] = d->w_betas;
+    a.loose_weight = (float)d->loose_weight;
+    a.B = B; a.pelvis_id = d->pelvis_id; a.mode = d->mode; a.gt_pose_is_rotmat = d->gt_pose_is_rotmat;
+    LAUNCH_OK(launch_val_loss(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_token_ce(const float* x, const int32_t* target, int32_t rows, float* out, float* workspace, void* stream) {
+    thmr_engine* e = nullptr;
+    if (!x || !target || !out || !workspace) return fail(e, THMR_ERR_INVALID, "token_ce: null buffer");
+    if (rows < 1) return fail(e, THMR_ERR_INVALID, "token_ce: rows >= 1 is required");
+    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) return fail(e, THMR_ERR_INVALID, "token_ce: x must be 16-byte aligned");
+    LAUNCH_OK(launch_token_ce(x, target, rows, out, workspace, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 // ---- evaluation metrics (stateless) ----
 int thmr_eval_pose(const float* pred_j, const float* gt_j, int32_t nj, int32_t gt_stride, const int32_t* kp, int32_t nkp,
                    int32_t pelvis_ind, int32_t pelvis_mode, const float* pred_v, const float* gt_v, int32_t nv, int32_t B,

@@ -142,7 +142,9 @@ __global__ void rot6d_kernel(const float* __restrict__ x, float* __restrict__ Rm
 }
 
 // aa_to_rotmat (tokenhmr/lib/utils/geometry.py:5-44): axis-angle -> quaternion -> rotation matrix, operation by operation
-// (angle = ||theta + 1e-8||, axis = theta / angle, half-angle quaternion, re-normalised, nine quadratic forms)
+// (angle = ||theta + 1e-8||, axis = theta / angle, half-angle quaternion, re-normalised, nine quadratic forms).
+// TWIN: rotation_device.h's aa_to_rotmat_dev (the validation loss, loss.hip) restates this body line for line; change both together.
+// This kernel keeps its own copy because its bits are pinned by tests and calling the shared function changes how the compiler packs it.
 __global__ void aa_to_rotmat_kernel(const float* __restrict__ aa, float* __restrict__ Rm, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;

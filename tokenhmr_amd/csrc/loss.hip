@@ -1,0 +1,243 @@
+// The forward value of the reference's training / validation loss:
+//   TokenHMR.compute_loss      tokenhmr/lib/models/tokenhmr.py:190-277  (plain branch :250-262 = validation; LOOSE_SUP branch :214-249)
+//   its loss modules           tokenhmr/lib/models/losses.py:36-228 (Keypoint2DLoss / Keypoint3DLoss / ParameterLoss and the *PCKT forms)
+//   joint_angle_error          losses.py:22-33
+//   TokenLoss                  losses.py:230-252 (CrossEntropyLoss, mean, on whatever matrix it is handed)
+//
+// val_loss: two launches.  (1) one wave64 per item, four items per 256-thread workgroup: lanes 0..43 own a keypoint, lanes 0..23 a joint,
+// lanes 0..9 a beta; the lanes' terms are added by xor-shuffles in a fixed order and lane 0 writes the item's five sums to the workspace
+// (and the optional taps).  (2) one workgroup adds the B x 5 partial sums in fp64 (per thread over items t, t + 256, ... in index order,
+// then a fixed tree), applies the weights and updates the running sums.  No float atomics, no arrival counter, no LDS in (1); every
+// workspace word (2) reads was written by (1) of the same call, so nothing needs zeroing and a captured call replays like the eager one.
+//
+// The reference writes into the batch (:223, :227, :240); nothing is written into an input here — the written values are the optional
+// outputs conf2d_used / conf3d_used / has_betas_used.
+//
+// Loads: gt_keypoints_3d rows as float4, pred_keypoints_2d rows as float2 (the entry point refuses a base pointer that is not 16- / 8-byte
+// aligned); the 12-byte rows ((.,44,3) keypoints, axis-angle) and the 36-byte matrices are 4-byte aligned only and are read as 3- and 9-float
+// records the compiler may merge (global_load_dwordx3).  The kernel moves ~3.3 KB per item and is bound by the latency of its dependent
+// chain (loads -> cos / sin / atan2 -> shuffles), not by bandwidth.
+#include "common.h"
+#include "rotation_device.h"
+
+namespace {
+
+constexpr int kKp = 44, kJoints = 24, kBetas = 10, kTerms = 5;
+constexpr int kClasses = 2048;
+
+struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
+struct __attribute__((packed, aligned(4))) F9 { float m[9]; };
+
+__global__ __launch_bounds__(256) void val_loss_items_kernel(ValLossArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;              // whole waves leave: nothing below crosses waves
+    const bool loose = a.mode == 1;
+    const float lw = a.loose_weight;
+    const float v3 = loose ? a.valid_3d[b] : 0.f;
+
+    // ---- keypoints: lane k < 44 ----
+    float s2 = 0.f, w2 = 0.f, s3 = 0.f;
+    {
+        const int k = lane < kKp ? lane : 0;
+        const int64_t r = (int64_t)b * kKp + k;
+        const float2 p2 = reinterpret_cast<const float2*>(a.pred_kp2d)[r];
+        const F3 g2 = reinterpret_cast<const F3*>(a.gt_kp2d)[r];
+        const F3 p3 = reinterpret_cast<const F3*>(a.pred_kp3d)[r];
+        const float4 g3 = reinterpret_cast<const float4*>(a.gt_kp3d)[r];
+        const float dx = p2.x - g2.x, dy = p2.y - g2.y;
+        const float l1 = fabsf(dx) + fabsf(dy);
+        float conf2 = g2.z;                    // what the 2D loss multiplies with (Keypoint2DLoss, losses.py:61-63)
+        float conf3 = g3.w;
+        if (loose) {
+            const float err = conf2 * (dx * dx + dy * dy);                 // tokenhmr.py:218-219
+            const float valid = err > a.kp2d_thresh[k] ? 1.f : 0.f;        // :220
+            const float weak = conf2 * (1.f - valid);                      // :221
+            conf2 = conf2 * valid;                                         // :223
+            conf3 = conf3 * ((v3 + conf2) > 0.5f ? 1.f : 0.f);             // :227
+            if (lane < kKp) {
+                w2 = weak * l1;                                            // losses.py:130
+                if (a.kp2d_err) a.kp2d_err[r] = err;
+                if (a.valid2d) a.valid2d[r] = valid;
+                if (a.weak2d) a.weak2d[r] = weak;
+                if (a.conf2d_used) a.conf2d_used[r] = conf2;
+                if (a.conf3d_used) a.conf3d_used[r] = conf3;
+            }
+        }
+        // Keypoint3DLoss (losses.py:94-98): both sides relative to their own pelvis
+        const float ppx = __shfl(p3.x, a.pelvis_id, 64), ppy = __shfl(p3.y, a.pelvis_id, 64), ppz = __shfl(p3.z, a.pelvis_id, 64);
+        const float gpx = __shfl(g3.x, a.pelvis_id, 64), gpy = __shfl(g3.y, a.pelvis_id, 64), gpz = __shfl(g3.z, a.pelvis_id, 64);
+        if (lane < kKp) {
+            s2 = conf2 * l1;
+            s3 = conf3 * ((fabsf((p3.x - ppx) - (g3.x - gpx)) + fabsf((p3.y - ppy) - (g3.y - gpy))) + fabsf((p3.z - ppz) - (g3.z - gpz)));
+        }
+    }
+
+    // ---- joints: lane j < 24, joint 0 = global_orient ----
+    float srot = 0.f, wrot = 0.f;
+    {
+        const int j = lane < kJoints ? lane : 0;
+        const int64_t r = (int64_t)b * kJoints + j;
+        const F9 P = reinterpret_cast<const F9*>(a.pred_rotmat)[r];
+        float G[9];
+        if (a.gt_pose_is_rotmat) {
+            const F9 Gm = reinterpret_cast<const F9*>(a.gt_pose)[r];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) G[i] = Gm.m[i];
+        } else {
+            const F3 t = reinterpret_cast<const F3*>(a.gt_pose)[r];
+            aa_to_rotmat_dev(t.x, t.y, t.z, G);                            // tokenhmr.py:235,260
+        }
+        float sq = 0.f;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const float d = P.m[i] - G[i];
+            sq = fmaf(d, d, sq);
+        }
+        const float has = j == 0 ? a.has_global_orient[b] : a.has_body_pose[b];
+        float strong = has * sq, weakv = 0.f;                              // ParameterLoss (losses.py:187-192)
+        if (loose) {
+            // joint_angle_error (losses.py:22-33): |matrix_to_axis_angle(R_pred R_gt^T)|
+            float Rr[9];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    Rr[i * 3 + k] = fmaf(P.m[i * 3 + 2], G[k * 3 + 2], fmaf(P.m[i * 3 + 1], G[k * 3 + 1], P.m[i * 3 + 0] * G[k * 3 + 0]));
+            float ax, ay, az;
+            rotmat_to_aa_dev(Rr, ax, ay, az);
+            const float angle = sqrtf(ax * ax + ay * ay + az * az);
+            const float over = angle > a.angle_thresh[j] ? 1.f : 0.f;      // tokenhmr.py:244
+            const float valid = (over * has + v3) != 0.f ? 1.f : 0.f;      // :245, .bool()
+            const float weak = (1.f - valid) * has;                        // :246
+            strong = valid * sq;                                           // losses.py:214
+            weakv = weak * sq;                                             // :218
+            if (lane < kJoints) {
+                if (a.angle_err) a.angle_err[r] = angle;
+                if (a.valid_rot) a.valid_rot[r] = valid;
+                if (a.weak_rot) a.weak_rot[r] = weak;
+            }
+        }
+        if (lane < kJoints) { srot = strong; wrot = weakv; }
+    }
+
+    // ---- betas: lane i < 10 ----
+    float sb = 0.f;
+    float hb = a.has_betas[b];
+    if (loose) hb = hb * v3;                                               // tokenhmr.py:240
+    if (lane < kBetas) {
+        const float d = a.pred_betas[(int64_t)b * kBetas + lane] - a.gt_betas[(int64_t)b * kBetas + lane];
+        sb = hb * (d * d);
+    }
+
+    // ---- the item's five sums: xor-shuffle trees, one order for every call ----
+    const float go_s = __shfl(srot, 0, 64), go_w = __shfl(wrot, 0, 64);
+    if (lane == 0) { srot = 0.f; wrot = 0.f; }                             // lanes 1..23 are the body pose
+    const float t2 = wave_sum(s2), t2w = wave_sum(w2), t3 = wave_sum(s3), tb = wave_sum(srot), tbw = wave_sum(wrot), tbe = wave_sum(sb);
+    if (lane == 0) {
+        float out[kTerms];
+        out[0] = loose ? t2 + lw * t2w : t2;                               // losses.py:128-131
+        out[1] = t3;
+        out[2] = loose ? go_s + lw * go_w : go_s;                          // losses.py:214-220
+        out[3] = loose ? tb + lw * tbw : tb;
+        out[4] = tbe;
+#pragma unroll
+        for (int i = 0; i < kTerms; ++i) {
+            a.partial[(int64_t)b * kTerms + i] = out[i];
+            if (a.per_item) a.per_item[(int64_t)b * kTerms + i] = out[i];
+        }
+        if (loose && a.has_betas_used) a.has_betas_used[b] = hb;
+    }
+}
+
+// one workgroup: thread t adds items t, t + 256, ... in index order in fp64, then a fixed tree over the 256 threads
+__global__ __launch_bounds__(256) void val_loss_final_kernel(ValLossArgs a) {
+    __shared__ double sh[kTerms][256];
+    const int t = threadIdx.x;
+    double acc[kTerms] = {0, 0, 0, 0, 0};
+    for (int i = t; i < a.B; i += 256)
+#pragma unroll
+        for (int c = 0; c < kTerms; ++c) acc[c] += (double)a.partial[(int64_t)i * kTerms + c];
+#pragma unroll
+    for (int c = 0; c < kTerms; ++c) sh[c][t] = acc[c];
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (t < o)
+#pragma unroll
+            for (int c = 0; c < kTerms; ++c) sh[c][t] += sh[c][t + o];
+        __syncthreads();
+    }
+    if (t == 0) {
+        // tokenhmr.py:264-266: 3D, 2D, then the parameter terms in the dict's order
+        const double total = a.w[1] * sh[1][0] + a.w[0] * sh[0][0] + ((a.w[2] * sh[2][0] + a.w[3] * sh[3][0]) + a.w[4] * sh[4][0]);
+        const float l[6] = {(float)total, (float)sh[0][0], (float)sh[1][0], (float)sh[2][0], (float)sh[3][0], (float)sh[4][0]};
+        if (a.losses)
+            for (int i = 0; i < 6; ++i) a.losses[i] = l[i];
+        if (a.running) {          // what averaging validation_step_outputs adds up: the fp32 values of every batch
+            for (int i = 0; i < 6; ++i) a.running[i] += (double)l[i];
+            a.running[6] += 1.0;
+        }
+    }
+}
+
+// CrossEntropyLoss per row of 2048: one wave per row, the row read once as 8 float4 per lane (1 KiB per wave instruction) and kept in
+// registers; max, sum of exp(x - max), log — all in one order.  A target outside [0, 2048) is not read through: the row's loss is NaN.
+__global__ __launch_bounds__(256) void token_ce_rows_kernel(const float* __restrict__ x, const int32_t* __restrict__ target, int rows,
+                                                            float* __restrict__ row_loss) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float4* xr = reinterpret_cast<const float4*>(x + row * kClasses);
+    float4 v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = xr[i * 64 + lane];
+    float m = v[0].x;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) m = fmaxf(fmaxf(fmaxf(m, v[i].x), v[i].y), fmaxf(v[i].z, v[i].w));
+    m = wave_max(m);
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s += (expf(v[i].x - m) + expf(v[i].y - m)) + (expf(v[i].z - m) + expf(v[i].w - m));
+    s = wave_sum(s);
+    if (lane == 0) {
+        const int tg = target[row];
+        const bool ok = tg >= 0 && tg < kClasses;
+        const float xt = ok ? x[row * kClasses + tg] : 0.f;
+        row_loss[row] = ok ? (logf(s) + m) - xt : __builtin_nanf("");
+    }
+}
+
+__global__ __launch_bounds__(256) void token_ce_final_kernel(const float* __restrict__ row_loss, int rows, float* __restrict__ out) {
+    __shared__ double sh[256];
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    for (int i = t; i < rows; i += 256) acc += (double)row_loss[i];
+    sh[t] = acc;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    if (t == 0) out[0] = (float)(sh[0] / (double)rows);
+}
+
+}  // namespace
+
+int launch_val_loss(const ValLossArgs& a, hipStream_t s) {
+    if (a.B < 1 || !a.partial || a.pelvis_id < 0 || a.pelvis_id >= kKp || (a.mode != 0 && a.mode != 1)) return -1;
+    hipLaunchKernelGGL(val_loss_items_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a);
+    if (hipGetLastError() != hipSuccess) return -2;
+    if (a.losses || a.running) {
+        hipLaunchKernelGGL(val_loss_final_kernel, dim3(1), dim3(256), 0, s, a);
+        if (hipGetLastError() != hipSuccess) return -2;
+    }
+    return 0;
+}
+
+int launch_token_ce(const float* x, const int32_t* target, int rows, float* out, float* row_loss, hipStream_t s) {
+    if (!x || !target || !out || !row_loss || rows < 1) return -1;
+    hipLaunchKernelGGL(token_ce_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, target, rows, row_loss);
+    if (hipGetLastError() != hipSuccess) return -2;
+    hipLaunchKernelGGL(token_ce_final_kernel, dim3(1), dim3(256), 0, s, row_loss, rows, out);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}

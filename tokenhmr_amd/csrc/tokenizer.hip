@@ -17,6 +17,7 @@
 //   rotmat_to_aa    matrix_to_axis_angle (rotation_utils.py:428-441 = quaternion_to_axis_angle(matrix_to_quaternion)): the reference's route
 //                   step for step (see the kernel), no quaternion standardisation — an angle above pi stays above pi.
 #include "common.h"
+#include "rotation_device.h"
 
 namespace {
 
@@ -144,44 +145,16 @@ __global__ __launch_bounds__(256) void vq_stats_final_kernel(const float* __rest
     }
 }
 
-// matrix_to_quaternion (rotation_utils.py:104-163) + quaternion_to_axis_angle (:478-506), one lane per matrix.  Every value the reference
-// computes for the winning candidate is computed here by the same fp32 operations in the same order; contraction into FMAs is off.
+// matrix_to_quaternion (rotation_utils.py:104-163) + quaternion_to_axis_angle (:478-506), one lane per matrix: the body is
+// rotmat_to_aa_dev (rotation_device.h)
 __global__ __launch_bounds__(256) void rotmat_to_aa_kernel(const float* __restrict__ Rm, float* __restrict__ aa, int n) {
-#pragma clang fp contract(off)
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float* m = Rm + (int64_t)i * 9;
-    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5], m20 = m[6], m21 = m[7], m22 = m[8];
-    // _sqrt_positive_part of the four squared magnitudes (:122-132)
-    const float s[4] = {1.0f + m00 + m11 + m22, 1.0f + m00 - m11 - m22, 1.0f - m00 + m11 - m22, 1.0f - m00 - m11 + m22};
-    float qa[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) qa[k] = s[k] > 0.f ? sqrtf(s[k]) : 0.f;
-    // q_abs.argmax(dim=-1), lowest index on ties (:161-163)
-    int w = 0;
-    float best = qa[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-        if (qa[k] > best) { best = qa[k]; w = k; }
-    // the winning row of quat_by_rijk (:135-151) over 2 max(q_abs, 0.1) (:155-156; safe_zero_division's clamp at the smallest normal
-    // number never bites a denominator >= 0.2)
-    float q0, q1, q2, q3;
-    const float sq = best * best;
-    if (w == 0)      { q0 = sq;        q1 = m21 - m12; q2 = m02 - m20; q3 = m10 - m01; }
-    else if (w == 1) { q0 = m21 - m12; q1 = sq;        q2 = m10 + m01; q3 = m02 + m20; }
-    else if (w == 2) { q0 = m02 - m20; q1 = m10 + m01; q2 = sq;        q3 = m12 + m21; }
-    else             { q0 = m10 - m01; q1 = m20 + m02; q2 = m21 + m12; q3 = sq; }
-    const float den = 2.0f * fmaxf(best, 0.1f);
-    q0 = q0 / den; q1 = q1 / den; q2 = q2 / den; q3 = q3 / den;
-    // quaternion_to_axis_angle (:492-506)
-    const float norm = sqrtf(q1 * q1 + q2 * q2 + q3 * q3);
-    const float half = atan2f(norm, q0);
-    const float angle = 2.0f * half;
-    const float so = fabsf(angle) < 1e-6f ? 0.5f - (angle * angle) / 48.0f : sinf(half) / angle;
-    const float d = fmaxf(so, 1.17549435e-38f);        // safe_zero_division: clamp(min = finfo(float32).tiny)
-    aa[(int64_t)i * 3 + 0] = q1 / d;
-    aa[(int64_t)i * 3 + 1] = q2 / d;
-    aa[(int64_t)i * 3 + 2] = q3 / d;
+    float ax, ay, az;
+    rotmat_to_aa_dev(Rm + (int64_t)i * 9, ax, ay, az);
+    aa[(int64_t)i * 3 + 0] = ax;
+    aa[(int64_t)i * 3 + 1] = ay;
+    aa[(int64_t)i * 3 + 2] = az;
 }
 
 }  // namespace

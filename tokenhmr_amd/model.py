@@ -34,6 +34,7 @@ class TokenHMR:
         self.smpl = _SmplHandle(torch.zeros(13776, 3, dtype=torch.int64))
         self.training = False
         self.return_taps = False
+        self.validation_loss = None      # built by compute_loss on first use
 
     # ---- construction -------------------------------------------------------------------
     @classmethod
@@ -56,7 +57,7 @@ class TokenHMR:
         m.cfg = model_cfg if model_cfg is not None else types.SimpleNamespace(**engine.cfg.to_dict())
         m.max_batch, m.device, m.engine = engine.max_batch, engine.device, engine
         m.smpl = _SmplHandle(faces if faces is not None else torch.zeros(13776, 3, dtype=torch.int64))
-        m.training, m.return_taps = False, False
+        m.training, m.return_taps, m.validation_loss = False, False, None
         return m
 
     # ---- nn.Module-like surface used by eval.py:52-54 / demo.py:35-37 ------------------------
@@ -99,6 +100,24 @@ class TokenHMR:
         if train:
             raise NotImplementedError("inference only")
         return self.forward(batch)
+
+    def compute_loss(self, batch, output, train=False):
+        """tokenhmr.py:190-277, the forward value only (tokenhmr_amd/losses.py): sets output['losses'], returns the total as a 0-dim
+        device tensor.  The ValidationLoss is built from self.cfg on first use; replace `model.validation_loss` to pass thresholds."""
+        if self.validation_loss is None:
+            from .losses import ValidationLoss
+            try:
+                self.validation_loss = ValidationLoss(self.cfg)
+            except KeyError as e:
+                raise KeyError(f"compute_loss reads LOSS_WEIGHTS and MODEL from the reference's model config, and {e.args[0]}: pass "
+                               "`model_cfg` when the model is built (load_tokenhmr does), or set model.validation_loss") from None
+        return self.validation_loss(batch, output, train=train)
+
+    def validation_step(self, batch, batch_idx=0, dataloader_idx=0):
+        """tokenhmr.py:421-440 without the logging: forward + compute_loss, output['loss'] = the total."""
+        output = self.forward_step(batch, train=False)
+        output["loss"] = self.compute_loss(batch, output, train=False)
+        return output
 
     def _pack(self, o):
         R = o["rotmat"]

@@ -452,3 +452,80 @@ def rotmat_to_aa(R):
     with torch.cuda.device(R.device):
         _check(_L().thmr_op_rotmat_to_aa(_p(m), _p(aa), n, _s(R)))
     return aa
+
+
+# ---- the forward value of the loss (csrc/loss.hip) ----
+VAL_LOSS_TAPS = ("kp2d_err", "angle_err", "valid2d", "weak2d", "valid_rot", "weak_rot", "conf2d_used", "conf3d_used", "has_betas_used")
+
+
+def val_loss(pred_kp2d, pred_kp3d, pred_rotmat, pred_betas, gt_kp2d, gt_kp3d, gt_pose, gt_betas, has_global_orient, has_body_pose,
+             has_betas, weights, loose=False, loose_weight=0.0, valid_3d=None, kp2d_thresh=None, angle_thresh=None, pelvis_id=39,
+             taps=True, running=None, workspace=None, losses=None):
+    """thmr_val_loss: compute_loss (tokenhmr.py:190-277) for B items.  pred_kp2d (B,44,2), pred_kp3d (B,44,3), pred_rotmat (B,24,3,3),
+    pred_betas (B,10), gt_kp2d (B,44,3), gt_kp3d (B,44,4), gt_pose (B,72) axis-angle or (B,24,3,3) matrices, gt_betas (B,10), has_* (B);
+    weights: the five LOSS_WEIGHTS in the order 2D, 3D, global_orient, body_pose, betas.  loose: valid_3d (B), kp2d_thresh (44),
+    angle_thresh (24).  Returns a dict of device tensors: 'losses' (6, the reference's dict order), 'per_item' (B,5) and — loose with
+    taps — VAL_LOSS_TAPS.  running: a (7) float64 device tensor that the call adds its six losses and a count of 1 to.  No host
+    synchronisation; nothing is written into an input."""
+    ins = [pred_kp2d, pred_kp3d, pred_rotmat, pred_betas, gt_kp2d, gt_kp3d, gt_pose, gt_betas, has_global_orient, has_body_pose, has_betas]
+    _req(*ins, valid_3d, kp2d_thresh, angle_thresh, workspace, losses)
+    B = pred_kp2d.shape[0]
+    if gt_pose.shape == (B, 72):
+        is_rotmat = 0
+    elif gt_pose.shape == (B, 24, 3, 3):
+        is_rotmat = 1
+    else:
+        raise ValueError(f"val_loss: gt_pose is (B,72) axis-angle or (B,24,3,3) matrices, got {tuple(gt_pose.shape)}")
+    want = [(B, 44, 2), (B, 44, 3), (B, 24, 3, 3), (B, 10), (B, 44, 3), (B, 44, 4), tuple(gt_pose.shape), (B, 10), (B,), (B,), (B,)]
+    for t, w in zip(ins, want):
+        if tuple(t.shape) != w:
+            raise ValueError(f"val_loss: a tensor of shape {tuple(t.shape)} where {w} is expected")
+    if loose:
+        if valid_3d is None or kp2d_thresh is None or angle_thresh is None:
+            raise ValueError("val_loss: the loose mode needs valid_3d, kp2d_thresh and angle_thresh")
+        if tuple(valid_3d.shape) != (B,) or tuple(kp2d_thresh.shape) != (44,) or tuple(angle_thresh.shape) != (24,):
+            raise ValueError("val_loss: valid_3d (B), kp2d_thresh (44), angle_thresh (24)")
+    if running is not None and not (running.is_cuda and running.dtype == torch.float64 and running.shape == (7,) and running.is_contiguous()):
+        raise ValueError("val_loss: running is a contiguous (7) float64 CUDA tensor")
+    if len(weights) != 5:
+        raise ValueError("val_loss: five weights (2D, 3D, global_orient, body_pose, betas)")
+    dev = pred_kp2d.device
+    new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)      # noqa: E731
+    res = {"losses": losses if losses is not None else new(6), "per_item": new(B, 5)}
+    if res["losses"].shape != (6,):
+        raise ValueError("val_loss: losses is a (6) tensor")
+    if loose and taps:
+        res.update({k: new(B) if k == "has_betas_used" else new(B, 44 if "2d" in k or "3d" in k else 24) for k in VAL_LOSS_TAPS})
+    need = _cabi.VAL_LOSS_WS_PER_ITEM * B
+    if workspace is None:
+        workspace = new(need)
+    elif workspace.numel() < need:
+        raise ValueError(f"val_loss: the workspace holds {workspace.numel()} floats, {need} are needed")
+    w = [float(x) for x in weights]
+    desc = _cabi.ValLossDesc(*w, float(loose_weight), int(pelvis_id), _cabi.VAL_LOSS_LOOSE if loose else _cabi.VAL_LOSS_PLAIN, is_rotmat, 0)
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    cin = _cabi.ValLossIn(*[ptr(t) for t in ins], ptr(valid_3d), ptr(kp2d_thresh), ptr(angle_thresh))
+    cout = _cabi.ValLossOut(**{k: ptr(res.get(k)) for k in _cabi.VAL_LOSS_OUT_FIELDS if k != "running"}, running=ptr(running))
+    with torch.cuda.device(dev):
+        _check(_L().thmr_val_loss(C.byref(desc), C.byref(cin), B, C.byref(cout), _p(workspace), _s(pred_kp2d)))
+    return res
+
+
+def token_ce(x, target, out=None, workspace=None):
+    """thmr_op_token_ce: TokenLoss (losses.py:230-252), CrossEntropyLoss in mean reduction over the rows of x (rows, 2048) fp32 with int32
+    targets (rows) -> a 0-dim device float (or `out`).  The per-row losses are left in `workspace` (rows floats).  A target outside
+    [0, 2048) makes its row, and the mean, NaN."""
+    _req(x, out, workspace)
+    _req_i32(target)
+    rows = x.shape[0]
+    if x.shape != (rows, 2048) or target.shape != (rows,):
+        raise ValueError(f"token_ce needs x (rows, 2048) and target (rows), got {tuple(x.shape)} and {tuple(target.shape)}")
+    out = out if out is not None else torch.empty((), device=x.device, dtype=torch.float32)
+    need = _cabi.TOKEN_CE_WS_PER_ROW * rows
+    if workspace is None:
+        workspace = torch.empty(need, device=x.device, dtype=torch.float32)
+    elif workspace.numel() < need:
+        raise ValueError(f"token_ce: the workspace holds {workspace.numel()} floats, {need} are needed")
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_token_ce(_p(x), _p(target), rows, _p(out), _p(workspace), _s(x)))
+    return out
