@@ -611,6 +611,29 @@ int  thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int3
                       const thmr_crop_desc* crops_host, int32_t n, int32_t patch, int32_t swap_rb, const float* mean_host,
                       const float* std_host, float* out_dev, void* stream);
 
+/* A batch of crops from a TABLE of frames (the eval.py shape: n items, n decoded frames of n sizes, one crop each), in one call:
+ * one descriptor copy and at most three launches (rows pass, columns pass, warp); each workgroup takes frame pointer, geometry and
+ * window origin from its item's descriptor.  The arithmetic is thmr_cropper_run's: item i is bit-equal to thmr_cropper_run on that
+ * item's full frame alone.
+ * An item need not bring its whole frame, only a WINDOW of it that covers what the crop can touch:
+ *   un-blurred  the fixed-point source coordinates of the four patch corners (the value thmr_cropper_run's warp computes, >> 10),
+ *               [lo - 1, hi + 2] on each axis, clipped to the frame;
+ *   blurred     that box widened by the kernel radius lw = int(truncate * sigma + 0.5) on all four sides, clipped to the frame;
+ *   an empty box means every output pixel is border: nothing of that item's window is read and win_dev may be null.
+ * tokenhmr_amd.preprocess.source_window restates the rule.  Refused with THMR_ERR_INVALID and the item's index in
+ * thmr_cropper_last_error, before any HIP call: a window that does not lie inside the frame or does not cover the box, a null
+ * pointer where the box is not empty, row_stride < win_w * 3, a frame side above 32767 (the warp's 16-bit texel coordinates), and
+ * what thmr_cropper_run refuses.  The arguments are checked before the handle, so the refusals need no device. */
+typedef struct thmr_frame_crop {
+    const uint8_t* win_dev;     /* device pointer to a WINDOW of this item's decoded frame, (win_h, win_w, 3) uint8 */
+    int64_t  row_stride;        /* bytes per window row, >= win_w * 3 */
+    int32_t  H, W;              /* size of the FULL frame: the zero-border and edge-replication rules use these */
+    int32_t  win_x0, win_y0, win_w, win_h;   /* where the window sits in the frame; (0,0,W,H) = the whole frame */
+    double   M[6], sigma, truncate;          /* as thmr_crop_desc */
+} thmr_frame_crop;
+int  thmr_cropper_run_frames(thmr_cropper* c, const thmr_frame_crop* items_host, int32_t n, int32_t patch, int32_t swap_rb,
+                             const float* mean_host, const float* std_host, float* out_dev /* (n,3,patch,patch) */, void* stream);
+
 /* Mesh renderer: the reference's pyrender scenes (tokenhmr/lib/utils/renderer.py) rasterised on the device
  * (csrc/render.hip).  The kernels know no presets: the host scene builder (tokenhmr_amd/render.py) fills the descriptor.
  *   camera frame   x right, y down, z forward (the frame of perspective_projection); per mesh m

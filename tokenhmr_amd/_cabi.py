@@ -81,6 +81,13 @@ class CropDesc(C.Structure):
     _fields_ = [("M", C.c_double * 6), ("sigma", C.c_double), ("truncate", C.c_double)]
 
 
+class FrameCrop(C.Structure):
+    """thmr_frame_crop: one item of thmr_cropper_run_frames."""
+    _fields_ = [("win_dev", C.c_void_p), ("row_stride", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("win_x0", C.c_int32),
+                ("win_y0", C.c_int32), ("win_w", C.c_int32), ("win_h", C.c_int32), ("M", C.c_double * 6), ("sigma", C.c_double),
+                ("truncate", C.c_double)]
+
+
 RENDER_MAX_LIGHTS = 16
 # thmr_render_desc.mode / thmr_render_light.type (header: THMR_RENDER_* / THMR_LIGHT_*)
 RENDER_PER_IMAGE, RENDER_ONE_IMAGE = 0, 1
@@ -160,6 +167,9 @@ SMPLH_SYMBOLS = ("thmr_smplh_create", "thmr_smplh_destroy", "thmr_smplh_forward"
 # the forward value of the loss (csrc/loss.hip): new symbols under ABI 5 as well
 LOSS_SYMBOLS = ("thmr_val_loss", "thmr_op_token_ce")
 
+# a batch of crops from a table of frames (csrc/crop.hip): a new symbol under ABI 5 as well
+FRAMES_SYMBOLS = ("thmr_cropper_run_frames",)
+
 
 def load(exp=None):
     """The shipped library, or (exp=True, or exp=None with THMR_LIB=exp in the environment) the experiments build.
@@ -195,7 +205,7 @@ def load(exp=None):
     older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
     # a build loaded by path may also predate thmr_renderer_sheet / thmr_debug_vit_plan (added without an ABI change: new symbols, no layout touched)
     missing = [s for s in declared_symbols() if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
-               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS)]
+               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS + FRAMES_SYMBOLS)]
     if missing:
         raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -276,6 +286,8 @@ def load(exp=None):
     lib.thmr_cropper_last_error.argtypes = [vp]
     lib.thmr_cropper_last_error.restype = C.c_char_p
     lib.thmr_cropper_run.argtypes = [vp, vp, i32, i32, i64, C.POINTER(CropDesc), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
+    if hasattr(lib, "thmr_cropper_run_frames"):          # the frame-table entry (added without an ABI change)
+        lib.thmr_cropper_run_frames.argtypes = [vp, C.POINTER(FrameCrop), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
     lib.thmr_renderer_create.argtypes = [i32, vp, i32, i32, C.POINTER(vp)]
     lib.thmr_renderer_destroy.argtypes = [vp]
     lib.thmr_renderer_destroy.restype = None

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -43,32 +44,40 @@ struct CropDev {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// One frame per descriptor (thmr_cropper_run_frames): the crop's own descriptor plus where its texels live.  `win` points at texel
+// (wx0, wy0) of the frame; the host has checked that the window lies inside the frame and covers every texel the crop can touch.
+struct FrameDev {
+    CropDev c;
+    const uint8_t* win;
+    int64_t stride;
+    int32_t H, W;                 // the FULL frame: border and edge-replication rules
+    int32_t wx0, wy0, ww, wh;     // the window; ww = 0 when the crop touches no texel (nothing is read then)
+};
+
+// The three bodies below serve both entries: `base` points at texel (ox, oy) of the frame, so the one-frame entry passes the frame
+// and (0, 0) and the frame-table entry its window and the window's origin.  Integer and contraction-free fp64 arithmetic only, so
+// both instantiations give the same bits.
+
 // rows pass: tmp[y][x][c] over the region rows and the widened column range
-__global__ __launch_bounds__(256) void crop_vpass_kernel(const uint8_t* __restrict__ frame, int H, int W, int64_t stride,
-                                                         const CropDev* __restrict__ cds, const double* __restrict__ wts,
-                                                         double* __restrict__ scratch) {
-    const CropDev c = cds[blockIdx.y];
-    if (!c.blur) return;
+__device__ __forceinline__ void vpass_body(const CropDev& c, const uint8_t* __restrict__ base, int H, int64_t stride, int ox, int oy,
+                                           const double* __restrict__ wts, double* __restrict__ scratch) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)c.rh * c.tw * 3) return;
     const int ch = (int)(idx % 3), x = (int)((idx / 3) % c.tw), y = (int)(idx / (3 * (int64_t)c.tw));
     const int gx = c.tx0 + x, gy = c.ry0 + y;
     const double* fw = wts + c.w_off + c.lw;
-    const uint8_t* col = frame + (int64_t)gx * 3 + ch;
-    double t = (double)col[(int64_t)gy * stride] * fw[0];
+    const uint8_t* col = base + (int64_t)(gx - ox) * 3 + ch;
+    double t = (double)col[(int64_t)(gy - oy) * stride] * fw[0];
     for (int jj = -c.lw; jj < 0; ++jj) {
-        const double a = (double)col[(int64_t)clampi(gy + jj, 0, H - 1) * stride];
-        const double b = (double)col[(int64_t)clampi(gy - jj, 0, H - 1) * stride];
+        const double a = (double)col[(int64_t)(clampi(gy + jj, 0, H - 1) - oy) * stride];
+        const double b = (double)col[(int64_t)(clampi(gy - jj, 0, H - 1) - oy) * stride];
         t = t + (a + b) * fw[jj];
     }
     scratch[c.tmp_off + idx] = t;
 }
 
 // columns pass: blur[y][x][c] over the region
-__global__ __launch_bounds__(256) void crop_hpass_kernel(int W, const CropDev* __restrict__ cds, const double* __restrict__ wts,
-                                                         double* __restrict__ scratch) {
-    const CropDev c = cds[blockIdx.y];
-    if (!c.blur) return;
+__device__ __forceinline__ void hpass_body(const CropDev& c, int W, const double* __restrict__ wts, double* __restrict__ scratch) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)c.rh * c.rw * 3) return;
     const int ch = (int)(idx % 3), x = (int)((idx / 3) % c.rw), y = (int)(idx / (3 * (int64_t)c.rw));
@@ -84,11 +93,12 @@ __global__ __launch_bounds__(256) void crop_hpass_kernel(int W, const CropDev* _
     scratch[c.blur_off + idx] = t;
 }
 
-__global__ __launch_bounds__(256) void crop_warp_kernel(const uint8_t* __restrict__ frame, int H, int W, int64_t stride,
-                                                        const CropDev* __restrict__ cds, const double* __restrict__ scratch,
-                                                        int P, int swap_rb, float m0, float m1, float m2, float s0, float s1,
-                                                        float s2, float* __restrict__ out) {
-    const CropDev c = cds[blockIdx.y];
+// warp + normalise one output pixel.  A texel is read when it lies in the rectangle [vx0, vx1) x [vy0, vy1): the whole frame for
+// the one-frame entry; for the frame table the item's window (un-blurred) or its blurred region, which hold every in-frame texel
+// the crop samples, so the test selects the same texels and no address outside the rectangle is ever formed into a load.
+__device__ __forceinline__ void warp_body(const CropDev& c, const uint8_t* __restrict__ base, int64_t stride, int ox, int oy, int vx0,
+                                          int vy0, int vx1, int vy1, const double* __restrict__ scratch, int P, int swap_rb,
+                                          const float (&mean)[3], const float (&sd)[3], float* __restrict__ out) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= P * P) return;
     const int x = idx % P, y = idx / P;
@@ -102,12 +112,12 @@ __global__ __launch_bounds__(256) void crop_warp_kernel(const uint8_t* __restric
     sxl = sxl < -32768 ? -32768 : (sxl > 32767 ? 32767 : sxl);      // saturate_cast<short>
     syl = syl < -32768 ? -32768 : (syl > 32767 ? 32767 : syl);
     const int sx = (int)sxl, sy = (int)syl, fx = (int)(X & 31), fy = (int)(Y & 31);
-    const bool in00 = sx >= 0 && sx < W && sy >= 0 && sy < H, in01 = sx + 1 >= 0 && sx + 1 < W && sy >= 0 && sy < H;
-    const bool in10 = sx >= 0 && sx < W && sy + 1 >= 0 && sy + 1 < H, in11 = sx + 1 >= 0 && sx + 1 < W && sy + 1 >= 0 && sy + 1 < H;
+    const bool in00 = sx >= vx0 && sx < vx1 && sy >= vy0 && sy < vy1, in01 = sx + 1 >= vx0 && sx + 1 < vx1 && sy >= vy0 && sy < vy1;
+    const bool in10 = sx >= vx0 && sx < vx1 && sy + 1 >= vy0 && sy + 1 < vy1, in11 = sx + 1 >= vx0 && sx + 1 < vx1 && sy + 1 >= vy0 && sy + 1 < vy1;
     float v[3];
     if (!c.blur) {
         const int w00 = 32 * (32 - fy) * (32 - fx), w01 = 32 * (32 - fy) * fx, w10 = 32 * fy * (32 - fx), w11 = 32 * fy * fx;
-        const uint8_t* p = frame + (int64_t)sy * stride + (int64_t)sx * 3;
+        const uint8_t* p = base + (int64_t)(sy - oy) * stride + (int64_t)(sx - ox) * 3;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const int a = in00 ? p[ch] : 0, b = in01 ? p[3 + ch] : 0, d = in10 ? p[stride + ch] : 0, e = in11 ? p[stride + 3 + ch] : 0;
@@ -127,12 +137,61 @@ __global__ __launch_bounds__(256) void crop_warp_kernel(const uint8_t* __restric
         }
     }
     float* o = out + (int64_t)blockIdx.y * 3 * P * P + idx;
-    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};      // indexed by OUTPUT channel
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
         const int oc = swap_rb ? 2 - ch : ch;
         o[(int64_t)oc * P * P] = (v[ch] - mean[oc]) / sd[oc];
     }
+}
+
+__global__ __launch_bounds__(256) void crop_vpass_kernel(const uint8_t* __restrict__ frame, int H, int W, int64_t stride,
+                                                         const CropDev* __restrict__ cds, const double* __restrict__ wts,
+                                                         double* __restrict__ scratch) {
+    const CropDev c = cds[blockIdx.y];
+    if (!c.blur) return;
+    vpass_body(c, frame, H, stride, 0, 0, wts, scratch);
+}
+
+__global__ __launch_bounds__(256) void crop_hpass_kernel(int W, const CropDev* __restrict__ cds, const double* __restrict__ wts,
+                                                         double* __restrict__ scratch) {
+    const CropDev c = cds[blockIdx.y];
+    if (!c.blur) return;
+    hpass_body(c, W, wts, scratch);
+}
+
+__global__ __launch_bounds__(256) void crop_warp_kernel(const uint8_t* __restrict__ frame, int H, int W, int64_t stride,
+                                                        const CropDev* __restrict__ cds, const double* __restrict__ scratch,
+                                                        int P, int swap_rb, float m0, float m1, float m2, float s0, float s1,
+                                                        float s2, float* __restrict__ out) {
+    const CropDev c = cds[blockIdx.y];
+    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};      // indexed by OUTPUT channel
+    warp_body(c, frame, stride, 0, 0, 0, 0, W, H, scratch, P, swap_rb, mean, sd, out);
+}
+
+// The frame-table kernels: workgroup (x, item) takes frame pointer, geometry and window origin from its item's descriptor.
+__global__ __launch_bounds__(256) void crop_frames_vpass_kernel(const FrameDev* __restrict__ fds, const double* __restrict__ wts,
+                                                                double* __restrict__ scratch) {
+    const FrameDev f = fds[blockIdx.y];
+    if (!f.c.blur) return;
+    vpass_body(f.c, f.win, f.H, f.stride, f.wx0, f.wy0, wts, scratch);
+}
+
+__global__ __launch_bounds__(256) void crop_frames_hpass_kernel(const FrameDev* __restrict__ fds, const double* __restrict__ wts,
+                                                                double* __restrict__ scratch) {
+    const FrameDev f = fds[blockIdx.y];
+    if (!f.c.blur) return;
+    hpass_body(f.c, f.W, wts, scratch);
+}
+
+__global__ __launch_bounds__(256) void crop_frames_warp_kernel(const FrameDev* __restrict__ fds, const double* __restrict__ scratch, int P,
+                                                               int swap_rb, float m0, float m1, float m2, float s0, float s1, float s2,
+                                                               float* __restrict__ out) {
+    const FrameDev f = fds[blockIdx.y];
+    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};      // indexed by OUTPUT channel
+    if (f.c.blur)
+        warp_body(f.c, f.win, f.stride, f.wx0, f.wy0, f.c.rx0, f.c.ry0, f.c.rx0 + f.c.rw, f.c.ry0 + f.c.rh, scratch, P, swap_rb, mean, sd, out);
+    else
+        warp_body(f.c, f.win, f.stride, f.wx0, f.wy0, f.wx0, f.wy0, f.wx0 + f.ww, f.wy0 + f.wh, scratch, P, swap_rb, mean, sd, out);
 }
 
 thread_local std::string g_crop_err;
@@ -156,6 +215,76 @@ double np_sum(const std::vector<double>& a) {
     return res;
 }
 
+// what a crop can touch in its frame: [x0, x1] x [y0, y1] inclusive, empty when x0 > x1 or y0 > y1.  For a blurred crop the blur
+// reads this box widened by the kernel radius on all four sides, clipped to the frame: [bx0, bx1] x [by0, by1].
+struct TouchBox {
+    long long x0 = 0, x1 = -1, y0 = 0, y1 = -1, bx0 = 0, bx1 = -1, by0 = 0, by1 = -1;
+    bool empty() const { return x0 > x1 || y0 > y1; }
+};
+struct CropPlan {
+    size_t need = 0;              // scratch doubles
+    int64_t max_v = 0, max_h = 0;
+};
+
+// One crop's device descriptor from its forward affine: the inverse as cv::warpAffine computes it, the box of texels the warp can
+// touch and, for a blurred crop, the region, weights and scratch offsets.  `blur_only_box`: skip the box of an un-blurred crop
+// (the one-frame entry needs it only to size a blur).  Returns false with the refusal in `err`.
+bool prep_crop(const double* Mfwd, double sigma, double truncate, int i, int patch, int H, int W, bool blur_only_box, CropDev& d,
+               std::vector<double>& wts, CropPlan& plan, TouchBox& box, std::string& err) {
+    double M[6];
+    for (int k = 0; k < 6; ++k) M[k] = Mfwd[k];
+    // cv::warpAffine: invert the forward 2x3 matrix in double
+    double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0 ? 1. / D : 0;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+    const double b1 = -M[0] * M[2] - M[1] * M[5], b2 = -M[3] * M[2] - M[4] * M[5];
+    M[2] = b1; M[5] = b2;
+    for (int k = 0; k < 6; ++k) {
+        if (!std::isfinite(M[k])) { err = "crop " + std::to_string(i) + ": singular or non-finite affine"; return false; }
+        d.Mi[k] = M[k];
+    }
+    d.blur = 0; d.lw = 0; d.rx0 = d.ry0 = d.rw = d.rh = d.tx0 = d.tw = 0; d.w_off = 0; d.pad = 0; d.tmp_off = d.blur_off = 0;
+    if (!(sigma >= 0) || !std::isfinite(sigma) || !(truncate > 0)) { err = "crop " + std::to_string(i) + ": bad sigma / truncate"; return false; }
+    const bool blur = sigma > 1e-15;          // scipy.ndimage.gaussian_filter skips axes with sigma <= 1e-15
+    if (!blur && blur_only_box) return true;
+    // bounding box of the texels the warp can touch: the map is affine, so the extremes are at the patch corners
+    long long lo_x = INT64_MAX, hi_x = INT64_MIN, lo_y = INT64_MAX, hi_y = INT64_MIN;
+    for (int cy = 0; cy < 2; ++cy)
+        for (int cx = 0; cx < 2; ++cx) {
+            const double x = cx ? patch - 1 : 0, y = cy ? patch - 1 : 0;
+            const long long X = ((long long)std::llrint((M[1] * y + M[2]) * 1024.0) + 16 + (long long)std::llrint(M[0] * x * 1024.0)) >> 10;
+            const long long Y = ((long long)std::llrint((M[4] * y + M[5]) * 1024.0) + 16 + (long long)std::llrint(M[3] * x * 1024.0)) >> 10;
+            lo_x = std::min(lo_x, X); hi_x = std::max(hi_x, X); lo_y = std::min(lo_y, Y); hi_y = std::max(hi_y, Y);
+        }
+    // +-1: the per-pixel sum of two separately rounded terms can differ by one fixed-point step from the corner value
+    const long long x0 = std::max<long long>(lo_x - 1, 0), x1 = std::min<long long>(hi_x + 2, W - 1);
+    const long long y0 = std::max<long long>(lo_y - 1, 0), y1 = std::min<long long>(hi_y + 2, H - 1);
+    box.x0 = box.bx0 = x0; box.x1 = box.bx1 = x1; box.y0 = box.by0 = y0; box.y1 = box.by1 = y1;
+    if (blur && x0 <= x1 && y0 <= y1) {
+        d.blur = 1;
+        d.lw = (int)(truncate * sigma + 0.5);            // scipy: int(truncate * sd + 0.5)
+        if (d.lw > 4096) { err = "crop " + std::to_string(i) + ": blur radius too large"; return false; }
+        d.rx0 = (int)x0; d.ry0 = (int)y0; d.rw = (int)(x1 - x0 + 1); d.rh = (int)(y1 - y0 + 1);
+        d.tx0 = (int)std::max<long long>(x0 - d.lw, 0);
+        d.tw = (int)(std::min<long long>(x1 + d.lw, W - 1) - d.tx0 + 1);
+        box.bx0 = d.tx0; box.bx1 = d.tx0 + d.tw - 1;
+        box.by0 = std::max<long long>(y0 - d.lw, 0); box.by1 = std::min<long long>(y1 + d.lw, H - 1);
+        // scipy _gaussian_kernel1d: exp(-0.5 / sigma^2 * x^2), normalised by the numpy sum
+        std::vector<double> phi(2 * d.lw + 1);
+        const double s2 = sigma * sigma;
+        for (int k = -d.lw; k <= d.lw; ++k) phi[k + d.lw] = std::exp(-0.5 / s2 * (double)(k * k));
+        const double tot = np_sum(phi);
+        d.w_off = (int)wts.size();
+        for (double p : phi) wts.push_back(p / tot);
+        d.tmp_off = (int64_t)plan.need; plan.need += (size_t)d.rh * d.tw * 3;
+        d.blur_off = (int64_t)plan.need; plan.need += (size_t)d.rh * d.rw * 3;
+        plan.max_v = std::max<int64_t>(plan.max_v, (int64_t)d.rh * d.tw * 3);
+        plan.max_h = std::max<int64_t>(plan.max_h, (int64_t)d.rh * d.rw * 3);
+    }
+    return true;
+}
+
 }  // namespace
 
 struct thmr_cropper {
@@ -165,6 +294,8 @@ struct thmr_cropper {
     CropDev* cds = nullptr;
     double* wts = nullptr;
     size_t cds_cap = 0, wts_cap = 0;
+    char* fds = nullptr;          // thmr_cropper_run_frames: n frame descriptors, then the blur weights, in one buffer
+    size_t fds_cap = 0;
     std::string err;
 };
 
@@ -192,6 +323,7 @@ void thmr_cropper_destroy(thmr_cropper* c) {
     if (c->scratch) (void)hipFree(c->scratch);
     if (c->cds) (void)hipFree(c->cds);
     if (c->wts) (void)hipFree(c->wts);
+    if (c->fds) (void)hipFree(c->fds);
     delete c;
 }
 
@@ -207,60 +339,14 @@ int thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int32
 
     std::vector<CropDev> cds(n);
     std::vector<double> wts;
-    size_t need = 0;
-    int64_t max_v = 0, max_h = 0;
+    CropPlan plan;
     for (int i = 0; i < n; ++i) {
-        CropDev& d = cds[i];
-        double M[6];
-        for (int k = 0; k < 6; ++k) M[k] = crops[i].M[k];
-        // cv::warpAffine: invert the forward 2x3 matrix in double
-        double D = M[0] * M[4] - M[1] * M[3];
-        D = D != 0 ? 1. / D : 0;
-        const double A11 = M[4] * D, A22 = M[0] * D;
-        M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
-        const double b1 = -M[0] * M[2] - M[1] * M[5], b2 = -M[3] * M[2] - M[4] * M[5];
-        M[2] = b1; M[5] = b2;
-        for (int k = 0; k < 6; ++k) {
-            if (!std::isfinite(M[k])) return bad("crop " + std::to_string(i) + ": singular or non-finite affine");
-            d.Mi[k] = M[k];
-        }
-        d.blur = 0; d.lw = 0; d.rx0 = d.ry0 = d.rw = d.rh = d.tx0 = d.tw = 0; d.w_off = 0; d.pad = 0; d.tmp_off = d.blur_off = 0;
-        const double sigma = crops[i].sigma;
-        if (!(sigma >= 0) || !std::isfinite(sigma) || !(crops[i].truncate > 0)) return bad("crop " + std::to_string(i) + ": bad sigma / truncate");
-        if (sigma > 1e-15) {          // scipy.ndimage.gaussian_filter skips axes with sigma <= 1e-15
-            // bounding box of the texels the warp can touch: the map is affine, so the extremes are at the patch corners
-            long long lo_x = INT64_MAX, hi_x = INT64_MIN, lo_y = INT64_MAX, hi_y = INT64_MIN;
-            for (int cy = 0; cy < 2; ++cy)
-                for (int cx = 0; cx < 2; ++cx) {
-                    const double x = cx ? patch - 1 : 0, y = cy ? patch - 1 : 0;
-                    const long long X = ((long long)std::llrint((M[1] * y + M[2]) * 1024.0) + 16 + (long long)std::llrint(M[0] * x * 1024.0)) >> 10;
-                    const long long Y = ((long long)std::llrint((M[4] * y + M[5]) * 1024.0) + 16 + (long long)std::llrint(M[3] * x * 1024.0)) >> 10;
-                    lo_x = std::min(lo_x, X); hi_x = std::max(hi_x, X); lo_y = std::min(lo_y, Y); hi_y = std::max(hi_y, Y);
-                }
-            // +-1: the per-pixel sum of two separately rounded terms can differ by one fixed-point step from the corner value
-            const long long x0 = std::max<long long>(lo_x - 1, 0), x1 = std::min<long long>(hi_x + 2, W - 1);
-            const long long y0 = std::max<long long>(lo_y - 1, 0), y1 = std::min<long long>(hi_y + 2, H - 1);
-            if (x0 <= x1 && y0 <= y1) {
-                d.blur = 1;
-                d.lw = (int)(crops[i].truncate * sigma + 0.5);            // scipy: int(truncate * sd + 0.5)
-                if (d.lw > 4096) return bad("crop " + std::to_string(i) + ": blur radius too large");
-                d.rx0 = (int)x0; d.ry0 = (int)y0; d.rw = (int)(x1 - x0 + 1); d.rh = (int)(y1 - y0 + 1);
-                d.tx0 = (int)std::max<long long>(x0 - d.lw, 0);
-                d.tw = (int)(std::min<long long>(x1 + d.lw, W - 1) - d.tx0 + 1);
-                // scipy _gaussian_kernel1d: exp(-0.5 / sigma^2 * x^2), normalised by the numpy sum
-                std::vector<double> phi(2 * d.lw + 1);
-                const double s2 = sigma * sigma;
-                for (int k = -d.lw; k <= d.lw; ++k) phi[k + d.lw] = std::exp(-0.5 / s2 * (double)(k * k));
-                const double tot = np_sum(phi);
-                d.w_off = (int)wts.size();
-                for (double p : phi) wts.push_back(p / tot);
-                d.tmp_off = (int64_t)need; need += (size_t)d.rh * d.tw * 3;
-                d.blur_off = (int64_t)need; need += (size_t)d.rh * d.rw * 3;
-                max_v = std::max<int64_t>(max_v, (int64_t)d.rh * d.tw * 3);
-                max_h = std::max<int64_t>(max_h, (int64_t)d.rh * d.rw * 3);
-            }
-        }
+        std::string m;
+        TouchBox box;
+        if (!prep_crop(crops[i].M, crops[i].sigma, crops[i].truncate, i, patch, H, W, true, cds[i], wts, plan, box, m)) return bad(m);
     }
+    const size_t need = plan.need;
+    const int64_t max_v = plan.max_v, max_h = plan.max_h;
     auto hip_bad = [&](const char* what, hipError_t e) { c->err = std::string(what) + ": " + hipGetErrorString(e); g_crop_err = c->err; return THMR_ERR_HIP; };
     hipError_t e;
     // grow-only device buffers (re-allocation synchronises the stream first: earlier launches may still read the old ones)
@@ -296,6 +382,76 @@ int thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int32
     }
     hipLaunchKernelGGL(crop_warp_kernel, dim3((patch * patch + 255) / 256, n), dim3(256), 0, st, frame_dev, H, W, row_stride, c->cds,
                        c->scratch, patch, swap_rb, mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], out_dev);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_bad("crop kernel launch", e);
+    return 0;
+}
+
+int thmr_cropper_run_frames(thmr_cropper* c, const thmr_frame_crop* items, int32_t n, int32_t patch, int32_t swap_rb, const float* mean,
+                            const float* std_, float* out_dev, void* stream) {
+    // every argument is checked before the handle, and the handle before any HIP call: a refusal never touches the device
+    auto bad = [&](const std::string& m) { if (c) c->err = m; g_crop_err = m; return THMR_ERR_INVALID; };
+    if (!items || !out_dev || !mean || !std_) return bad("null buffer");
+    if (n <= 0 || patch <= 0 || patch > 4096) return bad("bad batch / patch geometry");
+    // descriptors and weights travel in one buffer: [n FrameDev][weights]
+    std::vector<FrameDev> fds(n);
+    std::vector<double> wts;
+    CropPlan plan;
+    for (int i = 0; i < n; ++i) {
+        const thmr_frame_crop& it = items[i];
+        const std::string who = "item " + std::to_string(i) + ": ";
+        // the warp keeps 16-bit texel coordinates (saturate_cast<short>), which the corner rule below does not model
+        if (it.H <= 0 || it.W <= 0 || it.H > 32767 || it.W > 32767) return bad(who + "bad frame geometry");
+        if (it.win_x0 < 0 || it.win_y0 < 0 || it.win_w < 0 || it.win_h < 0 || (int64_t)it.win_x0 + it.win_w > it.W ||
+            (int64_t)it.win_y0 + it.win_h > it.H)
+            return bad(who + "the window does not lie inside the frame");
+        if (it.row_stride < (int64_t)it.win_w * 3) return bad(who + "row_stride is less than win_w * 3");
+        FrameDev& f = fds[i];
+        TouchBox box;
+        std::string m;
+        if (!prep_crop(it.M, it.sigma, it.truncate, i, patch, it.H, it.W, false, f.c, wts, plan, box, m)) return bad(m);
+        f.win = nullptr; f.stride = 0; f.H = it.H; f.W = it.W; f.wx0 = f.wy0 = f.ww = f.wh = 0;
+        if (box.empty()) continue;          // every output pixel is border: the kernels read nothing of this item
+        if (!it.win_dev) return bad(who + "null window pointer");
+        if (box.bx0 < it.win_x0 || box.bx1 >= (int64_t)it.win_x0 + it.win_w || box.by0 < it.win_y0 || box.by1 >= (int64_t)it.win_y0 + it.win_h)
+            return bad(who + "the window does not cover the texels the crop can touch: x " + std::to_string(box.bx0) + ".." +
+                       std::to_string(box.bx1) + ", y " + std::to_string(box.by0) + ".." + std::to_string(box.by1));
+        f.win = it.win_dev; f.stride = it.row_stride; f.wx0 = it.win_x0; f.wy0 = it.win_y0; f.ww = it.win_w; f.wh = it.win_h;
+    }
+    if (!c) return bad("null cropper");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipSetDevice(c->device) != hipSuccess) return bad("hipSetDevice failed");
+    auto hip_bad = [&](const char* what, hipError_t e) { c->err = std::string(what) + ": " + hipGetErrorString(e); g_crop_err = c->err; return THMR_ERR_HIP; };
+    hipError_t e;
+    const size_t desc_bytes = sizeof(FrameDev) * (size_t)n, bytes = desc_bytes + sizeof(double) * wts.size();
+    // grow-only device buffers (re-allocation synchronises the stream first: earlier launches may still read the old ones)
+    if (bytes > c->fds_cap || plan.need > c->scratch_doubles) {
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_bad("hipStreamSynchronize", e);
+        if (bytes > c->fds_cap) {
+            if (c->fds) (void)hipFree(c->fds);
+            c->fds = nullptr; c->fds_cap = 0;
+            if ((e = hipMalloc(&c->fds, bytes * 2)) != hipSuccess) return hip_bad("hipMalloc(frame descriptors)", e);
+            c->fds_cap = bytes * 2;
+        }
+        if (plan.need > c->scratch_doubles) {
+            if (c->scratch) (void)hipFree(c->scratch);
+            c->scratch = nullptr; c->scratch_doubles = 0;
+            if ((e = hipMalloc(&c->scratch, sizeof(double) * plan.need)) != hipSuccess) return hip_bad("hipMalloc(blur scratch)", e);
+            c->scratch_doubles = plan.need;
+        }
+    }
+    std::vector<char> host(bytes);
+    memcpy(host.data(), fds.data(), desc_bytes);
+    if (!wts.empty()) memcpy(host.data() + desc_bytes, wts.data(), sizeof(double) * wts.size());
+    // a pageable-host -> device copy returns after staging, so the vector may die at the end of this call
+    if ((e = hipMemcpyAsync(c->fds, host.data(), bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_bad("hipMemcpyAsync", e);
+    const FrameDev* fd = reinterpret_cast<const FrameDev*>(c->fds);
+    const double* wd = reinterpret_cast<const double*>(c->fds + desc_bytes);
+    if (plan.max_v > 0) {
+        hipLaunchKernelGGL(crop_frames_vpass_kernel, dim3((unsigned)((plan.max_v + 255) / 256), n), dim3(256), 0, st, fd, wd, c->scratch);
+        hipLaunchKernelGGL(crop_frames_hpass_kernel, dim3((unsigned)((plan.max_h + 255) / 256), n), dim3(256), 0, st, fd, wd, c->scratch);
+    }
+    hipLaunchKernelGGL(crop_frames_warp_kernel, dim3((patch * patch + 255) / 256, n), dim3(256), 0, st, fd, c->scratch, patch, swap_rb,
+                       mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], out_dev);
     if ((e = hipGetLastError()) != hipSuccess) return hip_bad("crop kernel launch", e);
     return 0;
 }

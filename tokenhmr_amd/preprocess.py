@@ -12,6 +12,9 @@ in ONE GPU call, already collated and resident on the device.  `crop_examples` i
 The box -> affine arithmetic (3 points, float32, lib/datasets/utils.py:81-128 + cv2.getAffineTransform) runs here on the host
 in numpy; warp, anti-alias blur, channel flip and normalisation run in csrc/crop.hip through the C ABI (thmr_cropper_run).
 torch is used only to hold device memory.  There is no CPU fallback.
+
+`Cropper.warp_frames` is the eval.py shape: B items from B frames of B sizes, one crop each, in ONE call
+(thmr_cropper_run_frames), uploading only the window of each frame its crop can touch (`source_window`).
 """
 import ctypes as C
 
@@ -69,8 +72,49 @@ def expand_to_aspect_ratio(input_shape, target_aspect_ratio=None):
     return np.array([max(float(h) * w_t / h_t, w), h])
 
 
+def source_window(M, patch, H, W, sigma=0.0, truncate=3.0):
+    """The box of frame texels a crop can touch — (x0, y0, w, h), or None when every output pixel is border — as
+    thmr_cropper_run_frames computes it (include/tokenhmr_hip.h), restated in Python floats (IEEE double, no fused operations) and
+    integers: the fixed-point source coordinate of the four patch corners, [lo - 1, hi + 2] on each axis, clipped to the frame; for a
+    blurred crop (sigma > 1e-15) widened by the kernel radius int(truncate * sigma + 0.5) on all four sides, clipped again.
+    Raises ValueError where the C side refuses the crop itself (singular affine, bad sigma / truncate)."""
+    m = [float(v) for v in np.asarray(M, dtype=np.float64).reshape(6)]
+    sigma, truncate, patch, H, W = float(sigma), float(truncate), int(patch), int(H), int(W)
+    # cv::warpAffine: invert the forward 2x3 matrix in double
+    D = m[0] * m[4] - m[1] * m[3]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = m[4] * D, m[0] * D
+    m[0] = A11; m[1] *= -D; m[3] *= -D; m[4] = A22
+    b1, b2 = -m[0] * m[2] - m[1] * m[5], -m[3] * m[2] - m[4] * m[5]
+    m[2], m[5] = b1, b2
+    if not all(np.isfinite(m)):
+        raise ValueError("singular or non-finite affine")
+    if not (sigma >= 0) or not np.isfinite(sigma) or not (truncate > 0):
+        raise ValueError("bad sigma / truncate")
+    xs, ys = [], []
+    for y in (0.0, float(patch - 1)):
+        for x in (0.0, float(patch - 1)):
+            xs.append((round((m[1] * y + m[2]) * 1024.0) + 16 + round(m[0] * x * 1024.0)) >> 10)        # round(): half to even, as llrint
+            ys.append((round((m[4] * y + m[5]) * 1024.0) + 16 + round(m[3] * x * 1024.0)) >> 10)
+    x0, x1 = max(min(xs) - 1, 0), min(max(xs) + 2, W - 1)
+    y0, y1 = max(min(ys) - 1, 0), min(max(ys) + 2, H - 1)
+    if x0 > x1 or y0 > y1:
+        return None
+    if sigma > 1e-15:
+        lw = int(truncate * sigma + 0.5)
+        x0, x1, y0, y1 = max(x0 - lw, 0), min(x1 + lw, W - 1), max(y0 - lw, 0), min(y1 + lw, H - 1)
+    return x0, y0, x1 - x0 + 1, y1 - y0 + 1
+
+
+class _Staging:
+    """One set of staging buffers of warp_frames: pinned host bytes, their device twin, and the event behind their last use."""
+
+    def __init__(self):
+        self.host = self.dev = self.event = None
+
+
 class Cropper:
-    """Owns a thmr_cropper handle (device scratch for blurred regions)."""
+    """Owns a thmr_cropper handle (device scratch for blurred regions) and, for warp_frames, two grow-only sets of staging buffers."""
 
     def __init__(self, device="cuda:0"):
         self.device = torch.device(device)
@@ -85,9 +129,14 @@ class Cropper:
         if rc != 0:
             raise _cabi.EngineError(f"thmr_cropper_create: {self.lib.thmr_cropper_last_error(None).decode()}")
         self.h = h
+        self._stage, self._turn = (_Staging(), _Staging()), 0
+        self.last_staged_bytes = 0
 
     def close(self):
         if getattr(self, "h", None):
+            for st in self._stage:
+                if st.event is not None:
+                    st.event.synchronize()
             self.lib.thmr_cropper_destroy(self.h)
             self.h = None
 
@@ -128,6 +177,97 @@ class Cropper:
         if rc != 0:
             raise _cabi.EngineError(f"thmr_cropper_run error {rc}: {self.lib.thmr_cropper_last_error(self.h).decode()}")
         return out
+
+    def warp_frames(self, frames, trans, sigmas=None, truncate=3.0, patch=256, mean=DEFAULT_MEAN, std=DEFAULT_STD, is_bgr=True,
+                    windows=True, out=None, extra=None):
+        """n items from n frames, one crop each, in one call: frames is a list of (H_i, W_i, 3) uint8 arrays (the same array object
+        may appear several times), trans (n,2,3) and sigmas (n,) as for `warp`.  Returns (n,3,patch,patch) float32 on the device,
+        item i bit-equal to `warp(frames[i], trans[i:i+1], ...)`.
+        windows=True uploads of each frame only `source_window` of its crop, windows=False whole frames; a list gives one
+        (x0, y0, w, h) or None per item (the C side refuses a window that does not cover what the crop can touch).  Everything is
+        packed back to back, each start 256-byte aligned, into one pinned staging buffer and uploaded with ONE non-blocking copy on
+        the current stream.  There are two sets of staging buffers, used alternately, so the host may pack the next batch while this
+        one's copy is in flight; a set is reused only after the event recorded behind its last use has completed.
+        Memory: each of the two sets holds up to 1.25 x the largest batch staged so far, pinned on the host and again on the device,
+        until close() — with windows=False at 64 full-HD frames that is 2 x 0.5 GB of each; with windows, 2 x 66 MB.
+        extra: a 1-D uint8 array that rides in the same upload (a batch's small host arrays); the call then returns
+        (crops, a fresh device copy of those bytes) — fresh, because the staging it arrived in is recycled two calls later."""
+        n = len(frames)
+        trans = np.asarray(trans, dtype=np.float64).reshape(-1, 6)
+        if n == 0 or trans.shape[0] != n:
+            raise ValueError("warp_frames needs one affine per frame and at least one frame")
+        sig = np.zeros(n) if sigmas is None else np.asarray(sigmas, dtype=np.float64).reshape(n)
+        wins, offs, placed, total = [], [], {}, 0
+        for i, fr in enumerate(frames):
+            if not isinstance(fr, np.ndarray) or fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3:
+                raise ValueError(f"frame {i} must be an (H, W, 3) uint8 array")
+            H, W = fr.shape[:2]
+            if windows is True:
+                w = source_window(trans[i], patch, H, W, sig[i], truncate)
+            elif windows is False:
+                w = (0, 0, W, H)
+            else:
+                w = windows[i]
+            w = (0, 0, 0, 0) if w is None else tuple(int(v) for v in w)
+            if w[0] < 0 or w[1] < 0 or w[2] < 0 or w[3] < 0 or w[0] + w[2] > W or w[1] + w[3] > H:
+                raise ValueError(f"item {i}: the window {w} does not lie inside the {W}x{H} frame")
+            wins.append(w)
+            key = (id(fr), w)
+            if key not in placed:          # items that share a frame object and a window share its bytes
+                placed[key] = total
+                total = (total + w[2] * w[3] * 3 + 255) & ~255
+            offs.append(placed[key])
+        if extra is not None:
+            extra = np.ascontiguousarray(extra, dtype=np.uint8).reshape(-1)
+            extra_off = total
+            total = (total + extra.size + 255) & ~255
+        st = self._stage[self._turn]
+        self._turn ^= 1
+        if st.event is not None:
+            st.event.synchronize()         # the copy and the kernels that last read this set are done
+        if st.host is None or st.host.numel() < total:
+            cap = max(total + total // 4, 1 << 20)          # 25 % headroom: see the docstring for what whole frames cost
+            st.host = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
+            st.dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        hbuf = st.host.numpy()
+        done = set()
+        for i, fr in enumerate(frames):
+            (x0, y0, w, h), o = wins[i], offs[i]
+            if o in done or w * h == 0:
+                continue
+            done.add(o)
+            hbuf[o:o + w * h * 3].reshape(h, w, 3)[...] = fr[y0:y0 + h, x0:x0 + w]
+        if extra is not None:
+            hbuf[extra_off:extra_off + extra.size] = extra
+        self.last_staged_bytes = total
+        items = (_cabi.FrameCrop * n)()
+        for i, fr in enumerate(frames):
+            x0, y0, w, h = wins[i]
+            it = items[i]
+            it.win_dev = st.dev.data_ptr() + offs[i] if w * h else None
+            it.row_stride, it.H, it.W = w * 3, fr.shape[0], fr.shape[1]
+            it.win_x0, it.win_y0, it.win_w, it.win_h = x0, y0, w, h
+            it.M[:] = trans[i].tolist()
+            it.sigma, it.truncate = float(sig[i]), float(truncate)
+        m = (C.c_float * 3)(*[np.float32(255.0 * v) for v in mean])
+        s = (C.c_float * 3)(*[np.float32(255.0 * v) for v in std])
+        if out is None:
+            out = torch.empty(n, 3, patch, patch, device=self.device, dtype=torch.float32)
+        elif out.shape != (n, 3, patch, patch) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous (n,3,patch,patch) float32 tensor on the cropper's device")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            if total:
+                st.dev[:total].copy_(st.host[:total], non_blocking=True)
+            rc = self.lib.thmr_cropper_run_frames(self.h, items, n, int(patch), int(bool(is_bgr)), m, s, C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(stream.cuda_stream))
+            extra_dev = st.dev[extra_off:extra_off + extra.size].clone() if extra is not None else None
+            if st.event is None:
+                st.event = torch.cuda.Event()
+            st.event.record(stream)
+        if rc != 0:
+            raise _cabi.EngineError(f"thmr_cropper_run_frames error {rc}: {self.lib.thmr_cropper_last_error(self.h).decode()}")
+        return out if extra is None else (out, extra_dev)
 
 
 class ViTDetDataset:

@@ -91,12 +91,16 @@ def _np(x):
     return np.asarray(x)
 
 
-def load_smpl_pkl(model_pkl: str, j19_pkl: str, cfg: HMRConfig = RELEASE):
-    """Real SMPL constants -> the same dict layout as make_synthetic_smpl()."""
+def load_smpl_pkl(model_pkl: str, j19_pkl, cfg: HMRConfig = RELEASE):
+    """Real SMPL constants -> the same dict layout as make_synthetic_smpl().  j19_pkl=None: a zero extra-joint regressor, for callers
+    that read the vertices only (the datasets' ground-truth meshes)."""
     with open(model_pkl, "rb") as f:
         d = _Unpickler(f, encoding="latin1").load()
-    with open(j19_pkl, "rb") as f:
-        j19 = pickle.load(f, encoding="latin1")
+    if j19_pkl is None:
+        j19 = np.zeros((cfg.n_j19, cfg.n_verts), dtype=np.float32)
+    else:
+        with open(j19_pkl, "rb") as f:
+            j19 = pickle.load(f, encoding="latin1")
     V = cfg.n_verts
     a = {}
     a["v_template"] = torch.from_numpy(_np(d["v_template"]).astype(np.float32))
