@@ -316,7 +316,7 @@ int thmr_op_gemm(const float* A_dev, int64_t lda, const float* W_dev, const floa
  *   -1 = the engine's rule; 0 = 128x256 tile, 8 waves; 2 = 128x128, 4 waves; 5 = the 128x256 grid with its ragged last round as 128x128
  *         half tiles (only shapes whose tile count leaves at most half a round: fc1 of a 64-crop batch; else an error) — all bit-identical;
  *   202 / 204 = split-K 2 / 4 on the big tiles (the engine's 5 ... 31 crops use 2, 3 and 4 crops 4);
- *   300 = 256 PERSISTENT workgroups over a tile stream (M % 128 == 0, N % 256 == 0, at least 256 tiles, a 256-CU device; a ragged last round
+ *   300 = 256 PERSISTENT workgroups over a tile stream (M % 32 == 0, N % 256 == 0, at least 256 tiles, a 256-CU device; a ragged last round
  *         is split along K with the accumulators handed from one workgroup to the next through memory — bit-identical to 0 / 2; the
  *         engine's fc2 at 32 crops and more);
  *   + 1000 (1000, 1002, 1202, 1204, 1300; epi 0 / 4): A is a ROW-BLOCKED split3 operand [rows / 32][K / 8][3][32][8] (rows padded to 32;

@@ -545,7 +545,7 @@ def test_standalone_smpl_gt_meshes(built_lib, cuda_dev):
 def test_batch_regimes_agree(built_lib, cuda_dev, mode):
     """The ViT has regimes of the batch size, and within one a crop's result may not depend on the batch it rides in (bit-identical);
     across regimes the K sums are associated differently (fp32-rounding-close).
-      "f32" (csrc/engine.hip kKeysplitMaxB, kSmallM, kMidLoM, kMidHiM): B <= 2 and 3 ... 6 (both: 64x64 ring kernel, split-K 4 on proj /
+      "f32" (csrc/vit_plan.h kKeysplitMaxB, kSmallM, kMidLoM, kMidHiM): B <= 2 and 3 ... 6 (both: 64x64 ring kernel, split-K 4 on proj /
         fc2; one or two crops additionally use the key-split attention kernel), 7 ... 16 (big tiles, split-K 2), >= 17 (big tiles, unsplit).
       "split3" (the default; kSplit3LowMinB, kSplit3MidMinB, kSplit3MinB, kSplit3Fc2MaxB): B <= 2 (the exact-fp32 kernels), 3 ... 4 (proj /
         fc2 split K four ways), 5 ... 15 (two ways; the head has its own boundary between 6 and 7 crops — the VQ decoder's tiny-M kernel —

@@ -563,6 +563,53 @@ def test_gemm_ring_rejects(built_lib, cuda_dev):
         ops.gemm(a, w, variant="ring4/k2")            # 96 % 64 != 0
 
 
+def test_splitk_operators_share_one_partial_sum_pool(built_lib, cuda_dev):
+    """The split-K kinds of the stateless GEMM operators keep their partial planes in ONE grow-only buffer per (device, stream)
+    (csrc/ops_abi.hip op_partial_ws; each library has its own).  Interleaved on one stream without a host synchronisation in between:
+    the f32 ring kernel, the f32 big tile, the split3 tile and (experiments build) the split3 ring kernel, each at the smallest shape its
+    own split-K test uses, then at a shape at least four times larger — every one of those grows the buffer, i.e. replaces it while the
+    earlier launches are still queued — then small again, then large again.  Every result equals the same call's first result bit for
+    bit and the fp64 product within the tolerance of the kind's own test (test_gemm_ring_shapes / test_gemm_big_tile_splitk: 3e-5;
+    test_gemm_split3: 2e-4 with its outlier channels)."""
+    from tokenhmr_amd import ops
+    #        kind               small           large (ascending in ksplit * M * N, so each one grows the shipped library's buffer)
+    cases = [("ring4/k4", False, (64, 64, 256), (128, 128, 256)),
+             ("128x128/k2", False, (200, 72, 512), (400, 144, 512)),
+             ("auto/k2", True, (1, 8, 64), (384, 512, 256)),
+             ("ring/k2", True, (1, 8, 64), (384, 512, 256))]
+    calls = {}
+    for name, s3, small, large in cases:
+        for shape in (small, large):
+            M, N, K = shape
+            a, w, b, r = _rand(M, K, seed=1), _rand(N, K, seed=2, scale=1 / math.sqrt(K)), _rand(N, seed=3), _rand(M, N, seed=4)
+            if s3:
+                a[:, ::7] *= 30.0
+            da, dw, db, dr = a.to(cuda_dev), w.to(cuda_dev), b.to(cuda_dev), r.to(cuda_dev)
+            ref = _gemm_ref(a, w, b, r, "bias_resid", 1.0, 0)
+            if s3:
+                sa, sw = ops.split3(da), ops.split3(dw)
+                def run(sa=sa, sw=sw, db=db, dr=dr, name=name):
+                    if name in ops.SPLIT3_EXP_ONLY:
+                        with ops.experiments_build():
+                            return ops.gemm_split3(sa, sw, db, dr, epi="bias_resid", variant=name)
+                    return ops.gemm_split3(sa, sw, db, dr, epi="bias_resid", variant=name)
+            else:
+                run = lambda da=da, dw=dw, db=db, dr=dr, name=name: ops.gemm(da, dw, db, dr, epi="bias_resid", variant=name)
+            calls[(name, shape)] = (run, ref, 2e-4 if s3 else 3e-5)
+    torch.cuda.synchronize()
+    outs = []                                     # the whole sequence is queued before anything is read back
+    for which in (2, 3, 2, 3):                    # small, large, small, large
+        for case in cases:
+            key = (case[0], case[which])
+            outs.append((key, calls[key][0]()))
+    torch.cuda.synchronize()
+    first = {}
+    for key, o in outs:
+        _, ref, atol = calls[key]
+        assert torch.equal(o, first.setdefault(key, o)), key
+        assert torch.allclose(o.cpu(), ref, atol=atol, rtol=1e-5), (key, (o.cpu() - ref).abs().max())
+
+
 def test_gelu_epilogue_ulp(built_lib, cuda_dev):
     """The epilogue's branch-free erf (csrc/common.h erf_gelu; erf_fast in the THMR_GELU_IMPL=1/2 builds) against fp64 GELU on a dense grid.  A has x in column 0 and
     W a single 1, so C[m, n] = gelu(x_m) with no accumulation error.  fp32 GELU itself loses bits to the 1+erf cancellation

@@ -339,6 +339,97 @@ def test_rowops_entry_points_reject_bad_arguments_without_a_gpu(built_lib, exp):
     assert set(ok) == {s[len("thmr_op_"):] for s in _cabi.ROWOPS_SYMBOLS}       # every one of the 13 entry points was refused at least once
 
 
+@pytest.mark.parametrize("exp", [False, True])
+def test_gemm_operator_variant_tables_without_a_gpu(built_lib, exp):
+    """The `variant` ids of thmr_op_gemm, thmr_op_gemm_split3 and thmr_op_gemm_split3_out_split3 are decoded from one table
+    (csrc/op_gemm_variants.h) before any HIP call, so without a GPU a call that the table accepts fails LATER (THMR_ERR_HIP / _NOMEM at its
+    first HIP call, or a shape / device refusal of the launcher) and a call that the table refuses says which ids exist.  Skipped on a GPU
+    box: an accepted id would launch on the dummy addresses.
+    Not every id belongs to every operator: 300, the split-K ids and the timing-only ones have an fp32 result only (C_ONLY), 302 / 311 /
+    312 a split3 result only (OUT_ONLY).  thmr_op_gemm has never refused an id — what launch_gemm does not know runs its default tile — and still does not: the ids
+    "outside the tables" are asserted on the two split3 operators."""
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    from tokenhmr_amd import ops
+    L = _cabi.load(exp=exp)
+    null = C.c_void_p(0)
+    A, Wt, Cc, bias, resid = (C.c_void_p(4096 * i) for i in range(1, 6))      # non-null dummies: nothing dereferences them without a device
+    M, N, K = 128, 256, 256
+
+    def call(entry, code, epi=0):
+        if entry == "gemm":
+            rc = L.thmr_op_gemm(A, K, Wt, bias, resid, Cc, N, M, N, K, epi, 1.0, 0, code, null)
+        elif entry == "gemm_split3":
+            rc = L.thmr_op_gemm_split3(A, K, Wt, K, bias, resid, Cc, N, M, N, K, epi, 1.0, 0, code, null)
+        else:
+            rc = L.thmr_op_gemm_split3_out_split3(A, K, Wt, K, bias, Cc, N, M, N, K, epi, 1.0, 0, code, null)
+        return rc, (L.thmr_last_error(None) or b"").decode()
+
+    def by_table(msg):          # the three refusals op_gemm_decode words
+        return "bad variant" in msg or "exists only in the experiments build" in msg or "takes epilogues" in msg
+
+    def accepted(entry, code, epi=0):
+        rc, msg = call(entry, code, epi)
+        assert rc < 0 and not by_table(msg), (entry, code, epi, rc, msg)
+
+    def refused(entry, code, epi=0, words=("bad variant", "valid:")):
+        rc, msg = call(entry, code, epi)
+        assert rc == -1 and all(w in msg for w in words), (entry, code, epi, rc, msg)
+        return msg
+
+    C_ONLY = {"auto/k2", "auto/k4", "persist", "persist/128x128/k2", "persist/128x128/k4", "ring/k2", "ring/k4", "old/persist",
+              "exp/reads-every-2nd", "abl/no-copies", "abl/no-barrier", "abl/no-reads", "abl/none"}
+    OUT_ONLY = {"persist/swap", "old/persist/lds", "old/persist/swap"}
+    assert ops.SPLIT3_EXP_ONLY <= set(ops.SPLIT3_VARIANT) and (C_ONLY | OUT_ONLY) <= set(ops.SPLIT3_VARIANT)
+    for code in ops.VARIANT.values():
+        accepted("gemm", code)
+    for name, code in ops.SPLIT3_VARIANT.items():
+        for entry in [e for e, skip in (("gemm_split3", OUT_ONLY), ("gemm_split3_out", C_ONLY)) if name not in skip]:
+            if name not in ops.SPLIT3_EXP_ONLY or exp:
+                accepted(entry, code)
+            else:
+                refused(entry, code, words=("exists only in the experiments build", str(code)))
+    # ids outside the tables.  On ..._out_split3 + 1000 goes with ANY id, so 1001 and 1320 are ids 1 (experiments only) and 320 there; 1003
+    # and 1300 take their place (3 and 300 have an fp32 result only)
+    accepted("gemm_split3_out", 1320)
+    accepted("gemm_split3_out", 1001) if exp else refused("gemm_split3_out", 1001, words=("exists only in the experiments build",))
+    for entry, codes in (("gemm_split3", (12, 99, 205, 301, 323, 1001, 1320, -2, 2000)), ("gemm_split3_out", (12, 99, 205, 301, 323, 1003, 1300, -2, 2000))):
+        for code in codes:
+            msg = refused(entry, code)
+            valid = msg[msg.index("valid:"):]
+            for listed in ("-1, 0, 2, 5, 8, 10", "320", "experiments build", "100", "row-blocked", "1000, 1002"):      # the error names the valid set
+                assert listed in valid, (entry, code, msg)
+            assert ("300" in valid and "1300" in valid and "302" not in valid) if entry == "gemm_split3" else ("302" in valid and "1302" in valid)
+    # the epilogue restrictions of the header: no pos-embed on a ring / split-K / ring16 / stream id, no bias_resid on ring16 ...
+    for code in (100, 101, 112, 207, 400, 120):
+        refused("gemm", code, epi=6, words=("takes epilogues", str(code)))
+    refused("gemm", 120, epi=4, words=("takes epilogues 0, 1, 2, 3, 5 only",))
+    for code in (-1, 7, 9, 2):
+        accepted("gemm", code, epi=6)
+    for code in (5, 202, 204, 300, 320, 322) + ((100, 101, 1, 20) if exp else ()):
+        refused("gemm_split3", code, epi=6, words=("takes epilogues 0, 1, 2, 4, 5 only",))
+    for code in (-1, 0, 2, 8, 10) + ((6, 9, 11) if exp else ()):
+        accepted("gemm_split3", code, epi=6)
+    refused("gemm_split3", 0, epi=3, words=("epilogue must be one of 0, 1, 2, 4, 5, 6",))
+    # ... a row-blocked A only on the ids that read one, and only with the epilogues fc2 runs (0 / 4) ...
+    for code in (1000, 1002, 1008, 1202, 1204, 1300):
+        for epi in (0, 4):
+            accepted("gemm_split3", code, epi)
+        for epi in (1, 2, 5, 6):
+            refused("gemm_split3", code, epi, words=("takes epilogues 0, 4 only",))
+    for code in (999, 1005, 1010, 1320, 1322):
+        refused("gemm_split3", code)
+    # ... and a split3 result with none of the epilogues that read a residual or the position table
+    for code in (-1, 0, 302, 1000, 1302):
+        for epi in (3, 4, 6):
+            refused("gemm_split3_out", code, epi, words=("epilogue must be one of 0, 1, 2, 5",))
+        for epi in (0, 1, 2, 5):
+            accepted("gemm_split3_out", code, epi)
+    if exp:
+        for epi in (1, 5):
+            refused("gemm_split3_out", 311, epi, words=("takes epilogues 0, 2 only",))
+
+
 def test_gemm_k_loops_carry_no_valu_instruction(built_lib, tmp_path):
     """ISA-level regression guard (CPU): on gfx950 every VALU instruction issued between fp32 MFMAs costs matrix-pipe time
     (profiles/r1_mfma_valu_microbench.log), so the K loops of the product GEMM (128x160 tile, fc1 epilogue) and of the

@@ -453,7 +453,7 @@ __device__ __forceinline__ void split16_body(GemmArgs& a, int tiles_m, int tiles
         int j, kb, ke, kind, bm0, bn0;
         seg_of(0, j, kb, ke, kind);
         tile_of(j, bm0, bn0);
-        set_offsets(bm0, bn0);          // persistent: M % 128 == 0 and N % 256 == 0, the offsets are the same for every tile
+        set_offsets(bm0, bn0);          // persistent: N % 256 == 0; with M % 128 == 0 the offsets are the same for every tile, a ragged M (M % 32 == 0) sets them again per segment (fetch_seg)
     }
     fill(0);
     if constexpr (PERSIST) {
@@ -684,8 +684,8 @@ __device__ __forceinline__ void split16_body(GemmArgs& a, int tiles_m, int tiles
     }
 }
 
-// WN = waves along N (4: 128 x 256 tile, 8 waves; 2: 128 x 128, 4 waves).  PERSIST: 256 workgroups over a tile stream (WN = 4; M % 128 == 0,
-// N % 256 == 0) instead of one workgroup per (tile, K slice).  ABLK: A is a row-blocked split3 operand (GemmArgs::a_blk).
+// WN = waves along N (4: 128 x 256 tile, 8 waves; 2: 128 x 128, 4 waves).  PERSIST: 256 workgroups over a tile stream (WN = 4; M % 32 == 0:
+// a ragged M is served in whole 32-row blocks; N % 256 == 0) instead of one workgroup per (tile, K slice).  ABLK: A is a row-blocked split3 operand (GemmArgs::a_blk).
 // (__launch_bounds__(512) for the 4-wave instantiation too: told that a workgroup has 256 threads hipcc budgets 512 registers per lane,
 // parks fragments in AGPRs and copies them back inside the K loop — ~40 v_accvgpr moves per 192 MFMAs.  A bound of 512 threads = 256
 // registers gives it the 8-wave instantiation's allocation: none.)

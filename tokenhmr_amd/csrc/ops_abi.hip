@@ -1,0 +1,573 @@
+// The stateless C entry points of include/tokenhmr_hip.h: every thmr_op_* operator, the stand-alone body models (thmr_smpl_*, thmr_smplh_*),
+// the loss value and the evaluation metrics.  None of them touches a thmr_engine (engine.hip owns those calls): each validates its
+// arguments before any HIP call and then launches what the engine launches, through the same launch_* functions (common.h).
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <map>
+#include <mutex>
+
+#include "abi_util.h"
+#include "op_gemm_variants.h"
+#include "vit_plan.h"      // DIM, INNER
+
+#define THMR_FAIL(code, msg) fail(code, msg)      // HIP_OK / LAUNCH_OK (abi_util.h)
+
+namespace {
+
+// The partial planes of a split-K operator call: one grow-only buffer per (device, stream), whichever kernel writes it — launches on one
+// stream are ordered, so they may share a buffer; different streams never do.  (The engine uses its own scratch arena instead.)  `held` is
+// locked here and stays locked across the caller's launches that use the buffer; the device is synchronised before a buffer is replaced.
+// nullptr: a HIP call failed.
+float* op_partial_ws(int dev, void* stream, size_t floats, std::unique_lock<std::mutex>& held) {
+    static std::mutex mu;
+    static std::map<std::pair<int, void*>, std::pair<float*, size_t>> pool;
+    held = std::unique_lock<std::mutex>(mu);
+    auto& slot = pool[{dev, stream}];
+    if (floats <= slot.second) return slot.first;
+    if (slot.first && (hipDeviceSynchronize() != hipSuccess || hipFree(slot.first) != hipSuccess)) return nullptr;
+    slot = {nullptr, 0};
+    if (hipMalloc(&slot.first, floats * sizeof(float)) != hipSuccess) return slot.first = nullptr;
+    slot.second = floats;
+    return slot.first;
+}
+
+// one GEMM as its table row says (op_gemm_variants.h); the refusals that depend on the shape or the device are written here, once per kind
+int op_gemm_run(const OpGemmRow& r, const GemmArgs& a, int epi, void* stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool s3 = r.kind >= THMR_GEMM_S3_TILE && r.kind <= THMR_GEMM_S3_RING;
+    const bool wide = r.kind == THMR_GEMM_S3_STREAM_WIDE, narrow = r.kind == THMR_GEMM_S3_STREAM_NARROW;
+    if (s3 && r.ksplit > 1 && (a.K % (32 * r.ksplit)) != 0) return fail(THMR_ERR_INVALID, "split3 split-K GEMM: K must be a multiple of 32 * ksplit");
+    if (narrow && !gemm_split3_persist_narrow_ok(a)) return fail(THMR_ERR_INVALID, "persistent 128 x 128 split3 GEMM: N % 128 == 0, >= 256 tiles, K >= 96, row-major A");
+    if (wide && !gemm_split3_persist_ok(a))
+        return fail(THMR_ERR_INVALID, "persistent split3 GEMM: M % 32 == 0 (a ragged M is served in whole 32-row blocks), N % 256 == 0, ceil(M / 128) * N / 256 >= 256, K >= 64");
+    if ((wide || narrow) && !device_has_256_cus())
+        return fail(THMR_ERR_INVALID, "persistent split3 GEMM: its 8 x 32 workgroup decomposition needs a 256-CU device (use variant 0 / 2)");
+    std::unique_lock<std::mutex> held;       // the partial planes stay ours until the reduce that reads them is launched
+    float* part = nullptr;
+    if (r.ksplit > 1) {
+        int dev = 0;
+        HIP_OK(hipGetDevice(&dev));
+        part = op_partial_ws(dev, stream, (size_t)r.ksplit * a.M * a.N, held);
+        if (!part) return fail(THMR_ERR_HIP, std::string("split-K partial-sum workspace: ") + hipGetErrorString(hipGetLastError()));
+    }
+    void* ws = nullptr;                      // hand-over workspace of the tile streams
+    if (wide || narrow || r.kind == THMR_GEMM_S3_SPLITK_STREAM) {
+        ws = gemm_split3_persist_op_ws(st);
+        if (!ws) return fail(THMR_ERR_NOMEM, "persistent split3 GEMM: workspace allocation failed");
+    }
+    switch (r.kind) {
+        case THMR_GEMM_F32_TILE: LAUNCH_OK(launch_gemm(a, epi, r.sub, st)); break;
+        case OPK_F32_SKINNY: LAUNCH_OK(launch_gemm_skinny(a, epi, st)); break;
+        case THMR_GEMM_F32_RING16: LAUNCH_OK(launch_gemm_ring16(a, epi, st)); break;
+        case THMR_GEMM_F32_RING: LAUNCH_OK(launch_gemm_ring(a, epi, r.sub, r.ksplit, part, st)); break;
+        case THMR_GEMM_F32_TILE_SPLITK: LAUNCH_OK(launch_gemm_splitk(a, r.sub, r.ksplit, part, st)); break;
+        case THMR_GEMM_S3_TILE: LAUNCH_OK(launch_gemm_split3(a, epi, r.sub, st)); break;
+        case THMR_GEMM_S3_TILE_SPLITK: LAUNCH_OK(launch_gemm_split3_splitk(a, r.ksplit, part, st)); break;
+        case THMR_GEMM_S3_STREAM_WIDE: LAUNCH_OK(launch_gemm_split3_persist(a, epi, r.sub, ws, st)); break;
+        case THMR_GEMM_S3_STREAM_NARROW: LAUNCH_OK(launch_gemm_split3_persist_narrow(a, epi, ws, st)); break;
+        case THMR_GEMM_S3_SPLITK_STREAM:
+            if (launch_gemm_split3_splitk_stream(a, r.ksplit, part, ws, st) != 0)
+                return fail(THMR_ERR_INVALID, "split-K through the 128 x 128 stream: N % 128 == 0, >= 256 (tile, slice) units, >= 3 K tiles per slice, row-major A");
+            break;
+#ifdef THMR_EXPERIMENTS
+        case THMR_GEMM_S3_RING: LAUNCH_OK(launch_gemm_split3_ring(a, epi, r.ksplit, part, st)); break;
+#endif
+        default: return fail(THMR_ERR_INVALID, "internal: GEMM kind without a launcher in this build");
+    }
+    // the fixed-order reduce + epilogue over the partial planes (what the engine fuses into its residual + LayerNorm kernel)
+    if (r.ksplit > 1) LAUNCH_OK(launch_splitk_epilogue(a, epi, part, r.ksplit, st));
+    return 0;
+}
+
+// the checks the three operators share, then the table: fills `r` and `blk`, or refuses
+int op_gemm_prepare(OpGemmEntry entry, bool buffers, int epi, const float* bias, const float* resid, int variant, OpGemmRow* r, bool* blk) {
+    if (!buffers) return fail(THMR_ERR_INVALID, "null buffer");
+    std::string why;
+    *r = op_gemm_decode(entry, variant, epi, blk, &why);
+    if (r->kind < 0) return fail(THMR_ERR_INVALID, why);
+    if (epi != EPI_NONE && !bias) return fail(THMR_ERR_INVALID, "epilogue needs bias");
+    if ((epi == EPI_BIAS_RESID || epi == EPI_BIAS_POS) && !resid) return fail(THMR_ERR_INVALID, "epilogue needs resid");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- the three GEMM operators: validate, decode the variant id (op_gemm_variants.h), launch (op_gemm_run) ----
+int thmr_op_gemm(const float* A, int64_t lda, const float* W, const float* bias, const float* resid, float* C, int64_t ldc,
+                 int32_t M, int32_t N, int32_t K, int32_t epi, float qscale, int32_t qcols, int32_t variant, void* stream) {
+    OpGemmRow r;
+    bool blk;
+    if (int rc = op_gemm_prepare(OP_GEMM_F32, A && W && C, epi, bias, resid, variant, &r, &blk)) return rc;
+    GemmArgs a = mk(A, lda, W, K, bias, resid, ldc, C, ldc, M, N, K);
+    a.qscale = qscale; a.qcols = qcols;
+    return op_gemm_run(r, a, epi, stream);
+}
+
+int thmr_op_split3(const float* src, int64_t ld_src, void* dst, int64_t ld_dst, int64_t rows, int32_t K, void* stream) {
+    if (!src || !dst) return fail(THMR_ERR_INVALID, "null buffer");
+    if (rows <= 0 || K <= 0 || (K % 8) != 0 || (ld_src % 4) != 0 || (ld_dst % 8) != 0 || ld_dst < K || ld_src < K)
+        return fail(THMR_ERR_INVALID, "split3: K % 8, ld_src % 4, ld_dst % 8 must be 0 and the strides >= K");
+    LAUNCH_OK(launch_split3(src, ld_src, dst, ld_dst, rows, K, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_gemm_split3(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const float* resid, float* C,
+                        int64_t ldc, int32_t M, int32_t N, int32_t K, int32_t epi, float qscale, int32_t qcols, int32_t variant,
+                        void* stream) {
+    OpGemmRow r;
+    bool blk;      // A is a ROW-BLOCKED split3 operand ([M / 32][K / 8][3][32][8], rows padded to 32; GemmArgs::a_blk)
+    if (int rc = op_gemm_prepare(OP_GEMM_S3, A && W && C, epi, bias, resid, variant, &r, &blk)) return rc;
+    if (epi == EPI_BIAS_POS && (N % 4) != 0) return fail(THMR_ERR_INVALID, "split3 GEMM: the pos-embed epilogue needs N % 4 == 0");
+    if (M <= 0 || N <= 0 || K <= 0 || (K % 32) != 0 || (lda % 8) != 0 || (ldw % 8) != 0 || lda < K || ldw < K || ldc < N)
+        return fail(THMR_ERR_INVALID, "split3 GEMM: K % 32 == 0, lda / ldw multiples of 8 and >= K, ldc >= N");
+    GemmArgs a = mk(static_cast<const float*>(A), lda, static_cast<const float*>(W), ldw, bias, resid, ldc, C, ldc, M, N, K);
+    a.qscale = qscale; a.qcols = qcols;
+    a.a_blk = blk;
+    return op_gemm_run(r, a, epi, stream);
+}
+
+int thmr_op_gemm_split3_out_split3(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* Cs, int64_t ldcs,
+                                   int32_t M, int32_t N, int32_t K, int32_t epi, float qscale, int32_t qcols, int32_t variant, void* stream) {
+    OpGemmRow r;
+    bool blk;      // the result in the ROW-BLOCKED form ([M / 32][N / 8][3][32][8], Cs holds ceil(M / 32) * 32 rows; GemmArgs::cs_blk)
+    if (int rc = op_gemm_prepare(OP_GEMM_S3_OUT, A && W && Cs, epi, bias, nullptr, variant, &r, &blk)) return rc;
+    if (M <= 0 || N <= 0 || K <= 0 || (K % 32) != 0 || (lda % 8) != 0 || (ldw % 8) != 0 || lda < K || ldw < K || (N % 8) != 0 ||
+        (ldcs % 8) != 0 || ldcs < N)
+        return fail(THMR_ERR_INVALID, "split3 GEMM: K % 32 == 0, N % 8 == 0, lda / ldw / ldcs multiples of 8 and >= K / K / N");
+    GemmArgs a = mk(static_cast<const float*>(A), lda, static_cast<const float*>(W), ldw, bias, nullptr, 0, nullptr, 0, M, N, K);
+    a.qscale = qscale; a.qcols = qcols;
+    a.c_split = Cs; a.ldcs = ldcs;
+    a.cs_blk = blk;
+    return op_gemm_run(r, a, epi, stream);
+}
+
+int thmr_op_layernorm(const float* x, const float* g, const float* b, float* y, int32_t rows, int32_t D, float eps,
+                      int32_t relu, void* stream) {
+    if (!x || !g || !b || !y) return fail(THMR_ERR_INVALID, "null buffer");
+    LAUNCH_OK(launch_layernorm(x, g, b, y, rows, D, eps, relu, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_vit_attention(const float* qkv, float* out, int32_t B, void* stream) {
+    if (!qkv || !out) return fail(THMR_ERR_INVALID, "null buffer");
+    LAUNCH_OK(launch_vit_attention(qkv, out, B, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_vit_attention_split3(const float* qkv, void* out_split, int32_t B, void* stream) {
+    if (!qkv || !out_split || B <= 0) return fail(THMR_ERR_INVALID, "bad argument");
+    LAUNCH_OK(launch_vit_attention_split3(qkv, out_split, B, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_vit_attention_b16(const float* qkv, void* out, int32_t B, int32_t out_split, int32_t qt, void* stream) {
+    if (!qkv || !out || B <= 0) return fail(THMR_ERR_INVALID, "bad argument");
+    LAUNCH_OK(launch_vit_attention_b16(qkv, out, B, out_split != 0, qt, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_vit_attention_variant(const float* qkv, float* out, int32_t B, int32_t variant, void* stream) {
+    if (!qkv || !out) return fail(THMR_ERR_INVALID, "null buffer");
+    LAUNCH_OK(launch_vit_attention_variant(qkv, out, B, variant, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_rot6d(const float* x, float* R, int32_t n, void* stream) {
+    if (!x || !R || n < 1) return fail(THMR_ERR_INVALID, "bad argument");
+    LAUNCH_OK(launch_rot6d(x, R, n, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_aa_to_rotmat(const float* aa, float* R, int32_t n, void* stream) {
+    if (!aa || !R || n < 1) return fail(THMR_ERR_INVALID, "bad argument");
+    LAUNCH_OK(launch_aa_to_rotmat(aa, R, n, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- stateless entry points of the row, glue and head kernels (tests/test_gpu_rowops.py): thin wrappers over the launch_* functions the
+// engine calls; every argument is validated here, before any HIP call, because several of those launchers validate nothing ----
+int thmr_op_splitk_resid_ln(const float* part, int32_t S, int32_t rows, int32_t D, const float* bias, const float* resid, float* xout,
+                            const float* gamma, const float* beta, void* y, float eps, int32_t y_is_split3, void* stream) {
+    if (!part || !bias || !resid || !xout || !gamma || !beta || !y) return fail(THMR_ERR_INVALID, "splitk_resid_ln: null buffer");
+    if (rows <= 0 || S < 1 || D != DIM) return fail(THMR_ERR_INVALID, "splitk_resid_ln: rows >= 1, S >= 1 and D == 1280 are required");
+    if (y_is_split3 && S != 2 && S != 4) return fail(THMR_ERR_INVALID, "splitk_resid_ln: the split3 output exists for S = 2 and 4 only");
+    LAUNCH_OK(launch_splitk_resid_ln(part, S, rows, D, bias, resid, xout, gamma, beta, static_cast<float*>(y), eps,
+                                     static_cast<hipStream_t>(stream), y_is_split3 != 0));
+    return 0;
+}
+
+int thmr_op_add_ln64(const float* x, const float* y, const float* gamma, const float* beta, float* s_out, float* z_out, int32_t rows,
+                     float eps, void* stream) {
+    if (!x || !y || !gamma || !beta || !s_out || !z_out) return fail(THMR_ERR_INVALID, "add_ln64: null buffer");
+    if (rows <= 0) return fail(THMR_ERR_INVALID, "add_ln64: rows >= 1 is required");
+    LAUNCH_OK(launch_add_ln64(x, y, gamma, beta, s_out, z_out, rows, eps, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_transpose(const float* in, float* out, int32_t Bn, int32_t R, int32_t C, void* stream) {
+    if (!in || !out) return fail(THMR_ERR_INVALID, "transpose: null buffer");
+    if (Bn <= 0 || R <= 0 || C <= 0 || Bn > 65535 || (R + 31) / 32 > 65535)
+        return fail(THMR_ERR_INVALID, "transpose: Bn, R, C >= 1, Bn <= 65535 and R <= 32 * 65535 are required (grid y / z)");
+    LAUNCH_OK(launch_transpose(in, out, Bn, R, C, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_softmax_argmax(const float* logits, float* probs, int32_t* idx, int32_t rows, void* stream) {
+    if (!logits) return fail(THMR_ERR_INVALID, "softmax_argmax: null buffer");
+    if (!probs && !idx) return fail(THMR_ERR_INVALID, "softmax_argmax: probs and idx are both null");
+    if (rows <= 0) return fail(THMR_ERR_INVALID, "softmax_argmax: rows >= 1 is required");
+    LAUNCH_OK(launch_softmax_argmax2048(logits, probs, idx, rows, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_cross_attn(const float* q, const float* kv, int64_t ldkv, int32_t koff, float* out, int32_t B, void* stream) {
+    if (!q || !kv || !out) return fail(THMR_ERR_INVALID, "cross_attn: null buffer");
+    if (B <= 0 || B > (1 << 24)) return fail(THMR_ERR_INVALID, "cross_attn: 1 <= B <= 2^24 is required");
+    if (ldkv <= 0 || koff < 0 || (ldkv % 4) != 0 || (koff % 4) != 0 || (int64_t)koff + 2 * INNER > ldkv)
+        return fail(THMR_ERR_INVALID, "cross_attn: ldkv % 4 == 0, koff % 4 == 0 and koff + 1024 <= ldkv are required");
+    LAUNCH_OK(launch_cross_attn(q, kv, ldkv, koff, out, B, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_im2col_patch(const float* img, void* A, int32_t B, int32_t out_split, void* stream) {
+    if (!img || !A) return fail(THMR_ERR_INVALID, "im2col_patch: null buffer");
+    if (B <= 0) return fail(THMR_ERR_INVALID, "im2col_patch: B >= 1 is required");
+    if (out_split) LAUNCH_OK(launch_im2col_patch_split3(img, A, B, static_cast<hipStream_t>(stream)));
+    else LAUNCH_OK(launch_im2col_patch(img, static_cast<float*>(A), B, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_conv3_gather(const float* in, float* out, const int32_t* src, int32_t Bn, int32_t Tin, int32_t Tout, int32_t C, int32_t dil,
+                         int32_t prerelu, void* stream) {
+    if (!in || !out) return fail(THMR_ERR_INVALID, "conv3_gather: null buffer");
+    if (Bn <= 0 || Tin <= 0 || Tout <= 0 || C <= 0 || (C % 4) != 0 || dil < 1)
+        return fail(THMR_ERR_INVALID, "conv3_gather: Bn, Tin, Tout >= 1, C % 4 == 0 and dil >= 1 are required");
+    if (!src && Tin < Tout) return fail(THMR_ERR_INVALID, "conv3_gather: without an index table Tin >= Tout is required");
+    LAUNCH_OK(launch_conv3_gather(in, out, src, Bn, Tin, Tout, C, dil, prerelu, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_conv_gather(const float* in, float* out, const int32_t* src, int32_t Bn, int32_t Tin, int32_t Tsrc, int32_t Tout, int32_t C,
+                        int32_t Cp, int32_t ks, int32_t stride, int32_t pad, void* stream) {
+    if (!in || !out) return fail(THMR_ERR_INVALID, "conv_gather: null buffer");
+    if (Bn <= 0 || Tin <= 0 || Tsrc <= 0 || Tout <= 0 || C <= 0 || Cp < C || ks < 1 || stride < 1 || pad < 0)
+        return fail(THMR_ERR_INVALID, "conv_gather: counts >= 1, Cp >= C, ks >= 1, stride >= 1 and pad >= 0 are required");
+    if (!src && Tin < Tsrc) return fail(THMR_ERR_INVALID, "conv_gather: without an index table Tin >= Tsrc is required");
+    LAUNCH_OK(launch_conv_gather_general(in, out, src, Bn, Tin, Tsrc, Tout, C, Cp, ks, stride, pad, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_conv_repack(const float* w, float* wp, int32_t co, int32_t ci, int32_t cp, int32_t kk, void* stream) {
+    if (!w || !wp) return fail(THMR_ERR_INVALID, "conv_repack: null buffer");
+    if (co <= 0 || ci <= 0 || kk <= 0 || cp < ci) return fail(THMR_ERR_INVALID, "conv_repack: co, ci, kk >= 1 and cp >= ci are required");
+    if (cp == ci) LAUNCH_OK(launch_conv_repack(w, wp, co, ci, kk, static_cast<hipStream_t>(stream)));
+    else LAUNCH_OK(launch_conv_repack_pad(w, wp, co, ci, cp, kk, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_vq_argmin_rows(const float* x, const float* dot, const float* cnorm, int32_t* idx, float* dist, int32_t rows, void* stream) {
+    if (!x || !dot || !cnorm || !idx) return fail(THMR_ERR_INVALID, "vq_argmin_rows: null buffer");
+    if (rows <= 0) return fail(THMR_ERR_INVALID, "vq_argmin_rows: rows >= 1 is required");
+    LAUNCH_OK(launch_vq_argmin_rows(x, dot, cnorm, idx, dist, rows, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_code_norm(const float* cb, float* cn, int32_t ncode, void* stream) {
+    if (!cb || !cn) return fail(THMR_ERR_INVALID, "code_norm: null buffer");
+    if (ncode <= 0) return fail(THMR_ERR_INVALID, "code_norm: ncode >= 1 is required");
+    LAUNCH_OK(launch_code_norm(cb, cn, ncode, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_vq_stats(const float* x, const float* codebook, const int32_t* idx, int32_t rows, int32_t* code_count, int32_t accumulate,
+                     float* partial_scratch, float* commit, float* perplexity, void* stream) {
+    if (!x || !codebook || !idx || !code_count || !partial_scratch) return fail(THMR_ERR_INVALID, "vq_stats: null buffer");
+    if (rows <= 0) return fail(THMR_ERR_INVALID, "vq_stats: rows >= 1 is required");
+    LAUNCH_OK(launch_vq_stats(x, codebook, idx, rows, code_count, accumulate != 0, partial_scratch, commit, perplexity, nullptr,
+                              static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_rotmat_to_aa(const float* R, float* aa, int32_t n, void* stream) {
+    if (!R || !aa) return fail(THMR_ERR_INVALID, "rotmat_to_aa: null buffer");
+    if (n <= 0) return fail(THMR_ERR_INVALID, "rotmat_to_aa: n >= 1 is required");
+    LAUNCH_OK(launch_rotmat_to_aa(R, aa, n, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_head_finish(int32_t kind, const float* ro, int32_t ldro, const float* bpose, const float* init_pose, const float* init_betas,
+                        const float* init_cam, float* pose6d, float* rotmat, float* betas, float* cam, float* cam_t, float* focal,
+                        float focal_length, float img_size, int32_t B, void* stream) {
+    if (kind != 0 && kind != 1) return fail(THMR_ERR_INVALID, "head_finish: kind is 0 (token head) or 1 (HMR2 head)");
+    if (!ro || !init_pose || !init_betas || !init_cam || !rotmat || !betas || !cam) return fail(THMR_ERR_INVALID, "head_finish: null buffer");
+    if (kind == 0 && !bpose) return fail(THMR_ERR_INVALID, "head_finish: the token head needs the VQ-decoded body pose");
+    if (B <= 0) return fail(THMR_ERR_INVALID, "head_finish: B >= 1 is required");
+    if (ldro < (kind == 0 ? 31 : THMR_HMR2_RO_ROWS))
+        return fail(THMR_ERR_INVALID, "head_finish: ldro is below the read-out's column count (31 token head, 157 HMR2 head)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (kind == 0)
+        LAUNCH_OK(launch_assemble(ro, ldro, bpose, init_pose, init_betas, init_cam, pose6d, rotmat, betas, cam, cam_t, focal, focal_length,
+                                  img_size, B, st));
+    else
+        LAUNCH_OK(launch_hmr2_finish(ro, ldro, init_pose, init_betas, init_cam, pose6d, rotmat, betas, cam, cam_t, focal, focal_length,
+                                     img_size, B, st));
+    return 0;
+}
+
+int thmr_op_decoder_init(const float* bias, const float* pos, float* x, int32_t B, int32_t E, void* stream) {
+    if (!bias || !pos || !x) return fail(THMR_ERR_INVALID, "decoder_init: null buffer");
+    if (B <= 0 || E <= 0 || (int64_t)B * E > (int64_t)1 << 30) return fail(THMR_ERR_INVALID, "decoder_init: B, E >= 1 and B * E <= 2^30 are required");
+    LAUNCH_OK(launch_decoder_init(bias, pos, x, B, E, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- stand-alone SMPL model ----
+struct thmr_smpl {
+    float* mem = nullptr;
+    int max_batch = 0;
+    size_t o_vt, o_sd, o_pd, o_jr, o_w, o_j19, o_int, o_jt, o_jsd, o_dirs, o_A, o_pf, o_Jtr, o_vposed, o_rot, o_joints, o_xv, o_cnt, total;
+};
+
+int thmr_smpl_create(const thmr_smpl_desc* d, int32_t max_batch, int32_t device, thmr_smpl** out) {
+    if (!d || !out || max_batch < 1) return fail(THMR_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    if (!d->v_template || !d->shapedirs || !d->posedirs || !d->J_regressor || !d->lbs_weights || !d->J19_regressor ||
+        !d->parents || !d->extra_verts || !d->joint_map)
+        return fail(THMR_ERR_INVALID, "thmr_smpl_desc has a null field");
+    HIP_OK(hipSetDevice(device));
+    thmr_smpl* m = new thmr_smpl();
+    m->max_batch = max_batch;
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
+    m->o_vt = take((size_t)NV * 3); m->o_sd = take((size_t)NV * 30); m->o_pd = take((size_t)NP * NV * 3);
+    m->o_jr = take((size_t)NJ * NV); m->o_w = take((size_t)NV * NJ); m->o_j19 = take((size_t)19 * NV);
+    m->o_int = take(128); m->o_jt = take(NJ * 3); m->o_jsd = take(NJ * 30); m->o_dirs = take((size_t)NV * 3 * THMR_LBS_KX);
+    const size_t B = (size_t)max_batch;
+    m->o_A = take(B * NJ * 12); m->o_pf = take(B * THMR_LBS_XF); m->o_Jtr = take(B * NJ * 3); m->o_rot = take(B * NJ * 9);
+    m->o_vposed = take(B * NV * 3);
+    m->o_joints = take(B * 132);
+    m->o_xv = take(B * 63); m->o_cnt = take(B);
+    m->total = off;
+    if (hipMalloc(&m->mem, off * sizeof(float)) != hipSuccess) { delete m; return fail(THMR_ERR_NOMEM, "hipMalloc(smpl) failed"); }
+    if (hipMemset(m->mem + m->o_cnt, 0, B * sizeof(float)) != hipSuccess) { thmr_smpl_destroy(m); return fail(THMR_ERR_HIP, "hipMemset(lbs counters) failed"); }
+    const hipMemcpyKind k = d->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    auto cp = [&](size_t o, const void* src, size_t bytes) { return hipMemcpy(m->mem + o, src, bytes, k) == hipSuccess; };
+    int32_t* ints = reinterpret_cast<int32_t*>(m->mem + m->o_int);
+    bool ok = cp(m->o_vt, d->v_template, sizeof(float) * NV * 3) && cp(m->o_sd, d->shapedirs, sizeof(float) * NV * 30) &&
+              cp(m->o_pd, d->posedirs, sizeof(float) * (size_t)NP * NV * 3) && cp(m->o_jr, d->J_regressor, sizeof(float) * NJ * NV) &&
+              cp(m->o_w, d->lbs_weights, sizeof(float) * NV * NJ) && cp(m->o_j19, d->J19_regressor, sizeof(float) * 19 * NV) &&
+              hipMemcpy(ints, d->parents, sizeof(int32_t) * 24, k) == hipSuccess &&
+              hipMemcpy(ints + 24, d->extra_verts, sizeof(int32_t) * 21, k) == hipSuccess &&
+              hipMemcpy(ints + 48, d->joint_map, sizeof(int32_t) * 25, k) == hipSuccess;
+    const int32_t hips = d->update_hips ? 1 : 0;
+    ok = ok && hipMemcpy(ints + 80, &hips, sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok || launch_lbs_jreg(m->mem + m->o_jr, m->mem + m->o_vt, m->mem + m->o_sd, m->mem + m->o_jt, m->mem + m->o_jsd, nullptr) != 0 ||
+        launch_lbs_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirs, nullptr) != 0 ||
+        hipDeviceSynchronize() != hipSuccess) {
+        thmr_smpl_destroy(m);
+        return fail(THMR_ERR_HIP, "SMPL constant upload failed");
+    }
+    *out = m;
+    return 0;
+}
+
+void thmr_smpl_destroy(thmr_smpl* m) {
+    if (!m) return;
+    if (m->mem) (void)hipFree(m->mem);
+    delete m;
+}
+
+int thmr_smpl_forward(thmr_smpl* m, const float* pose, int32_t pose2rot, const float* betas, int32_t B, float* verts,
+                      float* joints, void* stream) {
+    if (!m || !pose || !betas || !verts) return fail(THMR_ERR_INVALID, "null argument");
+    if (B < 1 || B > m->max_batch) return fail(THMR_ERR_INVALID, "batch outside [1, max_batch]");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float* rot = pose;
+    if (pose2rot) {
+        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * NJ, st));
+        rot = m->mem + m->o_rot;
+    }
+    const int32_t* ints = reinterpret_cast<const int32_t*>(m->mem + m->o_int);
+    LAUNCH_OK(launch_lbs(rot, betas, nullptr, m->mem + m->o_jt, m->mem + m->o_jsd, ints, m->mem + m->o_vt, m->mem + m->o_dirs,
+                         m->mem + m->o_w, m->mem + m->o_j19, ints + 24, ints + 48, ints + 80, m->mem + m->o_A, m->mem + m->o_pf,
+                         m->mem + m->o_Jtr, m->mem + m->o_vposed, verts, joints ? joints : m->mem + m->o_joints, nullptr,
+                         FOCAL / IMG, B, m->mem + m->o_xv, reinterpret_cast<unsigned*>(m->mem + m->o_cnt), st));
+    return 0;
+}
+
+// ---- stand-alone SMPL-H model (csrc/smplh.hip) ----
+struct thmr_smplh {
+    float* mem = nullptr;
+    int max_batch = 0;
+    size_t o_vt, o_sd, o_pd, o_jr, o_w, o_wb, o_int, o_jt, o_jsd, o_dirs, o_dirsb, o_A, o_xf, o_vposed, o_rot, total;
+};
+
+int thmr_smplh_create(const thmr_smplh_desc* d, int32_t max_batch, int32_t device, thmr_smplh** out) {
+    constexpr int HJ = THMR_SMPLH_NJ, HB = THMR_SMPLH_NBODY, HP = THMR_SMPLH_NP;
+    if (!d || !out || max_batch < 1) return fail(THMR_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    if (!d->v_template || !d->shapedirs || !d->posedirs || !d->J_regressor || !d->lbs_weights || !d->parents || !d->extra_verts)
+        return fail(THMR_ERR_INVALID, "thmr_smplh_desc has a null field");
+    HIP_OK(hipSetDevice(device));
+    int32_t par[HJ], ext[21], fold[HJ];
+    if (d->on_device) {
+        HIP_OK(hipMemcpy(par, d->parents, sizeof(par), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(ext, d->extra_verts, sizeof(ext), hipMemcpyDeviceToHost));
+    } else {
+        memcpy(par, d->parents, sizeof(par));
+        memcpy(ext, d->extra_verts, sizeof(ext));
+    }
+    if (par[0] != -1) return fail(THMR_ERR_INVALID, "thmr_smplh_desc.parents[0] must be -1 (the root)");
+    for (int i = 1; i < HJ; ++i)
+        if (par[i] < 0 || par[i] >= i)
+            return fail(THMR_ERR_INVALID, "thmr_smplh_desc.parents[" + std::to_string(i) + "] = " + std::to_string(par[i]) + " is outside [0, " + std::to_string(i) + ")");
+    for (int k = 0; k < 21; ++k)
+        if (ext[k] < 0 || ext[k] >= NV)
+            return fail(THMR_ERR_INVALID, "thmr_smplh_desc.extra_verts[" + std::to_string(k) + "] = " + std::to_string(ext[k]) + " is outside [0, 6890)");
+    // fold[j]: the body joint whose bone matrix joint j has when every hand rotation is the identity.  parents[i] < i keeps the 22 body
+    // joints a chain of their own and gives fold[j] < 22 by induction (one ascending pass)
+    for (int j = 0; j < HJ; ++j) fold[j] = j < HB ? j : fold[par[j]];
+    thmr_smplh* m = new thmr_smplh();
+    m->max_batch = max_batch;
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
+    m->o_vt = take((size_t)NV * 3); m->o_sd = take((size_t)NV * 30); m->o_pd = take((size_t)HP * NV * 3);
+    m->o_jr = take((size_t)HJ * NV); m->o_w = take((size_t)NV * HJ); m->o_wb = take((size_t)NV * THMR_SMPLH_NBODY_PAD);
+    m->o_int = take(192); m->o_jt = take(HJ * 3); m->o_jsd = take(HJ * 30);
+    m->o_dirs = take((size_t)NV * 3 * THMR_SMPLH_KX); m->o_dirsb = take((size_t)NV * 3 * THMR_SMPLH_KXB);
+    const size_t B = (size_t)max_batch;
+    m->o_A = take(B * HJ * 12); m->o_xf = take(B * THMR_SMPLH_KX); m->o_rot = take(B * HJ * 9); m->o_vposed = take(B * NV * 3);
+    m->total = off;
+    if (hipMalloc(&m->mem, off * sizeof(float)) != hipSuccess) { delete m; return fail(THMR_ERR_NOMEM, "hipMalloc(smplh) failed"); }
+    const hipMemcpyKind k = d->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    auto cp = [&](size_t o, const void* src, size_t bytes) { return hipMemcpy(m->mem + o, src, bytes, k) == hipSuccess; };
+    int32_t* ints = reinterpret_cast<int32_t*>(m->mem + m->o_int);      // parents [0, 52) | extra_verts [64, 85) | fold [128, 180)
+    bool ok = cp(m->o_vt, d->v_template, sizeof(float) * NV * 3) && cp(m->o_sd, d->shapedirs, sizeof(float) * NV * 30) &&
+              cp(m->o_pd, d->posedirs, sizeof(float) * (size_t)HP * NV * 3) && cp(m->o_jr, d->J_regressor, sizeof(float) * HJ * NV) &&
+              cp(m->o_w, d->lbs_weights, sizeof(float) * NV * HJ) &&
+              hipMemcpy(ints, par, sizeof(par), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(ints + 64, ext, sizeof(ext), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(ints + 128, fold, sizeof(fold), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok || launch_smplh_jreg(m->mem + m->o_jr, m->mem + m->o_vt, m->mem + m->o_sd, m->mem + m->o_jt, m->mem + m->o_jsd, nullptr) != 0 ||
+        launch_smplh_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirs, 0, nullptr) != 0 ||
+        launch_smplh_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirsb, 1, nullptr) != 0 ||
+        launch_smplh_fold_weights(m->mem + m->o_w, ints + 128, m->mem + m->o_wb, nullptr) != 0 ||
+        hipDeviceSynchronize() != hipSuccess) {
+        thmr_smplh_destroy(m);
+        return fail(THMR_ERR_HIP, "SMPL-H constant upload failed");
+    }
+    *out = m;
+    return 0;
+}
+
+void thmr_smplh_destroy(thmr_smplh* m) {
+    if (!m) return;
+    if (m->mem) (void)hipFree(m->mem);
+    delete m;
+}
+
+int thmr_smplh_forward(thmr_smplh* m, const float* pose, int32_t pose2rot, const float* betas, const float* transl, int32_t body_only,
+                       int32_t B, float* verts, float* joints, void* stream) {
+    if (!m || !pose || !verts) return fail(THMR_ERR_INVALID, "smplh_forward: null argument");
+    if (B < 1 || B > m->max_batch) return fail(THMR_ERR_INVALID, "smplh_forward: batch outside [1, max_batch]");
+    if ((pose2rot != 0 && pose2rot != 1) || (body_only != 0 && body_only != 1))
+        return fail(THMR_ERR_INVALID, "smplh_forward: pose2rot and body_only are 0 or 1");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nj = body_only ? THMR_SMPLH_NBODY : THMR_SMPLH_NJ;
+    const float* rot = pose;
+    if (pose2rot) {
+        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * nj, st));
+        rot = m->mem + m->o_rot;
+    }
+    const int32_t* ints = reinterpret_cast<const int32_t*>(m->mem + m->o_int);
+    SmplhArgs a{};
+    a.rotmat = rot; a.betas = betas; a.transl = transl; a.Jt = m->mem + m->o_jt; a.Jsd = m->mem + m->o_jsd;
+    a.parents = ints; a.extra = ints + 64; a.fold = ints + 128;
+    a.vt = m->mem + m->o_vt; a.dirsT = m->mem + m->o_dirs; a.dirsT_body = m->mem + m->o_dirsb; a.W = m->mem + m->o_w; a.W_body = m->mem + m->o_wb;
+    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_xf; a.vposed = m->mem + m->o_vposed;
+    a.verts = verts; a.joints = joints; a.B = B; a.body_only = body_only;
+    LAUNCH_OK(launch_smplh(a, st));
+    return 0;
+}
+
+int thmr_op_mean_row_dist(const float* a, const float* b, int32_t n_rows_per_item, int32_t row_lo, int32_t row_hi, int32_t B, float* out,
+                          float* workspace, void* stream) {
+    if (!a || !b || !out || !workspace) return fail(THMR_ERR_INVALID, "mean_row_dist: null buffer");
+    if (B < 1 || n_rows_per_item < 1 || row_lo < 0 || row_hi <= row_lo || row_hi > n_rows_per_item)
+        return fail(THMR_ERR_INVALID, "mean_row_dist: B >= 1 and 0 <= row_lo < row_hi <= n_rows_per_item are required");
+    if ((int64_t)B * n_rows_per_item > ((int64_t)1 << 29))
+        return fail(THMR_ERR_INVALID, "mean_row_dist: B * n_rows_per_item <= 2^29 is required");
+    LAUNCH_OK(launch_mean_row_dist(a, b, n_rows_per_item, row_lo, row_hi, B, out, workspace, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- the forward value of the loss (stateless; csrc/loss.hip) ----
+int thmr_val_loss(const thmr_val_loss_desc* d, const thmr_val_loss_in* in, int32_t B, const thmr_val_loss_out* out, float* workspace,
+                  void* stream) {
+    if (!d || !in || !out) return fail(THMR_ERR_INVALID, "val_loss: null descriptor, input or output struct");
+    if (!in->pred_keypoints_2d || !in->pred_keypoints_3d || !in->pred_rotmat || !in->pred_betas || !in->gt_keypoints_2d ||
+        !in->gt_keypoints_3d || !in->gt_pose || !in->gt_betas || !in->has_global_orient || !in->has_body_pose || !in->has_betas)
+        return fail(THMR_ERR_INVALID, "val_loss: null input buffer");
+    if (B < 1 || B > (1 << 24)) return fail(THMR_ERR_INVALID, "val_loss: 1 <= B <= 2^24 is required");
+    if (d->mode != THMR_VAL_LOSS_PLAIN && d->mode != THMR_VAL_LOSS_LOOSE)
+        return fail(THMR_ERR_INVALID, "val_loss: mode is THMR_VAL_LOSS_PLAIN (0) or THMR_VAL_LOSS_LOOSE (1)");
+    if (d->mode == THMR_VAL_LOSS_LOOSE && (!in->valid_3d || !in->kp2d_thresh || !in->angle_thresh))
+        return fail(THMR_ERR_INVALID, "val_loss: the loose mode needs valid_3d, kp2d_thresh and angle_thresh");
+    if (d->pelvis_id < 0 || d->pelvis_id >= 44) return fail(THMR_ERR_INVALID, "val_loss: pelvis_id outside [0, 44)");
+    if (d->gt_pose_is_rotmat != 0 && d->gt_pose_is_rotmat != 1) return fail(THMR_ERR_INVALID, "val_loss: gt_pose_is_rotmat is 0 or 1");
+    if (!workspace) return fail(THMR_ERR_INVALID, "val_loss: null workspace");
+    if (reinterpret_cast<uintptr_t>(in->gt_keypoints_3d) % 16 != 0 || reinterpret_cast<uintptr_t>(in->pred_keypoints_2d) % 8 != 0)
+        return fail(THMR_ERR_INVALID, "val_loss: gt_keypoints_3d must be 16-byte and pred_keypoints_2d 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out->running) % 8 != 0) return fail(THMR_ERR_INVALID, "val_loss: running (7 doubles) must be 8-byte aligned");
+    ValLossArgs a{};
+    a.pred_kp2d = in->pred_keypoints_2d; a.pred_kp3d = in->pred_keypoints_3d; a.pred_rotmat = in->pred_rotmat; a.pred_betas = in->pred_betas;
+    a.gt_kp2d = in->gt_keypoints_2d; a.gt_kp3d = in->gt_keypoints_3d; a.gt_pose = in->gt_pose; a.gt_betas = in->gt_betas;
+    a.has_global_orient = in->has_global_orient; a.has_body_pose = in->has_body_pose; a.has_betas = in->has_betas;
+    a.valid_3d = in->valid_3d; a.kp2d_thresh = in->kp2d_thresh; a.angle_thresh = in->angle_thresh;
+    a.losses = out->losses; a.per_item = out->per_item; a.running = out->running;
+    if (d->mode == THMR_VAL_LOSS_LOOSE) {
+        a.kp2d_err = out->kp2d_err; a.angle_err = out->angle_err; a.valid2d = out->valid2d; a.weak2d = out->weak2d;
+        a.valid_rot = out->valid_rot; a.weak_rot = out->weak_rot; a.conf2d_used = out->conf2d_used; a.conf3d_used = out->conf3d_used;
+        a.has_betas_used = out->has_betas_used;
+    }
+    a.partial = workspace;
+    a.w[0] = d->w_keypoints_2d; a.w[1] = d->w_keypoints_3d; a.w[2] = d->w_global_orient; a.w[3] = d->w_body_pose; a.w[4] = d->w_betas;
+    a.loose_weight = (float)d->loose_weight;
+    a.B = B; a.pelvis_id = d->pelvis_id; a.mode = d->mode; a.gt_pose_is_rotmat = d->gt_pose_is_rotmat;
+    LAUNCH_OK(launch_val_loss(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_op_token_ce(const float* x, const int32_t* target, int32_t rows, float* out, float* workspace, void* stream) {
+    if (!x || !target || !out || !workspace) return fail(THMR_ERR_INVALID, "token_ce: null buffer");
+    if (rows < 1) return fail(THMR_ERR_INVALID, "token_ce: rows >= 1 is required");
+    if (reinterpret_cast<uintptr_t>(x) % 16 != 0) return fail(THMR_ERR_INVALID, "token_ce: x must be 16-byte aligned");
+    LAUNCH_OK(launch_token_ce(x, target, rows, out, workspace, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- evaluation metrics (stateless) ----
+int thmr_eval_pose(const float* pred_j, const float* gt_j, int32_t nj, int32_t gt_stride, const int32_t* kp, int32_t nkp,
+                   int32_t pelvis_ind, int32_t pelvis_mode, const float* pred_v, const float* gt_v, int32_t nv, int32_t B,
+                   float* mpjpe, float* re, float* pve, float* pelv, void* stream) {
+    if (!pred_j || !gt_j || !kp || !mpjpe || !re || !pelv) return fail(THMR_ERR_INVALID, "null buffer");
+    if (nkp < 1 || nkp > 64 || gt_stride < 3 || B < 1 || pelvis_ind < 0 || pelvis_ind >= nj || nj < 3)
+        return fail(THMR_ERR_INVALID, "bad evaluator arguments (1 <= n_kp <= 64, gt_stride >= 3)");
+    if (pelvis_mode != 0 && pelvis_mode != 1) return fail(THMR_ERR_INVALID, "bad evaluator arguments (pelvis_mode is 0 or 1)");
+    if (pred_v && gt_v && pve && nv < 1) return fail(THMR_ERR_INVALID, "bad evaluator arguments (PVE needs n_verts >= 1)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    LAUNCH_OK(launch_eval_pose(pred_j, gt_j, nj, gt_stride, kp, nkp, pelvis_ind, pelvis_mode, mpjpe, re, pelv, B, st));
+    if (pred_v && gt_v && pve) LAUNCH_OK(launch_eval_pve(pred_v, gt_v, pelv, nv, pve, B, st));
+    return 0;
+}
+
+int thmr_regress_joints(const float* J, const float* verts, int32_t nj, int32_t nv, int32_t B, float* out, void* stream) {
+    if (!J || !verts || !out || nj < 1 || nv < 1 || B < 1) return fail(THMR_ERR_INVALID, "bad argument");
+    LAUNCH_OK(launch_regress_joints(J, verts, nj, nv, out, B, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // extern "C"
