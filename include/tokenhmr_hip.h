@@ -44,7 +44,8 @@ typedef enum {
     THMR_ERR_INVALID = -1,      /* bad argument / shape / missing tensor */
     THMR_ERR_HIP = -2,          /* a HIP runtime call failed */
     THMR_ERR_STATE = -3,        /* call order violated (e.g. forward before weights are finalised) */
-    THMR_ERR_NOMEM = -4
+    THMR_ERR_NOMEM = -4,
+    THMR_ERR_UNSUPPORTED = -5   /* a well-formed input of a kind this library does not handle (thmr_jpeg_*: the message names what was found) */
 } thmr_status;
 
 typedef struct thmr_engine thmr_engine;
@@ -771,6 +772,74 @@ int thmr_set_vit_gemm(thmr_engine* e, int32_t mode, void* stream);
 int thmr_get_vit_gemm(thmr_engine* e);
 int thmr_prof_enable(thmr_engine* e, int32_t on);
 int thmr_prof_collect(thmr_engine* e, thmr_prof_entry* entries /*[THMR_PROF_NUM]*/, int32_t reset);
+
+/* Baseline JPEG decoding for the evaluation datasets (csrc/jpeg.hip, jpeg_host.h, jpeg_math.h): new symbols under ABI 5.
+ * A hybrid: the host parses the markers and decodes the Huffman stream — the sequential part — into quantised coefficient blocks, only
+ * for the MCU rows and blocks a WINDOW of the frame needs; the device dequantises, runs the inverse DCT, upsamples the chroma and converts
+ * the colour, for that window only, straight into the (win_h, win_w, 3) uint8 buffer thmr_cropper_run_frames takes.  The arithmetic is
+ * libjpeg's default pipeline restated in integers, bit for bit: the JDCT_ISLOW inverse DCT (13-bit constants, PASS1_BITS 2), h2v1 / h2v2
+ * "fancy" triangle upsampling with the edges replicated at the TRUE downsampled component size (plain replication where that width is
+ * at most 2, as libjpeg chooses), and the 16-bit fixed-point YCbCr -> RGB tables.
+ *   supported     SOF0 (baseline sequential DCT), Huffman, 8 bits, ONE interleaved scan; 1 component (grey, replicated to 3 channels) or
+ *                 3 (YCbCr) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; DRI / RSTn; 0xFF00 stuffing; up to four Huffman and four
+ *                 quantisation tables, redefined between markers; APPn / COM skipped
+ *   unsupported   THMR_ERR_UNSUPPORTED, the message names what was found: every other SOF (progressive, extended, lossless, arithmetic),
+ *                 DAC, another sample precision, 4 components, Adobe APP14 transform 0 or component ids 'R','G','B' with 3 components,
+ *                 a scan that does not hold every component (multi-scan), other sampling factors, a side above 32767, height 0 (DNL)
+ *   malformed     THMR_ERR_INVALID: never a read outside [data, data + len), never an unbounded loop (every Huffman symbol is at most
+ *                 16 + 15 bits, and a block that consumed bits past the last entropy-coded byte ends the decode)
+ * The host entry points need no device, are re-entrant and keep no state; their message is in thmr_last_error(NULL) (thread-local). */
+typedef struct thmr_jpeg_info {
+    int32_t height, width, components;  /* components: 1 or 3 where supported, else what the frame header says */
+    int32_t h_samp, v_samp;             /* luma sampling factors (1,1) (2,1) (2,2); (1,1) for grey */
+    int32_t restart_interval;           /* MCUs between RSTn markers, 0 = none */
+    int32_t supported;                  /* 1, or 0 with the reason in thmr_last_error(NULL) */
+    int32_t reserved;
+} thmr_jpeg_info;
+/* What thmr_jpeg_entropy_decode kept.  Component c's blocks are the rectangle [bx0, bx0 + bw) x [by0, by0 + bh) of its 8x8-block grid,
+ * stored row-major from block index coef_block[c] of the coefficient buffer, 64 int16 each: QUANTISED values in natural (row-major,
+ * zig-zag undone) order.  The rectangles cover the window's samples, for sub-sampled chroma widened by the one sample on each side that
+ * fancy upsampling reads, clipped to the component's true size. */
+typedef struct thmr_jpeg_plan {
+    int32_t height, width, components, h_samp, v_samp;
+    int32_t win_x0, win_y0, win_w, win_h;       /* the window the plan was made for */
+    int32_t mcu_row0, mcu_rows_kept;            /* MCU rows that hold kept blocks */
+    int32_t mcu_rows_decoded;                   /* MCU rows entropy-decoded, those above the window (decoded and discarded) included */
+    int32_t bx0[3], by0[3], bw[3], bh[3], coef_block[3];
+    int32_t n_blocks;                           /* blocks in the coefficient buffer */
+    uint16_t quant[3][64];                      /* each component's quantisation table, natural order */
+} thmr_jpeg_plan;
+int thmr_jpeg_probe(const uint8_t* data, size_t len, thmr_jpeg_info* info);
+/* window: {x0, y0, w, h} inside the frame (an empty one keeps nothing), NULL = the whole frame.  coef NULL: only the plan is filled
+ * (the size: n_blocks * 64 int16) and nothing is entropy-decoded; otherwise coef_capacity_blocks >= plan->n_blocks blocks are written.
+ * MCU rows above the window are decoded and discarded; decoding stops after the last MCU row the window needs. */
+int thmr_jpeg_entropy_decode(const uint8_t* data, size_t len, const int32_t* window, int16_t* coef, int64_t coef_capacity_blocks,
+                             thmr_jpeg_plan* plan);
+/* The full decode of a window on the CPU, with the kernels' arithmetic (shared __host__ __device__ functions, csrc/jpeg_math.h):
+ * out (win_h, win_w, 3) uint8 host, row_stride >= win_w * 3 bytes per row, bytes beyond win_w * 3 of a row untouched; bgr = 1 writes
+ * B, G, R (cv2.imread), 0 R, G, B (PIL). */
+int thmr_jpeg_decode_host(const uint8_t* data, size_t len, const int32_t* window, int32_t bgr, uint8_t* out, int64_t row_stride);
+/* The device half.  The handle owns two grow-only sets of staging (pinned host + device), used alternately, and device scratch for the
+ * component planes.  thmr_jpeg_decode_batch decodes n items of n sizes and formats with ONE packed upload and TWO launches (inverse
+ * DCT of every block of the batch; upsampling + colour of every window).  A staging set is rewritten only after the event behind its
+ * last use — two calls back — has completed; beyond that the call synchronises only when a buffer grows (never inside a
+ * stream capture: THMR_ERR_STATE then — run the call once at those sizes first; a captured call keeps reading its staging set, so
+ * give it a handle of its own).  Every argument is checked before the handle and the handle before any HIP call: n <= 0, a null table,
+ * and per item (the message names its index) a null plan / coefficients, a window outside the frame or other than the plan's frame,
+ * row_stride < win_w * 3, a null out_dev with a non-empty window, a plan whose block rectangles do not cover the window or lie outside
+ * the component.  Bytes of out_dev beyond win_w * 3 of a row are not written. */
+typedef struct thmr_jpeg_item {
+    const int16_t* coef;                /* host: plan->n_blocks * 64 int16 */
+    const thmr_jpeg_plan* plan;         /* host */
+    int32_t win_x0, win_y0, win_w, win_h;
+    uint8_t* out_dev;                   /* device: (win_h, win_w, 3) uint8 */
+    int64_t row_stride;                 /* bytes per output row, >= win_w * 3 */
+} thmr_jpeg_item;
+typedef struct thmr_jpeg thmr_jpeg;
+int  thmr_jpeg_create(int32_t device, thmr_jpeg** out);
+void thmr_jpeg_destroy(thmr_jpeg* j);
+const char* thmr_jpeg_last_error(const thmr_jpeg* j);
+int  thmr_jpeg_decode_batch(thmr_jpeg* j, const thmr_jpeg_item* items_host, int32_t n, int32_t bgr, void* stream);
 
 #ifdef __cplusplus
 }

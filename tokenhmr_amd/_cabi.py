@@ -88,6 +88,26 @@ class FrameCrop(C.Structure):
                 ("truncate", C.c_double)]
 
 
+class JpegInfo(C.Structure):
+    """thmr_jpeg_info."""
+    _fields_ = [(n, C.c_int32) for n in ("height", "width", "components", "h_samp", "v_samp", "restart_interval", "supported", "reserved")]
+
+
+class JpegPlan(C.Structure):
+    """thmr_jpeg_plan: what thmr_jpeg_entropy_decode kept."""
+    _fields_ = [(n, C.c_int32) for n in ("height", "width", "components", "h_samp", "v_samp", "win_x0", "win_y0", "win_w", "win_h", "mcu_row0",
+                                         "mcu_rows_kept", "mcu_rows_decoded")] + \
+               [(n, C.c_int32 * 3) for n in ("bx0", "by0", "bw", "bh", "coef_block")] + [("n_blocks", C.c_int32), ("quant", (C.c_uint16 * 64) * 3)]
+
+
+class JpegItem(C.Structure):
+    """thmr_jpeg_item: one item of thmr_jpeg_decode_batch."""
+    _fields_ = [("coef", C.c_void_p), ("plan", C.POINTER(JpegPlan)), ("win_x0", C.c_int32), ("win_y0", C.c_int32), ("win_w", C.c_int32),
+                ("win_h", C.c_int32), ("out_dev", C.c_void_p), ("row_stride", C.c_int64)]
+
+
+ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM, ERR_UNSUPPORTED = -1, -2, -3, -4, -5      # header: thmr_status
+
 RENDER_MAX_LIGHTS = 16
 # thmr_render_desc.mode / thmr_render_light.type (header: THMR_RENDER_* / THMR_LIGHT_*)
 RENDER_PER_IMAGE, RENDER_ONE_IMAGE = 0, 1
@@ -170,6 +190,10 @@ LOSS_SYMBOLS = ("thmr_val_loss", "thmr_op_token_ce")
 # a batch of crops from a table of frames (csrc/crop.hip): a new symbol under ABI 5 as well
 FRAMES_SYMBOLS = ("thmr_cropper_run_frames",)
 
+# baseline JPEG decoding (csrc/jpeg.hip): new symbols under ABI 5 as well
+JPEG_SYMBOLS = ("thmr_jpeg_probe", "thmr_jpeg_entropy_decode", "thmr_jpeg_decode_host", "thmr_jpeg_create", "thmr_jpeg_destroy",
+                "thmr_jpeg_last_error", "thmr_jpeg_decode_batch")
+
 
 def load(exp=None):
     """The shipped library, or (exp=True, or exp=None with THMR_LIB=exp in the environment) the experiments build.
@@ -205,7 +229,7 @@ def load(exp=None):
     older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
     # a build loaded by path may also predate thmr_renderer_sheet / thmr_debug_vit_plan (added without an ABI change: new symbols, no layout touched)
     missing = [s for s in declared_symbols() if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
-               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS + FRAMES_SYMBOLS)]
+               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS + FRAMES_SYMBOLS + JPEG_SYMBOLS)]
     if missing:
         raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -288,6 +312,16 @@ def load(exp=None):
     lib.thmr_cropper_run.argtypes = [vp, vp, i32, i32, i64, C.POINTER(CropDesc), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
     if hasattr(lib, "thmr_cropper_run_frames"):          # the frame-table entry (added without an ABI change)
         lib.thmr_cropper_run_frames.argtypes = [vp, C.POINTER(FrameCrop), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
+    if hasattr(lib, "thmr_jpeg_probe"):                  # baseline JPEG decoding (added without an ABI change)
+        lib.thmr_jpeg_probe.argtypes = [vp, sz, C.POINTER(JpegInfo)]
+        lib.thmr_jpeg_entropy_decode.argtypes = [vp, sz, C.POINTER(i32), vp, i64, C.POINTER(JpegPlan)]
+        lib.thmr_jpeg_decode_host.argtypes = [vp, sz, C.POINTER(i32), i32, vp, i64]
+        lib.thmr_jpeg_create.argtypes = [i32, C.POINTER(vp)]
+        lib.thmr_jpeg_destroy.argtypes = [vp]
+        lib.thmr_jpeg_destroy.restype = None
+        lib.thmr_jpeg_last_error.argtypes = [vp]
+        lib.thmr_jpeg_last_error.restype = C.c_char_p
+        lib.thmr_jpeg_decode_batch.argtypes = [vp, C.POINTER(JpegItem), i32, i32, vp]
     lib.thmr_renderer_create.argtypes = [i32, vp, i32, i32, C.POINTER(vp)]
     lib.thmr_renderer_destroy.argtypes = [vp]
     lib.thmr_renderer_destroy.restype = None
@@ -310,7 +344,7 @@ def load(exp=None):
         fn = getattr(lib, name)
         if name not in ("thmr_build_info", "thmr_last_error", "thmr_destroy", "thmr_smpl_destroy", "thmr_smplh_destroy", "thmr_cropper_destroy",
                         "thmr_cropper_last_error", "thmr_collective_last_error", "thmr_renderer_destroy",
-                        "thmr_renderer_last_error"):
+                        "thmr_renderer_last_error", "thmr_jpeg_destroy", "thmr_jpeg_last_error"):
             fn.restype = C.c_int
     if lib.thmr_abi_version() != ABI_VERSION and not older:
         raise RuntimeError("libtokenhmr_hip.so ABI version mismatch")

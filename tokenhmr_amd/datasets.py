@@ -25,6 +25,9 @@ Departures from the reference, stated:
   * Images are decoded by `imread(path) -> (H, W, 3) uint8 BGR`: cv2.imread(path, IMREAD_COLOR | IMREAD_IGNORE_ORIENTATION) where cv2
     imports, else PIL (no EXIF transpose, convert('RGB'), channel-reversed), else ImportError.  Two JPEG decoders (libjpeg versions, IDCT
     choices) may differ by a grey level on some pixels; bit-parity with the reference's crops holds for the same decoded frame.
+    That is decode="host", the default.  decode="device" (opt-in) leaves the decode threads only the marker parsing and Huffman decoding
+    of a baseline JPEG file, for the window the item's crop reads, and finishes it on the device (tokenhmr_amd/jpeg.py) with libjpeg's
+    default arithmetic bit for bit; any other file goes to `imread`, that item alone.
 There is no CPU fallback for the device half.
 """
 import os
@@ -38,6 +41,7 @@ import torch
 from . import preprocess as PP
 
 MAX_WORKERS = 16      # decode threads: a fixed cap, never derived from the machine's CPU count
+DECODE_MODES = ("host", "device")
 
 
 def dataset_eval_config(path):
@@ -105,9 +109,13 @@ class _EvalDataset:
 
     kind = ""
 
-    def _init_common(self, cfg, dataset_file, img_dir, train, device, imread, cropper, smpl_male, smpl_female):
+    def _init_common(self, cfg, dataset_file, img_dir, train, device, imread, cropper, smpl_male, smpl_female, decode="host"):
         if train:
             raise NotImplementedError("train=True: the device datasets are evaluation-only (augmentation stays with the reference)")
+        if decode not in DECODE_MODES:
+            raise ValueError(f"decode={decode!r}: the decoders are {DECODE_MODES}")
+        self.decode, self._jpeg = decode, None
+        self.decode_stats = {"device": 0, "fallback": 0, "coef_bytes": 0}
         self.train, self.cfg = False, cfg
         self.img_size = int(cfg.MODEL.IMAGE_SIZE)
         self.mean_rgb, self.std_rgb = tuple(cfg.MODEL.IMAGE_MEAN), tuple(cfg.MODEL.IMAGE_STD)
@@ -178,6 +186,41 @@ class _EvalDataset:
             raise ValueError(f"imread({path!r}) must give an (H, W, 3) uint8 BGR array, got {fr.dtype} {fr.shape}")
         return fr
 
+    def _item_window(self, i, H, W):
+        """The window of its (H, W) frame that item i's crop can touch — what `warp_frames` uploads of it — or the whole frame with
+        windows=False; (0, 0, 0, 0) when every output pixel is border."""
+        if self.windows is False:
+            return (0, 0, W, H)
+        s, c, P = self.scale[i], self.center[i], self.img_size
+        b = PP.expand_to_aspect_ratio(s * 200, target_aspect_ratio=self.bbox_shape).max()
+        w = PP.source_window(PP.gen_trans_from_patch_cv(c[0], c[1], b, b, P, P, 1.0, 0), P, H, W, 0.0, 3.0)
+        return (0, 0, 0, 0) if w is None else w
+
+    def read_item(self, i):
+        """What the decode threads produce for item i.  decode="host": the decoded frame (read_frame).  decode="device": the file's
+        bytes are read, probed and entropy-decoded for the item's window only (tokenhmr_amd.jpeg.entropy_decode: ctypes releases the
+        GIL) -> a PlannedItem the batch call finishes on the device; a file that is no JPEG, or a JPEG of a kind the decoder does not
+        handle, is decoded by `imread` instead (that item alone, counted in decode_stats["fallback"]); a malformed JPEG raises what an
+        unreadable file raises."""
+        if self.decode == "host":
+            return self.read_frame(i)
+        from . import jpeg as J
+        path = self._names([i])[1][0]
+        try:
+            with open(path, "rb") as f:
+                data = f.read()
+        except OSError:
+            raise IOError("Fail to read %s" % path) from None
+        if data[:2] == b"\xff\xd8":
+            try:
+                info = J.probe(data)
+                return J.entropy_decode(data, self._item_window(int(i), info["height"], info["width"]))
+            except J.JpegUnsupported:
+                pass
+            except J.JpegError:
+                raise IOError("Fail to read %s" % path) from None
+        return self.read_frame(i)
+
     def host_batch(self, idxs, sizes):
         """Everything of a batch but the crops and the meshes, as numpy arrays in the dtypes default_collate gives the reference's
         items: `sizes` is the (H, W) of each item's frame.  Returns (arrays, affines (n,2,3), strings)."""
@@ -222,6 +265,37 @@ class _EvalDataset:
             self._cropper = PP.Cropper(self.device)
             self.device = self._cropper.device
         return self._cropper
+
+    @property
+    def jpeg_decoder(self):
+        if self._jpeg is None:
+            from .jpeg import JpegDecoder
+            self._jpeg = JpegDecoder(self.cropper.device)
+        return self._jpeg
+
+    def _crops_from_items(self, idxs, items, trans, extra):
+        """decode="device": the windows of the entropy-decoded items are finished on the device by ONE thmr_jpeg_decode_batch, the
+        windows of the items `imread` decoded are uploaded, and one thmr_cropper_run_frames crops them all — on the current stream."""
+        dev = self.cropper.device
+        planned = [k for k, it in enumerate(items) if not isinstance(it, np.ndarray)]
+        wins, sizes, wdev = [None] * len(items), [None] * len(items), [None] * len(items)
+        if planned:
+            outs = self.jpeg_decoder.decode_planned([items[k] for k in planned], bgr=True)
+            for k, o in zip(planned, outs):
+                wins[k], sizes[k], wdev[k] = items[k].window, items[k].size, o
+            self.decode_stats["coef_bytes"] += self.jpeg_decoder.last_coef_bytes
+        for k, fr in enumerate(items):
+            if isinstance(fr, np.ndarray):
+                H, W = fr.shape[:2]
+                x0, y0, w, h = self._item_window(idxs[k], H, W)
+                wins[k], sizes[k] = (x0, y0, w, h), (H, W)
+                if w * h:
+                    wdev[k] = torch.from_numpy(np.ascontiguousarray(fr[y0:y0 + h, x0:x0 + w])).to(dev)
+        self.decode_stats["device"] += len(planned)
+        self.decode_stats["fallback"] += len(items) - len(planned)
+        img = self.cropper.warp_device_windows(wdev, sizes, wins, trans, None, truncate=3.0, patch=self.img_size, mean=self.mean_rgb,
+                                               std=self.std_rgb, is_bgr=True)
+        return img, torch.from_numpy(extra).to(dev)
 
     def smpl_constants(self, g):
         """The SMPL constants of gender g (0 male, 1 female): those passed as smpl_male= / smpl_female=, else read — host only — from
@@ -272,12 +346,12 @@ class _EvalDataset:
         return verts, kp3d
 
     def batch(self, idxs, frames=None):
-        """One collated batch of the given items, on the device, enqueued on the current stream.  `frames`: their decoded frames,
-        where the caller has them already (the iterator's decode threads); read here otherwise."""
+        """One collated batch of the given items, on the device, enqueued on the current stream.  `frames`: what `read_item` gives
+        for them, where the caller has it already (the iterator's decode threads); read here otherwise."""
         idxs = [int(i) for i in idxs]
         if frames is None:
-            frames = [self.read_frame(i) for i in idxs]
-        a, trans, strings = self.host_batch(idxs, [f.shape[:2] for f in frames])
+            frames = [self.read_item(i) for i in idxs]
+        a, trans, strings = self.host_batch(idxs, [f.shape[:2] if isinstance(f, np.ndarray) else f.size for f in frames])
         pack = _Pack()
         for k, v in a.items():
             if isinstance(v, dict):
@@ -289,8 +363,11 @@ class _EvalDataset:
         if genders is not None:
             pack.add("_rows_m", np.nonzero(genders != 1)[0].astype(np.int64))
             pack.add("_rows_f", np.nonzero(genders == 1)[0].astype(np.int64))
-        img, extra = self.cropper.warp_frames(frames, trans, None, truncate=3.0, patch=self.img_size, mean=self.mean_rgb, std=self.std_rgb,
-                                              is_bgr=True, windows=self.windows, extra=pack.bytes())
+        if self.decode == "device":
+            img, extra = self._crops_from_items(idxs, frames, trans, pack.bytes())
+        else:
+            img, extra = self.cropper.warp_frames(frames, trans, None, truncate=3.0, patch=self.img_size, mean=self.mean_rgb, std=self.std_rgb,
+                                                  is_bgr=True, windows=self.windows, extra=pack.bytes())
         batch = {"img": img}
         for k, v in pack.views(extra).items():
             if isinstance(k, tuple):
@@ -356,7 +433,7 @@ def _produce(ds, groups, prefetch, pool, q, stop, side):
         for k in range(len(groups)):
             for j in range(k, min(k + ahead, len(groups))):
                 if j not in futs:
-                    futs[j] = [pool.submit(ds.read_frame, i) for i in groups[j]]
+                    futs[j] = [pool.submit(ds.read_item, i) for i in groups[j]]
             if stop.is_set():
                 return
             frames = [f.result() for f in futs.pop(k)]
@@ -449,8 +526,8 @@ class ImageDataset(_EvalDataset):
     kind = "ImageDataset"
 
     def __init__(self, cfg, dataset_file, img_dir, train=False, prune=None, dataset_name="", device="cuda:0", imread=None, cropper=None,
-                 smpl_male=None, smpl_female=None, windows=True, **kwargs):
-        self._init_common(cfg, dataset_file, img_dir, train, device, imread, cropper, smpl_male, smpl_female)
+                 smpl_male=None, smpl_female=None, windows=True, decode="host", **kwargs):
+        self._init_common(cfg, dataset_file, img_dir, train, device, imread, cropper, smpl_male, smpl_female, decode)
         self.dataset_name, self.windows = dataset_name, windows
         n = len(self.imgname)
         num_pose = 3 * (int(cfg.SMPL.NUM_BODY_JOINTS) + 1)
@@ -491,8 +568,8 @@ class EMDBDataset(_EvalDataset):
     kind = "EMDBDataset"
 
     def __init__(self, cfg, dataset_file, img_dir, train=False, prune=None, device="cuda:0", imread=None, cropper=None, smpl_male=None,
-                 smpl_female=None, windows=True, **kwargs):
-        self._init_common(cfg, dataset_file, img_dir, train, device, imread, cropper, smpl_male, smpl_female)
+                 smpl_female=None, windows=True, decode="host", **kwargs):
+        self._init_common(cfg, dataset_file, img_dir, train, device, imread, cropper, smpl_male, smpl_female, decode)
         self.windows = windows
         try:
             self.extra_info = self.data["extra_info"]
@@ -517,9 +594,14 @@ class EMDBDataset(_EvalDataset):
 _TYPES = {"ImageDataset": ImageDataset, "EMDBDataset": EMDBDataset}
 
 
-def create_dataset(cfg, dataset_cfg, train=False, device="cuda:0", imread=None, **kwargs):
+def create_dataset(cfg, dataset_cfg, train=False, device="cuda:0", imread=None, decode="host", **kwargs):
     """lib/datasets/__init__.py:17-26 for the two evaluation types: dispatches on dataset_cfg.TYPE and passes the node's other keys,
-    lower-cased, to the constructor (dataset_file, img_dir; keypoint_list, use_hips ride along unused, as in the reference)."""
+    lower-cased, to the constructor (dataset_file, img_dir; keypoint_list, use_hips ride along unused, as in the reference).
+    decode="host" (the default): `imread` decodes every frame on the host.  decode="device": baseline JPEG files are only
+    entropy-decoded on the host, for the window their crop reads, and finished on the device (tokenhmr_amd.jpeg); other files fall back
+    to `imread` one by one; `dataset.decode_stats` counts both and the coefficient bytes uploaded."""
+    if decode not in DECODE_MODES:
+        raise ValueError(f"decode={decode!r}: the decoders are {DECODE_MODES}")
     if train:
         raise NotImplementedError("train=True: the device datasets are evaluation-only (augmentation stays with the reference)")
     t = dataset_cfg["TYPE"] if "TYPE" in dataset_cfg else None
@@ -528,4 +610,4 @@ def create_dataset(cfg, dataset_cfg, train=False, device="cuda:0", imread=None, 
     kw = {k.lower(): v for k, v in dataset_cfg.items()}
     kw.pop("type")
     kw.update(kwargs)
-    return _TYPES[t](cfg, train=train, device=device, imread=imread, **kw)
+    return _TYPES[t](cfg, train=train, device=device, imread=imread, decode=decode, **kw)

@@ -269,6 +269,47 @@ class Cropper:
             raise _cabi.EngineError(f"thmr_cropper_run_frames error {rc}: {self.lib.thmr_cropper_last_error(self.h).decode()}")
         return out if extra is None else (out, extra_dev)
 
+    def warp_device_windows(self, windows_dev, frame_sizes, wins, trans, sigmas=None, truncate=3.0, patch=256, mean=DEFAULT_MEAN,
+                            std=DEFAULT_STD, is_bgr=True, out=None, row_strides=None):
+        """`warp_frames` for windows that are ALREADY on the device (tokenhmr_amd.jpeg.JpegDecoder writes them there): windows_dev[i] a
+        contiguous uint8 device tensor holding item i's (win_h, win_w, 3) window with row_strides[i] bytes per row (default win_w * 3),
+        frame_sizes[i] the (H, W) of its full frame, wins[i] = (x0, y0, w, h) where the window sits in it (None or an empty window: every
+        output pixel is border, windows_dev[i] may be None).  Nothing is staged or uploaded but the descriptors; the kernels are enqueued
+        on the current stream, behind whatever filled the windows there.  Item i is bit-equal to `warp_frames` on the same pixels."""
+        n = len(windows_dev)
+        trans = np.asarray(trans, dtype=np.float64).reshape(-1, 6)
+        if n == 0 or trans.shape[0] != n or len(frame_sizes) != n or len(wins) != n:
+            raise ValueError("warp_device_windows needs one frame size, one window and one affine per item and at least one item")
+        sig = np.zeros(n) if sigmas is None else np.asarray(sigmas, dtype=np.float64).reshape(n)
+        items = (_cabi.FrameCrop * n)()
+        for i in range(n):
+            x0, y0, w, h = (0, 0, 0, 0) if wins[i] is None else tuple(int(v) for v in wins[i])
+            stride = int(row_strides[i]) if row_strides is not None else w * 3
+            t = windows_dev[i]
+            if w * h:
+                if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.device != self.device or not t.is_contiguous():
+                    raise ValueError(f"item {i}: the window must be a contiguous uint8 tensor on {self.device}")
+                if t.numel() < (h - 1) * stride + w * 3:
+                    raise ValueError(f"item {i}: the tensor holds {t.numel()} bytes, the window needs {(h - 1) * stride + w * 3}")
+            it = items[i]
+            it.win_dev = t.data_ptr() if w * h else None
+            it.row_stride, it.H, it.W = stride, int(frame_sizes[i][0]), int(frame_sizes[i][1])
+            it.win_x0, it.win_y0, it.win_w, it.win_h = x0, y0, w, h
+            it.M[:] = trans[i].tolist()
+            it.sigma, it.truncate = float(sig[i]), float(truncate)
+        m = (C.c_float * 3)(*[np.float32(255.0 * v) for v in mean])
+        s = (C.c_float * 3)(*[np.float32(255.0 * v) for v in std])
+        if out is None:
+            out = torch.empty(n, 3, patch, patch, device=self.device, dtype=torch.float32)
+        elif out.shape != (n, 3, patch, patch) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous (n,3,patch,patch) float32 tensor on the cropper's device")
+        with torch.cuda.device(self.device):
+            rc = self.lib.thmr_cropper_run_frames(self.h, items, n, int(patch), int(bool(is_bgr)), m, s, C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise _cabi.EngineError(f"thmr_cropper_run_frames error {rc}: {self.lib.thmr_cropper_last_error(self.h).decode()}")
+        return out
+
 
 class ViTDetDataset:
     """Mirror of lib/datasets/vitdet_dataset.py:16-88 (inference only).  cfg needs MODEL.IMAGE_SIZE / IMAGE_MEAN / IMAGE_STD and
