@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY — a SECOND, independently derived SMPL forward (fp64 numpy), used to bound the
 unpinned SMPL stage (smplx==0.1.28 is absent; `oracle.tokenhmr_oracle.smpl_forward` restates smplx's lbs.py).
 
-It shares no code and no algebra with `oracle.tokenhmr_oracle.smpl_forward` or `csrc/lbs.hip`.  Those two follow smplx's
+It shares no code and no algebra with `oracle.tokenhmr_oracle.smpl_forward` or `csrc/body_model.hip`.  Those two follow smplx's
 formulation: relative transforms chained in array order, `A_j = G_j - [0 | G_j J_j]` (the rest joint removed by a
 subtraction), joints through precomputed `J_template / J_shapedirs`.  This file follows the SMPL paper instead
 (Loper et al. 2015, eq. 2-4):

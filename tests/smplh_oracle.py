@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY — two restatements of the SMPL-H forward that csrc/smplh.hip is held to (smplx is installed nowhere, so
+"""TEST INFRASTRUCTURE ONLY — two restatements of the SMPL-H forward that csrc/body_model.hip is held to (smplx is installed nowhere, so
 neither is pinned against smplx itself).
 
   (a) `smplh_forward_independent`: fp64 NumPy, derived from the SMPL paper like oracle/lbs_independent.py and built on ITS

@@ -1,4 +1,4 @@
-"""SMPL-H on the device (csrc/smplh.hip, tokenhmr_amd/smplh.py) and the tokenizer's mesh evaluation (thmr_op_mean_row_dist,
+"""SMPL-H on the device (csrc/body_model.hip, tokenhmr_amd/smplh.py) and the tokenizer's mesh evaluation (thmr_op_mean_row_dist,
 tokenhmr_amd/tokenizer_eval.py).
 
 Bound of the mesh tests: max(2e-6 m, 2 x d_ref) against the independent fp64 derivation (a) of tests/smplh_oracle.py, where d_ref is
@@ -95,7 +95,7 @@ def _picked_equal(out):
     return torch.equal(out.joints[:, 52:], out.vertices[:, SMPL_EXTRA_VERTS])
 
 
-# poses per skin workgroup (smplh.hip smplh_poses_per_workgroup): 1 below 64 poses, 2 from 64, 4 from 128, 8 from 256
+# poses per skin workgroup (body_model.hip smplh_poses_per_workgroup): 1 below 64 poses, 2 from 64, 4 from 128, 8 from 256
 BATCHES = [(1, 256, "one pose"), (5, 5, "5 = max_batch"), (5, 256, "5 of 256"), (63, 256, "63: last batch of 1 pose per workgroup"),
            (64, 256, "64: first of 2 per workgroup"), (127, 256, "127: last of 2, ragged group"), (128, 256, "128: first of 4"),
            (255, 256, "255: last of 4, ragged group"), (256, 256, "256 = max_batch: first of 8")]

@@ -1,7 +1,7 @@
 """The SMPL boundary.  smplx==0.1.28 is un-vendored and not installable here, so this stage has no
 reference-produced golden ("parity unpinned").  Three layers bound it instead:
   1. an INDEPENDENT fp64 derivation from the SMPL paper (oracle/lbs_independent.py: explicit ancestor paths, explicit 4x4
-     inverses of the rest chain, un-precomputed joints) that shares nothing with the oracle's smplx restatement or lbs.hip —
+     inverses of the rest chain, un-precomputed joints) that shares nothing with the oracle's smplx restatement or body_model.hip —
      oracle (CPU) and HIP (GPU) must match it to 2e-6 m on random poses and shapes;
   2. the reference's OWN wrapper smpl_wrapper.py:27-41 (joint_map, update_hips, extra joints) executed in place over a
      stand-in lbs == the oracle bit for bit (pins the wrapper, not lbs);
@@ -46,7 +46,7 @@ def test_oracle_matches_independent_derivation(hips):
 def test_independent_derivation_does_not_depend_on_joint_order():
     """Relabel the 24 joints by a random permutation (children may now precede their parents in the arrays): the
     independent derivation walks ancestor paths, so vertices are unchanged — i.e. it does not silently rely on the
-    parents-first order that smplx (and therefore the oracle and lbs.hip) assume."""
+    parents-first order that smplx (and therefore the oracle and body_model.hip) assume."""
     from oracle.lbs_independent import smpl_forward_independent
     smpl, R, betas = _case(2, 5)
     v0, _ = smpl_forward_independent(R.double().numpy(), betas.double().numpy(), smpl)
@@ -88,7 +88,7 @@ def test_gpu_lbs_matches_independent_derivation(built_lib, cuda_dev, hips):
     o = m(R[:, :1], R[:, 1:], betas, pose2rot=False)
     dv = np.abs(o.vertices.cpu().double().numpy() - v64).max()
     dj = np.abs(o.joints.cpu().double().numpy() - j64).max()
-    print(f"lbs.hip vs independent fp64 derivation (update_hips={hips}): verts {dv:.2e} m, joints {dj:.2e} m")
+    print(f"body_model.hip vs independent fp64 derivation (update_hips={hips}): verts {dv:.2e} m, joints {dj:.2e} m")
     assert dv < TOL_M and dj < TOL_M
 
 

@@ -137,7 +137,7 @@ def test_load_smplh_pkl_roundtrip(tmp_path, consts):
 
 def test_symbols_declared_exported_and_bound():
     import __graft_entry__
-    assert "smplh.hip" in __graft_entry__.SOURCES
+    assert "body_model.hip" in __graft_entry__.SOURCES
     declared = _cabi.declared_symbols()
     for s in _cabi.SMPLH_SYMBOLS:
         assert s in declared

@@ -458,19 +458,6 @@ int vq_stats_partials(int rows);
 int launch_vq_stats(const float* x, const float* cb, const int32_t* idx, int rows, int32_t* count, int accumulate, float* partial,
                     float* commit, float* perplexity, unsigned* bad_flag, hipStream_t s);
 int launch_rotmat_to_aa(const float* R, float* aa, int n, hipStream_t s);      // matrix_to_axis_angle (rotation_utils.py:428-441)
-// lbs.hip
-int launch_lbs_jreg(const float* Jreg, const float* vt, const float* sd, float* Jt, float* Jsd, hipStream_t s);
-// dirsT (20670 x 224): [shapedirs | posedirs | 0]^T built once by launch_lbs_build_dirs; scratch A (B,24,12),
-// xf (B, THMR_LBS_XF) [224 operand floats per crop, then 27*57 regressor partial sums per crop], Jtr (B,24,3), vposed (B,20670)
-constexpr int THMR_LBS_KX = 224, THMR_LBS_XF = 224 + 27 * 57;
-int launch_lbs_build_dirs(const float* sd, const float* pd, float* dirsT, hipStream_t s);
-int launch_lbs(const float* rotmat, const float* betas, const float* cam_t, const float* Jt, const float* Jsd,
-               const int32_t* parents, const float* vt, const float* dirsT, const float* W, const float* J19,
-               const int32_t* extra, const int32_t* jmap, const int32_t* update_hips, float* A, float* xf, float* Jtr,
-               float* vposed, float* verts, float* joints, float* kp2d, float focal_over_size, int B, float* xv,
-               unsigned* cnt, hipStream_t s);
-// extra scratch of the fused skin + joints kernel: xv (B, 21, 3) picked extra-joint vertices, cnt (B) arrival counters (zeroed ONCE)
-int launch_rodrigues(const float* aa, float* R, int n, hipStream_t s);
 // eval.hip
 int launch_eval_pose(const float* pred, const float* gt, int nj, int gt_stride, const int32_t* kp, int nkp, int pelvis_ind,
                      int pelvis_mode, float* mpjpe, float* re, float* pelv, int B, hipStream_t s);
@@ -497,15 +484,33 @@ struct ValLossArgs {
 int launch_val_loss(const ValLossArgs& a, hipStream_t s);
 // out[0] = mean over rows of logsumexp(x_r) - x_r[target_r], x (rows, 2048); row_loss: rows floats of workspace
 int launch_token_ce(const float* x, const int32_t* target, int rows, float* out, float* row_loss, hipStream_t s);
-// smplh.hip: SMPL-H, 52 chain joints (22 body + 2 x 15 hand) and 73 output joints; the folded body-only path works on 22 joints, its weight
-// table padded to 24 columns.  dirsT (20670 x 480) = [shapedirs | posedirs (459) | 0]^T, dirsT_body (20670 x 224) = [shapedirs | the 189
-// body features | 0]^T (launch_smplh_build_dirs); scratch A (B,52,12), xf (B,480), vposed (B,20670)
+// body_model.hip: SMPL and SMPL-H on one set of kernels (prep -> blend GEMM -> skin).  One-time, per model: Jt (nj,3) / Jsd (nj,3,10) from
+// the joint regressor (launch_body_jreg), dirsT (20670 x kx) = [shapedirs | the first npf rows of posedirs | 0]^T (launch_body_build_dirs)
+int launch_body_jreg(const float* Jreg, const float* vt, const float* sd, float* Jt, float* Jsd, int nj, hipStream_t s);
+int launch_body_build_dirs(const float* sd, const float* pd, float* dirsT, int npf, int kx, hipStream_t s);
+int launch_rodrigues(const float* aa, float* R, int n, hipStream_t s);
+// SMPL, 24 joints: dirsT (20670 x 224); xf holds 224 operand floats per crop, then 27*57 regressor partial sums per crop
+constexpr int THMR_LBS_KX = 224, THMR_LBS_XF = 224 + 27 * 57;
+struct LbsArgs {
+    const float *rotmat, *betas, *cam_t;                  // (B,24,3,3), (B,10); (B,3) or null (no kp2d)
+    const float *Jt, *Jsd, *vt, *dirsT, *W, *J19;         // the constant block (SmplConsts::fill, abi_util.h)
+    const int32_t *parents, *extra, *jmap, *update_hips;  // (24), (21), (25), (1)
+    float *A, *xf, *Jtr, *vposed, *xv;                    // scratch: (B,24,12), (B,THMR_LBS_XF), (B,24,3), (B,20670), (B,21,3) picked vertices
+    unsigned* cnt;                                        // scratch: (B) arrival counters of the skin workgroups, zeroed by the call's own prep launch
+    float *verts, *joints, *kp2d;                         // (B,6890,3); (B,44,3) or null; (B,44,2) or null
+    float focal_over_size;
+    int B;
+};
+int launch_lbs(const LbsArgs& a, hipStream_t s);
+// SMPL-H, 52 chain joints (22 body + 2 x 15 hand) and 73 output joints; the folded body-only path works on 22 joints, its weight table
+// padded to 24 columns.  dirsT (20670 x 480) = [shapedirs | posedirs (459) | 0]^T, dirsT_body (20670 x 224) = [shapedirs | the 189 body
+// features | 0]^T; scratch A (B,52,12), xf (B,480), vposed (B,20670)
 constexpr int THMR_SMPLH_NJ = 52, THMR_SMPLH_NBODY = 22, THMR_SMPLH_NBODY_PAD = 24, THMR_SMPLH_NOUT = 73, THMR_SMPLH_NP = 459;
 constexpr int THMR_SMPLH_KX = 480, THMR_SMPLH_KXB = 224;
 struct SmplhArgs {
     const float *rotmat;              // (B,52,3,3), or (B,22,3,3) when body_only
     const float *betas, *transl;      // (B,10) / (B,3); either may be null (zeros)
-    const float *Jt, *Jsd;            // (52,3), (52,3,10)  (launch_smplh_jreg)
+    const float *Jt, *Jsd;            // (52,3), (52,3,10)
     const int32_t *parents, *fold;    // (52): parent; the body joint a joint folds into (itself below 22, else its wrist)
     const int32_t* extra;             // (21) selected vertex ids
     const float *vt, *dirsT, *dirsT_body, *W, *W_body;   // W (6890,52), W_body (6890,24) (launch_smplh_fold_weights)
@@ -513,8 +518,5 @@ struct SmplhArgs {
     float *verts, *joints;            // (B,6890,3); (B,73,3) or null
     int B, body_only;
 };
-int launch_smplh_jreg(const float* Jreg, const float* vt, const float* sd, float* Jt, float* Jsd, hipStream_t s);
-int launch_smplh_build_dirs(const float* sd, const float* pd, float* dirsT, int body_only, hipStream_t s);
 int launch_smplh_fold_weights(const float* W, const int32_t* fold, float* Wf, hipStream_t s);
-int smplh_poses_per_workgroup(int B);
 int launch_smplh(const SmplhArgs& a, hipStream_t s);

@@ -110,15 +110,14 @@ struct thmr_engine {
     size_t o_kv_all = 0, o_ro_w = 0, o_ro_b = 0;
     size_t o_convp[7] = {0};      // repacked k=3 convs: 0,3,6,9,12, res0.conv1, res1.conv1, 14.1, 15 -> see conv_names
     size_t o_cbT = 0, o_cnorm = 0, o_idx = 0, o_inv = 0;   // idx / inverse idx tables as int32 within the float arena
-    size_t o_smpl_vt = 0, o_smpl_sd = 0, o_smpl_pd = 0, o_smpl_jr = 0, o_smpl_w = 0, o_smpl_j19 = 0, o_smpl_int = 0,
-           o_smpl_jt = 0, o_smpl_jsd = 0, o_smpl_dirs = 0;
+    SmplConsts smpl;              // the SMPL constant block
     std::vector<size_t> convp;    // repacked conv offsets, index by conv id
     // optional tokenizer ENCODER (EncodeTokens, vanilla_pose_vqvae.py:304-346): 'encoder.encoder.*' tensors
     std::vector<std::string> enc_names;
     std::vector<size_t> enc_convp;   // repacked encoder convs, index by kEnc id
     size_t o_idx_enc = 0, o_flags = 0;
     bool enc_ready = false;
-    int32_t flag_host[2] = {0, 0}, hips_host = 0;
+    int32_t flag_host[2] = {0, 0};
     std::vector<int32_t> idx_host, eidx_host, inv_host;   // staging for the index tables (must outlive the async copy)
     int vq_len[5] = {160, 125, 90, 55, 21};
     // scratch offsets (floats)
@@ -348,16 +347,7 @@ void layout_weights(thmr_engine* e) {
         e->o_inv = off;   off = align64(off + 4 * 160);
     }
     // SMPL constants
-    e->o_smpl_vt = off;  off = align64(off + (size_t)NV * 3);
-    e->o_smpl_sd = off;  off = align64(off + (size_t)NV * 30);
-    e->o_smpl_pd = off;  off = align64(off + (size_t)NP * NV * 3);
-    e->o_smpl_jr = off;  off = align64(off + (size_t)NJ * NV);
-    e->o_smpl_w = off;   off = align64(off + (size_t)NV * NJ);
-    e->o_smpl_j19 = off; off = align64(off + (size_t)19 * NV);
-    e->o_smpl_int = off; off = align64(off + 128);       // parents(24) | extra(21) | jmap(25) as int32
-    e->o_smpl_jt = off;  off = align64(off + NJ * 3);
-    e->o_smpl_jsd = off; off = align64(off + NJ * 30);
-    e->o_smpl_dirs = off; off = align64(off + (size_t)NV * 3 * THMR_LBS_KX);   // [shapedirs | posedirs | 0]^T, derived
+    off = e->smpl.lay(off);
     // optional tokenizer encoder (tokenizer.pth 'encoder.encoder.*'): raw tensors, repacked convs, resample tables
     for (int i = 0; i < (e->hmr2 ? 0 : kEncN); ++i) {
         const std::string n = kEnc[i].name;
@@ -950,13 +940,14 @@ int lbs(thmr_engine* e, const float* rot, const float* betas, const float* camt,
         float* kp2d, hipStream_t st) {
     auto& so = e->so;
     ProfScope ps(e, st, THMR_PROF_LBS, 2.0 * B * 8.1e6, 4.0 * (B * (NV * 3.0 + 132 + 226) + 4.95e6));
-    const int32_t* ints = reinterpret_cast<const int32_t*>(e->warena + e->o_smpl_int);
-    if (!verts) verts = e->S(so.verts);
-    LAUNCH_OK(launch_lbs(rot, betas, camt, e->warena + e->o_smpl_jt, e->warena + e->o_smpl_jsd, ints,
-                         e->warena + e->o_smpl_vt, e->warena + e->o_smpl_dirs, e->warena + e->o_smpl_w,
-                         e->warena + e->o_smpl_j19, ints + 24, ints + 48, ints + 80, e->S(so.A), e->S(so.pf), e->S(so.Jtr),
-                         e->S(so.vposed), verts, joints, kp2d, FOCAL / IMG, B, e->S(so.xv),
-                         reinterpret_cast<unsigned*>(e->S(so.lcnt)), st));
+    LbsArgs a{};
+    e->smpl.fill(a, e->warena);
+    a.rotmat = rot; a.betas = betas; a.cam_t = camt;
+    a.A = e->S(so.A); a.xf = e->S(so.pf); a.Jtr = e->S(so.Jtr); a.vposed = e->S(so.vposed); a.xv = e->S(so.xv);
+    a.cnt = reinterpret_cast<unsigned*>(e->S(so.lcnt));
+    a.verts = verts ? verts : e->S(so.verts); a.joints = joints; a.kp2d = kp2d;
+    a.focal_over_size = FOCAL / IMG; a.B = B;
+    LAUNCH_OK(launch_lbs(a, st));
     return 0;
 }
 
@@ -1356,19 +1347,7 @@ int thmr_load_smpl(thmr_engine* e, const thmr_smpl_desc* s, void* stream) {
         !s->parents || !s->extra_verts || !s->joint_map)
         return fail(e, THMR_ERR_INVALID, "thmr_smpl_desc has a null field");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const hipMemcpyKind k = s->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIP_OK(hipMemcpyAsync(e->warena + e->o_smpl_vt, s->v_template, sizeof(float) * NV * 3, k, st));
-    HIP_OK(hipMemcpyAsync(e->warena + e->o_smpl_sd, s->shapedirs, sizeof(float) * NV * 30, k, st));
-    HIP_OK(hipMemcpyAsync(e->warena + e->o_smpl_pd, s->posedirs, sizeof(float) * (size_t)NP * NV * 3, k, st));
-    HIP_OK(hipMemcpyAsync(e->warena + e->o_smpl_jr, s->J_regressor, sizeof(float) * NJ * NV, k, st));
-    HIP_OK(hipMemcpyAsync(e->warena + e->o_smpl_w, s->lbs_weights, sizeof(float) * NV * NJ, k, st));
-    HIP_OK(hipMemcpyAsync(e->warena + e->o_smpl_j19, s->J19_regressor, sizeof(float) * 19 * NV, k, st));
-    int32_t* ints = reinterpret_cast<int32_t*>(e->warena + e->o_smpl_int);
-    HIP_OK(hipMemcpyAsync(ints, s->parents, sizeof(int32_t) * 24, k, st));
-    HIP_OK(hipMemcpyAsync(ints + 24, s->extra_verts, sizeof(int32_t) * 21, k, st));
-    HIP_OK(hipMemcpyAsync(ints + 48, s->joint_map, sizeof(int32_t) * 25, k, st));
-    e->hips_host = s->update_hips ? 1 : 0;      // SMPL(update_hips=...), smpl_wrapper.py:11,33-36; lives in the arena (ints[80])
-    HIP_OK(hipMemcpyAsync(ints + 80, &e->hips_host, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(e->smpl.upload(e->warena, s, s->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     e->smpl_loaded = true;
     e->finalized = false;
     return 0;
@@ -1467,9 +1446,7 @@ int thmr_finalize_weights(thmr_engine* e, int32_t assume_all_loaded, void* strea
         LAUNCH_OK(launch_transpose(e->W("quantizer.codebook"), e->warena + e->o_cbT, 1, NCLS, CODE, st));
         LAUNCH_OK(launch_code_norm(e->W("quantizer.codebook"), e->warena + e->o_cnorm, NCLS, st));
     }
-    LAUNCH_OK(launch_lbs_jreg(e->warena + e->o_smpl_jr, e->warena + e->o_smpl_vt, e->warena + e->o_smpl_sd,
-                              e->warena + e->o_smpl_jt, e->warena + e->o_smpl_jsd, st));
-    LAUNCH_OK(launch_lbs_build_dirs(e->warena + e->o_smpl_sd, e->warena + e->o_smpl_pd, e->warena + e->o_smpl_dirs, st));
+    LAUNCH_OK(e->smpl.derive(e->warena, st));
     if (e->enc_ready)
         for (int i = 0; i < kEncN; ++i)
             if (kEnc[i].ks > 1)

@@ -328,7 +328,8 @@ int thmr_op_decoder_init(const float* bias, const float* pos, float* x, int32_t 
 struct thmr_smpl {
     float* mem = nullptr;
     int max_batch = 0;
-    size_t o_vt, o_sd, o_pd, o_jr, o_w, o_j19, o_int, o_jt, o_jsd, o_dirs, o_A, o_pf, o_Jtr, o_vposed, o_rot, o_joints, o_xv, o_cnt, total;
+    SmplConsts c;
+    size_t o_A, o_pf, o_Jtr, o_vposed, o_rot, o_joints, o_xv, o_cnt, total;
 };
 
 int thmr_smpl_create(const thmr_smpl_desc* d, int32_t max_batch, int32_t device, thmr_smpl** out) {
@@ -340,11 +341,8 @@ int thmr_smpl_create(const thmr_smpl_desc* d, int32_t max_batch, int32_t device,
     HIP_OK(hipSetDevice(device));
     thmr_smpl* m = new thmr_smpl();
     m->max_batch = max_batch;
-    size_t off = 0;
+    size_t off = m->c.lay(0);
     auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
-    m->o_vt = take((size_t)NV * 3); m->o_sd = take((size_t)NV * 30); m->o_pd = take((size_t)NP * NV * 3);
-    m->o_jr = take((size_t)NJ * NV); m->o_w = take((size_t)NV * NJ); m->o_j19 = take((size_t)19 * NV);
-    m->o_int = take(128); m->o_jt = take(NJ * 3); m->o_jsd = take(NJ * 30); m->o_dirs = take((size_t)NV * 3 * THMR_LBS_KX);
     const size_t B = (size_t)max_batch;
     m->o_A = take(B * NJ * 12); m->o_pf = take(B * THMR_LBS_XF); m->o_Jtr = take(B * NJ * 3); m->o_rot = take(B * NJ * 9);
     m->o_vposed = take(B * NV * 3);
@@ -353,20 +351,9 @@ int thmr_smpl_create(const thmr_smpl_desc* d, int32_t max_batch, int32_t device,
     m->total = off;
     if (hipMalloc(&m->mem, off * sizeof(float)) != hipSuccess) { delete m; return fail(THMR_ERR_NOMEM, "hipMalloc(smpl) failed"); }
     if (hipMemset(m->mem + m->o_cnt, 0, B * sizeof(float)) != hipSuccess) { thmr_smpl_destroy(m); return fail(THMR_ERR_HIP, "hipMemset(lbs counters) failed"); }
-    const hipMemcpyKind k = d->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    auto cp = [&](size_t o, const void* src, size_t bytes) { return hipMemcpy(m->mem + o, src, bytes, k) == hipSuccess; };
-    int32_t* ints = reinterpret_cast<int32_t*>(m->mem + m->o_int);
-    bool ok = cp(m->o_vt, d->v_template, sizeof(float) * NV * 3) && cp(m->o_sd, d->shapedirs, sizeof(float) * NV * 30) &&
-              cp(m->o_pd, d->posedirs, sizeof(float) * (size_t)NP * NV * 3) && cp(m->o_jr, d->J_regressor, sizeof(float) * NJ * NV) &&
-              cp(m->o_w, d->lbs_weights, sizeof(float) * NV * NJ) && cp(m->o_j19, d->J19_regressor, sizeof(float) * 19 * NV) &&
-              hipMemcpy(ints, d->parents, sizeof(int32_t) * 24, k) == hipSuccess &&
-              hipMemcpy(ints + 24, d->extra_verts, sizeof(int32_t) * 21, k) == hipSuccess &&
-              hipMemcpy(ints + 48, d->joint_map, sizeof(int32_t) * 25, k) == hipSuccess;
-    const int32_t hips = d->update_hips ? 1 : 0;
-    ok = ok && hipMemcpy(ints + 80, &hips, sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok || launch_lbs_jreg(m->mem + m->o_jr, m->mem + m->o_vt, m->mem + m->o_sd, m->mem + m->o_jt, m->mem + m->o_jsd, nullptr) != 0 ||
-        launch_lbs_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirs, nullptr) != 0 ||
-        hipDeviceSynchronize() != hipSuccess) {
+    // upload() only enqueues its copies: d's arrays and m->c.hips_host are read until the hipDeviceSynchronize() below
+    if (m->c.upload(m->mem, d, d->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, nullptr) != hipSuccess ||
+        m->c.derive(m->mem, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
         thmr_smpl_destroy(m);
         return fail(THMR_ERR_HIP, "SMPL constant upload failed");
     }
@@ -390,15 +377,18 @@ int thmr_smpl_forward(thmr_smpl* m, const float* pose, int32_t pose2rot, const f
         LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * NJ, st));
         rot = m->mem + m->o_rot;
     }
-    const int32_t* ints = reinterpret_cast<const int32_t*>(m->mem + m->o_int);
-    LAUNCH_OK(launch_lbs(rot, betas, nullptr, m->mem + m->o_jt, m->mem + m->o_jsd, ints, m->mem + m->o_vt, m->mem + m->o_dirs,
-                         m->mem + m->o_w, m->mem + m->o_j19, ints + 24, ints + 48, ints + 80, m->mem + m->o_A, m->mem + m->o_pf,
-                         m->mem + m->o_Jtr, m->mem + m->o_vposed, verts, joints ? joints : m->mem + m->o_joints, nullptr,
-                         FOCAL / IMG, B, m->mem + m->o_xv, reinterpret_cast<unsigned*>(m->mem + m->o_cnt), st));
+    LbsArgs a{};
+    m->c.fill(a, m->mem);
+    a.rotmat = rot; a.betas = betas;
+    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_pf; a.Jtr = m->mem + m->o_Jtr; a.vposed = m->mem + m->o_vposed; a.xv = m->mem + m->o_xv;
+    a.cnt = reinterpret_cast<unsigned*>(m->mem + m->o_cnt);
+    a.verts = verts; a.joints = joints ? joints : m->mem + m->o_joints;
+    a.focal_over_size = FOCAL / IMG; a.B = B;
+    LAUNCH_OK(launch_lbs(a, st));
     return 0;
 }
 
-// ---- stand-alone SMPL-H model (csrc/smplh.hip) ----
+// ---- stand-alone SMPL-H model (csrc/body_model.hip) ----
 struct thmr_smplh {
     float* mem = nullptr;
     int max_batch = 0;
@@ -451,9 +441,9 @@ int thmr_smplh_create(const thmr_smplh_desc* d, int32_t max_batch, int32_t devic
               hipMemcpy(ints, par, sizeof(par), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(ints + 64, ext, sizeof(ext), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(ints + 128, fold, sizeof(fold), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok || launch_smplh_jreg(m->mem + m->o_jr, m->mem + m->o_vt, m->mem + m->o_sd, m->mem + m->o_jt, m->mem + m->o_jsd, nullptr) != 0 ||
-        launch_smplh_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirs, 0, nullptr) != 0 ||
-        launch_smplh_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirsb, 1, nullptr) != 0 ||
+    if (!ok || launch_body_jreg(m->mem + m->o_jr, m->mem + m->o_vt, m->mem + m->o_sd, m->mem + m->o_jt, m->mem + m->o_jsd, HJ, nullptr) != 0 ||
+        launch_body_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirs, (HJ - 1) * 9, THMR_SMPLH_KX, nullptr) != 0 ||
+        launch_body_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirsb, (HB - 1) * 9, THMR_SMPLH_KXB, nullptr) != 0 ||
         launch_smplh_fold_weights(m->mem + m->o_w, ints + 128, m->mem + m->o_wb, nullptr) != 0 ||
         hipDeviceSynchronize() != hipSuccess) {
         thmr_smplh_destroy(m);

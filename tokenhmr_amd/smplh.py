@@ -10,7 +10,7 @@
 smplx is installed nowhere this package is built or tested, so the semantics below are RESTATED from its published source, not
 pinned against it:
   * SMPLHLayer takes rotation matrices; whatever is omitted is the identity; no hand mean is added.  Omitted hands select the folded
-    22-joint path of the kernels (`thmr_smplh_forward(body_only=1)`, csrc/smplh.hip); `folded_calls` / `full_calls` count which ran.
+    22-joint path of the kernels (`thmr_smplh_forward(body_only=1)`, csrc/body_model.hip); `folded_calls` / `full_calls` count which ran.
   * SMPLH takes axis-angle; an omitted body_pose / global_orient is zeros.  With use_pca=True hands arrive as `num_pca_comps`
     coefficients (omitted: zeros) and are expanded by hands_components{l,r}[:num_pca_comps]; with use_pca=False as 45 values.  Then
     pose_mean is added — zeros except hands_mean{l,r} when flat_hand_mean=False — and the full 52-joint path runs.
