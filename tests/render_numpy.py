@@ -1,5 +1,5 @@
 """NumPy restatement of the renderer contract — test infrastructure for tests/test_render_host.py and
-tests/test_gpu_render.py.
+tests/test_gpu_render.py / tests/test_gpu_render_edges.py.
 
   * transform + projection: the kernel's fp32 operations in the kernel's order (numpy float32 arithmetic is IEEE, no fused
     multiply-add), snapped to 1/256 px with round-half-even — bit for bit what csrc/render.hip computes

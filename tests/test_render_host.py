@@ -324,6 +324,82 @@ def test_triangle_behind_znear_is_rejected():
     verts2 = verts.copy()
     verts2[0, 2, 2] = 0.04                                   # one corner in front of znear
     assert (RN.render(sc, faces, verts2, np.zeros((1, 3)))["ids"] >= 0).sum() == 0
+    verts2[0, 2, 2] = -1.0                                   # one corner behind the camera: its projection flips, the face still goes
+    assert (RN.render(sc, faces, verts2, np.zeros((1, 3)))["ids"] >= 0).sum() == 0
+
+
+def test_triangle_with_a_corner_beyond_the_guard_band_is_rejected():
+    sc = _flat_scene(32, 32)
+    faces = np.array([[0, 1, 2]])
+    verts = np.array([[[-0.5, -0.5, 1.0], [-0.5, 0.5, 1.0], [2.0e4, 0.0, 1.0]]])       # u = 2,000,016 px: inside 2^21 = 2,097,152
+    P, fix, ok = RN.project(sc, verts, np.zeros((1, 3)))
+    assert ok.all() and fix[0, 2, 0] == 2000016 * 256
+    assert (RN.render(sc, faces, verts, np.zeros((1, 3)))["ids"] >= 0).sum() > 0
+    verts[0, 2, 0] = 2.1e4                                   # u = 2,100,016 px: beyond it
+    assert list(RN.project(sc, verts, np.zeros((1, 3)))[2][0]) == [True, True, False]
+    assert (RN.render(sc, faces, verts, np.zeros((1, 3)))["ids"] >= 0).sum() == 0
+    verts[0, 2] = [0.0, -2.1e4, 1.0]                         # the same in v
+    for winding in (faces, faces[:, ::-1]):
+        assert (RN.render(sc, winding, verts, np.zeros((1, 3)))["ids"] >= 0).sum() == 0
+
+
+def _analytic_quad_count(x0, y0, x1, y1, W, H, S):
+    """Samples of a W x H image inside [x0, x1) x [y0, y1) px — top-left rule: the left and top edges own their samples."""
+    ox = np.array([128]) if S == 1 else RN.OX
+    oy = np.array([128]) if S == 1 else RN.OY
+    n = 0
+    for s in range(S):
+        xs, ys = np.arange(W) * 256 + ox[s], np.arange(H) * 256 + oy[s]
+        n += int(((xs >= x0 * 256) & (xs < x1 * 256)).sum() * ((ys >= y0 * 256) & (ys < y1 * 256)).sum())
+    return n
+
+
+# a quad over each border and each corner of a 37 x 23 image (neither a multiple of the 16-pixel tile), corners on the 1/4 px grid
+_OVERHANG = {"left": (-6.25, 4.5, 9.75, 15.25), "right": (30.5, 3.25, 44.0, 19.75), "top": (5.25, -7.5, 28.75, 6.25),
+             "bottom": (8.5, 17.25, 21.25, 31.0), "top_left": (-3.75, -9.25, 11.5, 8.75), "top_right": (25.25, -2.5, 51.0, 10.25),
+             "bottom_left": (-12.0, 14.75, 7.25, 40.5), "bottom_right": (29.75, 12.5, 37.25, 23.5),
+             "all_round": (-5.0, -4.0, 41.0, 30.0), "last_column_only": (36.75, 2.0, 50.0, 20.0)}
+
+
+@pytest.mark.parametrize("S", [1, 4])
+@pytest.mark.parametrize("where", sorted(_OVERHANG))
+def test_overhanging_quad_covers_the_analytic_count_of_its_visible_part(where, S):
+    W, H = 37, 23
+    x0, y0, x1, y1 = _OVERHANG[where]
+    sc, verts, faces = _screen_quad(x0, y0, x1, y1, W, H)
+    _, fix, ok = RN.project(sc, verts, np.zeros((1, 3)))
+    assert ok.all() and sorted(map(tuple, fix[0])) == sorted((int(x * 256), int(y * 256)) for x in (x0, x1) for y in (y0, y1))
+    ids = RN.render(sc, faces, verts, np.zeros((1, 3)), samples=S)["ids"][0]
+    expect = _analytic_quad_count(x0, y0, x1, y1, W, H, S)
+    assert expect > 0 or where == "last_column_only"
+    assert (ids >= 0).sum() == expect
+    # and it is the right samples: every covered pixel lies inside the quad's pixel box, clipped to the image
+    py, px = np.nonzero((ids >= 0).any(-1))
+    if len(px):
+        assert px.min() >= max(int(np.floor(x0)), 0) and px.max() <= min(int(np.ceil(x1)) - 1, W - 1)
+        assert py.min() >= max(int(np.floor(y0)), 0) and py.max() <= min(int(np.ceil(y1)) - 1, H - 1)
+
+
+@pytest.mark.parametrize("size", [(37, 23), (1, 1)])
+@pytest.mark.parametrize("S", [1, 4])
+def test_one_huge_triangle_covers_every_sample(S, size):
+    W, H = size
+    sc = _flat_scene(W, H)
+    to3 = lambda u, v: ((u - W / 2) / 100.0, (v - H / 2) / 100.0, 1.0)
+    verts = np.array([[to3(-300, -200), to3(-300, 900), to3(1200, -200)]])      # the image is deep inside: 337/1500 + 223/1100 < 1
+    faces = np.array([[0, 1, 2]])                                                # negative doubled area in the image frame: front
+    ids = RN.render(sc, faces, verts, np.zeros((1, 3)), samples=S)["ids"]
+    assert ids.shape == (1, H, W, S) and (ids == 0).all()
+    assert (RN.render(sc, faces[:, ::-1], verts, np.zeros((1, 3)), samples=S)["ids"] == -1).all()     # its back covers nothing
+
+
+@pytest.mark.parametrize("S", [1, 4])
+@pytest.mark.parametrize("box", [(-20.0, 3.0, -2.25, 18.0), (4.0, -30.5, 30.0, -1.0), (37.0, 2.0, 60.0, 20.0), (3.0, 23.0, 30.0, 45.5),
+                                 (-9.0, -9.0, 0.0, 0.0), (37.25, 23.5, 50.0, 40.0)])
+def test_quad_outside_the_image_covers_nothing(box, S):
+    """Left of, above, right of and below a 37 x 23 image, and touching it only at a corner or an edge it does not own."""
+    sc, verts, faces = _screen_quad(*box, 37, 23)
+    assert (RN.render(sc, faces, verts, np.zeros((1, 3)), samples=S)["ids"] >= 0).sum() == 0
 
 
 # ------------------------------------------------------------------------------------------------ arguments and errors

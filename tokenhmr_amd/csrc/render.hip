@@ -161,9 +161,10 @@ __global__ void render_setup_kernel(Params p, const int32_t* __restrict__ faces,
     const int64_t base = (int64_t)m * p.V;
     int2 a = fix[base + fv[0]], b = fix[base + fv[1]], c = fix[base + fv[2]];
     double Za = pos[(base + fv[0]) * 3 + 2], Zb = pos[(base + fv[1]) * 3 + 2], Zc = pos[(base + fv[2]) * 3 + 2];
-    const int64_t area = edge(a.x, a.y, b.x, b.y, c.x, c.y);
+    // an unusable corner (INT_MIN marker) rejects the face before any arithmetic on it: the marker's differences overflow int32
+    const bool usable = a.x != INT_MIN && b.x != INT_MIN && c.x != INT_MIN;
     // front faces are counter-clockwise in GL window coordinates (y up), i.e. negative doubled area in the image frame
-    if (a.x != INT_MIN && b.x != INT_MIN && c.x != INT_MIN && area < 0) {
+    if (usable && edge(a.x, a.y, b.x, b.y, c.x, c.y) < 0) {
         { int2 t = b; b = c; c = t; double tz = Zb; Zb = Zc; Zc = tz; }   // orient positively
         const int px0 = min(a.x, min(b.x, c.x)) >> 8, px1 = max(a.x, max(b.x, c.x)) >> 8;
         const int py0 = min(a.y, min(b.y, c.y)) >> 8, py1 = max(a.y, max(b.y, c.y)) >> 8;
