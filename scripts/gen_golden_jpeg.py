@@ -56,6 +56,9 @@ CASES = [
     ("c420_150x200_q90_opt_rst3", (150, 200), "RGB", "420", 90, {"optimize": True, "restart_marker_blocks": 3}, 60),
     ("progressive_16x16", (16, 16), "RGB", "420", 90, {"progressive": True}, 30),
     ("cmyk_16x16", (16, 16), "CMYK", None, 90, {}, 30),
+    # the two sizes of the grow-and-reuse test (tests/test_gpu_jpeg.py): appended, so the seeds of the cases above stay
+    ("grey_16x16_q90", (16, 16), "L", None, 90, {}, 30),
+    ("c420_40x48_q90", (40, 48), "RGB", "420", 90, {}, 30),
 ]
 
 

@@ -184,6 +184,39 @@ def test_gpu_cropper_errors_and_rgb(built_lib, cuda_dev, gold):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("entry", ["run", "run_frames"])
+def test_gpu_one_handle_grown_then_reused_equals_fresh_handles(built_lib, cuda_dev, entry):
+    """Reuse after growth, and the capacity bookkeeping: one handle, one stream, no host synchronisation between the calls.  1 un-blurred
+    crop, then 3 blurred ones (descriptors, weights and blur scratch all grow), then 1 blurred crop inside the grown buffers.  Every
+    result is bit-equal to the same call on a handle of its own.  48x64 frame, patch 32; sigma 1.5 at truncate 3.0 is a kernel radius
+    of 5.  (A missing synchronisation before the growth would not show here: hipFree waits for the device by itself.)"""
+    from tokenhmr_amd.preprocess import Cropper, gen_trans_from_patch_cv
+    H, W, P = 48, 64, 32
+    frame = torch.as_tensor(np.random.default_rng(5).integers(0, 256, (H, W, 3), dtype=np.uint8)).to(cuda_dev)
+    boxes = [(32.0, 24.0, 40.0), (10.0, 8.0, 30.0), (60.0, 44.0, 56.0)]          # centre x, y and side: inside, over two corners
+    M = np.stack([gen_trans_from_patch_cv(cx, cy, s, s, P, P, 1.0, 0) for cx, cy, s in boxes])
+    steps = [(M[:1], [0.0]), (M, [1.5] * 3), (M[1:2], [1.5])]
+
+    def call(cr, trans, sig):
+        if entry == "run":
+            return cr.warp(frame, trans, sig, truncate=3.0, patch=P)
+        n = len(sig)
+        return cr.warp_device_windows([frame.reshape(-1)] * n, [(H, W)] * n, [(0, 0, W, H)] * n, trans, sig, truncate=3.0, patch=P)
+
+    one = Cropper(cuda_dev)
+    got = [call(one, t, s) for t, s in steps]
+    torch.cuda.synchronize()
+    one.close()
+    for k, ((t, s), g) in enumerate(zip(steps, got)):
+        fresh = Cropper(cuda_dev)
+        want = call(fresh, t, s).cpu()
+        fresh.close()
+        assert g.shape == (len(s), 3, P, P) and torch.equal(g.cpu(), want), (entry, k)
+    # the same crop gives the same pixels from either batch, and the blur really ran
+    assert torch.equal(got[2][0], got[1][1]) and not torch.equal(got[1][0], got[0][0])
+
+
+@pytest.mark.gpu
 def test_gpu_crops_feed_the_model(built_lib, cuda_dev, gold):
     """demo.py's loop body with both pieces swapped in: ViTDetDataset(...).batch() -> model(batch)."""
     from tokenhmr_amd.config import HMRConfig

@@ -131,6 +131,29 @@ def test_reuse_after_growth_and_on_the_alternate_staging_set(built_lib, cuda_dev
         d.close()
 
 
+def test_one_handle_grown_then_reused_without_host_sync_equals_fresh_handles(built_lib, cuda_dev):
+    """Reuse after growth, and the capacity bookkeeping: one handle, one stream, nothing waited for between the calls.  A 16x16 grey
+    file, then a 40x48 4:2:0 file twice in a row (each of the two staging sets and the plane scratch grow), then the small file again
+    inside the grown buffers.  Every result is bit-equal to the same call on a handle of its own, to the CPU decode and to the pixels
+    Pillow stored.  (A missing synchronisation before the growth would not show here: hipFree waits for the device by itself.)"""
+    from tokenhmr_amd import jpeg as J
+    _, jpg, rgb = gold()
+    small, large = J.entropy_decode(jpg["grey_16x16_q90"]), J.entropy_decode(jpg["c420_40x48_q90"])
+    assert small.size == (16, 16) and large.size == (40, 48) and (large.plan.h_samp, large.plan.v_samp) == (2, 2)
+    steps = [small, large, large, small]
+    one = J.JpegDecoder(cuda_dev)
+    got = [one.decode_planned([p])[0] for p in steps]
+    torch.cuda.synchronize()
+    one.close()
+    for k, (p, g) in enumerate(zip(steps, got)):
+        fresh = J.JpegDecoder(cuda_dev)
+        want = fresh.decode_planned([p])[0].cpu()
+        fresh.close()
+        assert torch.equal(g.cpu(), want), k
+        name = "grey_16x16_q90" if p is small else "c420_40x48_q90"
+        assert np.array_equal(want.numpy(), host_reference(name, None)) and np.array_equal(want.numpy(), rgb[name][:, :, ::-1]), k
+
+
 def test_one_captured_call_replays_the_same_bytes(built_lib, cuda_dev):
     """A decoder of its own (a captured call keeps reading its staging set), warmed up at the sizes, then one call captured at fixed
     sizes and replayed into cleared outputs.  The runtime's queue settings are left as they are."""

@@ -257,3 +257,33 @@ def test_scratch_growth_and_errors(built_lib, cuda_dev):
     assert L.thmr_renderer_run(h, C.byref(d), v.data_ptr(), t.data_ptr(), 2, o.data_ptr(), o.data_ptr(), None) == -1   # bg needs 3 channels
     torch.cuda.synchronize()
     assert np.array_equal(grown.render_scene(verts, cam_t, 320, 240, 300).cpu().numpy(), small)
+
+
+def test_one_handle_grown_then_reused_without_host_sync_equals_fresh_handles(built_lib, cuda_dev):
+    """Reuse after growth, and the capacity bookkeeping: one handle, one stream, no host synchronisation between the calls.  1 mesh,
+    then 3 (every scratch buffer grows), then 1 again inside the grown buffers.  64x64 images, 1 sample.  Every result, colours and
+    winning ids, is bit-equal to the same call on a renderer of its own.  (A missing synchronisation before the growth would not
+    show here: hipFree waits for the device by itself.)"""
+    from tokenhmr_amd import _cabi
+    from tokenhmr_amd import render as R
+    faces, verts, cam_t = _scene_meshes("sphere")
+    v3 = torch.as_tensor(np.repeat(verts, 3, axis=0) * np.array([1.0, 0.7, 1.3])[:, None, None], dtype=torch.float32).to(cuda_dev)
+    t3 = torch.as_tensor(cam_t + np.array([[0.0, 0.0, 0.0], [0.8, -0.6, 1.0], [-1.2, 0.9, -2.0]]), dtype=torch.float32).to(cuda_dev)
+    sc = R.build_scene("call", 64, 64, 120.0, np.zeros(3), mesh_base_color=(0.9, 0.6, 0.3), scene_bg_color=(0.2, 0.3, 0.4))
+    steps = [slice(0, 1), slice(0, 3), slice(2, 3)]
+    torch.cuda.synchronize()
+
+    def call(r, k):
+        return r._run(sc, v3[k], t3[k], _cabi.RENDER_PER_IMAGE, 4, return_ids=True)
+
+    one = R.Renderer(_cfg(focal=120, res=64), faces, device=cuda_dev, samples=1)
+    got = [call(one, k) for k in steps]
+    torch.cuda.synchronize()
+    one.close()
+    for i, (k, (out, ids)) in enumerate(zip(steps, got)):
+        fresh = R.Renderer(_cfg(focal=120, res=64), faces, device=cuda_dev, samples=1)
+        want, want_ids = call(fresh, k)
+        assert torch.equal(out.cpu(), want.cpu()) and torch.equal(ids.cpu(), want_ids.cpu()), i
+        fresh.close()
+        assert (ids >= 0).sum() > 100 * ids.shape[0] and (ids < 0).any(), i          # every image shows its mesh against background
+    assert torch.equal(got[2][0][0], got[1][0][2])                                    # the same mesh, alone or third of three

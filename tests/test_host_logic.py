@@ -248,6 +248,12 @@ def test_stateless_entry_points_reject_bad_arguments_without_a_gpu(built_lib):
     assert L.thmr_encode_tokens(null, one, 1, one, null, null) < 0 and L.thmr_vq_decode(null, one, 1, one, null) < 0
     assert L.thmr_cropper_run(null, one, 8, 8, 24, None, 1, 256, 1, None, None, one, null) < 0
     assert b"null cropper" in L.thmr_cropper_last_error(None)
+    # each handle family keeps its own per-thread message: the renderer's refusal leaves the cropper's alone
+    assert L.thmr_renderer_run(null, None, one, one, 1, null, one, null) < 0
+    assert b"null renderer" in L.thmr_renderer_last_error(None) and b"null cropper" in L.thmr_cropper_last_error(None)
+    # the JPEG family, and only it, also reports through thmr_last_error
+    assert L.thmr_jpeg_probe(one, 0, C.byref(_cabi.JpegInfo())) < 0
+    assert b"not a JPEG" in L.thmr_jpeg_last_error(None) and b"not a JPEG" in L.thmr_last_error(None)
     assert L.thmr_smpl_create(None, 1, 0, None) < 0
     h = C.c_void_p(0)
     assert L.thmr_cropper_create(-1, C.byref(h)) < 0 and not h.value

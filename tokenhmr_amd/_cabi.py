@@ -163,12 +163,17 @@ class ProfEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
 
-def declared_symbols():
-    """Every function the header declares (used by the symbol-export test)."""
+def declared_functions():
+    """{name: return type as written} of every function the header declares: 'int', 'void' or 'const char*'."""
     with open(HEADER) as f:
         text = f.read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(thmr_[a-z0-9_]+)\s*\(", text)))
+    return {name: ret.strip() for ret, name in re.findall(r"([A-Za-z_][\w \t*]*?)\b(thmr_[a-z0-9_]+)\s*\(", text)}
+
+
+def declared_symbols():
+    """Every function the header declares (used by the symbol-export test)."""
+    return sorted(declared_functions())
 
 
 _libs = {}
@@ -226,16 +231,20 @@ def load(exp=None):
     except ImportError:
         pass
     lib = C.CDLL(path)
+    declared = declared_functions()
+    restypes = {"int": C.c_int, "void": None, "const char*": C.c_char_p}
+    for name, ret in declared.items():                   # every return type as the header writes it
+        if ret not in restypes:
+            raise RuntimeError(f"tokenhmr_hip.h declares {name} as returning '{ret}': _cabi.load() knows {sorted(restypes)}")
+        if hasattr(lib, name):
+            getattr(lib, name).restype = restypes[ret]
     older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
     # a build loaded by path may also predate thmr_renderer_sheet / thmr_debug_vit_plan (added without an ABI change: new symbols, no layout touched)
-    missing = [s for s in declared_symbols() if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
+    missing = [s for s in sorted(declared) if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
                and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS + FRAMES_SYMBOLS + JPEG_SYMBOLS)]
     if missing:
         raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
-    lib.thmr_abi_version.restype = C.c_int
-    lib.thmr_build_info.restype = C.c_char_p
-    lib.thmr_last_error.restype = C.c_char_p
     lib.thmr_last_error.argtypes = [vp]
     lib.thmr_arena_bytes.argtypes = [C.POINTER(Config), C.POINTER(sz), C.POINTER(sz)]
     lib.thmr_spec.argtypes = [C.POINTER(Config), i32, C.POINTER(C.c_char_p), C.POINTER(i64)]
@@ -243,7 +252,6 @@ def load(exp=None):
         lib.thmr_mode_bytes.argtypes = [C.POINTER(Config), i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     lib.thmr_create.argtypes = [C.POINTER(Config), vp, vp, C.POINTER(vp)]
     lib.thmr_destroy.argtypes = [vp]
-    lib.thmr_destroy.restype = None
     lib.thmr_load_weights.argtypes = [vp, C.POINTER(TensorDesc), sz, vp]
     lib.thmr_load_smpl.argtypes = [vp, C.POINTER(SmplDesc), vp]
     lib.thmr_finalize_weights.argtypes = [vp, i32, vp]
@@ -292,7 +300,6 @@ def load(exp=None):
     if hasattr(lib, "thmr_smplh_create"):                # the SMPL-H body model (added without an ABI change)
         lib.thmr_smplh_create.argtypes = [C.POINTER(SmplhDesc), i32, i32, C.POINTER(vp)]
         lib.thmr_smplh_destroy.argtypes = [vp]
-        lib.thmr_smplh_destroy.restype = None
         lib.thmr_smplh_forward.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]
         lib.thmr_op_mean_row_dist.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     if hasattr(lib, "thmr_val_loss"):                    # the forward value of the loss (added without an ABI change)
@@ -300,15 +307,12 @@ def load(exp=None):
         lib.thmr_op_token_ce.argtypes = [vp, vp, i32, vp, vp, vp]
     lib.thmr_smpl_create.argtypes = [C.POINTER(SmplDesc), i32, i32, C.POINTER(vp)]
     lib.thmr_smpl_destroy.argtypes = [vp]
-    lib.thmr_smpl_destroy.restype = None
     lib.thmr_smpl_forward.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
     lib.thmr_eval_pose.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.thmr_regress_joints.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.thmr_cropper_create.argtypes = [i32, C.POINTER(vp)]
     lib.thmr_cropper_destroy.argtypes = [vp]
-    lib.thmr_cropper_destroy.restype = None
     lib.thmr_cropper_last_error.argtypes = [vp]
-    lib.thmr_cropper_last_error.restype = C.c_char_p
     lib.thmr_cropper_run.argtypes = [vp, vp, i32, i32, i64, C.POINTER(CropDesc), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
     if hasattr(lib, "thmr_cropper_run_frames"):          # the frame-table entry (added without an ABI change)
         lib.thmr_cropper_run_frames.argtypes = [vp, C.POINTER(FrameCrop), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
@@ -318,34 +322,21 @@ def load(exp=None):
         lib.thmr_jpeg_decode_host.argtypes = [vp, sz, C.POINTER(i32), i32, vp, i64]
         lib.thmr_jpeg_create.argtypes = [i32, C.POINTER(vp)]
         lib.thmr_jpeg_destroy.argtypes = [vp]
-        lib.thmr_jpeg_destroy.restype = None
         lib.thmr_jpeg_last_error.argtypes = [vp]
-        lib.thmr_jpeg_last_error.restype = C.c_char_p
         lib.thmr_jpeg_decode_batch.argtypes = [vp, C.POINTER(JpegItem), i32, i32, vp]
     lib.thmr_renderer_create.argtypes = [i32, vp, i32, i32, C.POINTER(vp)]
     lib.thmr_renderer_destroy.argtypes = [vp]
-    lib.thmr_renderer_destroy.restype = None
     lib.thmr_renderer_last_error.argtypes = [vp]
-    lib.thmr_renderer_last_error.restype = C.c_char_p
     lib.thmr_renderer_run.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, i32, vp, vp, vp]
     if hasattr(lib, "thmr_renderer_sheet"):
         lib.thmr_renderer_sheet.argtypes = [vp, C.POINTER(SheetDesc), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.thmr_pack_records.argtypes = [C.POINTER(Outputs), i32, vp, vp]
     lib.thmr_bcast_weights.argtypes = [vp, vp, i32, vp]
     lib.thmr_allgather_records.argtypes = [vp, vp, i32, vp, vp]
-    lib.thmr_collective_last_error.restype = C.c_char_p
     lib.thmr_prof_enable.argtypes = [vp, i32]
     lib.thmr_set_vit_gemm.argtypes = [vp, i32, vp]
     lib.thmr_get_vit_gemm.argtypes = [vp]
     lib.thmr_prof_collect.argtypes = [vp, C.POINTER(ProfEntry), i32]
-    for name in declared_symbols():
-        if not hasattr(lib, name):
-            continue
-        fn = getattr(lib, name)
-        if name not in ("thmr_build_info", "thmr_last_error", "thmr_destroy", "thmr_smpl_destroy", "thmr_smplh_destroy", "thmr_cropper_destroy",
-                        "thmr_cropper_last_error", "thmr_collective_last_error", "thmr_renderer_destroy",
-                        "thmr_renderer_last_error", "thmr_jpeg_destroy", "thmr_jpeg_last_error"):
-            fn.restype = C.c_int
     if lib.thmr_abi_version() != ABI_VERSION and not older:
         raise RuntimeError("libtokenhmr_hip.so ABI version mismatch")
     _libs[exp] = lib
@@ -361,3 +352,61 @@ def check(rc, engine=None, lib=None):
         lib = lib if lib is not None else load()
         msg = lib.thmr_last_error(engine)
         raise EngineError(f"tokenhmr_hip error {rc}: {msg.decode() if msg else '?'}")
+
+
+def raise_error(rc, what, msg, error=EngineError, by_code=None):
+    """The one text of a failed C call: '<entry point> error <rc>: <the C message>'; by_code picks another class for some codes."""
+    raise (by_code or {}).get(rc, error)(f"{what} error {rc}: {msg.decode() if msg else '?'}")
+
+
+class Handle:
+    """Owner of one C handle of the family `stem` (thmr_cropper -> thmr_cropper_create / _destroy / _last_error): resolves the device
+    ('cuda' without an index means the CURRENT device, like Engine, not device 0), creates the handle with _open, raises the family's
+    exception with the C side's own message from _check, and destroys the handle once — by close() or when the object is collected.
+    last_error: the symbol that reads the message where the family has no thmr_X_last_error of its own (the body models report
+    through thmr_last_error(NULL): their handles keep no string)."""
+    error, error_by_code, no_gpu_error = EngineError, None, RuntimeError
+
+    @classmethod
+    def cuda_device(cls, device, needs_gpu, resolve):
+        """torch.device(device), refused with `needs_gpu` unless it is a GPU.  resolve: 'cuda' without an index becomes the current
+        device, which needs a GPU."""
+        import torch
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise cls.no_gpu_error(needs_gpu)
+        return torch.device("cuda", torch.cuda.current_device()) if resolve and dev.index is None else dev
+
+    def __init__(self, device, stem, needs_gpu, last_error=None):
+        self.device = self.cuda_device(device, needs_gpu, resolve=False)
+        self._needs_gpu = needs_gpu
+        self.lib = load()
+        self._stem, self._per_handle = stem, last_error is None
+        self._last_error = getattr(self.lib, last_error or stem + "_last_error")
+        self.h = None
+
+    def _index(self):
+        """The device index; 'cuda' without one becomes the current device here, which needs a GPU."""
+        self.device = self.cuda_device(self.device, self._needs_gpu, resolve=True)
+        return self.device.index
+
+    def _open(self, *args):
+        """thmr_X_create(*args, &handle)."""
+        h = C.c_void_p()
+        self._check(getattr(self.lib, self._stem + "_create")(*args, C.byref(h)), self._stem + "_create")
+        self.h = h
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise_error(rc, what, self._last_error(self.h if self._per_handle else None), self.error, self.error_by_code)
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.lib, self._stem + "_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -27,7 +27,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tokenhmr_hip.h"
+#include "handle_util.h"
 
 #pragma clang fp contract(off)
 
@@ -194,8 +194,7 @@ __global__ __launch_bounds__(256) void crop_frames_warp_kernel(const FrameDev* _
         warp_body(f.c, f.win, f.stride, f.wx0, f.wy0, f.wx0, f.wy0, f.wx0 + f.ww, f.wy0 + f.wh, scratch, P, swap_rb, mean, sd, out);
 }
 
-thread_local std::string g_crop_err;
-int cfail(int code, const std::string& m) { g_crop_err = m; return code; }
+thread_local ErrorSink<thmr_cropper> g_crop_err;
 
 // numpy's pairwise sum (loops_utils.h.src) for n <= 128 — the normalisation of scipy's _gaussian_kernel1d uses ndarray.sum()
 double np_sum(const std::vector<double>& a) {
@@ -289,28 +288,21 @@ bool prep_crop(const double* Mfwd, double sigma, double truncate, int i, int pat
 
 struct thmr_cropper {
     int device = 0;
-    double* scratch = nullptr;
-    size_t scratch_doubles = 0;
-    CropDev* cds = nullptr;
-    double* wts = nullptr;
-    size_t cds_cap = 0, wts_cap = 0;
-    char* fds = nullptr;          // thmr_cropper_run_frames: n frame descriptors, then the blur weights, in one buffer
-    size_t fds_cap = 0;
+    DevBuf<double> scratch;       // the blurred regions of both entries
+    DevBuf<CropDev> cds;
+    DevBuf<double> wts;
+    DevBuf<char> fds;             // thmr_cropper_run_frames: n frame descriptors, then the blur weights, in one buffer
     std::string err;
 };
 
 extern "C" {
 
-const char* thmr_cropper_last_error(const thmr_cropper* c) { return c ? c->err.c_str() : g_crop_err.c_str(); }
+const char* thmr_cropper_last_error(const thmr_cropper* c) { return g_crop_err.read(c); }
 
 int thmr_cropper_create(int32_t device, thmr_cropper** out) {
-    if (!out) return cfail(THMR_ERR_INVALID, "null out");
+    if (!out) return g_crop_err.invalid(nullptr, "null out");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        (void)hipGetLastError();
-        return cfail(THMR_ERR_HIP, "no such HIP device (the crop kernels have no CPU fallback)");
-    }
+    if (!check_device(device)) return g_crop_err.fail(nullptr, THMR_ERR_HIP, "no such HIP device (the crop kernels have no CPU fallback)");
     thmr_cropper* c = new thmr_cropper();
     c->device = device;
     *out = c;
@@ -320,22 +312,18 @@ int thmr_cropper_create(int32_t device, thmr_cropper** out) {
 void thmr_cropper_destroy(thmr_cropper* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->cds) (void)hipFree(c->cds);
-    if (c->wts) (void)hipFree(c->wts);
-    if (c->fds) (void)hipFree(c->fds);
-    delete c;
+    delete c;          // the buffers free themselves
 }
 
 int thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int32_t W, int64_t row_stride,
                      const thmr_crop_desc* crops, int32_t n, int32_t patch, int32_t swap_rb, const float* mean, const float* std_,
                      float* out_dev, void* stream) {
-    if (!c) return cfail(THMR_ERR_INVALID, "null cropper");
-    auto bad = [&](const std::string& m) { c->err = m; g_crop_err = m; return THMR_ERR_INVALID; };
-    if (!frame_dev || !crops || !out_dev || !mean || !std_) return bad("null buffer");
-    if (H <= 0 || W <= 0 || n <= 0 || patch <= 0 || patch > 4096 || row_stride < (int64_t)W * 3) return bad("bad frame / patch geometry");
+    if (!c) return g_crop_err.invalid(nullptr, "null cropper");
+    if (!frame_dev || !crops || !out_dev || !mean || !std_) return g_crop_err.invalid(c, "null buffer");
+    if (H <= 0 || W <= 0 || n <= 0 || patch <= 0 || patch > 4096 || row_stride < (int64_t)W * 3)
+        return g_crop_err.invalid(c, "bad frame / patch geometry");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(c->device) != hipSuccess) return bad("hipSetDevice failed");
+    if (hipSetDevice(c->device) != hipSuccess) return g_crop_err.invalid(c, "hipSetDevice failed");
 
     std::vector<CropDev> cds(n);
     std::vector<double> wts;
@@ -343,38 +331,21 @@ int thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int32
     for (int i = 0; i < n; ++i) {
         std::string m;
         TouchBox box;
-        if (!prep_crop(crops[i].M, crops[i].sigma, crops[i].truncate, i, patch, H, W, true, cds[i], wts, plan, box, m)) return bad(m);
+        if (!prep_crop(crops[i].M, crops[i].sigma, crops[i].truncate, i, patch, H, W, true, cds[i], wts, plan, box, m))
+            return g_crop_err.invalid(c, m);
     }
-    const size_t need = plan.need;
     const int64_t max_v = plan.max_v, max_h = plan.max_h;
-    auto hip_bad = [&](const char* what, hipError_t e) { c->err = std::string(what) + ": " + hipGetErrorString(e); g_crop_err = c->err; return THMR_ERR_HIP; };
     hipError_t e;
-    // grow-only device buffers (re-allocation synchronises the stream first: earlier launches may still read the old ones)
-    if ((size_t)n > c->cds_cap || wts.size() > c->wts_cap || need > c->scratch_doubles) {
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_bad("hipStreamSynchronize", e);
-        if ((size_t)n > c->cds_cap) {
-            if (c->cds) (void)hipFree(c->cds);
-            c->cds = nullptr; c->cds_cap = 0;
-            if ((e = hipMalloc(&c->cds, sizeof(CropDev) * (size_t)n * 2)) != hipSuccess) return hip_bad("hipMalloc(crop descriptors)", e);
-            c->cds_cap = (size_t)n * 2;
-        }
-        if (wts.size() > c->wts_cap) {
-            if (c->wts) (void)hipFree(c->wts);
-            c->wts = nullptr; c->wts_cap = 0;
-            if ((e = hipMalloc(&c->wts, sizeof(double) * wts.size() * 2)) != hipSuccess) return hip_bad("hipMalloc(weights)", e);
-            c->wts_cap = wts.size() * 2;
-        }
-        if (need > c->scratch_doubles) {
-            if (c->scratch) (void)hipFree(c->scratch);
-            c->scratch = nullptr; c->scratch_doubles = 0;
-            if ((e = hipMalloc(&c->scratch, sizeof(double) * need)) != hipSuccess) return hip_bad("hipMalloc(blur scratch)", e);
-            c->scratch_doubles = need;
-        }
-    }
+    const char* what;
+    e = grow_synced(st, {c->cds.want(n, (size_t)n * 2, "hipMalloc(crop descriptors)"),
+                         c->wts.want(wts.size(), wts.size() * 2, "hipMalloc(weights)"),
+                         c->scratch.want(plan.need, plan.need, "hipMalloc(blur scratch)")}, what);
+    if (e != hipSuccess) return g_crop_err.hip(c, what, e);
     // pageable-host -> device copies return after staging, so the vectors may die at the end of this call
-    if ((e = hipMemcpyAsync(c->cds, cds.data(), sizeof(CropDev) * n, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_bad("hipMemcpyAsync", e);
+    if ((e = hipMemcpyAsync(c->cds, cds.data(), sizeof(CropDev) * n, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return g_crop_err.hip(c, "hipMemcpyAsync", e);
     if (!wts.empty() && (e = hipMemcpyAsync(c->wts, wts.data(), sizeof(double) * wts.size(), hipMemcpyHostToDevice, st)) != hipSuccess)
-        return hip_bad("hipMemcpyAsync", e);
+        return g_crop_err.hip(c, "hipMemcpyAsync", e);
     if (max_v > 0) {
         hipLaunchKernelGGL(crop_vpass_kernel, dim3((unsigned)((max_v + 255) / 256), n), dim3(256), 0, st, frame_dev, H, W, row_stride,
                            c->cds, c->wts, c->scratch);
@@ -382,16 +353,15 @@ int thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int32
     }
     hipLaunchKernelGGL(crop_warp_kernel, dim3((patch * patch + 255) / 256, n), dim3(256), 0, st, frame_dev, H, W, row_stride, c->cds,
                        c->scratch, patch, swap_rb, mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], out_dev);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_bad("crop kernel launch", e);
+    if ((e = hipGetLastError()) != hipSuccess) return g_crop_err.hip(c, "crop kernel launch", e);
     return 0;
 }
 
 int thmr_cropper_run_frames(thmr_cropper* c, const thmr_frame_crop* items, int32_t n, int32_t patch, int32_t swap_rb, const float* mean,
                             const float* std_, float* out_dev, void* stream) {
     // every argument is checked before the handle, and the handle before any HIP call: a refusal never touches the device
-    auto bad = [&](const std::string& m) { if (c) c->err = m; g_crop_err = m; return THMR_ERR_INVALID; };
-    if (!items || !out_dev || !mean || !std_) return bad("null buffer");
-    if (n <= 0 || patch <= 0 || patch > 4096) return bad("bad batch / patch geometry");
+    if (!items || !out_dev || !mean || !std_) return g_crop_err.invalid(c, "null buffer");
+    if (n <= 0 || patch <= 0 || patch > 4096) return g_crop_err.invalid(c, "bad batch / patch geometry");
     // descriptors and weights travel in one buffer: [n FrameDev][weights]
     std::vector<FrameDev> fds(n);
     std::vector<double> wts;
@@ -400,59 +370,46 @@ int thmr_cropper_run_frames(thmr_cropper* c, const thmr_frame_crop* items, int32
         const thmr_frame_crop& it = items[i];
         const std::string who = "item " + std::to_string(i) + ": ";
         // the warp keeps 16-bit texel coordinates (saturate_cast<short>), which the corner rule below does not model
-        if (it.H <= 0 || it.W <= 0 || it.H > 32767 || it.W > 32767) return bad(who + "bad frame geometry");
+        if (it.H <= 0 || it.W <= 0 || it.H > 32767 || it.W > 32767) return g_crop_err.invalid(c, who + "bad frame geometry");
         if (it.win_x0 < 0 || it.win_y0 < 0 || it.win_w < 0 || it.win_h < 0 || (int64_t)it.win_x0 + it.win_w > it.W ||
             (int64_t)it.win_y0 + it.win_h > it.H)
-            return bad(who + "the window does not lie inside the frame");
-        if (it.row_stride < (int64_t)it.win_w * 3) return bad(who + "row_stride is less than win_w * 3");
+            return g_crop_err.invalid(c, who + "the window does not lie inside the frame");
+        if (it.row_stride < (int64_t)it.win_w * 3) return g_crop_err.invalid(c, who + "row_stride is less than win_w * 3");
         FrameDev& f = fds[i];
         TouchBox box;
         std::string m;
-        if (!prep_crop(it.M, it.sigma, it.truncate, i, patch, it.H, it.W, false, f.c, wts, plan, box, m)) return bad(m);
+        if (!prep_crop(it.M, it.sigma, it.truncate, i, patch, it.H, it.W, false, f.c, wts, plan, box, m)) return g_crop_err.invalid(c, m);
         f.win = nullptr; f.stride = 0; f.H = it.H; f.W = it.W; f.wx0 = f.wy0 = f.ww = f.wh = 0;
         if (box.empty()) continue;          // every output pixel is border: the kernels read nothing of this item
-        if (!it.win_dev) return bad(who + "null window pointer");
+        if (!it.win_dev) return g_crop_err.invalid(c, who + "null window pointer");
         if (box.bx0 < it.win_x0 || box.bx1 >= (int64_t)it.win_x0 + it.win_w || box.by0 < it.win_y0 || box.by1 >= (int64_t)it.win_y0 + it.win_h)
-            return bad(who + "the window does not cover the texels the crop can touch: x " + std::to_string(box.bx0) + ".." +
+            return g_crop_err.invalid(c, who + "the window does not cover the texels the crop can touch: x " + std::to_string(box.bx0) + ".." +
                        std::to_string(box.bx1) + ", y " + std::to_string(box.by0) + ".." + std::to_string(box.by1));
         f.win = it.win_dev; f.stride = it.row_stride; f.wx0 = it.win_x0; f.wy0 = it.win_y0; f.ww = it.win_w; f.wh = it.win_h;
     }
-    if (!c) return bad("null cropper");
+    if (!c) return g_crop_err.invalid(nullptr, "null cropper");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(c->device) != hipSuccess) return bad("hipSetDevice failed");
-    auto hip_bad = [&](const char* what, hipError_t e) { c->err = std::string(what) + ": " + hipGetErrorString(e); g_crop_err = c->err; return THMR_ERR_HIP; };
+    if (hipSetDevice(c->device) != hipSuccess) return g_crop_err.invalid(c, "hipSetDevice failed");
     hipError_t e;
     const size_t desc_bytes = sizeof(FrameDev) * (size_t)n, bytes = desc_bytes + sizeof(double) * wts.size();
-    // grow-only device buffers (re-allocation synchronises the stream first: earlier launches may still read the old ones)
-    if (bytes > c->fds_cap || plan.need > c->scratch_doubles) {
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_bad("hipStreamSynchronize", e);
-        if (bytes > c->fds_cap) {
-            if (c->fds) (void)hipFree(c->fds);
-            c->fds = nullptr; c->fds_cap = 0;
-            if ((e = hipMalloc(&c->fds, bytes * 2)) != hipSuccess) return hip_bad("hipMalloc(frame descriptors)", e);
-            c->fds_cap = bytes * 2;
-        }
-        if (plan.need > c->scratch_doubles) {
-            if (c->scratch) (void)hipFree(c->scratch);
-            c->scratch = nullptr; c->scratch_doubles = 0;
-            if ((e = hipMalloc(&c->scratch, sizeof(double) * plan.need)) != hipSuccess) return hip_bad("hipMalloc(blur scratch)", e);
-            c->scratch_doubles = plan.need;
-        }
-    }
+    const char* what;
+    e = grow_synced(st, {c->fds.want(bytes, bytes * 2, "hipMalloc(frame descriptors)"),
+                         c->scratch.want(plan.need, plan.need, "hipMalloc(blur scratch)")}, what);
+    if (e != hipSuccess) return g_crop_err.hip(c, what, e);
     std::vector<char> host(bytes);
     memcpy(host.data(), fds.data(), desc_bytes);
     if (!wts.empty()) memcpy(host.data() + desc_bytes, wts.data(), sizeof(double) * wts.size());
     // a pageable-host -> device copy returns after staging, so the vector may die at the end of this call
-    if ((e = hipMemcpyAsync(c->fds, host.data(), bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_bad("hipMemcpyAsync", e);
-    const FrameDev* fd = reinterpret_cast<const FrameDev*>(c->fds);
-    const double* wd = reinterpret_cast<const double*>(c->fds + desc_bytes);
+    if ((e = hipMemcpyAsync(c->fds, host.data(), bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return g_crop_err.hip(c, "hipMemcpyAsync", e);
+    const FrameDev* fd = reinterpret_cast<const FrameDev*>(c->fds.ptr());
+    const double* wd = reinterpret_cast<const double*>(c->fds.ptr() + desc_bytes);
     if (plan.max_v > 0) {
         hipLaunchKernelGGL(crop_frames_vpass_kernel, dim3((unsigned)((plan.max_v + 255) / 256), n), dim3(256), 0, st, fd, wd, c->scratch);
         hipLaunchKernelGGL(crop_frames_hpass_kernel, dim3((unsigned)((plan.max_h + 255) / 256), n), dim3(256), 0, st, fd, wd, c->scratch);
     }
     hipLaunchKernelGGL(crop_frames_warp_kernel, dim3((patch * patch + 255) / 256, n), dim3(256), 0, st, fd, c->scratch, patch, swap_rb,
                        mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], out_dev);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_bad("crop kernel launch", e);
+    if ((e = hipGetLastError()) != hipSuccess) return g_crop_err.hip(c, "crop kernel launch", e);
     return 0;
 }
 

@@ -7,13 +7,12 @@
 #include <string>
 #include <vector>
 
-#include "abi_util.h"
+#include "handle_util.h"
 #include "jpeg_host.h"
 
 namespace {
 
-thread_local std::string g_jpeg_err;
-int jfail(thmr_jpeg* j, int code, const std::string& m);
+thread_local ErrorSink<thmr_jpeg> g_jpeg_err{true};      // also behind thmr_last_error(NULL)
 
 // One item as the kernels see it.  Offsets are into the call's staging (coefficients) and the handle's plane scratch.
 struct JpegItemDev {
@@ -103,9 +102,8 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const JpegItemDev* __r
 }
 
 struct Stage {
-    char* host = nullptr;       // pinned
-    char* dev = nullptr;
-    size_t cap = 0;
+    PinnedBuf<char> host;       // both of one capacity
+    DevBuf<char> dev;
     hipEvent_t ev = nullptr;    // behind the last use of this set
     bool recorded = false;
 };
@@ -123,88 +121,76 @@ struct thmr_jpeg {
     int device = 0;
     Stage stage[2];
     int turn = 0;
-    uint8_t* planes = nullptr;
-    size_t planes_cap = 0;
+    DevBuf<uint8_t> planes;
     std::string err;
 };
-
-namespace {
-int jfail(thmr_jpeg* j, int code, const std::string& m) {
-    if (j) j->err = m;
-    g_jpeg_err = m;
-    return fail(code, m);
-}
-}  // namespace
 
 extern "C" {
 
 int thmr_jpeg_probe(const uint8_t* data, size_t len, thmr_jpeg_info* info) {
-    if (!info) return jfail(nullptr, THMR_ERR_INVALID, "null info");
+    if (!info) return g_jpeg_err.invalid(nullptr, "null info");
     memset(info, 0, sizeof(*info));
-    if (!data || len == 0) return jfail(nullptr, THMR_ERR_INVALID, "not a JPEG: empty buffer");
+    if (!data || len == 0) return g_jpeg_err.invalid(nullptr, "not a JPEG: empty buffer");
     jpegh::Header h;
     std::string err;
     const int rc = jpegh::parse_header(data, len, h, err);
-    if (rc) return jfail(nullptr, rc, err);
+    if (rc) return g_jpeg_err.fail(nullptr, rc, err);
     info->height = h.H; info->width = h.W; info->components = h.ncomp;
     info->h_samp = h.hs; info->v_samp = h.vs; info->restart_interval = h.restart_interval;
     info->supported = h.unsupported ? 0 : 1;
-    if (h.unsupported) return jfail(nullptr, THMR_ERR_UNSUPPORTED, "unsupported JPEG: " + h.why);
+    if (h.unsupported) return g_jpeg_err.fail(nullptr, THMR_ERR_UNSUPPORTED, "unsupported JPEG: " + h.why);
     return 0;
 }
 
 int thmr_jpeg_entropy_decode(const uint8_t* data, size_t len, const int32_t* window, int16_t* coef, int64_t coef_capacity_blocks,
                              thmr_jpeg_plan* plan) {
-    if (!plan) return jfail(nullptr, THMR_ERR_INVALID, "null plan");
+    if (!plan) return g_jpeg_err.invalid(nullptr, "null plan");
     memset(plan, 0, sizeof(*plan));
-    if (!data || len == 0) return jfail(nullptr, THMR_ERR_INVALID, "not a JPEG: empty buffer");
+    if (!data || len == 0) return g_jpeg_err.invalid(nullptr, "not a JPEG: empty buffer");
     jpegh::Header h;
     std::string err;
     int rc = parse_supported(data, len, h, err);
-    if (rc) return jfail(nullptr, rc, err);
-    if ((rc = jpegh::make_plan(h, window, *plan, err)) != 0) return jfail(nullptr, rc, err);
+    if (rc) return g_jpeg_err.fail(nullptr, rc, err);
+    if ((rc = jpegh::make_plan(h, window, *plan, err)) != 0) return g_jpeg_err.fail(nullptr, rc, err);
     if (!coef) return 0;
     if (coef_capacity_blocks < plan->n_blocks)
-        return jfail(nullptr, THMR_ERR_INVALID, "the coefficient buffer holds " + std::to_string(coef_capacity_blocks) + " blocks, the window needs " +
+        return g_jpeg_err.invalid(nullptr, "the coefficient buffer holds " + std::to_string(coef_capacity_blocks) + " blocks, the window needs " +
                                                     std::to_string(plan->n_blocks));
-    if ((rc = jpegh::entropy_decode(data, len, h, *plan, coef, err)) != 0) return jfail(nullptr, rc, err);
+    if ((rc = jpegh::entropy_decode(data, len, h, *plan, coef, err)) != 0) return g_jpeg_err.fail(nullptr, rc, err);
     return 0;
 }
 
 int thmr_jpeg_decode_host(const uint8_t* data, size_t len, const int32_t* window, int32_t bgr, uint8_t* out, int64_t row_stride) {
-    if (!data || len == 0) return jfail(nullptr, THMR_ERR_INVALID, "not a JPEG: empty buffer");
+    if (!data || len == 0) return g_jpeg_err.invalid(nullptr, "not a JPEG: empty buffer");
     jpegh::Header h;
     std::string err;
     thmr_jpeg_plan plan;
     int rc = parse_supported(data, len, h, err);
-    if (rc) return jfail(nullptr, rc, err);
-    if ((rc = jpegh::make_plan(h, window, plan, err)) != 0) return jfail(nullptr, rc, err);
+    if (rc) return g_jpeg_err.fail(nullptr, rc, err);
+    if ((rc = jpegh::make_plan(h, window, plan, err)) != 0) return g_jpeg_err.fail(nullptr, rc, err);
     if (plan.n_blocks == 0) return 0;
-    if (!out) return jfail(nullptr, THMR_ERR_INVALID, "null out");
-    if (row_stride < (int64_t)plan.win_w * 3) return jfail(nullptr, THMR_ERR_INVALID, "row_stride is less than win_w * 3");
+    if (!out) return g_jpeg_err.invalid(nullptr, "null out");
+    if (row_stride < (int64_t)plan.win_w * 3) return g_jpeg_err.invalid(nullptr, "row_stride is less than win_w * 3");
     std::vector<int16_t> coef;
     std::vector<uint8_t> planes;
     try {
         coef.resize((size_t)plan.n_blocks * 64);
         planes.resize((size_t)jpegh::plane_bytes(plan));
     } catch (const std::bad_alloc&) {
-        return jfail(nullptr, THMR_ERR_NOMEM, "out of host memory for the coefficient blocks");
+        return g_jpeg_err.fail(nullptr, THMR_ERR_NOMEM, "out of host memory for the coefficient blocks");
     }
-    if ((rc = jpegh::entropy_decode(data, len, h, plan, coef.data(), err)) != 0) return jfail(nullptr, rc, err);
+    if ((rc = jpegh::entropy_decode(data, len, h, plan, coef.data(), err)) != 0) return g_jpeg_err.fail(nullptr, rc, err);
     jpegh::reconstruct(plan, coef.data(), planes.data(), bgr, out, row_stride);
     return 0;
 }
 
-const char* thmr_jpeg_last_error(const thmr_jpeg* j) { return j ? j->err.c_str() : g_jpeg_err.c_str(); }
+const char* thmr_jpeg_last_error(const thmr_jpeg* j) { return g_jpeg_err.read(j); }
 
 int thmr_jpeg_create(int32_t device, thmr_jpeg** out) {
-    if (!out) return jfail(nullptr, THMR_ERR_INVALID, "null out");
+    if (!out) return g_jpeg_err.invalid(nullptr, "null out");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        (void)hipGetLastError();
-        return jfail(nullptr, THMR_ERR_HIP, "no such HIP device (without one, thmr_jpeg_decode_host decodes on the CPU)");
-    }
+    if (!check_device(device))
+        return g_jpeg_err.fail(nullptr, THMR_ERR_HIP, "no such HIP device (without one, thmr_jpeg_decode_host decodes on the CPU)");
     thmr_jpeg* j = new thmr_jpeg();
     j->device = device;
     *out = j;
@@ -214,57 +200,52 @@ int thmr_jpeg_create(int32_t device, thmr_jpeg** out) {
 void thmr_jpeg_destroy(thmr_jpeg* j) {
     if (!j) return;
     (void)hipSetDevice(j->device);
-    for (Stage& s : j->stage) {
+    for (Stage& s : j->stage)
         if (s.ev) { if (s.recorded) (void)hipEventSynchronize(s.ev); (void)hipEventDestroy(s.ev); }
-        if (s.host) (void)hipHostFree(s.host);
-        if (s.dev) (void)hipFree(s.dev);
-    }
-    if (j->planes) (void)hipFree(j->planes);
-    delete j;
+    delete j;          // the buffers free themselves
 }
 
 int thmr_jpeg_decode_batch(thmr_jpeg* j, const thmr_jpeg_item* items, int32_t n, int32_t bgr, void* stream) {
     // every argument is checked before the handle, and the handle before any HIP call: a refusal never touches the device
-    auto bad = [&](const std::string& m) { return jfail(j, THMR_ERR_INVALID, m); };
-    if (n <= 0 || n > 65535) return bad("n must be 1 ... 65535");
-    if (!items) return bad("null item table");
+    if (n <= 0 || n > 65535) return g_jpeg_err.invalid(j, "n must be 1 ... 65535");
+    if (!items) return g_jpeg_err.invalid(j, "null item table");
     std::vector<JpegItemDev> ids((size_t)n);
     int64_t total_blocks = 0, plane_total = 0, coef_total = 0, max_pix = 0;
     for (int i = 0; i < n; ++i) {
         const thmr_jpeg_item& it = items[i];
         const std::string who = "item " + std::to_string(i) + ": ";
-        if (!it.plan) return bad(who + "null plan");
+        if (!it.plan) return g_jpeg_err.invalid(j, who + "null plan");
         const thmr_jpeg_plan& p = *it.plan;
         const bool samp_ok = p.components == 1 ? (p.h_samp == 1 && p.v_samp == 1)
                                                : ((p.h_samp == 1 && p.v_samp == 1) || (p.h_samp == 2 && (p.v_samp == 1 || p.v_samp == 2)));
         if ((p.components != 1 && p.components != 3) || !samp_ok || p.height < 1 || p.width < 1 || p.height > 32767 || p.width > 32767)
-            return bad(who + "the plan's frame geometry / sampling is not one thmr_jpeg_entropy_decode produces");
+            return g_jpeg_err.invalid(j, who + "the plan's frame geometry / sampling is not one thmr_jpeg_entropy_decode produces");
         if (it.win_x0 < 0 || it.win_y0 < 0 || it.win_w < 0 || it.win_h < 0 || (int64_t)it.win_x0 + it.win_w > p.width ||
             (int64_t)it.win_y0 + it.win_h > p.height)
-            return bad(who + "the window does not lie inside the frame");
-        if (it.row_stride < (int64_t)it.win_w * 3) return bad(who + "row_stride is less than win_w * 3");
+            return g_jpeg_err.invalid(j, who + "the window does not lie inside the frame");
+        if (it.row_stride < (int64_t)it.win_w * 3) return g_jpeg_err.invalid(j, who + "row_stride is less than win_w * 3");
         JpegItemDev& d = ids[(size_t)i];
         memset(&d, 0, sizeof(d));
         d.blk0 = (int32_t)total_blocks;
         d.ncomp = p.components; d.hs = p.h_samp; d.vs = p.v_samp;
         d.cw = jpegh::ceil_div(p.width, p.h_samp); d.ch = jpegh::ceil_div(p.height, p.v_samp);
         if (it.win_w == 0 || it.win_h == 0) continue;          // nothing to write: the kernels see an empty item
-        if (!it.out_dev) return bad(who + "null out_dev with a non-empty window");
+        if (!it.out_dev) return g_jpeg_err.invalid(j, who + "null out_dev with a non-empty window");
         int32_t rx0[3], ry0[3], rw[3], rh[3];
         jpegh::required_blocks(p.height, p.width, p.components, p.h_samp, p.v_samp, it.win_x0, it.win_y0, it.win_w, it.win_h, rx0, ry0, rw, rh);
         int64_t blocks = 0;
         for (int c = 0; c < p.components; ++c) {
             const int gw = jpegh::ceil_div(jpegh::ceil_div(p.width, c ? p.h_samp : 1), 8), gh = jpegh::ceil_div(jpegh::ceil_div(p.height, c ? p.v_samp : 1), 8);
             if (p.bx0[c] < 0 || p.by0[c] < 0 || p.bw[c] < 1 || p.bh[c] < 1 || (int64_t)p.bx0[c] + p.bw[c] > gw || (int64_t)p.by0[c] + p.bh[c] > gh)
-                return bad(who + "the plan's block rectangle of component " + std::to_string(c) + " lies outside the component");
+                return g_jpeg_err.invalid(j, who + "the plan's block rectangle of component " + std::to_string(c) + " lies outside the component");
             if (p.bx0[c] > rx0[c] || p.by0[c] > ry0[c] || p.bx0[c] + p.bw[c] < rx0[c] + rw[c] || p.by0[c] + p.bh[c] < ry0[c] + rh[c])
-                return bad(who + "the plan's block rectangle of component " + std::to_string(c) + " does not cover the window");
-            if (p.coef_block[c] != blocks) return bad(who + "the plan's coefficient offsets are not the packed layout");
+                return g_jpeg_err.invalid(j, who + "the plan's block rectangle of component " + std::to_string(c) + " does not cover the window");
+            if (p.coef_block[c] != blocks) return g_jpeg_err.invalid(j, who + "the plan's coefficient offsets are not the packed layout");
             blocks += (int64_t)p.bw[c] * p.bh[c];
         }
-        if (p.n_blocks != blocks) return bad(who + "the plan's block count does not match its rectangles");
-        if (!it.coef) return bad(who + "null coefficients");
-        if (total_blocks + blocks > (int64_t)1 << 28) return bad(who + "more than 2^28 blocks in one batch");
+        if (p.n_blocks != blocks) return g_jpeg_err.invalid(j, who + "the plan's block count does not match its rectangles");
+        if (!it.coef) return g_jpeg_err.invalid(j, who + "null coefficients");
+        if (total_blocks + blocks > (int64_t)1 << 28) return g_jpeg_err.invalid(j, who + "more than 2^28 blocks in one batch");
         d.out = it.out_dev; d.row_stride = it.row_stride;
         d.x0 = it.win_x0; d.y0 = it.win_y0; d.w = it.win_w; d.h = it.win_h;
         d.nblk = (int32_t)blocks;
@@ -277,14 +258,13 @@ int thmr_jpeg_decode_batch(thmr_jpeg* j, const thmr_jpeg_item* items, int32_t n,
         total_blocks += blocks; plane_total += blocks * 64; coef_total += blocks * 64;
         max_pix = std::max<int64_t>(max_pix, (int64_t)it.win_w * it.win_h);
     }
-    if (!j) return bad("null handle");
+    if (!j) return g_jpeg_err.invalid(j, "null handle");
     if (total_blocks == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    auto hip_bad = [&](const char* what, hipError_t e) { return jfail(j, THMR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); };
     hipError_t e;
-    if ((e = hipSetDevice(j->device)) != hipSuccess) return hip_bad("hipSetDevice", e);
+    if ((e = hipSetDevice(j->device)) != hipSuccess) return g_jpeg_err.hip(j, "hipSetDevice", e);
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if ((e = hipStreamIsCapturing(st, &cap)) != hipSuccess) return hip_bad("hipStreamIsCapturing", e);
+    if ((e = hipStreamIsCapturing(st, &cap)) != hipSuccess) return g_jpeg_err.hip(j, "hipStreamIsCapturing", e);
     const bool capturing = cap != hipStreamCaptureStatusNone;
 
     const size_t desc_bytes = (sizeof(JpegItemDev) * (size_t)n + 255) & ~size_t(255);
@@ -293,44 +273,30 @@ int thmr_jpeg_decode_batch(thmr_jpeg* j, const thmr_jpeg_item* items, int32_t n,
     j->turn ^= 1;
     if (!capturing && s.recorded) {
         // the upload and the kernels that last read this set (two calls ago) are done before the host writes it again
-        if ((e = hipEventSynchronize(s.ev)) != hipSuccess) return hip_bad("hipEventSynchronize", e);
+        if ((e = hipEventSynchronize(s.ev)) != hipSuccess) return g_jpeg_err.hip(j, "hipEventSynchronize", e);
         s.recorded = false;
     }
-    if (bytes > s.cap || (size_t)plane_total > j->planes_cap) {
-        if (capturing) return jfail(j, THMR_ERR_STATE, "the staging would grow inside a stream capture: run the call once at these sizes first");
-        // grow-only buffers (re-allocation synchronises the stream first: earlier launches may still read the old ones)
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_bad("hipStreamSynchronize", e);
-        if (bytes > s.cap) {
-            if (s.host) (void)hipHostFree(s.host);
-            if (s.dev) (void)hipFree(s.dev);
-            s.host = s.dev = nullptr; s.cap = 0;
-            const size_t cap_bytes = bytes + bytes / 4;
-            if ((e = hipHostMalloc(reinterpret_cast<void**>(&s.host), cap_bytes, hipHostMallocDefault)) != hipSuccess) return hip_bad("hipHostMalloc(staging)", e);
-            if ((e = hipMalloc(reinterpret_cast<void**>(&s.dev), cap_bytes)) != hipSuccess) return hip_bad("hipMalloc(staging)", e);
-            s.cap = cap_bytes;
-        }
-        if ((size_t)plane_total > j->planes_cap) {
-            if (j->planes) (void)hipFree(j->planes);
-            j->planes = nullptr; j->planes_cap = 0;
-            const size_t cap_bytes = (size_t)plane_total + (size_t)plane_total / 4;
-            if ((e = hipMalloc(reinterpret_cast<void**>(&j->planes), cap_bytes)) != hipSuccess) return hip_bad("hipMalloc(planes)", e);
-            j->planes_cap = cap_bytes;
-        }
-    }
-    if (!s.ev && (e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming)) != hipSuccess) return hip_bad("hipEventCreate", e);
+    const size_t pl = (size_t)plane_total;
+    const auto grow = {s.host.want(bytes, bytes + bytes / 4, "hipHostMalloc(staging)"),
+                       s.dev.want(bytes, bytes + bytes / 4, "hipMalloc(staging)"), j->planes.want(pl, pl + pl / 4, "hipMalloc(planes)")};
+    if (capturing && must_grow(grow))
+        return g_jpeg_err.fail(j, THMR_ERR_STATE, "the staging would grow inside a stream capture: run the call once at these sizes first");
+    const char* what;
+    if ((e = grow_synced(st, grow, what)) != hipSuccess) return g_jpeg_err.hip(j, what, e);
+    if (!s.ev && (e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming)) != hipSuccess) return g_jpeg_err.hip(j, "hipEventCreate", e);
     memcpy(s.host, ids.data(), sizeof(JpegItemDev) * (size_t)n);
-    int16_t* hc = reinterpret_cast<int16_t*>(s.host + desc_bytes);
+    int16_t* hc = reinterpret_cast<int16_t*>(s.host.ptr() + desc_bytes);
     for (int i = 0; i < n; ++i)
         if (ids[(size_t)i].nblk) memcpy(hc + ids[(size_t)i].coef_off, items[i].coef, (size_t)ids[(size_t)i].nblk * 128);
-    if ((e = hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_bad("hipMemcpyAsync", e);
-    const JpegItemDev* idev = reinterpret_cast<const JpegItemDev*>(s.dev);
-    const int16_t* cdev = reinterpret_cast<const int16_t*>(s.dev + desc_bytes);
+    if ((e = hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return g_jpeg_err.hip(j, "hipMemcpyAsync", e);
+    const JpegItemDev* idev = reinterpret_cast<const JpegItemDev*>(s.dev.ptr());
+    const int16_t* cdev = reinterpret_cast<const int16_t*>(s.dev.ptr() + desc_bytes);
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((total_blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS)), dim3(256), 0, st, idev, n, cdev,
                        j->planes, (int)total_blocks);
     hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pix + 255) / 256), (unsigned)n), dim3(256), 0, st, idev, j->planes, bgr ? 1 : 0);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_bad("jpeg kernel launch", e);
+    if ((e = hipGetLastError()) != hipSuccess) return g_jpeg_err.hip(j, "jpeg kernel launch", e);
     if (!capturing) {
-        if ((e = hipEventRecord(s.ev, st)) != hipSuccess) return hip_bad("hipEventRecord", e);
+        if ((e = hipEventRecord(s.ev, st)) != hipSuccess) return g_jpeg_err.hip(j, "hipEventRecord", e);
         s.recorded = true;
     }
     return 0;

@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tokenhmr_hip.h"
+#include "handle_util.h"
 
 #pragma clang fp contract(off)
 
@@ -60,23 +60,21 @@ struct Params {
     Light L[THMR_RENDER_MAX_LIGHTS];
 };
 
-struct Scratch {
-    float* pos = nullptr;          // (N, V, 3) camera frame
-    int2* fix = nullptr;           // (N, V) snapped u, v; x = INT_MIN: vertex unusable
-    float* nrm = nullptr;          // (N, V, 3)
-    FaceRec* rec = nullptr;        // (N, F)
-    uint32_t* cnt = nullptr;       // (T) tile counts, then (T + 1) offsets, (T) cursors, (n_img) large counts
-    uint32_t* off = nullptr;
-    uint32_t* cur = nullptr;
-    uint32_t* lcnt = nullptr;
-    uint32_t* bins = nullptr;      // (N F SMALL_TILES)
-    uint32_t* large = nullptr;     // (N F)
-    float* colors = nullptr;       // (N, 3)
+struct Scratch {                   // grow-only, sized exactly
+    DevBuf<float> pos;             // (N, V, 3) camera frame
+    DevBuf<int2> fix;              // (N, V) snapped u, v; x = INT_MIN: vertex unusable
+    DevBuf<float> nrm;             // (N, V, 3)
+    DevBuf<FaceRec> rec;           // (N, F)
+    DevBuf<uint32_t> cnt;          // (T) tile counts, then (T + 1) offsets, (T) cursors, (n_img) large counts
+    DevBuf<uint32_t> off;
+    DevBuf<uint32_t> cur;
+    DevBuf<uint32_t> lcnt;
+    DevBuf<uint32_t> bins;         // (N F SMALL_TILES)
+    DevBuf<uint32_t> large;        // (N F)
+    DevBuf<float> colors;          // (N, 3)
 };
 
-std::string g_render_err;
-
-int rfail(int code, const std::string& m) { g_render_err = m; return code; }
+thread_local ErrorSink<thmr_renderer> g_render_err;
 
 __device__ __forceinline__ int64_t edge(int32_t ax, int32_t ay, int32_t bx, int32_t by, int32_t px, int32_t py) {
     return (int64_t)(bx - ax) * (int64_t)(py - ay) - (int64_t)(by - ay) * (int64_t)(px - ax);
@@ -407,43 +405,31 @@ __global__ void __launch_bounds__(256) render_raster_kernel(Params p, const int3
         for (int s = 0; s < S; ++s) ids_out[pix * S + s] = bid[s];
 }
 
-template <typename T>
-hipError_t grow(T*& ptr, size_t& cap, size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr; cap = 0;
-    hipError_t e = hipMalloc(&ptr, sizeof(T) * n);
-    if (e == hipSuccess) cap = n;
-    return e;
-}
-
 }  // namespace
 
 struct thmr_renderer {
     int device = 0;
     int32_t F = 0, V = 0;
-    int32_t* faces = nullptr;      // (F, 3) device
-    int32_t* csr_off = nullptr;    // (V + 1)
-    int32_t* csr = nullptr;        // (3F) face << 2 | corner, by vertex, face-ascending
+    DevBuf<int32_t> faces;         // (F, 3) device
+    DevBuf<int32_t> csr_off;       // (V + 1)
+    DevBuf<int32_t> csr;           // (3F) face << 2 | corner, by vertex, face-ascending
     Scratch s;
-    size_t cap_pos = 0, cap_fix = 0, cap_nrm = 0, cap_rec = 0, cap_cnt = 0, cap_off = 0, cap_cur = 0, cap_lcnt = 0, cap_bins = 0,
-           cap_large = 0, cap_colors = 0;
     std::string err;
 };
 
 extern "C" {
 
-const char* thmr_renderer_last_error(const thmr_renderer* r) { return r ? r->err.c_str() : g_render_err.c_str(); }
+const char* thmr_renderer_last_error(const thmr_renderer* r) { return g_render_err.read(r); }
 
 int thmr_renderer_create(int32_t device, const int32_t* faces_host, int32_t F, int32_t V, thmr_renderer** out) {
-    if (!out) return rfail(THMR_ERR_INVALID, "null out");
+    if (!out) return g_render_err.invalid(nullptr, "null out");
     *out = nullptr;
-    if (!faces_host) return rfail(THMR_ERR_INVALID, "null faces");
-    if (F <= 0 || V <= 0 || V > (1 << 28) || F > (1 << 28)) return rfail(THMR_ERR_INVALID, "bad face / vertex count");
+    if (!faces_host) return g_render_err.invalid(nullptr, "null faces");
+    if (F <= 0 || V <= 0 || V > (1 << 28) || F > (1 << 28)) return g_render_err.invalid(nullptr, "bad face / vertex count");
     std::vector<int32_t> cnt((size_t)V + 1, 0);
     for (int64_t k = 0; k < (int64_t)F * 3; ++k) {
         const int32_t v = faces_host[k];
-        if (v < 0 || v >= V) return rfail(THMR_ERR_INVALID, "face " + std::to_string(k / 3) + " indexes vertex " + std::to_string(v) +
+        if (v < 0 || v >= V) return g_render_err.invalid(nullptr, "face " + std::to_string(k / 3) + " indexes vertex " + std::to_string(v) +
                                                             " outside [0, " + std::to_string(V) + ")");
         ++cnt[v + 1];
     }
@@ -451,24 +437,20 @@ int thmr_renderer_create(int32_t device, const int32_t* faces_host, int32_t F, i
     std::vector<int32_t> csr((size_t)F * 3), fill(cnt.begin(), cnt.end() - 1);
     for (int32_t f = 0; f < F; ++f)
         for (int c = 0; c < 3; ++c) csr[fill[faces_host[(int64_t)f * 3 + c]]++] = (f << 2) | c;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        (void)hipGetLastError();
-        return rfail(THMR_ERR_HIP, "no such HIP device (the render kernels have no CPU fallback)");
-    }
-    if (hipSetDevice(device) != hipSuccess) return rfail(THMR_ERR_HIP, "hipSetDevice failed");
+    if (!check_device(device)) return g_render_err.fail(nullptr, THMR_ERR_HIP, "no such HIP device (the render kernels have no CPU fallback)");
+    if (hipSetDevice(device) != hipSuccess) return g_render_err.fail(nullptr, THMR_ERR_HIP, "hipSetDevice failed");
     thmr_renderer* r = new thmr_renderer();
     r->device = device; r->F = F; r->V = V;
-    hipError_t e = hipMalloc(&r->faces, sizeof(int32_t) * (size_t)F * 3);
-    if (e == hipSuccess) e = hipMalloc(&r->csr_off, sizeof(int32_t) * ((size_t)V + 1));
-    if (e == hipSuccess) e = hipMalloc(&r->csr, sizeof(int32_t) * (size_t)F * 3);
+    hipError_t e = r->faces.reserve((size_t)F * 3, (size_t)F * 3);
+    if (e == hipSuccess) e = r->csr_off.reserve((size_t)V + 1, (size_t)V + 1);
+    if (e == hipSuccess) e = r->csr.reserve((size_t)F * 3, (size_t)F * 3);
     if (e == hipSuccess) e = hipMemcpy(r->faces, faces_host, sizeof(int32_t) * (size_t)F * 3, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(r->csr_off, cnt.data(), sizeof(int32_t) * ((size_t)V + 1), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(r->csr, csr.data(), sizeof(int32_t) * (size_t)F * 3, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         const std::string m = std::string("renderer setup: ") + hipGetErrorString(e);
         thmr_renderer_destroy(r);
-        return rfail(THMR_ERR_HIP, m);
+        return g_render_err.fail(nullptr, THMR_ERR_HIP, m);
     }
     *out = r;
     return 0;
@@ -477,34 +459,33 @@ int thmr_renderer_create(int32_t device, const int32_t* faces_host, int32_t F, i
 void thmr_renderer_destroy(thmr_renderer* r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
-    void* bufs[] = {r->faces, r->csr_off, r->csr, r->s.pos, r->s.fix, r->s.nrm, r->s.rec, r->s.cnt, r->s.off, r->s.cur, r->s.lcnt,
-                    r->s.bins, r->s.large, r->s.colors};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    delete r;
+    delete r;          // the buffers free themselves
 }
 
 int thmr_renderer_run(thmr_renderer* r, const thmr_render_desc* d, const float* verts_dev, const float* cam_t_dev, int32_t N,
                       const float* bg_dev, float* out_dev, void* stream) {
-    if (!r) return rfail(THMR_ERR_INVALID, "null renderer");
-    auto bad = [&](const std::string& m) { r->err = m; g_render_err = m; return THMR_ERR_INVALID; };
-    if (!d || !verts_dev || !cam_t_dev || !out_dev) return bad("null descriptor or buffer");
-    if (d->width < 1 || d->height < 1 || d->width > 8192 || d->height > 8192) return bad("image size must be 1 ... 8192 per side");
-    if (d->samples != 1 && d->samples != 4) return bad("samples must be 1 or 4");
-    if (N < 1) return bad("N must be >= 1");
-    if (d->mode != THMR_RENDER_PER_IMAGE && d->mode != THMR_RENDER_ONE_IMAGE) return bad("mode must be THMR_RENDER_PER_IMAGE or THMR_RENDER_ONE_IMAGE");
-    if (d->out_channels != 3 && d->out_channels != 4) return bad("out_channels must be 3 or 4");
-    if (bg_dev && d->out_channels != 3) return bad("compositing over background images writes 3 channels");
-    if (d->n_lights < 0 || d->n_lights > THMR_RENDER_MAX_LIGHTS) return bad("n_lights must be 0 ... THMR_RENDER_MAX_LIGHTS");
-    if ((int64_t)N * r->F * SMALL_TILES >= (int64_t)NONE || (int64_t)N * r->V * 3 >= ((int64_t)1 << 40)) return bad("too many meshes");
+    if (!r) return g_render_err.invalid(nullptr, "null renderer");
+    if (!d || !verts_dev || !cam_t_dev || !out_dev) return g_render_err.invalid(r, "null descriptor or buffer");
+    if (d->width < 1 || d->height < 1 || d->width > 8192 || d->height > 8192)
+        return g_render_err.invalid(r, "image size must be 1 ... 8192 per side");
+    if (d->samples != 1 && d->samples != 4) return g_render_err.invalid(r, "samples must be 1 or 4");
+    if (N < 1) return g_render_err.invalid(r, "N must be >= 1");
+    if (d->mode != THMR_RENDER_PER_IMAGE && d->mode != THMR_RENDER_ONE_IMAGE)
+        return g_render_err.invalid(r, "mode must be THMR_RENDER_PER_IMAGE or THMR_RENDER_ONE_IMAGE");
+    if (d->out_channels != 3 && d->out_channels != 4) return g_render_err.invalid(r, "out_channels must be 3 or 4");
+    if (bg_dev && d->out_channels != 3) return g_render_err.invalid(r, "compositing over background images writes 3 channels");
+    if (d->n_lights < 0 || d->n_lights > THMR_RENDER_MAX_LIGHTS) return g_render_err.invalid(r, "n_lights must be 0 ... THMR_RENDER_MAX_LIGHTS");
+    if ((int64_t)N * r->F * SMALL_TILES >= (int64_t)NONE || (int64_t)N * r->V * 3 >= ((int64_t)1 << 40))
+        return g_render_err.invalid(r, "too many meshes");
     const float fl[] = {d->fx, d->fy, d->cx, d->cy};
     for (float v : fl)
-        if (!std::isfinite(v)) return bad("non-finite intrinsics");
-    if (!(d->znear > 0.f) || !std::isfinite(d->znear)) return bad("znear must be a positive number");
+        if (!std::isfinite(v)) return g_render_err.invalid(r, "non-finite intrinsics");
+    if (!(d->znear > 0.f) || !std::isfinite(d->znear)) return g_render_err.invalid(r, "znear must be a positive number");
     for (int k = 0; k < 9; ++k)
-        if (!std::isfinite(d->rot[k])) return bad("non-finite rotation");
+        if (!std::isfinite(d->rot[k])) return g_render_err.invalid(r, "non-finite rotation");
     for (int i = 0; i < d->n_lights; ++i)
-        if (d->lights[i].type != THMR_LIGHT_DIRECTIONAL && d->lights[i].type != THMR_LIGHT_POINT) return bad("light " + std::to_string(i) + ": unknown type");
+        if (d->lights[i].type != THMR_LIGHT_DIRECTIONAL && d->lights[i].type != THMR_LIGHT_POINT)
+            return g_render_err.invalid(r, "light " + std::to_string(i) + ": unknown type");
 
     Params p{};
     p.W = d->width; p.H = d->height; p.S = d->samples; p.mode = d->mode; p.tr_first = d->translate_first ? 1 : 0;
@@ -526,27 +507,20 @@ int thmr_renderer_run(thmr_renderer* r, const thmr_render_desc* d, const float* 
     const int64_t T = (int64_t)p.n_img * p.tiles_x * p.tiles_y;
     const size_t NV = (size_t)N * r->V, NF = (size_t)N * r->F;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(r->device) != hipSuccess) return bad("hipSetDevice failed");
-    auto hip_bad = [&](const char* what, hipError_t e) { r->err = std::string(what) + ": " + hipGetErrorString(e); g_render_err = r->err; return THMR_ERR_HIP; };
+    if (hipSetDevice(r->device) != hipSuccess) return g_render_err.invalid(r, "hipSetDevice failed");
     hipError_t e;
     Scratch& s = r->s;
-    // grow-only scratch; growing synchronises the stream first (earlier launches may still use the old buffers)
-    if (NV * 3 > r->cap_pos || NV > r->cap_fix || NF > r->cap_rec || (size_t)T > r->cap_cnt || (size_t)T + 1 > r->cap_off ||
-        (size_t)p.n_img > r->cap_lcnt || NF * SMALL_TILES > r->cap_bins || (size_t)N * 3 > r->cap_colors) {
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_bad("hipStreamSynchronize", e);
-        if ((e = grow(s.pos, r->cap_pos, NV * 3)) != hipSuccess || (e = grow(s.nrm, r->cap_nrm, NV * 3)) != hipSuccess ||
-            (e = grow(s.fix, r->cap_fix, NV)) != hipSuccess || (e = grow(s.rec, r->cap_rec, NF)) != hipSuccess ||
-            (e = grow(s.cnt, r->cap_cnt, (size_t)T)) != hipSuccess || (e = grow(s.off, r->cap_off, (size_t)T + 1)) != hipSuccess ||
-            (e = grow(s.cur, r->cap_cur, (size_t)T)) != hipSuccess || (e = grow(s.lcnt, r->cap_lcnt, (size_t)p.n_img)) != hipSuccess ||
-            (e = grow(s.bins, r->cap_bins, NF * SMALL_TILES)) != hipSuccess || (e = grow(s.large, r->cap_large, NF)) != hipSuccess ||
-            (e = grow(s.colors, r->cap_colors, (size_t)N * 3)) != hipSuccess)
-            return hip_bad("hipMalloc(render scratch)", e);
-    }
+    const char* what;
+    auto exact = [](auto& buf, size_t n) { return buf.want(n, n, "hipMalloc(render scratch)"); };
+    if ((e = grow_synced(st, {exact(s.pos, NV * 3), exact(s.nrm, NV * 3), exact(s.fix, NV), exact(s.rec, NF), exact(s.cnt, (size_t)T),
+                              exact(s.off, (size_t)T + 1), exact(s.cur, (size_t)T), exact(s.lcnt, (size_t)p.n_img),
+                              exact(s.bins, NF * SMALL_TILES), exact(s.large, NF), exact(s.colors, (size_t)N * 3)}, what)) != hipSuccess)
+        return g_render_err.hip(r, what, e);
     if (d->mesh_colors &&
         (e = hipMemcpyAsync(s.colors, d->mesh_colors, sizeof(float) * (size_t)N * 3, hipMemcpyHostToDevice, st)) != hipSuccess)
-        return hip_bad("hipMemcpyAsync(mesh colours)", e);
-    if ((e = hipMemsetAsync(s.cnt, 0, sizeof(uint32_t) * (size_t)T, st)) != hipSuccess) return hip_bad("hipMemsetAsync", e);
-    if ((e = hipMemsetAsync(s.lcnt, 0, sizeof(uint32_t) * (size_t)p.n_img, st)) != hipSuccess) return hip_bad("hipMemsetAsync", e);
+        return g_render_err.hip(r, "hipMemcpyAsync(mesh colours)", e);
+    if ((e = hipMemsetAsync(s.cnt, 0, sizeof(uint32_t) * (size_t)T, st)) != hipSuccess) return g_render_err.hip(r, "hipMemsetAsync", e);
+    if ((e = hipMemsetAsync(s.lcnt, 0, sizeof(uint32_t) * (size_t)p.n_img, st)) != hipSuccess) return g_render_err.hip(r, "hipMemsetAsync", e);
     const unsigned gv = (unsigned)((NV + 255) / 256), gf = (unsigned)((NF + 255) / 256);
     hipLaunchKernelGGL(render_vertex_kernel, dim3(gv), dim3(256), 0, st, p, verts_dev, cam_t_dev, s.pos, s.fix);
     hipLaunchKernelGGL(render_normal_kernel, dim3(gv), dim3(256), 0, st, p, r->faces, r->csr_off, r->csr, s.pos, s.nrm);
@@ -560,7 +534,7 @@ int thmr_renderer_run(thmr_renderer* r, const thmr_render_desc* d, const float* 
     else
         hipLaunchKernelGGL(render_raster_kernel<1>, grid, dim3(256), 0, st, p, r->faces, s.pos, s.fix, s.nrm, s.colors, s.rec, s.off,
                            s.bins, s.lcnt, s.large, bg_dev, out_dev, d->ids_dev);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_bad("render kernel launch", e);
+    if ((e = hipGetLastError()) != hipSuccess) return g_render_err.hip(r, "render kernel launch", e);
     return 0;
 }
 
@@ -769,18 +743,19 @@ extern "C" {
 
 int thmr_renderer_sheet(thmr_renderer* r, const thmr_sheet_desc* d, const float* images_dev, const float* front_dev, const float* side_dev,
                         const float* pred_kp_dev, float* gt_kp_dev, int32_t* records_dev, float* canvas_dev, void* stream) {
-    if (!r) return rfail(THMR_ERR_INVALID, "null renderer");
-    auto bad = [&](const std::string& m) { r->err = m; g_render_err = m; return THMR_ERR_INVALID; };
-    if (!d || !images_dev || !canvas_dev) return bad("null descriptor or buffer");
-    if (d->n < 1 || d->n > (1 << 20)) return bad("n must be 1 ... 2^20 people");
-    if (d->width < 1 || d->height < 1 || d->width > 8192 || d->height > 8192) return bad("image size must be 1 ... 8192 per side");
-    if (d->img_res < 1 || d->img_res > 8192) return bad("img_res must be 1 ... 8192");
-    if (d->nrow < 1 || d->padding < 0 || d->padding > 4096) return bad("nrow must be >= 1 and padding 0 ... 4096");
-    if (d->panels & ~(THMR_SHEET_IMAGE | THMR_SHEET_FRONT | THMR_SHEET_SIDE)) return bad("unknown panel bit");
-    if (((d->panels & THMR_SHEET_FRONT) && !front_dev) || ((d->panels & THMR_SHEET_SIDE) && !side_dev)) return bad("a requested mesh panel has no render");
-    if ((pred_kp_dev || gt_kp_dev) && !records_dev) return bad("skeleton panels need the records buffer");
+    if (!r) return g_render_err.invalid(nullptr, "null renderer");
+    if (!d || !images_dev || !canvas_dev) return g_render_err.invalid(r, "null descriptor or buffer");
+    if (d->n < 1 || d->n > (1 << 20)) return g_render_err.invalid(r, "n must be 1 ... 2^20 people");
+    if (d->width < 1 || d->height < 1 || d->width > 8192 || d->height > 8192)
+        return g_render_err.invalid(r, "image size must be 1 ... 8192 per side");
+    if (d->img_res < 1 || d->img_res > 8192) return g_render_err.invalid(r, "img_res must be 1 ... 8192");
+    if (d->nrow < 1 || d->padding < 0 || d->padding > 4096) return g_render_err.invalid(r, "nrow must be >= 1 and padding 0 ... 4096");
+    if (d->panels & ~(THMR_SHEET_IMAGE | THMR_SHEET_FRONT | THMR_SHEET_SIDE)) return g_render_err.invalid(r, "unknown panel bit");
+    if (((d->panels & THMR_SHEET_FRONT) && !front_dev) || ((d->panels & THMR_SHEET_SIDE) && !side_dev))
+        return g_render_err.invalid(r, "a requested mesh panel has no render");
+    if ((pred_kp_dev || gt_kp_dev) && !records_dev) return g_render_err.invalid(r, "skeleton panels need the records buffer");
     if (reinterpret_cast<uintptr_t>(records_dev) % 16 || reinterpret_cast<uintptr_t>(front_dev) % 16 || reinterpret_cast<uintptr_t>(side_dev) % 16)
-        return bad("records and RGBA buffers must be 16-byte aligned");
+        return g_render_err.invalid(r, "records and RGBA buffers must be 16-byte aligned");
     SheetParams p{};
     p.B = d->n; p.W = d->width; p.H = d->height; p.img_res = d->img_res; p.pad = d->padding;
     p.has_pred = pred_kp_dev ? 1 : 0; p.has_gt = gt_kp_dev ? 1 : 0;
@@ -789,28 +764,28 @@ int thmr_renderer_sheet(thmr_renderer* r, const thmr_sheet_desc* d, const float*
     if (d->panels & THMR_SHEET_SIDE) p.kind[p.n_panels++] = PANEL_SIDE;
     if (p.has_pred) p.kind[p.n_panels++] = PANEL_PRED;
     if (p.has_gt) p.kind[p.n_panels++] = PANEL_GT;
-    if (!p.n_panels) return bad("no panel requested");
+    if (!p.n_panels) return g_render_err.invalid(r, "no panel requested");
     // torchvision.utils.make_grid(list, nrow, padding), pad value 0
     const int64_t tiles = (int64_t)p.B * p.n_panels;
     const int64_t xmaps = std::min<int64_t>(d->nrow, tiles), ymaps = (tiles + xmaps - 1) / xmaps;
     const int64_t Wg = xmaps * (p.W + p.pad) + p.pad, Hg = ymaps * (p.H + p.pad) + p.pad;
-    if (Wg > (1 << 24) || Hg > (1 << 24)) return bad("canvas beyond 2^24 per side");
+    if (Wg > (1 << 24) || Hg > (1 << 24)) return g_render_err.invalid(r, "canvas beyond 2^24 per side");
     if (d->canvas_width != Wg || d->canvas_height != Hg)
-        return bad("canvas must be " + std::to_string(Hg) + " x " + std::to_string(Wg) + " for these tiles");
+        return g_render_err.invalid(r, "canvas must be " + std::to_string(Hg) + " x " + std::to_string(Wg) + " for these tiles");
     p.xmaps = (int32_t)xmaps; p.ymaps = (int32_t)ymaps; p.Wg = (int32_t)Wg; p.Hg = (int32_t)Hg;
     p.vec = (Wg % 4 == 0 && reinterpret_cast<uintptr_t>(canvas_dev) % 16 == 0) ? 1 : 0;
     p.thick = std::sqrt((double)((int64_t)p.W * 3)) * (1.0 / 75.0);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(r->device) != hipSuccess) return bad("hipSetDevice failed");
+    if (hipSetDevice(r->device) != hipSuccess) return g_render_err.invalid(r, "hipSetDevice failed");
     const int n_skel = (p.has_pred + p.has_gt) * p.B;
     if (n_skel) hipLaunchKernelGGL(sheet_build_kernel, dim3((unsigned)n_skel), dim3(64), 0, st, p, pred_kp_dev, gt_kp_dev, records_dev);
     const int64_t items = (int64_t)(((p.W + 2 * p.pad + 3) >> 2) + 1) * (p.H + 2 * p.pad);
     const int64_t cells = xmaps * ymaps;
-    if (cells > 65535) return bad("more than 65535 grid cells");
+    if (cells > 65535) return g_render_err.invalid(r, "more than 65535 grid cells");
     hipLaunchKernelGGL(sheet_kernel, dim3((unsigned)((items + 255) / 256), (unsigned)cells), dim3(256), 0, st, p, images_dev, front_dev, side_dev,
                        records_dev, canvas_dev);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { r->err = std::string("sheet kernel launch: ") + hipGetErrorString(e); g_render_err = r->err; return THMR_ERR_HIP; }
+    if (e != hipSuccess) return g_render_err.hip(r, "sheet kernel launch", e);
     return 0;
 }
 

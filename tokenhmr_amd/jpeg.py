@@ -25,9 +25,11 @@ class JpegUnsupported(JpegError):
     """A well-formed file of a kind the decoder does not handle (THMR_ERR_UNSUPPORTED); the message names what was found."""
 
 
-def _raise(lib, rc, what, handle=None):
-    msg = (lib.thmr_jpeg_last_error(handle) or b"?").decode()
-    raise (JpegUnsupported if rc == _cabi.ERR_UNSUPPORTED else JpegError)(f"{what} error {rc}: {msg}")
+_BY_CODE = {_cabi.ERR_UNSUPPORTED: JpegUnsupported}
+
+
+def _raise(lib, rc, what):
+    _cabi.raise_error(rc, what, lib.thmr_jpeg_last_error(None), JpegError, _BY_CODE)
 
 
 def _buf(data):
@@ -100,34 +102,15 @@ def decode_host(data, window=None, bgr=True, lib=None):
     return out
 
 
-class JpegDecoder:
+class JpegDecoder(_cabi.Handle):
     """Owns a thmr_jpeg handle: two grow-only sets of pinned + device staging, used alternately, and the component-plane scratch.
     One stream at a time; a call captured in a graph keeps reading its staging set, so give a captured call a decoder of its own."""
+    error, error_by_code = JpegError, _BY_CODE
 
     def __init__(self, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("JpegDecoder needs a GPU device; decode_host() is the CPU decode")
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        self.lib = _cabi.load()
-        h = C.c_void_p()
-        rc = self.lib.thmr_jpeg_create(idx, C.byref(h))
-        if rc != 0:
-            _raise(self.lib, rc, "thmr_jpeg_create")
-        self.h = h
+        super().__init__(device, "thmr_jpeg", "JpegDecoder needs a GPU device; decode_host() is the CPU decode")
         self.last_coef_bytes = 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.thmr_jpeg_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(self._index())
 
     def decode_planned(self, planned, bgr=True, out=None, row_strides=None):
         """Items already entropy-decoded (in worker threads) -> one device tensor (win_h, win_w, 3) uint8 each, in ONE batch call on the
@@ -157,8 +140,7 @@ class JpegDecoder:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             rc = self.lib.thmr_jpeg_decode_batch(self.h, items, n, int(bool(bgr)), C.c_void_p(stream.cuda_stream))
-        if rc != 0:
-            _raise(self.lib, rc, "thmr_jpeg_decode_batch", self.h)
+        self._check(rc, "thmr_jpeg_decode_batch")
         return out
 
     def decode(self, datas, windows=None, bgr=True):

@@ -106,6 +106,11 @@ def source_window(M, patch, H, W, sigma=0.0, truncate=3.0):
     return x0, y0, x1 - x0 + 1, y1 - y0 + 1
 
 
+def _scaled(triple):
+    """mean / std of 0 ... 1 pixel values as the kernels take them: float32(255 v), three of them."""
+    return (C.c_float * 3)(*[np.float32(255.0 * v) for v in triple])
+
+
 class _Staging:
     """One set of staging buffers of warp_frames: pinned host bytes, their device twin, and the event behind their last use."""
 
@@ -113,38 +118,21 @@ class _Staging:
         self.host = self.dev = self.event = None
 
 
-class Cropper:
+class Cropper(_cabi.Handle):
     """Owns a thmr_cropper handle (device scratch for blurred regions) and, for warp_frames, two grow-only sets of staging buffers."""
 
     def __init__(self, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("Cropper needs a GPU device: the crop kernels have no CPU fallback")
-        # 'cuda' without an index means the CURRENT device (like Engine), not device 0
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
-        self.lib = _cabi.load()
-        h = C.c_void_p()
-        rc = self.lib.thmr_cropper_create(idx, C.byref(h))
-        if rc != 0:
-            raise _cabi.EngineError(f"thmr_cropper_create: {self.lib.thmr_cropper_last_error(None).decode()}")
-        self.h = h
+        super().__init__(device, "thmr_cropper", "Cropper needs a GPU device: the crop kernels have no CPU fallback")
         self._stage, self._turn = (_Staging(), _Staging()), 0
         self.last_staged_bytes = 0
+        self._open(self._index())
 
     def close(self):
         if getattr(self, "h", None):
-            for st in self._stage:
+            for st in self._stage:          # the copies and kernels that read the staging are done before anything is freed
                 if st.event is not None:
                     st.event.synchronize()
-            self.lib.thmr_cropper_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     def to_device(self, frame):
         """(H, W, 3) uint8 numpy array or tensor -> contiguous device tensor (one H2D copy per frame, shared by its crops)."""
@@ -164,19 +152,37 @@ class Cropper:
         for i in range(n):
             descs[i].M[:] = trans[i].tolist()
             descs[i].sigma, descs[i].truncate = float(sig[i]), float(truncate)
-        m = (C.c_float * 3)(*[np.float32(255.0 * v) for v in mean])
-        s = (C.c_float * 3)(*[np.float32(255.0 * v) for v in std])
-        if out is None:
-            out = torch.empty(n, 3, patch, patch, device=self.device, dtype=torch.float32)
-        elif out.shape != (n, 3, patch, patch) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous (n,3,patch,patch) float32 tensor on the cropper's device")
+        out = self._out(out, n, patch)
         H, W = int(fr.shape[0]), int(fr.shape[1])
         with torch.cuda.device(self.device):
-            rc = self.lib.thmr_cropper_run(self.h, C.c_void_p(fr.data_ptr()), H, W, W * 3, descs, n, int(patch), int(bool(is_bgr)), m, s,
-                                           C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise _cabi.EngineError(f"thmr_cropper_run error {rc}: {self.lib.thmr_cropper_last_error(self.h).decode()}")
+            rc = self.lib.thmr_cropper_run(self.h, C.c_void_p(fr.data_ptr()), H, W, W * 3, descs, n, int(patch), int(bool(is_bgr)),
+                                           _scaled(mean), _scaled(std), C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        self._check(rc, "thmr_cropper_run")
         return out
+
+    def _out(self, out, n, patch):
+        """The caller's output tensor, validated, or a fresh one."""
+        if out is None:
+            return torch.empty(n, 3, patch, patch, device=self.device, dtype=torch.float32)
+        if out.shape != (n, 3, patch, patch) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("out must be a contiguous (n,3,patch,patch) float32 tensor on the cropper's device")
+        return out
+
+    @staticmethod
+    def _item(it, win_dev, stride, size, win, M, sigma, truncate):
+        """Fills one thmr_frame_crop; an empty window carries no pointer."""
+        x0, y0, w, h = win
+        it.win_dev = win_dev if w * h else None
+        it.row_stride, it.H, it.W = stride, int(size[0]), int(size[1])
+        it.win_x0, it.win_y0, it.win_w, it.win_h = x0, y0, w, h
+        it.M[:] = M.tolist()
+        it.sigma, it.truncate = float(sigma), float(truncate)
+
+    def _run_frames(self, items, n, patch, is_bgr, mean, std, out, stream):
+        """thmr_cropper_run_frames on `stream` of this device; the caller raises through _check once its own bookkeeping is done."""
+        return self.lib.thmr_cropper_run_frames(self.h, items, n, int(patch), int(bool(is_bgr)), _scaled(mean), _scaled(std),
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
 
     def warp_frames(self, frames, trans, sigmas=None, truncate=3.0, patch=256, mean=DEFAULT_MEAN, std=DEFAULT_STD, is_bgr=True,
                     windows=True, out=None, extra=None):
@@ -242,31 +248,18 @@ class Cropper:
         self.last_staged_bytes = total
         items = (_cabi.FrameCrop * n)()
         for i, fr in enumerate(frames):
-            x0, y0, w, h = wins[i]
-            it = items[i]
-            it.win_dev = st.dev.data_ptr() + offs[i] if w * h else None
-            it.row_stride, it.H, it.W = w * 3, fr.shape[0], fr.shape[1]
-            it.win_x0, it.win_y0, it.win_w, it.win_h = x0, y0, w, h
-            it.M[:] = trans[i].tolist()
-            it.sigma, it.truncate = float(sig[i]), float(truncate)
-        m = (C.c_float * 3)(*[np.float32(255.0 * v) for v in mean])
-        s = (C.c_float * 3)(*[np.float32(255.0 * v) for v in std])
-        if out is None:
-            out = torch.empty(n, 3, patch, patch, device=self.device, dtype=torch.float32)
-        elif out.shape != (n, 3, patch, patch) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous (n,3,patch,patch) float32 tensor on the cropper's device")
+            self._item(items[i], st.dev.data_ptr() + offs[i], wins[i][2] * 3, fr.shape[:2], wins[i], trans[i], sig[i], truncate)
+        out = self._out(out, n, patch)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             if total:
                 st.dev[:total].copy_(st.host[:total], non_blocking=True)
-            rc = self.lib.thmr_cropper_run_frames(self.h, items, n, int(patch), int(bool(is_bgr)), m, s, C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(stream.cuda_stream))
+            rc = self._run_frames(items, n, patch, is_bgr, mean, std, out, stream)
             extra_dev = st.dev[extra_off:extra_off + extra.size].clone() if extra is not None else None
             if st.event is None:
                 st.event = torch.cuda.Event()
             st.event.record(stream)
-        if rc != 0:
-            raise _cabi.EngineError(f"thmr_cropper_run_frames error {rc}: {self.lib.thmr_cropper_last_error(self.h).decode()}")
+        self._check(rc, "thmr_cropper_run_frames")
         return out if extra is None else (out, extra_dev)
 
     def warp_device_windows(self, windows_dev, frame_sizes, wins, trans, sigmas=None, truncate=3.0, patch=256, mean=DEFAULT_MEAN,
@@ -291,23 +284,11 @@ class Cropper:
                     raise ValueError(f"item {i}: the window must be a contiguous uint8 tensor on {self.device}")
                 if t.numel() < (h - 1) * stride + w * 3:
                     raise ValueError(f"item {i}: the tensor holds {t.numel()} bytes, the window needs {(h - 1) * stride + w * 3}")
-            it = items[i]
-            it.win_dev = t.data_ptr() if w * h else None
-            it.row_stride, it.H, it.W = stride, int(frame_sizes[i][0]), int(frame_sizes[i][1])
-            it.win_x0, it.win_y0, it.win_w, it.win_h = x0, y0, w, h
-            it.M[:] = trans[i].tolist()
-            it.sigma, it.truncate = float(sig[i]), float(truncate)
-        m = (C.c_float * 3)(*[np.float32(255.0 * v) for v in mean])
-        s = (C.c_float * 3)(*[np.float32(255.0 * v) for v in std])
-        if out is None:
-            out = torch.empty(n, 3, patch, patch, device=self.device, dtype=torch.float32)
-        elif out.shape != (n, 3, patch, patch) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("out must be a contiguous (n,3,patch,patch) float32 tensor on the cropper's device")
+            self._item(items[i], t.data_ptr() if w * h else None, stride, frame_sizes[i], (x0, y0, w, h), trans[i], sig[i], truncate)
+        out = self._out(out, n, patch)
         with torch.cuda.device(self.device):
-            rc = self.lib.thmr_cropper_run_frames(self.h, items, n, int(patch), int(bool(is_bgr)), m, s, C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise _cabi.EngineError(f"thmr_cropper_run_frames error {rc}: {self.lib.thmr_cropper_last_error(self.h).decode()}")
+            rc = self._run_frames(items, n, patch, is_bgr, mean, std, out, torch.cuda.current_stream(self.device))
+        self._check(rc, "thmr_cropper_run_frames")
         return out
 
 

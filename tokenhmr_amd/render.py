@@ -29,6 +29,7 @@ from . import _cabi
 ZNEAR = 0.05            # faces with a vertex nearer than this are rejected (no clipping: DESIGN.md §3.6)
 AMBIENT = (0.3, 0.3, 0.3)
 MAX_SIZE = 8192
+_NEEDS_GPU = "Renderer needs a GPU device: the render kernels have no CPU fallback"
 
 
 # ------------------------------------------------------------------------------------------------ the reference's scene arithmetic
@@ -230,13 +231,19 @@ class Mesh:
 
 
 # ------------------------------------------------------------------------------------------------ the renderer
+class _Handle(_cabi.Handle):
+    """One thmr_renderer: the vertex -> face lists of `faces` for meshes of V vertices, and its grow-only scratch."""
+
+    def __init__(self, device, faces, V):
+        super().__init__(device, "thmr_renderer", _NEEDS_GPU)
+        self._open(self._index(), faces.ctypes.data, faces.shape[0], V)
+
+
 class Renderer:
     """renderer.py:137-396 on the GPU.  Owns one thmr_renderer handle per vertex count (the vertex -> face lists)."""
 
     def __init__(self, cfg, faces, device="cuda:0", samples=4):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("Renderer needs a GPU device: the render kernels have no CPU fallback")
+        dev = _Handle.cuda_device(device, _NEEDS_GPU, resolve=False)
         if samples not in (1, 4):
             raise ValueError("samples must be 1 or 4")
         self.cfg = cfg
@@ -247,32 +254,23 @@ class Renderer:
         self.samples = samples
         self._faces32 = check_faces(faces)
         self._max_index = int(self._faces32.max())
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
+        self.device = _Handle.cuda_device(dev, _NEEDS_GPU, resolve=True)
         self.lib = _cabi.load()
         self._handles = {}
 
     def close(self):
-        for h in getattr(self, "_handles", {}).values():
-            self.lib.thmr_renderer_destroy(h)
+        for h in self._handles.values():
+            h.close()
         self._handles = {}
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _owner(self, V):
+        """The _Handle for meshes of V vertices, created on first use; it is destroyed by close() or with this object."""
+        if V not in self._handles:
+            self._handles[V] = _Handle(self.device, self._faces32, V)
+        return self._handles[V]
 
     def _handle(self, V):
-        h = self._handles.get(V)
-        if h is None:
-            h = C.c_void_p()
-            f = self._faces32
-            rc = self.lib.thmr_renderer_create(self.device.index, f.ctypes.data, f.shape[0], V, C.byref(h))
-            if rc != 0:
-                raise _cabi.EngineError(f"thmr_renderer_create: {self.lib.thmr_renderer_last_error(None).decode()}")
-            self._handles[V] = h
-        return h
+        return self._owner(V).h
 
     def _run(self, scene, vertices, cam_t, mode, out_channels, images=None, mesh_colors=None, mean=(0, 0, 0), std=(1, 1, 1),
              return_ids=False):
@@ -293,11 +291,10 @@ class Renderer:
         d = make_desc(scene, self.samples, mode, out_channels, colors, mean, std, ids)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            h = self._handle(V)
-            rc = self.lib.thmr_renderer_run(h, C.byref(d), v.data_ptr(), t.data_ptr(), N, img.data_ptr() if img is not None else None,
+            owner = self._owner(V)
+            rc = self.lib.thmr_renderer_run(owner.h, C.byref(d), v.data_ptr(), t.data_ptr(), N, img.data_ptr() if img is not None else None,
                                             out.data_ptr(), stream)
-        if rc != 0:
-            raise _cabi.EngineError(f"thmr_renderer_run: {self.lib.thmr_renderer_last_error(h).decode()}")
+        owner._check(rc, "thmr_renderer_run")
         return (out, ids) if return_ids else out
 
     # ---- batched device paths
@@ -416,9 +413,7 @@ class MeshRenderer:
     host and nothing synchronises."""
 
     def __init__(self, cfg, faces=None, device="cuda:0", samples=4):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("MeshRenderer needs a GPU device: the render kernels have no CPU fallback")
+        dev = _Handle.cuda_device(device, "MeshRenderer needs a GPU device: the render kernels have no CPU fallback", resolve=False)
         if samples not in (1, 4):
             raise ValueError("samples must be 1 or 4")
         self.cfg = cfg
@@ -460,11 +455,10 @@ class MeshRenderer:
         ptr = lambda t: t.data_ptr() if t is not None else None
         with torch.cuda.device(r.device):
             stream = torch.cuda.current_stream(r.device).cuda_stream
-            h = r._handle(n_verts)                     # the handle the two renders ran on
-            rc = r.lib.thmr_renderer_sheet(h, C.byref(d), images.data_ptr(), ptr(front), ptr(side), ptr(pred), ptr(gt), ptr(records),
+            owner = r._owner(n_verts)                  # the handle the two renders ran on
+            rc = r.lib.thmr_renderer_sheet(owner.h, C.byref(d), images.data_ptr(), ptr(front), ptr(side), ptr(pred), ptr(gt), ptr(records),
                                            canvas.data_ptr(), stream)
-        if rc != 0:
-            raise _cabi.EngineError(f"thmr_renderer_sheet: {r.lib.thmr_renderer_last_error(h).decode()}")
+        owner._check(rc, "thmr_renderer_sheet")
         return canvas, records
 
     def __call__(self, vertices, camera_translation, image, focal_length=5000, text=None, resize=None, side_view=False,

@@ -17,14 +17,11 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-class SMPL:
+class SMPL(_cabi.Handle):
+    no_gpu_error = _cabi.EngineError
+
     def __init__(self, constants, max_batch=64, device="cuda:0"):
-        self.lib = _cabi.load()
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _cabi.EngineError("tokenhmr_amd.smpl.SMPL runs on a HIP device only")
-        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self.device = torch.device("cuda", idx)
+        super().__init__(device, "thmr_smpl", "tokenhmr_amd.smpl.SMPL runs on a HIP device only", last_error="thmr_last_error")
         self.max_batch = int(max_batch)
         keys = ["v_template", "shapedirs", "posedirs", "J_regressor", "lbs_weights", "J19_regressor"]
         ikeys = ["parents", "extra_verts", "joint_map"]
@@ -32,21 +29,8 @@ class SMPL:
         ts.update({k: constants[k].detach().to(torch.int32).contiguous().cpu() for k in ikeys})
         d = _cabi.SmplDesc(**{k: ts[k].data_ptr() for k in keys + ikeys}, on_device=0,
                            update_hips=1 if constants.get("update_hips", False) else 0)
-        h = C.c_void_p(0)
-        _cabi.check(self.lib.thmr_smpl_create(C.byref(d), self.max_batch, idx, C.byref(h)))
-        self.h = h
+        self._open(C.byref(d), self.max_batch, self._index())
         self.faces = constants.get("faces")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.thmr_smpl_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def forward(self, global_orient, body_pose, betas, pose2rot=True):
         """pose2rot=True: axis-angle (B,3)+(B,69) (smplx.SMPL); False: rotation matrices (B,1,3,3)+(B,23,3,3) (SMPLLayer)."""
@@ -61,7 +45,8 @@ class SMPL:
         joints = torch.empty(B, 44, 3, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _cabi.check(self.lib.thmr_smpl_forward(self.h, _p(pose), 1 if pose2rot else 0, _p(betas), B, _p(verts), _p(joints), st))
+            self._check(self.lib.thmr_smpl_forward(self.h, _p(pose), 1 if pose2rot else 0, _p(betas), B, _p(verts), _p(joints), st),
+                        "thmr_smpl_forward")
         return types.SimpleNamespace(vertices=verts, joints=joints)
 
     __call__ = forward

@@ -45,7 +45,9 @@ def _constants(model, num_betas, ext, gender):
     return load_smplh_pkl(path, num_betas)
 
 
-class _SMPLHBase:
+class _SMPLHBase(_cabi.Handle):
+    no_gpu_error = _cabi.EngineError
+
     def __init__(self, model_path_or_constants, num_betas=10, ext="pkl", gender="neutral", use_pca=True, num_pca_comps=6,
                  flat_hand_mean=False, *, max_batch=64, device="cuda:0"):
         if num_betas != 10:
@@ -64,44 +66,25 @@ class _SMPLHBase:
         for k, s in shapes.items():
             if tuple(constants[k].shape) != s:
                 raise ValueError(f"SMPL-H constant '{k}' has shape {tuple(constants[k].shape)}, the kernels are built for {s}")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _cabi.EngineError("tokenhmr_amd.smplh runs on a HIP device only")
+        super().__init__(device, "thmr_smplh", "tokenhmr_amd.smplh runs on a HIP device only", last_error="thmr_last_error")
         self.max_batch = int(max_batch)
         self.faces = constants.get("faces")
         self.folded_calls = self.full_calls = 0
         self._host = constants
-        self.h = None
-        self.lib = _cabi.load()
 
     def _handle(self):
         """The device handle, created by the first forward: construction and every argument check need no GPU."""
         if self.h is None:
-            idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            self.device = torch.device("cuda", idx)
             c = self._host
             ts = {k: c[k].detach().float().contiguous().cpu() for k in _KEYS}
             ts.update({k: c[k].detach().to(torch.int32).contiguous().cpu() for k in _IKEYS})
             d = _cabi.SmplhDesc(**{k: ts[k].data_ptr() for k in _KEYS + _IKEYS}, on_device=0)
-            h = C.c_void_p(0)
-            _cabi.check(self.lib.thmr_smplh_create(C.byref(d), self.max_batch, idx, C.byref(h)), lib=self.lib)
-            self.h = h
+            self._open(C.byref(d), self.max_batch, self._index())
             self._on_device()
         return self.h
 
     def _on_device(self):
         pass
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.thmr_smplh_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # nn.Module surface the callers touch
     def cuda(self, device=None):
@@ -120,7 +103,7 @@ class _SMPLHBase:
         return B
 
     @staticmethod
-    def _check(t, B, n, name):
+    def _sized(t, B, n, name):
         if t is not None and t.numel() != B * n:
             raise ValueError(f"{name} expects {n} values per item, got shape {tuple(t.shape)}")
 
@@ -132,8 +115,8 @@ class _SMPLHBase:
         joints = torch.empty(B, 73, 3, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _cabi.check(self.lib.thmr_smplh_forward(self._handle(), _p(pose), 1 if pose2rot else 0, _p(betas), _p(transl), 1 if body_only else 0, B,
-                                                    _p(verts), _p(joints), st), lib=self.lib)
+            self._check(self.lib.thmr_smplh_forward(self._handle(), _p(pose), 1 if pose2rot else 0, _p(betas), _p(transl), 1 if body_only else 0, B,
+                                                    _p(verts), _p(joints), st), "thmr_smplh_forward")
         if body_only:
             self.folded_calls += 1
         else:
@@ -152,7 +135,7 @@ class SMPLHLayer(_SMPLHBase):
         B = self._batch(betas, global_orient, body_pose, left_hand_pose, right_hand_pose, transl)
         for t, n, name in ((global_orient, 9, "global_orient"), (body_pose, 21 * 9, "body_pose"), (left_hand_pose, 15 * 9, "left_hand_pose"),
                            (right_hand_pose, 15 * 9, "right_hand_pose"), (betas, 10, "betas"), (transl, 3, "transl")):
-            self._check(t, B, n, name)
+            self._sized(t, B, n, name)
         self._handle()
 
         def rot(t, n):
@@ -200,7 +183,7 @@ class SMPLH(_SMPLHBase):
         nh = self.num_pca_comps if self.use_pca else 45
         for t, n, name in ((global_orient, 3, "global_orient"), (body_pose, 63, "body_pose"), (left_hand_pose, nh, "left_hand_pose"),
                            (right_hand_pose, nh, "right_hand_pose"), (betas, 10, "betas"), (transl, 3, "transl")):
-            self._check(t, B, n, name)
+            self._sized(t, B, n, name)
         self._handle()
         zeros = lambda n: torch.zeros(B, n, device=self.device, dtype=torch.float32)      # noqa: E731
         go, bp = self._opt(global_orient, B, 3), self._opt(body_pose, B, 63)
