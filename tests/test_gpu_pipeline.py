@@ -3,9 +3,19 @@ frame + boxes -> crops (N2, tokenhmr_amd.preprocess) -> TokenHMR forward (the ho
 meshes (N1 evaluator, N3 stand-alone SMPL) — compared with the same pipeline assembled from the CPU oracles
 (oracle.crop_oracle -> oracle.tokenhmr_oracle.forward -> oracle.eval_oracle).  north_star asks MPJPE parity within
 +-0.1 mm; asserted here at 0.02 mm."""
+import json
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+from conftest import GOLDEN_DIR, ROOT
+
+if os.path.join(ROOT, "scripts") not in sys.path:
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import gen_golden_prof_accounting as PA      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -522,3 +532,45 @@ def test_forward_is_captured_into_a_hip_graph_and_replays_bit_identically(built_
                 for k in keys:
                     assert torch.equal(outs[k], w[k]), (mode, B, rep, k)
         eng.status()
+
+
+@pytest.mark.parametrize("case", PA.CASES, ids=[c["name"] for c in PA.CASES])
+def test_profiler_accounting_is_pinned(built_lib, cuda_dev, case):
+    """Every ProfScope of csrc/engine.hip records a class, flops and bytes computed on the host from the call's shapes and the plan: after one
+    thmr_forward, launches / flops / bytes of EVERY profiler class equal what the library of the commit named in
+    tests/golden/prof_accounting.json reported for the same call (scripts/gen_golden_prof_accounting.py) — exactly: nothing here is
+    measured, `ms` is never compared.  A census of the launch sequence per class and of the accounting formulas in every regime of
+    vit_plan.h, both modes, both heads, the every-fourth-fc1 sampling of profiler mode "fc1", and the experiments library's
+    THMR_SPLIT3_SMALL path — which is also held to the oracle here, under test_small_vs_oracle's bounds (nothing else runs it on the GPU)."""
+    with open(os.path.join(GOLDEN_DIR, "prof_accounting.json")) as f:
+        golden = json.load(f)
+    assert [{k: v for k, v in c.items() if k != "expect"} for c in golden["cases"]] == list(PA.CASES), "the fixture's cases are not the script's"
+    assert (golden["dec_depth"], golden["max_batch"]) == (PA.DEC_DEPTH, PA.MAX_BATCH) and golden["commit"]
+    expect = next(c["expect"] for c in golden["cases"] if c["name"] == case["name"])
+    inputs = PA.case_inputs(case)
+    prof, out = PA.run_case(case, cuda_dev, {"shipped": None, "exp": True}, inputs)
+    assert set(prof) == set(expect)
+    assert any(v["launches"] for v in expect.values())
+    for cls in expect:
+        got = {k: prof[cls][k] for k in ("launches", "flops", "bytes")}
+        print(f"[{case['name']}] {cls}: {got}")
+        assert got == expect[cls], (case["name"], cls, got, expect[cls])
+    if case["env"].get("THMR_SPLIT3_SMALL") != "1":
+        return
+    from oracle import tokenhmr_oracle as O
+    from test_gpu_model import _check_against
+    cfg, sd, tok, smpl, img = inputs
+    with torch.no_grad():
+        orc = O.forward(img, sd, tok, smpl, cfg)
+    o = {k: v.cpu() for k, v in out.items()}
+    o["pred_smpl_params"] = {"global_orient": o["rotmat"][:, :1], "body_pose": o["rotmat"][:, 1:], "betas": o["betas"]}
+    top2 = orc["cls_logits"].topk(2, dim=-1).values
+    ref = dict(vit_features=orc["vit_features"], token_out=orc["token_out"], cls_logits=orc["cls_logits"],
+               rotmat=torch.cat([orc["pred_smpl_params"]["global_orient"], orc["pred_smpl_params"]["body_pose"]], 1),
+               betas=orc["pred_smpl_params"]["betas"], cam=orc["pred_cam"], verts=orc["pred_vertices"],
+               joints=orc["pred_keypoints_3d"], kp2d=orc["pred_keypoints_2d"], token_idx=orc["token_idx"])
+    _check_against(o, ref, top2[..., 0] - top2[..., 1], case["name"] + " vs oracle")
+    assert torch.allclose(o["cls_logits_softmax"], orc["cls_logits_softmax"], atol=1e-5)
+    assert torch.allclose(o["pred_cam_t"], orc["pred_cam_t"], rtol=1e-4, atol=1e-3)
+    assert torch.equal(o["focal_length"], orc["focal_length"])
+    assert torch.allclose(o["pose6d"].reshape(orc["pose6d"].shape), orc["pose6d"], atol=1e-4)

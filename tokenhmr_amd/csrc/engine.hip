@@ -69,13 +69,17 @@ struct thmr_engine {
     size_t wfloats = 0, sfloats = 0;
     std::unordered_map<std::string, Slot> slots;
     std::vector<std::string> required;
-    std::vector<VitBlockW> vitw;      // filled by thmr_finalize_weights
-    DecParams dec{};                  // decoder weight pointers + scratch, resolved once (finalize)
+    std::vector<VitBlockW> vitw;      // filled by resolve_weights (thmr_finalize_weights)
+    DecParams dec{};                  // decoder weight pointers + scratch, resolved once (finalize); the launch-chain head reads them too
     MixerParams mix{};                // MLP-Mixer stack weight pointers
-    struct HotW {                     // every other weight the default path touches, resolved once (no name hashing per call)
+    // every other weight a call touches.  With vitw, dec and mix this is ALL of them: resolve_weights (thmr_finalize_weights) is the only
+    // place behind the layout and the load that looks a tensor up by name, and no call path builds or hashes a name
+    struct HotW {
         const float *pe_w, *pe_b, *pos, *lastn_w, *lastn_b, *cls_w, *cls_b, *init_pose, *init_betas, *init_cam;
         const float* conv_b[9];       // biases of the nine k = 3 convs of the VQ decoder, execution order (kConv3)
         const float *res_w[2], *res_b[2];   // the two 1x1 convs of the ResConv blocks
+        const float* codebook;        // quantizer.codebook (2048, 256); null on an HMR2 engine
+        const float *enc_w[11], *enc_b[11];   // tokenizer encoder, execution order (kEnc): the REPACKED weights where ks > 1; null unless enc_ready
     } hot{};
     bool counted = false;             // registered in the per-device engine count (decoder turnstile)
     bool hmr2 = false;                // THMR_CFG_HEAD_HMR2: the HMR2.0 regressor head (stacked read-out + finish) instead of the token head
@@ -276,7 +280,7 @@ const EncConv kEnc[] = {
     {"encoder.encoder.14.1.model.1.conv2", VQW, VQW, VQW, 1},
     {"encoder.encoder.15", VQW, VQW, CODE, 3},                 // -> (B,160,256)
 };
-constexpr int kEncN = 11;
+constexpr int kEncN = 11;      // = the length of thmr_engine::HotW::enc_w / enc_b
 
 // the token head's read-outs as one (31,1024) matrix + (31) biases, from `off` (= o_ro_w); returns the offset behind them
 size_t layout_readout_token(thmr_engine* e, size_t off) {
@@ -488,190 +492,106 @@ int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipSt
         }
     }
     const float qscale = 1.0f / sqrtf(80.0f);   // head_dim ** -0.5  (vit.py:101)
-    const float* lastn_w = e->hot.lastn_w;
-    const float* lastn_b = e->hot.lastn_b;
-    if (plan.path == THMR_VIT_PATH_SPLIT3) {
-        const int ks_proj = plan.proj.ksplit, ks_fc2 = plan.fc2.ksplit;
-        float* part2 = plan.part2_in_scratch ? part : reinterpret_cast<float*>(e->split_act + (size_t)e->max_batch * TOK * (DIM + MLP) * 6);
-        // The four GEMMs as split3 products on the bf16 matrix pipe (csrc/gemm_split.hip); everything else — patch embed, attention,
-        // LayerNorm arithmetic, epilogues — is the fp32 path's.  A operands: the LayerNorms, the attention kernel and fc1's GELU epilogue
-        // write their results directly as three bf16 pieces (hs, bs): no conversion pass, no fp32 copy of those activations.
-        char* hs = e->split_act;                                    // [M][1280] split3: LayerNorm / attention output
-        char* bs = e->split_act + (size_t)M * DIM * 6;              // [M][5120] split3: GELU output
-        // an unsplit split3 product with an fp32 result (qkv, proj, fc2)
-        auto gemm_s = [&](int cls, GemmChoice c, const char* A, int K, const char* Wt, const float* bias, const float* resid, float* C, int N, int epi, int a_blk = 0) -> int {
-            ProfScope ps(e, st, cls, 2.0 * M * (double)N * K, 6.0 * ((double)M * K + (double)N * K) + 4.0 * M * N * (resid ? 2.0 : 1.0));
-            GemmArgs a = mk(reinterpret_cast<const float*>(A), K, reinterpret_cast<const float*>(Wt), K, bias, resid, N, C, N, M, N, K);
-            a.qscale = qscale; a.qcols = DIM;
-            a.a_blk = a_blk;
-            a.tile_opts = plan.tile_opts;
-            return run_gemm(e, c, a, epi, nullptr, st);
-        };
-        // ... and one whose K sum is split into the planes of `dst` (proj, fc2), reduced by the residual + LayerNorm kernel
-        auto gemm_s_splitk = [&](int cls, GemmChoice c, const char* A, int K, const char* Wt, float* dst) -> int {
-            ProfScope ps(e, st, cls, 2.0 * M * DIM * (double)K, 6.0 * ((double)M * K + (double)DIM * K) + 4.0 * c.ksplit * M * DIM);
-            GemmArgs a = mk(reinterpret_cast<const float*>(A), K, reinterpret_cast<const float*>(Wt), K, nullptr, nullptr, 0, x, DIM, M, DIM, K);
-            a.tile_opts = plan.tile_opts;
-            return run_gemm(e, c, a, EPI_NONE, dst, st);
-        };
-        {
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 10.0 * M * DIM);
-            LAUNCH_OK(launch_layernorm_split3(x, e->vitw[0].n1w, e->vitw[0].n1b, hs, M, DIM, VIT_EPS, st));
-        }
-        for (int i = 0; i < e->vit_depth; ++i) {
-            const VitBlockW& w = e->vitw[i];
-            const thmr_engine::SplitW& ws = e->vitw_s[i];
-            const bool last = i + 1 == e->vit_depth;
-            LAUNCH_OK(gemm_s(THMR_PROF_GEMM_QKV, plan.qkv, hs, DIM, ws.qkv, w.qkvb, nullptr, big, 3 * DIM, EPI_BIAS_QSCALE));
-            {   // attention, its output written directly as proj's split3 operand
-                ProfScope ps(e, st, THMR_PROF_ATTN, 4.0 * B * HEADS * 192.0 * 192.0 * 80.0, 4.0 * (3.0 * M * DIM) + 6.0 * M * DIM);
-                if (plan.attn == THMR_ATTN_B16) LAUNCH_OK(launch_vit_attention_b16(big, hs, B, true, 0, st));
-                else LAUNCH_OK(launch_vit_attention_split3(big, hs, B, st));
-            }
-            if (ks_proj > 1) {
-                LAUNCH_OK(gemm_s_splitk(THMR_PROF_GEMM_PROJ, plan.proj, hs, DIM, ws.proj, part));
-                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks_proj + 2.0) * M * DIM + 6.0 * M * DIM);
-                LAUNCH_OK(launch_splitk_resid_ln(part, ks_proj, M, DIM, w.pb, x, x, w.n2w, w.n2b, reinterpret_cast<float*>(hs), VIT_EPS, st, true));
-            } else {
-                LAUNCH_OK(gemm_s(THMR_PROF_GEMM_PROJ, plan.proj, hs, DIM, ws.proj, w.pb, x, x, DIM, EPI_BIAS_RESID));
-                ProfScope ps(e, st, THMR_PROF_LN, 0, 10.0 * M * DIM);
-                LAUNCH_OK(launch_layernorm_split3(x, w.n2w, w.n2b, hs, M, DIM, VIT_EPS, st));
-            }
-            {   // fc1 + exact GELU, written directly as fc2's split3 operand (no fp32 copy of the hidden activations exists)
-                ProfScope ps(e, st, THMR_PROF_GEMM_FC1, 2.0 * M * DIM * (double)MLP, 6.0 * ((double)M * DIM + (double)DIM * MLP + (double)M * MLP));
-                GemmArgs a = mk(reinterpret_cast<const float*>(hs), DIM, reinterpret_cast<const float*>(ws.fc1), DIM, w.f1b, nullptr, 0, nullptr, 0, M, MLP, DIM);
-                a.c_split = bs; a.ldcs = MLP;
-                a.cs_blk = plan.bs_blk;
-                a.tile_opts = plan.tile_opts;
-                LAUNCH_OK(run_gemm(e, plan.fc1, a, EPI_BIAS_GELU, nullptr, st));
-            }
-            if (ks_fc2 > 1) {
-                LAUNCH_OK(gemm_s_splitk(THMR_PROF_GEMM_FC2, plan.fc2, bs, MLP, ws.fc2, part2));
-                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks_fc2 + 3.0) * M * DIM);
-                if (last)
-                    LAUNCH_OK(launch_splitk_resid_ln(part2, ks_fc2, M, DIM, w.f2b, x, x, lastn_w, lastn_b, feats_out ? feats_out : h, VIT_EPS, st));
-                else
-                    LAUNCH_OK(launch_splitk_resid_ln(part2, ks_fc2, M, DIM, w.f2b, x, x, e->vitw[i + 1].n1w, e->vitw[i + 1].n1b,
-                                                     reinterpret_cast<float*>(hs), VIT_EPS, st, true));
-            } else {
-                LAUNCH_OK(gemm_s(THMR_PROF_GEMM_FC2, plan.fc2, bs, MLP, ws.fc2, w.f2b, x, x, DIM, EPI_BIAS_RESID, plan.bs_blk));
-                ProfScope ps(e, st, THMR_PROF_LN, 0, 10.0 * M * DIM);
-                if (last) LAUNCH_OK(launch_layernorm(x, lastn_w, lastn_b, feats_out ? feats_out : h, M, DIM, VIT_EPS, 0, st));
-                else LAUNCH_OK(launch_layernorm_split3(x, e->vitw[i + 1].n1w, e->vitw[i + 1].n1b, hs, M, DIM, VIT_EPS, st));
-            }
-        }
-        return 0;
-    }
-#ifdef THMR_EXPERIMENTS
-    if (plan.path == THMR_VIT_PATH_SPLIT3_SMALL) {
-        // EXPERIMENT (THMR_SPLIT3_SMALL=1, off by default): a small-batch regime (up to six crops) of the split3 mode — the ring kernel
-        // on split3 operands (64 x 64 tiles, 4-deep LDS-DMA ring; proj / fc2 split K four ways into `part`, reduced by the residual +
-        // LayerNorm kernel as in the fp32 regime), producers writing split3 operands directly.  A wave's MFMA chain per K tile shrinks from
-        // 16 x 64 to 12 x 32 cycles, but the call gets SLOWER: 4.28 vs 3.89 ms at one crop, 6.88 vs 5.84 at two, 16.3 vs 14.1 at six
-        // (profiles/r3y_split3_small_batch_regime_ab.log).  At these sizes the GEMMs are bound by the bytes a CU can keep in flight
-        // (three 24 KB stages) against a ~4 us loaded memory round trip, not by the matrix pipe, and split3 operands are 1.5x the bytes.
-        const int ks_proj = plan.proj.ksplit, ks_fc2 = plan.fc2.ksplit;
-        char* hs = e->split_act;
-        char* bs = e->split_act + (size_t)M * DIM * 6;
-        auto sgemm = [&](const char* A, int K, const char* Wt, const float* bias, float* C, int N) {
-            return mk(reinterpret_cast<const float*>(A), K, reinterpret_cast<const float*>(Wt), K, bias, nullptr, 0, C, N, M, N, K);
-        };
-        {
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 10.0 * M * DIM);
-            LAUNCH_OK(launch_layernorm_split3(x, e->vitw[0].n1w, e->vitw[0].n1b, hs, M, DIM, VIT_EPS, st));
-        }
-        for (int i = 0; i < e->vit_depth; ++i) {
-            const VitBlockW& w = e->vitw[i];
-            const thmr_engine::SplitW& ws = e->vitw_s[i];
-            const bool last = i + 1 == e->vit_depth;
-            {
-                ProfScope ps(e, st, THMR_PROF_GEMM_QKV, 2.0 * M * DIM * 3.0 * DIM, 6.0 * ((double)M * DIM + 3.0 * DIM * DIM) + 12.0 * M * DIM);
-                GemmArgs a = sgemm(hs, DIM, ws.qkv, w.qkvb, big, 3 * DIM);
-                a.qscale = qscale; a.qcols = DIM;
-                LAUNCH_OK(run_gemm(e, plan.qkv, a, EPI_BIAS_QSCALE, nullptr, st));
-            }
-            {
-                ProfScope ps(e, st, THMR_PROF_ATTN, 4.0 * B * HEADS * 192.0 * 192.0 * 80.0, 4.0 * (3.0 * M * DIM) + 6.0 * M * DIM);
-                LAUNCH_OK(launch_vit_attention_split3(big, hs, B, st));
-            }
-            {
-                ProfScope ps(e, st, THMR_PROF_GEMM_PROJ, 2.0 * M * DIM * (double)DIM, 6.0 * ((double)M * DIM + (double)DIM * DIM) + 4.0 * ks_proj * M * DIM);
-                GemmArgs a = sgemm(hs, DIM, ws.proj, nullptr, x, DIM);
-                LAUNCH_OK(run_gemm(e, plan.proj, a, EPI_NONE, part, st));
-            }
-            {
-                ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks_proj + 2.0) * M * DIM + 6.0 * M * DIM);
-                LAUNCH_OK(launch_splitk_resid_ln(part, ks_proj, M, DIM, w.pb, x, x, w.n2w, w.n2b, reinterpret_cast<float*>(hs), VIT_EPS, st, true));
-            }
-            {
-                ProfScope ps(e, st, THMR_PROF_GEMM_FC1, 2.0 * M * DIM * (double)MLP, 6.0 * ((double)M * DIM + (double)DIM * MLP + (double)M * MLP), (i & 3) == 0);
-                GemmArgs a = sgemm(hs, DIM, ws.fc1, w.f1b, nullptr, MLP);
-                a.c_split = bs; a.ldcs = MLP;
-                LAUNCH_OK(run_gemm(e, plan.fc1, a, EPI_BIAS_GELU, nullptr, st));
-            }
-            {
-                ProfScope ps(e, st, THMR_PROF_GEMM_FC2, 2.0 * M * DIM * (double)MLP, 6.0 * ((double)M * MLP + (double)DIM * MLP) + 4.0 * ks_fc2 * M * DIM);
-                GemmArgs a = sgemm(bs, MLP, ws.fc2, nullptr, x, DIM);
-                LAUNCH_OK(run_gemm(e, plan.fc2, a, EPI_NONE, part, st));
-            }
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (ks_fc2 + 3.0) * M * DIM);
-            if (last)
-                LAUNCH_OK(launch_splitk_resid_ln(part, ks_fc2, M, DIM, w.f2b, x, x, lastn_w, lastn_b, feats_out ? feats_out : h, VIT_EPS, st));
-            else
-                LAUNCH_OK(launch_splitk_resid_ln(part, ks_fc2, M, DIM, w.f2b, x, x, e->vitw[i + 1].n1w, e->vitw[i + 1].n1b,
-                                                 reinterpret_cast<float*>(hs), VIT_EPS, st, true));
-        }
-        return 0;
-    }
-#endif  // THMR_EXPERIMENTS
-    // x += Linear(A) + bias;  y = LayerNorm(x)      (vit.py:149 / :150 followed by the next norm): K split into `part` (few crops on the ring
-    // kernel, the mid range on the big tiles) and reduced by the residual + LayerNorm kernel, or unsplit with the residual in the epilogue
-    auto resid_linear_ln = [&](int cls, GemmChoice c, const float* A, int K, const float* Wt, const float* bias, const float* g, const float* bt, float* y) -> int {
-        const bool split = c.ksplit > 1;
-        {
-            ProfScope ps(e, st, cls, 2.0 * M * DIM * (double)K, 4.0 * ((double)M * K + (double)DIM * K + 2.0 * M * DIM));
-            GemmArgs a = split ? mk(A, K, Wt, K, nullptr, nullptr, 0, x, DIM, M, DIM, K) : mk(A, K, Wt, K, bias, x, DIM, x, DIM, M, DIM, K);
-            LAUNCH_OK(run_gemm(e, c, a, split ? EPI_NONE : EPI_BIAS_RESID, part, st));
-        }
-        if (split) {
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (c.ksplit + 3.0) * M * DIM);
-            LAUNCH_OK(launch_splitk_resid_ln(part, c.ksplit, M, DIM, bias, x, x, g, bt, y, VIT_EPS, st));
-        } else {
-            ProfScope ps(e, st, THMR_PROF_LN, 0, 8.0 * M * DIM);
-            LAUNCH_OK(launch_layernorm(x, g, bt, y, M, DIM, VIT_EPS, 0, st));
-        }
+    // What the plan's three paths differ in.  Every step of a block is written ONCE below, in terms of this; which kernel a GEMM or the
+    // attention runs, and every split factor, is the plan's.
+    //   THMR_VIT_PATH_F32: exact-fp32 MFMA; the operands h and big live in the scratch arena.
+    //   THMR_VIT_PATH_SPLIT3: the four GEMMs as split3 products on the bf16 matrix pipe (csrc/gemm_split.hip); everything else — patch embed,
+    //     LayerNorm arithmetic, epilogues — is the fp32 path's.  The LayerNorms, the attention kernel and fc1's GELU epilogue write their
+    //     results directly as three bf16 pieces (hs [M][1280], bs [M][5120]): no conversion pass, no fp32 copy of those activations.
+    //   THMR_VIT_PATH_SPLIT3_SMALL: EXPERIMENT (experiments library, THMR_SPLIT3_SMALL=1, off by default): a small-batch regime (up to six
+    //     crops) of the split3 mode — the ring kernel on split3 operands (64 x 64 tiles, 4-deep LDS-DMA ring; proj / fc2 split K four ways
+    //     into `part`, reduced by the residual + LayerNorm kernel as in the fp32 regime), producers writing split3 operands directly.  A
+    //     wave's MFMA chain per K tile shrinks from 16 x 64 to 12 x 32 cycles, but the call gets SLOWER: 4.28 vs 3.89 ms at one crop, 6.88 vs
+    //     5.84 at two, 16.3 vs 14.1 at six (profiles/r3y_split3_small_batch_regime_ab.log).  At these sizes the GEMMs are bound by the bytes
+    //     a CU can keep in flight (three 24 KB stages) against a ~4 us loaded memory round trip, not by the matrix pipe, and split3 operands
+    //     are 1.5x the bytes.
+    struct VitPath {
+        bool s3;                       // operands of the four GEMMs: split3 (6 bytes a value) or fp32
+        bool tiled;                    // THMR_VIT_PATH_SPLIT3 itself.  Apart from fc1's profiler sampling it only selects GemmArgs fields that no
+                                       // kernel reads (ldr / qscale / qcols of products without that epilogue, ldc next to c_split), kept as they were
+        float* a;                      // A of qkv, proj and fc1 = what the LayerNorms and the attention write: hs or h
+        float* mid;                    // fc1's destination = fc2's A: bs (through GemmArgs::c_split / ldcs / cs_blk) or big
+        float *part_proj, *part_fc2;   // partial planes of a split-K proj / fc2
+        int tile_opts;
+        int a_blk;                     // fc1 -> fc2 operand in the row-blocked form (plan.bs_blk: fc2 on the 128 x 256 stream)
+    };
+    const bool s3 = plan.path != THMR_VIT_PATH_F32, tiled = plan.path == THMR_VIT_PATH_SPLIT3;
+    // fc2's planes of the split3 path: behind the engine's operand buffers, or (3 and 4 crops: four planes) in the scratch arena's `part`
+    float* part2 = tiled && !plan.part2_in_scratch ? reinterpret_cast<float*>(e->split_act + (size_t)e->max_batch * TOK * (DIM + MLP) * 6) : part;
+    const VitPath pth{s3, tiled, s3 ? reinterpret_cast<float*>(e->split_act) : h,
+                      s3 ? reinterpret_cast<float*>(e->split_act + (size_t)M * DIM * 6) : big, part, part2, tiled ? plan.tile_opts : 0, plan.bs_blk};
+    const double ob = pth.s3 ? 6.0 : 4.0;      // bytes of one operand value, for the profiler's accounting
+    // y = LayerNorm(x), written as the next GEMM's A operand (as_operand: split3 in the split3 paths) or as fp32 features (last_norm)
+    auto norm = [&](const float* g, const float* bt, float* y, bool as_operand) -> int {
+        ProfScope ps(e, st, THMR_PROF_LN, 0, (4.0 + ob) * M * DIM);
+        if (pth.s3 && as_operand) LAUNCH_OK(launch_layernorm_split3(x, g, bt, y, M, DIM, VIT_EPS, st));
+        else LAUNCH_OK(launch_layernorm(x, g, bt, y, M, DIM, VIT_EPS, 0, st));
         return 0;
     };
-    {
-        ProfScope ps(e, st, THMR_PROF_LN, 0, 8.0 * M * DIM);
-        LAUNCH_OK(launch_layernorm(x, e->vitw[0].n1w, e->vitw[0].n1b, h, M, DIM, VIT_EPS, 0, st));
-    }
+    // x += Linear(A) + bias;  y = LayerNorm(x)      (vit.py:149 / :150 followed by the next norm): K split into `planes` (few crops on the ring
+    // kernel, the mid range on the big tiles / the tile streams) and reduced by the residual + LayerNorm kernel, or unsplit with the residual
+    // in the epilogue.  The byte counts are the ones each path has always reported: a split3 path counts its planes, the fp32 path two
+    // passes over x whatever the split; fc2's reduce counts an fp32 y even where it writes split3 (open items).
+    auto resid_linear_ln = [&](int cls, GemmChoice c, const float* A, int K, const float* Wt, const float* bias, float* planes, int a_blk,
+                               const float* g, const float* bt, float* y, bool as_operand) -> int {
+        const bool split = c.ksplit > 1;
+        {
+            ProfScope ps(e, st, cls, 2.0 * M * DIM * (double)K, ob * ((double)M * K + (double)DIM * K) + 4.0 * (pth.s3 && split ? c.ksplit : 2.0) * M * DIM);
+            GemmArgs a = split ? mk(A, K, Wt, K, nullptr, nullptr, 0, x, DIM, M, DIM, K) : mk(A, K, Wt, K, bias, x, DIM, x, DIM, M, DIM, K);
+            if (pth.tiled && !split) { a.qscale = qscale; a.qcols = DIM; }
+            a.a_blk = a_blk;
+            a.tile_opts = pth.tile_opts;
+            LAUNCH_OK(run_gemm(e, c, a, split ? EPI_NONE : EPI_BIAS_RESID, planes, st));
+        }
+        if (!split) return norm(g, bt, y, as_operand);
+        ProfScope ps(e, st, THMR_PROF_LN, 0, 4.0 * (c.ksplit + 2.0) * M * DIM + (cls == THMR_PROF_GEMM_PROJ ? ob : 4.0) * M * DIM);
+        LAUNCH_OK(launch_splitk_resid_ln(planes, c.ksplit, M, DIM, bias, x, x, g, bt, y, VIT_EPS, st, pth.s3 && as_operand));
+        return 0;
+    };
+    if (int rc = norm(e->vitw[0].n1w, e->vitw[0].n1b, pth.a, true)) return rc;
     for (int i = 0; i < e->vit_depth; ++i) {
         const VitBlockW& w = e->vitw[i];
         const bool last = i + 1 == e->vit_depth;
-        const float* nxt_w = last ? lastn_w : e->vitw[i + 1].n1w;      // the norm that follows this block's fc2
-        const float* nxt_b = last ? lastn_b : e->vitw[i + 1].n1b;
+        const float* nxt_w = last ? e->hot.lastn_w : e->vitw[i + 1].n1w;      // the norm that follows this block's fc2
+        const float* nxt_b = last ? e->hot.lastn_b : e->vitw[i + 1].n1b;
+        const float *wqkv = w.qkvw, *wproj = w.pw, *wfc1 = w.f1w, *wfc2 = w.f2w;      // the block's matrices in the path's operand kind
+        if (pth.s3) {
+            const thmr_engine::SplitW& ws = e->vitw_s[i];
+            wqkv = reinterpret_cast<const float*>(ws.qkv); wproj = reinterpret_cast<const float*>(ws.proj);
+            wfc1 = reinterpret_cast<const float*>(ws.fc1); wfc2 = reinterpret_cast<const float*>(ws.fc2);
+        }
         {   // qkv Linear; q columns scaled in the epilogue (vit.py:112,116)
-            ProfScope ps(e, st, THMR_PROF_GEMM_QKV, 2.0 * M * DIM * 3.0 * DIM, 4.0 * ((double)M * DIM + 3.0 * DIM * DIM + 3.0 * M * DIM));
-            GemmArgs a = mk(h, DIM, w.qkvw, DIM, w.qkvb, nullptr, 0, big, 3 * DIM, M, 3 * DIM, DIM);
+            ProfScope ps(e, st, THMR_PROF_GEMM_QKV, 2.0 * M * DIM * 3.0 * DIM, ob * ((double)M * DIM + 3.0 * DIM * DIM) + 12.0 * M * DIM);
+            GemmArgs a = mk(pth.a, DIM, wqkv, DIM, w.qkvb, nullptr, pth.tiled ? 3 * DIM : 0, big, 3 * DIM, M, 3 * DIM, DIM);
             a.qscale = qscale; a.qcols = DIM;
+            a.tile_opts = pth.tile_opts;
             LAUNCH_OK(run_gemm(e, plan.qkv, a, EPI_BIAS_QSCALE, nullptr, st));
         }
-        {
-            ProfScope ps(e, st, THMR_PROF_ATTN, 4.0 * B * HEADS * 192.0 * 192.0 * 80.0, 4.0 * (4.0 * M * DIM));
-            if (plan.attn == THMR_ATTN_F32_KEYSPLIT) LAUNCH_OK(launch_vit_attention_keysplit(big, h, B, st));
-            else LAUNCH_OK(launch_vit_attention(big, h, B, st));
+        {   // attention, its output written directly as proj's A operand
+            ProfScope ps(e, st, THMR_PROF_ATTN, 4.0 * B * HEADS * 192.0 * 192.0 * 80.0, 4.0 * (3.0 * M * DIM) + ob * M * DIM);
+            if (pth.s3) {
+                if (plan.attn == THMR_ATTN_B16) LAUNCH_OK(launch_vit_attention_b16(big, pth.a, B, true, 0, st));
+                else LAUNCH_OK(launch_vit_attention_split3(big, pth.a, B, st));
+            } else {
+                if (plan.attn == THMR_ATTN_F32_KEYSPLIT) LAUNCH_OK(launch_vit_attention_keysplit(big, pth.a, B, st));
+                else LAUNCH_OK(launch_vit_attention(big, pth.a, B, st));
+            }
         }
         // proj + residual, then norm2 (vit.py:123,149,150)
-        if (int rc = resid_linear_ln(THMR_PROF_GEMM_PROJ, plan.proj, h, DIM, w.pw, w.pb, w.n2w, w.n2b, h)) return rc;
-        {   // fc1 + exact GELU (vit.py:83-84)
-            ProfScope ps(e, st, THMR_PROF_GEMM_FC1, 2.0 * M * DIM * (double)MLP, 4.0 * ((double)M * DIM + (double)DIM * MLP + (double)M * MLP), (i & 3) == 0);
-            GemmArgs a = mk(h, DIM, w.f1w, DIM, w.f1b, nullptr, 0, big, MLP, M, MLP, DIM);
+        if (int rc = resid_linear_ln(THMR_PROF_GEMM_PROJ, plan.proj, pth.a, DIM, wproj, w.pb, pth.part_proj, 0, w.n2w, w.n2b, pth.a, true)) return rc;
+        {   // fc1 + exact GELU (vit.py:83-84), written as fc2's A operand — in the split3 paths directly as three bf16 pieces: no fp32 copy of
+            // the hidden activations exists.  `sampled` (ProfScope): the split3 path has never passed it (open items)
+            ProfScope ps(e, st, THMR_PROF_GEMM_FC1, 2.0 * M * DIM * (double)MLP, ob * ((double)M * DIM + (double)DIM * MLP + (double)M * MLP),
+                         pth.tiled || (i & 3) == 0);
+            GemmArgs a = mk(pth.a, DIM, wfc1, DIM, w.f1b, nullptr, 0, pth.s3 ? nullptr : pth.mid, pth.tiled ? 0 : MLP, M, MLP, DIM);
+            if (pth.s3) { a.c_split = pth.mid; a.ldcs = MLP; a.cs_blk = pth.a_blk; }
+            a.tile_opts = pth.tile_opts;
             LAUNCH_OK(run_gemm(e, plan.fc1, a, EPI_BIAS_GELU, nullptr, st));
         }
-        // fc2 + residual (vit.py:85,150), then the next block's norm1 — or last_norm (vit.py:335), kept token-major: the
-        // :337 permute is undone by token_head.py:69
-        if (int rc = resid_linear_ln(THMR_PROF_GEMM_FC2, plan.fc2, big, MLP, w.f2w, w.f2b, nxt_w, nxt_b, last && feats_out ? feats_out : h))
+        // fc2 + residual (vit.py:85,150), then the next block's norm1 — or last_norm (vit.py:335), fp32 in every path and kept token-major:
+        // the :337 permute is undone by token_head.py:69
+        if (int rc = resid_linear_ln(THMR_PROF_GEMM_FC2, plan.fc2, pth.mid, MLP, wfc2, w.f2b, pth.part_fc2, pth.a_blk, nxt_w, nxt_b,
+                                     last ? (feats_out ? feats_out : h) : pth.a, !last))
             return rc;
     }
     return 0;
@@ -759,7 +679,7 @@ int vq_decode(thmr_engine* e, const float* probs, int B, float* bpose, hipStream
 // hard codebook lookup (QuantizeEMAReset.dequantize, quantize_cnn.py:88-90) -> the same operand; x = null: the code rows themselves,
 // else the straight-through value x + (c - x) of quantize_cnn.py:124.  A bad index sets the engine's host-mapped flag word [2].
 int vq_decode_idx(thmr_engine* e, const int32_t* idx, const float* x, int B, float* bpose, hipStream_t st) {
-    LAUNCH_OK(launch_vq_lookup(idx, x, e->W("quantizer.codebook"), e->S(e->so.gat), B, e->host_err ? e->host_err + 2 : nullptr, st));
+    LAUNCH_OK(launch_vq_lookup(idx, x, e->hot.codebook, e->S(e->so.gat), B, e->host_err ? e->host_err + 2 : nullptr, st));
     return vq_decode_convs(e, B, bpose, st);
 }
 
@@ -785,8 +705,6 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
     }
     ProfScope ps_head(e, st, THMR_PROF_HEAD, e->hmr2 ? 2.0 * B * (6.0 * 4.2e6 + 0.16e6) : 2.0 * B * (6.0 * 4.2e6 + 116.7e6 + 167.8e6 + 705.0e6), 0);
     float *dx = e->S(so.dx), *dh = e->S(so.dh), *dv = e->S(so.dv), *dq = e->S(so.dq), *dca = e->S(so.dca), *dff = e->S(so.dff);
-    const std::string T = "smpl_head.transformer.";
-    const std::string C = "smpl_head.decpose.";
     float* ro = e->S(so.ro);
     float *mt = e->S(so.mt), *cf = e->S(so.cf), *cf2 = e->S(so.cf2);
     const bool fused_head = !e->legacy_head && B <= kFusedHeadMaxB;
@@ -811,38 +729,39 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
             LAUNCH_OK(launch_decoder_fused(d, st));            // the caller's Turn (thmr_forward / thmr_head_forward) orders engines
         }
     } else {
-    LAUNCH_OK(launch_decoder_init(e->W(T + "to_token_embedding.bias"), e->W(T + "pos_embedding"), dx, B, E, st));
+    // the launch chain: the same weights the persistent kernels read (e->dec, e->mix: resolved by resolve_weights)
+    LAUNCH_OK(launch_decoder_init(e->dec.tok_bias, e->dec.pos, dx, B, E, st));
     for (int l = 0; l < e->dec_depth; ++l) {
-        const std::string p = T + "transformer.layers." + std::to_string(l) + ".";
+        const DecLayerW& w = e->dec.L[l];
         // self-attention over ONE token: softmax of a single score == 1, so out = to_out(v)  (pose_transformer.py:75-86)
-        LAUNCH_OK(launch_layernorm(dx, e->W(p + "0.norm.weight"), e->W(p + "0.norm.bias"), dh, B, E, LN_EPS, 0, st));
+        LAUNCH_OK(launch_layernorm(dx, w.n0w, w.n0b, dh, B, E, LN_EPS, 0, st));
         {
-            GemmArgs a = mk(dh, E, e->W(p + "0.fn.to_qkv.weight") + (size_t)2 * INNER * E, E, nullptr, nullptr, 0, dv, INNER, B, INNER, E);
+            GemmArgs a = mk(dh, E, w.wv, E, nullptr, nullptr, 0, dv, INNER, B, INNER, E);
             LAUNCH_OK(launch_gemm_skinny(a, EPI_NONE, st));
         }
         {
-            GemmArgs a = mk(dv, INNER, e->W(p + "0.fn.to_out.0.weight"), INNER, e->W(p + "0.fn.to_out.0.bias"), dx, E, dx, E, B, E, INNER);
+            GemmArgs a = mk(dv, INNER, w.wo1, INNER, w.bo1, dx, E, dx, E, B, E, INNER);
             LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS_RESID, st));
         }
         // cross-attention (pose_transformer.py:111-124)
-        LAUNCH_OK(launch_layernorm(dx, e->W(p + "1.norm.weight"), e->W(p + "1.norm.bias"), dh, B, E, LN_EPS, 0, st));
+        LAUNCH_OK(launch_layernorm(dx, w.n1w, w.n1b, dh, B, E, LN_EPS, 0, st));
         {
-            GemmArgs a = mk(dh, E, e->W(p + "1.fn.to_q.weight"), E, nullptr, nullptr, 0, dq, INNER, B, INNER, E);
+            GemmArgs a = mk(dh, E, w.wq, E, nullptr, nullptr, 0, dq, INNER, B, INNER, E);
             LAUNCH_OK(launch_gemm_skinny(a, EPI_NONE, st));
         }
         LAUNCH_OK(launch_cross_attn(dq, big, ldkv, l * 2 * INNER, dca, B, st));
         {
-            GemmArgs a = mk(dca, INNER, e->W(p + "1.fn.to_out.0.weight"), INNER, e->W(p + "1.fn.to_out.0.bias"), dx, E, dx, E, B, E, INNER);
+            GemmArgs a = mk(dca, INNER, w.wo2, INNER, w.bo2, dx, E, dx, E, B, E, INNER);
             LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS_RESID, st));
         }
         // feed-forward (pose_transformer.py:40-52)
-        LAUNCH_OK(launch_layernorm(dx, e->W(p + "2.norm.weight"), e->W(p + "2.norm.bias"), dh, B, E, LN_EPS, 0, st));
+        LAUNCH_OK(launch_layernorm(dx, w.n2w, w.n2b, dh, B, E, LN_EPS, 0, st));
         {
-            GemmArgs a = mk(dh, E, e->W(p + "2.fn.net.0.weight"), E, e->W(p + "2.fn.net.0.bias"), nullptr, 0, dff, DEC_MLP, B, DEC_MLP, E);
+            GemmArgs a = mk(dh, E, w.w1, E, w.b1, nullptr, 0, dff, DEC_MLP, B, DEC_MLP, E);
             LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS_GELU, st));
         }
         {
-            GemmArgs a = mk(dff, DEC_MLP, e->W(p + "2.fn.net.3.weight"), DEC_MLP, e->W(p + "2.fn.net.3.bias"), dx, E, dx, E, B, E, DEC_MLP);
+            GemmArgs a = mk(dff, DEC_MLP, w.w2, DEC_MLP, w.b2, dx, E, dx, E, B, E, DEC_MLP);
             LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS_RESID, st));
         }
     }
@@ -858,7 +777,7 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
         }
         // token classifier (token_classifier.py:89-104)
         {
-            GemmArgs a = mk(dx, E, e->W(C + "mixer_trans.ff.0.weight"), E, e->W(C + "mixer_trans.ff.0.bias"), nullptr, 0, mt, TN * HID, B, TN * HID, E);
+            GemmArgs a = mk(dx, E, e->dec.mt_w, E, e->dec.mt_b, nullptr, 0, mt, TN * HID, B, TN * HID, E);
             LAUNCH_OK(launch_gemm_skinny(a, EPI_BIAS, st));
         }
     }
@@ -881,38 +800,38 @@ int head_forward(thmr_engine* e, const float* ctx, int B, const thmr_outputs* ou
         // ONE kernel, one workgroup per crop: mixer_trans LayerNorm + ReLU, the 4 MixerLayers, mixer_norm_layer (mixer_fused.hip)
         if (!mixer_in_decoder) LAUNCH_OK(launch_mixer_fused(e->mix, B, st));
     } else {
-        LAUNCH_OK(launch_layernorm(mt, e->W(C + "mixer_trans.ff.1.weight"), e->W(C + "mixer_trans.ff.1.bias"), cf, B, TN * HID, LN_EPS, 1, st));
+        LAUNCH_OK(launch_layernorm(mt, e->mix.tln_w, e->mix.tln_b, cf, B, TN * HID, LN_EPS, 1, st));
         for (int m = 0; m < MIX; ++m) {   // MixerLayer, heads/modules.py:55-63
-            const std::string p = C + "mixer_head." + std::to_string(m) + ".";
+            const MixerLayerW& w = e->mix.L[m];
             float *y1 = e->S(so.y1), *tT = e->S(so.tT), *u = e->S(so.u), *yt = e->S(so.yt), *y = e->S(so.y), *s = e->S(so.s),
                   *z0 = e->S(so.z0), *zh = e->S(so.zh);
-            LAUNCH_OK(launch_layernorm(cf, e->W(p + "layernorm1.weight"), e->W(p + "layernorm1.bias"), y1, R, HID, LN_EPS, 0, st));
+            LAUNCH_OK(launch_layernorm(cf, w.ln1w, w.ln1b, y1, R, HID, LN_EPS, 0, st));
             LAUNCH_OK(launch_transpose(y1, tT, B, TN, HID, st));                                   // (B,160,64)->(B,64,160)
             {
-                GemmArgs a = mk(tT, TN, e->W(p + "MLP_token.ff.0.weight"), TN, e->W(p + "MLP_token.ff.0.bias"), nullptr, 0, u, TOK_INTER, B * HID, TOK_INTER, TN);
+                GemmArgs a = mk(tT, TN, w.wt1, TN, w.bt1, nullptr, 0, u, TOK_INTER, B * HID, TOK_INTER, TN);
                 LAUNCH_OK(launch_gemm(a, EPI_BIAS_GELU, -1, st));
             }
             {
-                GemmArgs a = mk(u, TOK_INTER, e->W(p + "MLP_token.ff.3.weight"), TOK_INTER, e->W(p + "MLP_token.ff.3.bias"), nullptr, 0, yt, TN, B * HID, TN, TOK_INTER);
+                GemmArgs a = mk(u, TOK_INTER, w.wt2, TOK_INTER, w.bt2, nullptr, 0, yt, TN, B * HID, TN, TOK_INTER);
                 LAUNCH_OK(launch_gemm(a, EPI_BIAS, -1, st));
             }
             LAUNCH_OK(launch_transpose(yt, y, B, HID, TN, st));                                    // (B,64,160)->(B,160,64)
-            LAUNCH_OK(launch_add_ln64(cf, y, e->W(p + "layernorm2.weight"), e->W(p + "layernorm2.bias"), s, z0, R, LN_EPS, st));
+            LAUNCH_OK(launch_add_ln64(cf, y, w.ln2w, w.ln2b, s, z0, R, LN_EPS, st));
             {
-                GemmArgs a = mk(z0, HID, e->W(p + "MLP_channel.ff.0.weight"), HID, e->W(p + "MLP_channel.ff.0.bias"), nullptr, 0, zh, HID_INTER, R, HID_INTER, HID);
+                GemmArgs a = mk(z0, HID, w.wc1, HID, w.bc1, nullptr, 0, zh, HID_INTER, R, HID_INTER, HID);
                 LAUNCH_OK(launch_gemm(a, EPI_BIAS_GELU, -1, st));
             }
             {   // out = (x + y) + z
-                GemmArgs a = mk(zh, HID_INTER, e->W(p + "MLP_channel.ff.3.weight"), HID_INTER, e->W(p + "MLP_channel.ff.3.bias"), s, HID, cf2, HID, R, HID, HID_INTER);
+                GemmArgs a = mk(zh, HID_INTER, w.wc2, HID_INTER, w.bc2, s, HID, cf2, HID, R, HID, HID_INTER);
                 LAUNCH_OK(launch_gemm(a, EPI_BIAS_RESID, -1, st));
             }
             std::swap(cf, cf2);
         }
         {
-            GemmArgs a = mk(cf, HID, e->W(C + "mixer_norm_layer.ff.0.weight"), HID, e->W(C + "mixer_norm_layer.ff.0.bias"), nullptr, 0, nl, HID, R, HID, HID);
+            GemmArgs a = mk(cf, HID, e->mix.wn, HID, e->mix.bn, nullptr, 0, nl, HID, R, HID, HID);
             LAUNCH_OK(launch_gemm(a, EPI_BIAS, -1, st));
         }
-        LAUNCH_OK(launch_layernorm(nl, e->W(C + "mixer_norm_layer.ff.1.weight"), e->W(C + "mixer_norm_layer.ff.1.bias"), nl2, R, HID, LN_EPS, 1, st));
+        LAUNCH_OK(launch_layernorm(nl, e->mix.nln_w, e->mix.nln_b, nl2, R, HID, LN_EPS, 1, st));
     }
     // logits / softmax / token index; KV in `big` is dead after the decoder, so logits+probs live there
     float* logits = (out && out->cls_logits) ? out->cls_logits : big;
@@ -1353,6 +1272,100 @@ int thmr_load_smpl(thmr_engine* e, const thmr_smpl_desc* s, void* stream) {
     return 0;
 }
 
+// Every weight pointer a call reads, resolved from the name map ONCE (thmr_finalize_weights): the name map is for the layout and the load,
+// and no call path looks a tensor up by name.  Also the scratch pointers, knobs and grid limit of the persistent decoder kernel, which
+// travel in the same structures.  An unknown name (impossible for a valid layout) fails here instead of leaving a null pointer behind.
+static int resolve_weights(thmr_engine* e) {
+    bool known = true;
+    auto W = [&](const std::string& name) { float* p = e->W(name); known = known && p != nullptr; return p; };
+    e->hot = thmr_engine::HotW{};
+    e->vitw.resize(e->vit_depth);
+    for (int i = 0; i < e->vit_depth; ++i) {
+        const std::string p = "backbone.blocks." + std::to_string(i) + ".";
+        VitBlockW& w = e->vitw[i];
+        w.n1w = W(p + "norm1.weight"); w.n1b = W(p + "norm1.bias");
+        w.qkvw = W(p + "attn.qkv.weight"); w.qkvb = W(p + "attn.qkv.bias");
+        w.pw = W(p + "attn.proj.weight"); w.pb = W(p + "attn.proj.bias");
+        w.n2w = W(p + "norm2.weight"); w.n2b = W(p + "norm2.bias");
+        w.f1w = W(p + "mlp.fc1.weight"); w.f1b = W(p + "mlp.fc1.bias");
+        w.f2w = W(p + "mlp.fc2.weight"); w.f2b = W(p + "mlp.fc2.bias");
+    }
+    // decoder / read-out / mixer_trans: the persistent decoder kernel's parameters, and what the launch-chain head reads
+    DecParams& d = e->dec;
+    const std::string T = "smpl_head.transformer.";
+    for (int l = 0; l < e->dec_depth; ++l) {
+        const std::string p = T + "transformer.layers." + std::to_string(l) + ".";
+        DecLayerW& w = d.L[l];
+        w.n0w = W(p + "0.norm.weight"); w.n0b = W(p + "0.norm.bias");
+        const float* qkv = W(p + "0.fn.to_qkv.weight");
+        w.wv = qkv ? qkv + (size_t)2 * INNER * E : nullptr;                     // v slice of to_qkv (rows 1024..1535)
+        w.wo1 = W(p + "0.fn.to_out.0.weight"); w.bo1 = W(p + "0.fn.to_out.0.bias");
+        w.n1w = W(p + "1.norm.weight"); w.n1b = W(p + "1.norm.bias");
+        w.wq = W(p + "1.fn.to_q.weight");
+        w.wo2 = W(p + "1.fn.to_out.0.weight"); w.bo2 = W(p + "1.fn.to_out.0.bias");
+        w.n2w = W(p + "2.norm.weight"); w.n2b = W(p + "2.norm.bias");
+        w.w1 = W(p + "2.fn.net.0.weight"); w.b1 = W(p + "2.fn.net.0.bias");
+        w.w2 = W(p + "2.fn.net.3.weight"); w.b2 = W(p + "2.fn.net.3.bias");
+    }
+    d.tok_bias = W(T + "to_token_embedding.bias"); d.pos = W(T + "pos_embedding");
+    d.kv = e->S(e->so.big); d.ldkv = (int64_t)e->dec_depth * 2 * INNER;
+    d.ro_w = e->warena + e->o_ro_w; d.ro_b = e->warena + e->o_ro_b;
+    d.dx = e->S(e->so.dx); d.dv = e->S(e->so.dv); d.dq = e->S(e->so.dq); d.dca = e->S(e->so.dca); d.dff = e->S(e->so.dff);
+    d.ro = e->S(e->so.ro); d.mt = e->S(e->so.mt);
+    d.sync = reinterpret_cast<unsigned*>(e->S(e->so.sync));
+    d.depth = e->dec_depth; d.B = 0;
+    { const char* tl = thmr_knob("THMR_DEC_TIMELINE"); d.timeline = tl && tl[0] == '1'; }
+    { const char* ft = thmr_knob("THMR_DEC_FORCE_TIMEOUT"); d.debug_fail = ft && ft[0] == '1'; }
+    // all-to-all barrier: measured SLOWER (head 0.711 vs 0.664 ms at one crop, 2.87-2.90 vs 2.81-2.82 at 64: 128-256 workgroups x
+    // 128-256 device-scope polls contend; profiles/r3k_decoder_barrier_all_to_all_ab.log) — kept behind the knob only
+    { const char* bm = thmr_knob("THMR_DEC_BARRIER"); d.barrier_a2a = bm && bm[0] == '1'; }
+    {
+        // never more workgroups than can be resident at once (occupancy query x CUs): the grid barrier depends on it
+        const int nb = decoder_max_coresident_blocks(e->cfg.device, e->hmr2 ? THMR_HEAD_HMR2 : THMR_HEAD_TOKEN);
+        if (nb < 1) return fail(e, THMR_ERR_HIP, "persistent decoder kernel cannot be resident on this device (occupancy query failed)");
+        d.max_blocks = nb;
+        d.host_err = e->host_err;
+    }
+    auto& h = e->hot;
+    h.pe_w = W("backbone.patch_embed.proj.weight"); h.pe_b = W("backbone.patch_embed.proj.bias");
+    h.pos = W("backbone.pos_embed");
+    h.lastn_w = W("backbone.last_norm.weight"); h.lastn_b = W("backbone.last_norm.bias");
+    h.init_pose = W("smpl_head.init_body_pose"); h.init_betas = W("smpl_head.init_betas"); h.init_cam = W("smpl_head.init_cam");
+    if (!e->hmr2) {      // the token head: mixer stack, classifier, VQ decoder, codebook
+        const std::string C = "smpl_head.decpose.";
+        d.mt_w = W(C + "mixer_trans.ff.0.weight"); d.mt_b = W(C + "mixer_trans.ff.0.bias");
+        MixerParams& m = e->mix;
+        for (int i = 0; i < MIX; ++i) {
+            const std::string p = C + "mixer_head." + std::to_string(i) + ".";
+            MixerLayerW& w = m.L[i];
+            w.ln1w = W(p + "layernorm1.weight"); w.ln1b = W(p + "layernorm1.bias");
+            w.wt1 = W(p + "MLP_token.ff.0.weight"); w.bt1 = W(p + "MLP_token.ff.0.bias");
+            w.wt2 = W(p + "MLP_token.ff.3.weight"); w.bt2 = W(p + "MLP_token.ff.3.bias");
+            w.ln2w = W(p + "layernorm2.weight"); w.ln2b = W(p + "layernorm2.bias");
+            w.wc1 = W(p + "MLP_channel.ff.0.weight"); w.bc1 = W(p + "MLP_channel.ff.0.bias");
+            w.wc2 = W(p + "MLP_channel.ff.3.weight"); w.bc2 = W(p + "MLP_channel.ff.3.bias");
+        }
+        m.tln_w = W(C + "mixer_trans.ff.1.weight"); m.tln_b = W(C + "mixer_trans.ff.1.bias");
+        m.wn = W(C + "mixer_norm_layer.ff.0.weight"); m.bn = W(C + "mixer_norm_layer.ff.0.bias");
+        m.nln_w = W(C + "mixer_norm_layer.ff.1.weight"); m.nln_b = W(C + "mixer_norm_layer.ff.1.bias");
+        m.mt = e->S(e->so.mt); m.out = e->S(e->so.nl2);
+        h.cls_w = W(C + "class_pred_layer.weight"); h.cls_b = W(C + "class_pred_layer.bias");
+        for (int i = 0; i < 9; ++i) h.conv_b[i] = W(std::string(kConv3[i]) + ".bias");
+        for (int b = 0; b < 2; ++b) {
+            const std::string p = "decoder.decoder.14.0.model." + std::to_string(b) + ".";
+            h.res_w[b] = W(p + "conv2.weight"); h.res_b[b] = W(p + "conv2.bias");
+        }
+        h.codebook = W("quantizer.codebook");
+    }
+    // the optional tokenizer encoder: a k > 1 conv reads its repacked copy (thmr_finalize_weights), a 1 x 1 conv the checkpoint tensor
+    for (int i = 0; i < (e->enc_ready ? kEncN : 0); ++i) {
+        const std::string n = kEnc[i].name;
+        h.enc_w[i] = kEnc[i].ks > 1 ? e->warena + e->enc_convp[i] : W(n + ".weight");
+        h.enc_b[i] = W(n + ".bias");
+    }
+    return known ? 0 : fail(e, THMR_ERR_STATE, e->err);      // e->err: "internal: unknown weight <name>" (thmr_engine::W)
+}
+
 // split3 copies of the four ViT GEMM weights of every block (6 bytes per weight) + the activation operand buffers, engine-owned
 static int build_split_weights(thmr_engine* e, hipStream_t st) {
     if (e->max_batch < kSplit3LowMinB) return 0;      // no call of this engine can reach the mode (one and two crops run the exact-fp32 kernels)
@@ -1452,84 +1465,7 @@ int thmr_finalize_weights(thmr_engine* e, int32_t assume_all_loaded, void* strea
             if (kEnc[i].ks > 1)
                 LAUNCH_OK(launch_conv_repack_pad(e->W(std::string(kEnc[i].name) + ".weight"), e->warena + e->enc_convp[i],
                                                  kEnc[i].co, kEnc[i].ci, kEnc[i].cp, kEnc[i].ks, st));
-    // per-block weight pointers of the ViT loop, resolved once (the name map is for load time, not for the hot path)
-    e->vitw.resize(e->vit_depth);
-    for (int i = 0; i < e->vit_depth; ++i) {
-        const std::string p = "backbone.blocks." + std::to_string(i) + ".";
-        VitBlockW& w = e->vitw[i];
-        w.n1w = e->W(p + "norm1.weight"); w.n1b = e->W(p + "norm1.bias");
-        w.qkvw = e->W(p + "attn.qkv.weight"); w.qkvb = e->W(p + "attn.qkv.bias");
-        w.pw = e->W(p + "attn.proj.weight"); w.pb = e->W(p + "attn.proj.bias");
-        w.n2w = e->W(p + "norm2.weight"); w.n2b = e->W(p + "norm2.bias");
-        w.f1w = e->W(p + "mlp.fc1.weight"); w.f1b = e->W(p + "mlp.fc1.bias");
-        w.f2w = e->W(p + "mlp.fc2.weight"); w.f2b = e->W(p + "mlp.fc2.bias");
-    }
-    {   // decoder / read-out / mixer_trans pointers of the persistent decoder kernel, resolved once
-        DecParams& d = e->dec;
-        const std::string T = "smpl_head.transformer.";
-        for (int l = 0; l < e->dec_depth; ++l) {
-            const std::string p = T + "transformer.layers." + std::to_string(l) + ".";
-            DecLayerW& w = d.L[l];
-            w.n0w = e->W(p + "0.norm.weight"); w.n0b = e->W(p + "0.norm.bias");
-            w.wv = e->W(p + "0.fn.to_qkv.weight") + (size_t)2 * INNER * E;            // v slice of to_qkv (rows 1024..1535)
-            w.wo1 = e->W(p + "0.fn.to_out.0.weight"); w.bo1 = e->W(p + "0.fn.to_out.0.bias");
-            w.n1w = e->W(p + "1.norm.weight"); w.n1b = e->W(p + "1.norm.bias");
-            w.wq = e->W(p + "1.fn.to_q.weight");
-            w.wo2 = e->W(p + "1.fn.to_out.0.weight"); w.bo2 = e->W(p + "1.fn.to_out.0.bias");
-            w.n2w = e->W(p + "2.norm.weight"); w.n2b = e->W(p + "2.norm.bias");
-            w.w1 = e->W(p + "2.fn.net.0.weight"); w.b1 = e->W(p + "2.fn.net.0.bias");
-            w.w2 = e->W(p + "2.fn.net.3.weight"); w.b2 = e->W(p + "2.fn.net.3.bias");
-        }
-        d.tok_bias = e->W(T + "to_token_embedding.bias"); d.pos = e->W(T + "pos_embedding");
-        d.kv = e->S(e->so.big); d.ldkv = (int64_t)e->dec_depth * 2 * INNER;
-        d.ro_w = e->warena + e->o_ro_w; d.ro_b = e->warena + e->o_ro_b;
-        if (!e->hmr2) { d.mt_w = e->W("smpl_head.decpose.mixer_trans.ff.0.weight"); d.mt_b = e->W("smpl_head.decpose.mixer_trans.ff.0.bias"); }
-        d.dx = e->S(e->so.dx); d.dv = e->S(e->so.dv); d.dq = e->S(e->so.dq); d.dca = e->S(e->so.dca); d.dff = e->S(e->so.dff);
-        d.ro = e->S(e->so.ro); d.mt = e->S(e->so.mt);
-        d.sync = reinterpret_cast<unsigned*>(e->S(e->so.sync));
-        d.depth = e->dec_depth; d.B = 0;
-        { const char* tl = thmr_knob("THMR_DEC_TIMELINE"); d.timeline = tl && tl[0] == '1'; }
-        { const char* ft = thmr_knob("THMR_DEC_FORCE_TIMEOUT"); d.debug_fail = ft && ft[0] == '1'; }
-        // all-to-all barrier: measured SLOWER (head 0.711 vs 0.664 ms at one crop, 2.87-2.90 vs 2.81-2.82 at 64: 128-256 workgroups x
-        // 128-256 device-scope polls contend; profiles/r3k_decoder_barrier_all_to_all_ab.log) — kept behind the knob only
-        { const char* bm = thmr_knob("THMR_DEC_BARRIER"); d.barrier_a2a = bm && bm[0] == '1'; }
-        {
-            // never more workgroups than can be resident at once (occupancy query x CUs): the grid barrier depends on it
-            const int nb = decoder_max_coresident_blocks(e->cfg.device, e->hmr2 ? THMR_HEAD_HMR2 : THMR_HEAD_TOKEN);
-            if (nb < 1) return fail(e, THMR_ERR_HIP, "persistent decoder kernel cannot be resident on this device (occupancy query failed)");
-            d.max_blocks = nb;
-            d.host_err = e->host_err;
-        }
-        MixerParams& m = e->mix;
-        const std::string C = "smpl_head.decpose.";
-        for (int i = 0; i < (e->hmr2 ? 0 : MIX); ++i) {
-            const std::string p = C + "mixer_head." + std::to_string(i) + ".";
-            MixerLayerW& w = m.L[i];
-            w.ln1w = e->W(p + "layernorm1.weight"); w.ln1b = e->W(p + "layernorm1.bias");
-            w.wt1 = e->W(p + "MLP_token.ff.0.weight"); w.bt1 = e->W(p + "MLP_token.ff.0.bias");
-            w.wt2 = e->W(p + "MLP_token.ff.3.weight"); w.bt2 = e->W(p + "MLP_token.ff.3.bias");
-            w.ln2w = e->W(p + "layernorm2.weight"); w.ln2b = e->W(p + "layernorm2.bias");
-            w.wc1 = e->W(p + "MLP_channel.ff.0.weight"); w.bc1 = e->W(p + "MLP_channel.ff.0.bias");
-            w.wc2 = e->W(p + "MLP_channel.ff.3.weight"); w.bc2 = e->W(p + "MLP_channel.ff.3.bias");
-        }
-        if (!e->hmr2) {
-            m.tln_w = e->W(C + "mixer_trans.ff.1.weight"); m.tln_b = e->W(C + "mixer_trans.ff.1.bias");
-            m.wn = e->W(C + "mixer_norm_layer.ff.0.weight"); m.bn = e->W(C + "mixer_norm_layer.ff.0.bias");
-            m.nln_w = e->W(C + "mixer_norm_layer.ff.1.weight"); m.nln_b = e->W(C + "mixer_norm_layer.ff.1.bias");
-            m.mt = e->S(e->so.mt); m.out = e->S(e->so.nl2);
-        }
-        auto& h = e->hot;
-        h.pe_w = e->W("backbone.patch_embed.proj.weight"); h.pe_b = e->W("backbone.patch_embed.proj.bias");
-        h.pos = e->W("backbone.pos_embed");
-        h.lastn_w = e->W("backbone.last_norm.weight"); h.lastn_b = e->W("backbone.last_norm.bias");
-        if (!e->hmr2) { h.cls_w = e->W(C + "class_pred_layer.weight"); h.cls_b = e->W(C + "class_pred_layer.bias"); }
-        h.init_pose = e->W("smpl_head.init_body_pose"); h.init_betas = e->W("smpl_head.init_betas"); h.init_cam = e->W("smpl_head.init_cam");
-        for (int i = 0; i < (e->hmr2 ? 0 : 9); ++i) h.conv_b[i] = e->W(std::string(kConv3[i]) + ".bias");
-        for (int b = 0; b < (e->hmr2 ? 0 : 2); ++b) {
-            const std::string p = "decoder.decoder.14.0.model." + std::to_string(b) + ".";
-            h.res_w[b] = e->W(p + "conv2.weight"); h.res_b[b] = e->W(p + "conv2.bias");
-        }
-    }
+    if (int r = resolve_weights(e)) return r;
     if (e->vit_gemm_mode == 1) {                                       // weights were (re)loaded with the split3 mode on
         if (int r = build_split_weights(e, st)) return r;              // (on failure the engine stays un-finalized: no forward can run on half-built operands)
         HIP_OK(hipStreamSynchronize(st));                              // as in thmr_set_vit_gemm: visible to forwards on any stream
@@ -1590,8 +1526,8 @@ static int encode_tokens_call(thmr_engine* e, const float* pose_dev, int B, int3
     float* a1 = a0 + (size_t)B * 320 * VQW;
     float* a2 = a1 + (size_t)B * 320 * VQW;
     const int32_t* tab = reinterpret_cast<const int32_t*>(e->warena + e->o_idx_enc);
-    auto W = [&](int i) { return kEnc[i].ks > 1 ? e->warena + e->enc_convp[i] : e->W(std::string(kEnc[i].name) + ".weight"); };
-    auto Bv = [&](int i) { return e->W(std::string(kEnc[i].name) + ".bias"); };
+    auto W = [&](int i) { return e->hot.enc_w[i]; };      // the repacked weights where ks > 1
+    auto Bv = [&](int i) { return e->hot.enc_b[i]; };
     // 0: Conv1d(6->512,k3,p1)+ReLU at T=21 (channels zero-padded 6->32 so that K = 96)
     LAUNCH_OK(launch_conv_gather_general(pose_dev, gat, nullptr, B, 21, 21, 21, 6, 32, 3, 1, 1, st));
     {
@@ -1633,7 +1569,7 @@ static int encode_tokens_call(thmr_engine* e, const float* pose_dev, int B, int3
         LAUNCH_OK(launch_gemm(a, EPI_BIAS, -1, st));
     }
     // argmin-L2 against the codebook; the x.C^T scores go to the gather region (B*160*2048 <= B*320*1536)
-    GemmArgs d = mk(lat, CODE, e->W("quantizer.codebook"), CODE, nullptr, nullptr, 0, gat, NCLS, B * 160, NCLS, CODE);
+    GemmArgs d = mk(lat, CODE, e->hot.codebook, CODE, nullptr, nullptr, 0, gat, NCLS, B * 160, NCLS, CODE);
     LAUNCH_OK(launch_gemm(d, EPI_NONE, -1, st));
     LAUNCH_OK(launch_vq_argmin_rows(lat, gat, e->warena + e->o_cnorm, idx_dev, nullptr, B * 160, st));
     if (lat_out) *lat_out = lat;
@@ -1680,7 +1616,7 @@ int thmr_tokenizer_roundtrip(thmr_engine* e, const float* pose6d_dev, int32_t B,
     const float* lat = nullptr;
     if (int r = encode_tokens_call(e, pose6d_dev, B, idx, out->latent, &lat, st)) return r;
     unsigned* flag = e->host_err ? e->host_err + 2 : nullptr;
-    const float* cb = e->W("quantizer.codebook");
+    const float* cb = e->hot.codebook;
     if (out->commit_loss || out->perplexity || out->code_count) {
         float* sc = enc_scratch_a2(e, B) + (size_t)B * 320 * VQW;      // behind a2: 2048 counts, then the partial sums
         int32_t* cnt = out->code_count ? out->code_count : reinterpret_cast<int32_t*>(sc);
@@ -1842,7 +1778,7 @@ int thmr_vq_argmin(thmr_engine* e, const float* x_dev, int32_t rows, int32_t* id
     if ((size_t)rows * NCLS > (size_t)e->max_batch * TOK * 6144) return fail(e, THMR_ERR_INVALID, "rows exceed scratch capacity");
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* dot = e->S(e->so.big);
-    GemmArgs a = mk(x_dev, CODE, e->W("quantizer.codebook"), CODE, nullptr, nullptr, 0, dot, NCLS, rows, NCLS, CODE);
+    GemmArgs a = mk(x_dev, CODE, e->hot.codebook, CODE, nullptr, nullptr, 0, dot, NCLS, rows, NCLS, CODE);
     LAUNCH_OK(launch_gemm(a, EPI_NONE, -1, st));
     LAUNCH_OK(launch_vq_argmin_rows(x_dev, dot, e->warena + e->o_cnorm, idx_dev, dist_dev, rows, st));
     return 0;
