@@ -841,6 +841,53 @@ void thmr_jpeg_destroy(thmr_jpeg* j);
 const char* thmr_jpeg_last_error(const thmr_jpeg* j);
 int  thmr_jpeg_decode_batch(thmr_jpeg* j, const thmr_jpeg_item* items_host, int32_t n, int32_t bgr, void* stream);
 
+/* PNG encoding of device images: the counterpart of cv2.imwrite(".png") (csrc/png.hip, png_host.h, png_math.h): new symbols
+ * under ABI 5.  Everything is integer arithmetic and deterministic: the bytes of a file are a function of the pixels and the arguments
+ * only, and thmr_png_encode_host — the same algorithm on the CPU, sharing its arithmetic and selection rules with the kernels through
+ * __host__ __device__ functions — writes the same file byte for byte.
+ *   pixels        uint8 or float32, 1 / 3 / 4 channels, any ELEMENT strides (stride_y, stride_x, stride_c): HWC, CHW, a panel of a sheet.
+ *                 swap_rb reverses the first three channels of a 3 / 4-channel image (cv2 hands over BGR(A), the file holds RGB(A)).
+ *                 float32 is multiplied by `scale` in fp32 (one rounding) and converted by `rounding`: THMR_PNG_ROUND_NEAREST rounds to
+ *                 nearest even and saturates to [0, 255] (cv2's saturate_cast<uchar>); THMR_PNG_ROUND_TRUNC clamps to [0, 255] and
+ *                 truncates (np.clip(x, 0, 255).astype(np.uint8)).  NaN gives 0 in both, +-inf saturate.  uint8 ignores both.
+ *   file          signature, IHDR (8 bits; grey, RGB or RGBA; no interlace), ONE IDAT, IEND.  Each row takes the filter 0 ... 4 with the
+ *                 smallest sum of |residual as a signed byte| (libpng's default heuristic), ties to the lowest number; row 0 sees a zero
+ *                 previous row.  The zlib stream is 78 01, then the filtered stream cut into segments of thmr_png_segment_bytes() bytes,
+ *                 each compressed alone — LZ77 with matches that never reach behind the segment start, one fixed-Huffman block, and
+ *                 (but for the last) an empty stored block 00 00 FF FF back to a byte boundary; a segment whose coded form would be
+ *                 larger than a stored block is a stored block — then the Adler-32.  No file is larger than thmr_png_bound().
+ *   refused       before any HIP call, the message names the item: THMR_ERR_UNSUPPORTED for a 16-bit dtype and for 2 channels;
+ *                 THMR_ERR_INVALID for any other dtype / channel count / rounding, width or height < 1, a filtered stream of 2^31 bytes
+ *                 or more, a null pointer, and a capacity below thmr_png_bound(). */
+enum { THMR_PNG_U8 = 0, THMR_PNG_F32 = 1, THMR_PNG_U16 = 2 /* refused by name */ };
+enum { THMR_PNG_ROUND_NEAREST = 0, THMR_PNG_ROUND_TRUNC = 1 };
+typedef struct thmr_png_item {
+    const void* pixels;                 /* element (0, 0, 0): device memory for thmr_png_encode_batch, host for thmr_png_encode_host */
+    int32_t dtype;                      /* THMR_PNG_U8 / THMR_PNG_F32 */
+    int32_t width, height, channels;
+    int64_t stride_y, stride_x, stride_c;       /* in ELEMENTS */
+    float scale;                        /* float32 input only */
+    int32_t rounding;                   /* THMR_PNG_ROUND_* */
+    int32_t swap_rb;
+    int32_t reserved;                   /* 0 */
+    uint8_t* out;                       /* host: the file */
+    int64_t capacity;                   /* bytes at out, >= thmr_png_bound(width, height, channels) */
+    int64_t written;                    /* set by the call: the file's length */
+} thmr_png_item;
+int thmr_png_segment_bytes(void);
+/* raw + 5 bytes per segment + 6 zlib bytes + 57 container bytes; 0 for arguments the encoder refuses */
+int64_t thmr_png_bound(int32_t width, int32_t height, int32_t channels);
+int thmr_png_encode_host(thmr_png_item* item);
+/* The handle owns grow-only device scratch (filtered stream, one slot per segment, the packed streams) and pinned staging.  One call
+ * encodes n images of n sizes, dtypes and layouts with ONE descriptor upload and THREE launches (convert + filter of every row;
+ * deflate of every segment, one wave each; gather of the segments into one packed stream), synchronises `stream`, and returns with the
+ * complete files at every item's `out`.  Not inside a stream capture (THMR_ERR_STATE). */
+typedef struct thmr_png thmr_png;
+int  thmr_png_create(int32_t device, thmr_png** out);
+void thmr_png_destroy(thmr_png* p);
+const char* thmr_png_last_error(const thmr_png* p);
+int  thmr_png_encode_batch(thmr_png* p, thmr_png_item* items_host, int32_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

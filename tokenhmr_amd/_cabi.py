@@ -100,6 +100,17 @@ class JpegPlan(C.Structure):
                [(n, C.c_int32 * 3) for n in ("bx0", "by0", "bw", "bh", "coef_block")] + [("n_blocks", C.c_int32), ("quant", (C.c_uint16 * 64) * 3)]
 
 
+class PngItem(C.Structure):
+    """thmr_png_item: one image of thmr_png_encode_batch / thmr_png_encode_host."""
+    _fields_ = [("pixels", C.c_void_p), ("dtype", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
+                ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("stride_c", C.c_int64), ("scale", C.c_float), ("rounding", C.c_int32),
+                ("swap_rb", C.c_int32), ("reserved", C.c_int32), ("out", C.c_void_p), ("capacity", C.c_int64), ("written", C.c_int64)]
+
+
+PNG_U8, PNG_F32, PNG_U16 = 0, 1, 2                  # header: THMR_PNG_*
+PNG_ROUND_NEAREST, PNG_ROUND_TRUNC = 0, 1           # header: THMR_PNG_ROUND_*
+
+
 class JpegItem(C.Structure):
     """thmr_jpeg_item: one item of thmr_jpeg_decode_batch."""
     _fields_ = [("coef", C.c_void_p), ("plan", C.POINTER(JpegPlan)), ("win_x0", C.c_int32), ("win_y0", C.c_int32), ("win_w", C.c_int32),
@@ -164,7 +175,7 @@ class ProfEntry(C.Structure):
 
 
 def declared_functions():
-    """{name: return type as written} of every function the header declares: 'int', 'void' or 'const char*'."""
+    """{name: return type as written} of every function the header declares: 'int', 'int64_t', 'void' or 'const char*'."""
     with open(HEADER) as f:
         text = f.read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
@@ -199,6 +210,10 @@ FRAMES_SYMBOLS = ("thmr_cropper_run_frames",)
 JPEG_SYMBOLS = ("thmr_jpeg_probe", "thmr_jpeg_entropy_decode", "thmr_jpeg_decode_host", "thmr_jpeg_create", "thmr_jpeg_destroy",
                 "thmr_jpeg_last_error", "thmr_jpeg_decode_batch")
 
+# PNG encoding (csrc/png.hip): new symbols under ABI 5 as well
+PNG_SYMBOLS = ("thmr_png_segment_bytes", "thmr_png_bound", "thmr_png_encode_host", "thmr_png_create", "thmr_png_destroy",
+               "thmr_png_last_error", "thmr_png_encode_batch")
+
 
 def load(exp=None):
     """The shipped library, or (exp=True, or exp=None with THMR_LIB=exp in the environment) the experiments build.
@@ -232,7 +247,7 @@ def load(exp=None):
         pass
     lib = C.CDLL(path)
     declared = declared_functions()
-    restypes = {"int": C.c_int, "void": None, "const char*": C.c_char_p}
+    restypes = {"int": C.c_int, "int64_t": C.c_int64, "void": None, "const char*": C.c_char_p}
     for name, ret in declared.items():                   # every return type as the header writes it
         if ret not in restypes:
             raise RuntimeError(f"tokenhmr_hip.h declares {name} as returning '{ret}': _cabi.load() knows {sorted(restypes)}")
@@ -241,7 +256,7 @@ def load(exp=None):
     older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
     # a build loaded by path may also predate thmr_renderer_sheet / thmr_debug_vit_plan (added without an ABI change: new symbols, no layout touched)
     missing = [s for s in sorted(declared) if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
-               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS + FRAMES_SYMBOLS + JPEG_SYMBOLS)]
+               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS + FRAMES_SYMBOLS + JPEG_SYMBOLS + PNG_SYMBOLS)]
     if missing:
         raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
     vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
@@ -324,6 +339,14 @@ def load(exp=None):
         lib.thmr_jpeg_destroy.argtypes = [vp]
         lib.thmr_jpeg_last_error.argtypes = [vp]
         lib.thmr_jpeg_decode_batch.argtypes = [vp, C.POINTER(JpegItem), i32, i32, vp]
+    if hasattr(lib, "thmr_png_encode_batch"):            # PNG encoding (added without an ABI change)
+        lib.thmr_png_segment_bytes.argtypes = []
+        lib.thmr_png_bound.argtypes = [i32, i32, i32]
+        lib.thmr_png_encode_host.argtypes = [C.POINTER(PngItem)]
+        lib.thmr_png_create.argtypes = [i32, C.POINTER(vp)]
+        lib.thmr_png_destroy.argtypes = [vp]
+        lib.thmr_png_last_error.argtypes = [vp]
+        lib.thmr_png_encode_batch.argtypes = [vp, C.POINTER(PngItem), i32, vp]
     lib.thmr_renderer_create.argtypes = [i32, vp, i32, i32, C.POINTER(vp)]
     lib.thmr_renderer_destroy.argtypes = [vp]
     lib.thmr_renderer_last_error.argtypes = [vp]

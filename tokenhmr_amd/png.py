@@ -1,0 +1,183 @@
+"""PNG encoding of device images: the drop-in for cv2.imwrite(".png") (include/tokenhmr_hip.h; csrc/png.hip, png_host.h, png_math.h).
+
+    imwrite("panel.png", panel)                          # device tensor or numpy array, (H, W), (H, W, 1 | 3 | 4); BGR(A) like cv2
+    imwrite_batch(paths, panels)                         # ONE device call, the files written from a small thread pool
+    files = PNGEncoder("cuda:0").encode([a, b, ...], scale=255, rounding="trunc", bgr=False)      # list[bytes]
+    data = encode_host(array)                            # the same bytes on the CPU (thmr_png_encode_host)
+
+An image is uint8 or float32 with any strides (a CHW tensor permuted to HWC, a panel sliced from a sheet: no copy is made).  Float
+values are multiplied by `scale` and converted by `rounding`: "nearest" is cv2.imwrite's saturate_cast (nearest even, saturated),
+"trunc" is np.clip(x, 0, 255).astype(np.uint8).  The file is 8-bit grey / RGB / RGBA, filtered per row by libpng's default heuristic
+and deflated in independent segments; the device and the host path write the same bytes.
+"""
+import ctypes as C
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import _cabi
+
+
+class PngError(_cabi.EngineError):
+    """A refused argument (THMR_ERR_INVALID) or a HIP failure."""
+
+
+class PngUnsupported(PngError):
+    """An image of a kind the encoder does not write (THMR_ERR_UNSUPPORTED): 16-bit samples, 2 channels."""
+
+
+_BY_CODE = {_cabi.ERR_UNSUPPORTED: PngUnsupported}
+_ROUNDING = {"nearest": _cabi.PNG_ROUND_NEAREST, "trunc": _cabi.PNG_ROUND_TRUNC}
+_DTYPES = {torch.uint8: _cabi.PNG_U8, torch.float32: _cabi.PNG_F32, np.dtype(np.uint8): _cabi.PNG_U8, np.dtype(np.float32): _cabi.PNG_F32,
+           np.dtype(np.uint16): _cabi.PNG_U16}
+if hasattr(torch, "uint16"):
+    _DTYPES[torch.uint16] = _cabi.PNG_U16
+WRITE_THREADS = 16      # what one command gets on the GPU boxes, whatever os.cpu_count() says of the whole machine
+
+
+def segment_bytes(lib=None):
+    return int((lib or _cabi.load()).thmr_png_segment_bytes())
+
+
+def bound(width, height, channels, lib=None):
+    """The largest file the encoder writes for an image of this size (0 for a size it refuses)."""
+    return int((lib or _cabi.load()).thmr_png_bound(int(width), int(height), int(channels)))
+
+
+def _fill(item, img, scale, rounding, bgr):
+    """One image -> the fields of a thmr_png_item but the pointers; returns (height, width, channels) as the facade sees them."""
+    if rounding not in _ROUNDING:
+        raise ValueError(f"rounding must be 'nearest' or 'trunc', got {rounding!r}")
+    if img.ndim == 2:
+        h, w = img.shape
+        c, sc = 1, 0
+        sy, sx = (img.stride() if isinstance(img, torch.Tensor) else [s // img.itemsize for s in img.strides])
+    elif img.ndim == 3:
+        h, w, c = img.shape
+        sy, sx, sc = (img.stride() if isinstance(img, torch.Tensor) else [s // img.itemsize for s in img.strides])
+    else:
+        raise ValueError(f"an image is (H, W) or (H, W, C), got shape {tuple(img.shape)}")
+    if img.dtype not in _DTYPES:
+        raise PngError(f"dtype must be uint8 or float32, got {img.dtype}")
+    item.dtype = _DTYPES[img.dtype]
+    item.width, item.height, item.channels = int(w), int(h), int(c)
+    item.stride_y, item.stride_x, item.stride_c = int(sy), int(sx), int(sc)
+    item.scale, item.rounding, item.swap_rb, item.reserved = float(scale), _ROUNDING[rounding], int(bool(bgr)), 0
+    return int(h), int(w), int(c)
+
+
+def _out(item, h, w, c, lib, capacity=None):
+    cap = bound(w, h, c, lib) if capacity is None else int(capacity)
+    buf = np.empty(max(cap, 1), dtype=np.uint8)
+    item.out, item.capacity = buf.ctypes.data, cap
+    return buf
+
+
+def encode_host(img, *, scale=1.0, rounding="nearest", bgr=True, capacity=None, lib=None):
+    """One numpy image -> the file's bytes, on the CPU with the kernels' arithmetic: the oracle of PNGEncoder, and what a caller without
+    a device gets.  capacity: the output buffer's size (default thmr_png_bound), for the refusal test."""
+    lib = lib or _cabi.load()
+    img = np.asarray(img)
+    item = _cabi.PngItem()
+    h, w, c = _fill(item, img, scale, rounding, bgr)
+    item.pixels = img.ctypes.data
+    buf = _out(item, h, w, c, lib, capacity)
+    rc = lib.thmr_png_encode_host(C.byref(item))
+    if rc != 0:
+        _cabi.raise_error(rc, "thmr_png_encode_host", lib.thmr_png_last_error(None), PngError, _BY_CODE)
+    return buf[:item.written].tobytes()
+
+
+class PNGEncoder(_cabi.Handle):
+    """Owns a thmr_png handle: grow-only device scratch and pinned staging.  One stream at a time; encode() synchronises it."""
+    error, error_by_code = PngError, _BY_CODE
+
+    def __init__(self, device="cuda:0"):
+        super().__init__(device, "thmr_png", "PNGEncoder needs a GPU device; encode_host() is the CPU encode")
+        self._open(self._index())
+
+    def encode(self, images, *, scale=1.0, rounding="nearest", bgr=True):
+        """A list of images — device tensors, or host tensors / numpy arrays (uploaded) — of any sizes, dtypes and strides -> the files,
+        list[bytes], in ONE batch call on the current stream.  bgr: the images hold B, G, R(, A) like cv2's; False: R, G, B(, A)."""
+        n = len(images)
+        if n == 0:
+            return []
+        items = (_cabi.PngItem * n)()
+        keep, bufs = [], []
+        for i, img in enumerate(images):
+            if isinstance(img, np.ndarray):
+                if img.dtype == np.float64:          # what 255 * img gives in demo.py; the device reads float32
+                    img = img.astype(np.float32)
+                if img.dtype not in _DTYPES or _DTYPES[img.dtype] == _cabi.PNG_U16:
+                    raise (PngUnsupported if img.dtype == np.uint16 else PngError)(
+                        f"image {i}: dtype must be uint8 or float32, got {img.dtype}" + (" (16-bit samples are unsupported)" if img.dtype == np.uint16 else ""))
+                img = torch.from_numpy(np.ascontiguousarray(img))
+            if img.device != self.device:
+                img = img.to(self.device)
+            h, w, c = _fill(items[i], img, scale, rounding, bgr)
+            items[i].pixels = img.data_ptr()
+            keep.append(img)
+            bufs.append(_out(items[i], h, w, c, self.lib))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = self.lib.thmr_png_encode_batch(self.h, items, n, C.c_void_p(stream.cuda_stream))
+        self._check(rc, "thmr_png_encode_batch")
+        return [bufs[i][:items[i].written].tobytes() for i in range(n)]
+
+
+_encoders = {}
+
+
+def _encoder(device):
+    device = _cabi.Handle.cuda_device(device, "imwrite needs a GPU device; encode_host() is the CPU encode", resolve=True)
+    if device not in _encoders:
+        _encoders[device] = PNGEncoder(device)
+    return _encoders[device]
+
+
+def _check_path(path):
+    ext = os.path.splitext(os.fspath(path))[1]
+    if ext.lower() != ".png":
+        raise ValueError(f"imwrite writes .png files only, got extension {ext!r} ({os.fspath(path)!r})")
+
+
+def _device_of(images, device):
+    if device is not None:
+        return device
+    for img in images:
+        if isinstance(img, torch.Tensor) and img.device.type == "cuda":
+            return img.device
+    return "cuda"
+
+
+def _write(path, data):
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def imwrite(path, img, params=None, *, scale=1.0, rounding="nearest", bgr=True, device=None):
+    """cv2.imwrite for .png: a device tensor or a numpy array, (H, W) or (H, W, C), channels in cv2's B, G, R(, A) order.  params is
+    accepted and ignored (cv2's compression level has no counterpart).  A numpy array goes to `device` (default: the current GPU).
+    Returns True; raises ValueError naming the extension for anything but .png."""
+    _check_path(path)
+    data = _encoder(_device_of([img], device)).encode([img], scale=scale, rounding=rounding, bgr=bgr)[0]
+    _write(path, data)
+    return True
+
+
+def imwrite_batch(paths, images, *, scale=1.0, rounding="nearest", bgr=True, device=None, threads=None):
+    """imwrite for many files: ONE device call for all images, then the files are written from a thread pool (at most WRITE_THREADS)."""
+    paths = list(paths)
+    if len(paths) != len(images):
+        raise ValueError(f"{len(paths)} paths for {len(images)} images")
+    for p in paths:
+        _check_path(p)
+    if not paths:
+        return True
+    files = _encoder(_device_of(images, device)).encode(list(images), scale=scale, rounding=rounding, bgr=bgr)
+    workers = max(1, min(WRITE_THREADS if threads is None else int(threads), len(paths)))
+    with ThreadPoolExecutor(workers) as pool:
+        list(pool.map(_write, paths, files))
+    return True
