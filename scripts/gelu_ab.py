@@ -31,13 +31,12 @@ def build():
 
 def run(rounds):
     import torch
+    from tokenhmr_amd import _cabi
     dev = torch.device("cuda:0")
     libs = {}
     for k in (0, 1, 2, 3):
         lib = C.CDLL(os.path.join(AB, f"libgelu{k}.so"))
-        vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float
-        lib.thmr_op_gemm.argtypes = [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, i32, vp]
-        libs[k] = lib
+        libs[k] = _cabi.bind(lib, partial=True)
     M, N, K = 64 * 192, 5120, 1280
     g = torch.Generator().manual_seed(0)
     a = torch.randn(M, K, generator=g).to(dev)

@@ -48,15 +48,14 @@ def build():
 
 def run(rounds):
     import torch
+    from tokenhmr_amd import _cabi
     dev = torch.device("cuda:0")
     libs = {}
-    vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float
     for name in VARIANTS:
         if not os.path.exists(os.path.join(AB, f"libv_{name}.so")):
             continue
         lib = C.CDLL(os.path.join(AB, f"libv_{name}.so"))
-        lib.thmr_op_gemm.argtypes = [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, i32, vp]
-        libs[name] = lib
+        libs[name] = _cabi.bind(lib, partial=True)
     M = 64 * 192
     g = torch.Generator().manual_seed(0)
     a = torch.randn(M, 5120, generator=g).to(dev)

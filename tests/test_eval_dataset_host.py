@@ -45,10 +45,7 @@ def test_symbol_declared_bound_and_exported(built_lib):
     from tokenhmr_amd import _cabi
     assert _cabi.ABI_VERSION == 5 and built_lib.thmr_abi_version() == 5
     assert "thmr_cropper_run_frames" in _cabi.declared_symbols()
-    assert _cabi.FRAMES_SYMBOLS == ("thmr_cropper_run_frames",)
-    for exp in (False, True):
-        lib = _cabi.load(exp=exp)
-        assert hasattr(lib, "thmr_cropper_run_frames") and lib.thmr_cropper_run_frames.argtypes is not None
+    # (exported and typed in both builds, like every declared function: tests/test_cabi_header.py)
     # the struct mirrors the header: 8 + 8 + 6*4 + 8*8
     assert C.sizeof(_cabi.FrameCrop) == 104 and _cabi.FrameCrop.M.offset == 40
 

@@ -138,18 +138,14 @@ def test_load_smplh_pkl_roundtrip(tmp_path, consts):
 def test_symbols_declared_exported_and_bound():
     import __graft_entry__
     assert "body_model.hip" in __graft_entry__.SOURCES
-    declared = _cabi.declared_symbols()
-    for s in _cabi.SMPLH_SYMBOLS:
-        assert s in declared
+    assert {"thmr_smplh_create", "thmr_smplh_destroy", "thmr_smplh_forward", "thmr_op_mean_row_dist"} <= set(_cabi.declared_symbols())
     assert _cabi.ABI_VERSION == 5
     header = open(_cabi.HEADER).read()
     assert "#define THMR_ABI_VERSION 5" in header and f"#define THMR_MEAN_ROW_DIST_WS {_cabi.MEAN_ROW_DIST_WS}" in header
     assert [f[0] for f in _cabi.SmplhDesc._fields_][:8] == ["v_template", "shapedirs", "posedirs", "J_regressor", "lbs_weights", "parents",
                                                            "extra_verts", "on_device"]
     if os.path.exists(_cabi.LIB_PATH):
-        lib = _cabi.load()
-        for s in _cabi.SMPLH_SYMBOLS:
-            assert hasattr(lib, s)
+        lib = _cabi.load()              # raises unless the library exports every declared function
         # argument refusals happen before any HIP call, so they can be exercised without a device
         assert lib.thmr_smplh_create(None, 4, 0, None) != 0
         assert lib.thmr_op_mean_row_dist(None, None, 73, 1, 22, 2, None, None, None) != 0

@@ -214,12 +214,8 @@ def test_vanilla_tokenizer_refuses_before_touching_a_gpu(tmp_path, monkeypatch):
 def test_new_symbols_declared_and_exported(built_lib):
     from tokenhmr_amd import _cabi, ops
     from tokenhmr_amd.engine import Engine
-    declared = _cabi.declared_symbols()
-    assert set(_cabi.TOKENIZER_RT_SYMBOLS) == {"thmr_vq_decode_idx", "thmr_tokenizer_roundtrip", "thmr_op_vq_stats", "thmr_op_rotmat_to_aa"}
-    assert not set(_cabi.TOKENIZER_RT_SYMBOLS) & set(_cabi.ROWOPS_SYMBOLS)
-    for lib in (built_lib, _cabi.load(exp=True)):
-        for s in _cabi.TOKENIZER_RT_SYMBOLS:
-            assert s in declared and hasattr(lib, s), s
+    # (exported and typed in both builds, like every declared function: tests/test_cabi_header.py)
+    assert {"thmr_vq_decode_idx", "thmr_tokenizer_roundtrip", "thmr_op_vq_stats", "thmr_op_rotmat_to_aa"} <= set(_cabi.declared_symbols())
     assert [n for n, _ in _cabi.TokenizerOut._fields_] == ["idx", "latent", "pose6d", "rotmat", "aa", "commit_loss", "perplexity", "code_count",
                                                           "accumulate_counts", "reserved"]
     assert callable(Engine.vq_decode_idx) and callable(Engine.tokenizer_roundtrip) and callable(ops.vq_stats) and callable(ops.rotmat_to_aa)

@@ -2,8 +2,12 @@
 
 There is NO CPU fallback: if the shared library is missing or a symbol is absent this module
 raises, so a GPU box can never silently run anything but the HIP path.
+
+The header is the one source of every signature: bind() types each entry point from its prototype there (param_ctype is the rule).
+Hand-written here are only the struct mirrors and the constants, and tests/test_cabi_header.py holds both against the header.
 """
 import ctypes as C
+import functools
 import os
 import re
 
@@ -174,45 +178,90 @@ class ProfEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
 
-def declared_functions():
-    """{name: return type as written} of every function the header declares: 'int', 'int64_t', 'void' or 'const char*'."""
-    with open(HEADER) as f:
-        text = f.read()
+# every struct the header defines -> its mirror above (tests/test_cabi_header.py holds each against the compiler's layout of the header)
+STRUCTS = {"thmr_config": Config, "thmr_tensor_desc": TensorDesc, "thmr_smpl_desc": SmplDesc, "thmr_smplh_desc": SmplhDesc,
+           "thmr_val_loss_desc": ValLossDesc, "thmr_val_loss_in": ValLossIn, "thmr_val_loss_out": ValLossOut, "thmr_outputs": Outputs,
+           "thmr_crop_desc": CropDesc, "thmr_frame_crop": FrameCrop, "thmr_jpeg_info": JpegInfo, "thmr_jpeg_plan": JpegPlan,
+           "thmr_jpeg_item": JpegItem, "thmr_png_item": PngItem, "thmr_render_light": RenderLight, "thmr_render_desc": RenderDesc,
+           "thmr_sheet_desc": SheetDesc, "thmr_gemm_choice": GemmChoice, "thmr_vit_plan_desc": VitPlanDesc,
+           "thmr_tokenizer_out": TokenizerOut, "thmr_prof_entry": ProfEntry}
+
+_RESTYPES = {"int": C.c_int, "int64_t": C.c_int64, "void": None, "const char*": C.c_char_p}
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_HOST_OUT = {"size_t": C.c_size_t, "int64_t": C.c_int64, "uint64_t": C.c_uint64}     # T* of these: host out-parameters, never device memory
+_ADDRESSES = ("void", "float", "int32_t", "uint8_t", "int16_t")                      # T* of these, and of an opaque handle: a plain address
+
+
+def parse_prototypes(text):
+    """({name: (return type as written, [parameter type without `const`, blanks and the parameter's name, ...])} of every function that
+    the C text declares, the set of its opaque handle types `typedef struct thmr_x thmr_x;`)."""
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return {name: ret.strip() for ret, name in re.findall(r"([A-Za-z_][\w \t*]*?)\b(thmr_[a-z0-9_]+)\s*\(", text)}
+    funcs = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t*]*?)\b(thmr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        funcs[name] = (ret.strip(), [] if params.strip() == "void" else [re.sub(r"\bconst\b|\w+\s*$|\s", "", p) for p in params.split(",")])
+    return funcs, set(re.findall(r"typedef\s+struct\s+(thmr_\w+)\s+\1\s*;", text))
+
+
+def param_ctype(t, opaque=()):
+    """The ctypes type of one parameter type of parse_prototypes: the ONE rule every entry point is typed by.  Anything else raises."""
+    base, stars = t.rstrip("*"), len(t) - len(t.rstrip("*"))
+    address = base in _ADDRESSES or base in opaque
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and base in STRUCTS:
+        return C.POINTER(STRUCTS[base])
+    if stars == 2 and (base == "char" or address):
+        return C.POINTER(C.c_char_p if base == "char" else C.c_void_p)
+    if stars == 1 and base in _HOST_OUT:
+        return C.POINTER(_HOST_OUT[base])
+    if stars == 1 and address:
+        return C.c_void_p
+    raise RuntimeError(f"tokenhmr_hip.h has a parameter of type '{t}': _cabi.param_ctype() knows the scalars {sorted(_SCALARS)}, pointers "
+                       f"to the structs of _cabi.STRUCTS, to {sorted(_HOST_OUT)}, to {sorted(_ADDRESSES)} and to opaque handles, and T**")
+
+
+@functools.lru_cache(maxsize=None)
+def _header():
+    """(parse_prototypes' functions, {name: (restype, argtypes)} in ctypes) of include/tokenhmr_hip.h, read once per process."""
+    with open(HEADER) as f:
+        funcs, opaque = parse_prototypes(f.read())
+    for name, (ret, _) in funcs.items():                 # every return type as the header writes it
+        if ret not in _RESTYPES:
+            raise RuntimeError(f"tokenhmr_hip.h declares {name} as returning '{ret}': _cabi knows {sorted(_RESTYPES)}")
+    return funcs, {name: (_RESTYPES[ret], [param_ctype(t, opaque) for t in params]) for name, (ret, params) in funcs.items()}
+
+
+def declared_functions():
+    """{name: (return type, [parameter types])} of every function the header declares, as parse_prototypes gives them."""
+    return dict(_header()[0])
+
+
+def declared_return_types():
+    """{name: return type as written}: 'int', 'int64_t', 'void' or 'const char*'."""
+    return {name: ret for name, (ret, _) in _header()[0].items()}
 
 
 def declared_symbols():
     """Every function the header declares (used by the symbol-export test)."""
-    return sorted(declared_functions())
+    return sorted(_header()[0])
+
+
+def bind(lib, partial=False):
+    """Sets restype and argtypes, derived from the header, on every declared function that `lib` exports.  A declared function it does not
+    export raises here, by name — unless `partial`: then it is left unbound and fails (AttributeError) where it is called."""
+    missing = []
+    for name, (restype, argtypes) in _header()[1].items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        else:
+            missing.append(name)
+    if missing and not partial:
+        raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {sorted(missing)}")
+    return lib
 
 
 _libs = {}
-
-# the stateless operators of the row / glue / head kernels: new symbols under ABI 5, which an older build loaded by path lacks
-ROWOPS_SYMBOLS = ("thmr_op_splitk_resid_ln", "thmr_op_add_ln64", "thmr_op_transpose", "thmr_op_softmax_argmax", "thmr_op_cross_attn",
-                  "thmr_op_im2col_patch", "thmr_op_conv3_gather", "thmr_op_conv_gather", "thmr_op_conv_repack", "thmr_op_vq_argmin_rows",
-                  "thmr_op_code_norm", "thmr_op_head_finish", "thmr_op_decoder_init")
-
-# the tokenizer round trip (csrc/tokenizer.hip): new symbols under ABI 5 as well — hard decode, the round trip, and its two kernels alone
-TOKENIZER_RT_SYMBOLS = ("thmr_vq_decode_idx", "thmr_tokenizer_roundtrip", "thmr_op_vq_stats", "thmr_op_rotmat_to_aa")
-
-# the SMPL-H body model and the tokenizer's mesh metrics (csrc/smplh.hip, eval.hip): new symbols under ABI 5 as well
-SMPLH_SYMBOLS = ("thmr_smplh_create", "thmr_smplh_destroy", "thmr_smplh_forward", "thmr_op_mean_row_dist")
-
-# the forward value of the loss (csrc/loss.hip): new symbols under ABI 5 as well
-LOSS_SYMBOLS = ("thmr_val_loss", "thmr_op_token_ce")
-
-# a batch of crops from a table of frames (csrc/crop.hip): a new symbol under ABI 5 as well
-FRAMES_SYMBOLS = ("thmr_cropper_run_frames",)
-
-# baseline JPEG decoding (csrc/jpeg.hip): new symbols under ABI 5 as well
-JPEG_SYMBOLS = ("thmr_jpeg_probe", "thmr_jpeg_entropy_decode", "thmr_jpeg_decode_host", "thmr_jpeg_create", "thmr_jpeg_destroy",
-                "thmr_jpeg_last_error", "thmr_jpeg_decode_batch")
-
-# PNG encoding (csrc/png.hip): new symbols under ABI 5 as well
-PNG_SYMBOLS = ("thmr_png_segment_bytes", "thmr_png_bound", "thmr_png_encode_host", "thmr_png_create", "thmr_png_destroy",
-               "thmr_png_last_error", "thmr_png_encode_batch")
 
 
 def load(exp=None):
@@ -220,7 +269,8 @@ def load(exp=None):
     exp = a PATH (str): that very file — another BUILD of this library, e.g. the previous round's, loaded beside the current one by
     scripts/ab_same_box.py so that two builds are timed interleaved in one process on one box (A/B tooling only; ABI 3 and 4 builds
     accepted: no struct layout or signature changed between 3 and 5 — 4 changed the creation default of the ViT GEMM mode, 5 gave
-    thmr_config.reserved[0] a meaning and added thmr_mode_bytes, which such a build simply lacks)."""
+    thmr_config.reserved[0] a meaning and added thmr_mode_bytes, which such a build simply lacks).  A build loaded by path is bound
+    with partial=True: whatever declared function it lacks fails at the call, not here; the two builds of this tree must export all."""
     if exp is None:
         exp = os.environ.get("THMR_LIB", "") == "exp"
     if isinstance(exp, str):
@@ -246,121 +296,9 @@ def load(exp=None):
     except ImportError:
         pass
     lib = C.CDLL(path)
-    declared = declared_functions()
-    restypes = {"int": C.c_int, "int64_t": C.c_int64, "void": None, "const char*": C.c_char_p}
-    for name, ret in declared.items():                   # every return type as the header writes it
-        if ret not in restypes:
-            raise RuntimeError(f"tokenhmr_hip.h declares {name} as returning '{ret}': _cabi.load() knows {sorted(restypes)}")
-        if hasattr(lib, name):
-            getattr(lib, name).restype = restypes[ret]
-    older = isinstance(exp, str) and lib.thmr_abi_version() in (3, 4)          # a previous round's build, loaded by path (A/B tooling)
-    # a build loaded by path may also predate thmr_renderer_sheet / thmr_debug_vit_plan (added without an ABI change: new symbols, no layout touched)
-    missing = [s for s in sorted(declared) if not hasattr(lib, s) and not (older and s in ("thmr_mode_bytes",))
-               and not (isinstance(exp, str) and s in ("thmr_renderer_sheet", "thmr_debug_vit_plan") + ROWOPS_SYMBOLS + TOKENIZER_RT_SYMBOLS + FRAMES_SYMBOLS + JPEG_SYMBOLS + PNG_SYMBOLS)]
-    if missing:
-        raise RuntimeError(f"libtokenhmr_hip.so lacks symbols declared in tokenhmr_hip.h: {missing}")
-    vp, i32, i64, f32, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
-    lib.thmr_last_error.argtypes = [vp]
-    lib.thmr_arena_bytes.argtypes = [C.POINTER(Config), C.POINTER(sz), C.POINTER(sz)]
-    lib.thmr_spec.argtypes = [C.POINTER(Config), i32, C.POINTER(C.c_char_p), C.POINTER(i64)]
-    if hasattr(lib, "thmr_mode_bytes"):
-        lib.thmr_mode_bytes.argtypes = [C.POINTER(Config), i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
-    lib.thmr_create.argtypes = [C.POINTER(Config), vp, vp, C.POINTER(vp)]
-    lib.thmr_destroy.argtypes = [vp]
-    lib.thmr_load_weights.argtypes = [vp, C.POINTER(TensorDesc), sz, vp]
-    lib.thmr_load_smpl.argtypes = [vp, C.POINTER(SmplDesc), vp]
-    lib.thmr_finalize_weights.argtypes = [vp, i32, vp]
-    lib.thmr_weight_arena.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
-    lib.thmr_forward.argtypes = [vp, vp, i32, C.POINTER(Outputs), vp]
-    lib.thmr_engine_status.argtypes = [vp, vp]
-    lib.thmr_debug_decoder_timeline.argtypes = [vp, C.POINTER(C.c_uint64), i32, vp]
-    if hasattr(lib, "thmr_debug_vit_plan"):
-        lib.thmr_debug_vit_plan.argtypes = [C.POINTER(Config), i32, i32, i32, C.POINTER(VitPlanDesc)]
-    lib.thmr_vit_forward.argtypes = [vp, vp, i32, vp, vp]
-    lib.thmr_head_forward.argtypes = [vp, vp, i32, C.POINTER(Outputs), vp]
-    lib.thmr_lbs_forward.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    lib.thmr_vq_argmin.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.thmr_encode_tokens.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.thmr_vq_decode.argtypes = [vp, vp, i32, vp, vp]
-    lib.thmr_op_gemm.argtypes = [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, i32, vp]
-    lib.thmr_op_layernorm.argtypes = [vp, vp, vp, vp, i32, i32, f32, i32, vp]
-    lib.thmr_op_vit_attention.argtypes = [vp, vp, i32, vp]
-    lib.thmr_op_vit_attention_variant.argtypes = [vp, vp, i32, i32, vp]
-    lib.thmr_op_vit_attention_split3.argtypes = [vp, vp, i32, vp]
-    lib.thmr_op_vit_attention_b16.argtypes = [vp, vp, i32, i32, i32, vp]
-    lib.thmr_op_split3.argtypes = [vp, i64, vp, i64, i64, i32, vp]
-    lib.thmr_op_gemm_split3.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, i32, vp]
-    lib.thmr_op_gemm_split3_out_split3.argtypes = [vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, f32, i32, i32, vp]
-    lib.thmr_op_rot6d.argtypes = [vp, vp, i32, vp]
-    lib.thmr_op_aa_to_rotmat.argtypes = [vp, vp, i32, vp]
-    if hasattr(lib, "thmr_op_splitk_resid_ln"):          # the row / glue / head operators (added without an ABI change)
-        lib.thmr_op_splitk_resid_ln.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, i32, vp]
-        lib.thmr_op_add_ln64.argtypes = [vp, vp, vp, vp, vp, vp, i32, f32, vp]
-        lib.thmr_op_transpose.argtypes = [vp, vp, i32, i32, i32, vp]
-        lib.thmr_op_softmax_argmax.argtypes = [vp, vp, vp, i32, vp]
-        lib.thmr_op_cross_attn.argtypes = [vp, vp, i64, i32, vp, i32, vp]
-        lib.thmr_op_im2col_patch.argtypes = [vp, vp, i32, i32, vp]
-        lib.thmr_op_conv3_gather.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-        lib.thmr_op_conv_gather.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-        lib.thmr_op_conv_repack.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-        lib.thmr_op_vq_argmin_rows.argtypes = [vp, vp, vp, vp, vp, i32, vp]
-        lib.thmr_op_code_norm.argtypes = [vp, vp, i32, vp]
-        lib.thmr_op_head_finish.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp]
-        lib.thmr_op_decoder_init.argtypes = [vp, vp, vp, i32, i32, vp]
-    if hasattr(lib, "thmr_tokenizer_roundtrip"):         # the tokenizer round trip (added without an ABI change)
-        lib.thmr_vq_decode_idx.argtypes = [vp, vp, i32, vp, vp]
-        lib.thmr_tokenizer_roundtrip.argtypes = [vp, vp, i32, C.POINTER(TokenizerOut), vp]
-        lib.thmr_op_vq_stats.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
-        lib.thmr_op_rotmat_to_aa.argtypes = [vp, vp, i32, vp]
-    if hasattr(lib, "thmr_smplh_create"):                # the SMPL-H body model (added without an ABI change)
-        lib.thmr_smplh_create.argtypes = [C.POINTER(SmplhDesc), i32, i32, C.POINTER(vp)]
-        lib.thmr_smplh_destroy.argtypes = [vp]
-        lib.thmr_smplh_forward.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]
-        lib.thmr_op_mean_row_dist.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    if hasattr(lib, "thmr_val_loss"):                    # the forward value of the loss (added without an ABI change)
-        lib.thmr_val_loss.argtypes = [C.POINTER(ValLossDesc), C.POINTER(ValLossIn), i32, C.POINTER(ValLossOut), vp, vp]
-        lib.thmr_op_token_ce.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.thmr_smpl_create.argtypes = [C.POINTER(SmplDesc), i32, i32, C.POINTER(vp)]
-    lib.thmr_smpl_destroy.argtypes = [vp]
-    lib.thmr_smpl_forward.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
-    lib.thmr_eval_pose.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
-    lib.thmr_regress_joints.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    lib.thmr_cropper_create.argtypes = [i32, C.POINTER(vp)]
-    lib.thmr_cropper_destroy.argtypes = [vp]
-    lib.thmr_cropper_last_error.argtypes = [vp]
-    lib.thmr_cropper_run.argtypes = [vp, vp, i32, i32, i64, C.POINTER(CropDesc), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
-    if hasattr(lib, "thmr_cropper_run_frames"):          # the frame-table entry (added without an ABI change)
-        lib.thmr_cropper_run_frames.argtypes = [vp, C.POINTER(FrameCrop), i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
-    if hasattr(lib, "thmr_jpeg_probe"):                  # baseline JPEG decoding (added without an ABI change)
-        lib.thmr_jpeg_probe.argtypes = [vp, sz, C.POINTER(JpegInfo)]
-        lib.thmr_jpeg_entropy_decode.argtypes = [vp, sz, C.POINTER(i32), vp, i64, C.POINTER(JpegPlan)]
-        lib.thmr_jpeg_decode_host.argtypes = [vp, sz, C.POINTER(i32), i32, vp, i64]
-        lib.thmr_jpeg_create.argtypes = [i32, C.POINTER(vp)]
-        lib.thmr_jpeg_destroy.argtypes = [vp]
-        lib.thmr_jpeg_last_error.argtypes = [vp]
-        lib.thmr_jpeg_decode_batch.argtypes = [vp, C.POINTER(JpegItem), i32, i32, vp]
-    if hasattr(lib, "thmr_png_encode_batch"):            # PNG encoding (added without an ABI change)
-        lib.thmr_png_segment_bytes.argtypes = []
-        lib.thmr_png_bound.argtypes = [i32, i32, i32]
-        lib.thmr_png_encode_host.argtypes = [C.POINTER(PngItem)]
-        lib.thmr_png_create.argtypes = [i32, C.POINTER(vp)]
-        lib.thmr_png_destroy.argtypes = [vp]
-        lib.thmr_png_last_error.argtypes = [vp]
-        lib.thmr_png_encode_batch.argtypes = [vp, C.POINTER(PngItem), i32, vp]
-    lib.thmr_renderer_create.argtypes = [i32, vp, i32, i32, C.POINTER(vp)]
-    lib.thmr_renderer_destroy.argtypes = [vp]
-    lib.thmr_renderer_last_error.argtypes = [vp]
-    lib.thmr_renderer_run.argtypes = [vp, C.POINTER(RenderDesc), vp, vp, i32, vp, vp, vp]
-    if hasattr(lib, "thmr_renderer_sheet"):
-        lib.thmr_renderer_sheet.argtypes = [vp, C.POINTER(SheetDesc), vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.thmr_pack_records.argtypes = [C.POINTER(Outputs), i32, vp, vp]
-    lib.thmr_bcast_weights.argtypes = [vp, vp, i32, vp]
-    lib.thmr_allgather_records.argtypes = [vp, vp, i32, vp, vp]
-    lib.thmr_prof_enable.argtypes = [vp, i32]
-    lib.thmr_set_vit_gemm.argtypes = [vp, i32, vp]
-    lib.thmr_get_vit_gemm.argtypes = [vp]
-    lib.thmr_prof_collect.argtypes = [vp, C.POINTER(ProfEntry), i32]
-    if lib.thmr_abi_version() != ABI_VERSION and not older:
+    bind(lib, partial=isinstance(exp, str))
+    version = lib.thmr_abi_version()
+    if version != ABI_VERSION and not (isinstance(exp, str) and version in (3, 4)):    # a previous round's build, loaded by path
         raise RuntimeError("libtokenhmr_hip.so ABI version mismatch")
     _libs[exp] = lib
     return lib
