@@ -598,7 +598,11 @@ int thmr_regress_joints(const float* J_dev, const float* verts_dev, int32_t n_jo
  *   sigma   gaussian sigma of the anti-alias blur applied before the warp, 0 = none; truncate: 4.0 (vitdet) / 3.0 (get_example)
  *   frame   (H, W, 3) uint8, row_stride bytes per row; swap_rb = 1 flips the channel order (BGR frame -> RGB planes)
  *   mean/std  in 0..255 units, indexed by OUTPUT channel.
- * The handle owns grow-only device scratch for the blurred regions; growing it synchronises the stream. */
+ * The handle owns grow-only device scratch for the blurred regions; growing it synchronises the stream.
+ * thmr_cropper_run refuses with THMR_ERR_INVALID, before any HIP call: a null buffer, H, W, n or patch <= 0, patch > 4096,
+ * row_stride < W * 3, a frame side above 32767 (the warp's 16-bit texel coordinates), a singular or non-finite affine, a negative or
+ * non-finite sigma, truncate <= 0, and a blur radius above 4096: anything but truncate * sigma + 0.5 < 4097, compared in double,
+ * so an infinite or NaN product is refused too. */
 typedef struct thmr_crop_desc {
     double M[6];
     double sigma;

@@ -84,6 +84,20 @@ def test_entry_refuses_before_any_hip_call(built_lib):
     # entirely outside: the box is empty, a null pointer and an empty window are fine
     Mo = CO.gen_trans_from_patch_cv(-500, -500, 30, 30, 8, 8, 1.0, 0)
     assert _one_item(lib, Mo, 8, 48, 64, (0, 0, 0, 0), ptr=None)[1] == "null cropper"
+    # the blur radius int(truncate * sigma + 0.5) is compared in double before it is converted: 4096 is the largest, and a product
+    # beyond int (or infinite) is a refusal like any other, not a conversion the weights are then sized from
+    from tokenhmr_amd.preprocess import source_window
+    full = (0, 0, 64, 48)
+    for sigma, truncate in [(1e9, 3.0), (1e10, 3.0), (1e300, 3.0), (1.0, 1e300), (1e300, 1e300), (1366.0, 3.0)]:
+        rc, msg = _one_item(lib, M, 8, 48, 64, full, sigma=sigma, truncate=truncate)
+        assert rc != 0 and msg == "crop 0: blur radius too large", (sigma, truncate, msg)
+        with pytest.raises(ValueError, match="blur radius too large"):
+            source_window(M, 8, 48, 64, sigma, truncate)
+    for sigma, truncate in [(1365.0, 3.0), (0.1, 3.0)]:          # radius 4095 and radius 0
+        assert _one_item(lib, M, 8, 48, 64, full, sigma=sigma, truncate=truncate)[1] == "null cropper", (sigma, truncate)
+        win = source_window(M, 8, 48, 64, sigma, truncate)
+        assert win is not None and _one_item(lib, M, 8, 48, 64, win, sigma=sigma, truncate=truncate)[1] == "null cropper"
+    assert source_window(M, 8, 48, 64, 1365.0, 3.0) == full and source_window(M, 8, 48, 64, 0.1, 3.0) == source_window(M, 8, 48, 64)
 
 
 def _seeded_affines():

@@ -262,8 +262,10 @@ bool prep_crop(const double* Mfwd, double sigma, double truncate, int i, int pat
     box.x0 = box.bx0 = x0; box.x1 = box.bx1 = x1; box.y0 = box.by0 = y0; box.y1 = box.by1 = y1;
     if (blur && x0 <= x1 && y0 <= y1) {
         d.blur = 1;
-        d.lw = (int)(truncate * sigma + 0.5);            // scipy: int(truncate * sd + 0.5)
-        if (d.lw > 4096) { err = "crop " + std::to_string(i) + ": blur radius too large"; return false; }
+        // compared in double BEFORE the conversion: a product of 2^31 or more, inf or NaN has no int value (and would size the weights)
+        const double r = truncate * sigma + 0.5;
+        if (!(r < 4097.0)) { err = "crop " + std::to_string(i) + ": blur radius too large"; return false; }
+        d.lw = (int)r;                                   // scipy: int(truncate * sd + 0.5)
         d.rx0 = (int)x0; d.ry0 = (int)y0; d.rw = (int)(x1 - x0 + 1); d.rh = (int)(y1 - y0 + 1);
         d.tx0 = (int)std::max<long long>(x0 - d.lw, 0);
         d.tw = (int)(std::min<long long>(x1 + d.lw, W - 1) - d.tx0 + 1);
@@ -322,9 +324,11 @@ int thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int32
     if (!frame_dev || !crops || !out_dev || !mean || !std_) return g_crop_err.invalid(c, "null buffer");
     if (H <= 0 || W <= 0 || n <= 0 || patch <= 0 || patch > 4096 || row_stride < (int64_t)W * 3)
         return g_crop_err.invalid(c, "bad frame / patch geometry");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(c->device) != hipSuccess) return g_crop_err.invalid(c, "hipSetDevice failed");
+    // as thmr_cropper_run_frames: the warp keeps 16-bit texel coordinates (saturate_cast<short>); on a wider frame a saturated
+    // coordinate would still pass the in-frame test while the blurred region is sized from the unsaturated corners
+    if (H > 32767 || W > 32767) return g_crop_err.invalid(c, "bad frame geometry");
 
+    // every crop is planned, and may be refused, before any HIP call
     std::vector<CropDev> cds(n);
     std::vector<double> wts;
     CropPlan plan;
@@ -335,6 +339,8 @@ int thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int32
             return g_crop_err.invalid(c, m);
     }
     const int64_t max_v = plan.max_v, max_h = plan.max_h;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipSetDevice(c->device) != hipSuccess) return g_crop_err.invalid(c, "hipSetDevice failed");
     hipError_t e;
     const char* what;
     e = grow_synced(st, {c->cds.want(n, (size_t)n * 2, "hipMalloc(crop descriptors)"),

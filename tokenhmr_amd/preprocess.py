@@ -77,7 +77,7 @@ def source_window(M, patch, H, W, sigma=0.0, truncate=3.0):
     thmr_cropper_run_frames computes it (include/tokenhmr_hip.h), restated in Python floats (IEEE double, no fused operations) and
     integers: the fixed-point source coordinate of the four patch corners, [lo - 1, hi + 2] on each axis, clipped to the frame; for a
     blurred crop (sigma > 1e-15) widened by the kernel radius int(truncate * sigma + 0.5) on all four sides, clipped again.
-    Raises ValueError where the C side refuses the crop itself (singular affine, bad sigma / truncate)."""
+    Raises ValueError where the C side refuses the crop itself (singular affine, bad sigma / truncate, a blur radius above 4096)."""
     m = [float(v) for v in np.asarray(M, dtype=np.float64).reshape(6)]
     sigma, truncate, patch, H, W = float(sigma), float(truncate), int(patch), int(H), int(W)
     # cv::warpAffine: invert the forward 2x3 matrix in double
@@ -101,7 +101,10 @@ def source_window(M, patch, H, W, sigma=0.0, truncate=3.0):
     if x0 > x1 or y0 > y1:
         return None
     if sigma > 1e-15:
-        lw = int(truncate * sigma + 0.5)
+        r = truncate * sigma + 0.5
+        if not r < 4097.0:                    # inf and NaN included, before int() meets them
+            raise ValueError("blur radius too large")
+        lw = int(r)
         x0, x1, y0, y1 = max(x0 - lw, 0), min(x1 + lw, W - 1), max(y0 - lw, 0), min(y1 + lw, H - 1)
     return x0, y0, x1 - x0 + 1, y1 - y0 + 1
 
