@@ -248,7 +248,7 @@ class _GoldenRows:
         return v[:self._B] if k in self._PER_CROP else v
 
 
-# Every regime of the batch size (csrc/engine.hip: the association of the proj / fc2 K sums, the head's kernels) on both sides of each
+# Every regime of the batch size (csrc/engine_paths.hip: the association of the proj / fc2 K sums, the head's kernels) on both sides of each
 # boundary — split3: 1-2 | 3-4 | 5-15 | 16-31 | >= 32 (head: 6 | 7); f32: 1-2 | 3-6 | 7-16 | >= 17 — incl. demo.py:70's batch of 8 and
 # README.md:316's 32.
 REGIME_BATCHES = (1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 13, 14, 15, 16, 17, 24, 31, 32)      # incl. the sizes whose qkv / fc1 run as tile streams (round 6: 5-7, 9, 10, 12-14, 24)
@@ -611,7 +611,7 @@ def test_odd_batch_sizes_vs_oracle(built_lib, cuda_dev, B):
 def test_large_ragged_batch_equals_its_chunks(built_lib, cuda_dev):
     """Maximum-size edge: one call with B = 200 (M = 38400 rows: 300 row tiles, the last LBS crop group and the row groups
     of the head partially filled).  Per-crop results may not depend on the batch a crop travels in, WITHIN a regime of the
-    engine: the head runs as fused persistent kernels up to 128 crops and as a chain of tiled GEMMs above (csrc/engine.hip
+    engine: the head runs as fused persistent kernels up to 128 crops and as a chain of tiled GEMMs above (csrc/engine_paths.hip
     kFusedHeadMaxB; the ViT itself is in its large-batch regime from 7 crops on).  So: the 200-crop call equals, bit for bit,
     136-crop calls over the same crops (both above 128); a 100-crop call equals its 64 + 36 chunks (all at most 128); and
     across the boundary the two regimes agree to fp32 summation-order differences."""

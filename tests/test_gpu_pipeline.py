@@ -263,7 +263,7 @@ def test_run_eval_loop_matches_manual_loop(built_lib, cuda_dev):
 
 
 def test_head_regimes_agree_and_persistent_decoders_coexist(built_lib, cuda_dev):
-    """The head has two regimes (csrc/engine.hip kFusedHeadMaxB): up to 128 crops the persistent decoder kernel + the
+    """The head has two regimes (csrc/engine_paths.hip kFusedHeadMaxB): up to 128 crops the persistent decoder kernel + the
     one-workgroup-per-crop mixer kernel, above it the chain of tiled GEMMs.  (1) Both must agree with the CPU oracle, and a crop
     must get the same answer (to fp32 summation-order differences) whichever regime its batch falls in.  (2) Two engines that
     launch their persistent decoder kernels concurrently on two streams at a batch size where EACH asks for every CU (>= 49
@@ -536,7 +536,7 @@ def test_forward_is_captured_into_a_hip_graph_and_replays_bit_identically(built_
 
 @pytest.mark.parametrize("case", PA.CASES, ids=[c["name"] for c in PA.CASES])
 def test_profiler_accounting_is_pinned(built_lib, cuda_dev, case):
-    """Every ProfScope of csrc/engine.hip records a class, flops and bytes computed on the host from the call's shapes and the plan: after one
+    """Every ProfScope of csrc/engine_paths.hip records a class, flops and bytes computed on the host from the call's shapes and the plan: after one
     thmr_forward, launches / flops / bytes of EVERY profiler class equal what the library of the commit named in
     tests/golden/prof_accounting.json reported for the same call (scripts/gen_golden_prof_accounting.py) — exactly: nothing here is
     measured, `ms` is never compared.  A census of the launch sequence per class and of the accounting formulas in every regime of

@@ -1,5 +1,5 @@
-// Host-side plumbing shared by the files that own C entry points of include/tokenhmr_hip.h: engine.hip (every call that takes a
-// thmr_engine) and ops_abi.hip (the stateless operators).  Host only: no kernel includes this (SmplConsts::derive calls two launchers).
+// Host-side plumbing shared by the files that own C entry points of include/tokenhmr_hip.h: the engine units (engine.hip,
+// engine_weights.hip, engine_paths.hip: every call that takes a thmr_engine) and ops_abi.hip (the stateless operators).  Host only: no kernel includes this (SmplConsts::derive calls two launchers).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +18,7 @@ int fail(thmr_engine* e, int code, const std::string& msg);
 int fail(int code, const std::string& msg);
 
 // HIP_OK (a HIP call) / LAUNCH_OK (a launch_* helper: 0, -1 = it refused the arguments, else the launch failed) return from the calling
-// function through THMR_FAIL(code, msg), which the including file defines: engine.hip as fail(e, code, msg), ops_abi.hip as fail(code, msg).
+// function through THMR_FAIL(code, msg), which the including file defines: engine_state.h as fail(e, code, msg), ops_abi.hip as fail(code, msg).
 #define HIP_OK(call)                                                                          \
     do {                                                                                      \
         hipError_t _e = (call);                                                               \
