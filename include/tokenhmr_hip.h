@@ -860,11 +860,19 @@ int  thmr_jpeg_decode_batch(thmr_jpeg* j, const thmr_jpeg_item* items_host, int3
  *                 each compressed alone — LZ77 with matches that never reach behind the segment start, one fixed-Huffman block, and
  *                 (but for the last) an empty stored block 00 00 FF FF back to a byte boundary; a segment whose coded form would be
  *                 larger than a stored block is a stored block — then the Adler-32.  No file is larger than thmr_png_bound().
+ *   compression   THMR_PNG_FIXED writes the file above.  THMR_PNG_DYNAMIC keeps the filters, the segments and the LZ77 tokens, and gives
+ *                 a segment ONE dynamic-Huffman block where that takes strictly fewer bits than the fixed block, header included.  The
+ *                 block rule (csrc/png_math.h): the tokens' literal / length and distance symbols are counted with one end-of-block, a
+ *                 distance alphabet with fewer than two symbols in use is padded to two; optimal code lengths limited to 15 bits (7 for
+ *                 the code-length alphabet) by thmr_png_code_lengths, ties to the lower symbol index; canonical codes (RFC 1951
+ *                 3.2.2); HLIT, HDIST and HCLEN trimmed; the lengths run-length coded greedily with the symbols 16, 17 and 18.  The
+ *                 stored-block rule then applies to the winner, so thmr_png_bound() holds in both modes.
  *   refused       before any HIP call, the message names the item: THMR_ERR_UNSUPPORTED for a 16-bit dtype and for 2 channels;
  *                 THMR_ERR_INVALID for any other dtype / channel count / rounding, width or height < 1, a filtered stream of 2^31 bytes
- *                 or more, a null pointer, and a capacity below thmr_png_bound(). */
+ *                 or more, a compression other than the two named, a null pointer, and a capacity below thmr_png_bound(). */
 enum { THMR_PNG_U8 = 0, THMR_PNG_F32 = 1, THMR_PNG_U16 = 2 /* refused by name */ };
 enum { THMR_PNG_ROUND_NEAREST = 0, THMR_PNG_ROUND_TRUNC = 1 };
+enum { THMR_PNG_FIXED = 0, THMR_PNG_DYNAMIC = 1 };
 typedef struct thmr_png_item {
     const void* pixels;                 /* element (0, 0, 0): device memory for thmr_png_encode_batch, host for thmr_png_encode_host */
     int32_t dtype;                      /* THMR_PNG_U8 / THMR_PNG_F32 */
@@ -873,7 +881,7 @@ typedef struct thmr_png_item {
     float scale;                        /* float32 input only */
     int32_t rounding;                   /* THMR_PNG_ROUND_* */
     int32_t swap_rb;
-    int32_t reserved;                   /* 0 */
+    int32_t compression;                /* THMR_PNG_FIXED / THMR_PNG_DYNAMIC (the field was `reserved`, 0: a caller that zeroed it gets the fixed mode) */
     uint8_t* out;                       /* host: the file */
     int64_t capacity;                   /* bytes at out, >= thmr_png_bound(width, height, channels) */
     int64_t written;                    /* set by the call: the file's length */
@@ -882,6 +890,10 @@ int thmr_png_segment_bytes(void);
 /* raw + 5 bytes per segment + 6 zlib bytes + 57 container bytes; 0 for arguments the encoder refuses */
 int64_t thmr_png_bound(int32_t width, int32_t height, int32_t channels);
 int thmr_png_encode_host(thmr_png_item* item);
+/* The code lengths of the dynamic mode, the very routine the kernels run: lens[s] for n <= 286 symbols with frequencies freq[s] (0 ...
+ * 2^22 - 1), optimal under the limit max_bits (1 ... 15, with 2^max_bits >= the symbols in use), 0 where the frequency is 0; one
+ * symbol in use gets length 1.  Host only.  THMR_ERR_INVALID for a null pointer or an argument outside these ranges. */
+int thmr_png_code_lengths(const int32_t* freq, int32_t n, int32_t max_bits, int32_t* lens);
 /* The handle owns grow-only device scratch (filtered stream, one slot per segment, the packed streams) and pinned staging.  One call
  * encodes n images of n sizes, dtypes and layouts with ONE descriptor upload and THREE launches (convert + filter of every row;
  * deflate of every segment, one wave each; gather of the segments into one packed stream), synchronises `stream`, and returns with the

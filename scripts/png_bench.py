@@ -1,7 +1,7 @@
 """Times PNG encoding of device images, device against host, in one process on one GPU box with the arms interleaved, and writes
 profiles/png_encode.jsonl.
 
-    python scripts/png_bench.py [--out profiles/png_encode.jsonl] [--rounds 5]
+    python scripts/png_bench.py [--out profiles/png_encode.jsonl] [--rounds 5] [--compression fixed,dynamic]
 
 Workloads (procedural images: a white ground, a shaded disc, a noisy photographic half; nothing is committed):
   panels_u8 / panels_f32   64 panels of 256x512x3, uint8 and float32 in [0, 1] (scale=255)
@@ -9,12 +9,13 @@ Workloads (procedural images: a white ground, a shaded disc, a noisy photographi
   sheet                    the `eval.py --render` sheet: (3, 2066, 1292) float32 CHW as visualize_tensorboard returns it, encoded through its
                            HWC view with scale=255, rounding="trunc", bgr=False
 Arms, each [median, min, max] ms of wall clock over `rounds` alternating rounds, synchronised at both ends:
-  device          PNGEncoder.encode: the three launches, the copy of the files to the host and the container, files as bytes
+  device          PNGEncoder.encode: the three launches, the copy of the files to the host and the container, files as bytes; one arm
+                  per mode of --compression (device_ms / device_file_bytes are the fixed mode's, device_dynamic_* the dynamic mode's)
   host_1thread    device-to-host copy of the raw pixels (+ the float conversion in numpy), then Pillow at compress_level=1 per image
                   (without Pillow: zlib.compress(level 1) of the rows behind a filter-0 byte, and the record says so)
   host_16threads  the same from a pool of 16 threads (one image cannot be split: at most one thread per image)
-Sizes: bytes of the device files and of the host files, and for one render-like 256x512x3 panel the file over zlib.compress(level 1)
-of the same filtered bytes."""
+Sizes: bytes of the device files and of the host files, and for one render-like 256x512x3 panel the file of each mode over
+zlib.compress(level 1) of the same filtered bytes."""
 import argparse
 import io
 import json
@@ -85,7 +86,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "png_encode.jsonl"))
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--compression", default="fixed,dynamic", help="the device arms, comma separated: fixed, dynamic")
     args = ap.parse_args()
+    modes = args.compression.split(",")
+    assert modes and set(modes) <= {"fixed", "dynamic"}, modes
+    key = {"fixed": "device", "dynamic": "device_dynamic"}
     dev = torch.device("cuda:0")
     enc = P.PNGEncoder(dev)
     build = _cabi.load().thmr_build_info().decode()
@@ -101,18 +106,18 @@ def main():
     pool = ThreadPoolExecutor(16)
     records = []
     for name, images, kw in workloads:
-        def device_arm():
-            return enc.encode(images, **kw)
+        def device_arm(mode):
+            return enc.encode(images, compression=mode, **kw)
 
         def host_arm(threads):
             arrs = [to_host_u8(t, kw) for t in images]
             return list(pool.map(host_encode_one, arrs)) if threads > 1 else [host_encode_one(a) for a in arrs]
 
-        files = device_arm()
-        hfiles = host_arm(1)                      # warm-up of both arms, and the sizes
-        t = {"device": [], "host_1thread": [], "host_16threads": []}
+        files = {m: device_arm(m) for m in modes}
+        hfiles = host_arm(1)                      # warm-up of all arms, and the sizes
+        t = {**{key[m]: [] for m in modes}, "host_1thread": [], "host_16threads": []}
         for _ in range(args.rounds):
-            for arm, fn in (("device", device_arm), ("host_1thread", lambda: host_arm(1)), ("host_16threads", lambda: host_arm(16))):
+            for arm, fn in [(key[m], lambda m=m: device_arm(m)) for m in modes] + [("host_1thread", lambda: host_arm(1)), ("host_16threads", lambda: host_arm(16))]:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 fn()
@@ -121,24 +126,29 @@ def main():
         raw = sum(int(np.prod(i.shape)) for i in images)
         rec = {"what": "png_" + name, "images": len(images), "shape": list(images[0].shape), "dtype": str(images[0].dtype), "rounds": args.rounds,
                "columns": "[median, min, max] ms per call over all images, wall clock", "raw_bytes": raw,
-               "device_file_bytes": sum(map(len, files)), "host_file_bytes": sum(map(len, hfiles)),
+               **{key[m] + "_file_bytes": sum(map(len, files[m])) for m in modes}, "host_file_bytes": sum(map(len, hfiles)),
                "host_encoder": "Pillow compress_level=1" if Image is not None else "zlib.compress(level 1) of filter-0 rows (no Pillow)",
                "host_threads_used": min(16, len(images)),
-               "device_ms": med(t["device"]), "host_1thread_ms": med(t["host_1thread"]), "host_16threads_ms": med(t["host_16threads"]), "build": build}
-        rec["device_over_host_16threads"] = round(rec["device_ms"][0] / rec["host_16threads_ms"][0], 4)
+               **{key[m] + "_ms": med(t[key[m]]) for m in modes}, "host_1thread_ms": med(t["host_1thread"]),
+               "host_16threads_ms": med(t["host_16threads"]), "build": build}
+        for m in modes:
+            rec[key[m] + "_over_host_16threads"] = round(rec[key[m] + "_ms"][0] / rec["host_16threads_ms"][0], 4)
+            rec[key[m] + "_files_over_host_files"] = round(rec[key[m] + "_file_bytes"] / rec["host_file_bytes"], 4)
         records.append(rec)
         print(json.dumps(rec), flush=True)
 
     import _png_reader as R
     one = panels[0]
-    data = enc.encode([torch.from_numpy(one).to(dev)], bgr=False)[0]
-    pixels, _, stream = R.read(data)
-    assert np.array_equal(pixels, one) and data == P.encode_host(one, bgr=False)
-    z = len(zlib.compress(stream, 1))
-    rec = {"what": "png_size", "image": "render-like 256x512x3 (panel 0)", "file_bytes": len(data), "zlib_level1_of_same_filtered_bytes": z,
-           "ratio": round(len(data) / z, 4), "segment_bytes": P.segment_bytes(), "device_equals_host": True, "build": build}
-    records.append(rec)
-    print(json.dumps(rec), flush=True)
+    for m in modes:
+        data = enc.encode([torch.from_numpy(one).to(dev)], bgr=False, compression=m)[0]
+        pixels, _, stream = R.read(data)
+        assert np.array_equal(pixels, one) and data == P.encode_host(one, bgr=False, compression=m)
+        z = len(zlib.compress(stream, 1))
+        rec = {"what": "png_size", "compression": m, "image": "render-like 256x512x3 (panel 0)", "file_bytes": len(data),
+               "zlib_level1_of_same_filtered_bytes": z, "ratio": round(len(data) / z, 4), "segment_bytes": P.segment_bytes(),
+               "device_equals_host": True, "build": build}
+        records.append(rec)
+        print(json.dumps(rec), flush=True)
     with open(args.out, "w") as f:
         for r in records:
             f.write(json.dumps(r) + "\n")

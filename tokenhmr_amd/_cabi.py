@@ -108,11 +108,12 @@ class PngItem(C.Structure):
     """thmr_png_item: one image of thmr_png_encode_batch / thmr_png_encode_host."""
     _fields_ = [("pixels", C.c_void_p), ("dtype", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32),
                 ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("stride_c", C.c_int64), ("scale", C.c_float), ("rounding", C.c_int32),
-                ("swap_rb", C.c_int32), ("reserved", C.c_int32), ("out", C.c_void_p), ("capacity", C.c_int64), ("written", C.c_int64)]
+                ("swap_rb", C.c_int32), ("compression", C.c_int32), ("out", C.c_void_p), ("capacity", C.c_int64), ("written", C.c_int64)]
 
 
 PNG_U8, PNG_F32, PNG_U16 = 0, 1, 2                  # header: THMR_PNG_*
 PNG_ROUND_NEAREST, PNG_ROUND_TRUNC = 0, 1           # header: THMR_PNG_ROUND_*
+PNG_FIXED, PNG_DYNAMIC = 0, 1                       # header: THMR_PNG_FIXED / _DYNAMIC
 
 
 class JpegItem(C.Structure):

@@ -1,7 +1,8 @@
 // PNG encoding of device images (include/tokenhmr_hip.h).  Three launches over a whole batch: convert + filter of every row
 // (one wave per row), deflate of every segment of the filtered streams (one wave per segment, the segment in LDS), and the gather of
 // the segments into one packed stream that crosses to the host.  The arithmetic and every selection rule live in png_math.h, which the
-// CPU encode (png_host.h) shares: both write the same bytes.
+// CPU encode (png_host.h) shares: both write the same bytes.  A batch with a dynamic-Huffman item (compression THMR_PNG_DYNAMIC) runs
+// the DYNAMIC instantiation of png_deflate_kernel; a batch without one runs the other, the code it always ran.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,13 +26,13 @@ struct PngItemDev {
     int32_t total;              // bytes of the filtered stream
     int32_t row0, seg0, nseg;   // its rows / segments are [row0, row0 + h) / [seg0, seg0 + nseg) of the batch
     int32_t ncand, cand[pngm::MAX_CAND];
-    int32_t pad;
+    int32_t dynamic;            // compression THMR_PNG_DYNAMIC
 };
 static_assert(sizeof(PngItemDev) % 8 == 0, "descriptors are read as an array");
 static_assert(sizeof(thmr_png_item) == 88, "tokenhmr_amd/_cabi.py mirrors this layout");
 
 constexpr int SLOT = pngm::SEGMENT + pngm::SEGMENT / 8 + 64;     // bytes a segment's coded form can take: 3 + 9 bits a byte + the trailer
-constexpr int RING = 128;                                         // words of the LDS bit buffer: one step adds at most 64 * 31 bits
+constexpr int RING = 128;                                         // words of the LDS bit buffer: one step adds at most 64 * 31 bits (64 * 48 in a dynamic block)
 constexpr int64_t FINISH_CHUNK = 256 << 10;                       // bytes of a stream copied out and CRC-summed as one piece of work
 constexpr int FINISH_THREADS = 16;                                // at most: what one command gets of a GPU box
 static_assert(SLOT % 4 == 0 && pngm::SEGMENT % 16 == 0, "slots are written in words, segments loaded in 16-byte pieces");
@@ -97,22 +98,74 @@ __device__ void ring_flush(uint32_t* ring, uint32_t* slot, int from, int to, int
     }
 }
 
+// The greedy chain through a window of cnt positions from its first one: the mask of the positions it visits, and in pos how far it
+// gets (at or past cnt).  adv: each lane's step, its match length or 1; any_match: whether some lane has a match at all.
+__device__ uint64_t chain_through(int adv, bool any_match, int cnt, int& pos) {
+    if (!any_match) {
+        pos = cnt;
+        return cnt == 64 ? ~0ull : ((1ull << cnt) - 1);
+    }
+    uint64_t sel = 0;
+    for (pos = 0; pos < cnt;) {
+        sel |= 1ull << pos;
+        pos += __builtin_amdgcn_readlane(adv, pos);
+    }
+    return sel;
+}
+
+// One step of the bit stream: lane l appends k bits of t (k = 0: nothing) behind those of the lanes before it; the ring's complete
+// words then leave for the slot.  WIDE: k can exceed 32.
+template <bool WIDE>
+__device__ void ring_step(uint32_t* ring, uint32_t* slot, int64_t& bits, int& flushed, uint64_t t, int k, int lane) {
+    int incl = k;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
+    }
+    // ring_put shifts its bits by up to 31 inside 64: it takes at most 33 bits at a time (a fixed-code token has 31).  A token of a
+    // dynamic block has up to 15 + 5 + 15 + 13 = 48, so it goes in as its low 32 bits and the rest.
+    static_assert(2 * pngm::MAX_BITS + 5 + 13 <= 64, "a token fits the 64-bit token word, and two puts of at most 32 bits");
+    const int64_t at = bits + incl - k;
+    ring_put(ring, at, t & 0xFFFFFFFFull, k < 32 ? k : 32);
+    if (WIDE && k > 32) ring_put(ring, at + 32, t >> 32, k - 32);
+    bits += __builtin_amdgcn_readlane(incl, 63);
+    __syncthreads();
+    const int complete = (int)(bits >> 5);
+    ring_flush(ring, slot, flushed, complete, lane);
+    flushed = complete;
+    __syncthreads();
+}
+
 // Deflate: one wave per segment.  Per step the 64 lanes find the match at 64 consecutive positions (a function of the bytes alone), the
 // greedy chain through them is walked from the step's first position, the chosen tokens' bit lengths are prefix-summed and the tokens
 // ORed into an LDS ring, whose complete words go to the segment's slot.  The next step starts where the chain left the window.
+// DYNAMIC is the instantiation for a batch with a dynamic item (compression THMR_PNG_DYNAMIC); a fixed item's segment comes out of it
+// as out of the other.  A dynamic item's segment walks its chain twice.  The first walk counts the tokens' symbols into an LDS
+// histogram and sums their fixed-code bits; lane 0 then builds the block's codes and header (pngm::dynamic_block, a few thousand serial
+// steps while the other segments' waves run), and the block rule picks dynamic, fixed or stored before a bit is written.  The second
+// walk emits with the codes looked up in LDS; the header goes first, 64 pieces a step through the same ring (a step adds at most
+// 64 * 48 bits, the ring holds 4096 and never more than one word is left unflushed).
+template <bool DYNAMIC>
 __global__ __launch_bounds__(64) void png_deflate_kernel(const PngItemDev* __restrict__ items, int n_items, const uint8_t* __restrict__ filt,
                                                          uint8_t* __restrict__ slots, uint32_t* __restrict__ meta) {
     __shared__ __align__(16) uint8_t seg[pngm::SEGMENT + 16];
     __shared__ uint32_t ring[RING];
+    __shared__ pngm::DynBlock code;
+    __shared__ int64_t dynamic_bits;
+    static_assert(sizeof(pngm::DynBlock) % 4 == 0, "cleared in words");
     const int lane = threadIdx.x, g = blockIdx.x;
     const PngItemDev& it = items[item_of<&PngItemDev::seg0>(items, n_items, g)];
     const int s = g - it.seg0;
     const int64_t off = (int64_t)s * pngm::SEGMENT;
     const int n = (int64_t)it.total - off < pngm::SEGMENT ? (int)(it.total - off) : pngm::SEGMENT;
     const bool last = s == it.nseg - 1;
+    const bool want = DYNAMIC && it.dynamic != 0;
     const uint8_t* src = filt + it.filt_off + off;
     for (int i = lane * 16; i < n; i += 64 * 16) *reinterpret_cast<uint4*>(seg + i) = *reinterpret_cast<const uint4*>(src + i);
     for (int i = lane; i < RING; i += 64) ring[i] = 0;
+    if constexpr (DYNAMIC)
+        for (int i = lane; i < (int)(sizeof(pngm::DynBlock) / 4); i += 64) reinterpret_cast<int32_t*>(&code)[i] = 0;
     __syncthreads();
     if (lane < pngm::PAD) seg[n + lane] = 0;
     __syncthreads();
@@ -126,52 +179,73 @@ __global__ __launch_bounds__(64) void png_deflate_kernel(const PngItemDev* __res
 #pragma unroll
     for (int k = 0; k < pngm::MAX_CAND; ++k) cand[k] = it.cand[k];
 
-    uint32_t* slot = reinterpret_cast<uint32_t*>(slots + (int64_t)g * SLOT);
-    int64_t bits = 3;
-    int flushed = 0;
-    if (lane == 0) ring_put(ring, 0, (last ? 1u : 0u) | 2u, 3);
-    const int64_t give_up = ((int64_t)n + 6) * 8;        // beyond this the stored block has won whatever follows
-    for (int cur = 0; cur < n && bits <= give_up;) {
-        const int p = cur + lane;
-        int len = 0, dist = 0, k = 0;
-        uint64_t t = 0;
-        if (p < n) {
-            pngm::find_match(seg, p, n, cand, ncand, len, dist);
-            pngm::token_bits(seg[p], len, dist, t, k);
-        }
-        const int adv = len ? len : 1;
-        const int cnt = min(64, n - cur);
-        uint64_t sel = 0;
-        int pos = 0;
-        if (__ballot(len > 0) == 0) {
-            sel = cnt == 64 ? ~0ull : ((1ull << cnt) - 1);
-            pos = cnt;
-        } else {
-            while (pos < cnt) {
-                sel |= 1ull << pos;
-                pos += __builtin_amdgcn_readlane(adv, pos);
+    bool dyn = false, stored = false;
+    int eob_bits = 7;
+    uint32_t eob_code = 0;
+    if (want) {                                          // (never in the fixed instantiation)
+        uint64_t fixed = 0;
+        for (int cur = 0; cur < n;) {
+            const int p = cur + lane;
+            int len = 0, dist = 0, pos;
+            if (p < n) pngm::find_match(seg, p, n, cand, ncand, len, dist);
+            const uint64_t sel = chain_through(len ? len : 1, __ballot(len > 0) != 0, min(64, n - cur), pos);
+            if ((sel >> lane) & 1) {
+                int lsym, e, extra, dsym, de, dextra;
+                pngm::token_parts(seg[p], len, dist, lsym, e, extra, dsym, de, dextra);
+                atomicAdd(&code.ll[lsym], 1);
+                if (dsym >= 0) atomicAdd(&code.d[dsym], 1);
+                fixed += (uint64_t)pngm::fixed_token_bits(lsym, e, dsym, de);
             }
+            cur += pos;
         }
-        if (!((sel >> lane) & 1)) k = 0;
-        int incl = k;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
+        const int64_t fixed_bits = 3 + (int64_t)wave_sum(fixed);         // before the end-of-block
+        __syncthreads();
+        if (lane == 0) dynamic_bits = pngm::dynamic_block(code);
+        __syncthreads();
+        dyn = dynamic_bits < fixed_bits + 7;
+        if (dyn) {
+            eob_bits = (int)((uint32_t)code.ll[pngm::END_OF_BLOCK] >> 16);
+            eob_code = (uint32_t)code.ll[pngm::END_OF_BLOCK] & 0xFFFFu;
         }
-        const int total = __builtin_amdgcn_readlane(incl, 63);
-        ring_put(ring, bits + incl - k, t, k);
-        bits += total;
-        cur += pos;
-        __syncthreads();
-        const int complete = (int)(bits >> 5);
-        ring_flush(ring, slot, flushed, complete, lane);
-        flushed = complete;
-        __syncthreads();
+        stored = pngm::coded_bytes(dyn ? dynamic_bits - eob_bits : fixed_bits, last, eob_bits) > (int64_t)n + 5;
+    }
+
+    uint32_t* slot = reinterpret_cast<uint32_t*>(slots + (int64_t)g * SLOT);
+    int64_t bits = 0;
+    int flushed = 0;
+    if (!stored) {
+        if (DYNAMIC && dyn) {
+            const int pieces = pngm::header_pieces(code);
+            for (int i0 = 0; i0 < pieces; i0 += 64) {
+                uint64_t t = 0;
+                int k = 0;
+                if (i0 + lane < pieces) pngm::header_piece(code, i0 + lane, last, t, k);
+                ring_step<DYNAMIC>(ring, slot, bits, flushed, t, k, lane);
+            }
+        } else {
+            if (lane == 0) ring_put(ring, 0, (last ? 1u : 0u) | 2u, 3);
+            bits = 3;
+        }
+        const int64_t give_up = ((int64_t)n + 6) * 8;    // a fixed item learns here that the stored block has won; the others know
+        for (int cur = 0; cur < n && bits <= give_up;) {
+            const int p = cur + lane;
+            int len = 0, dist = 0, k = 0, pos;
+            uint64_t t = 0;
+            if (p < n) {
+                pngm::find_match(seg, p, n, cand, ncand, len, dist);
+                if (DYNAMIC && dyn) pngm::dynamic_token_bits(code, seg[p], len, dist, t, k);
+                else pngm::token_bits(seg[p], len, dist, t, k);
+            }
+            const uint64_t sel = chain_through(len ? len : 1, __ballot(len > 0) != 0, min(64, n - cur), pos);
+            if (!((sel >> lane) & 1)) k = 0;
+            ring_step<DYNAMIC>(ring, slot, bits, flushed, t, k, lane);
+            cur += pos;
+        }
+        stored = bits > give_up || pngm::coded_bytes(bits, last, eob_bits) > (int64_t)n + 5;
     }
 
     int bytes;
-    if (bits > give_up || pngm::coded_bytes(bits, last) > (int64_t)n + 5) {
+    if (stored) {
         uint8_t* sb = reinterpret_cast<uint8_t*>(slot);
         if (lane == 0) {
             sb[0] = last ? 1 : 0;
@@ -180,7 +254,8 @@ __global__ __launch_bounds__(64) void png_deflate_kernel(const PngItemDev* __res
         for (int i = lane; i < n; i += 64) sb[5 + i] = seg[i];
         bytes = n + 5;
     } else {
-        bits += 7;                                       // end of block: seven zero bits
+        if (lane == 0) ring_put(ring, bits, eob_code, eob_bits);
+        bits += eob_bits;
         if (!last) {
             bits = (bits + 3 + 7) & ~(int64_t)7;         // an empty stored block: three zero bits, up to the byte, 00 00 FF FF
             if (lane == 0) ring_put(ring, bits, 0xFFFF0000u, 32);
@@ -243,6 +318,12 @@ int thmr_png_encode_host(thmr_png_item* item) {
     return 0;
 }
 
+int thmr_png_code_lengths(const int32_t* freq, int32_t n, int32_t max_bits, int32_t* lens) {
+    std::string err;
+    if (const int rc = pngh::code_lengths(freq, n, max_bits, lens, err)) return g_png_err.fail(nullptr, rc, err);
+    return 0;
+}
+
 const char* thmr_png_last_error(const thmr_png* p) { return g_png_err.read(p); }
 
 int thmr_png_create(int32_t device, thmr_png** out) {
@@ -268,6 +349,7 @@ int thmr_png_encode_batch(thmr_png* p, thmr_png_item* items, int32_t n, void* st
     if (!items) return g_png_err.invalid(p, "null item table");
     std::vector<PngItemDev> ids((size_t)n);
     int64_t rows = 0, segs = 0, filt_bytes = 0, packed_bytes = 0;
+    bool any_dynamic = false;
     for (int i = 0; i < n; ++i) {
         thmr_png_item& it = items[i];
         it.written = 0;
@@ -281,6 +363,8 @@ int thmr_png_encode_batch(thmr_png* p, thmr_png_item* items, int32_t n, void* st
         d.filt_off = filt_bytes;
         d.row0 = (int32_t)rows; d.seg0 = (int32_t)segs; d.nseg = (int32_t)pngh::segments(d.total);
         d.ncand = pngm::candidates(it.channels, 1 + it.width * it.channels, d.cand);
+        d.dynamic = it.compression == THMR_PNG_DYNAMIC;
+        any_dynamic = any_dynamic || d.dynamic;
         rows += it.height; segs += d.nseg;
         filt_bytes += ((int64_t)d.total + 15 + 16) & ~(int64_t)15;        // a segment is loaded in whole 16-byte pieces
         packed_bytes += (int64_t)d.total + 5 * (int64_t)d.nseg;
@@ -309,7 +393,9 @@ int thmr_png_encode_batch(thmr_png* p, thmr_png_item* items, int32_t n, void* st
     const PngItemDev* idev = reinterpret_cast<const PngItemDev*>(p->desc.ptr());
     uint32_t* mdev = reinterpret_cast<uint32_t*>(p->desc.ptr() + desc_bytes);
     hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, idev, n, p->filt, (int)rows);
-    hipLaunchKernelGGL(png_deflate_kernel, dim3((unsigned)segs), dim3(64), 0, st, idev, n, p->filt, p->slots, mdev);
+    // a batch of fixed items runs the fixed instantiation; one dynamic item sends the whole batch through the one that knows both
+    if (any_dynamic) hipLaunchKernelGGL(png_deflate_kernel<true>, dim3((unsigned)segs), dim3(64), 0, st, idev, n, p->filt, p->slots, mdev);
+    else hipLaunchKernelGGL(png_deflate_kernel<false>, dim3((unsigned)segs), dim3(64), 0, st, idev, n, p->filt, p->slots, mdev);
     hipLaunchKernelGGL(png_gather_kernel, dim3((unsigned)segs), dim3(256), 0, st, mdev, p->slots, p->packed);
     if ((e = hipGetLastError()) != hipSuccess) return g_png_err.hip(p, "png kernel launch", e);
     const uint32_t* mh = reinterpret_cast<const uint32_t*>(p->host.ptr() + desc_bytes);

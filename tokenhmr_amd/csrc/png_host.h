@@ -38,7 +38,10 @@ inline int check_item(const thmr_png_item& it, std::string& err) {
     }
     if (stream_bytes(it.width, it.height, it.channels) >= ((int64_t)1 << 31)) { err = "the filtered stream would reach 2^31 bytes"; return THMR_ERR_INVALID; }
     if (it.rounding != THMR_PNG_ROUND_NEAREST && it.rounding != THMR_PNG_ROUND_TRUNC) { err = "rounding must be THMR_PNG_ROUND_NEAREST or _TRUNC"; return THMR_ERR_INVALID; }
-    if (it.reserved != 0) { err = "reserved must be 0"; return THMR_ERR_INVALID; }
+    if (it.compression != THMR_PNG_FIXED && it.compression != THMR_PNG_DYNAMIC) {
+        err = "compression must be THMR_PNG_FIXED or THMR_PNG_DYNAMIC, got " + std::to_string(it.compression);
+        return THMR_ERR_INVALID;
+    }
     if (!it.pixels) { err = "null pixels"; return THMR_ERR_INVALID; }
     if (!it.out) { err = "null out"; return THMR_ERR_INVALID; }
     const int64_t need = bound(it.width, it.height, it.channels);
@@ -46,6 +49,21 @@ inline int check_item(const thmr_png_item& it, std::string& err) {
         err = "capacity " + std::to_string(it.capacity) + " is below thmr_png_bound = " + std::to_string(need);
         return THMR_ERR_INVALID;
     }
+    return 0;
+}
+
+// thmr_png_code_lengths: the arguments checked, then pngm::code_lengths.
+inline int code_lengths(const int32_t* freq, int32_t n, int32_t max_bits, int32_t* lens, std::string& err) {
+    if (!freq || !lens) { err = "null freq or lens"; return THMR_ERR_INVALID; }
+    if (n < 1 || n > pngm::N_LL || max_bits < 1 || max_bits > pngm::MAX_BITS) { err = "n must be 1 ... 286 and max_bits 1 ... 15"; return THMR_ERR_INVALID; }
+    int used = 0;
+    for (int s = 0; s < n; ++s) {
+        if (freq[s] < 0 || freq[s] >= (1 << 22)) { err = "a frequency must be 0 ... 2^22 - 1, got " + std::to_string(freq[s]); return THMR_ERR_INVALID; }
+        used += freq[s] > 0;
+    }
+    if (used > (1 << max_bits)) { err = std::to_string(used) + " symbols in use cannot have codes of at most " + std::to_string(max_bits) + " bits"; return THMR_ERR_INVALID; }
+    int32_t a[pngm::N_LL], b[pngm::N_LL];
+    pngm::code_lengths(freq, n, max_bits, lens, a, b);
     return 0;
 }
 
@@ -145,11 +163,73 @@ struct BitWriter {
     void align() { if (n) { v.push_back((uint8_t)acc); acc = 0; n = 0; } }
 };
 
+inline void stored_block(const uint8_t* seg, int n, bool last, std::vector<uint8_t>& out) {
+    out.push_back(last ? 1 : 0);
+    out.push_back((uint8_t)n); out.push_back((uint8_t)(n >> 8));
+    out.push_back((uint8_t)~n); out.push_back((uint8_t)(~n >> 8));
+    out.insert(out.end(), seg, seg + n);
+}
+
+// How a coded segment ends behind its end-of-block code.
+inline void end_segment(BitWriter& bw, bool last, std::vector<uint8_t>& out) {
+    if (!last) {
+        bw.put(0, 3);
+        bw.align();
+        const uint8_t sync[4] = {0, 0, 0xFF, 0xFF};
+        out.insert(out.end(), sync, sync + 4);
+    } else {
+        bw.align();
+    }
+}
+
+// The segment as a dynamic-Huffman block (the block rule of png_math.h), or as the stored block where that is smaller still; false,
+// and nothing written, where the dynamic block does not take strictly fewer bits than the fixed one.
+inline bool deflate_segment_dynamic(const uint8_t* seg, int n, bool last, const int* cand, int ncand, std::vector<uint8_t>& out) {
+    struct Token { int lit, len, dist; };
+    std::vector<Token> tokens;
+    pngm::DynBlock k;
+    memset(&k, 0, sizeof(k));
+    int64_t fixed = 3 + 7;
+    for (int p = 0; p < n;) {
+        int len, dist, lsym, e, extra, dsym, de, dextra;
+        pngm::find_match(seg, p, n, cand, ncand, len, dist);
+        pngm::token_parts(seg[p], len, dist, lsym, e, extra, dsym, de, dextra);
+        ++k.ll[lsym];
+        if (dsym >= 0) ++k.d[dsym];
+        fixed += pngm::fixed_token_bits(lsym, e, dsym, de);
+        tokens.push_back({seg[p], len, dist});
+        p += len ? len : 1;
+    }
+    const int64_t bits = pngm::dynamic_block(k);
+    if (bits >= fixed) return false;
+    const int eob = (int)((uint32_t)k.ll[pngm::END_OF_BLOCK] >> 16);
+    if (pngm::coded_bytes(bits - eob, last, eob) > (int64_t)n + 5) {
+        stored_block(seg, n, last, out);
+        return true;
+    }
+    BitWriter bw{out};
+    uint64_t t;
+    int m;
+    for (int i = 0; i < pngm::header_pieces(k); ++i) {
+        pngm::header_piece(k, i, last, t, m);
+        bw.put(t, m);
+    }
+    for (const Token& tk : tokens) {
+        pngm::dynamic_token_bits(k, tk.lit, tk.len, tk.dist, t, m);
+        bw.put(t, m);
+    }
+    bw.put((uint32_t)k.ll[pngm::END_OF_BLOCK] & 0xFFFFu, eob);
+    end_segment(bw, last, out);
+    return true;
+}
+
 // One segment (n bytes at seg, PAD readable bytes behind) -> its deflate bytes appended to out; the Adler partials in s1, s2.
-inline void deflate_segment(const uint8_t* seg, int n, bool last, const int* cand, int ncand, std::vector<uint8_t>& out, uint32_t& s1, uint32_t& s2) {
+inline void deflate_segment(const uint8_t* seg, int n, bool last, const int* cand, int ncand, int compression, std::vector<uint8_t>& out, uint32_t& s1,
+                            uint32_t& s2) {
     uint64_t a = 0, b = 0;
     for (int i = 0; i < n; ++i) { a += seg[i]; b += (uint64_t)(n - i) * seg[i]; }
     s1 = (uint32_t)(a % pngm::ADLER_MOD); s2 = (uint32_t)(b % pngm::ADLER_MOD);
+    if (compression == THMR_PNG_DYNAMIC && deflate_segment_dynamic(seg, n, last, cand, ncand, out)) return;
     const size_t start = out.size();
     BitWriter bw{out};
     bw.put((last ? 1u : 0u) | 2u, 3);                   // BFINAL, BTYPE 01
@@ -164,21 +244,11 @@ inline void deflate_segment(const uint8_t* seg, int n, bool last, const int* can
     }
     if (pngm::coded_bytes(bits, last) > (int64_t)n + 5) {       // a stored block is smaller
         out.resize(start);
-        out.push_back(last ? 1 : 0);
-        out.push_back((uint8_t)n); out.push_back((uint8_t)(n >> 8));
-        out.push_back((uint8_t)~n); out.push_back((uint8_t)(~n >> 8));
-        out.insert(out.end(), seg, seg + n);
+        stored_block(seg, n, last, out);
         return;
     }
     bw.put(0, 7);
-    if (!last) {
-        bw.put(0, 3);
-        bw.align();
-        const uint8_t sync[4] = {0, 0, 0xFF, 0xFF};
-        out.insert(out.end(), sync, sync + 4);
-    } else {
-        bw.align();
-    }
+    end_segment(bw, last, out);
 }
 
 // The filtered stream of an image whose pixels are host memory.
@@ -218,7 +288,7 @@ inline void encode(thmr_png_item& it) {
         memcpy(seg.data(), stream.data() + off, (size_t)n);
         memset(seg.data() + n, 0, pngm::PAD);
         uint32_t s1, s2;
-        deflate_segment(seg.data(), n, s == nseg - 1, cand, ncand, body, s1, s2);
+        deflate_segment(seg.data(), n, s == nseg - 1, cand, ncand, it.compression, body, s1, s2);
         pngm::adler_append(a, b, s1, s2, (uint32_t)n);
     }
     memcpy(it.out + IDAT_DATA_AT + 2, body.data(), body.size());

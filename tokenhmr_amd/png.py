@@ -9,6 +9,10 @@ An image is uint8 or float32 with any strides (a CHW tensor permuted to HWC, a p
 values are multiplied by `scale` and converted by `rounding`: "nearest" is cv2.imwrite's saturate_cast (nearest even, saturated),
 "trunc" is np.clip(x, 0, 255).astype(np.uint8).  The file is 8-bit grey / RGB / RGBA, filtered per row by libpng's default heuristic
 and deflated in independent segments; the device and the host path write the same bytes.
+
+compression="fixed" (the default) codes every segment as one fixed-Huffman block; compression="dynamic" gives a segment its own Huffman
+code where that is smaller (the pixels, the filters and the segments are the same, the file is about a quarter smaller on render-like
+images and costs a second pass over the tokens).  Every entry takes the keyword; PNGEncoder.encode also takes one mode per image.
 """
 import ctypes as C
 import os
@@ -30,6 +34,7 @@ class PngUnsupported(PngError):
 
 _BY_CODE = {_cabi.ERR_UNSUPPORTED: PngUnsupported}
 _ROUNDING = {"nearest": _cabi.PNG_ROUND_NEAREST, "trunc": _cabi.PNG_ROUND_TRUNC}
+_COMPRESSION = {"fixed": _cabi.PNG_FIXED, "dynamic": _cabi.PNG_DYNAMIC}
 _DTYPES = {torch.uint8: _cabi.PNG_U8, torch.float32: _cabi.PNG_F32, np.dtype(np.uint8): _cabi.PNG_U8, np.dtype(np.float32): _cabi.PNG_F32,
            np.dtype(np.uint16): _cabi.PNG_U16}
 if hasattr(torch, "uint16"):
@@ -46,10 +51,12 @@ def bound(width, height, channels, lib=None):
     return int((lib or _cabi.load()).thmr_png_bound(int(width), int(height), int(channels)))
 
 
-def _fill(item, img, scale, rounding, bgr):
+def _fill(item, img, scale, rounding, bgr, compression="fixed"):
     """One image -> the fields of a thmr_png_item but the pointers; returns (height, width, channels) as the facade sees them."""
     if rounding not in _ROUNDING:
         raise ValueError(f"rounding must be 'nearest' or 'trunc', got {rounding!r}")
+    if not isinstance(compression, str) or compression not in _COMPRESSION:
+        raise ValueError(f"compression must be 'fixed' or 'dynamic', got {compression!r}")
     if img.ndim == 2:
         h, w = img.shape
         c, sc = 1, 0
@@ -64,7 +71,8 @@ def _fill(item, img, scale, rounding, bgr):
     item.dtype = _DTYPES[img.dtype]
     item.width, item.height, item.channels = int(w), int(h), int(c)
     item.stride_y, item.stride_x, item.stride_c = int(sy), int(sx), int(sc)
-    item.scale, item.rounding, item.swap_rb, item.reserved = float(scale), _ROUNDING[rounding], int(bool(bgr)), 0
+    item.scale, item.rounding, item.swap_rb = float(scale), _ROUNDING[rounding], int(bool(bgr))
+    item.compression = _COMPRESSION[compression]
     return int(h), int(w), int(c)
 
 
@@ -75,13 +83,13 @@ def _out(item, h, w, c, lib, capacity=None):
     return buf
 
 
-def encode_host(img, *, scale=1.0, rounding="nearest", bgr=True, capacity=None, lib=None):
+def encode_host(img, *, scale=1.0, rounding="nearest", bgr=True, compression="fixed", capacity=None, lib=None):
     """One numpy image -> the file's bytes, on the CPU with the kernels' arithmetic: the oracle of PNGEncoder, and what a caller without
     a device gets.  capacity: the output buffer's size (default thmr_png_bound), for the refusal test."""
     lib = lib or _cabi.load()
     img = np.asarray(img)
     item = _cabi.PngItem()
-    h, w, c = _fill(item, img, scale, rounding, bgr)
+    h, w, c = _fill(item, img, scale, rounding, bgr, compression=compression)
     item.pixels = img.ctypes.data
     buf = _out(item, h, w, c, lib, capacity)
     rc = lib.thmr_png_encode_host(C.byref(item))
@@ -98,10 +106,19 @@ class PNGEncoder(_cabi.Handle):
         super().__init__(device, "thmr_png", "PNGEncoder needs a GPU device; encode_host() is the CPU encode")
         self._open(self._index())
 
-    def encode(self, images, *, scale=1.0, rounding="nearest", bgr=True):
+    def encode(self, images, *, scale=1.0, rounding="nearest", bgr=True, compression="fixed"):
         """A list of images — device tensors, or host tensors / numpy arrays (uploaded) — of any sizes, dtypes and strides -> the files,
-        list[bytes], in ONE batch call on the current stream.  bgr: the images hold B, G, R(, A) like cv2's; False: R, G, B(, A)."""
+        list[bytes], in ONE batch call on the current stream.  bgr: the images hold B, G, R(, A) like cv2's; False: R, G, B(, A).
+        compression: "fixed" or "dynamic" for all images, or a list with one of them per image."""
         n = len(images)
+        if isinstance(compression, str):
+            modes = [compression] * n
+        elif isinstance(compression, (list, tuple)):
+            modes = list(compression)
+        else:
+            raise ValueError(f"compression must be 'fixed', 'dynamic' or a list of them, one per image, got {compression!r}")
+        if len(modes) != n:
+            raise ValueError(f"{len(modes)} compression modes for {n} images")
         if n == 0:
             return []
         items = (_cabi.PngItem * n)()
@@ -116,7 +133,7 @@ class PNGEncoder(_cabi.Handle):
                 img = torch.from_numpy(np.ascontiguousarray(img))
             if img.device != self.device:
                 img = img.to(self.device)
-            h, w, c = _fill(items[i], img, scale, rounding, bgr)
+            h, w, c = _fill(items[i], img, scale, rounding, bgr, compression=modes[i])
             items[i].pixels = img.data_ptr()
             keep.append(img)
             bufs.append(_out(items[i], h, w, c, self.lib))
@@ -157,17 +174,17 @@ def _write(path, data):
         f.write(data)
 
 
-def imwrite(path, img, params=None, *, scale=1.0, rounding="nearest", bgr=True, device=None):
+def imwrite(path, img, params=None, *, scale=1.0, rounding="nearest", bgr=True, compression="fixed", device=None):
     """cv2.imwrite for .png: a device tensor or a numpy array, (H, W) or (H, W, C), channels in cv2's B, G, R(, A) order.  params is
-    accepted and ignored (cv2's compression level has no counterpart).  A numpy array goes to `device` (default: the current GPU).
-    Returns True; raises ValueError naming the extension for anything but .png."""
+    accepted and ignored (cv2's compression level has no counterpart; `compression` chooses between the two block kinds).  A numpy
+    array goes to `device` (default: the current GPU).  Returns True; raises ValueError naming the extension for anything but .png."""
     _check_path(path)
-    data = _encoder(_device_of([img], device)).encode([img], scale=scale, rounding=rounding, bgr=bgr)[0]
+    data = _encoder(_device_of([img], device)).encode([img], scale=scale, rounding=rounding, bgr=bgr, compression=compression)[0]
     _write(path, data)
     return True
 
 
-def imwrite_batch(paths, images, *, scale=1.0, rounding="nearest", bgr=True, device=None, threads=None):
+def imwrite_batch(paths, images, *, scale=1.0, rounding="nearest", bgr=True, compression="fixed", device=None, threads=None):
     """imwrite for many files: ONE device call for all images, then the files are written from a thread pool (at most WRITE_THREADS)."""
     paths = list(paths)
     if len(paths) != len(images):
@@ -176,7 +193,7 @@ def imwrite_batch(paths, images, *, scale=1.0, rounding="nearest", bgr=True, dev
         _check_path(p)
     if not paths:
         return True
-    files = _encoder(_device_of(images, device)).encode(list(images), scale=scale, rounding=rounding, bgr=bgr)
+    files = _encoder(_device_of(images, device)).encode(list(images), scale=scale, rounding=rounding, bgr=bgr, compression=compression)
     workers = max(1, min(WRITE_THREADS if threads is None else int(threads), len(paths)))
     with ThreadPoolExecutor(workers) as pool:
         list(pool.map(_write, paths, files))
