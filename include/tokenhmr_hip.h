@@ -904,6 +904,50 @@ void thmr_png_destroy(thmr_png* p);
 const char* thmr_png_last_error(const thmr_png* p);
 int  thmr_png_encode_batch(thmr_png* p, thmr_png_item* items_host, int32_t n, void* stream);
 
+/* Baseline JPEG encoding of device images: the counterpart of cv2.imwrite(".jpg") (csrc/jpegenc.hip, jpegenc_host.h,
+ * jpegenc_math.h): new symbols under ABI 5.  The file is the one libjpeg (libjpeg-turbo, Pillow's save(format="JPEG", quality=q,
+ * subsampling=s)) writes for the same pixels, byte for byte, header included; it is a function of the pixels and the arguments only, and
+ * thmr_jpeg_encode_host — the same algorithm on the CPU, sharing its arithmetic with the kernels — writes the same bytes.  An image is
+ * described by a thmr_png_item with compression == 0; quality and subsampling are passed beside it.
+ *   samples       uint8 or float32, 1 / 3 / 4 channels, any element strides, converted to uint8 by the PNG encoder's rule (scale,
+ *                 rounding, NaN / inf) and swapped by swap_rb as there; the alpha of a 4-channel image is dropped (as cv2 does).
+ *   colour        jccolor.c, 16-bit fixed point: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B +
+ *                 8388608 + 32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16.  One channel: Y is the sample.
+ *   sampling      THMR_JPEG_444 (MCU 8x8) or THMR_JPEG_420 (MCU 16x16, blocks Y00 Y01 Y10 Y11 Cb Cr).  A component of w_c x h_c samples has
+ *                 ceil(w_c / 8) x ceil(h_c / 8) real blocks; luma is W x H, 4:2:0 chroma ceil(W / 2) x ceil(H / 2).  Samples of a real
+ *                 block beyond the image repeat luma column W - 1 and row H - 1.  4:2:0 chroma sample (r, c): r' = min(r, ceil(H / 2) - 1)
+ *                 (the DOWNSAMPLED row is repeated), pixel rows 2r' and min(2r' + 1, H - 1), columns min(2c, W - 1) and min(2c + 1, W - 1),
+ *                 value (sum of the four + bias) >> 2 with bias 1 for even c and 2 for odd c.  A luma block of a 4:2:0 MCU outside the
+ *                 luma grid is a dummy: it codes as DC difference 0 + end-of-block and leaves the predictor alone.
+ *   transform     jfdctint.c (JDCT_ISLOW) on sample - 128: CONST_BITS 13, PASS1_BITS 2, rows first, then columns.
+ *   quantisation  the Annex K tables scaled by s = 5000 / q (q < 50) or 200 - 2 q: clamp((base * s + 50) / 100, 1, 255); a coefficient c
+ *                 becomes sign(c) * ((|c| + 4 t) / (8 t)).
+ *   entropy       the Annex K Huffman tables, no optimisation pass, no restart markers: DC difference by category, AC as (run, size) with
+ *                 ZRL 0xF0 and EOB 0x00, a negative value sends the low bits of v - 1; bits MSB first, every 0xFF followed by 0x00, the
+ *                 last byte padded with ones (and stuffed if that makes it 0xFF).
+ *   container     SOI; APP0 JFIF 1.01, units 0, density 1 x 1; one DQT per table (0, then 1; 8-bit, zigzag); SOF0 with components 1 / 2 /
+ *                 3 at 0x22 or 0x11, 0x11, 0x11 and tables 0, 1, 1; one DHT per table in the order DC0, AC0, DC1, AC1; SOS with selectors
+ *                 0x00, 0x11, 0x11, Ss 0, Se 63, Ah/Al 0; the scan; EOI.  Grey has one component, table 0, DC0 and AC0 only.
+ *   refused       before any HIP call, the message names the item: THMR_ERR_UNSUPPORTED for a 16-bit dtype, 2 channels and
+ *                 THMR_JPEG_422; THMR_ERR_INVALID for a quality outside 1 ... 100, width or height < 1 or > 65535, any other dtype /
+ *                 channel count / rounding / subsampling, compression != 0, a null pointer, and a capacity below thmr_jpeg_encode_bound(). */
+enum { THMR_JPEG_444 = 0, THMR_JPEG_422 = 1 /* refused by name */, THMR_JPEG_420 = 2 };
+/* The largest file: every block of every MCU at its worst case — 22 bits of DC (an 11-bit code + 11 value bits) and 63 x (16 + 10) bits
+ * of AC = 1660 bits — rounded up to bytes, TWICE that (each byte may be 0xFF and draw a 0x00), the header (623 bytes, grey 328) and
+ * EOI.  0 for arguments the encoder refuses. */
+int64_t thmr_jpeg_encode_bound(int32_t width, int32_t height, int32_t channels, int32_t subsampling);
+int thmr_jpeg_encode_host(thmr_png_item* item, int32_t quality, int32_t subsampling);
+/* The handle owns grow-only device scratch (coefficients, bit counts, the unstuffed scans) and pinned staging that the device writes the
+ * finished scans into.  One call encodes n images of n sizes, layouts, qualities and samplings with ONE descriptor upload and a fixed
+ * number of launches (transform; count; two scans; pack; the 0xFF count, its scan and the scatter), synchronises `stream` ONCE, at the
+ * end, and returns with the complete files at every item's `out`.  Not inside a stream capture (THMR_ERR_STATE). */
+typedef struct thmr_jpeg_encoder thmr_jpeg_encoder;
+int  thmr_jpeg_encoder_create(int32_t device, thmr_jpeg_encoder** out);
+void thmr_jpeg_encoder_destroy(thmr_jpeg_encoder* e);
+const char* thmr_jpeg_encoder_last_error(const thmr_jpeg_encoder* e);
+int  thmr_jpeg_encode_batch(thmr_jpeg_encoder* e, thmr_png_item* items_host, const int32_t* qualities, const int32_t* subsamplings, int32_t n,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,212 @@
+// The arithmetic and the coding rules of the baseline JPEG encoder, shared by the kernels (jpegenc.hip) and the CPU encode
+// (jpegenc_host.h): libjpeg's default compression pipeline restated in integers — jccolor.c's 16-bit fixed-point RGB -> YCbCr, the h2v2
+// box downsampler with its alternating bias and libjpeg's edge expansion, jfdctint.c (JDCT_ISLOW, the constants of jpeg_math.h),
+// quantisation by 8 q with halves away from zero, and the Huffman coding of a block with the Annex K tables.  The samples come from
+// pngm::sample, the one pixel conversion of both encoders.  Everything is integer, so both sides give the same bytes.
+// Compiles with or without HIP.
+#pragma once
+#include <stdint.h>
+
+#include "jpeg_math.h"
+#include "png_math.h"
+
+namespace jpegem {
+
+constexpr int MAX_BLOCK_BITS = (11 + 11) + 63 * (16 + 10);      // the longest DC code (chroma category 11) + its bits, 63 x the longest AC code + 10 bits
+constexpr int TABLE_WORDS = 16 + 256;                           // one class's codes: DC categories 0 ... 11, then AC (run << 4 | size) at 16 +
+constexpr int EOB = 0x00, ZRL = 0xF0;
+
+// One image as the encoder sees it besides its pixels and tables.
+struct Frame {
+    pngm::Image im;
+    int32_t ncomp;              // 1 (grey) or 3
+    int32_t sub;                // 1: 4:2:0 (three components only), 0: 4:4:4
+    int32_t mcux, mcuy;         // MCUs per row / column
+    int32_t bpm;                // blocks per MCU: 1, 3 or 6
+    int32_t lbw, lbh;           // real luma blocks per row / column: ceil(W / 8), ceil(H / 8)
+};
+
+JPEG_HD Frame frame_of(const pngm::Image& im, int sub) {
+    Frame f;
+    f.im = im;
+    f.ncomp = im.c == 1 ? 1 : 3;
+    f.sub = f.ncomp == 3 && sub ? 1 : 0;
+    const int m = f.sub ? 16 : 8;
+    f.mcux = (im.w + m - 1) / m; f.mcuy = (im.h + m - 1) / m;
+    f.bpm = f.ncomp == 1 ? 1 : f.sub ? 6 : 3;
+    f.lbw = (im.w + 7) / 8; f.lbh = (im.h + 7) / 8;
+    return f;
+}
+
+JPEG_HD int zigzag_of_natural(int k) {
+    const uint8_t z[64] = {0,  1,  5,  6,  14, 15, 27, 28, 2,  4,  7,  13, 16, 26, 29, 42, 3,  8,  12, 17, 25, 30, 41, 43, 9,  11, 18, 24, 31, 40, 44, 53,
+                           10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63};
+    return z[k];
+}
+
+// Block k of MCU (mx, my): its component, its block coordinates in the component's grid, and whether it lies outside that grid (a
+// dummy: luma of 4:2:0 only).
+JPEG_HD void block_place(const Frame& f, int mx, int my, int k, int& comp, int& bx, int& by, bool& dummy) {
+    dummy = false;
+    if (f.sub && k < 4) {
+        comp = 0; bx = 2 * mx + (k & 1); by = 2 * my + (k >> 1);
+        dummy = bx >= f.lbw || by >= f.lbh;
+    } else {
+        comp = f.sub ? k - 3 : k; bx = mx; by = my;
+    }
+}
+
+// The block (index in scan order) whose DC value predicts block b's: the nearest real block of the same component before it, -1 for
+// the first.  Block 0 of an MCU is always real.
+JPEG_HD int64_t dc_predecessor(const Frame& f, int64_t b) {
+    const int64_t m = b / f.bpm;
+    const int k = (int)(b - m * f.bpm);
+    if (f.sub && k < 4) {
+        int comp, bx, by;
+        bool dummy;
+        const int64_t m0 = k > 0 ? m : m - 1;
+        if (m0 < 0) return -1;
+        const int my = (int)(m0 / f.mcux), mx = (int)(m0 - (int64_t)my * f.mcux);
+        for (int j = k > 0 ? k - 1 : 3; j > 0; --j) {
+            block_place(f, mx, my, j, comp, bx, by, dummy);
+            if (!dummy) return m0 * f.bpm + j;
+        }
+        return m0 * f.bpm;
+    }
+    return m > 0 ? b - f.bpm : -1;
+}
+
+JPEG_HD void rgb_to_ycc(int r, int g, int b, int& y, int& cb, int& cr) {
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+    cb = (-11059 * r - 21709 * g + 32768 * b + 8388608 + 32767) >> 16;
+    cr = (32768 * r - 27439 * g - 5329 * b + 8388608 + 32767) >> 16;
+}
+
+// Component `comp` of pixel (x, y), both inside the image.  The alpha of a 4-channel image is never read.
+JPEG_HD int pixel_component(const pngm::Image& im, const void* pixels, int comp, int y, int x) {
+    if (im.c == 1) return pngm::sample(im, pixels, y, x);
+    const int r = pngm::sample(im, pixels, y, x * im.c), g = pngm::sample(im, pixels, y, x * im.c + 1), b = pngm::sample(im, pixels, y, x * im.c + 2);
+    int yy, cb, cr;
+    rgb_to_ycc(r, g, b, yy, cb, cr);
+    return comp == 0 ? yy : comp == 1 ? cb : cr;
+}
+
+// Sample (row, col) of a component's padded plane, as libjpeg's edge expansion and h2v2 downsampler leave it.  A full-resolution
+// component replicates the last pixel column and row.  A 4:2:0 chroma plane replicates its last DOWNSAMPLED row (not the pixel
+// row), takes the pixel rows 2r and min(2r + 1, H - 1), the columns min(2c, W - 1) and min(2c + 1, W - 1), and rounds with the bias 1 for
+// an even column and 2 for an odd one.
+JPEG_HD int component_sample(const Frame& f, const void* pixels, int comp, int row, int col) {
+    const pngm::Image& im = f.im;
+    if (!(f.sub && comp > 0)) return pixel_component(im, pixels, comp, row < im.h ? row : im.h - 1, col < im.w ? col : im.w - 1);
+    const int ch = (im.h + 1) / 2;
+    const int r = row < ch ? row : ch - 1;
+    const int y0 = 2 * r, y1 = 2 * r + 1 < im.h ? 2 * r + 1 : im.h - 1;
+    const int x0 = 2 * col < im.w ? 2 * col : im.w - 1, x1 = 2 * col + 1 < im.w ? 2 * col + 1 : im.w - 1;
+    const int sum = pixel_component(im, pixels, comp, y0, x0) + pixel_component(im, pixels, comp, y0, x1) + pixel_component(im, pixels, comp, y1, x0) +
+                    pixel_component(im, pixels, comp, y1, x1);
+    return (sum + ((col & 1) ? 2 : 1)) >> 2;
+}
+
+// One 8-point pass of jpeg_fdct_islow, v[0..7] in place.  first: the row pass (outputs scaled up by PASS1_BITS); else the column pass.
+JPEG_HD void fdct8(int* v, bool first) {
+    using namespace jpegm;
+    const int tmp0 = v[0] + v[7], tmp7 = v[0] - v[7], tmp1 = v[1] + v[6], tmp6 = v[1] - v[6];
+    const int tmp2 = v[2] + v[5], tmp5 = v[2] - v[5], tmp3 = v[3] + v[4], tmp4 = v[3] - v[4];
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    const int shift = first ? CONST_BITS - PASS1_BITS : CONST_BITS + PASS1_BITS;
+    if (first) {
+        v[0] = shl(tmp10 + tmp11, PASS1_BITS);
+        v[4] = shl(tmp10 - tmp11, PASS1_BITS);
+    } else {
+        v[0] = descale(tmp10 + tmp11, PASS1_BITS);
+        v[4] = descale(tmp10 - tmp11, PASS1_BITS);
+    }
+    int z1 = (tmp12 + tmp13) * FIX_0_541196100;
+    v[2] = descale(z1 + tmp13 * FIX_0_765366865, shift);
+    v[6] = descale(z1 + tmp12 * -FIX_1_847759065, shift);
+    z1 = tmp4 + tmp7;
+    int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+    const int z5 = (z3 + z4) * FIX_1_175875602;
+    const int t4 = tmp4 * FIX_0_298631336, t5 = tmp5 * FIX_2_053119869, t6 = tmp6 * FIX_3_072711026, t7 = tmp7 * FIX_1_501321110;
+    z1 *= -FIX_0_899976223; z2 *= -FIX_2_562915447;
+    z3 = z3 * -FIX_1_961570560 + z5; z4 = z4 * -FIX_0_390180644 + z5;
+    v[7] = descale(t4 + z1 + z3, shift);
+    v[5] = descale(t5 + z2 + z4, shift);
+    v[3] = descale(t6 + z2 + z3, shift);
+    v[1] = descale(t7 + z1 + z4, shift);
+}
+
+// A DCT output (scaled by 8) over the table entry q: halves away from zero.
+JPEG_HD int quantise(int c, int q) {
+    const int a = c < 0 ? -c : c;
+    const int v = (a + 4 * q) / (8 * q);
+    return c < 0 ? -v : v;
+}
+
+// Entry k (natural order) of the table for `quality` 1 ... 100: cls 0 luma, 1 chroma.
+JPEG_HD int quant_entry(int cls, int k, int quality) {
+    const uint8_t luma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                              18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+    const uint8_t chroma[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    const int v = ((cls ? chroma[k] : luma[k]) * s + 50) / 100;
+    return v < 1 ? 1 : v > 255 ? 255 : v;
+}
+
+// The block of component `comp` at (bx, by): level shift, rows, columns, quantisation; out[zigzag position], q in zigzag order too.
+// (The kernel runs the same two passes with one row / column per lane.)
+JPEG_HD void forward_block(const Frame& f, const void* pixels, int comp, int bx, int by, const uint16_t* q, int16_t* out) {
+    int ws[64];
+    for (int r = 0; r < 8; ++r) {
+        for (int c = 0; c < 8; ++c) ws[r * 8 + c] = component_sample(f, pixels, comp, by * 8 + r, bx * 8 + c) - 128;
+        fdct8(ws + r * 8, true);
+    }
+    for (int c = 0; c < 8; ++c) {
+        int v[8];
+        for (int r = 0; r < 8; ++r) v[r] = ws[r * 8 + c];
+        fdct8(v, false);
+        for (int r = 0; r < 8; ++r) {
+            const int z = zigzag_of_natural(r * 8 + c);
+            out[z] = (int16_t)quantise(v[r], q[z]);
+        }
+    }
+}
+
+JPEG_HD int category(int v) {
+    const unsigned a = (unsigned)(v < 0 ? -v : v);
+    return a ? 32 - __builtin_clz(a) : 0;
+}
+
+// The codes of one block, in order, through emit(bits, count): each call carries one Huffman code with the value bits behind it, at
+// most 26 bits.  zz: the coefficients in zigzag order (zz[0] is not read: diff is the DC difference); table: the class's TABLE_WORDS
+// entries code | length << 16.  A negative value sends the low bits of v - 1.
+template <typename Emit>
+JPEG_HD void code_block(const int16_t* zz, int diff, const uint32_t* table, Emit&& emit) {
+    int s = category(diff);
+    uint32_t e = table[s];
+    emit(((e & 0xFFFFu) << s) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1)), (int)(e >> 16) + s);
+    int run = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll          // the coefficients stay in registers
+#endif
+    for (int k = 1; k < 64; ++k) {
+        const int v = zz[k];
+        if (v == 0) { ++run; continue; }
+        for (; run > 15; run -= 16) { e = table[16 + ZRL]; emit(e & 0xFFFFu, (int)(e >> 16)); }
+        s = category(v);
+        e = table[16 + (run << 4 | s)];
+        emit(((e & 0xFFFFu) << s) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1)), (int)(e >> 16) + s);
+        run = 0;
+    }
+    if (run > 0) { e = table[16 + EOB]; emit(e & 0xFFFFu, (int)(e >> 16)); }
+}
+
+// A dummy block: difference 0, then the end-of-block.
+template <typename Emit>
+JPEG_HD void code_dummy(const uint32_t* table, Emit&& emit) {
+    emit(table[0] & 0xFFFFu, (int)(table[0] >> 16));
+    emit(table[16 + EOB] & 0xFFFFu, (int)(table[16 + EOB] >> 16));
+}
+
+}  // namespace jpegem

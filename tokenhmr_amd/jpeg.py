@@ -8,13 +8,27 @@
 The pixels are libjpeg's default pipeline bit for bit (JDCT_ISLOW, fancy upsampling, fixed-point YCbCr -> RGB): what PIL and cv2.imread
 give.  A file of a kind the decoder does not handle (progressive, arithmetic, CMYK, ...) raises JpegUnsupported — callers fall back to
 their host decoder for that file; a malformed one raises JpegError.
+
+Baseline JPEG encoding of device images, the drop-in for cv2.imwrite(".jpg") (csrc/jpegenc.hip, jpegenc_host.h, jpegenc_math.h):
+
+    imwrite("frame.jpg", frame)                          # device tensor or numpy array, (H, W), (H, W, 1 | 3 | 4); BGR(A) like cv2; q 95, 4:2:0
+    imwrite_batch(paths, frames, quality=90)             # ONE device call, the files written from a small thread pool
+    files = JpegEncoder("cuda:0").encode([a, b, ...], quality=[95, 50, ...], subsampling="4:4:4", bgr=False)      # list[bytes]
+    data = encode_host(array, quality=75)                # the same bytes on the CPU (thmr_jpeg_encode_host)
+
+The file is the one libjpeg-turbo writes for the same pixels (Pillow's save(format="JPEG", quality=q, subsampling=s)), byte for byte:
+baseline JFIF, Annex-K Huffman tables, no restart markers, no optimisation pass.  Samples are converted as png.py converts them
+(`scale`, `rounding`); the alpha of a 4-channel image is dropped, as cv2 does.  "4:2:2" is refused by name.
 """
 import ctypes as C
+import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import _cabi
+from . import png as _png
 
 
 class JpegError(_cabi.EngineError):
@@ -149,3 +163,170 @@ class JpegDecoder(_cabi.Handle):
         decode_planned to overlap it."""
         windows = [None] * len(datas) if windows is None else windows
         return self.decode_planned([entropy_decode(d, w, self.lib) for d, w in zip(datas, windows)], bgr=bgr)
+
+
+# ---- encoding ----
+_SUBSAMPLING = {"4:4:4": _cabi.JPEG_444, "4:2:2": _cabi.JPEG_422, "4:2:0": _cabi.JPEG_420}
+IMWRITE_JPEG_QUALITY = 1        # cv2's flag, the one imwrite honours
+
+
+def encode_bound(width, height, channels, subsampling="4:2:0", lib=None):
+    """The largest file the encoder writes for an image of this size (0 for arguments it refuses)."""
+    return int((lib or _cabi.load()).thmr_jpeg_encode_bound(int(width), int(height), int(channels), _subsampling(subsampling)))
+
+
+def _subsampling(s):
+    if s not in _SUBSAMPLING:
+        raise ValueError(f"subsampling must be '4:4:4' or '4:2:0' ('4:2:2' is refused by the encoder), got {s!r}")
+    return _SUBSAMPLING[s]
+
+
+def _quality(q):
+    if isinstance(q, bool) or not isinstance(q, (int, np.integer)):
+        raise ValueError(f"quality must be an integer 1 ... 100, got {q!r}")
+    return int(q)
+
+
+def _per_image(value, n, what):
+    """One setting for all images, or a list with one per image."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError(f"{len(value)} {what} settings for {n} images")
+        return list(value)
+    return [value] * n
+
+
+def _fill(item, img, scale, rounding, bgr, what="image"):
+    if img.dtype not in _png._DTYPES:
+        raise JpegError(f"{what}: dtype must be uint8 or float32, got {img.dtype}")
+    return _png._fill(item, img, scale, rounding, bgr)
+
+
+def _out(item, h, w, c, sub, lib, capacity=None):
+    cap = int(lib.thmr_jpeg_encode_bound(w, h, c, sub)) if capacity is None else int(capacity)
+    buf = np.empty(max(cap, 1), dtype=np.uint8)
+    item.out, item.capacity = buf.ctypes.data, cap
+    return buf
+
+
+def encode_host(img, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, capacity=None, lib=None):
+    """One numpy image -> the file's bytes, on the CPU with the kernels' arithmetic: the oracle of JpegEncoder, and what a caller without
+    a device gets.  capacity: the output buffer's size (default thmr_jpeg_encode_bound), for the refusal test."""
+    lib = lib or _cabi.load()
+    img = np.asarray(img)
+    item = _cabi.PngItem()
+    q, sub = _quality(quality), _subsampling(subsampling)
+    h, w, c = _fill(item, img, scale, rounding, bgr)
+    item.pixels = img.ctypes.data
+    buf = _out(item, h, w, c, sub, lib, capacity)
+    rc = lib.thmr_jpeg_encode_host(C.byref(item), q, sub)
+    if rc != 0:
+        _cabi.raise_error(rc, "thmr_jpeg_encode_host", lib.thmr_jpeg_encoder_last_error(None), JpegError, _BY_CODE)
+    return buf[:item.written].tobytes()
+
+
+class JpegEncoder(_cabi.Handle):
+    """Owns a thmr_jpeg_encoder handle: grow-only device scratch and pinned staging, and a grow-only host buffer the files of a call are
+    written into before they become bytes (the bound of a frame is tens of MB: allocated once, not per call).  One stream at a time;
+    encode() synchronises it."""
+    error, error_by_code = JpegError, _BY_CODE
+
+    def __init__(self, device="cuda:0"):
+        super().__init__(device, "thmr_jpeg_encoder", "JpegEncoder needs a GPU device; encode_host() is the CPU encode")
+        self._files = np.empty(0, dtype=np.uint8)
+        self._open(self._index())
+
+    def encode(self, images, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True):
+        """A list of images — device tensors, or host tensors / numpy arrays (uploaded) — of any sizes, dtypes and strides -> the files,
+        list[bytes], in ONE batch call on the current stream.  quality (1 ... 100) and subsampling ("4:4:4", "4:2:0") hold for all
+        images, or are lists with one entry per image.  bgr: the images hold B, G, R(, A) like cv2's; False: R, G, B(, A)."""
+        n = len(images)
+        qs = [_quality(q) for q in _per_image(quality, n, "quality")]
+        subs = [_subsampling(s) for s in _per_image(subsampling, n, "subsampling")]
+        if n == 0:
+            return []
+        items = (_cabi.PngItem * n)()
+        keep, at, total = [], [], 0
+        for i, img in enumerate(images):
+            if isinstance(img, np.ndarray):
+                if img.dtype == np.float64:
+                    img = img.astype(np.float32)
+                if img.dtype not in _png._DTYPES or _png._DTYPES[img.dtype] == _cabi.PNG_U16:
+                    raise (JpegUnsupported if img.dtype == np.uint16 else JpegError)(
+                        f"image {i}: dtype must be uint8 or float32, got {img.dtype}" + (" (16-bit samples are unsupported)" if img.dtype == np.uint16 else ""))
+                img = torch.from_numpy(np.ascontiguousarray(img))
+            if img.device != self.device:
+                img = img.to(self.device)
+            h, w, c = _fill(items[i], img, scale, rounding, bgr, f"image {i}")
+            items[i].pixels = img.data_ptr()
+            keep.append(img)
+            items[i].capacity = int(self.lib.thmr_jpeg_encode_bound(w, h, c, subs[i]))         # 0 for an image the call refuses: it names it
+            at.append(total)
+            total += (items[i].capacity + 63) & ~63
+        if self._files.size < total:
+            self._files = np.empty(total + total // 4, dtype=np.uint8)
+        for i in range(n):
+            items[i].out = self._files.ctypes.data + at[i]
+        qa, sa = (C.c_int32 * n)(*qs), (C.c_int32 * n)(*subs)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            rc = self.lib.thmr_jpeg_encode_batch(self.h, items, qa, sa, n, C.c_void_p(stream.cuda_stream))
+        self._check(rc, "thmr_jpeg_encode_batch")
+        return [self._files[at[i]:at[i] + items[i].written].tobytes() for i in range(n)]
+
+
+_encoders = {}
+
+
+def _encoder(device):
+    device = _cabi.Handle.cuda_device(device, "imwrite needs a GPU device; encode_host() is the CPU encode", resolve=True)
+    if device not in _encoders:
+        _encoders[device] = JpegEncoder(device)
+    return _encoders[device]
+
+
+def _check_path(path):
+    ext = os.path.splitext(os.fspath(path))[1]
+    if ext.lower() not in (".jpg", ".jpeg"):
+        raise ValueError(f"jpeg.imwrite writes .jpg / .jpeg files only, got extension {ext!r} ({os.fspath(path)!r})")
+
+
+def _params_quality(params, quality):
+    """cv2's params list [flag, value, ...]: IMWRITE_JPEG_QUALITY sets the quality, any other flag is refused by its number."""
+    if params is None:
+        return quality
+    params = [int(p) for p in params]
+    if len(params) % 2:
+        raise ValueError(f"params must hold (flag, value) pairs, got {len(params)} entries")
+    for flag, value in zip(params[::2], params[1::2]):
+        if flag != IMWRITE_JPEG_QUALITY:
+            raise ValueError(f"params flag {flag} is not supported: jpeg.imwrite honours IMWRITE_JPEG_QUALITY ({IMWRITE_JPEG_QUALITY}) only")
+        quality = value
+    return quality
+
+
+def imwrite(path, img, params=None, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, device=None):
+    """cv2.imwrite for .jpg / .jpeg: a device tensor or a numpy array, (H, W) or (H, W, C), channels in cv2's B, G, R(, A) order; the
+    defaults are cv2's (quality 95, 4:2:0).  params=[cv2.IMWRITE_JPEG_QUALITY, q] is honoured; any other flag raises ValueError naming
+    it, and so does any other extension.  A numpy array goes to `device` (default: the current GPU).  Returns True."""
+    _check_path(path)
+    quality = _params_quality(params, quality)
+    data = _encoder(_png._device_of([img], device)).encode([img], quality=quality, subsampling=subsampling, scale=scale, rounding=rounding, bgr=bgr)[0]
+    _png._write(path, data)
+    return True
+
+
+def imwrite_batch(paths, images, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, device=None, threads=None):
+    """imwrite for many files: ONE device call for all images, then the files are written from a thread pool (at most png.WRITE_THREADS)."""
+    paths = list(paths)
+    if len(paths) != len(images):
+        raise ValueError(f"{len(paths)} paths for {len(images)} images")
+    for p in paths:
+        _check_path(p)
+    if not paths:
+        return True
+    files = _encoder(_png._device_of(images, device)).encode(list(images), quality=quality, subsampling=subsampling, scale=scale, rounding=rounding, bgr=bgr)
+    workers = max(1, min(_png.WRITE_THREADS if threads is None else int(threads), len(paths)))
+    with ThreadPoolExecutor(workers) as pool:
+        list(pool.map(_png._write, paths, files))
+    return True
