@@ -112,6 +112,18 @@ def test_batches_of_mixed_items_keep_their_canaries(n, decoder):
         assert np.array_equal(g, alone), (k, name, win)
 
 
+def test_an_empty_window_between_two_items(decoder):
+    # the middle item has no blocks and shares its first block with its successor: every block past it belongs to the successor
+    cases, _, _ = gold()
+    names = supported()[:3]
+    items = [(names[0], (0, 0, cases[names[0]]["width"], cases[names[0]]["height"])), (names[1], (0, 0, 0, 0)),
+             (names[2], (0, 0, cases[names[2]]["width"], cases[names[2]]["height"]))]
+    got = decode_in_canaries(decoder, items)
+    assert got[1].size == 0
+    for (name, win), g in zip(items, got):
+        assert np.array_equal(g, host_reference(name, win)), (name, win)
+
+
 def test_reuse_after_growth_and_on_the_alternate_staging_set(built_lib, cuda_dev):
     from tokenhmr_amd.jpeg import JpegDecoder
     d = JpegDecoder(cuda_dev)

@@ -89,6 +89,15 @@ def test_one_block_past_each_boundary(J, encoder, cuda_dev):
     check(J, encoder, cuda_dev, images, bgr=False, **kw)
 
 
+def test_items_of_one_three_and_twelve_blocks(J, encoder, cuda_dev):
+    # 1 x 1 grey, 17 x 23 at 4:2:0 and 8 x 8 at 4:4:4 have 1, 2 x 6 = 12 and 3 blocks, and each item starts a segment of its own:
+    # their first blocks are 0, 256 and 512, so nearly every lane that searches for its item finds one whose blocks it lies past
+    _, S, _ = kernel_constants()
+    assert S == 256
+    images = [K.picture("noise", 1, 1, 0), K.picture("noise", 17, 23), K.picture("smooth", 8, 8)]
+    check(J, encoder, cuda_dev, images, quality=[90, 75, 100], subsampling=["4:2:0", "4:2:0", "4:4:4"], bgr=False)
+
+
 def test_stuffing_dense_and_large_scans(J, encoder, cuda_dev):
     # 0 / 255 checkerboards at q 100: the largest categories and a 0xFF in most bytes' neighbourhood; the noise panel's scan has more
     # than 256 chunks, so the scan over the chunks takes a second round; an all-white image stuffs nothing

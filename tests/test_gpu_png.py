@@ -106,6 +106,16 @@ def test_mixed_batch_equals_each_alone_and_a_second_call(P, encoder, cuda_dev):
     assert encoder.encode(images[::-1], rounding="trunc") == together[::-1]
 
 
+def test_one_filter_workgroup_spans_three_items(P, encoder, cuda_dev):
+    # heights 1, 2 and 5: rows 0 ... 3 of the batch, one 4-row workgroup of the filter kernel, belong to items 0, 1, 1 and 2, so the
+    # search for a row's item ends at every item inside one workgroup; widths below, at and one past the 64 lanes of a row's wave
+    images = [K.image("noise", 1, 3, 3), K.image("render", 2, 64, 1), K.image("noise", 5, 65, 4)]
+    files = encoder.encode([torch.from_numpy(img).to(cuda_dev) for img in images], bgr=False)
+    for i, (img, data) in enumerate(zip(images, files)):
+        want = P.encode_host(img, bgr=False)
+        assert data == want, (i, first_difference(data, want))
+
+
 def test_imwrite_and_imwrite_batch(P, cuda_dev, tmp_path):
     bgr = K.image("render", 48, 80, 3)
     rgb = bgr[..., ::-1]

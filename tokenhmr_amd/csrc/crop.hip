@@ -302,20 +302,10 @@ extern "C" {
 const char* thmr_cropper_last_error(const thmr_cropper* c) { return g_crop_err.read(c); }
 
 int thmr_cropper_create(int32_t device, thmr_cropper** out) {
-    if (!out) return g_crop_err.invalid(nullptr, "null out");
-    *out = nullptr;
-    if (!check_device(device)) return g_crop_err.fail(nullptr, THMR_ERR_HIP, "no such HIP device (the crop kernels have no CPU fallback)");
-    thmr_cropper* c = new thmr_cropper();
-    c->device = device;
-    *out = c;
-    return 0;
+    return handle_create(device, out, g_crop_err, "no such HIP device (the crop kernels have no CPU fallback)");
 }
 
-void thmr_cropper_destroy(thmr_cropper* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    delete c;          // the buffers free themselves
-}
+void thmr_cropper_destroy(thmr_cropper* c) { handle_destroy(c); }
 
 int thmr_cropper_run(thmr_cropper* c, const uint8_t* frame_dev, int32_t H, int32_t W, int64_t row_stride,
                      const thmr_crop_desc* crops, int32_t n, int32_t patch, int32_t swap_rb, const float* mean, const float* std_,

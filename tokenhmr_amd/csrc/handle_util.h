@@ -1,5 +1,6 @@
-// Host-side plumbing shared by the stateful handle objects of include/tokenhmr_hip.h: thmr_cropper (crop.hip), thmr_renderer (render.hip)
-// and thmr_jpeg (jpeg.hip).  Host only: no kernel includes this.  The rules every such object keeps:
+// Host-side plumbing shared by the stateful handle objects of include/tokenhmr_hip.h: thmr_cropper (crop.hip), thmr_renderer (render.hip),
+// thmr_jpeg (jpeg.hip), thmr_jpeg_encoder (jpegenc.hip) and thmr_png (png.hip).  Host only: no kernel includes this.  The rules every
+// such object keeps:
 //   * an entry point checks its arguments before it touches the device, so a refusal costs no HIP call;
 //   * a grow-only buffer is re-allocated only behind a synchronisation of the caller's stream (grow_synced): earlier launches may
 //     still read the old allocation;
@@ -37,6 +38,37 @@ inline bool check_device(int device) {
     if (hipGetDeviceCount(&ndev) == hipSuccess && device >= 0 && device < ndev) return true;
     (void)hipGetLastError();
     return false;
+}
+
+// thmr_X_create / _destroy of a family whose handle starts empty (`int device` and grow-only buffers): the cropper, the JPEG decoder
+// and the two image writers.  no_device_text: what the refusal says where `device` is no HIP device.
+template <typename H>
+int handle_create(int32_t device, H** out, ErrorSink<H>& sink, const char* no_device_text) {
+    if (!out) return sink.invalid(nullptr, "null out");
+    *out = nullptr;
+    if (!check_device(device)) return sink.fail(nullptr, THMR_ERR_HIP, no_device_text);
+    H* h = new H();
+    h->device = device;
+    *out = h;
+    return 0;
+}
+template <typename H>
+void handle_destroy(H* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    delete h;          // the buffers free themselves
+}
+
+// What a batch entry does once its arguments and the handle are checked: selects the handle's device and asks whether `st` is being
+// captured.  0, or the status of the HIP failure, reported through the sink.  What a capture means is the caller's business.
+template <typename H>
+int enter_stream(H* h, hipStream_t st, ErrorSink<H>& sink, bool* capturing) {
+    hipError_t e;
+    if ((e = hipSetDevice(h->device)) != hipSuccess) return sink.hip(h, "hipSetDevice", e);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if ((e = hipStreamIsCapturing(st, &cap)) != hipSuccess) return sink.hip(h, "hipStreamIsCapturing", e);
+    *capturing = cap != hipStreamCaptureStatusNone;
+    return 0;
 }
 
 // One grow-only HIP allocation, untyped: device memory, or (pinned) page-locked host memory.  Freed by release() or the destructor; the

@@ -1,12 +1,14 @@
 // Baseline JPEG decoding (include/tokenhmr_hip.h).  The host entry points wrap the parser and entropy decoder of jpeg_host.h;
 // the device half runs two kernels over a whole batch: the dequantising JDCT_ISLOW inverse DCT of every kept block into component planes,
-// then fancy upsampling + colour conversion of every window.  The arithmetic of both lives in jpeg_math.h, which the CPU decode shares.
+// then fancy upsampling + colour conversion of every window.  The arithmetic of both lives in jpeg_math.h, which the CPU decode shares;
+// item_of is batch_device.h's, as in the two encoders (png.hip, jpegenc.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <string>
 #include <vector>
 
+#include "batch_device.h"
 #include "handle_util.h"
 #include "jpeg_host.h"
 
@@ -43,12 +45,7 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const JpegItemDev* __res
     const bool live = g < total_blocks;
     int item = 0, c = 0, local = 0;
     if (live) {
-        int lo = 0, hi = n - 1;          // the last item whose blk0 <= g (items without blocks share a blk0 with their successor)
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (items[mid].blk0 <= g) lo = mid; else hi = mid - 1;
-        }
-        item = lo;
+        item = item_of<&JpegItemDev::blk0>(items, n, g);          // items without blocks share a blk0 with their successor
         local = g - items[item].blk0;
         if (items[item].ncomp == 3) c = local >= items[item].cblk[2] ? 2 : local >= items[item].cblk[1] ? 1 : 0;
         const int16_t* src = coef + items[item].coef_off + (int64_t)local * 64;
@@ -187,14 +184,7 @@ int thmr_jpeg_decode_host(const uint8_t* data, size_t len, const int32_t* window
 const char* thmr_jpeg_last_error(const thmr_jpeg* j) { return g_jpeg_err.read(j); }
 
 int thmr_jpeg_create(int32_t device, thmr_jpeg** out) {
-    if (!out) return g_jpeg_err.invalid(nullptr, "null out");
-    *out = nullptr;
-    if (!check_device(device))
-        return g_jpeg_err.fail(nullptr, THMR_ERR_HIP, "no such HIP device (without one, thmr_jpeg_decode_host decodes on the CPU)");
-    thmr_jpeg* j = new thmr_jpeg();
-    j->device = device;
-    *out = j;
-    return 0;
+    return handle_create(device, out, g_jpeg_err, "no such HIP device (without one, thmr_jpeg_decode_host decodes on the CPU)");
 }
 
 void thmr_jpeg_destroy(thmr_jpeg* j) {
@@ -202,7 +192,7 @@ void thmr_jpeg_destroy(thmr_jpeg* j) {
     (void)hipSetDevice(j->device);
     for (Stage& s : j->stage)
         if (s.ev) { if (s.recorded) (void)hipEventSynchronize(s.ev); (void)hipEventDestroy(s.ev); }
-    delete j;          // the buffers free themselves
+    handle_destroy(j);
 }
 
 int thmr_jpeg_decode_batch(thmr_jpeg* j, const thmr_jpeg_item* items, int32_t n, int32_t bgr, void* stream) {
@@ -262,10 +252,8 @@ int thmr_jpeg_decode_batch(thmr_jpeg* j, const thmr_jpeg_item* items, int32_t n,
     if (total_blocks == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e;
-    if ((e = hipSetDevice(j->device)) != hipSuccess) return g_jpeg_err.hip(j, "hipSetDevice", e);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if ((e = hipStreamIsCapturing(st, &cap)) != hipSuccess) return g_jpeg_err.hip(j, "hipStreamIsCapturing", e);
-    const bool capturing = cap != hipStreamCaptureStatusNone;
+    bool capturing;
+    if (const int rc = enter_stream(j, st, g_jpeg_err, &capturing)) return rc;
 
     const size_t desc_bytes = (sizeof(JpegItemDev) * (size_t)n + 255) & ~size_t(255);
     const size_t bytes = desc_bytes + (size_t)coef_total * sizeof(int16_t);

@@ -10,12 +10,14 @@
 //               also packs the files' scans densely), and the bytes scattered with the 0x00 inserted — into the pinned staging, so the
 //               host needs one synchronisation and no second copy.  It comes after packing: stuffing depends on byte alignment.
 // The arithmetic and the coding rules live in jpegenc_math.h, which the CPU encode (jpegenc_host.h) shares: both write the same bytes.
-// Headers, DQT / DHT and EOI are written on the host.
+// Headers, DQT / DHT and EOI are written on the host.  The source image and its pixel conversion (image_source.h) and the item checks
+// (image_item_host.h) are the PNG encoder's too; item_of and block_scan are batch_device.h's.
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
+#include "batch_device.h"
 #include "handle_util.h"
 #include "jpegenc_host.h"
 
@@ -41,40 +43,6 @@ struct JpegItemDev {
 static_assert(sizeof(JpegItemDev) % 8 == 0, "descriptors are read as an array");
 constexpr size_t TABLE_BYTES = sizeof(uint32_t) * 2 * jpegem::TABLE_WORDS;
 static_assert(TABLE_BYTES % 16 == 0, "the descriptors follow the code tables");
-
-// The last item whose first block / segment / chunk (field at `first`) is <= g.
-template <int64_t JpegItemDev::*first>
-__device__ int item_of(const JpegItemDev* items, int n, int64_t g) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (items[mid].*first <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// Exclusive prefix sum over the 256 lanes of a workgroup; total: the sum, in every lane.  part: 4 words of LDS.
-template <typename T>
-__device__ T block_scan(T v, T* part, T& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    __syncthreads();                // the previous use of part is over
-    if (lane == 63) part[w] = incl;
-    __syncthreads();
-    T before = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (i < w) before += part[i];
-        total += part[i];
-    }
-    return before + incl - v;
-}
 
 __global__ __launch_bounds__(256) void jpegenc_transform_kernel(const JpegItemDev* __restrict__ items, int n, int16_t* __restrict__ coef) {
     __shared__ int ws[TRANSFORM_BLOCKS][72];
@@ -305,21 +273,10 @@ int thmr_jpeg_encode_host(thmr_png_item* item, int32_t quality, int32_t subsampl
 const char* thmr_jpeg_encoder_last_error(const thmr_jpeg_encoder* e) { return g_jenc_err.read(e); }
 
 int thmr_jpeg_encoder_create(int32_t device, thmr_jpeg_encoder** out) {
-    if (!out) return g_jenc_err.invalid(nullptr, "null out");
-    *out = nullptr;
-    if (!check_device(device))
-        return g_jenc_err.fail(nullptr, THMR_ERR_HIP, "no such HIP device (without one, thmr_jpeg_encode_host encodes on the CPU)");
-    thmr_jpeg_encoder* e = new thmr_jpeg_encoder();
-    e->device = device;
-    *out = e;
-    return 0;
+    return handle_create(device, out, g_jenc_err, "no such HIP device (without one, thmr_jpeg_encode_host encodes on the CPU)");
 }
 
-void thmr_jpeg_encoder_destroy(thmr_jpeg_encoder* e) {
-    if (!e) return;
-    (void)hipSetDevice(e->device);
-    delete e;          // the buffers free themselves
-}
+void thmr_jpeg_encoder_destroy(thmr_jpeg_encoder* e) { handle_destroy(e); }
 
 int thmr_jpeg_encode_batch(thmr_jpeg_encoder* e, thmr_png_item* items, const int32_t* qualities, const int32_t* subsamplings, int32_t n, void* stream) {
     // every argument is checked before the handle, and the handle before any HIP call: a refusal never touches the device
@@ -335,7 +292,7 @@ int thmr_jpeg_encode_batch(thmr_jpeg_encoder* e, thmr_png_item* items, const int
         JpegItemDev& d = ids[(size_t)i];
         memset(&d, 0, sizeof(d));
         d.pixels = it.pixels;
-        d.f = jpegem::frame_of(pngh::image_of(it), subsamplings[i] == THMR_JPEG_420);
+        d.f = jpegem::frame_of(jpegeh::image_of(it), subsamplings[i] == THMR_JPEG_420);
         d.blk0 = blks; d.nblk = jpegeh::blocks(it.width, it.height, it.channels, subsamplings[i]);
         d.seg0 = blks / SEG_BLOCKS; d.nseg = (d.nblk + SEG_BLOCKS - 1) / SEG_BLOCKS;
         d.chunk0 = chunks;
@@ -349,10 +306,9 @@ int thmr_jpeg_encode_batch(thmr_jpeg_encoder* e, thmr_png_item* items, const int
     if (!e) return g_jenc_err.invalid(e, "null handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t err;
-    if ((err = hipSetDevice(e->device)) != hipSuccess) return g_jenc_err.hip(e, "hipSetDevice", err);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if ((err = hipStreamIsCapturing(st, &cap)) != hipSuccess) return g_jenc_err.hip(e, "hipStreamIsCapturing", err);
-    if (cap != hipStreamCaptureStatusNone)
+    bool capturing;
+    if (const int rc = enter_stream(e, st, g_jenc_err, &capturing)) return rc;
+    if (capturing)
         return g_jenc_err.fail(e, THMR_ERR_STATE, "thmr_jpeg_encode_batch returns files in host memory and cannot run inside a stream capture");
 
     const int64_t segs = blks / SEG_BLOCKS;

@@ -8,11 +8,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tokenhmr_hip.h"
+#include "image_item_host.h"
 #include "jpegenc_math.h"
-#include "png_host.h"
 
 namespace jpegeh {
+
+using imgitem::image_of;
 
 // Annex K, tables K.3 - K.6: codes per length 1 ... 16, then the symbols in code order.
 struct HuffSpec { uint8_t bits[16]; const uint8_t* vals; int n; };
@@ -81,10 +82,7 @@ inline int64_t bound(int32_t w, int32_t h, int32_t c, int32_t sub) {
 
 // 0, or the status with the reason in err.  Pointers and capacity included.
 inline int check_item(const thmr_png_item& it, int32_t quality, int32_t sub, std::string& err) {
-    if (it.dtype == THMR_PNG_U16) { err = "unsupported: 16-bit samples (dtype THMR_PNG_U16); the encoder writes 8-bit files"; return THMR_ERR_UNSUPPORTED; }
-    if (it.dtype != THMR_PNG_U8 && it.dtype != THMR_PNG_F32) { err = "dtype must be THMR_PNG_U8 or THMR_PNG_F32"; return THMR_ERR_INVALID; }
-    if (it.channels == 2) { err = "unsupported: 2 channels (grey + alpha); the encoder reads 1, 3 or 4"; return THMR_ERR_UNSUPPORTED; }
-    if (it.channels != 1 && it.channels != 3 && it.channels != 4) { err = "channels must be 1, 3 or 4, got " + std::to_string(it.channels); return THMR_ERR_INVALID; }
+    if (const int rc = imgitem::check_source(it, "reads", err)) return rc;
     if (sub == THMR_JPEG_422) { err = "unsupported: 4:2:2 subsampling (THMR_JPEG_422); the encoder writes 4:4:4 and 4:2:0"; return THMR_ERR_UNSUPPORTED; }
     if (sub != THMR_JPEG_444 && sub != THMR_JPEG_420) { err = "subsampling must be THMR_JPEG_444 or THMR_JPEG_420, got " + std::to_string(sub); return THMR_ERR_INVALID; }
     if (quality < 1 || quality > 100) { err = "quality must be 1 ... 100, got " + std::to_string(quality); return THMR_ERR_INVALID; }
@@ -94,14 +92,7 @@ inline int check_item(const thmr_png_item& it, int32_t quality, int32_t sub, std
     }
     if (it.rounding != THMR_PNG_ROUND_NEAREST && it.rounding != THMR_PNG_ROUND_TRUNC) { err = "rounding must be THMR_PNG_ROUND_NEAREST or _TRUNC"; return THMR_ERR_INVALID; }
     if (it.compression != 0) { err = "compression must be 0 for a JPEG item, got " + std::to_string(it.compression); return THMR_ERR_INVALID; }
-    if (!it.pixels) { err = "null pixels"; return THMR_ERR_INVALID; }
-    if (!it.out) { err = "null out"; return THMR_ERR_INVALID; }
-    const int64_t need = bound(it.width, it.height, it.channels, sub);
-    if (it.capacity < need) {
-        err = "capacity " + std::to_string(it.capacity) + " is below thmr_jpeg_encode_bound = " + std::to_string(need);
-        return THMR_ERR_INVALID;
-    }
-    return 0;
+    return imgitem::check_buffers(it, bound(it.width, it.height, it.channels, sub), "thmr_jpeg_encode_bound", err);
 }
 
 // q[cls * 64 + zigzag position] for `quality`.
@@ -159,7 +150,7 @@ struct BitWriter {
 
 // The whole file on the CPU.  The item is already checked.
 inline void encode(thmr_png_item& it, int32_t quality, int32_t sub) {
-    const jpegem::Frame f = jpegem::frame_of(pngh::image_of(it), sub == THMR_JPEG_420);
+    const jpegem::Frame f = jpegem::frame_of(image_of(it), sub == THMR_JPEG_420);
     uint16_t q[128];
     quant_tables(quality, q);
     const uint32_t* codes = code_tables().t;

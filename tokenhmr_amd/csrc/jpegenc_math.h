@@ -2,13 +2,13 @@
 // (jpegenc_host.h): libjpeg's default compression pipeline restated in integers — jccolor.c's 16-bit fixed-point RGB -> YCbCr, the h2v2
 // box downsampler with its alternating bias and libjpeg's edge expansion, jfdctint.c (JDCT_ISLOW, the constants of jpeg_math.h),
 // quantisation by 8 q with halves away from zero, and the Huffman coding of a block with the Annex K tables.  The samples come from
-// pngm::sample, the one pixel conversion of both encoders.  Everything is integer, so both sides give the same bytes.
+// imgsrc::sample (image_source.h), the one pixel conversion of both encoders.  Everything is integer, so both sides give the same bytes.
 // Compiles with or without HIP.
 #pragma once
 #include <stdint.h>
 
+#include "image_source.h"
 #include "jpeg_math.h"
-#include "png_math.h"
 
 namespace jpegem {
 
@@ -18,7 +18,7 @@ constexpr int EOB = 0x00, ZRL = 0xF0;
 
 // One image as the encoder sees it besides its pixels and tables.
 struct Frame {
-    pngm::Image im;
+    imgsrc::Image im;
     int32_t ncomp;              // 1 (grey) or 3
     int32_t sub;                // 1: 4:2:0 (three components only), 0: 4:4:4
     int32_t mcux, mcuy;         // MCUs per row / column
@@ -26,7 +26,7 @@ struct Frame {
     int32_t lbw, lbh;           // real luma blocks per row / column: ceil(W / 8), ceil(H / 8)
 };
 
-JPEG_HD Frame frame_of(const pngm::Image& im, int sub) {
+JPEG_HD Frame frame_of(const imgsrc::Image& im, int sub) {
     Frame f;
     f.im = im;
     f.ncomp = im.c == 1 ? 1 : 3;
@@ -83,9 +83,9 @@ JPEG_HD void rgb_to_ycc(int r, int g, int b, int& y, int& cb, int& cr) {
 }
 
 // Component `comp` of pixel (x, y), both inside the image.  The alpha of a 4-channel image is never read.
-JPEG_HD int pixel_component(const pngm::Image& im, const void* pixels, int comp, int y, int x) {
-    if (im.c == 1) return pngm::sample(im, pixels, y, x);
-    const int r = pngm::sample(im, pixels, y, x * im.c), g = pngm::sample(im, pixels, y, x * im.c + 1), b = pngm::sample(im, pixels, y, x * im.c + 2);
+JPEG_HD int pixel_component(const imgsrc::Image& im, const void* pixels, int comp, int y, int x) {
+    if (im.c == 1) return imgsrc::sample(im, pixels, y, x);
+    const int r = imgsrc::sample(im, pixels, y, x * im.c), g = imgsrc::sample(im, pixels, y, x * im.c + 1), b = imgsrc::sample(im, pixels, y, x * im.c + 2);
     int yy, cb, cr;
     rgb_to_ycc(r, g, b, yy, cb, cr);
     return comp == 0 ? yy : comp == 1 ? cb : cr;
@@ -96,7 +96,7 @@ JPEG_HD int pixel_component(const pngm::Image& im, const void* pixels, int comp,
 // row), takes the pixel rows 2r and min(2r + 1, H - 1), the columns min(2c, W - 1) and min(2c + 1, W - 1), and rounds with the bias 1 for
 // an even column and 2 for an odd one.
 JPEG_HD int component_sample(const Frame& f, const void* pixels, int comp, int row, int col) {
-    const pngm::Image& im = f.im;
+    const imgsrc::Image& im = f.im;
     if (!(f.sub && comp > 0)) return pixel_component(im, pixels, comp, row < im.h ? row : im.h - 1, col < im.w ? col : im.w - 1);
     const int ch = (im.h + 1) / 2;
     const int r = row < ch ? row : ch - 1;

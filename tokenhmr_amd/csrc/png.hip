@@ -1,7 +1,8 @@
 // PNG encoding of device images (include/tokenhmr_hip.h).  Three launches over a whole batch: convert + filter of every row
 // (one wave per row), deflate of every segment of the filtered streams (one wave per segment, the segment in LDS), and the gather of
 // the segments into one packed stream that crosses to the host.  The arithmetic and every selection rule live in png_math.h, which the
-// CPU encode (png_host.h) shares: both write the same bytes.  A batch with a dynamic-Huffman item (compression THMR_PNG_DYNAMIC) runs
+// CPU encode (png_host.h) shares: both write the same bytes.  The source image and its pixel conversion (image_source.h) and the item
+// checks (image_item_host.h) are the JPEG encoder's too; item_of and the wave scans are batch_device.h's.  A batch with a dynamic-Huffman item (compression THMR_PNG_DYNAMIC) runs
 // the DYNAMIC instantiation of png_deflate_kernel; a batch without one runs the other, the code it always ran.
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "batch_device.h"
 #include "handle_util.h"
 #include "png_host.h"
 
@@ -29,30 +31,12 @@ struct PngItemDev {
     int32_t dynamic;            // compression THMR_PNG_DYNAMIC
 };
 static_assert(sizeof(PngItemDev) % 8 == 0, "descriptors are read as an array");
-static_assert(sizeof(thmr_png_item) == 88, "tokenhmr_amd/_cabi.py mirrors this layout");
 
 constexpr int SLOT = pngm::SEGMENT + pngm::SEGMENT / 8 + 64;     // bytes a segment's coded form can take: 3 + 9 bits a byte + the trailer
 constexpr int RING = 128;                                         // words of the LDS bit buffer: one step adds at most 64 * 31 bits (64 * 48 in a dynamic block)
 constexpr int64_t FINISH_CHUNK = 256 << 10;                       // bytes of a stream copied out and CRC-summed as one piece of work
 constexpr int FINISH_THREADS = 16;                                // at most: what one command gets of a GPU box
 static_assert(SLOT % 4 == 0 && pngm::SEGMENT % 16 == 0, "slots are written in words, segments loaded in 16-byte pieces");
-
-// The last item whose first row / segment (field at `first`) is <= g.
-template <int32_t PngItemDev::*first>
-__device__ int item_of(const PngItemDev* items, int n, int g) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (items[mid].*first <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 // Convert + filter: one wave per row.  The five costs are summed over the row and reduced across the wave; the winner is written.
 __global__ __launch_bounds__(256) void png_filter_kernel(const PngItemDev* __restrict__ items, int n, uint8_t* __restrict__ filt, int total_rows) {
@@ -117,12 +101,7 @@ __device__ uint64_t chain_through(int adv, bool any_match, int cnt, int& pos) {
 // words then leave for the slot.  WIDE: k can exceed 32.
 template <bool WIDE>
 __device__ void ring_step(uint32_t* ring, uint32_t* slot, int64_t& bits, int& flushed, uint64_t t, int k, int lane) {
-    int incl = k;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
+    const int incl = wave_scan_inclusive(k, lane);
     // ring_put shifts its bits by up to 31 inside 64: it takes at most 33 bits at a time (a fixed-code token has 31).  A token of a
     // dynamic block has up to 15 + 5 + 15 + 13 = 48, so it goes in as its low 32 bits and the rest.
     static_assert(2 * pngm::MAX_BITS + 5 + 13 <= 64, "a token fits the 64-bit token word, and two puts of at most 32 bits");
@@ -327,21 +306,10 @@ int thmr_png_code_lengths(const int32_t* freq, int32_t n, int32_t max_bits, int3
 const char* thmr_png_last_error(const thmr_png* p) { return g_png_err.read(p); }
 
 int thmr_png_create(int32_t device, thmr_png** out) {
-    if (!out) return g_png_err.invalid(nullptr, "null out");
-    *out = nullptr;
-    if (!check_device(device))
-        return g_png_err.fail(nullptr, THMR_ERR_HIP, "no such HIP device (without one, thmr_png_encode_host encodes on the CPU)");
-    thmr_png* p = new thmr_png();
-    p->device = device;
-    *out = p;
-    return 0;
+    return handle_create(device, out, g_png_err, "no such HIP device (without one, thmr_png_encode_host encodes on the CPU)");
 }
 
-void thmr_png_destroy(thmr_png* p) {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    delete p;          // the buffers free themselves
-}
+void thmr_png_destroy(thmr_png* p) { handle_destroy(p); }
 
 int thmr_png_encode_batch(thmr_png* p, thmr_png_item* items, int32_t n, void* stream) {
     // every argument is checked before the handle, and the handle before any HIP call: a refusal never touches the device
@@ -373,10 +341,9 @@ int thmr_png_encode_batch(thmr_png* p, thmr_png_item* items, int32_t n, void* st
     if (!p) return g_png_err.invalid(p, "null handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e;
-    if ((e = hipSetDevice(p->device)) != hipSuccess) return g_png_err.hip(p, "hipSetDevice", e);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if ((e = hipStreamIsCapturing(st, &cap)) != hipSuccess) return g_png_err.hip(p, "hipStreamIsCapturing", e);
-    if (cap != hipStreamCaptureStatusNone)
+    bool capturing;
+    if (const int rc = enter_stream(p, st, g_png_err, &capturing)) return rc;
+    if (capturing)
         return g_png_err.fail(p, THMR_ERR_STATE, "thmr_png_encode_batch returns files in host memory and cannot run inside a stream capture");
 
     const size_t desc_bytes = (sizeof(PngItemDev) * (size_t)n + 255) & ~size_t(255);

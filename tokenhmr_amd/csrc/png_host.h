@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tokenhmr_hip.h"
+#include "image_item_host.h"
 #include "png_math.h"
 
 namespace pngh {
@@ -26,12 +26,11 @@ inline int64_t bound(int32_t w, int32_t h, int32_t c) {
     return raw + 5 * segments(raw) + 6 + CONTAINER_BYTES;
 }
 
+using imgitem::image_of;
+
 // 0, or the status with the reason in err.  Pointers and capacity included.
 inline int check_item(const thmr_png_item& it, std::string& err) {
-    if (it.dtype == THMR_PNG_U16) { err = "unsupported: 16-bit samples (dtype THMR_PNG_U16); the encoder writes 8-bit files"; return THMR_ERR_UNSUPPORTED; }
-    if (it.dtype != THMR_PNG_U8 && it.dtype != THMR_PNG_F32) { err = "dtype must be THMR_PNG_U8 or THMR_PNG_F32"; return THMR_ERR_INVALID; }
-    if (it.channels == 2) { err = "unsupported: 2 channels (grey + alpha); the encoder writes 1, 3 or 4"; return THMR_ERR_UNSUPPORTED; }
-    if (it.channels != 1 && it.channels != 3 && it.channels != 4) { err = "channels must be 1, 3 or 4, got " + std::to_string(it.channels); return THMR_ERR_INVALID; }
+    if (const int rc = imgitem::check_source(it, "writes", err)) return rc;
     if (it.width < 1 || it.height < 1) {
         err = "width and height must be at least 1, got " + std::to_string(it.width) + " x " + std::to_string(it.height);
         return THMR_ERR_INVALID;
@@ -42,14 +41,7 @@ inline int check_item(const thmr_png_item& it, std::string& err) {
         err = "compression must be THMR_PNG_FIXED or THMR_PNG_DYNAMIC, got " + std::to_string(it.compression);
         return THMR_ERR_INVALID;
     }
-    if (!it.pixels) { err = "null pixels"; return THMR_ERR_INVALID; }
-    if (!it.out) { err = "null out"; return THMR_ERR_INVALID; }
-    const int64_t need = bound(it.width, it.height, it.channels);
-    if (it.capacity < need) {
-        err = "capacity " + std::to_string(it.capacity) + " is below thmr_png_bound = " + std::to_string(need);
-        return THMR_ERR_INVALID;
-    }
-    return 0;
+    return imgitem::check_buffers(it, bound(it.width, it.height, it.channels), "thmr_png_bound", err);
 }
 
 // thmr_png_code_lengths: the arguments checked, then pngm::code_lengths.
@@ -65,10 +57,6 @@ inline int code_lengths(const int32_t* freq, int32_t n, int32_t max_bits, int32_
     int32_t a[pngm::N_LL], b[pngm::N_LL];
     pngm::code_lengths(freq, n, max_bits, lens, a, b);
     return 0;
-}
-
-inline pngm::Image image_of(const thmr_png_item& it) {
-    return pngm::Image{it.dtype, it.width, it.height, it.channels, it.stride_y, it.stride_x, it.stride_c, it.scale, it.rounding, it.swap_rb ? 1 : 0};
 }
 
 inline uint32_t crc32(const uint8_t* p, size_t n, uint32_t crc = 0) {

@@ -1,19 +1,21 @@
-// The arithmetic and the selection rules of the PNG encoder, shared by the kernels (png.hip) and the CPU encode (png_host.h): pixel
-// conversion, the five row filters and their cost, the candidate distances and the match rule of the LZ77 stage, and the fixed-Huffman
-// token codes, and the dynamic-Huffman block of the opt-in mode (its rule stands above token_parts).  Everything is integer (the one float product of the conversion has a single rounding), so both sides give the same bytes.
-// Compiles with or without HIP: PNG_HD is __host__ __device__ under hipcc and nothing otherwise.
+// The arithmetic and the selection rules of the PNG encoder, shared by the kernels (png.hip) and the CPU encode (png_host.h): the
+// five row filters and their cost, the candidate distances and the match rule of the LZ77 stage, and the fixed-Huffman
+// token codes, and the dynamic-Huffman block of the opt-in mode (its rule stands above token_parts).  The pixels come through
+// image_source.h.  Everything is integer, so both sides give the same bytes.  Compiles with or without HIP (PNG_HD is image_source.h's macro).
 #pragma once
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define PNG_HD __host__ __device__ inline
-#else
-#define PNG_HD inline
-#endif
+#include "image_source.h"
+
+#define PNG_HD IMGSRC_HD
 
 namespace pngm {
+
+using imgsrc::Image;            // the source image and its pixel conversion: image_source.h, shared with the JPEG encoder
+using imgsrc::row_bytes;
+using imgsrc::sample;
 
 constexpr int SEGMENT = 16384;          // bytes of the filtered stream per independently compressed segment (<= 32768: every distance is legal)
 constexpr int PAD = 8;                  // readable bytes a segment buffer keeps past its end (the match loop compares 4 at a time)
@@ -21,34 +23,6 @@ constexpr int MIN_MATCH = 3, MAX_MATCH = 258;
 constexpr int FAR = 4096;               // a match further back than this needs 4 bytes: 3 would cost more bits than 3 literals
 constexpr int MAX_CAND = 8;
 constexpr uint32_t ADLER_MOD = 65521;
-
-// What the encoder needs of one image besides its pixels.
-struct Image {
-    int32_t dtype, w, h, c;
-    int64_t sy, sx, sc;
-    float scale;
-    int32_t rounding, swap_rb;
-};
-
-PNG_HD int row_bytes(const Image& im) { return im.w * im.c; }
-
-// float -> byte.  rounding 0: nearest even, saturated; 1: clamped, then truncated.  NaN -> 0.
-PNG_HD uint8_t convert(float x, float scale, int rounding) {
-    const float v = x * scale;
-    if (!(v > 0.0f)) return 0;          // negatives, -0, NaN
-    if (v >= 255.0f) return 255;
-    return (uint8_t)(int)(rounding == 0 ? rintf(v) : v);
-}
-
-// Byte i of row y of the image as the file holds it (channel order swapped where asked).
-PNG_HD uint8_t sample(const Image& im, const void* pixels, int y, int i) {
-    const int x = i / im.c;
-    int ch = i - x * im.c;
-    if (im.swap_rb && im.c >= 3 && ch < 3) ch = 2 - ch;
-    const int64_t at = (int64_t)y * im.sy + (int64_t)x * im.sx + (int64_t)ch * im.sc;
-    if (im.dtype == 0) return static_cast<const uint8_t*>(pixels)[at];
-    return convert(static_cast<const float*>(pixels)[at], im.scale, im.rounding);
-}
 
 PNG_HD int paeth(int a, int b, int c) {
     const int p = a + b - c;

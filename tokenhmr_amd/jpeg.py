@@ -21,14 +21,11 @@ baseline JFIF, Annex-K Huffman tables, no restart markers, no optimisation pass.
 (`scale`, `rounding`); the alpha of a 4-channel image is dropped, as cv2 does.  "4:2:2" is refused by name.
 """
 import ctypes as C
-import os
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import _cabi
-from . import png as _png
+from . import _cabi, _imwrite
 
 
 class JpegError(_cabi.EngineError):
@@ -187,26 +184,12 @@ def _quality(q):
     return int(q)
 
 
-def _per_image(value, n, what):
-    """One setting for all images, or a list with one per image."""
-    if isinstance(value, (list, tuple)):
-        if len(value) != n:
-            raise ValueError(f"{len(value)} {what} settings for {n} images")
-        return list(value)
-    return [value] * n
-
-
 def _fill(item, img, scale, rounding, bgr, what="image"):
-    if img.dtype not in _png._DTYPES:
-        raise JpegError(f"{what}: dtype must be uint8 or float32, got {img.dtype}")
-    return _png._fill(item, img, scale, rounding, bgr)
+    return _imwrite.fill_item(item, img, scale, rounding, bgr, error=JpegError, what=what)
 
 
 def _out(item, h, w, c, sub, lib, capacity=None):
-    cap = int(lib.thmr_jpeg_encode_bound(w, h, c, sub)) if capacity is None else int(capacity)
-    buf = np.empty(max(cap, 1), dtype=np.uint8)
-    item.out, item.capacity = buf.ctypes.data, cap
-    return buf
+    return _imwrite.out_buffer(item, lib.thmr_jpeg_encode_bound(w, h, c, sub) if capacity is None else capacity)
 
 
 def encode_host(img, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, capacity=None, lib=None):
@@ -241,22 +224,14 @@ class JpegEncoder(_cabi.Handle):
         list[bytes], in ONE batch call on the current stream.  quality (1 ... 100) and subsampling ("4:4:4", "4:2:0") hold for all
         images, or are lists with one entry per image.  bgr: the images hold B, G, R(, A) like cv2's; False: R, G, B(, A)."""
         n = len(images)
-        qs = [_quality(q) for q in _per_image(quality, n, "quality")]
-        subs = [_subsampling(s) for s in _per_image(subsampling, n, "subsampling")]
+        qs = [_quality(q) for q in _imwrite.per_image(quality, n, "quality settings")]
+        subs = [_subsampling(s) for s in _imwrite.per_image(subsampling, n, "subsampling settings")]
         if n == 0:
             return []
         items = (_cabi.PngItem * n)()
         keep, at, total = [], [], 0
         for i, img in enumerate(images):
-            if isinstance(img, np.ndarray):
-                if img.dtype == np.float64:
-                    img = img.astype(np.float32)
-                if img.dtype not in _png._DTYPES or _png._DTYPES[img.dtype] == _cabi.PNG_U16:
-                    raise (JpegUnsupported if img.dtype == np.uint16 else JpegError)(
-                        f"image {i}: dtype must be uint8 or float32, got {img.dtype}" + (" (16-bit samples are unsupported)" if img.dtype == np.uint16 else ""))
-                img = torch.from_numpy(np.ascontiguousarray(img))
-            if img.device != self.device:
-                img = img.to(self.device)
+            img = _imwrite.to_device_image(img, i, self.device, JpegError, JpegUnsupported)
             h, w, c = _fill(items[i], img, scale, rounding, bgr, f"image {i}")
             items[i].pixels = img.data_ptr()
             keep.append(img)
@@ -275,20 +250,11 @@ class JpegEncoder(_cabi.Handle):
         return [self._files[at[i]:at[i] + items[i].written].tobytes() for i in range(n)]
 
 
-_encoders = {}
-
-
-def _encoder(device):
-    device = _cabi.Handle.cuda_device(device, "imwrite needs a GPU device; encode_host() is the CPU encode", resolve=True)
-    if device not in _encoders:
-        _encoders[device] = JpegEncoder(device)
-    return _encoders[device]
+_encoders = _imwrite.encoders          # keyed (encoder class, device): png.py's live in the same cache
 
 
 def _check_path(path):
-    ext = os.path.splitext(os.fspath(path))[1]
-    if ext.lower() not in (".jpg", ".jpeg"):
-        raise ValueError(f"jpeg.imwrite writes .jpg / .jpeg files only, got extension {ext!r} ({os.fspath(path)!r})")
+    _imwrite.check_extension(path, (".jpg", ".jpeg"), "jpeg.imwrite")
 
 
 def _params_quality(params, quality):
@@ -310,23 +276,10 @@ def imwrite(path, img, params=None, *, quality=95, subsampling="4:2:0", scale=1.
     defaults are cv2's (quality 95, 4:2:0).  params=[cv2.IMWRITE_JPEG_QUALITY, q] is honoured; any other flag raises ValueError naming
     it, and so does any other extension.  A numpy array goes to `device` (default: the current GPU).  Returns True."""
     _check_path(path)
-    quality = _params_quality(params, quality)
-    data = _encoder(_png._device_of([img], device)).encode([img], quality=quality, subsampling=subsampling, scale=scale, rounding=rounding, bgr=bgr)[0]
-    _png._write(path, data)
-    return True
+    return imwrite_batch([path], [img], quality=_params_quality(params, quality), subsampling=subsampling, scale=scale, rounding=rounding, bgr=bgr, device=device)
 
 
 def imwrite_batch(paths, images, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, device=None, threads=None):
     """imwrite for many files: ONE device call for all images, then the files are written from a thread pool (at most png.WRITE_THREADS)."""
-    paths = list(paths)
-    if len(paths) != len(images):
-        raise ValueError(f"{len(paths)} paths for {len(images)} images")
-    for p in paths:
-        _check_path(p)
-    if not paths:
-        return True
-    files = _encoder(_png._device_of(images, device)).encode(list(images), quality=quality, subsampling=subsampling, scale=scale, rounding=rounding, bgr=bgr)
-    workers = max(1, min(_png.WRITE_THREADS if threads is None else int(threads), len(paths)))
-    with ThreadPoolExecutor(workers) as pool:
-        list(pool.map(_png._write, paths, files))
-    return True
+    return _imwrite.imwrite_batch(JpegEncoder, _check_path, paths, images, device, threads, quality=quality, subsampling=subsampling, scale=scale,
+                                  rounding=rounding, bgr=bgr)

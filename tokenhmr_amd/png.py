@@ -15,13 +15,11 @@ code where that is smaller (the pixels, the filters and the segments are the sam
 images and costs a second pass over the tokens).  Every entry takes the keyword; PNGEncoder.encode also takes one mode per image.
 """
 import ctypes as C
-import os
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
-from . import _cabi
+from . import _cabi, _imwrite
 
 
 class PngError(_cabi.EngineError):
@@ -33,13 +31,7 @@ class PngUnsupported(PngError):
 
 
 _BY_CODE = {_cabi.ERR_UNSUPPORTED: PngUnsupported}
-_ROUNDING = {"nearest": _cabi.PNG_ROUND_NEAREST, "trunc": _cabi.PNG_ROUND_TRUNC}
-_COMPRESSION = {"fixed": _cabi.PNG_FIXED, "dynamic": _cabi.PNG_DYNAMIC}
-_DTYPES = {torch.uint8: _cabi.PNG_U8, torch.float32: _cabi.PNG_F32, np.dtype(np.uint8): _cabi.PNG_U8, np.dtype(np.float32): _cabi.PNG_F32,
-           np.dtype(np.uint16): _cabi.PNG_U16}
-if hasattr(torch, "uint16"):
-    _DTYPES[torch.uint16] = _cabi.PNG_U16
-WRITE_THREADS = 16      # what one command gets on the GPU boxes, whatever os.cpu_count() says of the whole machine
+WRITE_THREADS = _imwrite.WRITE_THREADS
 
 
 def segment_bytes(lib=None):
@@ -53,34 +45,11 @@ def bound(width, height, channels, lib=None):
 
 def _fill(item, img, scale, rounding, bgr, compression="fixed"):
     """One image -> the fields of a thmr_png_item but the pointers; returns (height, width, channels) as the facade sees them."""
-    if rounding not in _ROUNDING:
-        raise ValueError(f"rounding must be 'nearest' or 'trunc', got {rounding!r}")
-    if not isinstance(compression, str) or compression not in _COMPRESSION:
-        raise ValueError(f"compression must be 'fixed' or 'dynamic', got {compression!r}")
-    if img.ndim == 2:
-        h, w = img.shape
-        c, sc = 1, 0
-        sy, sx = (img.stride() if isinstance(img, torch.Tensor) else [s // img.itemsize for s in img.strides])
-    elif img.ndim == 3:
-        h, w, c = img.shape
-        sy, sx, sc = (img.stride() if isinstance(img, torch.Tensor) else [s // img.itemsize for s in img.strides])
-    else:
-        raise ValueError(f"an image is (H, W) or (H, W, C), got shape {tuple(img.shape)}")
-    if img.dtype not in _DTYPES:
-        raise PngError(f"dtype must be uint8 or float32, got {img.dtype}")
-    item.dtype = _DTYPES[img.dtype]
-    item.width, item.height, item.channels = int(w), int(h), int(c)
-    item.stride_y, item.stride_x, item.stride_c = int(sy), int(sx), int(sc)
-    item.scale, item.rounding, item.swap_rb = float(scale), _ROUNDING[rounding], int(bool(bgr))
-    item.compression = _COMPRESSION[compression]
-    return int(h), int(w), int(c)
+    return _imwrite.fill_item(item, img, scale, rounding, bgr, compression, error=PngError)
 
 
 def _out(item, h, w, c, lib, capacity=None):
-    cap = bound(w, h, c, lib) if capacity is None else int(capacity)
-    buf = np.empty(max(cap, 1), dtype=np.uint8)
-    item.out, item.capacity = buf.ctypes.data, cap
-    return buf
+    return _imwrite.out_buffer(item, bound(w, h, c, lib) if capacity is None else capacity)
 
 
 def encode_host(img, *, scale=1.0, rounding="nearest", bgr=True, compression="fixed", capacity=None, lib=None):
@@ -111,28 +80,15 @@ class PNGEncoder(_cabi.Handle):
         list[bytes], in ONE batch call on the current stream.  bgr: the images hold B, G, R(, A) like cv2's; False: R, G, B(, A).
         compression: "fixed" or "dynamic" for all images, or a list with one of them per image."""
         n = len(images)
-        if isinstance(compression, str):
-            modes = [compression] * n
-        elif isinstance(compression, (list, tuple)):
-            modes = list(compression)
-        else:
+        if not isinstance(compression, (str, list, tuple)):
             raise ValueError(f"compression must be 'fixed', 'dynamic' or a list of them, one per image, got {compression!r}")
-        if len(modes) != n:
-            raise ValueError(f"{len(modes)} compression modes for {n} images")
+        modes = _imwrite.per_image(compression, n, "compression modes")
         if n == 0:
             return []
         items = (_cabi.PngItem * n)()
         keep, bufs = [], []
         for i, img in enumerate(images):
-            if isinstance(img, np.ndarray):
-                if img.dtype == np.float64:          # what 255 * img gives in demo.py; the device reads float32
-                    img = img.astype(np.float32)
-                if img.dtype not in _DTYPES or _DTYPES[img.dtype] == _cabi.PNG_U16:
-                    raise (PngUnsupported if img.dtype == np.uint16 else PngError)(
-                        f"image {i}: dtype must be uint8 or float32, got {img.dtype}" + (" (16-bit samples are unsupported)" if img.dtype == np.uint16 else ""))
-                img = torch.from_numpy(np.ascontiguousarray(img))
-            if img.device != self.device:
-                img = img.to(self.device)
+            img = _imwrite.to_device_image(img, i, self.device, PngError, PngUnsupported)
             h, w, c = _fill(items[i], img, scale, rounding, bgr, compression=modes[i])
             items[i].pixels = img.data_ptr()
             keep.append(img)
@@ -144,57 +100,20 @@ class PNGEncoder(_cabi.Handle):
         return [bufs[i][:items[i].written].tobytes() for i in range(n)]
 
 
-_encoders = {}
-
-
-def _encoder(device):
-    device = _cabi.Handle.cuda_device(device, "imwrite needs a GPU device; encode_host() is the CPU encode", resolve=True)
-    if device not in _encoders:
-        _encoders[device] = PNGEncoder(device)
-    return _encoders[device]
+_encoders = _imwrite.encoders          # keyed (encoder class, device): jpeg.py's live in the same cache
 
 
 def _check_path(path):
-    ext = os.path.splitext(os.fspath(path))[1]
-    if ext.lower() != ".png":
-        raise ValueError(f"imwrite writes .png files only, got extension {ext!r} ({os.fspath(path)!r})")
-
-
-def _device_of(images, device):
-    if device is not None:
-        return device
-    for img in images:
-        if isinstance(img, torch.Tensor) and img.device.type == "cuda":
-            return img.device
-    return "cuda"
-
-
-def _write(path, data):
-    with open(path, "wb") as f:
-        f.write(data)
+    _imwrite.check_extension(path, (".png",), "imwrite")
 
 
 def imwrite(path, img, params=None, *, scale=1.0, rounding="nearest", bgr=True, compression="fixed", device=None):
     """cv2.imwrite for .png: a device tensor or a numpy array, (H, W) or (H, W, C), channels in cv2's B, G, R(, A) order.  params is
     accepted and ignored (cv2's compression level has no counterpart; `compression` chooses between the two block kinds).  A numpy
     array goes to `device` (default: the current GPU).  Returns True; raises ValueError naming the extension for anything but .png."""
-    _check_path(path)
-    data = _encoder(_device_of([img], device)).encode([img], scale=scale, rounding=rounding, bgr=bgr, compression=compression)[0]
-    _write(path, data)
-    return True
+    return imwrite_batch([path], [img], scale=scale, rounding=rounding, bgr=bgr, compression=compression, device=device)
 
 
 def imwrite_batch(paths, images, *, scale=1.0, rounding="nearest", bgr=True, compression="fixed", device=None, threads=None):
     """imwrite for many files: ONE device call for all images, then the files are written from a thread pool (at most WRITE_THREADS)."""
-    paths = list(paths)
-    if len(paths) != len(images):
-        raise ValueError(f"{len(paths)} paths for {len(images)} images")
-    for p in paths:
-        _check_path(p)
-    if not paths:
-        return True
-    files = _encoder(_device_of(images, device)).encode(list(images), scale=scale, rounding=rounding, bgr=bgr, compression=compression)
-    workers = max(1, min(WRITE_THREADS if threads is None else int(threads), len(paths)))
-    with ThreadPoolExecutor(workers) as pool:
-        list(pool.map(_write, paths, files))
-    return True
+    return _imwrite.imwrite_batch(PNGEncoder, _check_path, paths, images, device, threads, scale=scale, rounding=rounding, bgr=bgr, compression=compression)
