@@ -925,28 +925,64 @@ int  thmr_png_encode_batch(thmr_png* p, thmr_png_item* items_host, int32_t n, vo
  *   entropy       the Annex K Huffman tables, no optimisation pass, no restart markers: DC difference by category, AC as (run, size) with
  *                 ZRL 0xF0 and EOB 0x00, a negative value sends the low bits of v - 1; bits MSB first, every 0xFF followed by 0x00, the
  *                 last byte padded with ones (and stuffed if that makes it 0xFF).
+ *   optimised     the flag THMR_JPEG_OPTIMIZE (the *_flags entry points; libjpeg's optimize_coding, Pillow's optimize=True, cv2's
+ *                 IMWRITE_JPEG_OPTIMIZE) keeps everything up to the quantised blocks and codes the scan with tables made from the image's
+ *                 own statistics; the file is again Pillow's, byte for byte.  Every symbol the scan codes is counted, the DC 0 + EOB of
+ *                 the dummy blocks included, into one histogram per table in use (DC0, AC0 and, with three components, DC1, AC1: the
+ *                 components use the tables 0, 1, 1 as in the header).  A table is jpeg_gen_optimal_table's (csrc/jpegenc_math.h): the
+ *                 symbols in use and a pseudo-symbol 256 of frequency 1, which keeps the all-ones code unused; the two least frequent
+ *                 entries are merged until one is left, among equal frequencies the larger symbol first; code sizes, which may pass 16,
+ *                 are limited to 16 by libjpeg's adjustment of the counts per length; the pseudo-symbol's count leaves the longest length
+ *                 in use; the symbols are listed by their size before the limit, then by value, and take canonical codes (Annex C).
+ *                 Pillow's bytes are the arbiter of every detail: where this text and Pillow disagree, Pillow wins (the tests hold the
+ *                 files and the DHT payloads to Pillow's).  The markers stay the same, only the DHT contents and lengths and the scan
+ *                 bits change.  An optimised image has at most 2^23 blocks (every frequency sum stays below libjpeg's 10^9).
  *   container     SOI; APP0 JFIF 1.01, units 0, density 1 x 1; one DQT per table (0, then 1; 8-bit, zigzag); SOF0 with components 1 / 2 /
  *                 3 at 0x22 or 0x11, 0x11, 0x11 and tables 0, 1, 1; one DHT per table in the order DC0, AC0, DC1, AC1; SOS with selectors
  *                 0x00, 0x11, 0x11, Ss 0, Se 63, Ah/Al 0; the scan; EOI.  Grey has one component, table 0, DC0 and AC0 only.
  *   refused       before any HIP call, the message names the item: THMR_ERR_UNSUPPORTED for a 16-bit dtype, 2 channels and
  *                 THMR_JPEG_422; THMR_ERR_INVALID for a quality outside 1 ... 100, width or height < 1 or > 65535, any other dtype /
- *                 channel count / rounding / subsampling, compression != 0, a null pointer, and a capacity below thmr_jpeg_encode_bound(). */
+ *                 channel count / rounding / subsampling, compression != 0, a null pointer, a capacity below thmr_jpeg_encode_bound()
+ *                 (thmr_jpeg_encode_bound_flags() for a flagged item), an unknown flag bit, and more than 2^23 blocks with the flag. */
 enum { THMR_JPEG_444 = 0, THMR_JPEG_422 = 1 /* refused by name */, THMR_JPEG_420 = 2 };
+enum { THMR_JPEG_OPTIMIZE = 1 };        /* a flag bit of the *_flags entry points; every other bit is refused */
 /* The largest file: every block of every MCU at its worst case — 22 bits of DC (an 11-bit code + 11 value bits) and 63 x (16 + 10) bits
  * of AC = 1660 bits — rounded up to bytes, TWICE that (each byte may be 0xFF and draw a 0x00), the header (623 bytes, grey 328) and
  * EOI.  0 for arguments the encoder refuses. */
 int64_t thmr_jpeg_encode_bound(int32_t width, int32_t height, int32_t channels, int32_t subsampling);
 int thmr_jpeg_encode_host(thmr_png_item* item, int32_t quality, int32_t subsampling);
+/* The bound of a mode.  The choice between a second bound and a proof that the first holds went to the bound: with THMR_JPEG_OPTIMIZE a
+ * DC table has up to 12 symbols and the pseudo-symbol, so a DC code can take 12 bits and a block 23 + 63 x 26 = 1661; an optimised table
+ * has no more symbols than an Annex K one, so the header is no longer.  Capacity checks, the unstuffed scratch and the staging of a
+ * flagged item are sized from it.  Flags 0: thmr_jpeg_encode_bound.  0 for arguments the encoder refuses, an unknown flag bit included. */
+int64_t thmr_jpeg_encode_bound_flags(int32_t width, int32_t height, int32_t channels, int32_t subsampling, int32_t flags);
+/* thmr_jpeg_encode_host with flags (0: the same file). */
+int thmr_jpeg_encode_host_flags(thmr_png_item* item, int32_t quality, int32_t subsampling, int32_t flags);
+/* The Huffman table of the optimised mode for the frequencies freq[0 ... 255] by symbol, the very routine the table kernel runs: bits[1
+ * ... 16] the codes per length, bits[0] the longest code size BEFORE the limit to 16 (above 16: the adjustment ran), huffval[0 ... *nsym)
+ * the symbols in code order (256 bytes of room).  Host only.  THMR_ERR_INVALID for a null pointer, a negative frequency, an all-zero
+ * histogram or a sum above 10^9; THMR_ERR_UNSUPPORTED for frequencies that give a size above 32 (libjpeg refuses them too). */
+int thmr_jpeg_optimal_table(const int32_t* freq, uint8_t* bits, uint8_t* huffval, int32_t* nsym);
+/* The statistics the optimised encode of this item builds its tables from: freq[t * 256 + symbol] for the tables t = 0 ... 3 in the
+ * order DC0, AC0, DC1, AC1 (1024 entries; grey leaves DC1 and AC1 zero).  Host only; the item's `out` is not touched. */
+int thmr_jpeg_histogram_host(const thmr_png_item* item, int32_t quality, int32_t subsampling, int32_t* freq);
 /* The handle owns grow-only device scratch (coefficients, bit counts, the unstuffed scans) and pinned staging that the device writes the
  * finished scans into.  One call encodes n images of n sizes, layouts, qualities and samplings with ONE descriptor upload and a fixed
  * number of launches (transform; count; two scans; pack; the 0xFF count, its scan and the scatter), synchronises `stream` ONCE, at the
- * end, and returns with the complete files at every item's `out`.  Not inside a stream capture (THMR_ERR_STATE). */
+ * end, and returns with the complete files at every item's `out`.  Not inside a stream capture (THMR_ERR_STATE).
+ * thmr_jpeg_encode_batch_flags takes one flag word per item; flagged and unflagged items share the ONE call, upload and synchronisation.
+ * Flagged items add two launches, whatever n: the symbol histogram (LDS per workgroup, integer atomics into the image's histograms,
+ * which are zeroed on the stream by every call) and the table build (one wave per image and table), whose code words the count and pack
+ * kernels then read for that image, chosen per workgroup; bits and huffval come back with the scans and the host writes the DHT segments.
+ * A call without a flagged item launches what thmr_jpeg_encode_batch launches. */
 typedef struct thmr_jpeg_encoder thmr_jpeg_encoder;
 int  thmr_jpeg_encoder_create(int32_t device, thmr_jpeg_encoder** out);
 void thmr_jpeg_encoder_destroy(thmr_jpeg_encoder* e);
 const char* thmr_jpeg_encoder_last_error(const thmr_jpeg_encoder* e);
 int  thmr_jpeg_encode_batch(thmr_jpeg_encoder* e, thmr_png_item* items_host, const int32_t* qualities, const int32_t* subsamplings, int32_t n,
                             void* stream);
+int  thmr_jpeg_encode_batch_flags(thmr_jpeg_encoder* e, thmr_png_item* items_host, const int32_t* qualities, const int32_t* subsamplings,
+                                  const int32_t* flags, int32_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -115,6 +115,7 @@ PNG_U8, PNG_F32, PNG_U16 = 0, 1, 2                  # header: THMR_PNG_*
 PNG_ROUND_NEAREST, PNG_ROUND_TRUNC = 0, 1           # header: THMR_PNG_ROUND_*
 PNG_FIXED, PNG_DYNAMIC = 0, 1                       # header: THMR_PNG_FIXED / _DYNAMIC
 JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2              # header: THMR_JPEG_* (thmr_jpeg_encode_*; 4:2:2 is refused by name)
+JPEG_OPTIMIZE = 1                                   # header: THMR_JPEG_OPTIMIZE, the flag bit of thmr_jpeg_encode_*_flags
 
 
 class JpegItem(C.Structure):

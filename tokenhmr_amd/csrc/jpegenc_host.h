@@ -1,4 +1,5 @@
-// The host half of the baseline JPEG encoder (include/tokenhmr_hip.h): argument checks, the quantisation and Huffman tables, the
+// The host half of the baseline JPEG encoder (include/tokenhmr_hip.h): argument checks, the quantisation and Huffman tables (Annex K,
+// or the image's own with THMR_JPEG_OPTIMIZE), the
 // container (SOI, APP0, DQT, SOF0, DHT, SOS ... EOI), and the whole encode on the CPU with the arithmetic of jpegenc_math.h — the oracle
 // of the kernels, and what a caller without a device gets.  Host only, no HIP call.
 #pragma once
@@ -69,20 +70,26 @@ inline int64_t blocks(int32_t w, int32_t h, int32_t c, int32_t sub) {
     return ((w + m - 1) / m) * ((h + m - 1) / m) * (c == 1 ? 1 : s ? 6 : 3);
 }
 
-// Bytes the unstuffed scan of `nblk` blocks can take: every block at MAX_BLOCK_BITS, and the padding to the byte.
-inline int64_t scan_bytes_max(int64_t nblk) { return (nblk * jpegem::MAX_BLOCK_BITS + 7) / 8; }
+// Bytes the unstuffed scan of `nblk` blocks can take: every block at MAX_BLOCK_BITS (MAX_BLOCK_BITS_OPT with the image's own tables),
+// and the padding to the byte.
+inline int64_t scan_bytes_max(int64_t nblk, int32_t flags = 0) {
+    return (nblk * ((flags & THMR_JPEG_OPTIMIZE) ? jpegem::MAX_BLOCK_BITS_OPT : jpegem::MAX_BLOCK_BITS) + 7) / 8;
+}
 
 // The worst case: a block takes at most MAX_BLOCK_BITS = 22 bits of DC (the longest DC code, 11 bits, with 11 value bits; luma's is
 // 9 + 11) and 63 x (16 + 10) bits of AC, every MCU block counted as such (a dummy takes 6); each byte of the scan may be 0xFF and draw
-// a zero byte behind it; then the header and EOI.
-inline int64_t bound(int32_t w, int32_t h, int32_t c, int32_t sub) {
+// a zero byte behind it; then the header and EOI.  An optimised table has at most the 12 / 162 symbols of an Annex K one, so its DHT
+// segment is no longer and header_bytes holds; its DC code can take 12 bits (12 symbols and the pseudo-symbol), one more per block.
+inline int64_t bound(int32_t w, int32_t h, int32_t c, int32_t sub, int32_t flags = 0) {
     if (w < 1 || h < 1 || w > 65535 || h > 65535 || (c != 1 && c != 3 && c != 4) || (sub != THMR_JPEG_444 && sub != THMR_JPEG_420)) return 0;
-    return header_bytes(c == 1 ? 1 : 3) + 2 * scan_bytes_max(blocks(w, h, c, sub)) + 2;
+    if (flags & ~THMR_JPEG_OPTIMIZE) return 0;
+    return header_bytes(c == 1 ? 1 : 3) + 2 * scan_bytes_max(blocks(w, h, c, sub), flags) + 2;
 }
 
 // 0, or the status with the reason in err.  Pointers and capacity included.
-inline int check_item(const thmr_png_item& it, int32_t quality, int32_t sub, std::string& err) {
+inline int check_item(const thmr_png_item& it, int32_t quality, int32_t sub, std::string& err, int32_t flags = 0) {
     if (const int rc = imgitem::check_source(it, "reads", err)) return rc;
+    if (flags & ~THMR_JPEG_OPTIMIZE) { err = "unknown flag bits " + std::to_string(flags & ~THMR_JPEG_OPTIMIZE) + " (THMR_JPEG_OPTIMIZE is the one flag)"; return THMR_ERR_INVALID; }
     if (sub == THMR_JPEG_422) { err = "unsupported: 4:2:2 subsampling (THMR_JPEG_422); the encoder writes 4:4:4 and 4:2:0"; return THMR_ERR_UNSUPPORTED; }
     if (sub != THMR_JPEG_444 && sub != THMR_JPEG_420) { err = "subsampling must be THMR_JPEG_444 or THMR_JPEG_420, got " + std::to_string(sub); return THMR_ERR_INVALID; }
     if (quality < 1 || quality > 100) { err = "quality must be 1 ... 100, got " + std::to_string(quality); return THMR_ERR_INVALID; }
@@ -92,7 +99,11 @@ inline int check_item(const thmr_png_item& it, int32_t quality, int32_t sub, std
     }
     if (it.rounding != THMR_PNG_ROUND_NEAREST && it.rounding != THMR_PNG_ROUND_TRUNC) { err = "rounding must be THMR_PNG_ROUND_NEAREST or _TRUNC"; return THMR_ERR_INVALID; }
     if (it.compression != 0) { err = "compression must be 0 for a JPEG item, got " + std::to_string(it.compression); return THMR_ERR_INVALID; }
-    return imgitem::check_buffers(it, bound(it.width, it.height, it.channels, sub), "thmr_jpeg_encode_bound", err);
+    if (flags && blocks(it.width, it.height, it.channels, sub) > jpegem::OPT_MAX_BLOCKS) {
+        err = "optimised coding takes an image of at most 2^23 blocks, got " + std::to_string(blocks(it.width, it.height, it.channels, sub));
+        return THMR_ERR_INVALID;
+    }
+    return imgitem::check_buffers(it, bound(it.width, it.height, it.channels, sub, flags), flags ? "thmr_jpeg_encode_bound_flags" : "thmr_jpeg_encode_bound", err);
 }
 
 // q[cls * 64 + zigzag position] for `quality`.
@@ -101,8 +112,9 @@ inline void quant_tables(int quality, uint16_t* q) {
         for (int k = 0; k < 64; ++k) q[cls * 64 + jpegem::zigzag_of_natural(k)] = (uint16_t)jpegem::quant_entry(cls, k, quality);
 }
 
-// Everything before the scan; returns its length (header_bytes).
-inline int64_t write_header(uint8_t* out, const jpegem::Frame& f, const uint16_t* q) {
+// Everything before the scan; returns its length (header_bytes, or less with the image's own tables).  opt: null for the Annex K
+// tables, else the image's tables [cls * 2 + ac].
+inline int64_t write_header(uint8_t* out, const jpegem::Frame& f, const uint16_t* q, const jpegem::OptimalTable* opt = nullptr) {
     uint8_t* p = out;
     auto marker = [&](int m, int len) { *p++ = 0xFF; *p++ = (uint8_t)m; *p++ = (uint8_t)(len >> 8); *p++ = (uint8_t)len; };
     *p++ = 0xFF; *p++ = 0xD8;
@@ -123,10 +135,11 @@ inline int64_t write_header(uint8_t* out, const jpegem::Frame& f, const uint16_t
     for (int cls = 0; cls < ncls; ++cls)
         for (int ac = 0; ac < 2; ++ac) {
             const HuffSpec& s = huff_spec(cls, ac);
-            marker(0xC4, 2 + 1 + 16 + s.n);
+            const int n = opt ? opt[cls * 2 + ac].nsym : s.n;
+            marker(0xC4, 2 + 1 + 16 + n);
             *p++ = (uint8_t)(ac << 4 | cls);
-            memcpy(p, s.bits, 16); p += 16;
-            memcpy(p, s.vals, (size_t)s.n); p += s.n;
+            memcpy(p, opt ? opt[cls * 2 + ac].bits + 1 : s.bits, 16); p += 16;
+            memcpy(p, opt ? opt[cls * 2 + ac].huffval : s.vals, (size_t)n); p += n;
         }
     marker(0xDA, 6 + 2 * f.ncomp);
     *p++ = (uint8_t)f.ncomp;
@@ -148,13 +161,9 @@ struct BitWriter {
     void pad() { if (n) (*this)((1u << (8 - n)) - 1, 8 - n); }
 };
 
-// The whole file on the CPU.  The item is already checked.
-inline void encode(thmr_png_item& it, int32_t quality, int32_t sub) {
-    const jpegem::Frame f = jpegem::frame_of(image_of(it), sub == THMR_JPEG_420);
-    uint16_t q[128];
-    quant_tables(quality, q);
-    const uint32_t* codes = code_tables().t;
-    BitWriter bw{it.out + write_header(it.out, f, q)};
+// Every block of the scan in order through fn(cls, dummy, zz, diff): the transform and the DC prediction of the CPU encode.
+template <typename Fn>
+inline void for_each_block(const jpegem::Frame& f, const void* pixels, const uint16_t* q, Fn&& fn) {
     int16_t zz[64];
     int pred[3] = {0, 0, 0};
     for (int my = 0; my < f.mcuy; ++my)
@@ -164,14 +173,69 @@ inline void encode(thmr_png_item& it, int32_t quality, int32_t sub) {
                 bool dummy;
                 jpegem::block_place(f, mx, my, k, comp, bx, by, dummy);
                 const int cls = comp ? 1 : 0;
-                if (dummy) { jpegem::code_dummy(codes + cls * jpegem::TABLE_WORDS, bw); continue; }
-                jpegem::forward_block(f, it.pixels, comp, bx, by, q + cls * 64, zz);
-                jpegem::code_block(zz, zz[0] - pred[comp], codes + cls * jpegem::TABLE_WORDS, bw);
+                if (dummy) { fn(cls, true, zz, 0); continue; }
+                jpegem::forward_block(f, pixels, comp, bx, by, q + cls * 64, zz);
+                fn(cls, false, zz, zz[0] - pred[comp]);
                 pred[comp] = zz[0];
             }
+}
+
+// The statistics of the optimised mode: hist[cls * TABLE_WORDS + slot] counts what the scan codes, the dummy blocks included.
+inline void histogram(const thmr_png_item& it, int32_t quality, int32_t sub, int32_t* hist) {
+    const jpegem::Frame f = jpegem::frame_of(image_of(it), sub == THMR_JPEG_420);
+    uint16_t q[128];
+    quant_tables(quality, q);
+    memset(hist, 0, sizeof(int32_t) * 2 * jpegem::TABLE_WORDS);
+    for_each_block(f, it.pixels, q, [&](int cls, bool dummy, const int16_t* zz, int diff) {
+        auto count = [&](int slot, uint32_t, int) { ++hist[cls * jpegem::TABLE_WORDS + slot]; };
+        if (dummy) jpegem::walk_dummy(count); else jpegem::walk_block(zz, diff, count);
+    });
+}
+
+// One table on the CPU, the routine of the table kernel with its steps in order.  nhist: 16 (a DC slot) or 256.  slot: null, or where
+// the table's code words go (zeroed before).
+inline void optimal_table(const int32_t* hist, int nhist, jpegem::OptimalTable& out, uint32_t* slot = nullptr) {
+    jpegem::OptimalWork w;
+    jpegem::SerialPar par;
+    memset(&out, 0, sizeof(out));
+    jpegem::optimal_table(hist, nhist, w, par, &out);
+    if (slot) jpegem::code_words(out, w, par, slot);
+}
+
+// The whole file on the CPU.  The item is already checked.  With THMR_JPEG_OPTIMIZE the blocks are walked twice (statistics, then the
+// coding with the image's own tables: the transform runs again rather than keeping every coefficient); 0, or THMR_ERR_UNSUPPORTED
+// for statistics that give a code of more than 32 bits before the limit (libjpeg refuses them too).
+inline int encode(thmr_png_item& it, int32_t quality, int32_t sub, int32_t flags, std::string& err) {
+    const jpegem::Frame f = jpegem::frame_of(image_of(it), sub == THMR_JPEG_420);
+    uint16_t q[128];
+    quant_tables(quality, q);
+    const uint32_t* codes = code_tables().t;
+    std::vector<uint32_t> own;
+    jpegem::OptimalTable opt[4];
+    if (flags & THMR_JPEG_OPTIMIZE) {
+        std::vector<int32_t> hist(2 * jpegem::TABLE_WORDS);
+        histogram(it, quality, sub, hist.data());
+        own.assign(2 * jpegem::TABLE_WORDS, 0);
+        for (int cls = 0; cls < (f.ncomp == 1 ? 1 : 2); ++cls)
+            for (int ac = 0; ac < 2; ++ac) {
+                jpegem::OptimalTable& t = opt[cls * 2 + ac];
+                optimal_table(hist.data() + cls * jpegem::TABLE_WORDS + ac * 16, ac ? 256 : 16, t, own.data() + cls * jpegem::TABLE_WORDS + ac * 16);
+                if (t.nsym < 0) { err = "unsupported: the image's statistics give a Huffman code of more than 32 bits before the limit"; return THMR_ERR_UNSUPPORTED; }
+            }
+        codes = own.data();
+    }
+    BitWriter bw{it.out + write_header(it.out, f, q, (flags & THMR_JPEG_OPTIMIZE) ? opt : nullptr)};
+    for_each_block(f, it.pixels, q, [&](int cls, bool dummy, const int16_t* zz, int diff) {
+        if (dummy) jpegem::code_dummy(codes + cls * jpegem::TABLE_WORDS, bw); else jpegem::code_block(zz, diff, codes + cls * jpegem::TABLE_WORDS, bw);
+    });
     bw.pad();
     *bw.p++ = 0xFF; *bw.p++ = 0xD9;
     it.written = bw.p - it.out;
+    return 0;
+}
+inline void encode(thmr_png_item& it, int32_t quality, int32_t sub) {
+    std::string err;
+    encode(it, quality, sub, 0, err);
 }
 
 }  // namespace jpegeh

@@ -1,9 +1,15 @@
 // The arithmetic and the coding rules of the baseline JPEG encoder, shared by the kernels (jpegenc.hip) and the CPU encode
 // (jpegenc_host.h): libjpeg's default compression pipeline restated in integers — jccolor.c's 16-bit fixed-point RGB -> YCbCr, the h2v2
 // box downsampler with its alternating bias and libjpeg's edge expansion, jfdctint.c (JDCT_ISLOW, the constants of jpeg_math.h),
-// quantisation by 8 q with halves away from zero, and the Huffman coding of a block with the Annex K tables.  The samples come from
-// imgsrc::sample (image_source.h), the one pixel conversion of both encoders.  Everything is integer, so both sides give the same bytes.
-// Compiles with or without HIP.
+// quantisation by 8 q with halves away from zero, and the Huffman coding of a block with the Annex K tables — or, for an image flagged
+// THMR_JPEG_OPTIMIZE, with tables made from that image's own symbol statistics as libjpeg's optimize_coding makes them (the symbol
+// walk, the table routine and its rule are at the end of this file).  The samples come from imgsrc::sample (image_source.h), the one
+// pixel conversion of both encoders.  Everything is integer, so both sides give the same bytes.  Compiles with or without HIP.
+//
+// The bound of the optimised mode: of the two ways — a second bound, or a proof that the first holds — the second bound was chosen
+// (thmr_jpeg_encode_bound_flags).  A DC table of an image's own has up to 12 symbols and the pseudo-symbol, so a DC code can take 12
+// bits where Annex K's longest takes 11: MAX_BLOCK_BITS_OPT = MAX_BLOCK_BITS + 1.  An AC code stays within 16 bits by the limit, and
+// such a table has no more symbols than an Annex K one (12 / 162), so the header is no longer.
 #pragma once
 #include <stdint.h>
 
@@ -12,7 +18,7 @@
 
 namespace jpegem {
 
-constexpr int MAX_BLOCK_BITS = (11 + 11) + 63 * (16 + 10);      // the longest DC code (chroma category 11) + its bits, 63 x the longest AC code + 10 bits
+constexpr int MAX_BLOCK_BITS = (11 + 11) + 63 * (16 + 10);      // Annex K: the longest DC code (chroma category 11) + its bits, 63 x the longest AC code + 10 bits
 constexpr int TABLE_WORDS = 16 + 256;                           // one class's codes: DC categories 0 ... 11, then AC (run << 4 | size) at 16 +
 constexpr int EOB = 0x00, ZRL = 0xF0;
 
@@ -178,14 +184,14 @@ JPEG_HD int category(int v) {
     return a ? 32 - __builtin_clz(a) : 0;
 }
 
-// The codes of one block, in order, through emit(bits, count): each call carries one Huffman code with the value bits behind it, at
-// most 26 bits.  zz: the coefficients in zigzag order (zz[0] is not read: diff is the DC difference); table: the class's TABLE_WORDS
-// entries code | length << 16.  A negative value sends the low bits of v - 1.
-template <typename Emit>
-JPEG_HD void code_block(const int16_t* zz, int diff, const uint32_t* table, Emit&& emit) {
+// The symbols of one block, in order, through visit(slot, value bits, count of value bits): slot is the symbol's place in a class's
+// TABLE_WORDS entries — the DC category 0 ... 11, or 16 + (run << 4 | size), 16 + ZRL, 16 + EOB.  zz: the coefficients in zigzag order
+// (zz[0] is not read: diff is the DC difference).  A negative value sends the low bits of v - 1.  Counting (the statistics of the
+// optimised mode) and coding both go through this walk, so they visit exactly the same symbols.
+template <typename Visit>
+JPEG_HD void walk_block(const int16_t* zz, int diff, Visit&& visit) {
     int s = category(diff);
-    uint32_t e = table[s];
-    emit(((e & 0xFFFFu) << s) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1)), (int)(e >> 16) + s);
+    visit(s, (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
     int run = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll          // the coefficients stay in registers
@@ -193,20 +199,164 @@ JPEG_HD void code_block(const int16_t* zz, int diff, const uint32_t* table, Emit
     for (int k = 1; k < 64; ++k) {
         const int v = zz[k];
         if (v == 0) { ++run; continue; }
-        for (; run > 15; run -= 16) { e = table[16 + ZRL]; emit(e & 0xFFFFu, (int)(e >> 16)); }
+        for (; run > 15; run -= 16) visit(16 + ZRL, 0u, 0);
         s = category(v);
-        e = table[16 + (run << 4 | s)];
-        emit(((e & 0xFFFFu) << s) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1)), (int)(e >> 16) + s);
+        visit(16 + (run << 4 | s), (uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
         run = 0;
     }
-    if (run > 0) { e = table[16 + EOB]; emit(e & 0xFFFFu, (int)(e >> 16)); }
+    if (run > 0) visit(16 + EOB, 0u, 0);
 }
 
-// A dummy block: difference 0, then the end-of-block.
+// A dummy block: difference 0, then the end-of-block.  It is coded, so it is counted.
+template <typename Visit>
+JPEG_HD void walk_dummy(Visit&& visit) {
+    visit(0, 0u, 0);
+    visit(16 + EOB, 0u, 0);
+}
+
+// The codes of one block, in order, through emit(bits, count): each call carries one Huffman code with the value bits behind it, at
+// most 26 bits (16 + 10 for an AC symbol, 12 + 11 for a DC category of an optimised table).  table: the class's TABLE_WORDS entries
+// code | length << 16.
+template <typename Emit>
+JPEG_HD void code_block(const int16_t* zz, int diff, const uint32_t* table, Emit&& emit) {
+    walk_block(zz, diff, [&](int slot, uint32_t value, int s) {
+        const uint32_t e = table[slot];
+        emit(((e & 0xFFFFu) << s) | value, (int)(e >> 16) + s);
+    });
+}
+
 template <typename Emit>
 JPEG_HD void code_dummy(const uint32_t* table, Emit&& emit) {
-    emit(table[0] & 0xFFFFu, (int)(table[0] >> 16));
-    emit(table[16 + EOB] & 0xFFFFu, (int)(table[16 + EOB] >> 16));
+    walk_dummy([&](int slot, uint32_t, int) { emit(table[slot] & 0xFFFFu, (int)(table[slot] >> 16)); });
+}
+
+// ---- optimised coding: the tables of ONE image from its own symbol statistics (libjpeg's optimize_coding) ----
+//
+// jpeg_gen_optimal_table (jchuff.c) restated.  The symbols in use (frequency > 0) are taken in symbol order, and a pseudo-symbol 256
+// with frequency 1 is put behind them, which keeps the all-ones code unused.  The two least frequent entries are merged until one is
+// left; among equal frequencies the LARGER symbol is taken first (so the pseudo-symbol wins every tie), the first of the two keeps the
+// sum.  A symbol's code size is the number of merges its tree took part in; it can reach 32 and more.  The sizes above 16 are then
+// brought down by libjpeg's adjustment of the COUNTS per length (from 32 down to 17: two symbols of length i leave, one goes to i - 1,
+// and a symbol of the longest length j <= i - 2 in use becomes the prefix of two of length j + 1), and one count is taken from the
+// longest length in use for the pseudo-symbol.  huffval lists the real symbols by their size BEFORE the adjustment, then by symbol
+// value; canonical codes (Annex C) go to them in that order.  Pillow's bytes (libjpeg-turbo) are the arbiter of every detail here:
+// tests/test_jpeg_enc_optimize_host.py holds the files and the DHT payloads to them, and where this text and Pillow ever disagree,
+// Pillow is right.
+//
+// The routine is written once, over a `Par` that says how its four kinds of step run: one(f) — f() once; each(n, f) — f(i) for every
+// i < n, in any order; compact(n, pred, put) — put(i, p) for every i < n with pred(i), p counting them in the order of i, and their
+// number; min2(n, key, k1, k2) — the two smallest of the distinct keys key(i).  SerialPar runs them in order on one
+// thread (thmr_jpeg_optimal_table, the host encode); the table kernel runs them on one wave (jpegenc.hip).  Neither changes a result.
+constexpr int OPT_SYMBOLS = 257, OPT_MAX_CLEN = 32;
+constexpr int32_t OPT_MERGED = 1000000001;                     // the frequency of an entry that was merged away: above every real sum
+constexpr uint64_t OPT_NO_KEY = ~(uint64_t)0;
+constexpr int64_t OPT_MAX_BLOCKS = (int64_t)1 << 23;           // 64 symbols a block at the most: every sum stays below 10^9, as libjpeg needs
+constexpr int MAX_BLOCK_BITS_OPT = (12 + 11) + 63 * (16 + 10); // 12 DC symbols and the pseudo-symbol: a DC code can take 12 bits
+
+struct OptimalWork {
+    int32_t freq[OPT_SYMBOLS], root[OPT_SYMBOLS], codesize[OPT_SYMBOLS], sym[OPT_SYMBOLS];
+};
+
+// What a table kernel or a caller gets back: bits[0] is the longest code size BEFORE the limit (above 16: the adjustment ran), bits[1
+// ... 16] the codes per length, huffval the nsym symbols in code order.  nsym < 0: a size above 32, which libjpeg refuses as well.
+struct OptimalTable {
+    uint8_t bits[17];
+    uint8_t pad[3];
+    int32_t nsym;
+    uint8_t huffval[256];
+};
+static_assert(sizeof(OptimalTable) == 280, "the tables lie in an array, device and host");
+
+struct SerialPar {
+    template <typename F> void one(F&& f) { f(); }
+    template <typename F> void each(int n, F&& f) { for (int i = 0; i < n; ++i) f(i); }
+    template <typename Pred, typename Put> int compact(int n, Pred&& pred, Put&& put) {
+        int p = 0;
+        for (int i = 0; i < n; ++i)
+            if (pred(i)) put(i, p++);
+        return p;
+    }
+    template <typename Key> void min2(int n, Key&& key, uint64_t& k1, uint64_t& k2) {
+        k1 = k2 = OPT_NO_KEY;
+        for (int i = 0; i < n; ++i) {
+            const uint64_t k = key(i);
+            if (k < k1) { k2 = k1; k1 = k; } else if (k < k2) k2 = k;
+        }
+    }
+};
+
+// hist[0 ... nhist): the frequencies by symbol (nhist <= 256, none negative).  out is written inside one().
+template <typename Par>
+JPEG_HD void optimal_table(const int32_t* hist, int nhist, OptimalWork& w, Par& par, OptimalTable* out) {
+    const int n = 1 + par.compact(nhist, [&](int i) { return hist[i] > 0; }, [&](int i, int p) { w.sym[p] = i; w.freq[p] = hist[i]; });
+    par.each(n, [&](int i) {
+        if (i == n - 1) { w.sym[i] = 256; w.freq[i] = 1; }
+        w.root[i] = i; w.codesize[i] = 0;
+    });
+    for (;;) {
+        // smaller frequency first, then the larger index; an entry merged away has no key
+        uint64_t k1, k2;
+        par.min2(n, [&](int i) { return w.freq[i] >= OPT_MERGED ? OPT_NO_KEY : ((uint64_t)w.freq[i] << 16) | (uint64_t)(0xFFFF - i); }, k1, k2);
+        if (k2 == OPT_NO_KEY) break;
+        const int c1 = 0xFFFF - (int)(k1 & 0xFFFF), c2 = 0xFFFF - (int)(k2 & 0xFFFF);
+        const int32_t f2 = (int32_t)(k2 >> 16);         // c2's frequency, which its key carries
+        par.each(n, [&](int i) {                // c1 keeps the sum, c2 leaves; every symbol of the two trees is one bit longer, the tree is c1's now
+            if (i == c1) w.freq[i] += f2; else if (i == c2) w.freq[i] = OPT_MERGED;
+            const int r = w.root[i];
+            if (r == c1 || r == c2) { ++w.codesize[i]; w.root[i] = c1; }
+        });
+    }
+    par.one([&]() {
+        int cnt[OPT_MAX_CLEN + 1], pos[OPT_MAX_CLEN + 1];
+        for (int i = 0; i <= OPT_MAX_CLEN; ++i) cnt[i] = 0;
+        int longest = 0;
+        bool over = false;
+        for (int i = 0; i < n; ++i) {
+            int cs = w.codesize[i];
+            if (cs > OPT_MAX_CLEN) { over = true; cs = OPT_MAX_CLEN; w.codesize[i] = cs; }
+            ++cnt[cs];
+            if (cs > longest) longest = cs;
+        }
+        int p = 0;
+        for (int i = 1; i <= OPT_MAX_CLEN; ++i) { pos[i] = p; p += cnt[i]; }
+        for (int i = 0; i < 17; ++i) out->bits[i] = 0;
+        out->pad[0] = out->pad[1] = out->pad[2] = 0;
+        out->nsym = over ? -1 : n - 1;
+        if (n < 2) return;                      // no symbol in use
+        for (int i = OPT_MAX_CLEN; i > 16; --i)
+            while (cnt[i] > 0) {
+                int j = i - 2;
+                while (cnt[j] == 0) --j;
+                cnt[i] -= 2; ++cnt[i - 1]; cnt[j + 1] += 2; --cnt[j];
+            }
+        int top = 16;
+        while (cnt[top] == 0) --top;
+        --cnt[top];                             // the pseudo-symbol's code
+        out->bits[0] = (uint8_t)longest;
+        for (int i = 1; i <= 16; ++i) out->bits[i] = (uint8_t)cnt[i];
+        for (int i = 0; i < n - 1; ++i) out->huffval[pos[w.codesize[i]]++] = (uint8_t)w.sym[i];
+    });
+}
+
+// The canonical codes of one table into a class's TABLE_WORDS entries: slot = table + 0 (DC) or table + 16 (AC), zeroed before.  The
+// codes of one length are consecutive, so symbol k of huffval takes (the first code of its length) + (k - the first position of its
+// length); w is scratch.
+template <typename Par>
+JPEG_HD void code_words(const OptimalTable& t, OptimalWork& w, Par& par, uint32_t* slot) {
+    par.one([&]() {
+        uint32_t code = 0;
+        int k = 0;
+        for (int len = 1; len <= 16; ++len, code <<= 1) {
+            w.root[len] = (int32_t)(code - (uint32_t)k);        // + k: the code at position k
+            code += t.bits[len]; k += t.bits[len];
+            w.codesize[len] = k;                                // the positions of this length end here
+        }
+    });
+    par.each(t.nsym < 0 ? 0 : t.nsym, [&](int k) {
+        int len = 1;
+        while (w.codesize[len] <= k) ++len;
+        slot[t.huffval[k]] = ((uint32_t)w.root[len] + (uint32_t)k) | (uint32_t)len << 16;
+    });
 }
 
 }  // namespace jpegem

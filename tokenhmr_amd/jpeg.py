@@ -17,7 +17,9 @@ Baseline JPEG encoding of device images, the drop-in for cv2.imwrite(".jpg") (cs
     data = encode_host(array, quality=75)                # the same bytes on the CPU (thmr_jpeg_encode_host)
 
 The file is the one libjpeg-turbo writes for the same pixels (Pillow's save(format="JPEG", quality=q, subsampling=s)), byte for byte:
-baseline JFIF, Annex-K Huffman tables, no restart markers, no optimisation pass.  Samples are converted as png.py converts them
+baseline JFIF, Annex-K Huffman tables, no restart markers.  optimize=True (per image in encode / imwrite_batch; cv2's
+params=[IMWRITE_JPEG_OPTIMIZE, 1] in imwrite) codes an image with Huffman tables made from its own statistics — libjpeg's
+optimize_coding, Pillow's save(..., optimize=True), again byte for byte: smaller files, the same pixels, a little more device time.  Samples are converted as png.py converts them
 (`scale`, `rounding`); the alpha of a 4-channel image is dropped, as cv2 does.  "4:2:2" is refused by name.
 """
 import ctypes as C
@@ -164,12 +166,16 @@ class JpegDecoder(_cabi.Handle):
 
 # ---- encoding ----
 _SUBSAMPLING = {"4:4:4": _cabi.JPEG_444, "4:2:2": _cabi.JPEG_422, "4:2:0": _cabi.JPEG_420}
-IMWRITE_JPEG_QUALITY = 1        # cv2's flag, the one imwrite honours
+IMWRITE_JPEG_QUALITY, IMWRITE_JPEG_OPTIMIZE = 1, 3          # cv2's flags, the two imwrite honours
 
 
-def encode_bound(width, height, channels, subsampling="4:2:0", lib=None):
-    """The largest file the encoder writes for an image of this size (0 for arguments it refuses)."""
-    return int((lib or _cabi.load()).thmr_jpeg_encode_bound(int(width), int(height), int(channels), _subsampling(subsampling)))
+def encode_bound(width, height, channels, subsampling="4:2:0", lib=None, optimize=False):
+    """The largest file the encoder writes for an image of this size (0 for arguments it refuses).  optimize: the bound of that mode,
+    one bit per block more (a DC code of an image's own table can take 12 bits)."""
+    lib = lib or _cabi.load()
+    if not optimize:
+        return int(lib.thmr_jpeg_encode_bound(int(width), int(height), int(channels), _subsampling(subsampling)))
+    return int(lib.thmr_jpeg_encode_bound_flags(int(width), int(height), int(channels), _subsampling(subsampling), _cabi.JPEG_OPTIMIZE))
 
 
 def _subsampling(s):
@@ -188,24 +194,62 @@ def _fill(item, img, scale, rounding, bgr, what="image"):
     return _imwrite.fill_item(item, img, scale, rounding, bgr, error=JpegError, what=what)
 
 
-def _out(item, h, w, c, sub, lib, capacity=None):
-    return _imwrite.out_buffer(item, lib.thmr_jpeg_encode_bound(w, h, c, sub) if capacity is None else capacity)
+def _flags(optimize):
+    if not isinstance(optimize, (bool, np.bool_)):
+        raise ValueError(f"optimize must be True or False, got {optimize!r}")
+    return _cabi.JPEG_OPTIMIZE if optimize else 0
 
 
-def encode_host(img, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, capacity=None, lib=None):
+def _out(item, h, w, c, sub, lib, capacity=None, flags=0):
+    return _imwrite.out_buffer(item, lib.thmr_jpeg_encode_bound_flags(w, h, c, sub, flags) if capacity is None else capacity)
+
+
+def encode_host(img, *, quality=95, subsampling="4:2:0", optimize=False, scale=1.0, rounding="nearest", bgr=True, capacity=None, flags=None, lib=None):
     """One numpy image -> the file's bytes, on the CPU with the kernels' arithmetic: the oracle of JpegEncoder, and what a caller without
-    a device gets.  capacity: the output buffer's size (default thmr_jpeg_encode_bound), for the refusal test."""
+    a device gets.  optimize: Huffman tables from the image's own statistics (Pillow's optimize=True).  capacity: the output buffer's
+    size (default the mode's bound) and flags: the raw flag word instead of `optimize` — both for the refusal tests."""
     lib = lib or _cabi.load()
     img = np.asarray(img)
     item = _cabi.PngItem()
     q, sub = _quality(quality), _subsampling(subsampling)
+    flags = _flags(optimize) if flags is None else int(flags)
     h, w, c = _fill(item, img, scale, rounding, bgr)
     item.pixels = img.ctypes.data
-    buf = _out(item, h, w, c, sub, lib, capacity)
-    rc = lib.thmr_jpeg_encode_host(C.byref(item), q, sub)
+    buf = _out(item, h, w, c, sub, lib, capacity, flags & _cabi.JPEG_OPTIMIZE)
+    rc = lib.thmr_jpeg_encode_host_flags(C.byref(item), q, sub, flags)
     if rc != 0:
-        _cabi.raise_error(rc, "thmr_jpeg_encode_host", lib.thmr_jpeg_encoder_last_error(None), JpegError, _BY_CODE)
+        _cabi.raise_error(rc, "thmr_jpeg_encode_host_flags", lib.thmr_jpeg_encoder_last_error(None), JpegError, _BY_CODE)
     return buf[:item.written].tobytes()
+
+
+def symbol_histogram(img, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, lib=None):
+    """The statistics encode_host(optimize=True) builds the image's tables from (thmr_jpeg_histogram_host): int32 (4, 256), the
+    frequency of every symbol of the tables DC0, AC0, DC1, AC1 — DC categories 0 ... 11, AC run << 4 | size with ZRL 0xF0 and EOB 0."""
+    lib = lib or _cabi.load()
+    img = np.asarray(img)
+    item = _cabi.PngItem()
+    h, w, c = _fill(item, img, scale, rounding, bgr)
+    item.pixels = img.ctypes.data
+    freq = np.zeros((4, 256), dtype=np.int32)
+    rc = lib.thmr_jpeg_histogram_host(C.byref(item), _quality(quality), _subsampling(subsampling), C.c_void_p(freq.ctypes.data))
+    if rc != 0:
+        _cabi.raise_error(rc, "thmr_jpeg_histogram_host", lib.thmr_jpeg_encoder_last_error(None), JpegError, _BY_CODE)
+    return freq
+
+
+def optimal_table(freq, lib=None):
+    """thmr_jpeg_optimal_table, the routine of the table kernel: 256 frequencies by symbol -> (bits, huffval).  bits: uint8 (17,),
+    bits[1:] the codes per length 1 ... 16 as a DHT segment holds them, bits[0] the longest code size BEFORE the limit to 16 (above 16:
+    libjpeg's adjustment ran); huffval: the symbols in use in code order."""
+    lib = lib or _cabi.load()
+    freq = np.ascontiguousarray(freq, dtype=np.int32)
+    if freq.shape != (256,):
+        raise ValueError(f"freq must hold 256 frequencies, got shape {freq.shape}")
+    bits, huffval, nsym = np.zeros(17, np.uint8), np.zeros(256, np.uint8), C.c_int32(0)
+    rc = lib.thmr_jpeg_optimal_table(C.c_void_p(freq.ctypes.data), C.c_void_p(bits.ctypes.data), C.c_void_p(huffval.ctypes.data), C.cast(C.byref(nsym), C.c_void_p))
+    if rc != 0:
+        _cabi.raise_error(rc, "thmr_jpeg_optimal_table", lib.thmr_jpeg_encoder_last_error(None), JpegError, _BY_CODE)
+    return bits, huffval[:nsym.value].copy()
 
 
 class JpegEncoder(_cabi.Handle):
@@ -219,13 +263,15 @@ class JpegEncoder(_cabi.Handle):
         self._files = np.empty(0, dtype=np.uint8)
         self._open(self._index())
 
-    def encode(self, images, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True):
+    def encode(self, images, *, quality=95, subsampling="4:2:0", optimize=False, scale=1.0, rounding="nearest", bgr=True):
         """A list of images — device tensors, or host tensors / numpy arrays (uploaded) — of any sizes, dtypes and strides -> the files,
-        list[bytes], in ONE batch call on the current stream.  quality (1 ... 100) and subsampling ("4:4:4", "4:2:0") hold for all
-        images, or are lists with one entry per image.  bgr: the images hold B, G, R(, A) like cv2's; False: R, G, B(, A)."""
+        list[bytes], in ONE batch call on the current stream.  quality (1 ... 100), subsampling ("4:4:4", "4:2:0") and optimize (Huffman
+        tables from the image's own statistics, built on the device) hold for all images, or are lists with one entry per image.  bgr:
+        the images hold B, G, R(, A) like cv2's; False: R, G, B(, A)."""
         n = len(images)
         qs = [_quality(q) for q in _imwrite.per_image(quality, n, "quality settings")]
         subs = [_subsampling(s) for s in _imwrite.per_image(subsampling, n, "subsampling settings")]
+        fls = [_flags(o) for o in _imwrite.per_image(optimize, n, "optimize settings")]
         if n == 0:
             return []
         items = (_cabi.PngItem * n)()
@@ -235,18 +281,22 @@ class JpegEncoder(_cabi.Handle):
             h, w, c = _fill(items[i], img, scale, rounding, bgr, f"image {i}")
             items[i].pixels = img.data_ptr()
             keep.append(img)
-            items[i].capacity = int(self.lib.thmr_jpeg_encode_bound(w, h, c, subs[i]))         # 0 for an image the call refuses: it names it
+            bound = self.lib.thmr_jpeg_encode_bound_flags(w, h, c, subs[i], fls[i]) if fls[i] else self.lib.thmr_jpeg_encode_bound(w, h, c, subs[i])
+            items[i].capacity = int(bound)          # 0 for an image the call refuses: it names it
             at.append(total)
             total += (items[i].capacity + 63) & ~63
         if self._files.size < total:
             self._files = np.empty(total + total // 4, dtype=np.uint8)
         for i in range(n):
             items[i].out = self._files.ctypes.data + at[i]
-        qa, sa = (C.c_int32 * n)(*qs), (C.c_int32 * n)(*subs)
+        qa, sa, fa = (C.c_int32 * n)(*qs), (C.c_int32 * n)(*subs), (C.c_int32 * n)(*fls)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
-            rc = self.lib.thmr_jpeg_encode_batch(self.h, items, qa, sa, n, C.c_void_p(stream.cuda_stream))
-        self._check(rc, "thmr_jpeg_encode_batch")
+            if any(fls):
+                rc = self.lib.thmr_jpeg_encode_batch_flags(self.h, items, qa, sa, fa, n, C.c_void_p(stream.cuda_stream))
+            else:               # today's entry point, today's launches
+                rc = self.lib.thmr_jpeg_encode_batch(self.h, items, qa, sa, n, C.c_void_p(stream.cuda_stream))
+        self._check(rc, "thmr_jpeg_encode_batch_flags" if any(fls) else "thmr_jpeg_encode_batch")
         return [self._files[at[i]:at[i] + items[i].written].tobytes() for i in range(n)]
 
 
@@ -257,29 +307,41 @@ def _check_path(path):
     _imwrite.check_extension(path, (".jpg", ".jpeg"), "jpeg.imwrite")
 
 
-def _params_quality(params, quality):
-    """cv2's params list [flag, value, ...]: IMWRITE_JPEG_QUALITY sets the quality, any other flag is refused by its number."""
+def _params(params, quality, optimize):
+    """cv2's params list [flag, value, ...] -> (quality, optimize): IMWRITE_JPEG_QUALITY sets the quality, IMWRITE_JPEG_OPTIMIZE
+    optimize = bool(value); any other flag is refused by its number."""
     if params is None:
-        return quality
+        return quality, optimize
     params = [int(p) for p in params]
     if len(params) % 2:
         raise ValueError(f"params must hold (flag, value) pairs, got {len(params)} entries")
     for flag, value in zip(params[::2], params[1::2]):
-        if flag != IMWRITE_JPEG_QUALITY:
-            raise ValueError(f"params flag {flag} is not supported: jpeg.imwrite honours IMWRITE_JPEG_QUALITY ({IMWRITE_JPEG_QUALITY}) only")
-        quality = value
-    return quality
+        if flag == IMWRITE_JPEG_OPTIMIZE:
+            optimize = bool(value)
+        elif flag == IMWRITE_JPEG_QUALITY:
+            quality = value
+        else:
+            raise ValueError(f"params flag {flag} is not supported: jpeg.imwrite honours IMWRITE_JPEG_QUALITY ({IMWRITE_JPEG_QUALITY}) and "
+                             f"IMWRITE_JPEG_OPTIMIZE ({IMWRITE_JPEG_OPTIMIZE}) only")
+    return quality, optimize
 
 
-def imwrite(path, img, params=None, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, device=None):
+def _params_quality(params, quality):
+    """The quality of a params list alone."""
+    return _params(params, quality, False)[0]
+
+
+def imwrite(path, img, params=None, *, quality=95, subsampling="4:2:0", optimize=False, scale=1.0, rounding="nearest", bgr=True, device=None):
     """cv2.imwrite for .jpg / .jpeg: a device tensor or a numpy array, (H, W) or (H, W, C), channels in cv2's B, G, R(, A) order; the
-    defaults are cv2's (quality 95, 4:2:0).  params=[cv2.IMWRITE_JPEG_QUALITY, q] is honoured; any other flag raises ValueError naming
-    it, and so does any other extension.  A numpy array goes to `device` (default: the current GPU).  Returns True."""
+    defaults are cv2's (quality 95, 4:2:0, no optimisation).  params=[cv2.IMWRITE_JPEG_QUALITY, q] and [cv2.IMWRITE_JPEG_OPTIMIZE, v]
+    are honoured, alone or together; any other flag raises ValueError naming it, and so does any other extension.  A numpy array goes
+    to `device` (default: the current GPU).  Returns True."""
     _check_path(path)
-    return imwrite_batch([path], [img], quality=_params_quality(params, quality), subsampling=subsampling, scale=scale, rounding=rounding, bgr=bgr, device=device)
+    quality, optimize = _params(params, quality, optimize)
+    return imwrite_batch([path], [img], quality=quality, subsampling=subsampling, optimize=optimize, scale=scale, rounding=rounding, bgr=bgr, device=device)
 
 
-def imwrite_batch(paths, images, *, quality=95, subsampling="4:2:0", scale=1.0, rounding="nearest", bgr=True, device=None, threads=None):
+def imwrite_batch(paths, images, *, quality=95, subsampling="4:2:0", optimize=False, scale=1.0, rounding="nearest", bgr=True, device=None, threads=None):
     """imwrite for many files: ONE device call for all images, then the files are written from a thread pool (at most png.WRITE_THREADS)."""
-    return _imwrite.imwrite_batch(JpegEncoder, _check_path, paths, images, device, threads, quality=quality, subsampling=subsampling, scale=scale,
-                                  rounding=rounding, bgr=bgr)
+    return _imwrite.imwrite_batch(JpegEncoder, _check_path, paths, images, device, threads, quality=quality, subsampling=subsampling, optimize=optimize,
+                                  scale=scale, rounding=rounding, bgr=bgr)
