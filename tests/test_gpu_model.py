@@ -5,6 +5,7 @@ Tolerances (fp32 kernels vs a CPU fp32 oracle, differences are su
   ViT features 2e-3 abs (values O(1-10) after 32 residual blocks), token_out 1e-3, logits 1e-3,
   token indices exactly equal wherever the reference's top-2 logit gap > 1e-3 (the ABSOLUTE mismatch count is
   printed; test_b64_tokens_vs_reference_golden puts the claim on 10,240 depth-32 tokens), rotmats 1e-4, vertices / joints 1e-4 m (0.1 mm), kp2d 1e-3.
+tests/test_gpu_stage_fp64.py holds every stage to the oracle in float64 within twice the oracle's own fp32 error.
 """
 import os
 

@@ -92,6 +92,90 @@ def test_gpu_lbs_matches_independent_derivation(built_lib, cuda_dev, hips):
     assert dv < TOL_M and dj < TOL_M
 
 
+# launch_lbs (tokenhmr_amd/csrc/body_model.hip) walks cg = B / 32 crops per workgroup pass, capped at 8, the bone matrices double-buffered on c & 1, one
+# arrival counter per crop group: both sides of every change of cg that has an odd size or a ragged last group
+CROP_GROUP_BATCHES = (31, 32, 63,            # cg 1
+                      64, 65, 95,            # cg 2: whole, last group of one, last group of one again at 47 whole groups
+                      96, 100,               # cg 3: whole, last group of one
+                      160, 161,              # cg 5
+                      224, 255,              # cg 7: whole, last group of three
+                      256, 257)              # cg 8: whole, last group of one
+CROP_GROUP_POOL = 11                         # coprime to every cg and to 32: row b holds pool item b % 11
+
+
+@pytest.fixture(scope="module", params=[False, True], ids=["plain", "update_hips"])
+def crop_group_case(request):
+    from oracle.lbs_independent import smpl_forward_independent
+    smpl, R, betas = _case(CROP_GROUP_POOL, 41, request.param)
+    v64, j64 = smpl_forward_independent(R.double().numpy(), betas.double().numpy(), smpl)
+    case = dict(smpl=smpl, R=R, betas=betas, v64=v64, j64=j64, model=None)      # model: ONE SMPL(max_batch=257) per update_hips value, made on first GPU use
+    yield case
+    if case["model"] is not None:
+        case["model"].close()
+
+
+def _crop_group_model(case, dev):
+    from tokenhmr_amd.smpl import SMPL
+    if case["model"] is None:
+        case["model"] = SMPL(case["smpl"], max_batch=257, device=dev)
+    return case["model"]
+
+
+def _crop_group_run(m, case, B):
+    sel = torch.arange(B) % CROP_GROUP_POOL
+    R, betas = case["R"][sel], case["betas"][sel]
+    o = m(R[:, :1], R[:, 1:], betas, pose2rot=False)
+    return o.vertices, o.joints
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", CROP_GROUP_BATCHES)
+def test_gpu_lbs_crop_group_edges(built_lib, cuda_dev, crop_group_case, B):
+    """The 24-joint path at every crop-group size, odd sizes and ragged last groups included, held to TOL_M against the independent
+    fp64 derivation (5 crops, cg 1, was the only size under that bound).  Row b holds pool item b % 11, so rows b and b + 11 must be
+    bit-equal and a crop that received a neighbour's bone matrices, partial sums or picked vertices cannot pass; the extra-vertex
+    joints are the kernel's own vertices bit for bit."""
+    case = crop_group_case
+    m = _crop_group_model(case, cuda_dev)
+    v, j = _crop_group_run(m, case, B)
+    assert torch.equal(v[CROP_GROUP_POOL:], v[:B - CROP_GROUP_POOL]) and torch.equal(j[CROP_GROUP_POOL:], j[:B - CROP_GROUP_POOL]), \
+        "rows b and b + 11 hold the same pose and shape but differ"
+    n = min(B, CROP_GROUP_POOL)
+    vc, jc = v[:n].cpu(), j[:n].cpu()
+    dv = np.abs(vc.double().numpy() - case["v64"][:n]).max()
+    dj = np.abs(jc.double().numpy() - case["j64"][:n]).max()
+    print(f"body_model.hip at {B} crops (update_hips={case['smpl']['update_hips']}) vs independent fp64 derivation: verts {dv:.2e} m, "
+          f"joints {dj:.2e} m, bound {TOL_M:.1e} m")
+    assert dv < TOL_M and dj < TOL_M
+    # joint_map slots >= 24 are picked vertices (smpl_wrapper.py:19-20, vertex_joint_selector.py); none of them is joint 9 / 12 of update_hips
+    jm, ev = case["smpl"]["joint_map"].tolist(), case["smpl"]["extra_verts"].tolist()
+    vall, jall = v.cpu(), j.cpu()
+    picked = 0
+    for slot, src in enumerate(jm):
+        if src >= 24 and slot not in (8, 9, 12):
+            assert torch.equal(jall[:, slot], vall[:, ev[src - 24]]), (B, slot)
+            picked += 1
+    assert picked >= 10
+
+
+@pytest.mark.gpu
+def test_gpu_lbs_smaller_call_after_larger_leaves_nothing_behind(built_lib, cuda_dev, crop_group_case):
+    """257 -> 65 -> 257 crops on ONE handle give the bits each size gives on a fresh handle: partial joint sums, picked vertices and
+    arrival counts a larger call left in the handle's workspace do not leak into a smaller one, nor the other way round."""
+    from tokenhmr_amd.smpl import SMPL
+    case = crop_group_case
+    want = {}
+    for B in (257, 65):
+        f = SMPL(case["smpl"], max_batch=257, device=cuda_dev)
+        want[B] = [t.clone() for t in _crop_group_run(f, case, B)]
+        f.close()
+    m = SMPL(case["smpl"], max_batch=257, device=cuda_dev)
+    for B in (257, 65, 257):
+        v, j = _crop_group_run(m, case, B)
+        assert torch.equal(v, want[B][0]) and torch.equal(j, want[B][1]), B
+    m.close()
+
+
 @pytest.mark.gpu
 def test_gpu_engine_applies_update_hips(built_lib, cuda_dev):
     """The flag travels in the weight arena (SMPL(update_hips=...), smpl_wrapper.py:11,33-36) and reaches thmr_forward's LBS."""
