@@ -110,7 +110,8 @@ def main():
         res[name] = {"lib": arm["spec"], "env": arm["env"], "build": arm["build"],
                      "ms_per_call_windows": [round(x, 3) for x in arm["ms"]], "ms_per_call_median": round(med, 3),
                      "crops_per_s_median": round(a.batch / med * 1e3, 1),
-                     "classes_ms_mean": {k: round(sum(p.get(k, 0.0) for p in arm["prof"]) / len(arm["prof"]), 3) for k in classes}}
+                     "classes_ms_mean": {k: round(sum(p.get(k, 0.0) for p in arm["prof"]) / len(arm["prof"]), 3) for k in classes},
+                     "classes_ms_windows": {k: [round(p.get(k, 0.0), 3) for p in arm["prof"]] for k in classes}}
     ma, mb = res["A"]["ms_per_call_median"], res["B"]["ms_per_call_median"]
     res["B_over_A_time"] = round(mb / ma, 4)
     res["classes_B_minus_A_ms"] = {k: round(res["B"]["classes_ms_mean"].get(k, 0) - res["A"]["classes_ms_mean"].get(k, 0), 3)

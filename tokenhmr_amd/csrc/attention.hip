@@ -26,6 +26,8 @@
 // d = 80 = 5 tiles of 16 and 80 = 20 k-steps of 4: the 16x16x4 shape wastes no MFMA work.
 // LDS rows: K stride 88 floats = 22 DMA slots of 16 B (20 data + 2 pad), V stride 84 floats = 21 slots (20 + 1): a wave's DMA
 // instruction fills 64 consecutive slots, i.e. lane l of instruction q carries slot 64q + l = (row, column) by division.
+// The phases — load_q, s_half, softmax_rows (row_max + exp_tiles), pv_half, store_o_f32 / store_o_split3 — are defined once in
+// attention_device.h; the plain and the persistent kernel below are two schedules (copies, waits, barriers, stamps) over them.
 #include <cstdlib>
 
 #include "common.h"
@@ -142,15 +144,10 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 6 : 2) void vit_attention_kerne
     }
     THMR_ATTN_STAMP(1)
 
-    // ---- Q fragments first (oldest VMEM operations of the wave): B operand of S^T = K Q^T.  B[kslot g][j = query l15];
-    //      with the k-permutation, register qf[qt][j][t] = Q[q0 + 16 qt + l15][16 j + 4 g + t] ----
+    // ---- Q fragments first (oldest VMEM operations of the wave) ----
     const int q0 = (qb * NW + wave) * 16 * QT;
     f32x4 qf[QT][5];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int j = 0; j < 5; ++j)
-            qf[qt][j] = *reinterpret_cast<const f32x4*>(base + (int64_t)(q0 + qt * 16 + l15) * QKV_LD + j * 16 + g * 4);
+    load_q<QT>(qf, base, q0, l15, g);
     // ---- both K halves go out now; the first one is awaited, the second lands under the first half of S ----
     {
         const KOff kd = dma_offsets<KS / 4, NW>(wave, lane);
@@ -159,16 +156,12 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 6 : 2) void vit_attention_kerne
     }
     const VOff vd = dma_offsets<VS / 4, NW>(wave, lane);     // 8 registers (NW = 4) that live across the S phases
 
-    // ---- S^T tiles: s[qt][kt][r] = S[q0 + 16 qt + l15][16 kt + 4 g + r] ----
     f32x4 s[QT][12];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int kt = 0; kt < 12; ++kt) s[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // one K fragment read per (kt, j) step feeding 4*QT MFMAs; software-pipelined: the fragment of step i+1 is read BEFORE
-    // the MFMAs of step i are issued (pinned with sched_barrier; hipcc's own schedule is read -> s_waitcnt lgkmcnt(0) -> MFMAs)
-    auto s_half = [&](int hf) {          // hf is a literal at both call sites
+    zero_tiles(s);
+    // attention_device.h's s_half<QT, KS>(s, qf, smem + hf * HALF * KS, hf, l15, g), stated in place: with the shared function hipcc
+    // allocates the two 64-query instantiations 92 / 90 registers instead of 90 / 88 (same instructions; every other phase and kernel
+    // came out equal).  Keep the two statements identical.
+    auto s_half_here = [&](int hf) {          // hf is a literal at both call sites
         f32x4 ka = *reinterpret_cast<const f32x4*>(&smem[(hf * HALF + l15) * KS + g * 4]);
 #pragma unroll
         for (int i = 0; i < 30; ++i) {
@@ -188,103 +181,34 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 6 : 2) void vit_attention_kerne
     };
     wait_vm_barrier<KOff::MINPER>();   // Q and K[0:96] have landed (at most this wave's MINPER youngest = K[96:192] copies are in flight)
     THMR_ATTN_STAMP(2)
-    s_half(0);
+    s_half_here(0);
     THMR_ATTN_STAMP(3)
     wait_vm_barrier<0>();        // K[96:192] landed; every wave is done with the first K half ...
     dma_half<VS / 4, NW>(base + 2 * DIM, smem, wave, vd);                                        // ... which V[0:96] overwrites
     THMR_ATTN_STAMP(4)
-    s_half(1);
+    s_half_here(1);
     THMR_ATTN_STAMP(5)
     wait_vm_barrier<VOff::MINPER>();   // every wave is done with the second K half (V[0:96] may still be in flight)
     dma_half<VS / 4, NW>(base + (int64_t)HALF * QKV_LD + 2 * DIM, smem + HALF * VS, wave, vd);
     THMR_ATTN_STAMP(6)
 
-    // ---- softmax over the 192 keys of each query (4 lanes x 48 registers per query), under the V copies.
-    //      e_j = 2^(s_j log2e - m log2e) as ONE packed fma per score PAIR (v_pk_fma_f32) + v_exp_f32; the rounding of the
-    //      constant m log2e is common to the whole row and cancels in e / sum.  The probabilities are NOT normalised here:
-    //      P.V accumulates the un-normalised e and the 80 outputs of a query are scaled by 1/sum afterwards — 20 multiplies
-    //      per lane instead of 48, and the row sums are packed adds.  (Round 1: sub, mul, exp, add, mul per score = 1353
-    //      non-MFMA VALU instructions per wave, profiles/r1_pmc_attention.json; VALU time is matrix-pipe time on gfx950.) ----
-    constexpr float LOG2E = 1.44269504088896340736f;
     float inv[QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-        float m = s[qt][0][0];
-#pragma unroll
-        for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) m = fmaxf(m, s[qt][kt][r]);
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        const f32x2 c2 = splat2(-(m * LOG2E)), l2 = splat2(LOG2E);
-        f32x2 sum2 = splat2(0.f);
-#pragma unroll
-        for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const f32x2 t = __builtin_elementwise_fma(f32x2{s[qt][kt][2 * h], s[qt][kt][2 * h + 1]}, l2, c2);
-                const f32x2 e = f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-                s[qt][kt][2 * h] = e.x;
-                s[qt][kt][2 * h + 1] = e.y;
-                sum2 += e;
-            }
-        float sum = sum2.x + sum2.y;
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        inv[qt] = 1.0f / sum;
-    }
+    softmax_rows<QT>(s, inv);          // under the V copies
 
-    // ---- O^T = V^T P^T: A[i = d l15][kslot g] = V[16 kt + 4 g + r][16 dt + l15], B[kslot g][j = query l15] = P register.
-    //      The transposed product leaves each lane with 4 CONSECUTIVE d of one query -> 16-byte output stores. ----
     f32x4 o[QT][5];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int dt = 0; dt < 5; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    auto pv_half = [&](int hf) {         // pipelined like s_half: the five V values of key step i+1 are read before step i's MFMAs
-        float vc[5], vn[5];
-#pragma unroll
-        for (int dt = 0; dt < 5; ++dt) vc[dt] = smem[(hf * HALF + g * 4) * VS + l15 + dt * 16];
-#pragma unroll
-        for (int i = 0; i < 24; ++i) {
-            const int kt = hf * 6 + i / 4, r = i % 4;
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt)
-                vn[dt] = (i + 1 < 24) ? smem[((hf * 6 + (i + 1) / 4) * 16 + g * 4 + (i + 1) % 4) * VS + l15 + dt * 16] : 0.f;
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt)
-#pragma unroll
-                for (int qt = 0; qt < QT; ++qt)
-                    o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vc[dt], s[qt][kt][r], o[qt][dt], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt) vc[dt] = vn[dt];
-        }
-    };
+    zero_tiles(o);
     THMR_ATTN_STAMP(7)
     wait_vm_barrier<VOff::MINPER>();   // V[0:96] landed for every wave
     THMR_ATTN_STAMP(8)
-    pv_half(0);
+    pv_half<QT, VS>(o, s, smem, 0, l15, g);
     THMR_ATTN_STAMP(9)
     wait_vm_barrier<0>();        // V[96:192] landed
     THMR_ATTN_STAMP(10)
-    pv_half(1);
+    pv_half<QT, VS>(o, s, smem + HALF * VS, 1, l15, g);
     THMR_ATTN_STAMP(11)
 
-    // ---- normalise + store: D layout of 16x16: col = lane&15 -> query (the lane that holds this query's 1/sum),
-    //      row = 4*(lane>>4) + reg -> d  (one float4 per tile) ----
-    float* obase = out + (int64_t)b * NTOK * DIM + h * HD;
-    if constexpr (SPLIT) {
-        store_o_split3<QT>(reinterpret_cast<char*>(out), (int64_t)b * NTOK + q0, h * HD, l15, g, o, inv);
-    } else {
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt)
-                *reinterpret_cast<f32x4*>(obase + (int64_t)(q0 + qt * 16 + l15) * DIM + dt * 16 + g * 4) = o[qt][dt] * inv[qt];
-    }
+    if constexpr (SPLIT) store_o_split3<QT>(reinterpret_cast<char*>(out), (int64_t)b * NTOK + q0, h * HD, l15, g, o, inv);
+    else store_o_f32<QT>(out + (int64_t)b * NTOK * DIM + h * HD, q0, l15, g, o, inv);
     if constexpr ((DBG & 1) != 0) {
         if (tid == 0) {
             unsigned long long* t = dbg.tl + (size_t)blockIdx.x * 16;
@@ -307,8 +231,8 @@ __global__ __launch_bounds__(NW * 64, NW == 12 ? 6 : 2) void vit_attention_kerne
 // before its first MFMA (profiles/r2n_attn_timeline.log) — 66 MB requested by 512 workgroups at once; 20 of the kernel's
 // 29 us above its MFMA floor.  Here only a workgroup's FIRST item pays that.  With at most 512 items (one per workgroup) it is
 // still ~3 % faster than the plain kernel — one copy-offset register instead of 17, 240 registers — and serves those grids too
-// (launch_vit_attention).  Per query the instruction sequence is the one of vit_attention_kernel, so results are bit-identical
-// (scripts/micro/attn_timeline.hip and tests/test_gpu_ops.py check it).
+// (launch_vit_attention).  Per query it runs the phase functions of vit_attention_kernel (attention_device.h: only the LDS row stride
+// and the half's base differ), so results are bit-identical (scripts/micro/attn_timeline.hip and tests/test_gpu_ops.py check it).
 // VMEM operations per wave and item, in issue order (in-order return): V[0:96] x8, V[96:192] x8, K'[0:96] x8, K'[96:192] x8, output
 // stores x15, Q' x15.  The copies are invisible to the compiler and waited for by hand (vmcnt); the stores and Q' are ordinary
 // instructions whose count the hand-written vmcnt(30) relies on (ISA-level guard: tests/test_host_logic.py).
@@ -331,12 +255,11 @@ __global__ __launch_bounds__(256, 2) void vit_attention_persistent_kernel(const 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-    // items of XCD x: [x * per_xcd, (x + 1) * per_xcd) (nitems = 16 B is a multiple of 8); this workgroup takes every wpx-th of them
-    const int xcd = blockIdx.x & 7, within = blockIdx.x >> 3, wpx = gridDim.x >> 3, per_xcd = nitems >> 3;
-    int it = within;                                    // index within the XCD's share
-    if (it >= per_xcd) return;
+    const XcdShare sh = xcd_share(nitems);              // nitems = 16 B
+    int it = sh.within;                                 // index within the XCD's share
+    if (it >= sh.per_xcd) return;
     auto item_base = [&](int i) {
-        const int bh = xcd * per_xcd + i;
+        const int bh = sh.item(i);
         return qkv + (int64_t)(bh / NH) * NTOK * QKV_LD + (bh % NH) * HD;
     };
     const float* base = item_base(it);
@@ -356,11 +279,7 @@ __global__ __launch_bounds__(256, 2) void vit_attention_persistent_kernel(const 
 
     const int q0 = wave * 16 * QT;
     f32x4 qf[QT][5];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int j = 0; j < 5; ++j)
-            qf[qt][j] = *reinterpret_cast<const f32x4*>(base + (int64_t)(q0 + qt * 16 + l15) * QKV_LD + j * 16 + g * 4);
+    load_q<QT>(qf, base, q0, l15, g);
     uint32_t doff, doff_last;
     {
         const int r = lane / (PS / 4), c = lane - r * (PS / 4);
@@ -380,44 +299,23 @@ __global__ __launch_bounds__(256, 2) void vit_attention_persistent_kernel(const 
     dma_rows(base + DIM, 0);
     dma_rows(base + (int64_t)HALF * QKV_LD + DIM, 1);
 
-    constexpr float LOG2E = 1.44269504088896340736f;
+    const float* const half1 = smem + HSLOTS * 4;        // second half of the LDS image
     wait_vm_barrier<CPW>();   // first item: Q and K[0:96] landed
     for (;;) {
-        const bool has_next = it + wpx < per_xcd;                    // wave-uniform
-        const float* nbase = has_next ? item_base(it + wpx) : base;
+        const bool has_next = it + sh.wpx < sh.per_xcd;              // wave-uniform
+        const float* nbase = has_next ? item_base(it + sh.wpx) : base;
         THMR_ATTN_STAMP(2)
         f32x4 s[QT][12];
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-            for (int kt = 0; kt < 12; ++kt) s[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto s_half = [&](int hf) {
-            f32x4 ka = *reinterpret_cast<const f32x4*>(&smem[hf * HSLOTS * 4 + l15 * PS + g * 4]);
-#pragma unroll
-            for (int i = 0; i < 30; ++i) {
-                const int kt = hf * 6 + i / 5, j = i % 5;
-                f32x4 kn = ka;
-                if (i + 1 < 30)
-                    kn = *reinterpret_cast<const f32x4*>(&smem[hf * HSLOTS * 4 + (((i + 1) / 5) * 16 + l15) * PS + ((i + 1) % 5) * 16 + g * 4]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int qt = 0; qt < QT; ++qt)
-                        s[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ka[t], qf[qt][j][t], s[qt][kt], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                ka = kn;
-            }
-        };
+        zero_tiles(s);
         if constexpr ((DBG & 8) != 0) __builtin_amdgcn_s_setprio(1);
-        s_half(0);
+        s_half<QT, PS>(s, qf, smem, 0, l15, g);
         if constexpr ((DBG & 8) != 0) __builtin_amdgcn_s_setprio(0);
         THMR_ATTN_STAMP(3)
         wait_vm_barrier<0>();          // K[96:192] landed (and the previous item's stores); every wave is done with the first K half
         dma_rows(base + 2 * DIM, 0);
         THMR_ATTN_STAMP(4)
         if constexpr ((DBG & 8) != 0) __builtin_amdgcn_s_setprio(1);
-        s_half(1);
+        s_half<QT, PS>(s, qf, half1, 1, l15, g);
         if constexpr ((DBG & 8) != 0) __builtin_amdgcn_s_setprio(0);
         THMR_ATTN_STAMP(5)
         barrier_only();                // every wave is done with the second K half
@@ -425,90 +323,33 @@ __global__ __launch_bounds__(256, 2) void vit_attention_persistent_kernel(const 
         THMR_ATTN_STAMP(6)
 
         float inv[QT];
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-            float m = s[qt][0][0];
-#pragma unroll
-            for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) m = fmaxf(m, s[qt][kt][r]);
-            m = fmaxf(m, __shfl_xor(m, 16, 64));
-            m = fmaxf(m, __shfl_xor(m, 32, 64));
-            const f32x2 c2 = splat2(-(m * LOG2E)), l2 = splat2(LOG2E);
-            f32x2 sum2 = splat2(0.f);
-#pragma unroll
-            for (int kt = 0; kt < 12; ++kt)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const f32x2 t = __builtin_elementwise_fma(f32x2{s[qt][kt][2 * h], s[qt][kt][2 * h + 1]}, l2, c2);
-                    const f32x2 e = f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-                    s[qt][kt][2 * h] = e.x;
-                    s[qt][kt][2 * h + 1] = e.y;
-                    sum2 += e;
-                }
-            float sum = sum2.x + sum2.y;
-            sum += __shfl_xor(sum, 16, 64);
-            sum += __shfl_xor(sum, 32, 64);
-            inv[qt] = 1.0f / sum;
-        }
-
+        softmax_rows<QT>(s, inv);
         f32x4 o[QT][5];
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        auto pv_half = [&](int hf) {
-            float vc[5], vn[5];
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt) vc[dt] = smem[hf * HSLOTS * 4 + (g * 4) * PS + l15 + dt * 16];
-#pragma unroll
-            for (int i = 0; i < 24; ++i) {
-                const int kt = hf * 6 + i / 4, r = i % 4;
-#pragma unroll
-                for (int dt = 0; dt < 5; ++dt)
-                    vn[dt] = (i + 1 < 24) ? smem[hf * HSLOTS * 4 + (((i + 1) / 4) * 16 + g * 4 + (i + 1) % 4) * PS + l15 + dt * 16] : 0.f;
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int dt = 0; dt < 5; ++dt)
-#pragma unroll
-                    for (int qt = 0; qt < QT; ++qt)
-                        o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vc[dt], s[qt][kt][r], o[qt][dt], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int dt = 0; dt < 5; ++dt) vc[dt] = vn[dt];
-            }
-        };
+        zero_tiles(o);
         THMR_ATTN_STAMP(7)
         wait_vm_barrier<CPW>();   // V[0:96] landed for every wave
         THMR_ATTN_STAMP(8)
         if constexpr ((DBG & 8) != 0) __builtin_amdgcn_s_setprio(1);
-        pv_half(0);
+        pv_half<QT, PS>(o, s, smem, 0, l15, g);
         if constexpr ((DBG & 8) != 0) __builtin_amdgcn_s_setprio(0);
         THMR_ATTN_STAMP(9)
         wait_vm_barrier<0>();              // V[96:192] landed; every wave is done with the first V half ...
         if (has_next) dma_rows(nbase + DIM, 0);       // ... which the next item's K[0:96] overwrites
         THMR_ATTN_STAMP(10)
         if constexpr ((DBG & 8) != 0) __builtin_amdgcn_s_setprio(1);
-        pv_half(1);
+        pv_half<QT, PS>(o, s, half1, 1, l15, g);
         if constexpr ((DBG & 8) != 0) __builtin_amdgcn_s_setprio(0);
         THMR_ATTN_STAMP(11)
         barrier_only();                    // every wave is done with the second V half
         if (has_next) dma_rows(nbase + (int64_t)HALF * QKV_LD + DIM, 1);
         {
-            const int bh = xcd * per_xcd + it;
-            float* obase = out + (int64_t)(bh / NH) * NTOK * DIM + (bh % NH) * HD;
-            if constexpr (SPLIT) {       // 24 stores per item instead of 15 (see the wait below)
-                store_o_split3<QT>(reinterpret_cast<char*>(out), (int64_t)(bh / NH) * NTOK + q0, (bh % NH) * HD, l15, g, o, inv);
-            } else {
-#pragma unroll
-                for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                    for (int dt = 0; dt < 5; ++dt)
-                        *reinterpret_cast<f32x4*>(obase + (int64_t)(q0 + qt * 16 + l15) * DIM + dt * 16 + g * 4) = o[qt][dt] * inv[qt];
-            }
+            const int bh = sh.item(it);
+            // split3: 24 stores per item instead of 15 (see the wait below)
+            if constexpr (SPLIT) store_o_split3<QT>(reinterpret_cast<char*>(out), (int64_t)(bh / NH) * NTOK + q0, (bh % NH) * HD, l15, g, o, inv);
+            else store_o_f32<QT>(out + (int64_t)(bh / NH) * NTOK * DIM + (bh % NH) * HD, q0, l15, g, o, inv);
         }
         if constexpr ((DBG & 1) != 0) {
-            if (tid == 0 && it == within) {          // timeline of the first item only
+            if (tid == 0 && it == sh.within) {       // timeline of the first item only
                 unsigned long long* t = dbg.tl + (size_t)blockIdx.x * 16;
 #pragma unroll
                 for (int i = 0; i < 12; ++i) t[i] = stamp[i];
@@ -523,14 +364,10 @@ __global__ __launch_bounds__(256, 2) void vit_attention_persistent_kernel(const 
         // (~2 us) is exposed, but K'[0:96] — the larger part of what the first MFMA needs — is on chip already.  Fetching Q' earlier
         // (under P.V, or before the stores) was built twice: the fragments then have to live beside the accumulators AND end up
         // where the scores are not, which hipcc can only do with 60 + 144 + 60 registers and 38-44 spills.
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-            for (int j = 0; j < 5; ++j)
-                qf[qt][j] = *reinterpret_cast<const f32x4*>(nbase + (int64_t)(q0 + qt * 16 + l15) * QKV_LD + j * 16 + g * 4);
+        load_q<QT>(qf, nbase, q0, l15, g);
         asm volatile("" ::: "memory");
         wait_vm_barrier<SPLIT ? kSplitStores3 + 15 : 30>();   // this wave's K'[0:96] and K'[96:192] copies landed: only the 15 (split3: 24) stores and the 15 Q' loads are younger
-        it += wpx;
+        it += sh.wpx;
         base = nbase;
     }
 }
@@ -550,11 +387,23 @@ __global__ __launch_bounds__(256, 2) void vit_attention_persistent_kernel(const 
 // QT = 16-query tiles per workgroup (1, 2, 3): every query is computed by the same instruction sequence whatever QT, so the
 // variants are bit-identical and the choice per batch size is free.  QT = 1 has the shortest chain (one crop: 192 workgroups);
 // larger QT re-reads K / V less often (12 / QT workgroups per (crop, head) each fetch all of K and V).
+// The merge's weights for query q: a[w] = 2^((m_w - M) log2 e), M = max_w m_w; returns L = sum_w l_w a[w], summed in wave order.
+template <int NQ>
+__device__ __forceinline__ float keysplit_weights(const float (&sm)[4][NQ], const float (&sl)[4][NQ], int q, float (&a)[4]) {
+    const float M = fmaxf(fmaxf(sm[0][q], sm[1][q]), fmaxf(sm[2][q], sm[3][q]));
+    float L = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        a[w] = __builtin_amdgcn_exp2f((sm[w][q] - M) * LOG2E);
+        L = fmaf(sl[w][q], a[w], L);
+    }
+    return L;
+}
+
 template <int QT, bool SPLIT = false>
 __global__ __launch_bounds__(256) void vit_attention_keysplit_kernel(const float* __restrict__ qkv, float* __restrict__ out) {
     constexpr int OS = 84;                                   // row stride of the partial-output tile in LDS (floats)
     constexpr int QB = 12 / QT;                              // workgroups per (crop, head)
-    constexpr float LOG2E = 1.44269504088896340736f;
     __shared__ __attribute__((aligned(16))) float so[4][16 * QT][OS];
     __shared__ float sm[4][16 * QT], sl[4][16 * QT];
     const int bh = blockIdx.x / QB, qb = blockIdx.x - bh * QB;
@@ -567,10 +416,7 @@ __global__ __launch_bounds__(256) void vit_attention_keysplit_kernel(const float
     // every operand fragment of this wave, requested up front: Q (B operand of S^T = K Q^T), K (A operand), V^T (A operand of O^T = V^T P^T)
     f32x4 qf[QT][5], kf[3][5];
     float vf[3][4][5];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int j = 0; j < 5; ++j) qf[qt][j] = *reinterpret_cast<const f32x4*>(base + (int64_t)(q0 + qt * 16 + l15) * QKV_LD + j * 16 + g * 4);
+    load_q<QT>(qf, base, q0, l15, g);
 #pragma unroll
     for (int kt = 0; kt < 3; ++kt)
 #pragma unroll
@@ -586,10 +432,7 @@ __global__ __launch_bounds__(256) void vit_attention_keysplit_kernel(const float
     __builtin_amdgcn_sched_barrier(0);       // all loads are issued before the first MFMA (hipcc otherwise sinks each load to its use: 20 round trips)
     // S^T tiles: s[qt][kt][r] = S[q0 + 16 qt + l15][k0 + 16 kt + 4 g + r]
     f32x4 s[QT][3];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int kt = 0; kt < 3; ++kt) s[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_tiles(s);
 #pragma unroll
     for (int kt = 0; kt < 3; ++kt)
 #pragma unroll
@@ -599,17 +442,12 @@ __global__ __launch_bounds__(256) void vit_attention_keysplit_kernel(const float
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt)
                     s[qt][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt][j][t], qf[qt][j][t], s[qt][kt], 0, 0, 0);
-    // this wave's softmax over its 48 keys of each of its queries (4 lanes x 12 registers per query)
+    // this wave's softmax over its 48 keys of each of its queries (4 lanes x 12 registers per query); the sum is sequential, NOT the packed
+    // one of exp_tiles: another association, kept as it is
     float m[QT], l[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-        float mm = s[qt][0][0];
-#pragma unroll
-        for (int kt = 0; kt < 3; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mm = fmaxf(mm, s[qt][kt][r]);
-        mm = fmaxf(mm, __shfl_xor(mm, 16, 64));
-        mm = fmaxf(mm, __shfl_xor(mm, 32, 64));
+        const float mm = row_max<3>(s[qt]);
         const float ml = mm * LOG2E;
         float ll = 0.f;
 #pragma unroll
@@ -625,10 +463,7 @@ __global__ __launch_bounds__(256) void vit_attention_keysplit_kernel(const float
     }
     // O_w^T tiles: o[qt][dt][i] = sum over this wave's keys of e * V, for d = 16 dt + 4 g + i, query 16 qt + l15
     f32x4 o[QT][5];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-        for (int dt = 0; dt < 5; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_tiles(o);
 #pragma unroll
     for (int kt = 0; kt < 3; ++kt)
 #pragma unroll
@@ -649,19 +484,17 @@ __global__ __launch_bounds__(256) void vit_attention_keysplit_kernel(const float
         // the same merge, eight consecutive d per thread, written as the three whole 16-byte chunks of one k-group (out = split3 operand)
         for (int idx = tid; idx < 16 * QT * (HD / 8); idx += 256) {
             const int q = idx / (HD / 8), d = (idx - q * (HD / 8)) * 8;
-            const float M = fmaxf(fmaxf(sm[0][q], sm[1][q]), fmaxf(sm[2][q], sm[3][q]));
+            float a[4];
+            const float L = keysplit_weights(sm, sl, q, a);
             f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-            float L = 0.f;
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
-                const float a = __builtin_amdgcn_exp2f((sm[w][q] - M) * LOG2E);
                 const f32x4 p0 = *reinterpret_cast<const f32x4*>(&so[w][q][d]), p1 = *reinterpret_cast<const f32x4*>(&so[w][q][d + 4]);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    acc0[e] = fmaf(p0[e], a, acc0[e]);
-                    acc1[e] = fmaf(p1[e], a, acc1[e]);
+                    acc0[e] = fmaf(p0[e], a[w], acc0[e]);
+                    acc1[e] = fmaf(p1[e], a[w], acc1[e]);
                 }
-                L = fmaf(sl[w][q], a, L);
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -676,29 +509,38 @@ __global__ __launch_bounds__(256) void vit_attention_keysplit_kernel(const float
 #pragma unroll
     for (int jj = 0; jj < 5 * QT; ++jj) {
         const int idx = tid + jj * 256, q = idx / HD, d = idx - q * HD;
-        const float M = fmaxf(fmaxf(sm[0][q], sm[1][q]), fmaxf(sm[2][q], sm[3][q]));
-        float acc = 0.f, L = 0.f;
+        float a[4], acc = 0.f;
+        const float L = keysplit_weights(sm, sl, q, a);
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float a = __builtin_amdgcn_exp2f((sm[w][q] - M) * LOG2E);
-            acc = fmaf(so[w][q][d], a, acc);
-            L = fmaf(sl[w][q], a, L);
-        }
+        for (int w = 0; w < 4; ++w) acc = fmaf(so[w][q][d], a[w], acc);
         out[((int64_t)b * NTOK + q0 + q) * DIM + h * HD + d] = acc / L;
     }
 }
+
+// The fp32 kernels' choice for a batch size, stated once for every launcher below.  The variants of a family are bit-identical, so the
+// choice is purely a matter of time.
+//   variant (profiles/r2ab_attn_variant_sweep.log, us per launch):
+//     1 = three 64-query workgroups per (crop, head): wins while its 48 B workgroups fill the 512 resident slots (2 per CU) evenly — up to
+//         10 crops (one round: 23-25 us vs 30-32) and again for 17-24 crops (two rounds: 44-54 us, where 16 B workgroups of 192 queries
+//         put two on some CUs and one on others: 56-58 us);
+//     5 = the persistent kernel everywhere else; with at most 512 items every workgroup has one item and it is still ~3 % faster than
+//         the plain 192-query kernel (3): one copy-offset register instead of 17, no spills; above 512 items it fetches the next item
+//         under the current one.
+//   keysplit_qt (profiles/r3j_attention_keysplit_ab.log): 16-query tiles per workgroup of the key-split kernel — one crop takes the
+//     shortest chain, more crops the fewer K / V re-reads.  The engine selects that kernel for one and two crops (engine.hip kKeysplitMaxB).
+struct AttnRule { int variant, keysplit_qt; };
+AttnRule attn_rule(int B) { return AttnRule{(B <= 10 || (B >= 17 && B <= 24)) ? 1 : 5, B == 1 ? 1 : B <= 2 ? 2 : 3}; }
 
 }  // namespace
 
 int launch_vit_attention_keysplit_qt(const float* qkv, float* out, int B, int want_qt, hipStream_t s) {
     if (B <= 0) return -1;
-    // 16 / 32 / 48 queries per workgroup are bit-identical: one crop takes the shortest chain, more crops the fewer K / V re-reads
     static const int forced_qt = [] { const char* e = thmr_knob("THMR_ATTN_KEYSPLIT_QT"); return e ? atoi(e) : 0; }();   // A/B knob
-    const int qt = want_qt ? want_qt : forced_qt ? forced_qt : (B == 1 ? 1 : B <= 2 ? 2 : 3);      // measured: profiles/r3j_attention_keysplit_ab.log
+    const int qt = want_qt ? want_qt : forced_qt ? forced_qt : attn_rule(B).keysplit_qt;
     if (qt == 1) hipLaunchKernelGGL(vit_attention_keysplit_kernel<1>, dim3(B * NH * 12), dim3(256), 0, s, qkv, out);
     else if (qt == 2) hipLaunchKernelGGL(vit_attention_keysplit_kernel<2>, dim3(B * NH * 6), dim3(256), 0, s, qkv, out);
     else hipLaunchKernelGGL(vit_attention_keysplit_kernel<3>, dim3(B * NH * 4), dim3(256), 0, s, qkv, out);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_status();
 }
 
 int launch_vit_attention_keysplit(const float* qkv, float* out, int B, hipStream_t s) { return launch_vit_attention_keysplit_qt(qkv, out, B, 0, s); }
@@ -711,39 +553,27 @@ int launch_vit_attention(const float* qkv, float* out, int B, hipStream_t s) { r
 int launch_vit_attention_split3(const float* qkv, void* out_split, int B, hipStream_t s) {
     if (B <= 0) return -1;
     float* out = reinterpret_cast<float*>(out_split);
-    const AttnDbg nodbg{nullptr, 0, 0};
-    if (B == 1) {
-        hipLaunchKernelGGL((vit_attention_keysplit_kernel<1, true>), dim3(B * NH * 12), dim3(256), 0, s, qkv, out);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    if (B == 2) {
-        hipLaunchKernelGGL((vit_attention_keysplit_kernel<2, true>), dim3(B * NH * 6), dim3(256), 0, s, qkv, out);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    if (B <= 10 || (B >= 17 && B <= 24)) {
+    const AttnRule rule = attn_rule(B);
+    if (B <= 2) {
+        if (rule.keysplit_qt == 1) hipLaunchKernelGGL((vit_attention_keysplit_kernel<1, true>), dim3(B * NH * 12), dim3(256), 0, s, qkv, out);
+        else hipLaunchKernelGGL((vit_attention_keysplit_kernel<2, true>), dim3(B * NH * 6), dim3(256), 0, s, qkv, out);
+    } else if (rule.variant == 1) {
+        const AttnDbg nodbg{nullptr, 0, 0};
         hipLaunchKernelGGL((vit_attention_kernel<1, 4, 0, true>), dim3(B * NH * 3), dim3(256), 0, s, qkv, out, nodbg);
     } else {
         const AttnDbg dph{nullptr, kAttnDephaseUs * 100, 0};
         hipLaunchKernelGGL((vit_attention_persistent_kernel<0, true>), dim3(min(B * NH, 512)), dim3(256), 0, s, qkv, out, B * NH, dph);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_status();
 }
 
-// variant 0 = the rule below (or THMR_ATTN_VARIANT); 1 / 3 / 5 / 12 / 6 force a kernel (unit tests, A/B)
+// variant 0 = attn_rule (or THMR_ATTN_VARIANT); 1 / 3 / 5 / 12 / 6 / 61-63 force a kernel (unit tests, A/B).
+//   6 = key-split (vit_attention_keysplit_kernel): another association of the key sum, A/B through the knob only here; the engine
+//       selects it for its whole small-batch regime through launch_vit_attention_keysplit
 int launch_vit_attention_variant(const float* qkv, float* out, int B, int want, hipStream_t s) {
     if (B <= 0) return -1;
-    // while 48*B workgroups of 64 queries still fit the 512 resident slots (2 per CU) they finish sooner than 16*B of 192
     static const int forced = [] { const char* e = thmr_knob("THMR_ATTN_VARIANT"); return e ? atoi(e) : 0; }();   // A/B knob (scripts/)
-    // The variants are bit-identical, so the choice is purely a matter of time (profiles/r2ab_attn_variant_sweep.log, us per launch):
-    //   1 = three 64-query workgroups per (crop, head): wins while its 48 B workgroups fill the 512 resident slots evenly — up to 10
-    //       crops (one round: 23-25 us vs 30-32) and again for 17-24 crops (two rounds: 44-54 us, where 16 B workgroups of 192
-    //       queries put two on some CUs and one on others: 56-58 us);
-    //   5 = the persistent kernel everywhere else; with at most 512 items every workgroup has one item and it is still ~3 % faster
-    //       than the plain 192-query kernel (3): one copy-offset register instead of 17, no spills; above 512 items it fetches the
-    //       next item under the current one.
-    //   6 = key-split (vit_attention_keysplit_kernel): another association of the key sum, A/B through the knob only here; the engine
-    //       selects it for its whole small-batch regime through launch_vit_attention_keysplit
-    const int variant = want ? want : forced ? forced : ((B <= 10 || (B >= 17 && B <= 24)) ? 1 : 5);
+    const int variant = want ? want : forced ? forced : attn_rule(B).variant;
     if (variant >= 61 && variant <= 63) return launch_vit_attention_keysplit_qt(qkv, out, B, variant - 60, s);     // key-split with 16 / 32 / 48 queries per workgroup
     if (variant != 1 && variant != 3 && variant != 5 && variant != 6 && variant != 12) return -1;
     const AttnDbg nodbg{nullptr, 0, 0};
@@ -752,14 +582,12 @@ int launch_vit_attention_variant(const float* qkv, float* out, int B, int want, 
         static const int dephase_us = [] { const char* e = thmr_knob("THMR_ATTN_DEPHASE_US"); return e ? atoi(e) : kAttnDephaseUs; }();   // A/B knob
         const AttnDbg dph{nullptr, dephase_us * 100, 0};
         hipLaunchKernelGGL((vit_attention_persistent_kernel<0>), dim3(min(B * NH, 512)), dim3(256), 0, s, qkv, out, B * NH, dph);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    if (variant == 1) hipLaunchKernelGGL((vit_attention_kernel<1, 4>), dim3(B * NH * 3), dim3(256), 0, s, qkv, out, nodbg);
+    } else if (variant == 1) hipLaunchKernelGGL((vit_attention_kernel<1, 4>), dim3(B * NH * 3), dim3(256), 0, s, qkv, out, nodbg);
 #ifdef THMR_EXPERIMENTS
     else if (variant == 12) hipLaunchKernelGGL((vit_attention_kernel<1, 12>), dim3(B * NH), dim3(768), 0, s, qkv, out, nodbg);   // A/B only: measured no faster (profiles/r2c_attention_variants.log)
 #else
     else if (variant == 12) return -1;            // 12 waves of 16 queries: experiments build only
 #endif
     else hipLaunchKernelGGL((vit_attention_kernel<3, 4>), dim3(B * NH), dim3(256), 0, s, qkv, out, nodbg);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_status();
 }

@@ -35,6 +35,8 @@
 // Per query the instruction sequence does not depend on QT, the grid or the batch size: QT = 3 (one workgroup per (crop, head)) and
 // QT = 1 (three workgroups of 64 queries: few crops) are bit-identical.  NOT bit-identical to attention.hip (fp32 products there,
 // 2^-24-truncated six-product sums here; another order of the key sum): the split3 mode's own attention, same error class as its GEMMs.
+// Shared with attention.hip through attention_device.h: the XCD share of the items (XcdShare), the row maximum and the exponentiation
+// (row_max, exp_tiles at 4 tiles), the fp32 store (store_o_f32).
 #include "common.h"
 #include "attention_device.h"
 #include "gemm_split_device.h"
@@ -50,7 +52,6 @@ constexpr int VPL = HD * VRS;            // one piece plane of the V^T image: [8
 constexpr int K_IMG = 3 * KPL, V_IMG = 3 * VPL;          // 43,008 + 38,400 bytes: two workgroups per CU
 static_assert(2 * (K_IMG + V_IMG) <= 160 * 1024, "two workgroups per CU");
 static_assert(V_IMG >= 4 * 16 * 480, "the split3 epilogue assembles 4 waves x 16 rows x 480 bytes in the dead V^T image");
-constexpr float LOG2E_F = 1.44269504088896340736f;
 
 typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
 
@@ -82,15 +83,13 @@ __global__ __launch_bounds__(256, OCC) void vit_attention_b16_kernel(const float
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-    // XCD-aware order (attention.hip): workgroup b runs on XCD b % 8; an XCD's share of the items is contiguous, so the 16 heads of a crop
-    // stream its 15 KB token rows through ONE L2.  nitems and the grid are multiples of 8 (launcher).
-    const int xcd = blockIdx.x & 7, within = blockIdx.x >> 3, wpx = gridDim.x >> 3, per_xcd = nitems >> 3;
-    int it = within;
-    if (it >= per_xcd) return;
+    const XcdShare sh = xcd_share(nitems);          // XCD-aware order; nitems and the grid are multiples of 8 (launcher)
+    int it = sh.within;
+    if (it >= sh.per_xcd) return;
     // an item: crop (its rows are the buffer resource), head column, first query of this wave
     struct Item { int crop, hcol, q0; };
     auto item_of = [&](int i) {
-        const int lg = xcd * per_xcd + i, bh = lg / QB, qb = lg - bh * QB;
+        const int lg = sh.item(i), bh = lg / QB, qb = lg - bh * QB;
         return Item{bh / NH, (bh % NH) * HD, (qb * 4 + wave) * 16 * QT};
     };
     // ---- global -> registers: buffer loads = {a crop's rows as the resource} + {wave-uniform SGPR offset} + {ONE 32-bit per-lane offset}.
@@ -202,14 +201,13 @@ __global__ __launch_bounds__(256, OCC) void vit_attention_b16_kernel(const float
 
 #pragma unroll 1
     for (;;) {
-        const bool has_next = it + wpx < per_xcd;            // wave-uniform
-        const Item nxt = has_next ? item_of(it + wpx) : cur;
+        const bool has_next = it + sh.wpx < sh.per_xcd;      // wave-uniform
+        const Item nxt = has_next ? item_of(it + sh.wpx) : cur;
         f32x4 o[QT][5];
         float lsum[QT], cneg[QT];            // per-lane partial row sums; -(running row maximum) log2 e
+        zero_tiles(o);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-#pragma unroll
-            for (int dt = 0; dt < 5; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
             lsum[qt] = 0.f;
             cneg[qt] = 3.0e38f;              // "no maximum yet": the first block's rescale factor is 2^(-huge) = 0 on sums and outputs that are 0
         }
@@ -218,10 +216,7 @@ __global__ __launch_bounds__(256, OCC) void vit_attention_b16_kernel(const float
             const bool more = blk + 1 < NBLK;                // this item has another block; else the next item's first block follows (if any)
             // ---- S^T of the block: 3 k steps x 4 key tiles x (6 products x QT) MFMAs; the fragment of the next (step, tile) is read before this one's MFMAs ----
             f32x4 s[QT][4];
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) s[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            zero_tiles(s);
             bf16x8 kc[3], kn[3];
 #pragma unroll
             for (int pc = 0; pc < 3; ++pc) kc[pc] = *reinterpret_cast<const bf16x8*>(kfr + pc * KPL);
@@ -275,35 +270,18 @@ __global__ __launch_bounds__(256, OCC) void vit_attention_b16_kernel(const float
                 }
             }
             __syncthreads();                                   // every wave is done with the K image (and with the V^T image: its P.V came first)
-            // ---- running softmax: m = max(m, block max); e = 2^(s log2 e - m log2 e); earlier sums and outputs scaled by 2^((m_old - m) log2 e) ----
+            // ---- running softmax: m = max(m, block max); e = 2^(s log2 e - m log2 e); earlier sums and outputs scaled by 2^((m_old - m) log2 e).
+            //      The row maximum and the exponentiation are attention_device.h's (row_max, exp_tiles at 4 tiles); the rescale is this kernel's ----
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
-                float m = s[qt][0][0];
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) m = fmaxf(m, s[qt][kt][r]);
-                m = fmaxf(m, __shfl_xor(m, 16, 64));
-                m = fmaxf(m, __shfl_xor(m, 32, 64));
-                const float c = fminf(-(m * LOG2E_F), cneg[qt]);                   // -(maximum so far) log2 e
+                const float m = row_max<4>(s[qt]);
+                const float c = fminf(-(m * LOG2E), cneg[qt]);                     // -(maximum so far) log2 e
                 const float alpha = __builtin_amdgcn_exp2f(c - cneg[qt]);          // 1 exactly when the maximum did not move
                 cneg[qt] = c;
                 lsum[qt] *= alpha;
 #pragma unroll
                 for (int dt = 0; dt < 5; ++dt) o[qt][dt] = o[qt][dt] * alpha;
-                const f32x2 c2 = splat2(c), l2 = splat2(LOG2E_F);
-                f32x2 sum2 = splat2(0.f);
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int hh = 0; hh < 2; ++hh) {
-                        const f32x2 t = __builtin_elementwise_fma(f32x2{s[qt][kt][2 * hh], s[qt][kt][2 * hh + 1]}, l2, c2);
-                        const f32x2 e = f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-                        s[qt][kt][2 * hh] = e.x;
-                        s[qt][kt][2 * hh + 1] = e.y;
-                        sum2 += e;
-                    }
-                lsum[qt] += sum2.x + sum2.y;
+                lsum[qt] += exp_tiles<4>(s[qt], c);
             }
             // ---- V block -> its image (transposed: rows = d, columns = key slots), next K block -> its image ----
             write_v();
@@ -418,16 +396,11 @@ __global__ __launch_bounds__(256, OCC) void vit_attention_b16_kernel(const float
                 }
             }
         } else {
-            float* obase = out + (int64_t)cur.crop * NTOK * DIM + cur.hcol;
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                for (int dt = 0; dt < 5; ++dt)
-                    *reinterpret_cast<f32x4*>(obase + (int64_t)(cur.q0 + qt * 16 + l15) * DIM + dt * 16 + g * 4) = o[qt][dt] * inv[qt];
+            store_o_f32<QT>(out + (int64_t)cur.crop * NTOK * DIM + cur.hcol, cur.q0, l15, g, o, inv);
         }
         if (!has_next) break;
         cur = nxt;
-        it += wpx;
+        it += sh.wpx;
     }
 }
 
@@ -460,7 +433,7 @@ int launch_vit_attention_b16(const float* qkv, void* out, int B, bool out_split,
                 case 3: hipLaunchKernelGGL((vit_attention_b16_kernel<3, true, 0, 3, 1>), grid, dim3(256), 0, s, qkv, o, nitems); break;
                 default: return -1;
             }
-            return hipGetLastError() == hipSuccess ? 0 : -2;
+            return launch_status();
         }
         if (early > 0 && qt == 3 && out_split) {
             switch (early) {
@@ -469,7 +442,7 @@ int launch_vit_attention_b16(const float* qkv, void* out, int B, bool out_split,
                 case 3: hipLaunchKernelGGL((vit_attention_b16_kernel<3, true, 0, 3>), grid, dim3(256), 0, s, qkv, o, nitems); break;
                 default: return -1;
             }
-            return hipGetLastError() == hipSuccess ? 0 : -2;
+            return launch_status();
         }
         const char* k = thmr_knob("THMR_ATTN_ABL");
         const int abl = k ? atoi(k) : 0;
@@ -483,7 +456,7 @@ int launch_vit_attention_b16(const float* qkv, void* out, int B, bool out_split,
                 case 7: hipLaunchKernelGGL((vit_attention_b16_kernel<3, true, 7>), grid, dim3(256), 0, s, qkv, o, nitems); break;
                 default: return -1;
             }
-            return hipGetLastError() == hipSuccess ? 0 : -2;
+            return launch_status();
         }
     }
 #endif
@@ -494,5 +467,5 @@ int launch_vit_attention_b16(const float* qkv, void* out, int B, bool out_split,
         if (out_split) hipLaunchKernelGGL((vit_attention_b16_kernel<3, true>), grid, dim3(256), 0, s, qkv, o, nitems);
         else hipLaunchKernelGGL((vit_attention_b16_kernel<3, false>), grid, dim3(256), 0, s, qkv, o, nitems);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_status();
 }
