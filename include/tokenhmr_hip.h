@@ -299,8 +299,14 @@ int thmr_tokenizer_roundtrip(thmr_engine* e, const float* pose6d_dev /*(B,21,6)*
 
 /* Stateless operator entry points (unit parity of individual kernels; no engine needed). */
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T) in exact fp32 (v_mfma_f32_32x32x2_f32 / 16x16x4_f32; csrc/gemm_f32.hip).  epi: 0 none, 1 +bias,
- * 2 +bias gelu(erf), 3 +bias relu, 4 resid + (acc+bias), 5 (+bias)*qscale on cols < qcols, 6 +bias +pos_embed (patch embed).  K % 32 == 0;
- * lda/ldc in elements, multiples of 4, < 2^22.  variant (the ids the ENGINE uses; the A/B-only ids are listed in tokenhmr_amd/ops.py):
+ * 2 +bias gelu(erf), 3 +bias relu, 4 resid + (acc+bias), 5 (+bias)*qscale on cols < qcols, 6 +bias +pos_embed (patch embed).  K % 32 == 0.
+ * Strides, in elements, < 2^22: lda (and, for the split3 operators below, ldw) is a multiple of 4 (split3: 8) and >= K; W of this operator
+ * is dense (row stride K); ldc is ANY value >= N (ldc < N, like M, N or K < 1, is refused before any launch).  The residual is read with
+ * C's row stride, and C == resid (the sum written in place, what the engine's proj / fc2 do) is allowed: every element is read and
+ * written by the same lane.  The split3 kernels store C as 16-byte vectors only when ldc % 4 == 0 and C is 16-byte aligned, and read the
+ * residual as vectors only when ldc % 4 == 0 (resid 16-byte aligned); otherwise element by element.  Nothing outside the M x N window
+ * is written.  The split-K ids of both families reduce with 16-byte stores: N % 4 == 0, ldc % 4 == 0 and C 16-byte aligned, else refused.
+ * variant (the ids the ENGINE uses; the A/B-only ids are listed in tokenhmr_amd/ops.py):
  *   -1 = tile picked by the cost model over the 128x128 / 128x160 / 128x96 / 64x64 LDS-DMA tiles (7 / 8 / 10 / 9 force one);
  *   2 = skinny (M <= 64); 100 + j = 64x64 ring kernel, 4-deep, split-K 2^j (few crops); 11 = tiny-M kernel (32x32 tiles, K split over the
  *   8 waves; K % 256 == 0; epilogues 0-5; the VQ decoder up to six crops); 120 = small-M kernel on 16x16x4 tiles (qkv at one and two crops);

@@ -561,6 +561,22 @@ def test_gemm_ring_rejects(built_lib, cuda_dev):
     a, w = _rand(64, 96, seed=1).to(cuda_dev), _rand(64, 96, seed=2).to(cuda_dev)
     with pytest.raises(_cabi.EngineError):
         ops.gemm(a, w, variant="ring4/k2")            # 96 % 64 != 0
+    # the stride contract (include/tokenhmr_hip.h): ldc < N and an empty product are refused before any launch, whatever the id; a
+    # split-K id also refuses an ldc that is no multiple of 4 (its reduce stores 16-byte vectors).  The output stays untouched.
+    import ctypes as C
+    L = _cabi.load()
+    a2, out = _rand(64, 128, seed=1).to(cuda_dev), torch.full((64, 68), 7.0, device=cuda_dev)
+    p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    for variant in (-1, 100, 101, 2, 11, 120):
+        for ldc, M, N, K, word in ((63, 64, 64, 128, "ldc >= N"), (68, 0, 64, 128, "M, N, K >= 1"), (68, 64, 0, 128, "M, N, K >= 1"), (68, 64, 64, 0, "M, N, K >= 1")):
+            with torch.cuda.device(cuda_dev):
+                rc = L.thmr_op_gemm(p(a2), 128, p(a2), None, None, p(out), ldc, M, N, K, 0, 1.0, 0, variant, None)
+            with pytest.raises(_cabi.EngineError, match=word):
+                _cabi.check(rc, None, L)
+    with pytest.raises(_cabi.EngineError, match="split-K"):
+        ops.gemm(a2, a2, variant="ring4/k2", out=torch.as_strided(out, (64, 64), (67, 1)))
+    torch.cuda.synchronize()
+    assert (out == 7.0).all()
 
 
 def test_splitk_operators_share_one_partial_sum_pool(built_lib, cuda_dev):

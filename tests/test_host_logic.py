@@ -241,6 +241,17 @@ def test_stateless_entry_points_reject_bad_arguments_without_a_gpu(built_lib):
     assert L.thmr_op_gemm(one, 32, one, null, null, one, 32, 1, 1, 32, 1, 1.0, 0, -1, null) < 0           # bias epilogue, no bias
     assert L.thmr_op_gemm(one, 32, one, one, null, one, 32, 1, 1, 32, 4, 1.0, 0, -1, null) < 0            # residual epilogue, no residual
     assert b"resid" in L.thmr_last_error(None)
+    # the stride contract of include/tokenhmr_hip.h: ldc is any value >= N, lda >= K, and no empty product — refused before any launch
+    assert L.thmr_op_gemm(one, 32, one, null, null, one, 31, 4, 32, 32, 0, 1.0, 0, -1, null) == -1        # ldc = N - 1
+    assert b"ldc >= N" in L.thmr_last_error(None)
+    assert L.thmr_op_gemm(one, 31, one, null, null, one, 32, 4, 32, 32, 0, 1.0, 0, -1, null) == -1        # lda < K
+    for m, n, k in ((0, 32, 32), (4, 0, 32), (4, 32, 0), (-1, 32, 32)):
+        assert L.thmr_op_gemm(one, 32, one, null, null, one, 32, m, n, k, 0, 1.0, 0, -1, null) == -1, (m, n, k)
+        assert b"M, N, K >= 1" in L.thmr_last_error(None)
+    assert L.thmr_op_gemm(one, 64, one, null, null, one, 33, 4, 32, 64, 0, 1.0, 0, 101, null) == -1       # split-K: the reduce stores 16-byte vectors
+    assert b"split-K" in L.thmr_last_error(None) and b"ldc % 4" in L.thmr_last_error(None)
+    assert L.thmr_op_gemm_split3(one, 64, one, 64, null, null, C.c_void_p(20), 32, 4, 32, 64, 0, 1.0, 0, 202, null) == -1      # ... C 16-byte aligned
+    assert b"split-K" in L.thmr_last_error(None)
     assert L.thmr_op_layernorm(null, one, one, one, 1, 64, 1e-5, 0, null) < 0
     assert L.thmr_op_rot6d(null, one, 1, null) < 0 and L.thmr_op_aa_to_rotmat(one, null, 1, null) < 0
     assert L.thmr_op_aa_to_rotmat(one, one, 0, null) < 0

@@ -38,6 +38,8 @@ int op_gemm_run(const OpGemmRow& r, const GemmArgs& a, int epi, void* stream) {
     const bool s3 = r.kind >= THMR_GEMM_S3_TILE && r.kind <= THMR_GEMM_S3_RING;
     const bool wide = r.kind == THMR_GEMM_S3_STREAM_WIDE, narrow = r.kind == THMR_GEMM_S3_STREAM_NARROW;
     if (s3 && r.ksplit > 1 && (a.K % (32 * r.ksplit)) != 0) return fail(THMR_ERR_INVALID, "split3 split-K GEMM: K must be a multiple of 32 * ksplit");
+    if (r.ksplit > 1 && ((a.N & 3) || (a.ldc & 3) || ((uintptr_t)a.C & 15)))      // launch_splitk_epilogue's rule, said before anything is launched
+        return fail(THMR_ERR_INVALID, "split-K GEMM: the reduce stores 16-byte vectors: N % 4 == 0, ldc % 4 == 0 and C 16-byte aligned");
     if (narrow && !gemm_split3_persist_narrow_ok(a)) return fail(THMR_ERR_INVALID, "persistent 128 x 128 split3 GEMM: N % 128 == 0, >= 256 tiles, K >= 96, row-major A");
     if (wide && !gemm_split3_persist_ok(a))
         return fail(THMR_ERR_INVALID, "persistent split3 GEMM: M % 32 == 0 (a ragged M is served in whole 32-row blocks), N % 256 == 0, ceil(M / 128) * N / 256 >= 256, K >= 64");
@@ -101,6 +103,7 @@ int thmr_op_gemm(const float* A, int64_t lda, const float* W, const float* bias,
     OpGemmRow r;
     bool blk;
     if (int rc = op_gemm_prepare(OP_GEMM_F32, A && W && C, epi, bias, resid, variant, &r, &blk)) return rc;
+    if (M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N) return fail(THMR_ERR_INVALID, "fp32 GEMM: M, N, K >= 1, lda >= K, ldc >= N");
     GemmArgs a = mk(A, lda, W, K, bias, resid, ldc, C, ldc, M, N, K);
     a.qscale = qscale; a.qcols = qcols;
     return op_gemm_run(r, a, epi, stream);

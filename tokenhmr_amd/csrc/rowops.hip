@@ -391,7 +391,7 @@ int launch_layernorm(const float* x, const float* g, const float* b, float* y, i
 }
 
 int launch_splitk_epilogue(const GemmArgs& a, int epi, const float* part, int S, hipStream_t s) {
-    if ((a.N & 3) || (a.ldc & 3) || S < 1) return -1;
+    if ((a.N & 3) || (a.ldc & 3) || ((uintptr_t)a.C & 15) || S < 1) return -1;      // 16-byte stores: whole quads, rows and base 16-byte aligned
     const int64_t total = (int64_t)a.M * (a.N >> 2);
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
 #define THMR_SK_CASE(E) \

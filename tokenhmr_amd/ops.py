@@ -1,5 +1,6 @@
 """Stateless operator wrappers over the C ABI (thmr_op_*), used for per-kernel parity tests and
-micro-benchmarks.  Inputs/outputs are contiguous fp32 CUDA tensors; no CPU path exists."""
+micro-benchmarks.  Inputs/outputs are contiguous fp32 CUDA tensors; no CPU path exists.  The GEMM family (`gemm`, `gemm_split3`, `split3`)
+also takes what its ABI takes: row-strided operands and a caller's `out=` (see `_ld`, `_ld_s3`)."""
 import ctypes as C
 
 import torch
@@ -60,14 +61,60 @@ def _req(*ts):
             raise ValueError("ops need contiguous float32 CUDA tensors")
 
 
-def gemm(a, w, bias=None, resid=None, epi="none", qscale=1.0, qcols=0, variant="auto"):
-    """C = epilogue(a @ w.T);  a (M,K), w (N,K) — torch.nn.Linear layout."""
-    _req(a, w, bias, resid)
+def _ld(t, what, mult=1):
+    """Row stride (the ABI's lda / ldc / ld_src, in elements) of a 2-D fp32 operand: rows of unit stride, `stride(0) >= columns` and a
+    multiple of `mult`.  Anything else is refused: the ABI cannot express it."""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] > 0 and t.stride(1) == 1):
+        raise ValueError(f"{what}: a 2-D float32 CUDA tensor whose rows have unit stride")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    if ld < t.shape[1] or ld % mult:
+        raise ValueError(f"{what}: row stride {ld} must be >= {t.shape[1]} columns" + (f" and a multiple of {mult}" if mult > 1 else ""))
+    return ld
+
+
+def _ld_s3(t, what):
+    """Row stride in fp32-EQUIVALENTS (the ABI's lda / ldw / ldcs / ld_dst: a row is 6 * ld bytes) of a row-major split3 operand: int16
+    (R, K/8, 3, 8), contiguous or the (R, K/8, 3, 8) view of a wider operand (strides (3 * ld, 24, 8, 1), ld % 8 == 0)."""
+    if not (t.is_cuda and t.dtype == torch.int16 and t.dim() == 4 and t.shape[1] > 0 and t.shape[2:] == (3, 8) and t.stride()[1:] == (24, 8, 1)):
+        raise ValueError(f"{what}: a split3 operand is int16 (R, K/8, 3, 8) with dense rows")
+    s0 = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), 24 * t.shape[1])
+    if s0 < 24 * t.shape[1] or s0 % 24:
+        raise ValueError(f"{what}: row stride {s0} int16 must be a multiple of 24 and >= {24 * t.shape[1]}")
+    return s0 // 3
+
+
+def _ldc_of(out, resid, M, N):
+    """ldc of an fp32 result: `out`'s row stride, N for a fresh one.  The C ABI reads the residual with C's row stride."""
+    if out is not None and tuple(out.shape) != (M, N):
+        raise ValueError(f"out must be ({M}, {N})")
+    ldc = _ld(out, "out") if out is not None else N
+    if resid is not None:
+        if tuple(resid.shape) != (M, N):
+            raise ValueError(f"resid must be ({M}, {N})")
+        if _ld(resid, "resid") != ldc:
+            raise ValueError(f"resid has row stride {_ld(resid, 'resid')}, the result {ldc}: the operator reads both with one stride (ldr = ldc)")
+    return ldc
+
+
+def gemm(a, w, bias=None, resid=None, epi="none", qscale=1.0, qcols=0, variant="auto", out=None):
+    """C = epilogue(a @ w.T);  a (M,K), w (N,K) — torch.nn.Linear layout.  `a` may be row-strided (lda = its row stride, a multiple of 4);
+    `w` is dense (the operator has no ldw).  `out`: write into this (M,N) tensor, row-strided or not (ldc = its row stride, any value >= N);
+    it may be `resid` itself (the sum in place).  `resid` (epi "bias_resid") must have the result's row stride."""
+    _req(w, bias)
     M, K = a.shape
     N = w.shape[0]
-    out = torch.empty(M, N, device=a.device, dtype=torch.float32)
+    lda = _ld(a, "a", 4)
+    if w.dim() != 2 or w.shape[1] != K:
+        raise ValueError("K mismatch")
+    if epi == "bias_pos":
+        _req(resid)                               # the position table (193, N), not a residual
+        ldc = _ldc_of(out, None, M, N)
+    else:
+        ldc = _ldc_of(out, resid, M, N)
+    if out is None:
+        out = torch.empty(M, N, device=a.device, dtype=torch.float32)
     with torch.cuda.device(a.device):
-        _check(_L().thmr_op_gemm(_p(a), K, _p(w), _p(bias), _p(resid), _p(out), N, M, N, K, EPI[epi],
+        _check(_L().thmr_op_gemm(_p(a), lda, _p(w), _p(bias), _p(resid), _p(out), ldc, M, N, K, EPI[epi],
                                              float(qscale), int(qcols), VARIANT[variant], _s(a)))
     return out
 
@@ -96,14 +143,18 @@ def _L_for(exp_only):
     return _cabi.load(exp=True) if exp_only else _L()
 
 
-def split3(x):
+def split3(x, out=None):
     """fp32 (R,K) -> the "split3" operand of gemm_split3: every element as three bf16 pieces h + m + l, laid out [R][K/8][3][8]
-    (returned as an int16 tensor of shape (R, K/8, 3, 8); see csrc/gemm_split.hip).  K % 8 == 0."""
-    _req(x)
+    (returned as an int16 tensor of shape (R, K/8, 3, 8); see csrc/gemm_split.hip).  K % 8 == 0.  `x` may be row-strided (ld_src = its row
+    stride, a multiple of 4); `out`: write into this (R, K/8, 3, 8) operand, which may be a view of a wider one (ld_dst, `_ld_s3`)."""
     R, K = x.shape
-    out = torch.empty(R, K // 8, 3, 8, device=x.device, dtype=torch.int16)
+    ld_src = _ld(x, "x", 4)
+    if out is None:
+        out = torch.empty(R, K // 8, 3, 8, device=x.device, dtype=torch.int16)
+    elif tuple(out.shape) != (R, K // 8, 3, 8):
+        raise ValueError("out must be (R, K/8, 3, 8)")
     with torch.cuda.device(x.device):
-        _check(_L().thmr_op_split3(_p(x), K, _p(out), K, R, K, _s(x)))
+        _check(_L().thmr_op_split3(_p(x), ld_src, _p(out), _ld_s3(out, "out"), R, K, _s(x)))
     return out
 
 
@@ -124,21 +175,23 @@ def split3_unblock(x_b, R):
 
 
 def gemm_split3(a_s, w_s, bias=None, resid=None, epi="none", qscale=1.0, qcols=0, variant="128x256/w8", out_split=False,
-                a_blocked_rows=None, out_blocked=False):
+                a_blocked_rows=None, out_blocked=False, out=None):
     """C = epilogue(a @ w.T) for split3 operands (`split3(a)`, `split3(w)`) on the bf16 matrix pipe with fp32-grade results: six
     bf16 products per element pair, fp32 accumulation.  `out_split`: the result as a split3 operand (what the engine's fc1 hands fc2);
     `out_blocked`: that operand in the row-blocked form (`split3_block`).  `a_blocked_rows=M`: `a_s` IS in the row-blocked form and has M rows.
-    What the engine runs for its ViT GEMMs in the default mode (`Engine.set_vit_gemm("split3")`, the creation default since ABI 4)."""
-    _req(bias, resid)
+    What the engine runs for its ViT GEMMs in the default mode (`Engine.set_vit_gemm("split3")`, the creation default since ABI 4).
+    Row-major operands may be views of wider ones (lda / ldw = their row strides, `_ld_s3`).  `out`: write into this tensor — fp32 (M,N),
+    row-strided or not (ldc; may be `resid` itself, and `resid` must share its row stride); with `out_split` an (M, N/8, 3, 8) operand or
+    view (ldcs); with `out_blocked` the contiguous (ceil(M/32), N/8, 3, 32, 8) tensor, whose pad rows the kernels leave alone."""
+    _req(bias)
     if a_blocked_rows is not None:
         if not (a_s.is_cuda and a_s.dtype == torch.int16 and a_s.is_contiguous() and a_s.dim() == 5 and a_s.shape[2:] == (3, 32, 8)):
             raise ValueError("a row-blocked split3 operand is int16 (ceil(R/32), K/8, 3, 32, 8)")
         M, K = int(a_blocked_rows), a_s.shape[1] * 8
     else:
         M, K = a_s.shape[0], a_s.shape[1] * 8
-    for t in ((w_s,) if a_blocked_rows is not None else (a_s, w_s)):
-        if not (t.is_cuda and t.dtype == torch.int16 and t.is_contiguous() and t.dim() == 4 and t.shape[2:] == (3, 8)):
-            raise ValueError("gemm_split3 needs split3 operands (int16, (R, K/8, 3, 8))")
+    ldw = _ld_s3(w_s, "w_s")
+    lda = K if a_blocked_rows is not None else _ld_s3(a_s, "a_s")
     N = w_s.shape[0]
     if w_s.shape[1] * 8 != K:
         raise ValueError("K mismatch")
@@ -147,18 +200,33 @@ def gemm_split3(a_s, w_s, bias=None, resid=None, epi="none", qscale=1.0, qcols=0
     if (out_blocked or a_blocked_rows is not None) and code < 0:
         raise ValueError("name the kernel (not 'auto') with a row-blocked operand")
     if out_split:
+        ldcs = N
         if out_blocked:
-            alloc = torch.empty if M % 32 == 0 else torch.zeros            # the kernels never write the pad rows of the last block
-            out = alloc((M + 31) // 32, N // 8, 3, 32, 8, device=a_s.device, dtype=torch.int16)
-        else:
+            shape = ((M + 31) // 32, N // 8, 3, 32, 8)
+            if out is None:
+                alloc = torch.empty if M % 32 == 0 else torch.zeros            # the kernels never write the pad rows of the last block
+                out = alloc(*shape, device=a_s.device, dtype=torch.int16)
+            elif not (out.is_cuda and out.dtype == torch.int16 and out.is_contiguous() and tuple(out.shape) == shape):
+                raise ValueError(f"out must be a contiguous int16 {shape}")
+        elif out is None:
             out = torch.empty(M, N // 8, 3, 8, device=a_s.device, dtype=torch.int16)
+        else:
+            if tuple(out.shape) != (M, N // 8, 3, 8):
+                raise ValueError("out must be (M, N/8, 3, 8)")
+            ldcs = _ld_s3(out, "out")
         with torch.cuda.device(a_s.device):
-            _cabi.check(lib.thmr_op_gemm_split3_out_split3(_p(a_s), K, _p(w_s), K, _p(bias), _p(out), N, M, N, K, EPI[epi],
+            _cabi.check(lib.thmr_op_gemm_split3_out_split3(_p(a_s), lda, _p(w_s), ldw, _p(bias), _p(out), ldcs, M, N, K, EPI[epi],
                                                            float(qscale), int(qcols), code + (1000 if out_blocked else 0), _s(a_s)), None, lib)
         return out
-    out = torch.empty(M, N, device=a_s.device, dtype=torch.float32)
+    if epi == "bias_pos":
+        _req(resid)                               # the position table (193, N), not a residual
+        ldc = _ldc_of(out, None, M, N)
+    else:
+        ldc = _ldc_of(out, resid, M, N)
+    if out is None:
+        out = torch.empty(M, N, device=a_s.device, dtype=torch.float32)
     with torch.cuda.device(a_s.device):
-        _cabi.check(lib.thmr_op_gemm_split3(_p(a_s), K, _p(w_s), K, _p(bias), _p(resid), _p(out), N, M, N, K, EPI[epi],
+        _cabi.check(lib.thmr_op_gemm_split3(_p(a_s), lda, _p(w_s), ldw, _p(bias), _p(resid), _p(out), ldc, M, N, K, EPI[epi],
                                             float(qscale), int(qcols), code + (1000 if a_blocked_rows is not None else 0), _s(a_s)), None, lib)
     return out
 
@@ -175,11 +243,20 @@ def layernorm(x, gamma, beta, eps, relu=False):
 ATTN_VARIANT = {"auto": 0, "q64": 1, "q192": 3, "persistent": 5, "q16x12": 12, "keysplit": 6, "keysplit/q16": 61, "keysplit/q32": 62, "keysplit/q48": 63}
 
 
-def vit_attention(qkv, variant="auto"):
-    """qkv (B,192,3840) with q pre-scaled -> (B,192,1280).  variant: "auto" (batch-size rule) or a forced kernel, see ATTN_VARIANT."""
+def _attn_out(out, shape, dtype, device):
+    if out is None:
+        return torch.empty(*shape, device=device, dtype=dtype)
+    if not (out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == shape):
+        raise ValueError(f"out must be a contiguous {dtype} CUDA tensor of shape {shape}")
+    return out
+
+
+def vit_attention(qkv, variant="auto", out=None):
+    """qkv (B,192,3840) with q pre-scaled -> (B,192,1280).  variant: "auto" (batch-size rule) or a forced kernel, see ATTN_VARIANT.
+    `out`: write into this contiguous (B,192,1280) tensor."""
     _req(qkv)
     B = qkv.shape[0]
-    out = torch.empty(B, 192, 1280, device=qkv.device, dtype=torch.float32)
+    out = _attn_out(out, (B, 192, 1280), torch.float32, qkv.device)
     with torch.cuda.device(qkv.device):
         if variant == "auto":
             _check(_L().thmr_op_vit_attention(_p(qkv), _p(out), B, _s(qkv)))
@@ -189,23 +266,25 @@ def vit_attention(qkv, variant="auto"):
     return out
 
 
-def vit_attention_split3(qkv):
-    """vit_attention with the output as a split3 operand (int16 (B*192, 160, 3, 8)): what the engine's split3 mode hands the proj GEMM."""
+def vit_attention_split3(qkv, out=None):
+    """vit_attention with the output as a split3 operand (int16 (B*192, 160, 3, 8)): what the engine's split3 mode hands the proj GEMM.
+    `out`: write into this contiguous tensor of that shape."""
     _req(qkv)
     B = qkv.shape[0]
-    out = torch.empty(B * 192, 160, 3, 8, device=qkv.device, dtype=torch.int16)
+    out = _attn_out(out, (B * 192, 160, 3, 8), torch.int16, qkv.device)
     with torch.cuda.device(qkv.device):
         _check(_L().thmr_op_vit_attention_split3(_p(qkv), _p(out), B, _s(qkv)))
     return out
 
 
-def vit_attention_b16(qkv, out_split=False, qt=0):
+def vit_attention_b16(qkv, out_split=False, qt=0, out=None):
     """The attention on the bf16 matrix pipe (three bf16 pieces per operand, six products, fp32 accumulate: csrc/attention_b16.hip).
-    out_split: the result as a split3 operand (int16 (B*192, 160, 3, 8)) instead of fp32 (B,192,1280); qt: 0 = batch-size rule, 1 / 3 = forced."""
+    out_split: the result as a split3 operand (int16 (B*192, 160, 3, 8)) instead of fp32 (B,192,1280); qt: 0 = batch-size rule, 1 / 3 = forced.
+    `out`: write into this contiguous tensor of the result's shape and type."""
     _req(qkv)
     B = qkv.shape[0]
-    out = (torch.empty(B * 192, 160, 3, 8, device=qkv.device, dtype=torch.int16) if out_split
-           else torch.empty(B, 192, 1280, device=qkv.device, dtype=torch.float32))
+    out = (_attn_out(out, (B * 192, 160, 3, 8), torch.int16, qkv.device) if out_split
+           else _attn_out(out, (B, 192, 1280), torch.float32, qkv.device))
     with torch.cuda.device(qkv.device):
         _check(_L().thmr_op_vit_attention_b16(_p(qkv), _p(out), B, int(out_split), int(qt), _s(qkv)))
     return out
