@@ -910,6 +910,86 @@ void thmr_png_destroy(thmr_png* p);
 const char* thmr_png_last_error(const thmr_png* p);
 int  thmr_png_encode_batch(thmr_png* p, thmr_png_item* items_host, int32_t n, void* stream);
 
+/* PNG decoding for the evaluation datasets and demo.py's imread (csrc/pngdec.hip, pngdec_host.h, pngdec_math.h): new symbols
+ * under ABI 5.  A hybrid in the shape of the JPEG decoder: the host walks the chunks and inflates the zlib stream — the sequential part,
+ * with an inflate of its own (the library links no zlib) — only down to the last row a WINDOW of the frame needs, and keeps only the
+ * bytes that can influence the window; the device un-filters them and converts palette, grey, alpha, 16-bit samples and the channel
+ * order, straight into the (win_h, win_w, 3) uint8 buffer thmr_cropper_run_frames takes.  Everything is bit-exact.
+ *   result        what cv2.imread(path, IMREAD_COLOR | IMREAD_IGNORE_ORIENTATION) gives for the file: (H, W, 3) uint8, B, G, R (bgr = 0:
+ *                 R, G, B).  Grey is replicated to three channels; a palette index goes through PLTE; alpha is dropped, never composited
+ *                 (the alpha channel of colour types 4 and 6, and tRNS); a 16-bit sample becomes its high byte.  For every supported
+ *                 8-bit file that is Pillow's Image.open(f).convert("RGB"), for 16-bit RGB(A) the array Pillow returns, for 16-bit grey
+ *                 Pillow's I;16 array >> 8; for 16-bit grey + alpha the rule stands on its own.
+ *   supported     non-interlaced, bit depth 8 in colour types 0, 2, 3, 4, 6 or bit depth 16 in colour types 0, 2, 4, 6; any number of
+ *                 consecutive IDAT chunks with the zlib stream running across their boundaries; ancillary chunks (gAMA, sRGB, iCCP,
+ *                 pHYs, tEXt, acTL, ...) are skipped and have no effect
+ *   unsupported   THMR_ERR_UNSUPPORTED, the message names what was found: Adam7 interlace, bit depths 1, 2 and 4, a side above 32767,
+ *                 a compression or filter method other than 0
+ *   malformed     THMR_ERR_INVALID, never a read outside [data, data + len), never an unbounded loop: a bad signature; a truncated
+ *                 chunk; a wrong CRC on IHDR, PLTE or an IDAT that is read; a first chunk other than IHDR; PLTE missing for colour type
+ *                 3; a palette index beyond PLTE; a zlib header that is not deflate with a window of 32K or less; a stored block whose
+ *                 length check fails; an over-subscribed or incomplete Huffman code (a single distance code of one bit is allowed, as
+ *                 zlib allows it); a distance that reaches before the first output byte; a stream that ends before the rows needed
+ *                 are out; a filter byte above 4.  The Adler-32 is checked only when the whole stream was inflated (a window that
+ *                 reaches the last row).
+ *   kept          a window {x0, y0, w, h} needs the unfiltered bytes [0, (x0 + w) * bpp) of the rows [row0, y0 + h): row0 is the last
+ *                 row at or above y0 whose filter is None or Sub (row 0 always qualifies: its previous row is zeros) — nothing above
+ *                 such a row and nothing right of the window can influence the window.  They are stored as rows of
+ *                 1 + kept_row_bytes, the filter byte first.
+ * The host entry points need no device, are re-entrant and keep no state; their message is in thmr_png_decoder_last_error(NULL)
+ * (thread-local). */
+/* The info and the plan are arrays of int32_t words, indexed by the constants below (no struct: the words are what a binding reads).
+ * info: THMR_PNG_INFO_WORDS words.  BPP is the bytes per pixel in the file, 1, 2, 3, 4, 6 or 8 where supported, else 0; SUPPORTED is 1,
+ * or 0 with the reason in thmr_png_decoder_last_error(NULL). */
+enum { THMR_PNG_INFO_HEIGHT = 0, THMR_PNG_INFO_WIDTH = 1, THMR_PNG_INFO_BIT_DEPTH = 2, THMR_PNG_INFO_COLOUR_TYPE = 3,
+       THMR_PNG_INFO_INTERLACE = 4, THMR_PNG_INFO_BPP = 5, THMR_PNG_INFO_SUPPORTED = 6, THMR_PNG_INFO_WORDS = 8 };
+/* plan: THMR_PNG_PLAN_WORDS words, what thmr_png_inflate_window kept.  WIN_*: the window the plan was made for.  The rows in the buffer
+ * are [ROW0, ROW0 + ROWS_KEPT) = [ROW0, WIN_Y0 + WIN_H); KEPT_ROW_BYTES is (WIN_X0 + WIN_W) * BPP, and a stored row has the filter byte
+ * before them; ROWS_INFLATED rows came out of the inflate, never more than WIN_Y0 + WIN_H.  From word THMR_PNG_PLAN_PALETTE on: 768
+ * BYTES, the palette as 256 x (R, G, B), zero beyond PALETTE_ENTRIES. */
+enum { THMR_PNG_PLAN_HEIGHT = 0, THMR_PNG_PLAN_WIDTH = 1, THMR_PNG_PLAN_BIT_DEPTH = 2, THMR_PNG_PLAN_COLOUR_TYPE = 3, THMR_PNG_PLAN_BPP = 4,
+       THMR_PNG_PLAN_WIN_X0 = 5, THMR_PNG_PLAN_WIN_Y0 = 6, THMR_PNG_PLAN_WIN_W = 7, THMR_PNG_PLAN_WIN_H = 8, THMR_PNG_PLAN_ROW0 = 9,
+       THMR_PNG_PLAN_ROWS_KEPT = 10, THMR_PNG_PLAN_KEPT_ROW_BYTES = 11, THMR_PNG_PLAN_ROWS_INFLATED = 12, THMR_PNG_PLAN_PALETTE_ENTRIES = 13,
+       THMR_PNG_PLAN_PALETTE = 14, THMR_PNG_PLAN_WORDS = 14 + 192 };
+/* Reads the signature and IHDR only.  info is filled for an unsupported file too (the return is THMR_ERR_UNSUPPORTED then). */
+int thmr_png_probe(const uint8_t* data, size_t len, int32_t* info /* [THMR_PNG_INFO_WORDS] */);
+/* window: {x0, y0, w, h} inside the frame (an empty one keeps nothing and inflates nothing), NULL = the whole frame.  rows NULL: the
+ * plan's geometry is filled, *bytes_needed is the bound (win_y0 + win_h) * (1 + kept_row_bytes) and nothing is inflated; otherwise
+ * `capacity` >= that bound, the kept rows are written from rows[0], the plan says which they are and *bytes_needed is
+ * rows_kept * (1 + kept_row_bytes).  One pass: the inflate writes rows from the top, moves its write position back to the start
+ * whenever it meets a None or Sub row at or above win_y0, and stops after row win_y0 + win_h - 1. */
+int thmr_png_inflate_window(const uint8_t* data, size_t len, const int32_t* window, uint8_t* rows, int64_t capacity,
+                            int32_t* plan /* [THMR_PNG_PLAN_WORDS] */, int64_t* bytes_needed);
+/* The inflate alone, on a whole zlib stream (header, deflate blocks, Adler-32): *written bytes at out, THMR_ERR_INVALID for a malformed
+ * stream or one that holds more than `capacity` bytes.  What the tests hold against zlib. */
+int thmr_png_inflate(const uint8_t* zdata, size_t len, uint8_t* out, int64_t capacity, int64_t* written);
+/* The full decode of a window on the CPU, with the kernels' arithmetic (shared __host__ __device__ functions, csrc/pngdec_math.h):
+ * out (win_h, win_w, 3) uint8 host, row_stride >= win_w * 3 bytes per row, bytes beyond win_w * 3 of a row untouched. */
+int thmr_png_decode_host(const uint8_t* data, size_t len, const int32_t* window, int32_t bgr, uint8_t* out, int64_t row_stride);
+/* The device half.  The handle owns two grow-only sets of staging (pinned host + device), used alternately, and device scratch for the
+ * unfiltered bytes.  thmr_png_decode_batch decodes n items of n sizes and formats with ONE packed upload and TWO launches.  Launch 1
+ * un-filters: the kept rows of an item fall into strips, each starting at a None or Sub row (or at the first kept row); strips are
+ * independent, and runs of short strips are joined into units of at most thmr_png_decode_band_rows() rows.  One wave takes a unit, a
+ * band of that many rows at a time: each lane owns a row and runs one pixel behind the lane above it, which hands it the upper and
+ * upper-left neighbours; the last row of a band feeds the next.  Launch 2 converts every window pixel.  A staging set is rewritten
+ * only after the event behind its last use — two calls back — has completed; beyond that the call synchronises only when a buffer
+ * grows (never inside a stream capture: THMR_ERR_STATE then — run the call once at those sizes first; a captured call keeps reading
+ * its staging set, so give it a handle of its own).
+ * An item is one entry of each of five host tables of n entries: rows_host[i] (host: ROWS_KEPT rows of 1 + KEPT_ROW_BYTES),
+ * plans_host[i] (host: its plan words), windows_host[4 i ...] = {x0, y0, w, h}, out_dev[i] (device: (win_h, win_w, 3) uint8) and
+ * row_strides_host[i] (bytes per output row, >= win_w * 3).  Every argument is checked before the handle and the handle before any HIP
+ * call: n <= 0, a null table, and per item (the message names its index) a null plan / rows, a plan that is not one
+ * thmr_png_inflate_window produces, a window outside the frame or outside what the plan kept, a filter byte above 4, a first kept row
+ * that needs a row above it, row_stride < win_w * 3, a null out_dev with a non-empty window.  Bytes of out_dev beyond win_w * 3 of a
+ * row are not written. */
+typedef struct thmr_png_decoder thmr_png_decoder;
+int  thmr_png_decode_band_rows(void);
+int  thmr_png_decoder_create(int32_t device, thmr_png_decoder** out);
+void thmr_png_decoder_destroy(thmr_png_decoder* d);
+const char* thmr_png_decoder_last_error(const thmr_png_decoder* d);
+int  thmr_png_decode_batch(thmr_png_decoder* d, const uint8_t** rows_host, const int32_t** plans_host, const int32_t* windows_host,
+                           uint8_t** out_dev, const int64_t* row_strides_host, int32_t n, int32_t bgr, void* stream);
+
 /* Baseline JPEG encoding of device images: the counterpart of cv2.imwrite(".jpg") (csrc/jpegenc.hip, jpegenc_host.h,
  * jpegenc_math.h): new symbols under ABI 5.  The file is the one libjpeg (libjpeg-turbo, Pillow's save(format="JPEG", quality=q,
  * subsampling=s)) writes for the same pixels, byte for byte, header included; it is a function of the pixels and the arguments only, and

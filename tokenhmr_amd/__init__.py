@@ -1,5 +1,5 @@
 """tokenhmr_amd: TokenHMR on HIP.  The submodules are imported where they are used; the PNG drop-ins are reachable from here by name."""
-_PNG_EXPORTS = ("PNGEncoder", "imwrite", "imwrite_batch")
+_PNG_EXPORTS = ("PNGEncoder", "imwrite", "imwrite_batch", "PNGDecoder", "imread")
 __all__ = list(_PNG_EXPORTS)
 
 

@@ -124,6 +124,13 @@ class JpegItem(C.Structure):
                 ("win_h", C.c_int32), ("out_dev", C.c_void_p), ("row_stride", C.c_int64)]
 
 
+# thmr_png_probe / thmr_png_inflate_window: the info and the plan are int32 words (header: THMR_PNG_INFO_* / THMR_PNG_PLAN_*)
+PNG_INFO_WORDS, PNG_PLAN_WORDS, PNG_PLAN_PALETTE = 8, 206, 14
+PNG_INFO_FIELDS = ["height", "width", "bit_depth", "colour_type", "interlace", "bpp", "supported"]
+PNG_PLAN_FIELDS = ["height", "width", "bit_depth", "colour_type", "bpp", "win_x0", "win_y0", "win_w", "win_h", "row0", "rows_kept",
+                   "kept_row_bytes", "rows_inflated", "palette_entries"]
+
+
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM, ERR_UNSUPPORTED = -1, -2, -3, -4, -5      # header: thmr_status
 
 RENDER_MAX_LIGHTS = 16

@@ -27,7 +27,10 @@ Departures from the reference, stated:
     choices) may differ by a grey level on some pixels; bit-parity with the reference's crops holds for the same decoded frame.
     That is decode="host", the default.  decode="device" (opt-in) leaves the decode threads only the marker parsing and Huffman decoding
     of a baseline JPEG file, for the window the item's crop reads, and finishes it on the device (tokenhmr_amd/jpeg.py) with libjpeg's
-    default arithmetic bit for bit; any other file goes to `imread`, that item alone.
+    default arithmetic bit for bit; any other file goes to `imread`, that item alone.  decode="device+png" (opt-in) treats JPEG files
+    as "device" does, and a PNG file likewise: the decode threads walk its chunks and inflate the rows the item's window needs, the
+    device un-filters and converts them (tokenhmr_amd/png.py), bit-equal to cv2's / Pillow's pixels; a PNG of a kind the decoder does
+    not handle (interlaced, 1 / 2 / 4 bits) goes to `imread`, that item alone.
 There is no CPU fallback for the device half.
 """
 import os
@@ -41,7 +44,8 @@ import torch
 from . import preprocess as PP
 
 MAX_WORKERS = 16      # decode threads: a fixed cap, never derived from the machine's CPU count
-DECODE_MODES = ("host", "device")
+DECODE_MODES = ("host", "device", "device+png")
+_PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
 def dataset_eval_config(path):
@@ -114,8 +118,10 @@ class _EvalDataset:
             raise NotImplementedError("train=True: the device datasets are evaluation-only (augmentation stays with the reference)")
         if decode not in DECODE_MODES:
             raise ValueError(f"decode={decode!r}: the decoders are {DECODE_MODES}")
-        self.decode, self._jpeg = decode, None
+        self.decode, self._jpeg, self._png = decode, None, None
         self.decode_stats = {"device": 0, "fallback": 0, "coef_bytes": 0}
+        self.png_stats = {"device": 0, "fallback": 0, "stream_bytes": 0}          # decode="device+png": the PNG files among the items
+        self._png_fallbacks = set()               # items whose PNG file the decoder does not handle (read_item, in the decode threads)
         self.train, self.cfg = False, cfg
         self.img_size = int(cfg.MODEL.IMAGE_SIZE)
         self.mean_rgb, self.std_rgb = tuple(cfg.MODEL.IMAGE_MEAN), tuple(cfg.MODEL.IMAGE_STD)
@@ -201,7 +207,8 @@ class _EvalDataset:
         bytes are read, probed and entropy-decoded for the item's window only (tokenhmr_amd.jpeg.entropy_decode: ctypes releases the
         GIL) -> a PlannedItem the batch call finishes on the device; a file that is no JPEG, or a JPEG of a kind the decoder does not
         handle, is decoded by `imread` instead (that item alone, counted in decode_stats["fallback"]); a malformed JPEG raises what an
-        unreadable file raises."""
+        unreadable file raises.  decode="device+png": a file with the PNG signature is probed and inflated for the item's window
+        (tokenhmr_amd.png.inflate_window) -> a PlannedPng; an unsupported PNG goes to `imread`, a malformed one raises likewise."""
         if self.decode == "host":
             return self.read_frame(i)
         from . import jpeg as J
@@ -218,6 +225,15 @@ class _EvalDataset:
             except J.JpegUnsupported:
                 pass
             except J.JpegError:
+                raise IOError("Fail to read %s" % path) from None
+        elif self.decode == "device+png" and data[:8] == _PNG_SIGNATURE:
+            from . import png as P
+            try:
+                info = P.probe(data)
+                return P.inflate_window(data, self._item_window(int(i), info["height"], info["width"]))
+            except P.PngUnsupported:
+                self._png_fallbacks.add(int(i))
+            except P.PngError:
                 raise IOError("Fail to read %s" % path) from None
         return self.read_frame(i)
 
@@ -273,17 +289,34 @@ class _EvalDataset:
             self._jpeg = JpegDecoder(self.cropper.device)
         return self._jpeg
 
+    @property
+    def png_decoder(self):
+        if self._png is None:
+            from .png import PNGDecoder
+            self._png = PNGDecoder(self.cropper.device)
+        return self._png
+
     def _crops_from_items(self, idxs, items, trans, extra):
         """decode="device": the windows of the entropy-decoded items are finished on the device by ONE thmr_jpeg_decode_batch, the
-        windows of the items `imread` decoded are uploaded, and one thmr_cropper_run_frames crops them all — on the current stream."""
+        windows of the items `imread` decoded are uploaded, and one thmr_cropper_run_frames crops them all — on the current stream.
+        decode="device+png": the inflated PNG items are finished by ONE thmr_png_decode_batch beside it, and cropped by the same call."""
+        from .png import PlannedPng
         dev = self.cropper.device
-        planned = [k for k, it in enumerate(items) if not isinstance(it, np.ndarray)]
+        pngs = [k for k, it in enumerate(items) if isinstance(it, PlannedPng)]
+        planned = [k for k, it in enumerate(items) if not isinstance(it, (np.ndarray, PlannedPng))]
         wins, sizes, wdev = [None] * len(items), [None] * len(items), [None] * len(items)
         if planned:
             outs = self.jpeg_decoder.decode_planned([items[k] for k in planned], bgr=True)
             for k, o in zip(planned, outs):
                 wins[k], sizes[k], wdev[k] = items[k].window, items[k].size, o
             self.decode_stats["coef_bytes"] += self.jpeg_decoder.last_coef_bytes
+        if pngs:
+            outs = self.png_decoder.decode_planned([items[k] for k in pngs], bgr=True)
+            for k, o in zip(pngs, outs):
+                wins[k], sizes[k], wdev[k] = items[k].window, items[k].size, o
+            self.png_stats["stream_bytes"] += self.png_decoder.last_row_bytes
+        self.png_stats["device"] += len(pngs)
+        self.png_stats["fallback"] += sum(1 for i in idxs if int(i) in self._png_fallbacks)
         for k, fr in enumerate(items):
             if isinstance(fr, np.ndarray):
                 H, W = fr.shape[:2]
@@ -292,7 +325,7 @@ class _EvalDataset:
                 if w * h:
                     wdev[k] = torch.from_numpy(np.ascontiguousarray(fr[y0:y0 + h, x0:x0 + w])).to(dev)
         self.decode_stats["device"] += len(planned)
-        self.decode_stats["fallback"] += len(items) - len(planned)
+        self.decode_stats["fallback"] += len(items) - len(planned) - len(pngs)
         img = self.cropper.warp_device_windows(wdev, sizes, wins, trans, None, truncate=3.0, patch=self.img_size, mean=self.mean_rgb,
                                                std=self.std_rgb, is_bgr=True)
         return img, torch.from_numpy(extra).to(dev)
@@ -363,7 +396,7 @@ class _EvalDataset:
         if genders is not None:
             pack.add("_rows_m", np.nonzero(genders != 1)[0].astype(np.int64))
             pack.add("_rows_f", np.nonzero(genders == 1)[0].astype(np.int64))
-        if self.decode == "device":
+        if self.decode != "host":
             img, extra = self._crops_from_items(idxs, frames, trans, pack.bytes())
         else:
             img, extra = self.cropper.warp_frames(frames, trans, None, truncate=3.0, patch=self.img_size, mean=self.mean_rgb, std=self.std_rgb,
@@ -599,7 +632,9 @@ def create_dataset(cfg, dataset_cfg, train=False, device="cuda:0", imread=None, 
     lower-cased, to the constructor (dataset_file, img_dir; keypoint_list, use_hips ride along unused, as in the reference).
     decode="host" (the default): `imread` decodes every frame on the host.  decode="device": baseline JPEG files are only
     entropy-decoded on the host, for the window their crop reads, and finished on the device (tokenhmr_amd.jpeg); other files fall back
-    to `imread` one by one; `dataset.decode_stats` counts both and the coefficient bytes uploaded."""
+    to `imread` one by one; `dataset.decode_stats` counts both and the coefficient bytes uploaded.  decode="device+png": as "device",
+    and PNG files are inflated on the host for their window and un-filtered and converted on the device (tokenhmr_amd.png);
+    `dataset.png_stats` counts the PNG items finished on the device, those that fell back and the filtered bytes uploaded."""
     if decode not in DECODE_MODES:
         raise ValueError(f"decode={decode!r}: the decoders are {DECODE_MODES}")
     if train:
