@@ -365,6 +365,11 @@ int thmr_op_rot6d(const float* x_dev, float* R_dev, int32_t n, void* stream);
 /* aa_to_rotmat (geometry.py:5-44; axis-angle -> quaternion -> rotation matrix, the reference's in-tree "Rodrigues" used for
  * ground-truth poses at tokenhmr.py:235,260,357): (n,3) -> (n,3,3) */
 int thmr_op_aa_to_rotmat(const float* aa_dev, float* R_dev, int32_t n, void* stream);
+/* grad_aa (n,3) = the vector-Jacobian product of axis-angle -> rotation matrix with grad_R (n,3,3): the adjoint of smplx batch_rodrigues'
+ * formula (angle = |aa + 1e-8|, R = I + sin K + (1 - cos) K^2, 1 - cos evaluated as 2 sin^2(angle / 2)), the kernel thmr_smpl_backward runs
+ * for pose2rot = 1.  thmr_op_aa_to_rotmat goes through a quaternion instead: the same function of aa up to 1e-8 / |aa|, so this is its
+ * gradient too. */
+int thmr_op_aa_to_rotmat_backward(const float* aa_dev, const float* grad_R_dev, float* grad_aa_dev, int32_t n, void* stream);
 
 /* The row, glue and head kernels around the GEMMs and the attention (csrc/rowops.hip, head.hip, hmr2_head.hip), each as the engine launches
  * it (tests/test_gpu_rowops.py).  Every entry point checks its arguments before any HIP call: a null buffer, a count <= 0 or a constraint
@@ -452,6 +457,23 @@ int  thmr_smpl_create(const thmr_smpl_desc* desc, int32_t max_batch, int32_t dev
 void thmr_smpl_destroy(thmr_smpl* m);
 int  thmr_smpl_forward(thmr_smpl* m, const float* pose_dev, int32_t pose2rot, const float* betas_dev, int32_t B,
                        float* verts_dev /*(B,6890,3)*/, float* joints_dev /*(B,44,3) or NULL*/, void* stream);
+/* The body model's vector-Jacobian product: what smplx.SMPL / SMPLLayer give under torch autograd.  New symbols under
+ * ABI 5: no struct or signature changed.
+ * thmr_smpl_grad_reserve, once per handle: allocates the backward workspace (the gradient of v_posed, the per-workgroup bone-matrix
+ * partial sums, the split-K planes of the blend GEMM's reverse) and builds the transposed copy of the blend-shape matrix.  It may allocate
+ * and synchronise; a second call does nothing.  A handle that never calls it keeps the footprint it had.
+ * thmr_smpl_backward takes the pose and betas of the forward it differentiates (it recomputes the forward's intermediates into the
+ * handle's workspace, so forwards issued in between do not matter) and the gradients of the two outputs; a NULL gradient input means
+ * zeros, a NULL output is not computed.  grad_pose_dev has the layout of pose_dev: (B,24,3,3) for pose2rot = 0 — the plain derivative by
+ * each matrix entry, as autograd gives it — or (B,72).  It never allocates and never synchronises: capturable in a graph on one stream.
+ * No floating-point atomics: every sum has a fixed order, so the result is bit-reproducible and a crop's gradient does not depend on the
+ * rest of the batch.  THMR_ERR_INVALID (message in thmr_last_error(NULL)) before any launch for a null handle, pose or betas, both
+ * gradient inputs null, both outputs null, B outside [1, max_batch], a pose2rot that is not 0 or 1, a handle that has not reserved. */
+int  thmr_smpl_grad_reserve(thmr_smpl* m);
+int  thmr_smpl_backward(thmr_smpl* m, const float* pose_dev, int32_t pose2rot, const float* betas_dev, int32_t B,
+                        const float* grad_verts_dev /*(B,6890,3) or NULL*/, const float* grad_joints_dev /*(B,44,3) or NULL*/,
+                        float* grad_pose_dev /*(B,24,3,3) or (B,72); may be NULL*/, float* grad_betas_dev /*(B,10); may be NULL*/,
+                        void* stream);
 
 /* Stand-alone SMPL-H model: the body mesh of the tokenizer workflow.  Replaces smplx.SMPLHLayer, the decoder's module-level
  * body model (tokenization/models/vanilla_pose_vqvae.py:10-17, called :182-191 as body_model(body_pose=rotmat)), and smplx.SMPLH, the

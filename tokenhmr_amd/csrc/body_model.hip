@@ -34,6 +34,8 @@
 //     into its wrist's once at creation (22 columns, padded to 24) and the pose correctives keep only the 21 body joints' 189 features
 //     (K = 199 -> 224).  The skin loop reads 66 broadcast float4 per pose instead of 156: the LDS return traffic that is this kernel's
 //     bound.  The posed HAND joints come from the wrist's transform applied to their rest position.
+//   * SMPL's backward (thmr_smpl_backward), further down: the forward's prep and blend GEMM recomputed, then skin-backward on SkinLane,
+//     the blend GEMM reversed and chain-backward, the mirror of prep.
 #include "common.h"
 
 namespace {
@@ -208,10 +210,11 @@ struct SkinLane {
             if (tid < NS * 3) AS[0][tid] = reinterpret_cast<const f32x4*>(A + (int64_t)b0 * NS * 12)[tid];
         }
     }
-    // crop b, the c-th of this pass; the caller's __syncthreads() came first: AS[c & 1] is complete
-    __device__ __forceinline__ void skin(const f32x4 (*AS)[NS * 3], const float* __restrict__ vposed, const float* __restrict__ A, int c,
-                                         int b, int B, int CG, float& ox, float& oy, float& oz) {
-        const float x = xn, y = yn, z = zn;
+    // crop b, the c-th of this pass; the caller's __syncthreads() came first: AS[c & 1] is complete.  The vertex's blended 3x4 transform
+    // (rows T0, T1, T2) and its posed rest position: what the forward applies (skin) and the backward transposes (lbs_skin_backward_kernel)
+    __device__ __forceinline__ void transform(const f32x4 (*AS)[NS * 3], const float* __restrict__ vposed, const float* __restrict__ A,
+                                              int c, int b, int B, int CG, f32x4& T0, f32x4& T1, f32x4& T2, float& x, float& y, float& z) {
+        x = xn, y = yn, z = zn;
         more = c + 1 < CG && b + 1 < B;
         if (more) {
             const float* p = vposed + ((int64_t)(b + 1) * NV + vv) * 3;
@@ -222,7 +225,7 @@ struct SkinLane {
         // traffic: each new crop misses the scalar cache and the 12 dependent s_load round trips per crop made the kernel slower,
         // 161 vs 142 us at 512 crops, profiles/r3b_lbs_scalar_loads.log.)
         const f32x4* ASc = AS[c & 1];
-        f32x4 T0 = {0.f, 0.f, 0.f, 0.f}, T1 = T0, T2 = T0;
+        T0 = f32x4{0.f, 0.f, 0.f, 0.f}, T1 = T0, T2 = T0;
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             const float w = wv[j >> 2][j & 3];
@@ -230,6 +233,12 @@ struct SkinLane {
             T1 += w * ASc[j * 3 + 1];
             T2 += w * ASc[j * 3 + 2];
         }
+    }
+    __device__ __forceinline__ void skin(const f32x4 (*AS)[NS * 3], const float* __restrict__ vposed, const float* __restrict__ A, int c,
+                                         int b, int B, int CG, float& ox, float& oy, float& oz) {
+        f32x4 T0, T1, T2;
+        float x, y, z;
+        transform(AS, vposed, A, c, b, B, CG, T0, T1, T2, x, y, z);
         ox = T0[0] * x + T0[1] * y + T0[2] * z + T0[3];
         oy = T1[0] * x + T1[1] * y + T1[2] * z + T1[3];
         oz = T2[0] * x + T2[1] * y + T2[2] * z + T2[3];
@@ -402,6 +411,294 @@ __global__ void rodrigues_kernel(const float* __restrict__ aa, float* __restrict
     for (int e = 0; e < 9; ++e) o[e] = ((e == 0 || e == 4 || e == 8) ? 1.0f : 0.0f) + s * k1[e] + oc * k2[e];
 }
 
+// ================================================================================================================================
+// SMPL's vector-Jacobian product (thmr_smpl_backward).  Given gV (B,6890,3) and gJ (B,44,3), with the forward's A and
+// v_posed recomputed by prep_kernel and the blend GEMM:
+//   skin-backward   per vertex  g = gV + sum_k J19[k][v] g19_k + (the mapped joints that pick this vertex),  g_vposed = T[:, :3]^T g,
+//                   gT = g (x) [v_posed; 1];  per workgroup  gA_j = sum_v W[v][j] gT_v  (24 x 12, stored per workgroup)
+//   blend reverse   gx (B x 224) = g_vposed (B x 20672) . dirs   on the fp32 split-K GEMM, THMR_LBS_GKSPLIT planes
+//   chain-backward  per crop: the 27 gA partials in block order, the planes in plane order, the reverse kinematic chain
+// Nothing crosses workgroups inside a launch and no floating-point atomic is used: every sum has one fixed order, so a crop's gradient
+// is the same bits whatever else is in the batch and however many crops a workgroup pass walks.
+// ================================================================================================================================
+
+// ---- one-time: dirsK[k][n] = dirsT[n][k], n < 20670; columns 20670, 20671 (the pad to the GEMM's K tile) zero ----
+__global__ __launch_bounds__(256) void build_dirs_k_kernel(const float* __restrict__ dirsT, float* __restrict__ dirsK, int kx) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)kx * THMR_LBS_GK) return;
+    const int k = (int)(idx / THMR_LBS_GK), n = (int)(idx % THMR_LBS_GK);
+    dirsK[idx] = n < NV * 3 ? dirsT[(int64_t)n * kx + k] : 0.f;
+}
+
+// ---- skin-backward: the forward's grid (27 workgroups of 256 vertices x crop groups, one thread per vertex, SkinLane's registers and
+//      LDS staging).  The in-workgroup reduction gA (24 x 12) = W^T (24 x 256) . gT (256 x 12) runs on v_mfma_f32_16x16x4_f32 (exact
+//      fp32): each wave owns its 64 vertices as K = 16 steps of 4, two 16-row blocks of joints (24 -> 32), 12 -> 16 columns.  The W^T
+//      fragments are constant over the crops of a pass and sit in registers in the MFMA's operand layout (lane l: joint l & 15,
+//      vertex 4 step + (l >> 4)), loaded once from global; gT goes through LDS once per crop ([256][12], read conflict-free: the 64 lanes
+//      of a step read 48 consecutive floats) — 16 ds_read_b32 and 32 MFMAs per wave and crop, where a VALU reduction out of LDS would read
+//      two operands per FMA (288 x 256 FMAs per crop) and wave reductions would take 288 x 6 cross-lane steps per thread.  The four waves'
+//      tiles are added in wave order. ----
+template <int NS>
+__global__ __launch_bounds__(256) void lbs_skin_backward_kernel(const float* __restrict__ vposed, const float* __restrict__ W,
+                                                                const float* __restrict__ A, const float* __restrict__ J19,
+                                                                const int32_t* __restrict__ extra, const int32_t* __restrict__ jmap,
+                                                                const int32_t* __restrict__ update_hips, const float* __restrict__ gV,
+                                                                const float* __restrict__ gJ, float* __restrict__ gvp,
+                                                                float* __restrict__ gApart, int B, int CG) {
+    static_assert(NS > 16 && NS <= 32 && NS % 4 == 0, "two 16-row MFMA blocks of joints");
+    constexpr int NOJ = 44, NMAP = 25;                // output joints; the mapped ones in front of the 19 regressed
+    __shared__ f32x4 AS[2][NS * 3];                   // bone matrices of the current / next crop
+    __shared__ float gjs[NOJ * 3];                    // the crop's joint gradients, update_hips' adjoint applied
+    __shared__ __attribute__((aligned(16))) float gTs[256 * 12];
+    __shared__ float red[4][NS * 12];
+    __shared__ float jws[19][256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    SkinLane<NS, NS> t;
+    const int b0 = blockIdx.y * CG;
+    t.begin(AS, vposed, W, A, extra, b0, B);
+    // the mapped joints that are this thread's vertex (bit s: joint_map[s] names a picked slot whose vertex id is v; an id may repeat)
+    unsigned jslots = 0;
+#pragma unroll
+    for (int s = 0; s < NMAP; ++s) {
+        const int src = jmap[s];
+        jslots |= (src >= NS && ((t.slots >> (src - NS)) & 1u)) ? 1u << s : 0u;
+    }
+    // the vertex's 19 regressor entries: LDS, not registers (the 24 skin weights and the 32 MFMA fragments already live there across
+    // the bone-matrix loop); [k][tid], read conflict-free
+    for (int k = 0; k < 19; ++k) jws[k][tid] = t.vok ? J19[(int64_t)k * NV + t.vv] : 0.f;
+    // W^T as the MFMA's A operand: step u, lane (i = lane & 15, k = lane >> 4): W[first vertex of the wave + 4 u + k][i (+ 16)]
+    float wm[16][2];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        const int gv = blockIdx.x * 256 + wave * 64 + u * 4 + (lane >> 4), i = lane & 15;
+        wm[u][0] = gv < NV ? W[(int64_t)gv * NS + i] : 0.f;
+        wm[u][1] = (gv < NV && 16 + i < NS) ? W[(int64_t)gv * NS + 16 + i] : 0.f;
+    }
+    const bool hips = *update_hips != 0;
+    for (int c = 0; c < CG; ++c) {
+        const int b = b0 + c;             // workgroup-uniform
+        if (b >= B) break;
+        // this thread's element of the crop's joint gradient; the forward is j9' = j9 - j12 / 2 + j8 / 2 (and 12 <-> 9), so
+        // (g9, g12, g8) <- (g9 - g12 / 2, g12 - g9 / 2, g8 + (g9 + g12) / 2)
+        float gjv = 0.f;
+        if (gJ && tid < NOJ * 3) {
+            const float* q = gJ + (int64_t)b * NOJ * 3;
+            const int j = tid / 3, i = tid % 3;
+            gjv = q[tid];
+            if (hips && j == 9) gjv = gjv - 0.5f * q[12 * 3 + i];
+            if (hips && j == 12) gjv = gjv - 0.5f * q[9 * 3 + i];
+            if (hips && j == 8) gjv = gjv + 0.5f * (q[9 * 3 + i] + q[12 * 3 + i]);
+        }
+        __syncthreads();                  // AS[c & 1] is complete; gjs, gTs and red of the previous crop are no longer read
+        if (tid < NOJ * 3) gjs[tid] = gjv;
+        f32x4 T0, T1, T2;
+        float x, y, z;
+        t.transform(AS, vposed, A, c, b, B, CG, T0, T1, T2, x, y, z);
+        __syncthreads();
+        float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+        if (gV && t.vok) {
+            const float* p = gV + ((int64_t)b * NV + t.v) * 3;
+            g0 = p[0]; g1 = p[1]; g2 = p[2];
+        }
+        if (gJ) {
+#pragma unroll
+            for (int k = 0; k < 19; ++k) {
+                const float jw = jws[k][tid];
+                g0 = fmaf(jw, gjs[(NMAP + k) * 3 + 0], g0);
+                g1 = fmaf(jw, gjs[(NMAP + k) * 3 + 1], g1);
+                g2 = fmaf(jw, gjs[(NMAP + k) * 3 + 2], g2);
+            }
+            for (unsigned m = jslots; m; m &= m - 1) {
+                const int s = __builtin_ctz(m);
+                g0 += gjs[s * 3 + 0]; g1 += gjs[s * 3 + 1]; g2 += gjs[s * 3 + 2];
+            }
+        }
+        if (!t.vok) g0 = g1 = g2 = 0.f;
+        // g_vposed = T[:, :3]^T g, the row padded to THMR_LBS_GK: the thread behind the last vertex writes the two pad columns
+        if (t.vok) {
+            float* o = gvp + (int64_t)b * THMR_LBS_GK + t.v * 3;
+            o[0] = T0[0] * g0 + T1[0] * g1 + T2[0] * g2;
+            o[1] = T0[1] * g0 + T1[1] * g1 + T2[1] * g2;
+            o[2] = T0[2] * g0 + T1[2] * g1 + T2[2] * g2;
+        } else if (t.v == NV) {
+            float* o = gvp + (int64_t)b * THMR_LBS_GK + NV * 3;
+            o[0] = 0.f; o[1] = 0.f;
+        }
+        // gT = g (x) [x y z 1], in the bone matrix's own order (row r of 3, column of 4)
+        f32x4* gq = reinterpret_cast<f32x4*>(gTs + tid * 12);
+        gq[0] = f32x4{g0 * x, g0 * y, g0 * z, g0};
+        gq[1] = f32x4{g1 * x, g1 * y, g1 * z, g1};
+        gq[2] = f32x4{g2 * x, g2 * y, g2 * z, g2};
+        __syncthreads();
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+        const int n = lane & 15, kq = lane >> 4;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const float bv = n < 12 ? gTs[(wave * 64 + u * 4 + kq) * 12 + n] : 0.f;
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wm[u][0], bv, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wm[u][1], bv, acc1, 0, 0, 0);
+        }
+        // result layout: register r of lane l is row 4 (l >> 4) + r, column l & 15
+        if (n < 12) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = kq * 4 + r;
+                red[wave][j * 12 + n] = acc0[r];
+                if (16 + j < NS) red[wave][(16 + j) * 12 + n] = acc1[r];
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < NS * 12; i += 256)
+            gApart[((int64_t)b * SKB + blockIdx.x) * (NS * 12) + i] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+        t.publish(AS, c);
+    }
+}
+
+// ---- chain-backward: one workgroup per crop, the mirror of prep_kernel.  Adds the 27 gA partials in block order and the split-K planes
+//      of the blend GEMM's reverse in plane order, recomputes J, R and G as prep_kernel does, and walks the chain from the leaves:
+//        gGr_j = gA_j[:, :3] - gA_j[:, 3] (x) J_j,  gGt_j = gA_j[:, 3] + gJtr_j,  gJ_j = -Gr_j^T gA_j[:, 3]
+//        i = NC-1 .. 1, p = parent(i), rel = J_i - J_p:  gR_i += Gr_p^T gGr_i;  gGr_p += gGr_i R_i^T + gGt_i (x) rel;
+//                                                         gGt_p += gGt_i;  grel = Gr_p^T gGt_i;  gJ_i += grel;  gJ_p -= grel
+//        gR_0 += gGr_0,  gJ_0 += gGt_0,  gbeta += sum_{j,i} Jsd[j][i][.] gJ_j[i]
+//      (parents[i] < i, as the forward assumes: every child of i has been folded into i before i is read). ----
+template <int NC, int KX, int KS>
+__global__ __launch_bounds__(128) void lbs_chain_backward_kernel(const float* __restrict__ rotmat, const float* __restrict__ betas,
+                                                                 const float* __restrict__ Jt, const float* __restrict__ Jsd,
+                                                                 const int32_t* __restrict__ parents, const int32_t* __restrict__ jmap,
+                                                                 const int32_t* __restrict__ update_hips, const float* __restrict__ gJo,
+                                                                 const float* __restrict__ gApart, const float* __restrict__ planes,
+                                                                 float* __restrict__ grad_rotmat, float* __restrict__ grad_betas,
+                                                                 int B) {
+    constexpr int NMAP = 25;
+    __shared__ float J[NC][3], R[NC][9], Gr[NC][9], Gt[NC][3], bs[NB];
+    __shared__ float gA[NC][12], gx[KX], gm[NMAP][3];
+    __shared__ float gGr[NC][9], gGt[NC][3], gJ[NC][3], gR[NC][9];
+    const int b = blockIdx.x, t = threadIdx.x;
+    for (int i = t; i < NC * 9; i += 128) R[i / 9][i % 9] = rotmat[(int64_t)b * NC * 9 + i];
+    if (t < NB) bs[t] = betas[(int64_t)b * NB + t];
+    for (int i = t; i < NC * 12; i += 128) {
+        float acc = 0.f;      // the loads of a sum are independent and issued together (compile-time counts); the adds keep their order
+#pragma unroll
+        for (int k = 0; k < SKB; ++k) acc += gApart[((int64_t)b * SKB + k) * (NC * 12) + i];
+        gA[i / 12][i % 12] = acc;
+    }
+    for (int i = t; i < KX; i += 128) {
+        float acc = 0.f;
+#pragma unroll
+        for (int sp = 0; sp < KS; ++sp) acc += planes[((int64_t)sp * B + b) * KX + i];
+        gx[i] = acc;
+    }
+    if (t < NMAP * 3) {                  // the mapped joints' gradient, update_hips' adjoint applied (as lbs_skin_backward_kernel)
+        float v = 0.f;
+        if (gJo) {
+            const float* q = gJo + (int64_t)b * 132;
+            const int j = t / 3, i = t % 3;
+            const bool hips = *update_hips != 0;
+            v = q[t];
+            if (hips && j == 9) v = v - 0.5f * q[12 * 3 + i];
+            if (hips && j == 12) v = v - 0.5f * q[9 * 3 + i];
+            if (hips && j == 8) v = v + 0.5f * (q[9 * 3 + i] + q[12 * 3 + i]);
+        }
+        gm[t / 3][t % 3] = v;
+    }
+    __syncthreads();
+    for (int i = t; i < NC * 3; i += 128) {
+        float v = 0.f;
+#pragma unroll
+        for (int l = 0; l < NB; ++l) v = fmaf(bs[l], Jsd[i * NB + l], v);
+        J[i / 3][i % 3] = Jt[i] + v;
+    }
+    __syncthreads();
+    // the forward chain, rotation and translation parts apart: Gr_i = Gr_p R_i, Gt_i = Gr_p (J_i - J_p) + Gt_p
+    if (t < 9) Gr[0][t] = R[0][t];
+    if (t >= 9 && t < 12) Gt[0][t - 9] = J[0][t - 9];
+    __syncthreads();
+    for (int i = 1; i < NC; ++i) {
+        const int p = parents[i];
+        if (t < 9) {
+            const int r = t / 3, c = t % 3;
+            Gr[i][t] = Gr[p][r * 3 + 0] * R[i][0 * 3 + c] + Gr[p][r * 3 + 1] * R[i][1 * 3 + c] + Gr[p][r * 3 + 2] * R[i][2 * 3 + c];
+        } else if (t < 12) {
+            const int r = t - 9;
+            const float rx = J[i][0] - J[p][0], ry = J[i][1] - J[p][1], rz = J[i][2] - J[p][2];
+            Gt[i][r] = Gr[p][r * 3 + 0] * rx + Gr[p][r * 3 + 1] * ry + Gr[p][r * 3 + 2] * rz + Gt[p][r];
+        }
+        __syncthreads();
+    }
+    // the adjoints of A_j = [Gr_j | Gt_j - Gr_j J_j] and of the posed joints (joint_map slots below NC, in slot order)
+    for (int i = t; i < NC * 9; i += 128) {
+        const int j = i / 9, r = (i % 9) / 3, c = i % 3;
+        gGr[j][i % 9] = gA[j][r * 4 + c] - gA[j][r * 4 + 3] * J[j][c];
+        gR[j][i % 9] = (j >= 1 && 10 + (j - 1) * 9 + i % 9 < KX) ? gx[10 + (j - 1) * 9 + i % 9] : 0.f;
+    }
+    for (int i = t; i < NC * 3; i += 128) {
+        const int j = i / 3, r = i % 3;
+        float v = gA[j][r * 4 + 3];
+        for (int s = 0; s < NMAP; ++s)
+            if (jmap[s] == j) v += gm[s][r];
+        gGt[j][r] = v;
+        gJ[j][r] = -(Gr[j][0 * 3 + r] * gA[j][0 * 4 + 3] + Gr[j][1 * 3 + r] * gA[j][1 * 4 + 3] + Gr[j][2 * 3 + r] * gA[j][2 * 4 + 3]);
+    }
+    __syncthreads();
+    for (int i = NC - 1; i >= 1; --i) {
+        const int p = parents[i];
+        if (t < 9) {                         // gR_i += Gr_p^T gGr_i
+            const int r = t / 3, c = t % 3;
+            gR[i][t] += Gr[p][0 * 3 + r] * gGr[i][0 * 3 + c] + Gr[p][1 * 3 + r] * gGr[i][1 * 3 + c] + Gr[p][2 * 3 + r] * gGr[i][2 * 3 + c];
+        } else if (t < 18) {                 // gGr_p += gGr_i R_i^T + gGt_i (x) rel
+            const int e = t - 9, r = e / 3, c = e % 3;
+            gGr[p][e] += (gGr[i][r * 3 + 0] * R[i][c * 3 + 0] + gGr[i][r * 3 + 1] * R[i][c * 3 + 1] + gGr[i][r * 3 + 2] * R[i][c * 3 + 2]) +
+                         gGt[i][r] * (J[i][c] - J[p][c]);
+        } else if (t < 21) {                 // gGt_p += gGt_i
+            gGt[p][t - 18] += gGt[i][t - 18];
+        } else if (t < 24) {                 // grel = Gr_p^T gGt_i;  gJ_i += grel;  gJ_p -= grel
+            const int r = t - 21;
+            const float grel = Gr[p][0 * 3 + r] * gGt[i][0] + Gr[p][1 * 3 + r] * gGt[i][1] + Gr[p][2 * 3 + r] * gGt[i][2];
+            gJ[i][r] += grel;
+            gJ[p][r] -= grel;
+        }
+        __syncthreads();
+    }
+    if (t < 9) gR[0][t] += gGr[0][t];
+    if (t >= 9 && t < 12) gJ[0][t - 9] += gGt[0][t - 9];
+    __syncthreads();
+    if (grad_rotmat)
+        for (int i = t; i < NC * 9; i += 128) grad_rotmat[(int64_t)b * NC * 9 + i] = gR[i / 9][i % 9];
+    if (grad_betas && t < NB) {
+        float v = gx[t];
+#pragma unroll
+        for (int i = 0; i < NC * 3; ++i) v = fmaf(Jsd[i * NB + t], gJ[i / 3][i % 3], v);
+        grad_betas[(int64_t)b * NB + t] = v;
+    }
+}
+
+// the adjoint of rodrigues_kernel's own formula: e = r + 1e-8, a = |e|, d = r / a, R = I + sin a K(d) + (1 - cos a) (d d^T - |d|^2 I).
+// 1 - cos a is evaluated as 2 sin^2(a / 2): in fp32 the plain form has lost every digit below a ~ 3e-4 rad
+__global__ void rodrigues_backward_kernel(const float* __restrict__ aa, const float* __restrict__ gR, float* __restrict__ gaa, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = aa[i * 3 + 0], y = aa[i * 3 + 1], z = aa[i * 3 + 2];
+    const float ex = x + 1e-8f, ey = y + 1e-8f, ez = z + 1e-8f;
+    const float a = sqrtf(ex * ex + ey * ey + ez * ez);
+    const float dx = x / a, dy = y / a, dz = z / a;
+    const float s = sinf(a), c = cosf(a), sh = sinf(0.5f * a), oc = 2.0f * sh * sh;
+    const float* G = gR + (int64_t)i * 9;
+    const float g00 = G[0], g01 = G[1], g02 = G[2], g10 = G[3], g11 = G[4], g12 = G[5], g20 = G[6], g21 = G[7], g22 = G[8];
+    const float wx = g21 - g12, wy = g02 - g20, wz = g10 - g01;         // sum(G o K(d)) = w . d
+    const float tr = g00 + g11 + g22;
+    const float sx = (g00 + g00) * dx + (g01 + g10) * dy + (g02 + g20) * dz;   // (G + G^T) d
+    const float sy = (g10 + g01) * dx + (g11 + g11) * dy + (g12 + g21) * dz;
+    const float sz = (g20 + g02) * dx + (g21 + g12) * dy + (g22 + g22) * dz;
+    const float dd = dx * dx + dy * dy + dz * dz;
+    const float gs = wx * dx + wy * dy + wz * dz;
+    const float goc = 0.5f * (sx * dx + sy * dy + sz * dz) - dd * tr;    // d^T G d - |d|^2 tr G
+    const float gdx = s * wx + oc * (sx - 2.0f * tr * dx), gdy = s * wy + oc * (sy - 2.0f * tr * dy), gdz = s * wz + oc * (sz - 2.0f * tr * dz);
+    const float ga = (gs * c + goc * s) - (gdx * x + gdy * y + gdz * z) / (a * a);
+    gaa[i * 3 + 0] = gdx / a + ga * (ex / a);
+    gaa[i * 3 + 1] = gdy / a + ga * (ey / a);
+    gaa[i * 3 + 2] = gdz / a + ga * (ez / a);
+}
+
 // v_posed (B x 20670) = xf (B x kx) . dirs^T + v_template
 int launch_blend(const float* xf, const float* dirsT, const float* vt, float* vposed, int B, int kx, hipStream_t s) {
     GemmArgs g{};
@@ -416,7 +713,49 @@ int launch_blend(const float* xf, const float* dirsT, const float* vt, float* vp
 // elsewhere
 int smplh_poses_per_workgroup(int B) { return B >= 256 ? 8 : (B >= 128 ? 4 : (B >= 64 ? 2 : 1)); }
 
+// crops per SMPL skin workgroup pass, forward and backward: reuse of the per-vertex constants only pays once the grid already fills the
+// chip several times (64 crops: 2 -> 864 workgroups; 256 crops and up: 8)
+int lbs_crops_per_pass(int B) { return B >= 32 * CG_MAX ? CG_MAX : (B >= 32 ? B / 32 : 1); }
+
+void launch_lbs_prep(const LbsArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((prep_kernel<NJ, NJ, THMR_LBS_KX, SMPL>), dim3(a.B), dim3(128), 0, s, a.rotmat, a.betas, nullptr, a.Jt, a.Jsd, a.parents,
+                       nullptr, a.A, a.xf, a.Jtr, a.cnt, nullptr);
+}
+
 }  // namespace
+
+int launch_body_build_dirs_k(const float* dirsT, float* dirsK, int kx, hipStream_t s) {
+    const int64_t total = (int64_t)kx * THMR_LBS_GK;
+    hipLaunchKernelGGL(build_dirs_k_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dirsT, dirsK, kx);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_rodrigues_backward(const float* aa, const float* gR, float* gaa, int n, hipStream_t s) {
+    hipLaunchKernelGGL(rodrigues_backward_kernel, dim3((n + 255) / 256), dim3(256), 0, s, aa, gR, gaa, n);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// prep -> blend GEMM (the forward's, recomputed) -> skin-backward -> blend GEMM reversed -> chain-backward: five launches
+int launch_lbs_backward(const LbsArgs& a, const LbsGradArgs& g, hipStream_t s) {
+    const int B = a.B;
+    if (B < 1 || (!g.gV && !g.gJ) || (!g.grad_rotmat && !g.grad_betas)) return -1;
+    launch_lbs_prep(a, s);
+    if (int r = launch_blend(a.xf, a.dirsT, a.vt, a.vposed, B, THMR_LBS_KX, s)) return r;
+    const int cg = lbs_crops_per_pass(B);
+    hipLaunchKernelGGL((lbs_skin_backward_kernel<NJ>), dim3(SKB, (B + cg - 1) / cg), dim3(256), 0, s, a.vposed, a.W, a.A, a.J19, a.extra,
+                       a.jmap, a.update_hips, g.gV, g.gJ, g.gvp, g.gApart, B, cg);
+    if (hipGetLastError() != hipSuccess) return -2;
+    // gx (B x 224) = g_vposed (B x 20672) . dirsK^T: M = B is skinny and N = 224 is two tiles, so K is split THMR_LBS_GKSPLIT = 38 ways (544
+    // = 17 K tiles per slice) to put 76 workgroups per 64 crops on the chip; ONE tile shape (64 x 128) at every batch size, so no
+    // dispatch switch exists between sizes (every shape sums a slice's K in the same order anyway, gemm_f32.hip)
+    GemmArgs ga{};
+    ga.A = g.gvp; ga.lda = THMR_LBS_GK; ga.W = g.dirsK; ga.ldw = THMR_LBS_GK; ga.M = B; ga.N = THMR_LBS_KX; ga.K = THMR_LBS_GK;
+    ga.qscale = 1.f;
+    if (int r = launch_gemm_splitk(ga, 12, THMR_LBS_GKSPLIT, g.planes, s)) return r;
+    hipLaunchKernelGGL((lbs_chain_backward_kernel<NJ, THMR_LBS_KX, THMR_LBS_GKSPLIT>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, a.Jt,
+                       a.Jsd, a.parents, a.jmap, a.update_hips, g.gJ, g.gApart, g.planes, g.grad_rotmat, g.grad_betas, B);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 
 int launch_rodrigues(const float* aa, float* R, int n, hipStream_t s) {
     hipLaunchKernelGGL(rodrigues_kernel, dim3((n + 255) / 256), dim3(256), 0, s, aa, R, n);
@@ -441,14 +780,11 @@ int launch_smplh_fold_weights(const float* W, const int32_t* fold, float* Wf, hi
 
 int launch_lbs(const LbsArgs& a, hipStream_t s) {
     const int B = a.B;
-    hipLaunchKernelGGL((prep_kernel<NJ, NJ, THMR_LBS_KX, SMPL>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, nullptr, a.Jt, a.Jsd, a.parents,
-                       nullptr, a.A, a.xf, a.Jtr, a.cnt, nullptr);
+    launch_lbs_prep(a, s);
     if (int r = launch_blend(a.xf, a.dirsT, a.vt, a.vposed, B, THMR_LBS_KX, s)) return r;
     // the J19 partial sums live behind the (B,224) operand rows in the xf scratch: B * 27 * 57 floats
     float* jpart = a.xf + (size_t)B * THMR_LBS_KX;
-    // crops per workgroup pass: reuse of the per-vertex constants only pays once the grid already fills the chip several times
-    // (64 crops: 2 -> 864 workgroups; 256 crops and up: 8)
-    const int cg = B >= 32 * CG_MAX ? CG_MAX : (B >= 32 ? B / 32 : 1);
+    const int cg = lbs_crops_per_pass(B);
     hipLaunchKernelGGL(lbs_skin_joints_kernel, dim3(SKB, (B + cg - 1) / cg), dim3(256), 0, s, a.vposed, a.W, a.A, a.J19, a.Jtr, a.extra,
                        a.jmap, a.update_hips, a.cam_t, a.verts, jpart, a.xv, a.cnt, a.joints, a.kp2d, a.focal_over_size, B, cg);
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -502,6 +502,19 @@ struct LbsArgs {
     int B;
 };
 int launch_lbs(const LbsArgs& a, hipStream_t s);
+// SMPL's vector-Jacobian product (body_model.hip): the forward's prep + blend recomputed into a.A / a.xf / a.Jtr / a.vposed,
+// then skin-backward -> the blend GEMM's reverse (split-K, THMR_LBS_GKSPLIT planes) -> chain-backward.  In `a`: rotmat, betas, the
+// constants and the scratch of launch_lbs (verts, joints, kp2d, cam_t, xv unused).  g_vposed rows are padded to the GEMM's 32-deep K tile.
+constexpr int THMR_LBS_GK = 20672, THMR_LBS_GKSPLIT = 38, THMR_LBS_GA = 27 * 24 * 12;     // K = 32 * 2 * 17 * 19; bone-matrix partials per crop
+struct LbsGradArgs {
+    const float *gV, *gJ;             // (B,6890,3), (B,44,3): either may be null (zeros), not both
+    const float* dirsK;               // (224, 20672) K-contiguous: dirsT transposed, the two pad columns zero (launch_body_build_dirs_k)
+    float *gvp, *gApart, *planes;     // scratch: (B,20672), (B,27,288), (THMR_LBS_GKSPLIT,B,224)
+    float *grad_rotmat, *grad_betas;  // (B,24,3,3), (B,10): either may be null, not both
+};
+int launch_body_build_dirs_k(const float* dirsT, float* dirsK, int kx, hipStream_t s);
+int launch_lbs_backward(const LbsArgs& a, const LbsGradArgs& g, hipStream_t s);
+int launch_rodrigues_backward(const float* aa, const float* gR, float* gaa, int n, hipStream_t s);
 // SMPL-H, 52 chain joints (22 body + 2 x 15 hand) and 73 output joints; the folded body-only path works on 22 joints, its weight table
 // padded to 24 columns.  dirsT (20670 x 480) = [shapedirs | posedirs (459) | 0]^T, dirsT_body (20670 x 224) = [shapedirs | the 189 body
 // features | 0]^T; scratch A (B,52,12), xf (B,480), vposed (B,20670)

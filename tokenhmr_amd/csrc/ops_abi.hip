@@ -294,6 +294,13 @@ int thmr_op_vq_stats(const float* x, const float* codebook, const int32_t* idx, 
     return 0;
 }
 
+int thmr_op_aa_to_rotmat_backward(const float* aa, const float* grad_R, float* grad_aa, int32_t n, void* stream) {
+    if (!aa || !grad_R || !grad_aa) return fail(THMR_ERR_INVALID, "aa_to_rotmat_backward: null buffer");
+    if (n <= 0) return fail(THMR_ERR_INVALID, "aa_to_rotmat_backward: n >= 1 is required");
+    LAUNCH_OK(launch_rodrigues_backward(aa, grad_R, grad_aa, n, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int thmr_op_rotmat_to_aa(const float* R, float* aa, int32_t n, void* stream) {
     if (!R || !aa) return fail(THMR_ERR_INVALID, "rotmat_to_aa: null buffer");
     if (n <= 0) return fail(THMR_ERR_INVALID, "rotmat_to_aa: n >= 1 is required");
@@ -333,6 +340,11 @@ struct thmr_smpl {
     int max_batch = 0;
     SmplConsts c;
     size_t o_A, o_pf, o_Jtr, o_vposed, o_rot, o_joints, o_xv, o_cnt, total;
+    // the backward's own allocation (thmr_smpl_grad_reserve): dirs (224, 20672), g_vposed (B, 20672), the bone-matrix partials (B, 27, 288),
+    // the split-K planes (38, B, 224) and, for pose2rot, the rotation matrices' gradient (B, 24, 9)
+    float* gmem = nullptr;
+    int device = 0;
+    size_t g_dirs, g_vp, g_part, g_planes, g_rot;
 };
 
 int thmr_smpl_create(const thmr_smpl_desc* d, int32_t max_batch, int32_t device, thmr_smpl** out) {
@@ -344,6 +356,7 @@ int thmr_smpl_create(const thmr_smpl_desc* d, int32_t max_batch, int32_t device,
     HIP_OK(hipSetDevice(device));
     thmr_smpl* m = new thmr_smpl();
     m->max_batch = max_batch;
+    m->device = device;
     size_t off = m->c.lay(0);
     auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
     const size_t B = (size_t)max_batch;
@@ -367,6 +380,7 @@ int thmr_smpl_create(const thmr_smpl_desc* d, int32_t max_batch, int32_t device,
 void thmr_smpl_destroy(thmr_smpl* m) {
     if (!m) return;
     if (m->mem) (void)hipFree(m->mem);
+    if (m->gmem) (void)hipFree(m->gmem);
     delete m;
 }
 
@@ -388,6 +402,55 @@ int thmr_smpl_forward(thmr_smpl* m, const float* pose, int32_t pose2rot, const f
     a.verts = verts; a.joints = joints ? joints : m->mem + m->o_joints;
     a.focal_over_size = FOCAL / IMG; a.B = B;
     LAUNCH_OK(launch_lbs(a, st));
+    return 0;
+}
+
+int thmr_smpl_grad_reserve(thmr_smpl* m) {
+    if (!m) return fail(THMR_ERR_INVALID, "smpl_grad_reserve: null handle");
+    if (m->gmem) return 0;
+    HIP_OK(hipSetDevice(m->device));
+    size_t off = 0;
+    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
+    const size_t B = (size_t)m->max_batch;
+    m->g_dirs = take((size_t)THMR_LBS_KX * THMR_LBS_GK); m->g_vp = take(B * THMR_LBS_GK); m->g_part = take(B * THMR_LBS_GA);
+    m->g_planes = take((size_t)THMR_LBS_GKSPLIT * B * THMR_LBS_KX); m->g_rot = take(B * NJ * 9);
+    float* g = nullptr;
+    if (hipMalloc(&g, off * sizeof(float)) != hipSuccess) return fail(THMR_ERR_NOMEM, "hipMalloc(smpl backward workspace) failed");
+    if (launch_body_build_dirs_k(m->mem + m->c.dirs, g + m->g_dirs, THMR_LBS_KX, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(g);
+        return fail(THMR_ERR_HIP, "smpl_grad_reserve: building the transposed blend-shape matrix failed");
+    }
+    m->gmem = g;
+    return 0;
+}
+
+int thmr_smpl_backward(thmr_smpl* m, const float* pose, int32_t pose2rot, const float* betas, int32_t B, const float* grad_verts,
+                       const float* grad_joints, float* grad_pose, float* grad_betas, void* stream) {
+    if (!m || !pose || !betas) return fail(THMR_ERR_INVALID, "smpl_backward: null handle, pose or betas");
+    if (!grad_verts && !grad_joints) return fail(THMR_ERR_INVALID, "smpl_backward: grad_verts and grad_joints are both null");
+    if (!grad_pose && !grad_betas) return fail(THMR_ERR_INVALID, "smpl_backward: grad_pose and grad_betas are both null");
+    if (B < 1 || B > m->max_batch) return fail(THMR_ERR_INVALID, "smpl_backward: batch outside [1, max_batch]");
+    if (pose2rot != 0 && pose2rot != 1) return fail(THMR_ERR_INVALID, "smpl_backward: pose2rot is 0 or 1");
+    if (!m->gmem) return fail(THMR_ERR_INVALID, "smpl_backward: call thmr_smpl_grad_reserve on this handle first");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float* rot = pose;
+    if (pose2rot) {
+        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * NJ, st));
+        rot = m->mem + m->o_rot;
+    }
+    LbsArgs a{};
+    m->c.fill(a, m->mem);
+    a.rotmat = rot; a.betas = betas;
+    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_pf; a.Jtr = m->mem + m->o_Jtr; a.vposed = m->mem + m->o_vposed;
+    a.cnt = reinterpret_cast<unsigned*>(m->mem + m->o_cnt);
+    a.B = B;
+    LbsGradArgs g{};
+    g.gV = grad_verts; g.gJ = grad_joints; g.dirsK = m->gmem + m->g_dirs;
+    g.gvp = m->gmem + m->g_vp; g.gApart = m->gmem + m->g_part; g.planes = m->gmem + m->g_planes;
+    g.grad_rotmat = !grad_pose ? nullptr : (pose2rot ? m->gmem + m->g_rot : grad_pose);
+    g.grad_betas = grad_betas;
+    LAUNCH_OK(launch_lbs_backward(a, g, st));
+    if (pose2rot && grad_pose) LAUNCH_OK(launch_rodrigues_backward(pose, m->gmem + m->g_rot, grad_pose, B * NJ, st));
     return 0;
 }
 

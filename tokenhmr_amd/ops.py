@@ -303,12 +303,38 @@ def rot6d_to_rotmat(x):
 def aa_to_rotmat(theta):
     """geometry.py:5-44 aa_to_rotmat: (n,3) axis-angle -> (n,3,3)."""
     _req(theta)
-    x = theta.reshape(-1, 3).contiguous()
+    if torch.is_grad_enabled() and theta.requires_grad:
+        return _AaToRotmatFn.apply(theta.reshape(-1, 3))      # the reshape carries the gradient back to theta's own shape
+    return _aa_to_rotmat(theta.reshape(-1, 3).contiguous())
+
+
+def _aa_to_rotmat(x):
     n = x.shape[0]
-    R = torch.empty(n, 3, 3, device=theta.device, dtype=torch.float32)
-    with torch.cuda.device(theta.device):
-        _check(_L().thmr_op_aa_to_rotmat(_p(x), _p(R), n, _s(theta)))
+    R = torch.empty(n, 3, 3, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_aa_to_rotmat(_p(x), _p(R), n, _s(x)))
     return R
+
+
+class _AaToRotmatFn(torch.autograd.Function):
+    """aa_to_rotmat under autograd: backward = thmr_op_aa_to_rotmat_backward (csrc/body_model.hip rodrigues_backward_kernel), once
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return _aa_to_rotmat(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gR):
+        x, = ctx.saved_tensors
+        gR = gR.to(torch.float32).contiguous()
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _check(_L().thmr_op_aa_to_rotmat_backward(_p(x), _p(gR), _p(g), x.shape[0], _s(x)))
+        return g
 
 
 # ---- the row, glue and head kernels (csrc/rowops.hip, head.hip, hmr2_head.hip), each as the engine launches it ----
