@@ -362,6 +362,11 @@ int thmr_op_vit_attention_split3(const float* qkv_dev, void* out_split_dev, int3
 int thmr_op_vit_attention_b16(const float* qkv_dev, void* out_dev, int32_t B, int32_t out_split, int32_t qt, void* stream);
 /* rot6d_to_rotmat (geometry.py:64-84): (n,6) -> (n,3,3) */
 int thmr_op_rot6d(const float* x_dev, float* R_dev, int32_t n, void* stream);
+/* grad_x (n,6) = the vector-Jacobian product of thmr_op_rot6d with grad_R (n,3,3): the adjoint of the Gram-Schmidt step as
+ * rotation_6d_to_matrix (tokenization/models/rotation_utils.py:510-531) and geometry.rot6d_to_rotmat write it — b1 = normalize(a1),
+ * b2 = normalize(a2 - (b1 . a2) b1), b3 = b1 x b2, rows stacked, F.normalize's clamp of the norm at 1e-12 included (below the clamp the
+ * normalisation is a division by a constant, as autograd has it).  Stateless, one launch, elementwise per rotation. */
+int thmr_op_rot6d_backward(const float* x_dev, const float* grad_R_dev, float* grad_x_dev, int32_t n, void* stream);
 /* aa_to_rotmat (geometry.py:5-44; axis-angle -> quaternion -> rotation matrix, the reference's in-tree "Rodrigues" used for
  * ground-truth poses at tokenhmr.py:235,260,357): (n,3) -> (n,3,3) */
 int thmr_op_aa_to_rotmat(const float* aa_dev, float* R_dev, int32_t n, void* stream);
@@ -508,6 +513,57 @@ void thmr_smplh_destroy(thmr_smplh* m);
 int  thmr_smplh_forward(thmr_smplh* m, const float* pose_dev, int32_t pose2rot, const float* betas_dev, const float* transl_dev,
                         int32_t body_only, int32_t B, float* verts_dev /*(B,6890,3)*/, float* joints_dev /*(B,73,3) or NULL*/,
                         void* stream);
+/* SMPL-H's vector-Jacobian product, both paths: what smplx.SMPLH / SMPLHLayer give under torch autograd.  New symbols
+ * under ABI 5: no struct or signature changed.
+ * thmr_smplh_grad_reserve, the one-time call: `paths` is a mask of THMR_SMPLH_GRAD_FOLDED (body_only = 1) and THMR_SMPLH_GRAD_FULL.  Per
+ * requested path it allocates the backward workspace and builds the transposed copy of that path's blend-shape matrix, (224, 20672) folded
+ * and (480, 20672) full — the full copy is 40 MB, so a handle pays only for what it asks for.  It may allocate and synchronise; a path
+ * already reserved is skipped.  A handle that never calls it keeps the footprint it had.
+ * thmr_smplh_backward takes the inputs of the forward it differentiates (it recomputes the forward's intermediates into the handle's
+ * workspace, so forwards issued in between do not matter) and the gradients of the two outputs; a NULL gradient input means zeros, a NULL
+ * output is not computed.  grad_pose_dev has the layout of pose_dev, (B,52,3,3) / (B,156) or with body_only (B,22,3,3) / (B,66): the
+ * plain derivative by each matrix entry, as autograd gives it.  betas_dev and transl_dev may be NULL, as in the forward.  It never
+ * allocates and never synchronises: five launches (seven with pose2rot) on `stream`, capturable in a graph.  No floating-point atomics:
+ * every sum has a fixed order, so the result is bit-reproducible and a pose's gradient does not depend on the rest of the batch.
+ * THMR_ERR_INVALID (message in thmr_last_error(NULL)) before any launch for a null handle or pose, both gradient inputs null, every output
+ * null, B outside [1, max_batch], a pose2rot or body_only that is not 0 or 1, a path that was not reserved. */
+#define THMR_SMPLH_GRAD_FOLDED 1
+#define THMR_SMPLH_GRAD_FULL 2
+int  thmr_smplh_grad_reserve(thmr_smplh* m, int32_t paths);
+int  thmr_smplh_backward(thmr_smplh* m, const float* pose_dev, int32_t pose2rot, const float* betas_dev, const float* transl_dev,
+                         int32_t body_only, int32_t B, const float* grad_verts_dev /*(B,6890,3) or NULL*/,
+                         const float* grad_joints_dev /*(B,73,3) or NULL*/, float* grad_pose_dev /*may be NULL*/,
+                         float* grad_betas_dev /*(B,10); may be NULL*/, float* grad_transl_dev /*(B,3); may be NULL*/, void* stream);
+/* The tokenizer's reconstruction objective, value and gradient in one call (csrc/loss.hip): PoseReConsLoss
+ * (tokenization/utils/losses.py:65-131) with the weighted total of tokenization/train_poseVQ.py:152-156.  Stateless, fp32 contiguous device
+ * buffers, two launches, no allocation, no synchronisation; fixed-order two-stage reduction (fp32 partials, fp64 finish) without float
+ * atomics, so two runs are bit-equal; the results stay on the device.
+ *   pred / gt rotation matrices (B,21,3,3), vertices (B,6890,3), joints (B,73,3); vert_weights (6890,3) or NULL (required by 'wt_l2' on the
+ *   mesh); commit: one device float or NULL (zero).  A term whose prediction and ground truth are both NULL is absent: its mean is 0 and
+ *   it has no gradient (at least one term is present).  A kind is THMR_RECON_L1 / _L2 / _L1_SMOOTH (torch's L1Loss / MSELoss / SmoothL1Loss,
+ *   beta = 1, mean reduction) or _WT_L2 (mean(w (a - b)^2); on the pose and the joints the reference's weights are all ones, so it is _L2
+ *   there).  THMR_RECON_GEODESIC and _ROTDIST are refused by name (THMR_ERR_UNSUPPORTED): acos at their clamp has no finite gradient.
+ *   The joint term runs over joint rows [joint_lo, joint_hi): [1, 22) for ONLY_VALID_JNT, [0, 73) otherwise.
+ *   losses_dev (4): the three unweighted means (pose, mesh, joints) and total = w_total (w_pose pose + w_mesh mesh + w_joint joints +
+ *   w_commit commit).  grad_*_dev: the gradient of that TOTAL by the predicted tensor, same shape; any may be NULL.  At the kinks torch's
+ *   conventions: l1 gives 0 at a zero difference, l1_smooth is continuous at |d| = 1.  Joints outside the row range get a written zero.
+ *   workspace_dev: THMR_TOK_RECON_WS_BASE + B * THMR_TOK_RECON_WS_PER_ITEM floats, written before it is read in every call.
+ * Refused before any launch: a null required buffer, B outside [1, 2^16], an unknown kind, a joint range outside
+ * 0 <= joint_lo < joint_hi <= 73. */
+#define THMR_RECON_L1 0
+#define THMR_RECON_L2 1
+#define THMR_RECON_L1_SMOOTH 2
+#define THMR_RECON_WT_L2 3
+#define THMR_RECON_GEODESIC 4
+#define THMR_RECON_ROTDIST 5
+#define THMR_TOK_RECON_WS_BASE 3
+#define THMR_TOK_RECON_WS_PER_ITEM 21
+int thmr_tok_recon_loss(const float* pred_rotmat_dev, const float* gt_rotmat_dev, const float* pred_verts_dev, const float* gt_verts_dev,
+                        const float* pred_joints_dev, const float* gt_joints_dev, const float* vert_weights_or_null,
+                        const float* commit_or_null, int32_t pose_kind, int32_t mesh_kind, int32_t joint_kind, int32_t joint_lo,
+                        int32_t joint_hi, double w_pose, double w_mesh, double w_joint, double w_commit, double w_total, int32_t B,
+                        float* losses_dev, float* grad_rotmat_or_null, float* grad_verts_or_null, float* grad_joints_or_null,
+                        float* workspace_dev, void* stream);
 /* out_dev[0] = mean over items b < B and rows row_lo <= i < row_hi of || a[b][i] - b[b][i] ||_2, a and b (B, n_rows_per_item, 3): the three
  * errors of the tokenizer's evaluation (tokenization/utils/eval_poseVQ.py) are this one operator —
  *   calculate_pose_reconstruction_error :47-48   rows of the rotation matrices:  n = 63 (21 matrices x 3 rows), rows [0, 63)

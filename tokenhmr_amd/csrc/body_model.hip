@@ -34,8 +34,9 @@
 //     into its wrist's once at creation (22 columns, padded to 24) and the pose correctives keep only the 21 body joints' 189 features
 //     (K = 199 -> 224).  The skin loop reads 66 broadcast float4 per pose instead of 156: the LDS return traffic that is this kernel's
 //     bound.  The posed HAND joints come from the wrist's transform applied to their rest position.
-//   * SMPL's backward (thmr_smpl_backward), further down: the forward's prep and blend GEMM recomputed, then skin-backward on SkinLane,
-//     the blend GEMM reversed and chain-backward, the mirror of prep.
+//   * the backward of both models (thmr_smpl_backward, thmr_smplh_backward for either path), further down: the forward's prep and blend GEMM
+//     recomputed, then skin-backward on SkinLane, the blend GEMM reversed and chain-backward, the mirror of prep — one pair of kernel
+//     templates, the model's joint finish under `if constexpr`.
 #include "common.h"
 
 namespace {
@@ -210,10 +211,9 @@ struct SkinLane {
             if (tid < NS * 3) AS[0][tid] = reinterpret_cast<const f32x4*>(A + (int64_t)b0 * NS * 12)[tid];
         }
     }
-    // crop b, the c-th of this pass; the caller's __syncthreads() came first: AS[c & 1] is complete.  The vertex's blended 3x4 transform
-    // (rows T0, T1, T2) and its posed rest position: what the forward applies (skin) and the backward transposes (lbs_skin_backward_kernel)
-    __device__ __forceinline__ void transform(const f32x4 (*AS)[NS * 3], const float* __restrict__ vposed, const float* __restrict__ A,
-                                              int c, int b, int B, int CG, f32x4& T0, f32x4& T1, f32x4& T2, float& x, float& y, float& z) {
+    // hands out the posed vertex of crop b and requests crop b + 1's vertex and bone matrices
+    __device__ __forceinline__ void advance(const float* __restrict__ vposed, const float* __restrict__ A, int c, int b, int B, int CG,
+                                            float& x, float& y, float& z) {
         x = xn, y = yn, z = zn;
         more = c + 1 < CG && b + 1 < B;
         if (more) {
@@ -221,6 +221,12 @@ struct SkinLane {
             xn = p[0]; yn = p[1]; zn = p[2];
             if (tid < NS * 3) an = reinterpret_cast<const f32x4*>(A + (int64_t)(b + 1) * NS * 12)[tid];
         }
+    }
+    // crop b, the c-th of this pass; the caller's __syncthreads() came first: AS[c & 1] is complete.  The vertex's blended 3x4 transform
+    // (rows T0, T1, T2) and its posed rest position: what the forward applies (skin) and the backward transposes (lbs_skin_backward_kernel)
+    __device__ __forceinline__ void transform(const f32x4 (*AS)[NS * 3], const float* __restrict__ vposed, const float* __restrict__ A,
+                                              int c, int b, int B, int CG, f32x4& T0, f32x4& T1, f32x4& T2, float& x, float& y, float& z) {
+        advance(vposed, A, c, b, B, CG, x, y, z);
         // (Round 3 also tried the bone matrices as SCALAR loads — 288 floats into SGPRs, one SGPR operand per FMA, no LDS return
         // traffic: each new crop misses the scalar cache and the 12 dependent s_load round trips per crop made the kernel slower,
         // 161 vs 142 us at 512 crops, profiles/r3b_lbs_scalar_loads.log.)
@@ -232,6 +238,27 @@ struct SkinLane {
             T0 += w * ASc[j * 3 + 0];
             T1 += w * ASc[j * 3 + 1];
             T2 += w * ASc[j * 3 + 2];
+        }
+    }
+    // the same transform with the joint loop rolled, four joints per trip, the weights read again from the table: for a kernel that has no
+    // registers left for NS weights and the NS * 3 rows the unrolled loop keeps in flight (the 52-joint skin-backward)
+    __device__ __forceinline__ void transform_rolled(const f32x4 (*AS)[NS * 3], const float* __restrict__ vposed, const float* __restrict__ W,
+                                                     const float* __restrict__ A, int c, int b, int B, int CG, f32x4& T0, f32x4& T1, f32x4& T2,
+                                                     float& x, float& y, float& z) {
+        advance(vposed, A, c, b, B, CG, x, y, z);
+        const f32x4* ASc = AS[c & 1];
+        const f32x4* wr = reinterpret_cast<const f32x4*>(W + (int64_t)vv * NSP);
+        T0 = f32x4{0.f, 0.f, 0.f, 0.f}, T1 = T0, T2 = T0;
+#pragma unroll 1
+        for (int q = 0; q < NS / 4; ++q) {
+            const f32x4 w4 = wr[q];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int j = q * 4 + k;
+                T0 += w4[k] * ASc[j * 3 + 0];
+                T1 += w4[k] * ASc[j * 3 + 1];
+                T2 += w4[k] * ASc[j * 3 + 2];
+            }
         }
     }
     __device__ __forceinline__ void skin(const f32x4 (*AS)[NS * 3], const float* __restrict__ vposed, const float* __restrict__ A, int c,
@@ -412,7 +439,8 @@ __global__ void rodrigues_kernel(const float* __restrict__ aa, float* __restrict
 }
 
 // ================================================================================================================================
-// SMPL's vector-Jacobian product (thmr_smpl_backward).  Given gV (B,6890,3) and gJ (B,44,3), with the forward's A and
+// The vector-Jacobian product of both models (thmr_smpl_backward, thmr_smplh_backward), stated for SMPL; what SMPL-H
+// exchanges stands at the two kernels.  Given gV (B,6890,3) and gJ (B,44,3), with the forward's A and
 // v_posed recomputed by prep_kernel and the blend GEMM:
 //   skin-backward   per vertex  g = gV + sum_k J19[k][v] g19_k + (the mapped joints that pick this vertex),  g_vposed = T[:, :3]^T g,
 //                   gT = g (x) [v_posed; 1];  per workgroup  gA_j = sum_v W[v][j] gT_v  (24 x 12, stored per workgroup)
@@ -430,6 +458,9 @@ __global__ __launch_bounds__(256) void build_dirs_k_kernel(const float* __restri
     dirsK[idx] = n < NV * 3 ? dirsT[(int64_t)n * kx + k] : 0.f;
 }
 
+// rows of a workgroup's gA partial: the NS bone matrices, and for SMPL-H a row of ones behind them (grad_transl)
+constexpr int skin_backward_rows(int ns, Model m) { return ns + (m == SMPLH ? 1 : 0); }
+
 // ---- skin-backward: the forward's grid (27 workgroups of 256 vertices x crop groups, one thread per vertex, SkinLane's registers and
 //      LDS staging).  The in-workgroup reduction gA (24 x 12) = W^T (24 x 256) . gT (256 x 12) runs on v_mfma_f32_16x16x4_f32 (exact
 //      fp32): each wave owns its 64 vertices as K = 16 steps of 4, two 16-row blocks of joints (24 -> 32), 12 -> 16 columns.  The W^T
@@ -437,44 +468,59 @@ __global__ __launch_bounds__(256) void build_dirs_k_kernel(const float* __restri
 //      vertex 4 step + (l >> 4)), loaded once from global; gT goes through LDS once per crop ([256][12], read conflict-free: the 64 lanes
 //      of a step read 48 consecutive floats) — 16 ds_read_b32 and 32 MFMAs per wave and crop, where a VALU reduction out of LDS would read
 //      two operands per FMA (288 x 256 FMAs per crop) and wave reductions would take 288 x 6 cross-lane steps per thread.  The four waves'
-//      tiles are added in wave order. ----
-template <int NS>
+//      tiles are added in wave order.
+//      SMPL-H (M == SMPLH): g = gV + the picked joints 52..72 that are this vertex, nothing else (no regressor, no remap); NSP is the weight
+//      table's row length (24 for the folded path's 22 joints).  WREG = false, the 52-joint path's four joint blocks: the W^T fragments do not
+//      stay in registers, and the bone-matrix loop is rolled (SkinLane::transform_rolled). ----
+template <int NS, int NSP, Model M, bool WREG>
 __global__ __launch_bounds__(256) void lbs_skin_backward_kernel(const float* __restrict__ vposed, const float* __restrict__ W,
                                                                 const float* __restrict__ A, const float* __restrict__ J19,
                                                                 const int32_t* __restrict__ extra, const int32_t* __restrict__ jmap,
                                                                 const int32_t* __restrict__ update_hips, const float* __restrict__ gV,
                                                                 const float* __restrict__ gJ, float* __restrict__ gvp,
                                                                 float* __restrict__ gApart, int B, int CG) {
-    static_assert(NS > 16 && NS <= 32 && NS % 4 == 0, "two 16-row MFMA blocks of joints");
-    constexpr int NOJ = 44, NMAP = 25;                // output joints; the mapped ones in front of the 19 regressed
+    // SMPL-H adds one row of ones behind the NS joints: its translation column is sum_v g_v, the vertices' share of grad_transl
+    constexpr int NA = skin_backward_rows(NS, M), NBLK = (NA + 15) / 16;
+    static_assert(NA <= NBLK * 16 && (WREG ? NBLK == 2 : NS % 4 == 0), "16-row MFMA blocks of joints; two of them fit in registers");
+    // SMPL: the 44 output joints, the 25 mapped ones in front of the 19 regressed.  SMPL-H: the 21 picked vertices, joints 52..72
+    constexpr int NOJ = M == SMPL ? 44 : 21, NMAP = 25, NREG = M == SMPL ? 19 : 1;
     __shared__ f32x4 AS[2][NS * 3];                   // bone matrices of the current / next crop
-    __shared__ float gjs[NOJ * 3];                    // the crop's joint gradients, update_hips' adjoint applied
+    __shared__ float gjs[NOJ * 3];                    // the crop's joint gradients (SMPL: update_hips' adjoint applied)
     __shared__ __attribute__((aligned(16))) float gTs[256 * 12];
-    __shared__ float red[4][NS * 12];
-    __shared__ float jws[19][256];
+    __shared__ float red[4][NA * 12];
+    __shared__ float jws[NREG][256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    SkinLane<NS, NS> t;
+    SkinLane<NS, NSP> t;
     const int b0 = blockIdx.y * CG;
     t.begin(AS, vposed, W, A, extra, b0, B);
     // the mapped joints that are this thread's vertex (bit s: joint_map[s] names a picked slot whose vertex id is v; an id may repeat)
     unsigned jslots = 0;
+    bool hips = false;
+    if constexpr (M == SMPL) {
 #pragma unroll
-    for (int s = 0; s < NMAP; ++s) {
-        const int src = jmap[s];
-        jslots |= (src >= NS && ((t.slots >> (src - NS)) & 1u)) ? 1u << s : 0u;
+        for (int s = 0; s < NMAP; ++s) {
+            const int src = jmap[s];
+            jslots |= (src >= NS && ((t.slots >> (src - NS)) & 1u)) ? 1u << s : 0u;
+        }
+        // the vertex's 19 regressor entries: LDS, not registers (the 24 skin weights and the 32 MFMA fragments already live there across
+        // the bone-matrix loop); [k][tid], read conflict-free
+        for (int k = 0; k < 19; ++k) jws[k][tid] = t.vok ? J19[(int64_t)k * NV + t.vv] : 0.f;
+    } else {
+        jslots = t.slots;             // no remap: slot k is joint 52 + k
     }
-    // the vertex's 19 regressor entries: LDS, not registers (the 24 skin weights and the 32 MFMA fragments already live there across
-    // the bone-matrix loop); [k][tid], read conflict-free
-    for (int k = 0; k < 19; ++k) jws[k][tid] = t.vok ? J19[(int64_t)k * NV + t.vv] : 0.f;
-    // W^T as the MFMA's A operand: step u, lane (i = lane & 15, k = lane >> 4): W[first vertex of the wave + 4 u + k][i (+ 16)]
-    float wm[16][2];
+    // W^T as the MFMA's A operand: step u, lane (i = lane & 15, k = lane >> 4): W[first vertex of the wave + 4 u + k][i (+ 16 ...)]
+    float wm[WREG ? 16 : 1][2];
+    if constexpr (WREG) {
 #pragma unroll
-    for (int u = 0; u < 16; ++u) {
-        const int gv = blockIdx.x * 256 + wave * 64 + u * 4 + (lane >> 4), i = lane & 15;
-        wm[u][0] = gv < NV ? W[(int64_t)gv * NS + i] : 0.f;
-        wm[u][1] = (gv < NV && 16 + i < NS) ? W[(int64_t)gv * NS + 16 + i] : 0.f;
+        for (int u = 0; u < 16; ++u) {
+            const int gv = blockIdx.x * 256 + wave * 64 + u * 4 + (lane >> 4), i = lane & 15;
+            wm[u][0] = gv < NV ? W[(int64_t)gv * NSP + i] : 0.f;
+            wm[u][1] = (gv < NV && 16 + i < NS) ? W[(int64_t)gv * NSP + 16 + i] : 0.f;
+            if constexpr (M == SMPLH)
+                if (gv < NV && 16 + i == NS) wm[u][1] = 1.f;
+        }
     }
-    const bool hips = *update_hips != 0;
+    if constexpr (M == SMPL) hips = *update_hips != 0;
     for (int c = 0; c < CG; ++c) {
         const int b = b0 + c;             // workgroup-uniform
         if (b >= B) break;
@@ -482,18 +528,23 @@ __global__ __launch_bounds__(256) void lbs_skin_backward_kernel(const float* __r
         // (g9, g12, g8) <- (g9 - g12 / 2, g12 - g9 / 2, g8 + (g9 + g12) / 2)
         float gjv = 0.f;
         if (gJ && tid < NOJ * 3) {
-            const float* q = gJ + (int64_t)b * NOJ * 3;
-            const int j = tid / 3, i = tid % 3;
-            gjv = q[tid];
-            if (hips && j == 9) gjv = gjv - 0.5f * q[12 * 3 + i];
-            if (hips && j == 12) gjv = gjv - 0.5f * q[9 * 3 + i];
-            if (hips && j == 8) gjv = gjv + 0.5f * (q[9 * 3 + i] + q[12 * 3 + i]);
+            if constexpr (M == SMPL) {
+                const float* q = gJ + (int64_t)b * NOJ * 3;
+                const int j = tid / 3, i = tid % 3;
+                gjv = q[tid];
+                if (hips && j == 9) gjv = gjv - 0.5f * q[12 * 3 + i];
+                if (hips && j == 12) gjv = gjv - 0.5f * q[9 * 3 + i];
+                if (hips && j == 8) gjv = gjv + 0.5f * (q[9 * 3 + i] + q[12 * 3 + i]);
+            } else {
+                gjv = gJ[((int64_t)b * NOUT + NJH) * 3 + tid];
+            }
         }
         __syncthreads();                  // AS[c & 1] is complete; gjs, gTs and red of the previous crop are no longer read
         if (tid < NOJ * 3) gjs[tid] = gjv;
         f32x4 T0, T1, T2;
         float x, y, z;
-        t.transform(AS, vposed, A, c, b, B, CG, T0, T1, T2, x, y, z);
+        if constexpr (WREG) t.transform(AS, vposed, A, c, b, B, CG, T0, T1, T2, x, y, z);
+        else t.transform_rolled(AS, vposed, W, A, c, b, B, CG, T0, T1, T2, x, y, z);
         __syncthreads();
         float g0 = 0.f, g1 = 0.f, g2 = 0.f;
         if (gV && t.vok) {
@@ -501,14 +552,16 @@ __global__ __launch_bounds__(256) void lbs_skin_backward_kernel(const float* __r
             g0 = p[0]; g1 = p[1]; g2 = p[2];
         }
         if (gJ) {
+            if constexpr (M == SMPL) {
 #pragma unroll
-            for (int k = 0; k < 19; ++k) {
-                const float jw = jws[k][tid];
-                g0 = fmaf(jw, gjs[(NMAP + k) * 3 + 0], g0);
-                g1 = fmaf(jw, gjs[(NMAP + k) * 3 + 1], g1);
-                g2 = fmaf(jw, gjs[(NMAP + k) * 3 + 2], g2);
+                for (int k = 0; k < 19; ++k) {
+                    const float jw = jws[k][tid];
+                    g0 = fmaf(jw, gjs[(NMAP + k) * 3 + 0], g0);
+                    g1 = fmaf(jw, gjs[(NMAP + k) * 3 + 1], g1);
+                    g2 = fmaf(jw, gjs[(NMAP + k) * 3 + 2], g2);
+                }
             }
-            for (unsigned m = jslots; m; m &= m - 1) {
+            for (unsigned m = jslots; m; m &= m - 1) {        // ascending slot order; a vertex named by two slots receives both
                 const int s = __builtin_ctz(m);
                 g0 += gjs[s * 3 + 0]; g1 += gjs[s * 3 + 1]; g2 += gjs[s * 3 + 2];
             }
@@ -530,26 +583,53 @@ __global__ __launch_bounds__(256) void lbs_skin_backward_kernel(const float* __r
         gq[1] = f32x4{g1 * x, g1 * y, g1 * z, g1};
         gq[2] = f32x4{g2 * x, g2 * y, g2 * z, g2};
         __syncthreads();
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
         const int n = lane & 15, kq = lane >> 4;
+        if constexpr (WREG) {
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
 #pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const float bv = n < 12 ? gTs[(wave * 64 + u * 4 + kq) * 12 + n] : 0.f;
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wm[u][0], bv, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wm[u][1], bv, acc1, 0, 0, 0);
-        }
-        // result layout: register r of lane l is row 4 (l >> 4) + r, column l & 15
-        if (n < 12) {
+            for (int u = 0; u < 16; ++u) {
+                const float bv = n < 12 ? gTs[(wave * 64 + u * 4 + kq) * 12 + n] : 0.f;
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wm[u][0], bv, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wm[u][1], bv, acc1, 0, 0, 0);
+            }
+            // result layout: register r of lane l is row 4 (l >> 4) + r, column l & 15
+            if (n < 12) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = kq * 4 + r;
-                red[wave][j * 12 + n] = acc0[r];
-                if (16 + j < NS) red[wave][(16 + j) * 12 + n] = acc1[r];
+                for (int r = 0; r < 4; ++r) {
+                    const int j = kq * 4 + r;
+                    red[wave][j * 12 + n] = acc0[r];
+                    if (16 + j < NA) red[wave][(16 + j) * 12 + n] = acc1[r];
+                }
+            }
+        } else {
+            // more joint blocks than registers hold fragments for: one 16-row block per pass over the gT tile in LDS, its W^T fragments
+            // straight from global (the workgroup's 256 rows of W stay in the cache across the crops of a pass)
+#pragma unroll 1
+            for (int blk = 0; blk < NBLK; ++blk) {
+                const float* Wl = W;
+                asm volatile("" : "+s"(Wl));      // loads that are the same in every crop are not to be hoisted into 64 registers
+                const int row = blk * 16 + n;
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    const int gv = blockIdx.x * 256 + wave * 64 + u * 4 + kq;
+                    const float bv = n < 12 ? gTs[(wave * 64 + u * 4 + kq) * 12 + n] : 0.f;
+                    float av = (gv < NV && row < NS) ? Wl[(int64_t)gv * NSP + row] : 0.f;
+                    if (M == SMPLH && gv < NV && row == NS) av = 1.f;
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+                }
+                if (n < 12) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int j = blk * 16 + kq * 4 + r;
+                        if (j < NA) red[wave][j * 12 + n] = acc[r];
+                    }
+                }
             }
         }
         __syncthreads();
-        for (int i = tid; i < NS * 12; i += 256)
-            gApart[((int64_t)b * SKB + blockIdx.x) * (NS * 12) + i] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+        for (int i = tid; i < NA * 12; i += 256)
+            gApart[((int64_t)b * SKB + blockIdx.x) * (NA * 12) + i] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
         t.publish(AS, c);
     }
 }
@@ -560,26 +640,33 @@ __global__ __launch_bounds__(256) void lbs_skin_backward_kernel(const float* __r
 //        i = NC-1 .. 1, p = parent(i), rel = J_i - J_p:  gR_i += Gr_p^T gGr_i;  gGr_p += gGr_i R_i^T + gGt_i (x) rel;
 //                                                         gGt_p += gGt_i;  grel = Gr_p^T gGt_i;  gJ_i += grel;  gJ_p -= grel
 //        gR_0 += gGr_0,  gJ_0 += gGt_0,  gbeta += sum_{j,i} Jsd[j][i][.] gJ_j[i]
-//      (parents[i] < i, as the forward assumes: every child of i has been folded into i before i is read). ----
-template <int NC, int KX, int KS>
+//      (parents[i] < i, as the forward assumes: every child of i has been folded into i before i is read).
+//      SMPL (24, 24): the posed joints' gradient arrives through joint_map with update_hips' adjoint.  SMPL-H (NR = 52 rest joints, NC = 52
+//      or 22 chain joints): output joint j < 52 IS chain joint j, so gJtr_j = gJo_j.  On the folded path (NC = 22) the forward writes hand
+//      joint j >= 22 as Gr_w (J_j - J_w) + Gt_w, w = fold[j] its wrist, whose adjoint, before the chain is walked and in ascending j, is
+//        gGr_w += gJo_j (x) (J_j - J_w);  gGt_w += gJo_j;  grel = Gr_w^T gJo_j;  gJ_j += grel;  gJ_w -= grel
+//      and reaches the betas through gJ.  grad_transl = the ones row of gA (sum_v g_v, lbs_skin_backward_kernel) + sum_j gJo_j, j ascending. ----
+template <int NR, int NC, int KX, int KS, Model M>
 __global__ __launch_bounds__(128) void lbs_chain_backward_kernel(const float* __restrict__ rotmat, const float* __restrict__ betas,
                                                                  const float* __restrict__ Jt, const float* __restrict__ Jsd,
                                                                  const int32_t* __restrict__ parents, const int32_t* __restrict__ jmap,
-                                                                 const int32_t* __restrict__ update_hips, const float* __restrict__ gJo,
+                                                                 const int32_t* __restrict__ update_hips, const int32_t* __restrict__ fold,
+                                                                 const float* __restrict__ gJo,
                                                                  const float* __restrict__ gApart, const float* __restrict__ planes,
                                                                  float* __restrict__ grad_rotmat, float* __restrict__ grad_betas,
-                                                                 int B) {
-    constexpr int NMAP = 25;
-    __shared__ float J[NC][3], R[NC][9], Gr[NC][9], Gt[NC][3], bs[NB];
-    __shared__ float gA[NC][12], gx[KX], gm[NMAP][3];
-    __shared__ float gGr[NC][9], gGt[NC][3], gJ[NC][3], gR[NC][9];
+                                                                 float* __restrict__ grad_transl, int B) {
+    constexpr int NMAP = M == SMPL ? 25 : NR, NA = skin_backward_rows(NC, M);      // gm: SMPL the mapped joints', SMPL-H all 52 chain joints'
+    static_assert(NC <= NR && (M == SMPLH || NC == NR), "SMPL has no joints outside its chain");
+    __shared__ float J[NR][3], R[NC][9], Gr[NC][9], Gt[NC][3], bs[NB];
+    __shared__ float gA[NA][12], gx[KX], gm[NMAP][3];
+    __shared__ float gGr[NC][9], gGt[NC][3], gJ[NR][3], gR[NC][9];
     const int b = blockIdx.x, t = threadIdx.x;
     for (int i = t; i < NC * 9; i += 128) R[i / 9][i % 9] = rotmat[(int64_t)b * NC * 9 + i];
-    if (t < NB) bs[t] = betas[(int64_t)b * NB + t];
-    for (int i = t; i < NC * 12; i += 128) {
+    if (t < NB) bs[t] = (M == SMPL || betas) ? betas[(int64_t)b * NB + t] : 0.f;      // only SMPL-H takes null betas (= zeros)
+    for (int i = t; i < NA * 12; i += 128) {
         float acc = 0.f;      // the loads of a sum are independent and issued together (compile-time counts); the adds keep their order
 #pragma unroll
-        for (int k = 0; k < SKB; ++k) acc += gApart[((int64_t)b * SKB + k) * (NC * 12) + i];
+        for (int k = 0; k < SKB; ++k) acc += gApart[((int64_t)b * SKB + k) * (NA * 12) + i];
         gA[i / 12][i % 12] = acc;
     }
     for (int i = t; i < KX; i += 128) {
@@ -588,7 +675,9 @@ __global__ __launch_bounds__(128) void lbs_chain_backward_kernel(const float* __
         for (int sp = 0; sp < KS; ++sp) acc += planes[((int64_t)sp * B + b) * KX + i];
         gx[i] = acc;
     }
-    if (t < NMAP * 3) {                  // the mapped joints' gradient, update_hips' adjoint applied (as lbs_skin_backward_kernel)
+    if constexpr (M == SMPLH) {
+        for (int i = t; i < NR * 3; i += 128) gm[i / 3][i % 3] = gJo ? gJo[(int64_t)b * NOUT * 3 + i] : 0.f;
+    } else if (t < NMAP * 3) {           // the mapped joints' gradient, update_hips' adjoint applied (as lbs_skin_backward_kernel)
         float v = 0.f;
         if (gJo) {
             const float* q = gJo + (int64_t)b * 132;
@@ -602,7 +691,7 @@ __global__ __launch_bounds__(128) void lbs_chain_backward_kernel(const float* __
         gm[t / 3][t % 3] = v;
     }
     __syncthreads();
-    for (int i = t; i < NC * 3; i += 128) {
+    for (int i = t; i < NR * 3; i += 128) {
         float v = 0.f;
 #pragma unroll
         for (int l = 0; l < NB; ++l) v = fmaf(bs[l], Jsd[i * NB + l], v);
@@ -634,12 +723,31 @@ __global__ __launch_bounds__(128) void lbs_chain_backward_kernel(const float* __
     for (int i = t; i < NC * 3; i += 128) {
         const int j = i / 3, r = i % 3;
         float v = gA[j][r * 4 + 3];
-        for (int s = 0; s < NMAP; ++s)
-            if (jmap[s] == j) v += gm[s][r];
+        if constexpr (M == SMPLH) v += gm[j][r];
+        else
+            for (int s = 0; s < NMAP; ++s)
+                if (jmap[s] == j) v += gm[s][r];
         gGt[j][r] = v;
         gJ[j][r] = -(Gr[j][0 * 3 + r] * gA[j][0 * 4 + 3] + Gr[j][1 * 3 + r] * gA[j][1 * 4 + 3] + Gr[j][2 * 3 + r] * gA[j][2 * 4 + 3]);
     }
     __syncthreads();
+    if constexpr (NC < NR) {                 // the folded path's hand joints: each thread owns one element index of every wrist, no barrier
+        for (int j = NC; j < NR; ++j) {
+            const int w = fold[j];
+            if (t < 9) {
+                const int r = t / 3, c = t % 3;
+                gGr[w][t] += gm[j][r] * (J[j][c] - J[w][c]);
+            } else if (t < 12) {
+                gGt[w][t - 9] += gm[j][t - 9];
+            } else if (t >= 32 && t < 32 + 3) {
+                const int r = t - 32;
+                const float grel = Gr[w][0 * 3 + r] * gm[j][0] + Gr[w][1 * 3 + r] * gm[j][1] + Gr[w][2 * 3 + r] * gm[j][2];
+                gJ[j][r] = grel;                 // a hand joint's rest position enters nowhere else
+                gJ[w][r] -= grel;
+            }
+        }
+        __syncthreads();
+    }
     for (int i = NC - 1; i >= 1; --i) {
         const int p = parents[i];
         if (t < 9) {                         // gR_i += Gr_p^T gGr_i
@@ -667,8 +775,19 @@ __global__ __launch_bounds__(128) void lbs_chain_backward_kernel(const float* __
     if (grad_betas && t < NB) {
         float v = gx[t];
 #pragma unroll
-        for (int i = 0; i < NC * 3; ++i) v = fmaf(Jsd[i * NB + t], gJ[i / 3][i % 3], v);
+        for (int i = 0; i < NR * 3; ++i) v = fmaf(Jsd[i * NB + t], gJ[i / 3][i % 3], v);
         grad_betas[(int64_t)b * NB + t] = v;
+    }
+    if constexpr (M == SMPLH) {
+        if (grad_transl && t >= 64 && t < 64 + 3) {
+            // 6890 + 73 terms of one sign-free sum: the 27 workgroups' fp32 partials and the joints' rows are added in fp64, in order
+            // (added in fp32 the 27 partials alone put it at 2.5 times the fp32 reference's distance to float64)
+            const int r = t - 64;
+            double v = 0.0;
+            for (int k = 0; k < SKB; ++k) v += (double)gApart[((int64_t)b * SKB + k) * (NA * 12) + NC * 12 + r * 4 + 3];
+            for (int j = 0; j < NR; ++j) v += (double)gm[j][r];
+            grad_transl[(int64_t)b * 3 + r] = (float)v;
+        }
     }
 }
 
@@ -742,8 +861,8 @@ int launch_lbs_backward(const LbsArgs& a, const LbsGradArgs& g, hipStream_t s) {
     launch_lbs_prep(a, s);
     if (int r = launch_blend(a.xf, a.dirsT, a.vt, a.vposed, B, THMR_LBS_KX, s)) return r;
     const int cg = lbs_crops_per_pass(B);
-    hipLaunchKernelGGL((lbs_skin_backward_kernel<NJ>), dim3(SKB, (B + cg - 1) / cg), dim3(256), 0, s, a.vposed, a.W, a.A, a.J19, a.extra,
-                       a.jmap, a.update_hips, g.gV, g.gJ, g.gvp, g.gApart, B, cg);
+    hipLaunchKernelGGL((lbs_skin_backward_kernel<NJ, NJ, SMPL, true>), dim3(SKB, (B + cg - 1) / cg), dim3(256), 0, s, a.vposed, a.W, a.A, a.J19,
+                       a.extra, a.jmap, a.update_hips, g.gV, g.gJ, g.gvp, g.gApart, B, cg);
     if (hipGetLastError() != hipSuccess) return -2;
     // gx (B x 224) = g_vposed (B x 20672) . dirsK^T: M = B is skinny and N = 224 is two tiles, so K is split THMR_LBS_GKSPLIT = 38 ways (544
     // = 17 K tiles per slice) to put 76 workgroups per 64 crops on the chip; ONE tile shape (64 x 128) at every batch size, so no
@@ -752,9 +871,38 @@ int launch_lbs_backward(const LbsArgs& a, const LbsGradArgs& g, hipStream_t s) {
     ga.A = g.gvp; ga.lda = THMR_LBS_GK; ga.W = g.dirsK; ga.ldw = THMR_LBS_GK; ga.M = B; ga.N = THMR_LBS_KX; ga.K = THMR_LBS_GK;
     ga.qscale = 1.f;
     if (int r = launch_gemm_splitk(ga, 12, THMR_LBS_GKSPLIT, g.planes, s)) return r;
-    hipLaunchKernelGGL((lbs_chain_backward_kernel<NJ, THMR_LBS_KX, THMR_LBS_GKSPLIT>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, a.Jt,
-                       a.Jsd, a.parents, a.jmap, a.update_hips, g.gJ, g.gApart, g.planes, g.grad_rotmat, g.grad_betas, B);
+    hipLaunchKernelGGL((lbs_chain_backward_kernel<NJ, NJ, THMR_LBS_KX, THMR_LBS_GKSPLIT, SMPL>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas,
+                       a.Jt, a.Jsd, a.parents, a.jmap, a.update_hips, nullptr, g.gJ, g.gApart, g.planes, g.grad_rotmat, g.grad_betas, nullptr, B);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// SMPL-H's backward, either path: the same five launches on the same kernels.  The forward's crops-per-pass rule; the blend GEMM's reverse
+// keeps SMPL's tile (64 x 128) and split (THMR_LBS_GKSPLIT = 38 slices of 17 K tiles) for N = 224 and N = 480 alike: 76 / 152 workgroups
+// per 64 poses
+template <int NC, int NSP, int KX, bool WREG>
+int launch_smplh_backward_path(const SmplhArgs& a, const SmplhGradArgs& g, const float* W, const float* dirsT, hipStream_t s) {
+    const int B = a.B;
+    hipLaunchKernelGGL((prep_kernel<NJH, NC, KX, SMPLH>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, a.transl, a.Jt, a.Jsd, a.parents, a.fold,
+                       a.A, a.xf, nullptr, nullptr, nullptr);
+    if (hipGetLastError() != hipSuccess) return -2;
+    if (int r = launch_blend(a.xf, dirsT, a.vt, a.vposed, B, KX, s)) return r;
+    const int cg = smplh_poses_per_workgroup(B);
+    hipLaunchKernelGGL((lbs_skin_backward_kernel<NC, NSP, SMPLH, WREG>), dim3(SKB, (B + cg - 1) / cg), dim3(256), 0, s, a.vposed, W, a.A, nullptr,
+                       a.extra, nullptr, nullptr, g.gV, g.gJ, g.gvp, g.gApart, B, cg);
+    if (hipGetLastError() != hipSuccess) return -2;
+    GemmArgs ga{};
+    ga.A = g.gvp; ga.lda = THMR_LBS_GK; ga.W = g.dirsK; ga.ldw = THMR_LBS_GK; ga.M = B; ga.N = KX; ga.K = THMR_LBS_GK;
+    ga.qscale = 1.f;
+    if (int r = launch_gemm_splitk(ga, 12, THMR_LBS_GKSPLIT, g.planes, s)) return r;
+    hipLaunchKernelGGL((lbs_chain_backward_kernel<NJH, NC, KX, THMR_LBS_GKSPLIT, SMPLH>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, a.Jt,
+                       a.Jsd, a.parents, nullptr, nullptr, a.fold, g.gJ, g.gApart, g.planes, g.grad_rotmat, g.grad_betas, g.grad_transl, B);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_smplh_backward(const SmplhArgs& a, const SmplhGradArgs& g, hipStream_t s) {
+    if (!a.rotmat || a.B < 1 || (!g.gV && !g.gJ) || (!g.grad_rotmat && !g.grad_betas && !g.grad_transl)) return -1;
+    if (a.body_only) return launch_smplh_backward_path<NBODY, THMR_SMPLH_NBODY_PAD, THMR_SMPLH_KXB, true>(a, g, a.W_body, a.dirsT_body, s);
+    return launch_smplh_backward_path<NJH, NJH, THMR_SMPLH_KX, false>(a, g, a.W, a.dirsT, s);
 }
 
 int launch_rodrigues(const float* aa, float* R, int n, hipStream_t s) {

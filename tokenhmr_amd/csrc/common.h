@@ -443,6 +443,7 @@ int launch_assemble(const float* ro, int ldro, const float* bpose, const float* 
                     const float* init_cam, float* pose6d, float* rotmat, float* betas, float* cam, float* cam_t,
                     float* focal, float focal_length, float img_size, int B, hipStream_t s);
 int launch_rot6d(const float* x, float* R, int n, hipStream_t s);
+int launch_rot6d_backward(const float* x, const float* gR, float* gx, int n, hipStream_t s);      // its adjoint: (n,6), (n,3,3) -> (n,6)
 int launch_aa_to_rotmat(const float* aa, float* R, int n, hipStream_t s);
 int launch_cam_t(const float* cam, float* cam_t, float focal_length, float img_size, int B, hipStream_t s);
 int launch_vq_argmin_rows(const float* x, const float* dot, const float* cnorm, int32_t* idx, float* dist, int rows,
@@ -482,6 +483,17 @@ struct ValLossArgs {
     int B, pelvis_id, mode, gt_pose_is_rotmat;
 };
 int launch_val_loss(const ValLossArgs& a, hipStream_t s);
+// PoseReConsLoss, value and gradient of the weighted total (loss.hip).  kind: THMR_RECON_* per term (pose, mesh, joints); w: POSE, MESH, JNT,
+// COMMIT, LOSS_WT; the launcher fills nblk, count and gscale.  partial: THMR_TOK_RECON_WS_BASE + B * THMR_TOK_RECON_WS_PER_ITEM floats
+struct ReconLossArgs {
+    const float *pred_rot, *gt_rot, *pred_verts, *gt_verts, *pred_joints, *gt_joints;      // (B,21,3,3) (B,6890,3) (B,73,3)
+    const float *vert_w, *commit;                                                          // (6890,3) or null; one float or null
+    float *losses, *grad_rot, *grad_verts, *grad_joints, *partial;                         // (4); the gradients may be null
+    int kind[3], jlo, jhi, B, nblk[3];
+    float gscale[3];
+    double w[5], count[3];
+};
+int launch_recon_loss(ReconLossArgs& a, hipStream_t s);
 // out[0] = mean over rows of logsumexp(x_r) - x_r[target_r], x (rows, 2048); row_loss: rows floats of workspace
 int launch_token_ce(const float* x, const int32_t* target, int rows, float* out, float* row_loss, hipStream_t s);
 // body_model.hip: SMPL and SMPL-H on one set of kernels (prep -> blend GEMM -> skin).  One-time, per model: Jt (nj,3) / Jsd (nj,3,10) from
@@ -533,3 +545,14 @@ struct SmplhArgs {
 };
 int launch_smplh_fold_weights(const float* W, const int32_t* fold, float* Wf, hipStream_t s);
 int launch_smplh(const SmplhArgs& a, hipStream_t s);
+// SMPL-H's vector-Jacobian product, either path (body_model.hip): SMPL's five launches on the same kernels.  In `a`: the
+// forward's inputs, constants and scratch (verts, joints unused).  A workgroup's gA partial carries one row more than the path has bone
+// matrices: a row of ones, whose translation column is the vertices' share of grad_transl.
+constexpr int THMR_SMPLH_GA = 27 * (THMR_SMPLH_NJ + 1) * 12, THMR_SMPLH_GA_BODY = 27 * (THMR_SMPLH_NBODY + 1) * 12;
+struct SmplhGradArgs {
+    const float *gV, *gJ;             // (B,6890,3), (B,73,3): either may be null (zeros), not both
+    const float* dirsK;               // the path's dirsT transposed, (480 or 224, 20672) (launch_body_build_dirs_k)
+    float *gvp, *gApart, *planes;     // scratch: (B,20672), (B,THMR_SMPLH_GA or _GA_BODY), (THMR_LBS_GKSPLIT,B,480 or 224)
+    float *grad_rotmat, *grad_betas, *grad_transl;   // (B,52 or 22,3,3), (B,10), (B,3): any may be null, not all
+};
+int launch_smplh_backward(const SmplhArgs& a, const SmplhGradArgs& g, hipStream_t s);

@@ -141,6 +141,37 @@ __global__ void rot6d_kernel(const float* __restrict__ x, float* __restrict__ Rm
     R[6] = b1y * b2z - b1z * b2y; R[7] = b1z * b2x - b1x * b2z; R[8] = b1x * b2y - b1y * b2x;
 }
 
+// the adjoint of rot6d_kernel: G1, G2, G3 the rows of grad_R.  b3 = b1 x b2 gives gb1 = G1 + b2 x G3, gb2 = G2 + G3 x b1; b = v / max(|v|, eps)
+// gives gv = (gb - b (b . gb)) / |v| where |v| >= eps and gb / eps below (torch's clamp_min passes no gradient to a norm under the clamp);
+// u = a2 - (b1 . a2) b1 gives ga2 = gu - (gu . b1) b1 and gb1 -= (b1 . a2) gu + (gu . b1) a2.
+// Evaluated in fp64 and rounded once: the two projections cancel whatever of gb lies along b, and for a2 near a1 the 1 / |u| in front
+// amplifies what the cancellation leaves — in fp32 one such vector decides a batch's largest error (measured 0.4 to 16 times the fp32
+// reference's on single vectors).  A few dozen fp64 operations per rotation, n = 21 per pose.
+__global__ void rot6d_backward_kernel(const float* __restrict__ x, const float* __restrict__ gR, float* __restrict__ gx, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float* p = x + (int64_t)i * 6;
+    const double a1x = p[0], a1y = p[1], a1z = p[2], a2x = p[3], a2y = p[4], a2z = p[5];
+    const double l1 = sqrt(a1x * a1x + a1y * a1y + a1z * a1z), n1 = fmax(l1, 1e-12);
+    const double b1x = a1x / n1, b1y = a1y / n1, b1z = a1z / n1;
+    const double dp = b1x * a2x + b1y * a2y + b1z * a2z;
+    const double ux = a2x - dp * b1x, uy = a2y - dp * b1y, uz = a2z - dp * b1z;
+    const double l2 = sqrt(ux * ux + uy * uy + uz * uz), n2 = fmax(l2, 1e-12);
+    const double b2x = ux / n2, b2y = uy / n2, b2z = uz / n2;
+    const float* G = gR + (int64_t)i * 9;
+    const double g3x = G[6], g3y = G[7], g3z = G[8];
+    double gb1x = G[0] + (b2y * g3z - b2z * g3y), gb1y = G[1] + (b2z * g3x - b2x * g3z), gb1z = G[2] + (b2x * g3y - b2y * g3x);
+    const double gb2x = G[3] + (g3y * b1z - g3z * b1y), gb2y = G[4] + (g3z * b1x - g3x * b1z), gb2z = G[5] + (g3x * b1y - g3y * b1x);
+    const double r2 = l2 >= 1e-12 ? b2x * gb2x + b2y * gb2y + b2z * gb2z : 0.0;
+    const double gux = (gb2x - b2x * r2) / n2, guy = (gb2y - b2y * r2) / n2, guz = (gb2z - b2z * r2) / n2;
+    const double gdp = -(gux * b1x + guy * b1y + guz * b1z);
+    gb1x += gdp * a2x - dp * gux; gb1y += gdp * a2y - dp * guy; gb1z += gdp * a2z - dp * guz;
+    const double r1 = l1 >= 1e-12 ? b1x * gb1x + b1y * gb1y + b1z * gb1z : 0.0;
+    float* o = gx + (int64_t)i * 6;
+    o[0] = (float)((gb1x - b1x * r1) / n1); o[1] = (float)((gb1y - b1y * r1) / n1); o[2] = (float)((gb1z - b1z * r1) / n1);
+    o[3] = (float)(gux + gdp * b1x); o[4] = (float)(guy + gdp * b1y); o[5] = (float)(guz + gdp * b1z);
+}
+
 // aa_to_rotmat (tokenhmr/lib/utils/geometry.py:5-44): axis-angle -> quaternion -> rotation matrix, operation by operation
 // (angle = ||theta + 1e-8||, axis = theta / angle, half-angle quaternion, re-normalised, nine quadratic forms).
 // TWIN: rotation_device.h's aa_to_rotmat_dev (the validation loss, loss.hip) restates this body line for line; change both together.
@@ -233,6 +264,11 @@ int launch_cam_t(const float* cam, float* cam_t, float focal_length, float img_s
 }
 int launch_aa_to_rotmat(const float* aa, float* R, int n, hipStream_t s) {
     hipLaunchKernelGGL(aa_to_rotmat_kernel, dim3((n + 255) / 256), dim3(256), 0, s, aa, R, n);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_rot6d_backward(const float* x, const float* gR, float* gx, int n, hipStream_t s) {
+    hipLaunchKernelGGL(rot6d_backward_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, gR, gx, n);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

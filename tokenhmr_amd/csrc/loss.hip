@@ -17,6 +17,7 @@
 // aligned); the 12-byte rows ((.,44,3) keypoints, axis-angle) and the 36-byte matrices are 4-byte aligned only and are read as 3- and 9-float
 // records the compiler may merge (global_load_dwordx3).  The kernel moves ~3.3 KB per item and is bound by the latency of its dependent
 // chain (loads -> cos / sin / atan2 -> shuffles), not by bandwidth.
+#include "../../include/tokenhmr_hip.h"      // THMR_RECON_*
 #include "common.h"
 #include "rotation_device.h"
 
@@ -221,7 +222,99 @@ __global__ __launch_bounds__(256) void token_ce_final_kernel(const float* __rest
     if (t == 0) out[0] = (float)(sh[0] / (double)rows);
 }
 
+// ---- PoseReConsLoss (tokenization/utils/losses.py:65-131) with the weighted total of train_poseVQ.py:152-156, value and gradient in one
+//      call: two launches.  (1) the three terms' elements as one row of workgroups — pose blocks, then mesh blocks, then joint blocks, each
+//      workgroup kReconSpan consecutive elements of ONE term, four per thread, coalesced — writes each element's gradient of the TOTAL
+//      (its scale w_total w_term / count is known before any sum is) and the workgroup's fp32 partial sum: per thread in element order,
+//      xor-shuffles, the four waves in order.  (2) one workgroup adds the partials of each term in fp64 (thread t: partials t, t + 256, ...,
+//      then a fixed tree) and writes the three means and the total.  No float atomics; every partial (2) reads was written by (1) of the
+//      same call.  Kinds as torch's L1Loss / MSELoss / SmoothL1Loss (beta = 1) with mean reduction and WeightedMSE; at the kinks the
+//      gradient is torch's: l1 gives 0 at d = 0, l1_smooth is d below |d| = 1 and sign(d) from it on. ----
+constexpr int kReconSpan = 1024;
+
+__device__ __forceinline__ void recon_elem(int kind, float d, float w, float& val, float& grad) {
+    if (kind == THMR_RECON_L1) { val = fabsf(d); grad = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+    else if (kind == THMR_RECON_L1_SMOOTH) {
+        const float ad = fabsf(d);
+        if (ad < 1.f) { val = 0.5f * d * d; grad = d; }
+        else { val = ad - 0.5f; grad = d > 0.f ? 1.f : -1.f; }
+    }
+    else if (kind == THMR_RECON_WT_L2) { val = w * (d * d); grad = 2.f * (w * d); }
+    else { val = d * d; grad = 2.f * d; }
+}
+
+__global__ __launch_bounds__(256) void recon_loss_terms_kernel(ReconLossArgs a) {
+    __shared__ float ws[4];
+    const int tid = threadIdx.x;
+    int term = 0, lb = blockIdx.x;
+    if (lb >= a.nblk[0]) { lb -= a.nblk[0]; term = 1; }
+    if (term == 1 && lb >= a.nblk[1]) { lb -= a.nblk[1]; term = 2; }
+    const float* pred = term == 0 ? a.pred_rot : (term == 1 ? a.pred_verts : a.pred_joints);
+    const float* gt = term == 0 ? a.gt_rot : (term == 1 ? a.gt_verts : a.gt_joints);
+    float* grad = term == 0 ? a.grad_rot : (term == 1 ? a.grad_verts : a.grad_joints);
+    const int per_item = term == 0 ? 189 : (term == 1 ? 20670 : THMR_SMPLH_NOUT * 3);
+    const int64_t total = (int64_t)a.B * per_item;
+    const int kind = a.kind[term];
+    const float gs = a.gscale[term];
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < kReconSpan / 256; ++k) {
+        const int64_t e = (int64_t)lb * kReconSpan + k * 256 + tid;
+        if (e >= total) break;
+        const int r = (int)(e % per_item);
+        const bool in = term != 2 || (r / 3 >= a.jlo && r / 3 < a.jhi);
+        float val = 0.f, g = 0.f;
+        if (in) recon_elem(kind, pred[e] - gt[e], (term == 1 && kind == THMR_RECON_WT_L2) ? a.vert_w[r] : 1.f, val, g);
+        acc += val;
+        if (grad) grad[e] = in ? gs * g : 0.f;
+    }
+    acc = wave_sum(acc);
+    if ((tid & 63) == 0) ws[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) a.partial[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+__global__ __launch_bounds__(256) void recon_loss_final_kernel(ReconLossArgs a) {
+    __shared__ double sh[3][256];
+    const int t = threadIdx.x;
+    int lo = 0;
+    for (int term = 0; term < 3; ++term) {
+        double acc = 0.0;
+        for (int i = t; i < a.nblk[term]; i += 256) acc += (double)a.partial[lo + i];
+        sh[term][t] = acc;
+        lo += a.nblk[term];
+    }
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (t < o)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sh[c][t] += sh[c][t + o];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double lp = sh[0][0] / a.count[0], lm = sh[1][0] / a.count[1], lj = sh[2][0] / a.count[2];
+        const double commit = a.commit ? (double)a.commit[0] : 0.0;
+        a.losses[0] = (float)lp; a.losses[1] = (float)lm; a.losses[2] = (float)lj;
+        a.losses[3] = (float)(a.w[4] * (((a.w[0] * lp + a.w[1] * lm) + a.w[2] * lj) + a.w[3] * commit));      // train_poseVQ.py:152-156
+    }
+}
+
 }  // namespace
+
+int launch_recon_loss(ReconLossArgs& a, hipStream_t s) {
+    if (a.B < 1 || !a.partial || !a.losses) return -1;
+    const int per[3] = {189, 20670, THMR_SMPLH_NOUT * 3};
+    const float* present[3] = {a.pred_rot, a.pred_verts, a.pred_joints};
+    int n = 0;
+    for (int i = 0; i < 3; ++i) n += a.nblk[i] = present[i] ? (int)(((int64_t)a.B * per[i] + kReconSpan - 1) / kReconSpan) : 0;      // an absent term: mean 0
+    if (n < 1) return -1;
+    a.count[0] = (double)a.B * 189; a.count[1] = (double)a.B * 20670; a.count[2] = (double)a.B * (a.jhi - a.jlo) * 3;
+    for (int i = 0; i < 3; ++i) a.gscale[i] = (float)(a.w[4] * a.w[i] / a.count[i]);
+    hipLaunchKernelGGL(recon_loss_terms_kernel, dim3(n), dim3(256), 0, s, a);
+    if (hipGetLastError() != hipSuccess) return -2;
+    hipLaunchKernelGGL(recon_loss_final_kernel, dim3(1), dim3(256), 0, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 
 int launch_val_loss(const ValLossArgs& a, hipStream_t s) {
     if (a.B < 1 || !a.partial || a.pelvis_id < 0 || a.pelvis_id >= kKp || (a.mode != 0 && a.mode != 1)) return -1;

@@ -184,6 +184,13 @@ int thmr_op_rot6d(const float* x, float* R, int32_t n, void* stream) {
     return 0;
 }
 
+int thmr_op_rot6d_backward(const float* x, const float* grad_R, float* grad_x, int32_t n, void* stream) {
+    if (!x || !grad_R || !grad_x) return fail(THMR_ERR_INVALID, "rot6d_backward: null buffer");
+    if (n < 1) return fail(THMR_ERR_INVALID, "rot6d_backward: n >= 1 is required");
+    LAUNCH_OK(launch_rot6d_backward(x, grad_R, grad_x, n, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int thmr_op_aa_to_rotmat(const float* aa, float* R, int32_t n, void* stream) {
     if (!aa || !R || n < 1) return fail(THMR_ERR_INVALID, "bad argument");
     LAUNCH_OK(launch_aa_to_rotmat(aa, R, n, static_cast<hipStream_t>(stream)));
@@ -459,7 +466,20 @@ struct thmr_smplh {
     float* mem = nullptr;
     int max_batch = 0;
     size_t o_vt, o_sd, o_pd, o_jr, o_w, o_wb, o_int, o_jt, o_jsd, o_dirs, o_dirsb, o_A, o_xf, o_vposed, o_rot, total;
+    // the backward's own allocations (thmr_smplh_grad_reserve), one per path, [0] full and [1] folded: the path's dirs transposed
+    // (kx, 20672), g_vposed (B, 20672), the gA partials (B, 27, (nj + 1) * 12), the split-K planes (38, B, kx) and, for pose2rot, the rotation
+    // matrices' gradient (B, nj, 9)
+    struct Grad { float* mem = nullptr; size_t dirs, vp, part, planes, rot; } grad[2];
+    int device = 0;
 };
+
+static void smplh_fill(const thmr_smplh* m, SmplhArgs& a) {
+    const int32_t* ints = reinterpret_cast<const int32_t*>(m->mem + m->o_int);
+    a.Jt = m->mem + m->o_jt; a.Jsd = m->mem + m->o_jsd;
+    a.parents = ints; a.extra = ints + 64; a.fold = ints + 128;
+    a.vt = m->mem + m->o_vt; a.dirsT = m->mem + m->o_dirs; a.dirsT_body = m->mem + m->o_dirsb; a.W = m->mem + m->o_w; a.W_body = m->mem + m->o_wb;
+    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_xf; a.vposed = m->mem + m->o_vposed;
+}
 
 int thmr_smplh_create(const thmr_smplh_desc* d, int32_t max_batch, int32_t device, thmr_smplh** out) {
     constexpr int HJ = THMR_SMPLH_NJ, HB = THMR_SMPLH_NBODY, HP = THMR_SMPLH_NP;
@@ -488,6 +508,7 @@ int thmr_smplh_create(const thmr_smplh_desc* d, int32_t max_batch, int32_t devic
     for (int j = 0; j < HJ; ++j) fold[j] = j < HB ? j : fold[par[j]];
     thmr_smplh* m = new thmr_smplh();
     m->max_batch = max_batch;
+    m->device = device;
     size_t off = 0;
     auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
     m->o_vt = take((size_t)NV * 3); m->o_sd = take((size_t)NV * 30); m->o_pd = take((size_t)HP * NV * 3);
@@ -522,6 +543,8 @@ int thmr_smplh_create(const thmr_smplh_desc* d, int32_t max_batch, int32_t devic
 void thmr_smplh_destroy(thmr_smplh* m) {
     if (!m) return;
     if (m->mem) (void)hipFree(m->mem);
+    for (auto& g : m->grad)
+        if (g.mem) (void)hipFree(g.mem);
     delete m;
 }
 
@@ -538,14 +561,69 @@ int thmr_smplh_forward(thmr_smplh* m, const float* pose, int32_t pose2rot, const
         LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * nj, st));
         rot = m->mem + m->o_rot;
     }
-    const int32_t* ints = reinterpret_cast<const int32_t*>(m->mem + m->o_int);
     SmplhArgs a{};
-    a.rotmat = rot; a.betas = betas; a.transl = transl; a.Jt = m->mem + m->o_jt; a.Jsd = m->mem + m->o_jsd;
-    a.parents = ints; a.extra = ints + 64; a.fold = ints + 128;
-    a.vt = m->mem + m->o_vt; a.dirsT = m->mem + m->o_dirs; a.dirsT_body = m->mem + m->o_dirsb; a.W = m->mem + m->o_w; a.W_body = m->mem + m->o_wb;
-    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_xf; a.vposed = m->mem + m->o_vposed;
+    smplh_fill(m, a);
+    a.rotmat = rot; a.betas = betas; a.transl = transl;
     a.verts = verts; a.joints = joints; a.B = B; a.body_only = body_only;
     LAUNCH_OK(launch_smplh(a, st));
+    return 0;
+}
+
+int thmr_smplh_grad_reserve(thmr_smplh* m, int32_t paths) {
+    if (!m) return fail(THMR_ERR_INVALID, "smplh_grad_reserve: null handle");
+    if (paths < 1 || paths > (THMR_SMPLH_GRAD_FOLDED | THMR_SMPLH_GRAD_FULL))
+        return fail(THMR_ERR_INVALID, "smplh_grad_reserve: paths is THMR_SMPLH_GRAD_FOLDED (1), THMR_SMPLH_GRAD_FULL (2) or both (3)");
+    HIP_OK(hipSetDevice(m->device));
+    for (int folded = 0; folded < 2; ++folded) {
+        thmr_smplh::Grad& g = m->grad[folded];
+        if (!(paths & (folded ? THMR_SMPLH_GRAD_FOLDED : THMR_SMPLH_GRAD_FULL)) || g.mem) continue;
+        const size_t B = (size_t)m->max_batch, kx = folded ? THMR_SMPLH_KXB : THMR_SMPLH_KX, nj = folded ? THMR_SMPLH_NBODY : THMR_SMPLH_NJ;
+        size_t off = 0;
+        auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
+        g.dirs = take(kx * THMR_LBS_GK); g.vp = take(B * THMR_LBS_GK); g.part = take(B * (folded ? THMR_SMPLH_GA_BODY : THMR_SMPLH_GA));
+        g.planes = take((size_t)THMR_LBS_GKSPLIT * B * kx); g.rot = take(B * nj * 9);
+        float* mem = nullptr;
+        if (hipMalloc(&mem, off * sizeof(float)) != hipSuccess) return fail(THMR_ERR_NOMEM, "hipMalloc(smplh backward workspace) failed");
+        if (launch_body_build_dirs_k(m->mem + (folded ? m->o_dirsb : m->o_dirs), mem + g.dirs, (int)kx, nullptr) != 0 ||
+            hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(mem);
+            return fail(THMR_ERR_HIP, "smplh_grad_reserve: building the transposed blend-shape matrix failed");
+        }
+        g.mem = mem;
+    }
+    return 0;
+}
+
+int thmr_smplh_backward(thmr_smplh* m, const float* pose, int32_t pose2rot, const float* betas, const float* transl, int32_t body_only,
+                        int32_t B, const float* grad_verts, const float* grad_joints, float* grad_pose, float* grad_betas,
+                        float* grad_transl, void* stream) {
+    if (!m || !pose) return fail(THMR_ERR_INVALID, "smplh_backward: null handle or pose");
+    if (!grad_verts && !grad_joints) return fail(THMR_ERR_INVALID, "smplh_backward: grad_verts and grad_joints are both null");
+    if (!grad_pose && !grad_betas && !grad_transl) return fail(THMR_ERR_INVALID, "smplh_backward: grad_pose, grad_betas and grad_transl are all null");
+    if (B < 1 || B > m->max_batch) return fail(THMR_ERR_INVALID, "smplh_backward: batch outside [1, max_batch]");
+    if ((pose2rot != 0 && pose2rot != 1) || (body_only != 0 && body_only != 1))
+        return fail(THMR_ERR_INVALID, "smplh_backward: pose2rot and body_only are 0 or 1");
+    const thmr_smplh::Grad& gm = m->grad[body_only];
+    if (!gm.mem)
+        return fail(THMR_ERR_INVALID, body_only ? "smplh_backward: the folded path was not reserved (thmr_smplh_grad_reserve with THMR_SMPLH_GRAD_FOLDED)"
+                                                : "smplh_backward: the full path was not reserved (thmr_smplh_grad_reserve with THMR_SMPLH_GRAD_FULL)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nj = body_only ? THMR_SMPLH_NBODY : THMR_SMPLH_NJ;
+    const float* rot = pose;
+    if (pose2rot) {
+        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * nj, st));
+        rot = m->mem + m->o_rot;
+    }
+    SmplhArgs a{};
+    smplh_fill(m, a);
+    a.rotmat = rot; a.betas = betas; a.transl = transl; a.B = B; a.body_only = body_only;
+    SmplhGradArgs g{};
+    g.gV = grad_verts; g.gJ = grad_joints; g.dirsK = gm.mem + gm.dirs;
+    g.gvp = gm.mem + gm.vp; g.gApart = gm.mem + gm.part; g.planes = gm.mem + gm.planes;
+    g.grad_rotmat = !grad_pose ? nullptr : (pose2rot ? gm.mem + gm.rot : grad_pose);
+    g.grad_betas = grad_betas; g.grad_transl = grad_transl;
+    LAUNCH_OK(launch_smplh_backward(a, g, st));
+    if (pose2rot && grad_pose) LAUNCH_OK(launch_rodrigues_backward(pose, gm.mem + gm.rot, grad_pose, B * nj, st));
     return 0;
 }
 
@@ -594,6 +672,44 @@ int thmr_val_loss(const thmr_val_loss_desc* d, const thmr_val_loss_in* in, int32
     a.loose_weight = (float)d->loose_weight;
     a.B = B; a.pelvis_id = d->pelvis_id; a.mode = d->mode; a.gt_pose_is_rotmat = d->gt_pose_is_rotmat;
     LAUNCH_OK(launch_val_loss(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// ---- PoseReConsLoss, value and gradient (stateless; csrc/loss.hip) ----
+int thmr_tok_recon_loss(const float* pred_rotmat, const float* gt_rotmat, const float* pred_verts, const float* gt_verts,
+                        const float* pred_joints, const float* gt_joints, const float* vert_weights, const float* commit, int32_t pose_kind,
+                        int32_t mesh_kind, int32_t joint_kind, int32_t joint_lo, int32_t joint_hi, double w_pose, double w_mesh,
+                        double w_joint, double w_commit, double w_total, int32_t B, float* losses, float* grad_rotmat, float* grad_verts,
+                        float* grad_joints, float* workspace, void* stream) {
+    if (!losses || !workspace) return fail(THMR_ERR_INVALID, "tok_recon_loss: null losses or workspace");
+    if (!pred_rotmat != !gt_rotmat || !pred_verts != !gt_verts || !pred_joints != !gt_joints)
+        return fail(THMR_ERR_INVALID, "tok_recon_loss: a term's prediction and ground truth are given together or not at all");
+    if (!pred_rotmat && !pred_verts && !pred_joints) return fail(THMR_ERR_INVALID, "tok_recon_loss: every term is absent");
+    if ((!pred_rotmat && grad_rotmat) || (!pred_verts && grad_verts) || (!pred_joints && grad_joints))
+        return fail(THMR_ERR_INVALID, "tok_recon_loss: a gradient is asked for a term that is absent");
+    if (B < 1 || B > (1 << 16)) return fail(THMR_ERR_INVALID, "tok_recon_loss: 1 <= B <= 2^16 is required");
+    const int32_t kinds[3] = {pose_kind, mesh_kind, joint_kind};
+    for (int i = 0; i < 3; ++i) {
+        if (kinds[i] == THMR_RECON_GEODESIC)
+            return fail(THMR_ERR_UNSUPPORTED, "tok_recon_loss: 'geodesic' is not differentiated here (acos at its clamp has no finite gradient)");
+        if (kinds[i] == THMR_RECON_ROTDIST)
+            return fail(THMR_ERR_UNSUPPORTED, "tok_recon_loss: 'rotdist' is not differentiated here (acos at its clamp has no finite gradient)");
+        if (kinds[i] < THMR_RECON_L1 || kinds[i] > THMR_RECON_WT_L2)
+            return fail(THMR_ERR_INVALID, "tok_recon_loss: a kind is THMR_RECON_L1, _L2, _L1_SMOOTH or _WT_L2");
+    }
+    if (pred_verts && mesh_kind == THMR_RECON_WT_L2 && !vert_weights) return fail(THMR_ERR_INVALID, "tok_recon_loss: 'wt_l2' on the mesh needs the vertex weights");
+    if (joint_lo < 0 || joint_hi <= joint_lo || joint_hi > THMR_SMPLH_NOUT)
+        return fail(THMR_ERR_INVALID, "tok_recon_loss: 0 <= joint_lo < joint_hi <= 73 is required");
+    ReconLossArgs a{};
+    a.pred_rot = pred_rotmat; a.gt_rot = gt_rotmat; a.pred_verts = pred_verts; a.gt_verts = gt_verts; a.pred_joints = pred_joints;
+    a.gt_joints = gt_joints; a.vert_w = vert_weights; a.commit = commit;
+    a.losses = losses; a.grad_rot = grad_rotmat; a.grad_verts = grad_verts; a.grad_joints = grad_joints; a.partial = workspace;
+    // WeightedMSE on the pose or the joints has all-ones weights in the reference (losses.py:93-100): it is l2
+    a.kind[0] = pose_kind == THMR_RECON_WT_L2 ? THMR_RECON_L2 : pose_kind; a.kind[1] = mesh_kind;
+    a.kind[2] = joint_kind == THMR_RECON_WT_L2 ? THMR_RECON_L2 : joint_kind;
+    a.jlo = joint_lo; a.jhi = joint_hi; a.B = B;
+    a.w[0] = w_pose; a.w[1] = w_mesh; a.w[2] = w_joint; a.w[3] = w_commit; a.w[4] = w_total;
+    LAUNCH_OK(launch_recon_loss(a, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

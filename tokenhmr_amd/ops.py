@@ -291,13 +291,45 @@ def vit_attention_b16(qkv, out_split=False, qt=0, out=None):
 
 
 def rot6d_to_rotmat(x):
+    """geometry.py:64-84 rot6d_to_rotmat == rotation_utils.py:510-531 rotation_6d_to_matrix: (..., 6) -> (n,3,3).  Differentiable: under
+    torch.is_grad_enabled(), an x that requires grad gets a graph whose backward is thmr_op_rot6d_backward."""
     _req(x)
-    x2 = x.reshape(-1, 6).contiguous()
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _Rot6dFn.apply(x.reshape(-1, 6))      # the reshape carries the gradient back to x's own shape
+    return _rot6d(x.reshape(-1, 6).contiguous())
+
+
+def _rot6d(x2):
     n = x2.shape[0]
-    R = torch.empty(n, 3, 3, device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        _check(_L().thmr_op_rot6d(_p(x2), _p(R), n, _s(x)))
+    R = torch.empty(n, 3, 3, device=x2.device, dtype=torch.float32)
+    with torch.cuda.device(x2.device):
+        _check(_L().thmr_op_rot6d(_p(x2), _p(R), n, _s(x2)))
     return R
+
+
+def rot6d_backward(x, grad_R, out=None):
+    """thmr_op_rot6d_backward: x (n,6), grad_R (n,3,3) -> the gradient by x, (n,6); `out` receives it when given (no allocation)."""
+    _req(x, grad_R)
+    g = torch.empty_like(x) if out is None else out
+    with torch.cuda.device(x.device):
+        _check(_L().thmr_op_rot6d_backward(_p(x), _p(grad_R), _p(g), x.shape[0], _s(x)))
+    return g
+
+
+class _Rot6dFn(torch.autograd.Function):
+    """rot6d_to_rotmat under autograd: backward = thmr_op_rot6d_backward (csrc/head.hip rot6d_backward_kernel), once differentiable."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return _rot6d(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gR):
+        x, = ctx.saved_tensors
+        return rot6d_backward(x, gR.to(torch.float32).contiguous())
 
 
 def aa_to_rotmat(theta):

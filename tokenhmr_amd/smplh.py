@@ -15,6 +15,10 @@ pinned against it:
     coefficients (omitted: zeros) and are expanded by hands_components{l,r}[:num_pca_comps]; with use_pca=False as 45 values.  Then
     pose_mean is added — zeros except hands_mean{l,r} when flat_hand_mean=False — and the full 52-joint path runs.
   * joints = the 52 posed chain joints, then the 21 vertices of config.SMPL_EXTRA_VERTS (VertexJointSelector order).
+Both classes are differentiable like the ones they stand in for: under torch.is_grad_enabled(), if any pose part, betas
+or transl requires grad, `vertices` and `joints` carry a graph whose backward is the device's own (`thmr_smplh_backward`, either path);
+SMPLH's PCA hands and mean pose are torch ops above the call and differentiate by themselves.  Otherwise exactly the plain path: the
+same launches and the same bits.  `enable_grad(paths=...)` reserves the backward's workspace ahead of a graph capture.
 One reference quirk follows and is reproduced, not corrected: the dataset's SMPLH(flat_hand_mean=False) gives the ground-truth mesh
 relaxed hands while the decoder's SMPLHLayer gives the predicted mesh flat hands, so the reference's mesh error carries a constant
 hand term.
@@ -45,6 +49,35 @@ def _constants(model, num_betas, ext, gender):
     return load_smplh_pkl(path, num_betas)
 
 
+GRAD_FOLDED, GRAD_FULL = 1, 2       # header: THMR_SMPLH_GRAD_*
+
+
+class _SmplhFn(torch.autograd.Function):
+    """forward = thmr_smplh_forward (the launches and bits of the plain path), backward = thmr_smplh_backward on the current stream.  Saves
+    the inputs only: the backward recomputes the forward's intermediates.  Once differentiable: a double backward raises."""
+
+    @staticmethod
+    def forward(ctx, model, pose, betas, transl, pose2rot, body_only):
+        ctx.model, ctx.pose2rot, ctx.body_only = model, pose2rot, body_only
+        ctx.save_for_backward(pose, betas, transl)
+        ctx.set_materialize_grads(False)            # an unused output's gradient stays None and becomes a NULL pointer, not a zero tensor
+        return model._launch(pose, pose2rot, betas, transl, body_only, pose.shape[0])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_verts, g_joints):
+        pose, betas, transl = ctx.saved_tensors
+        if g_verts is None and g_joints is None:
+            return None, None, None, None, None, None
+        m, B = ctx.model, pose.shape[0]
+        g_verts, g_joints = (None if g is None else g.to(m.device, torch.float32).contiguous() for g in (g_verts, g_joints))
+        g_pose = torch.empty_like(pose) if ctx.needs_input_grad[1] else None
+        g_betas = torch.empty_like(betas) if betas is not None and ctx.needs_input_grad[2] else None
+        g_transl = torch.empty_like(transl) if transl is not None and ctx.needs_input_grad[3] else None
+        m._backward(pose, ctx.pose2rot, betas, transl, ctx.body_only, B, g_verts, g_joints, g_pose, g_betas, g_transl)
+        return None, g_pose, g_betas, g_transl, None, None
+
+
 class _SMPLHBase(_cabi.Handle):
     no_gpu_error = _cabi.EngineError
 
@@ -71,6 +104,7 @@ class _SMPLHBase(_cabi.Handle):
         self.faces = constants.get("faces")
         self.folded_calls = self.full_calls = 0
         self._host = constants
+        self._grad_paths = 0
 
     def _handle(self):
         """The device handle, created by the first forward: construction and every argument check need no GPU."""
@@ -110,7 +144,37 @@ class _SMPLHBase(_cabi.Handle):
     def _opt(self, t, B, n):
         return None if t is None else t.reshape(B, n).to(self.device, torch.float32).contiguous()
 
+    def enable_grad(self, paths=("folded", "full")):
+        """Reserves the backward's workspace for the named paths (thmr_smplh_grad_reserve: allocates and synchronises once per path; a
+        differentiable forward does it on first need for the path it runs).  'folded' is SMPLHLayer without hands, the tokenizer's call;
+        'full' is everything else and costs 40 MB more.  Call it before capturing a differentiable forward + backward in a graph."""
+        names = {"folded": GRAD_FOLDED, "full": GRAD_FULL}
+        mask = 0
+        for p in ((paths,) if isinstance(paths, str) else paths):
+            if p not in names:
+                raise ValueError(f"enable_grad(paths=...) takes 'folded' and / or 'full', got {p!r}")
+            mask |= names[p]
+        if mask & ~self._grad_paths:
+            with torch.cuda.device(self.device):
+                self._check(self.lib.thmr_smplh_grad_reserve(self._handle(), mask), "thmr_smplh_grad_reserve")
+            self._grad_paths |= mask
+        return self
+
     def _run(self, pose, pose2rot, betas, transl, body_only, B):
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (pose, betas, transl)):
+            self.enable_grad("folded" if body_only else "full")
+            return _SmplhFn.apply(self, pose, betas, transl, bool(pose2rot), bool(body_only))
+        with torch.no_grad():
+            return self._launch(pose, pose2rot, betas, transl, body_only, B)
+
+    def _backward(self, pose, pose2rot, betas, transl, body_only, B, g_verts, g_joints, g_pose, g_betas, g_transl):
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._check(self.lib.thmr_smplh_backward(self._handle(), _p(pose), 1 if pose2rot else 0, _p(betas), _p(transl), 1 if body_only else 0,
+                                                     B, _p(g_verts), _p(g_joints), _p(g_pose), _p(g_betas), _p(g_transl), st),
+                        "thmr_smplh_backward")
+
+    def _launch(self, pose, pose2rot, betas, transl, body_only, B):
         verts = torch.empty(B, 6890, 3, device=self.device, dtype=torch.float32)
         joints = torch.empty(B, 73, 3, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
@@ -124,8 +188,7 @@ class _SMPLHBase(_cabi.Handle):
         return verts, joints
 
     def __call__(self, *args, **kwargs):
-        with torch.no_grad():
-            return self.forward(*args, **kwargs)
+        return self.forward(*args, **kwargs)
 
 
 class SMPLHLayer(_SMPLHBase):

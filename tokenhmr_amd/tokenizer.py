@@ -167,6 +167,12 @@ class VanillaTokenizer(_TokenizerModule):
     (smpl_assets.load_smplh_pkl / make_synthetic_smplh): the module then builds a `tokenhmr_amd.smplh.SMPLHLayer` on its device, which
     runs the folded 22-joint kernels; or any callable, called as body_model(body_pose=rotmat) like the reference's module-level layer.
 
+    `__call__` is the inference path and stays under no_grad.  The value and gradient of the training objective for its output (with a
+    body model) take two lines (tokenhmr_amd.tokenizer_loss):
+
+        output, loss_commit, perplexity = net(gt_pose)
+        losses, grad_6d = PoseReConsLoss(hparams.LOSS, 21, 'rotmat', 'smplh', body_model=net.body_model).value_and_grad(batch, output, loss_commit)
+
     encode(x) -> (B,160) int64 does what EncodeTokens does (encoder, `preprocess`, argmin).  The reference's own
     VanillaTokenizer.encode RAISES ("mat1 and mat2 shapes cannot be multiplied (768x160 and 256x2048)"): it skips `preprocess`
     (:238-240), so there is no reference behaviour to match beyond the layout its `.view(batch_size, -1)` intends.
