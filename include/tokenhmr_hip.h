@@ -643,6 +643,39 @@ typedef struct thmr_val_loss_out {   /* every pointer may be NULL */
 } thmr_val_loss_out;
 int thmr_val_loss(const thmr_val_loss_desc* desc, const thmr_val_loss_in* in, int32_t B, const thmr_val_loss_out* out,
                   float* workspace_dev, void* stream);
+/* The gradient of that loss (csrc/loss.hip): d total / d of what compute_loss reads and, through the projection of
+ * forward_step (tokenhmr.py:166-168, 183-185), d total / d (the body model's joints, pred_cam).  `desc` and `in` are thmr_val_loss's, with
+ * the same meaning; the total is the weighted SUM over the B items that thmr_val_loss writes to losses[0] (nothing is divided by B).  The
+ * masks of the loose mode are recomputed by the forward's own device functions and are constants for the gradient; the L1 terms carry
+ * torch's sign(0) = 0.  New symbol under ABI 5: no struct or signature changed.
+ * grads_host: a table in HOST memory of THMR_LOSS_GRAD_SLOTS device pointers, indexed by THMR_LOSS_GRAD_*.  A NULL slot is not computed;
+ * every other slot is written in full, zeros included:
+ *   KP2D   (B,44,2)    by pred_keypoints_2d:  w2d c2 sign(pred - gt), c2 = conf (plain) or conf valid2d + loose_weight weak2d (loose)
+ *   KP3D   (B,44,3)    by pred_keypoints_3d:  c_k = w3d conf3d_used sign((p_k - p_pelvis) - (g_k - g_pelvis)), minus sum_k c_k on the pelvis row
+ *   JOINTS (B,44,3)    by the body model's joints, KP3D + the projection's adjoint of KP2D: what thmr_smpl_backward takes as grad_joints_dev
+ *   CAM    (B,3)       by pred_cam, through t = (cam1, cam2, 2 F / (S cam0 + 1e-9))
+ *   ROTMAT (B,24,3,3)  by pred_rotmat, the direct term only:  2 w m (P - G), joint 0 with w_global_orient; m = has (plain) or
+ *                      valid_rot + loose_weight weak_rot (loose)
+ *   BETAS  (B,10)      by pred_betas, the direct term only:  2 w_betas has_betas (p - g); loose: has_betas valid_3d
+ * pred_cam (B,3) device memory or NULL; JOINTS and CAM need it.  The projection is that of thmr_lbs_forward with focal_length
+ * (EXTRA.FOCAL_LENGTH) and image_size (MODEL.IMAGE_SIZE): X = pred_keypoints_3d + t, (u, v) = (F / S) X_xy / X_z, with (u, v) read from
+ * pred_keypoints_2d, the values the loss saw.
+ * One launch on `stream` (one wave per item), no workspace, no allocation, no host synchronisation, no atomics: two runs are bit-equal and
+ * a captured call replays like the eager one.
+ * Refused before any HIP call (THMR_ERR_INVALID, message in thmr_last_error(NULL)): a null descriptor, input struct or table; what
+ * thmr_val_loss refuses of `desc`, `in` and B (a null required input, B outside [1, 2^24], a mode that is not 0 or 1, loose mode without
+ * valid_3d, kp2d_thresh or angle_thresh, pelvis_id outside [0, 44), a gt_pose_is_rotmat that is not 0 or 1, gt_keypoints_3d not 16-byte
+ * or pred_keypoints_2d not 8-byte aligned); every slot NULL; JOINTS or CAM without pred_cam; with pred_cam, a focal_length or image_size
+ * that is not finite and positive. */
+#define THMR_LOSS_GRAD_KP2D 0
+#define THMR_LOSS_GRAD_KP3D 1
+#define THMR_LOSS_GRAD_JOINTS 2
+#define THMR_LOSS_GRAD_CAM 3
+#define THMR_LOSS_GRAD_ROTMAT 4
+#define THMR_LOSS_GRAD_BETAS 5
+#define THMR_LOSS_GRAD_SLOTS 6
+int thmr_val_loss_grad(const thmr_val_loss_desc* desc, const thmr_val_loss_in* in, const float* pred_cam, double focal_length,
+                       double image_size, int32_t B, float** grads_host, void* stream);
 /* TokenLoss (losses.py:230-252): CrossEntropyLoss in mean reduction over the rows of an fp32 (rows, 2048) matrix,
  *   out_dev[0] = mean_r (log sum_k exp(x[r][k] - max_r) + max_r - x[r][target[r]]),
  * applied to whatever it is handed — the reference passes the softmax output cls_logits_softmax (rows = B x 160); raw logits work too.

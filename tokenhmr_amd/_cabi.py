@@ -53,6 +53,8 @@ MEAN_ROW_DIST_WS = 256      # header: THMR_MEAN_ROW_DIST_WS
 # thmr_val_loss / thmr_op_token_ce (header: THMR_VAL_LOSS_*, THMR_TOKEN_CE_WS_PER_ROW): modes and workspace floats per item / per row
 VAL_LOSS_PLAIN, VAL_LOSS_LOOSE = 0, 1
 VAL_LOSS_WS_PER_ITEM, TOKEN_CE_WS_PER_ROW = 5, 1
+# thmr_val_loss_grad (header: THMR_LOSS_GRAD_*): the slots of its host table of device pointers
+LOSS_GRAD_KP2D, LOSS_GRAD_KP3D, LOSS_GRAD_JOINTS, LOSS_GRAD_CAM, LOSS_GRAD_ROTMAT, LOSS_GRAD_BETAS, LOSS_GRAD_SLOTS = 0, 1, 2, 3, 4, 5, 6
 VAL_LOSS_IN_FIELDS = ["pred_keypoints_2d", "pred_keypoints_3d", "pred_rotmat", "pred_betas", "gt_keypoints_2d", "gt_keypoints_3d", "gt_pose",
                       "gt_betas", "has_global_orient", "has_body_pose", "has_betas", "valid_3d", "kp2d_thresh", "angle_thresh"]
 VAL_LOSS_OUT_FIELDS = ["losses", "per_item", "kp2d_err", "angle_err", "valid2d", "weak2d", "valid_rot", "weak_rot", "conf2d_used",

@@ -483,6 +483,15 @@ struct ValLossArgs {
     int B, pelvis_id, mode, gt_pose_is_rotmat;
 };
 int launch_val_loss(const ValLossArgs& a, hipStream_t s);
+// The gradient of the same loss (sums, nothing divided by B) by what compute_loss reads, and through the projection: `in` carries the
+// inputs, weights and mode of the forward (its output pointers are not read).  Every slot may be null: a null slot's branch is skipped.
+struct ValLossGradArgs {
+    ValLossArgs in;
+    const float* pred_cam;                                                // (B,3) or null: no projection adjoint (g_joints, g_cam null)
+    float *g_kp2d, *g_kp3d, *g_joints, *g_cam, *g_rotmat, *g_betas;       // (B,44,2) (B,44,3) (B,44,3) (B,3) (B,24,3,3) (B,10)
+    float focal_length, img_size;
+};
+int launch_val_loss_grad(const ValLossGradArgs& a, hipStream_t s);
 // PoseReConsLoss, value and gradient of the weighted total (loss.hip).  kind: THMR_RECON_* per term (pose, mesh, joints); w: POSE, MESH, JNT,
 // COMMIT, LOSS_WT; the launcher fills nblk, count and gscale.  partial: THMR_TOK_RECON_WS_BASE + B * THMR_TOK_RECON_WS_PER_ITEM floats
 struct ReconLossArgs {

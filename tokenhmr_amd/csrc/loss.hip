@@ -29,6 +29,38 @@ constexpr int kClasses = 2048;
 struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
 struct __attribute__((packed, aligned(4))) F9 { float m[9]; };
 
+// The masks of the LOOSE_SUP branch, written once for the value (val_loss_items_kernel) and for the gradient (val_loss_grad_kernel): both
+// evaluate these expressions in this fp32 order, so they cannot disagree about the side of a threshold an entry lies on.
+struct KpMask { float err, valid, weak, conf2, conf3; };
+__device__ __forceinline__ KpMask loose_kp_mask(float conf2, float conf3, float dx, float dy, float thresh, float v3) {
+    KpMask m;
+    m.err = conf2 * (dx * dx + dy * dy);                                   // tokenhmr.py:218-219
+    m.valid = m.err > thresh ? 1.f : 0.f;                                  // :220
+    m.weak = conf2 * (1.f - m.valid);                                      // :221
+    m.conf2 = conf2 * m.valid;                                             // :223
+    m.conf3 = conf3 * ((v3 + m.conf2) > 0.5f ? 1.f : 0.f);                 // :227
+    return m;
+}
+
+struct RotMask { float angle, valid, weak; };
+__device__ __forceinline__ RotMask loose_rot_mask(const float* P, const float* G, float has, float thresh, float v3) {
+    // joint_angle_error (losses.py:22-33): |matrix_to_axis_angle(R_pred R_gt^T)|
+    float Rr[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            Rr[i * 3 + k] = fmaf(P[i * 3 + 2], G[k * 3 + 2], fmaf(P[i * 3 + 1], G[k * 3 + 1], P[i * 3 + 0] * G[k * 3 + 0]));
+    float ax, ay, az;
+    rotmat_to_aa_dev(Rr, ax, ay, az);
+    RotMask m;
+    m.angle = sqrtf(ax * ax + ay * ay + az * az);
+    const float over = m.angle > thresh ? 1.f : 0.f;                       // tokenhmr.py:244
+    m.valid = (over * has + v3) != 0.f ? 1.f : 0.f;                        // :245, .bool()
+    m.weak = (1.f - m.valid) * has;                                        // :246
+    return m;
+}
+
 __global__ __launch_bounds__(256) void val_loss_items_kernel(ValLossArgs a) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -51,16 +83,14 @@ __global__ __launch_bounds__(256) void val_loss_items_kernel(ValLossArgs a) {
         float conf2 = g2.z;                    // what the 2D loss multiplies with (Keypoint2DLoss, losses.py:61-63)
         float conf3 = g3.w;
         if (loose) {
-            const float err = conf2 * (dx * dx + dy * dy);                 // tokenhmr.py:218-219
-            const float valid = err > a.kp2d_thresh[k] ? 1.f : 0.f;        // :220
-            const float weak = conf2 * (1.f - valid);                      // :221
-            conf2 = conf2 * valid;                                         // :223
-            conf3 = conf3 * ((v3 + conf2) > 0.5f ? 1.f : 0.f);             // :227
+            const KpMask m = loose_kp_mask(conf2, conf3, dx, dy, a.kp2d_thresh[k], v3);
+            conf2 = m.conf2;                                               // :223
+            conf3 = m.conf3;                                               // :227
             if (lane < kKp) {
-                w2 = weak * l1;                                            // losses.py:130
-                if (a.kp2d_err) a.kp2d_err[r] = err;
-                if (a.valid2d) a.valid2d[r] = valid;
-                if (a.weak2d) a.weak2d[r] = weak;
+                w2 = m.weak * l1;                                          // losses.py:130
+                if (a.kp2d_err) a.kp2d_err[r] = m.err;
+                if (a.valid2d) a.valid2d[r] = m.valid;
+                if (a.weak2d) a.weak2d[r] = m.weak;
                 if (a.conf2d_used) a.conf2d_used[r] = conf2;
                 if (a.conf3d_used) a.conf3d_used[r] = conf3;
             }
@@ -98,25 +128,13 @@ __global__ __launch_bounds__(256) void val_loss_items_kernel(ValLossArgs a) {
         const float has = j == 0 ? a.has_global_orient[b] : a.has_body_pose[b];
         float strong = has * sq, weakv = 0.f;                              // ParameterLoss (losses.py:187-192)
         if (loose) {
-            // joint_angle_error (losses.py:22-33): |matrix_to_axis_angle(R_pred R_gt^T)|
-            float Rr[9];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    Rr[i * 3 + k] = fmaf(P.m[i * 3 + 2], G[k * 3 + 2], fmaf(P.m[i * 3 + 1], G[k * 3 + 1], P.m[i * 3 + 0] * G[k * 3 + 0]));
-            float ax, ay, az;
-            rotmat_to_aa_dev(Rr, ax, ay, az);
-            const float angle = sqrtf(ax * ax + ay * ay + az * az);
-            const float over = angle > a.angle_thresh[j] ? 1.f : 0.f;      // tokenhmr.py:244
-            const float valid = (over * has + v3) != 0.f ? 1.f : 0.f;      // :245, .bool()
-            const float weak = (1.f - valid) * has;                        // :246
-            strong = valid * sq;                                           // losses.py:214
-            weakv = weak * sq;                                             // :218
+            const RotMask m = loose_rot_mask(P.m, G, has, a.angle_thresh[j], v3);
+            strong = m.valid * sq;                                         // losses.py:214
+            weakv = m.weak * sq;                                           // :218
             if (lane < kJoints) {
-                if (a.angle_err) a.angle_err[r] = angle;
-                if (a.valid_rot) a.valid_rot[r] = valid;
-                if (a.weak_rot) a.weak_rot[r] = weak;
+                if (a.angle_err) a.angle_err[r] = m.angle;
+                if (a.valid_rot) a.valid_rot[r] = m.valid;
+                if (a.weak_rot) a.weak_rot[r] = m.weak;
             }
         }
         if (lane < kJoints) { srot = strong; wrot = weakv; }
@@ -178,6 +196,124 @@ __global__ __launch_bounds__(256) void val_loss_final_kernel(ValLossArgs a) {
             for (int i = 0; i < 6; ++i) a.running[i] += (double)l[i];
             a.running[6] += 1.0;
         }
+    }
+}
+
+// ---- the gradient of the same loss: d total / d (pred_keypoints_2d, pred_keypoints_3d, pred_rotmat, pred_betas), and
+//      through the projection of forward_step (tokenhmr.py:166-168, 183-185; body_model.hip) d total / d (joints, pred_cam).  The shape of
+//      val_loss_items_kernel: one wave64 per item, lanes 0..43 a keypoint, 0..23 a joint, 0..9 a beta; no LDS, no atomics, nothing crosses
+//      items, so there is no workspace and no second launch.  The total is a SUM over items: nothing is divided by B.  The masks are
+//      constants for the gradient (in the reference they pass through `>` and .bool()) and come from the forward's own functions above.
+//      L1 terms carry torch's sign(0) = 0.  A null slot's branch is skipped; every other slot is written in full, zeros included. ----
+__device__ __forceinline__ float sign0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+
+__global__ __launch_bounds__(256) void val_loss_grad_kernel(ValLossGradArgs g) {
+    const ValLossArgs& a = g.in;
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;              // whole waves leave: nothing below crosses waves
+    const bool loose = a.mode == 1;
+    const float lw = a.loose_weight;
+    const float v3 = loose ? a.valid_3d[b] : 0.f;
+    const bool project = g.g_joints || g.g_cam;                            // the entry point refuses either without pred_cam
+    const bool want2 = g.g_kp2d || project, want3 = g.g_kp3d || g.g_joints;
+
+    // ---- keypoints: lane k < 44 ----
+    if (want2 || want3) {
+        const int k = lane < kKp ? lane : 0;
+        const int64_t r = (int64_t)b * kKp + k;
+        const float2 p2 = reinterpret_cast<const float2*>(a.pred_kp2d)[r];
+        const F3 g2 = reinterpret_cast<const F3*>(a.gt_kp2d)[r];
+        const F3 p3 = reinterpret_cast<const F3*>(a.pred_kp3d)[r];
+        const float4 g3 = reinterpret_cast<const float4*>(a.gt_kp3d)[r];
+        const float dx = p2.x - g2.x, dy = p2.y - g2.y;
+        float c2 = g2.z, conf3 = g3.w;
+        if (loose) {
+            const KpMask m = loose_kp_mask(g2.z, g3.w, dx, dy, a.kp2d_thresh[k], v3);
+            c2 = m.conf2 + lw * m.weak;                                    // losses.py:128-131: the strong and the weak sum of one |d|
+            conf3 = m.conf3;
+        }
+        // Keypoint2DLoss: w2d c2 sign(pred - gt)
+        float gu = 0.f, gv = 0.f;
+        if (want2 && lane < kKp) {
+            const float s = (float)a.w[0] * c2;
+            gu = s * sign0(dx);
+            gv = s * sign0(dy);
+            if (g.g_kp2d) { g.g_kp2d[r * 2 + 0] = gu; g.g_kp2d[r * 2 + 1] = gv; }
+        }
+        // Keypoint3DLoss: both sides relative to their own pelvis, so the pelvis row also collects minus every row's term
+        float cx = 0.f, cy = 0.f, cz = 0.f;
+        if (want3) {
+            const float ppx = __shfl(p3.x, a.pelvis_id, 64), ppy = __shfl(p3.y, a.pelvis_id, 64), ppz = __shfl(p3.z, a.pelvis_id, 64);
+            const float gpx = __shfl(g3.x, a.pelvis_id, 64), gpy = __shfl(g3.y, a.pelvis_id, 64), gpz = __shfl(g3.z, a.pelvis_id, 64);
+            if (lane < kKp) {
+                const float s = (float)a.w[1] * conf3;
+                cx = s * sign0((p3.x - ppx) - (g3.x - gpx));
+                cy = s * sign0((p3.y - ppy) - (g3.y - gpy));
+                cz = s * sign0((p3.z - ppz) - (g3.z - gpz));
+            }
+            const float sx = wave_sum(cx), sy = wave_sum(cy), sz = wave_sum(cz);
+            if (lane == a.pelvis_id) { cx -= sx; cy -= sy; cz -= sz; }
+            if (g.g_kp3d && lane < kKp) { g.g_kp3d[r * 3 + 0] = cx; g.g_kp3d[r * 3 + 1] = cy; g.g_kp3d[r * 3 + 2] = cz; }
+        }
+        // the projection's adjoint: X = J + t, t = (cam1, cam2, 2F / (S cam0 + 1e-9)), (u, v) = (F / S) X_xy / X_z; u, v as the loss saw them
+        if (project) {
+            const float c0 = g.pred_cam[(int64_t)b * 3 + 0];
+            const float den = g.img_size * c0 + 1e-9f;
+            const float tz = (2.0f * g.focal_length) / den;                // head.hip's cam_t
+            const float f = g.focal_length / g.img_size;
+            float qx = 0.f, qy = 0.f, qz = 0.f;
+            if (lane < kKp) {
+                const float xz = p3.z + tz;
+                qx = (f * gu) / xz;
+                qy = (f * gv) / xz;
+                qz = -(gu * p2.x + gv * p2.y) / xz;
+                if (g.g_joints) { g.g_joints[r * 3 + 0] = cx + qx; g.g_joints[r * 3 + 1] = cy + qy; g.g_joints[r * 3 + 2] = cz + qz; }
+            }
+            if (g.g_cam) {
+                const float tx = wave_sum(qx), ty = wave_sum(qy), tzs = wave_sum(qz);
+                if (lane == 0) {
+                    g.g_cam[(int64_t)b * 3 + 0] = tzs * (-(tz * g.img_size) / den);
+                    g.g_cam[(int64_t)b * 3 + 1] = tx;
+                    g.g_cam[(int64_t)b * 3 + 2] = ty;
+                }
+            }
+        }
+    }
+
+    // ---- joints: lane j < 24, joint 0 = global_orient.  ParameterLoss: 2 w m (P - G) ----
+    if (g.g_rotmat) {
+        const int j = lane < kJoints ? lane : 0;
+        const int64_t r = (int64_t)b * kJoints + j;
+        const F9 P = reinterpret_cast<const F9*>(a.pred_rotmat)[r];
+        float G[9];
+        if (a.gt_pose_is_rotmat) {
+            const F9 Gm = reinterpret_cast<const F9*>(a.gt_pose)[r];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) G[i] = Gm.m[i];
+        } else {
+            const F3 t = reinterpret_cast<const F3*>(a.gt_pose)[r];
+            aa_to_rotmat_dev(t.x, t.y, t.z, G);
+        }
+        const float has = j == 0 ? a.has_global_orient[b] : a.has_body_pose[b];
+        float m = has;
+        if (loose) {
+            const RotMask rm = loose_rot_mask(P.m, G, has, a.angle_thresh[j], v3);
+            m = rm.valid + lw * rm.weak;                                   // losses.py:214-220
+        }
+        const float s = (2.f * (float)(j == 0 ? a.w[2] : a.w[3])) * m;
+        if (lane < kJoints) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) g.g_rotmat[r * 9 + i] = s * (P.m[i] - G[i]);
+        }
+    }
+
+    // ---- betas: lane i < 10 ----
+    if (g.g_betas && lane < kBetas) {
+        float hb = a.has_betas[b];
+        if (loose) hb = hb * v3;                                           // tokenhmr.py:240
+        const int64_t r = (int64_t)b * kBetas + lane;
+        g.g_betas[r] = (2.f * (float)a.w[4] * hb) * (a.pred_betas[r] - a.gt_betas[r]);
     }
 }
 
@@ -325,6 +461,15 @@ int launch_val_loss(const ValLossArgs& a, hipStream_t s) {
         if (hipGetLastError() != hipSuccess) return -2;
     }
     return 0;
+}
+
+int launch_val_loss_grad(const ValLossGradArgs& g, hipStream_t s) {
+    const ValLossArgs& a = g.in;
+    if (a.B < 1 || a.pelvis_id < 0 || a.pelvis_id >= kKp || (a.mode != 0 && a.mode != 1)) return -1;
+    if (!g.g_kp2d && !g.g_kp3d && !g.g_joints && !g.g_cam && !g.g_rotmat && !g.g_betas) return -1;
+    if ((g.g_joints || g.g_cam) && !g.pred_cam) return -1;
+    hipLaunchKernelGGL(val_loss_grad_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, g);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int launch_token_ce(const float* x, const int32_t* target, int rows, float* out, float* row_loss, hipStream_t s) {

@@ -3,6 +3,7 @@
 // arguments before any HIP call and then launches what the engine launches, through the same launch_* functions (common.h).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -638,29 +639,42 @@ int thmr_op_mean_row_dist(const float* a, const float* b, int32_t n_rows_per_ite
     return 0;
 }
 
-// ---- the forward value of the loss (stateless; csrc/loss.hip) ----
-int thmr_val_loss(const thmr_val_loss_desc* d, const thmr_val_loss_in* in, int32_t B, const thmr_val_loss_out* out, float* workspace,
-                  void* stream) {
-    if (!d || !in || !out) return fail(THMR_ERR_INVALID, "val_loss: null descriptor, input or output struct");
+// ---- the forward value of the loss and its gradient (stateless; csrc/loss.hip) ----
+// What thmr_val_loss and thmr_val_loss_grad refuse alike, without the entry point's name in front; null when the arguments pass.
+static const char* val_loss_refusal(const thmr_val_loss_desc* d, const thmr_val_loss_in* in, int32_t B) {
     if (!in->pred_keypoints_2d || !in->pred_keypoints_3d || !in->pred_rotmat || !in->pred_betas || !in->gt_keypoints_2d ||
         !in->gt_keypoints_3d || !in->gt_pose || !in->gt_betas || !in->has_global_orient || !in->has_body_pose || !in->has_betas)
-        return fail(THMR_ERR_INVALID, "val_loss: null input buffer");
-    if (B < 1 || B > (1 << 24)) return fail(THMR_ERR_INVALID, "val_loss: 1 <= B <= 2^24 is required");
-    if (d->mode != THMR_VAL_LOSS_PLAIN && d->mode != THMR_VAL_LOSS_LOOSE)
-        return fail(THMR_ERR_INVALID, "val_loss: mode is THMR_VAL_LOSS_PLAIN (0) or THMR_VAL_LOSS_LOOSE (1)");
+        return "null input buffer";
+    if (B < 1 || B > (1 << 24)) return "1 <= B <= 2^24 is required";
+    if (d->mode != THMR_VAL_LOSS_PLAIN && d->mode != THMR_VAL_LOSS_LOOSE) return "mode is THMR_VAL_LOSS_PLAIN (0) or THMR_VAL_LOSS_LOOSE (1)";
     if (d->mode == THMR_VAL_LOSS_LOOSE && (!in->valid_3d || !in->kp2d_thresh || !in->angle_thresh))
-        return fail(THMR_ERR_INVALID, "val_loss: the loose mode needs valid_3d, kp2d_thresh and angle_thresh");
-    if (d->pelvis_id < 0 || d->pelvis_id >= 44) return fail(THMR_ERR_INVALID, "val_loss: pelvis_id outside [0, 44)");
-    if (d->gt_pose_is_rotmat != 0 && d->gt_pose_is_rotmat != 1) return fail(THMR_ERR_INVALID, "val_loss: gt_pose_is_rotmat is 0 or 1");
-    if (!workspace) return fail(THMR_ERR_INVALID, "val_loss: null workspace");
+        return "the loose mode needs valid_3d, kp2d_thresh and angle_thresh";
+    if (d->pelvis_id < 0 || d->pelvis_id >= 44) return "pelvis_id outside [0, 44)";
+    if (d->gt_pose_is_rotmat != 0 && d->gt_pose_is_rotmat != 1) return "gt_pose_is_rotmat is 0 or 1";
     if (reinterpret_cast<uintptr_t>(in->gt_keypoints_3d) % 16 != 0 || reinterpret_cast<uintptr_t>(in->pred_keypoints_2d) % 8 != 0)
-        return fail(THMR_ERR_INVALID, "val_loss: gt_keypoints_3d must be 16-byte and pred_keypoints_2d 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out->running) % 8 != 0) return fail(THMR_ERR_INVALID, "val_loss: running (7 doubles) must be 8-byte aligned");
-    ValLossArgs a{};
+        return "gt_keypoints_3d must be 16-byte and pred_keypoints_2d 8-byte aligned";
+    return nullptr;
+}
+
+// the inputs, weights and mode of both launches
+static void val_loss_inputs(ValLossArgs& a, const thmr_val_loss_desc* d, const thmr_val_loss_in* in, int32_t B) {
     a.pred_kp2d = in->pred_keypoints_2d; a.pred_kp3d = in->pred_keypoints_3d; a.pred_rotmat = in->pred_rotmat; a.pred_betas = in->pred_betas;
     a.gt_kp2d = in->gt_keypoints_2d; a.gt_kp3d = in->gt_keypoints_3d; a.gt_pose = in->gt_pose; a.gt_betas = in->gt_betas;
     a.has_global_orient = in->has_global_orient; a.has_body_pose = in->has_body_pose; a.has_betas = in->has_betas;
     a.valid_3d = in->valid_3d; a.kp2d_thresh = in->kp2d_thresh; a.angle_thresh = in->angle_thresh;
+    a.w[0] = d->w_keypoints_2d; a.w[1] = d->w_keypoints_3d; a.w[2] = d->w_global_orient; a.w[3] = d->w_body_pose; a.w[4] = d->w_betas;
+    a.loose_weight = (float)d->loose_weight;
+    a.B = B; a.pelvis_id = d->pelvis_id; a.mode = d->mode; a.gt_pose_is_rotmat = d->gt_pose_is_rotmat;
+}
+
+int thmr_val_loss(const thmr_val_loss_desc* d, const thmr_val_loss_in* in, int32_t B, const thmr_val_loss_out* out, float* workspace,
+                  void* stream) {
+    if (!d || !in || !out) return fail(THMR_ERR_INVALID, "val_loss: null descriptor, input or output struct");
+    if (const char* why = val_loss_refusal(d, in, B)) return fail(THMR_ERR_INVALID, std::string("val_loss: ") + why);
+    if (!workspace) return fail(THMR_ERR_INVALID, "val_loss: null workspace");
+    if (reinterpret_cast<uintptr_t>(out->running) % 8 != 0) return fail(THMR_ERR_INVALID, "val_loss: running (7 doubles) must be 8-byte aligned");
+    ValLossArgs a{};
+    val_loss_inputs(a, d, in, B);
     a.losses = out->losses; a.per_item = out->per_item; a.running = out->running;
     if (d->mode == THMR_VAL_LOSS_LOOSE) {
         a.kp2d_err = out->kp2d_err; a.angle_err = out->angle_err; a.valid2d = out->valid2d; a.weak2d = out->weak2d;
@@ -668,10 +682,28 @@ int thmr_val_loss(const thmr_val_loss_desc* d, const thmr_val_loss_in* in, int32
         a.has_betas_used = out->has_betas_used;
     }
     a.partial = workspace;
-    a.w[0] = d->w_keypoints_2d; a.w[1] = d->w_keypoints_3d; a.w[2] = d->w_global_orient; a.w[3] = d->w_body_pose; a.w[4] = d->w_betas;
-    a.loose_weight = (float)d->loose_weight;
-    a.B = B; a.pelvis_id = d->pelvis_id; a.mode = d->mode; a.gt_pose_is_rotmat = d->gt_pose_is_rotmat;
     LAUNCH_OK(launch_val_loss(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_val_loss_grad(const thmr_val_loss_desc* d, const thmr_val_loss_in* in, const float* pred_cam, double focal_length, double image_size,
+                       int32_t B, float** grads_host, void* stream) {
+    if (!d || !in || !grads_host) return fail(THMR_ERR_INVALID, "val_loss_grad: null descriptor, input struct or gradient table");
+    if (const char* why = val_loss_refusal(d, in, B)) return fail(THMR_ERR_INVALID, std::string("val_loss_grad: ") + why);
+    bool any = false;
+    for (int i = 0; i < THMR_LOSS_GRAD_SLOTS; ++i) any = any || grads_host[i];
+    if (!any) return fail(THMR_ERR_INVALID, "val_loss_grad: every slot of the gradient table is null");
+    if (!pred_cam && (grads_host[THMR_LOSS_GRAD_JOINTS] || grads_host[THMR_LOSS_GRAD_CAM]))
+        return fail(THMR_ERR_INVALID, "val_loss_grad: the JOINTS and CAM slots need pred_cam (the projection's adjoint)");
+    if (pred_cam && !(std::isfinite(focal_length) && focal_length > 0.0 && std::isfinite(image_size) && image_size > 0.0))
+        return fail(THMR_ERR_INVALID, "val_loss_grad: focal_length and image_size must be finite and positive when pred_cam is given");
+    ValLossGradArgs g{};
+    val_loss_inputs(g.in, d, in, B);
+    g.pred_cam = pred_cam;
+    g.g_kp2d = grads_host[THMR_LOSS_GRAD_KP2D]; g.g_kp3d = grads_host[THMR_LOSS_GRAD_KP3D]; g.g_joints = grads_host[THMR_LOSS_GRAD_JOINTS];
+    g.g_cam = grads_host[THMR_LOSS_GRAD_CAM]; g.g_rotmat = grads_host[THMR_LOSS_GRAD_ROTMAT]; g.g_betas = grads_host[THMR_LOSS_GRAD_BETAS];
+    g.focal_length = (float)focal_length; g.img_size = (float)image_size;
+    LAUNCH_OK(launch_val_loss_grad(g, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

@@ -6,8 +6,12 @@ as validation_step (:421-440) runs it, and TokenLoss (losses.py:230-252).
     means = vloss.get_metrics_dict()                   # the one synchronisation: the mean of every term over the batches so far
 
 One call enqueues the two launches of `thmr_val_loss` (plus one concatenation of the ground-truth pose) and leaves every result on the
-device.  The loss is the number the reference selects checkpoints by (best_validation_loss, :101); its backward pass, the optimisers and
-the discriminator terms are not built.
+device.  The loss is the number the reference selects checkpoints by (best_validation_loss, :101).  Its gradient is built as far as the
+head's outputs:
+
+    losses, grads = vloss.value_and_grad(batch, output, body_model=smpl_model)      # d loss / d (global_orient, body_pose, betas, pred_cam)
+
+There is no backward above the head; the optimisers and the discriminator terms are not built.
 
 Deliberate departure: the reference's LOOSE_SUP branch writes into the batch (keypoints_2d[:, :, -1], keypoints_3d[:, :, -1],
 has_smpl_params['betas']; :223, :227, :240).  Nothing in `batch` is modified here; what the reference would have written is returned in
@@ -72,6 +76,7 @@ class ValidationLoss:
         self.pelvis_id = int(pelvis_id)
         self.strict_flags = bool(strict_flags)
         self._dev = {}                      # device -> (kp2d_thresh, angle_thresh, running, workspace)
+        self._grad = {}                     # (device, B) -> the buffers of value_and_grad
 
     # ---- argument handling: everything up to the launch, on whatever device the tensors live ----
     def prepare(self, batch, output, train=False):
@@ -130,22 +135,84 @@ class ValidationLoss:
             st["ws"] = torch.empty(5 * max(B, 64), device=dev, dtype=torch.float32)
         return st
 
-    def __call__(self, batch, output, train=False):
-        a = self.prepare(batch, output, train)
-        loose = a.pop("loose")
-        dev = a["pred_kp2d"].device
-        st = self._device_state(dev, a["pred_kp2d"].shape[0])
+    def _value(self, a, loose, output, running, losses=None, out=None):
+        """The thmr_val_loss call of prepare()'s arguments; sets output['losses'], 'loss_per_item' and (loose) 'loss_masks'."""
+        st = self._device_state(a["pred_kp2d"].device, a["pred_kp2d"].shape[0])
         res = ops.val_loss(a["pred_kp2d"], a["pred_kp3d"], a["pred_rotmat"], a["pred_betas"], a["gt_kp2d"], a["gt_kp3d"], a["gt_pose"],
                            a["gt_betas"], a["has_global_orient"], a["has_body_pose"], a["has_betas"], self.weights, loose=loose,
                            loose_weight=self.loose_weight, valid_3d=a["valid_3d"], kp2d_thresh=st["kp2d"] if loose else None,
-                           angle_thresh=st["angle"] if loose else None, pelvis_id=self.pelvis_id, taps=True, running=st["running"],
-                           workspace=st["ws"])
-        losses = res.pop("losses")                                      # a fresh buffer per call: earlier batches' values stay valid
+                           angle_thresh=st["angle"] if loose else None, pelvis_id=self.pelvis_id, taps=True,
+                           running=st["running"] if running else None, workspace=st["ws"], losses=losses, out=out)
+        losses = res.pop("losses")
         output["losses"] = {k: losses[i] for i, k in enumerate(LOSS_KEYS)}       # tokenhmr.py:268-275
         output["loss_per_item"] = res.pop("per_item")
         if loose:
             output["loss_masks"] = res
-        return output["losses"]["loss"]
+        return output["losses"]
+
+    def __call__(self, batch, output, train=False):
+        a = self.prepare(batch, output, train)
+        loose = a.pop("loose")
+        return self._value(a, loose, output, running=True)["loss"]      # a fresh buffer per call: earlier batches' values stay valid
+
+    # ---- value and gradient (DESIGN.md 8 N14) ----
+    def _grad_buffers(self, dev, B, loose):
+        """The buffers of one (device, batch size): the value's outputs, the six slots, the body model's gradients and the two sums."""
+        f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)      # noqa: E731
+        b = self._grad.get((dev, B))
+        if b is None:
+            b = self._grad[(dev, B)] = dict(losses=f(6), value={"per_item": f(B, 5)}, kp2d=f(B, 44, 2), kp3d=f(B, 44, 3), joints=f(B, 44, 3),
+                                            cam=f(B, 3), rotmat=f(B, 24, 3, 3), betas=f(B, 10), bm_rotmat=f(B, 24, 3, 3), bm_betas=f(B, 10),
+                                            total_rotmat=f(B, 24, 3, 3), total_betas=f(B, 10))
+        if loose and "valid2d" not in b["value"]:          # the loose branch's taps, on its first call at this size
+            b["value"].update({k: f(B) if k == "has_betas_used" else f(B, 44 if "2d" in k or "3d" in k else 24) for k in ops.VAL_LOSS_TAPS})
+        return b
+
+    def value_and_grad(self, batch, output, body_model=None, train=False, focal_length=5000.0, image_size=256.0):
+        """-> (losses, grads).  `losses` is what __call__ sets as output['losses'], from the same thmr_val_loss call on the same arguments
+        (bit-equal to it); the running means of get_metrics_dict() count __call__ only.  The total is a SUM over the items, as the
+        reference's: nothing is divided by the batch size.
+        Without body_model, grads holds the plain partial derivatives by the five tensors compute_loss reads: 'pred_keypoints_2d'
+        (B,44,2), 'pred_keypoints_3d' (B,44,3), 'global_orient' (B,1,3,3), 'body_pose' (B,23,3,3), 'betas' (B,10).
+        With a tokenhmr_amd.smpl.SMPL and output['pred_cam'], grads holds the total derivative by the head's outputs, through the projection
+        (focal_length = EXTRA.FOCAL_LENGTH, image_size = MODEL.IMAGE_SIZE) and the body model: 'global_orient', 'body_pose', 'betas' and
+        'pred_cam' (B,3).  The chain: thmr_val_loss_grad, thmr_smpl_backward on its JOINTS slot in chunks of body_model.max_batch, one
+        torch.add per summed tensor; on the current stream, without synchronisation, and after the first call at a batch size without
+        allocations beyond prepare()'s own copies (capturable once body_model.enable_grad() has run; prepare() uploads valid_3d from
+        the host in the loose branch, which a capture refuses).  The returned tensors are buffers of this object, overwritten by the
+        next call at that batch size on that device."""
+        a = self.prepare(batch, output, train)
+        loose = a.pop("loose")
+        dev, B = a["pred_kp2d"].device, a["pred_kp2d"].shape[0]
+        b = self._grad_buffers(dev, B, loose)
+        losses = self._value(a, loose, output, running=False, losses=b["losses"], out=b["value"])
+        st = self._device_state(dev, B)
+        cam = None
+        if body_model is not None:
+            if output.get("pred_cam") is None:
+                raise ValueError("value_and_grad with a body model differentiates through the projection: output['pred_cam'] is needed")
+            if body_model.device != dev:
+                raise ValueError(f"the body model lives on {body_model.device}, the loss's inputs on {dev}")
+            cam = output["pred_cam"].detach().to(dev).float().reshape(B, 3).contiguous()
+            body_model.enable_grad()
+        want = ("joints", "cam", "rotmat", "betas") if body_model is not None else ("kp2d", "kp3d", "rotmat", "betas")
+        ops.val_loss_grad(a["pred_kp2d"], a["pred_kp3d"], a["pred_rotmat"], a["pred_betas"], a["gt_kp2d"], a["gt_kp3d"], a["gt_pose"],
+                          a["gt_betas"], a["has_global_orient"], a["has_body_pose"], a["has_betas"], self.weights, loose=loose,
+                          loose_weight=self.loose_weight, valid_3d=a["valid_3d"], kp2d_thresh=st["kp2d"] if loose else None,
+                          angle_thresh=st["angle"] if loose else None, pelvis_id=self.pelvis_id, pred_cam=cam, focal_length=focal_length,
+                          image_size=image_size, want=want, out=b)
+        if body_model is None:
+            return losses, {"pred_keypoints_2d": b["kp2d"], "pred_keypoints_3d": b["kp3d"], "global_orient": b["rotmat"][:, :1],
+                            "body_pose": b["rotmat"][:, 1:], "betas": b["betas"]}
+        with torch.no_grad():
+            for i in range(0, B, body_model.max_batch):
+                n = min(body_model.max_batch, B - i)
+                body_model._backward(a["pred_rotmat"][i:i + n], False, a["pred_betas"][i:i + n], n, None, b["joints"][i:i + n],
+                                     b["bm_rotmat"][i:i + n], b["bm_betas"][i:i + n])
+            torch.add(b["bm_rotmat"], b["rotmat"], out=b["total_rotmat"])
+            torch.add(b["bm_betas"], b["betas"], out=b["total_betas"])
+        return losses, {"global_orient": b["total_rotmat"][:, :1], "body_pose": b["total_rotmat"][:, 1:], "betas": b["total_betas"],
+                        "pred_cam": b["cam"]}
 
     def reset(self):
         for st in self._dev.values():

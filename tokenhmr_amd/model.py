@@ -35,6 +35,8 @@ class TokenHMR:
         self.training = False
         self.return_taps = False
         self.validation_loss = None      # built by compute_loss on first use
+        self.body_model = None           # a tokenhmr_amd.smpl.SMPL, built by loss_value_and_grad / head_loss on first use
+        self._smpl_constants = None
 
     # ---- construction -------------------------------------------------------------------
     @classmethod
@@ -47,6 +49,7 @@ class TokenHMR:
         m.engine.load_smpl(smpl)
         m.engine.finalize()
         m.smpl = _SmplHandle(smpl["faces"])
+        m._smpl_constants = smpl         # what the differentiable body model is built from, if it is ever asked for
         return m
 
     @classmethod
@@ -58,6 +61,7 @@ class TokenHMR:
         m.max_batch, m.device, m.engine = engine.max_batch, engine.device, engine
         m.smpl = _SmplHandle(faces if faces is not None else torch.zeros(13776, 3, dtype=torch.int64))
         m.training, m.return_taps, m.validation_loss = False, False, None
+        m.body_model, m._smpl_constants = None, None
         return m
 
     # ---- nn.Module-like surface used by eval.py:52-54 / demo.py:35-37 ------------------------
@@ -101,9 +105,7 @@ class TokenHMR:
             raise NotImplementedError("inference only")
         return self.forward(batch)
 
-    def compute_loss(self, batch, output, train=False):
-        """tokenhmr.py:190-277, the forward value only (tokenhmr_amd/losses.py): sets output['losses'], returns the total as a 0-dim
-        device tensor.  The ValidationLoss is built from self.cfg on first use; replace `model.validation_loss` to pass thresholds."""
+    def _loss_module(self):
         if self.validation_loss is None:
             from .losses import ValidationLoss
             try:
@@ -111,7 +113,62 @@ class TokenHMR:
             except KeyError as e:
                 raise KeyError(f"compute_loss reads LOSS_WEIGHTS and MODEL from the reference's model config, and {e.args[0]}: pass "
                                "`model_cfg` when the model is built (load_tokenhmr does), or set model.validation_loss") from None
-        return self.validation_loss(batch, output, train=train)
+        return self.validation_loss
+
+    def compute_loss(self, batch, output, train=False):
+        """tokenhmr.py:190-277, the forward value only (tokenhmr_amd/losses.py): sets output['losses'], returns the total as a 0-dim
+        device tensor.  The ValidationLoss is built from self.cfg on first use; replace `model.validation_loss` to pass thresholds."""
+        return self._loss_module()(batch, output, train=train)
+
+    # ---- value and gradient of compute_loss down to the head's outputs (DESIGN.md 8 N14) ----
+    def _projection(self):
+        """(EXTRA.FOCAL_LENGTH, MODEL.IMAGE_SIZE) of self.cfg; the engine's own values where the config carries neither node."""
+        from .losses import _node
+        try:
+            return float(_node(_node(self.cfg, "EXTRA"), "FOCAL_LENGTH")), float(_node(_node(self.cfg, "MODEL"), "IMAGE_SIZE"))
+        except KeyError:
+            return float(self.hmr_cfg.focal_length), float(self.hmr_cfg.img_size)
+
+    def _grad_body_model(self, body_model=None):
+        if body_model is not None:
+            return body_model
+        if self.body_model is None:
+            if self._smpl_constants is None:
+                raise ValueError("this model was built around an engine and holds no SMPL constants to build the differentiable body model "
+                                 "from: pass body_model= (a tokenhmr_amd.smpl.SMPL on the engine's device)")
+            from .smpl import SMPL
+            self.body_model = SMPL(self._smpl_constants, max_batch=self.max_batch, device=self.device).enable_grad()
+        return self.body_model
+
+    def loss_value_and_grad(self, batch, output, train=False, body_model=None):
+        """compute_loss and its gradient by the head's outputs -> (losses, grads): `losses` as compute_loss sets output['losses'], `grads`
+        with 'global_orient' (B,1,3,3), 'body_pose' (B,23,3,3), 'betas' (B,10) and 'pred_cam' (B,3) — the total derivative of the summed
+        loss through the projection and the body model (ValidationLoss.value_and_grad; buffers, overwritten by the next call at that
+        batch size).  `output` is what forward() returned.  There is no backward past the head: the ViT, the decoder and the tokenizer
+        stay inference only.  The body model is built from the SMPL constants on first use."""
+        F, S = self._projection()
+        return self._loss_module().value_and_grad(batch, output, body_model=self._grad_body_model(body_model), train=train, focal_length=F,
+                                                  image_size=S)
+
+    def _head_output(self, pred_smpl_params, pred_cam):
+        """The engine's own tail on a head's outputs: Engine.lbs_forward -> the part of forward()'s dict that compute_loss reads."""
+        go, bp, betas = (pred_smpl_params[k].detach().to(self.device, torch.float32) for k in ("global_orient", "body_pose", "betas"))
+        B = betas.shape[0]
+        R = torch.cat([go.reshape(B, 1, 3, 3), bp.reshape(B, 23, 3, 3)], 1)
+        cam = pred_cam.detach().to(self.device, torch.float32).reshape(B, 3)
+        _, joints, cam_t, kp2d = self.engine.lbs_forward(R, betas.reshape(B, 10), cam)
+        return {"pred_cam": cam, "pred_cam_t": cam_t, "pred_smpl_params": {"global_orient": R[:, :1], "body_pose": R[:, 1:], "betas": betas},
+                "pred_keypoints_3d": joints, "pred_keypoints_2d": kp2d}
+
+    def head_loss(self, batch, pred_smpl_params, pred_cam, train=False, body_model=None):
+        """compute_loss of a head's outputs under torch autograd: pred_smpl_params {'global_orient' (B,1,3,3), 'body_pose' (B,23,3,3),
+        'betas' (B,10)} and pred_cam (B,3) -> the 0-dim total.  Forward: Engine.lbs_forward and thmr_val_loss, the engine's own tail and
+        the existing value.  When grad is enabled and an input requires it, the total carries a graph whose backward is
+        loss_value_and_grad's chain (once differentiable; an input that needs no gradient gets None).  Otherwise the plain path."""
+        ins = (pred_smpl_params["global_orient"], pred_smpl_params["body_pose"], pred_smpl_params["betas"], pred_cam)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in ins):
+            return _HeadLossFn.apply(self, batch, bool(train), self._grad_body_model(body_model), *ins)
+        return self.compute_loss(batch, self._head_output(pred_smpl_params, pred_cam), train=train)
 
     def validation_step(self, batch, batch_idx=0, dataloader_idx=0):
         """tokenhmr.py:421-440 without the logging: forward + compute_loss, output['loss'] = the total."""
@@ -151,6 +208,31 @@ class TokenHMR:
             if k in o:
                 out[k] = o[k]
         return out
+
+
+class _HeadLossFn(torch.autograd.Function):
+    """TokenHMR.head_loss with a graph: the value and the four gradients come out of one loss_value_and_grad call in forward()."""
+
+    @staticmethod
+    def forward(ctx, model, batch, train, body_model, go, bp, betas, cam):
+        ctx.set_materialize_grads(False)
+        out = model._head_output({"global_orient": go, "body_pose": bp, "betas": betas}, cam)
+        losses, grads = model.loss_value_and_grad(batch, out, train=train, body_model=body_model)
+        # the gradients are buffers of the loss module: this graph keeps copies of those it will hand out
+        keep = [grads[k].reshape(t.shape).clone() if need else None
+                for k, t, need in zip(("global_orient", "body_pose", "betas", "pred_cam"), (go, bp, betas, cam), ctx.needs_input_grad[4:])]
+        ctx.which = [g is not None for g in keep]
+        ctx.save_for_backward(*[g for g in keep if g is not None])
+        return losses["loss"].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_total):
+        saved = iter(ctx.saved_tensors)
+        grads = [next(saved) if have else None for have in ctx.which]
+        if g_total is None:
+            return (None,) * 8
+        return (None, None, None, None) + tuple(None if g is None else g * g_total for g in grads)
 
 
 def _cat_outputs(outs):

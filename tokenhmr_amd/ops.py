@@ -595,56 +595,123 @@ def rotmat_to_aa(R):
 VAL_LOSS_TAPS = ("kp2d_err", "angle_err", "valid2d", "weak2d", "valid_rot", "weak_rot", "conf2d_used", "conf3d_used", "has_betas_used")
 
 
-def val_loss(pred_kp2d, pred_kp3d, pred_rotmat, pred_betas, gt_kp2d, gt_kp3d, gt_pose, gt_betas, has_global_orient, has_body_pose,
-             has_betas, weights, loose=False, loose_weight=0.0, valid_3d=None, kp2d_thresh=None, angle_thresh=None, pelvis_id=39,
-             taps=True, running=None, workspace=None, losses=None):
-    """thmr_val_loss: compute_loss (tokenhmr.py:190-277) for B items.  pred_kp2d (B,44,2), pred_kp3d (B,44,3), pred_rotmat (B,24,3,3),
-    pred_betas (B,10), gt_kp2d (B,44,3), gt_kp3d (B,44,4), gt_pose (B,72) axis-angle or (B,24,3,3) matrices, gt_betas (B,10), has_* (B);
-    weights: the five LOSS_WEIGHTS in the order 2D, 3D, global_orient, body_pose, betas.  loose: valid_3d (B), kp2d_thresh (44),
-    angle_thresh (24).  Returns a dict of device tensors: 'losses' (6, the reference's dict order), 'per_item' (B,5) and — loose with
-    taps — VAL_LOSS_TAPS.  running: a (7) float64 device tensor that the call adds its six losses and a count of 1 to.  No host
-    synchronisation; nothing is written into an input."""
-    ins = [pred_kp2d, pred_kp3d, pred_rotmat, pred_betas, gt_kp2d, gt_kp3d, gt_pose, gt_betas, has_global_orient, has_body_pose, has_betas]
-    _req(*ins, valid_3d, kp2d_thresh, angle_thresh, workspace, losses)
-    B = pred_kp2d.shape[0]
+def _val_loss_inputs(who, ins, loose, valid_3d, kp2d_thresh, angle_thresh, weights):
+    """The checks val_loss and val_loss_grad share, on the eleven inputs in the order of thmr_val_loss_in -> (B, gt_pose_is_rotmat)."""
+    _req(*ins, valid_3d, kp2d_thresh, angle_thresh)
+    B, gt_pose = ins[0].shape[0], ins[6]
     if gt_pose.shape == (B, 72):
         is_rotmat = 0
     elif gt_pose.shape == (B, 24, 3, 3):
         is_rotmat = 1
     else:
-        raise ValueError(f"val_loss: gt_pose is (B,72) axis-angle or (B,24,3,3) matrices, got {tuple(gt_pose.shape)}")
+        raise ValueError(f"{who}: gt_pose is (B,72) axis-angle or (B,24,3,3) matrices, got {tuple(gt_pose.shape)}")
     want = [(B, 44, 2), (B, 44, 3), (B, 24, 3, 3), (B, 10), (B, 44, 3), (B, 44, 4), tuple(gt_pose.shape), (B, 10), (B,), (B,), (B,)]
     for t, w in zip(ins, want):
         if tuple(t.shape) != w:
-            raise ValueError(f"val_loss: a tensor of shape {tuple(t.shape)} where {w} is expected")
+            raise ValueError(f"{who}: a tensor of shape {tuple(t.shape)} where {w} is expected")
     if loose:
         if valid_3d is None or kp2d_thresh is None or angle_thresh is None:
-            raise ValueError("val_loss: the loose mode needs valid_3d, kp2d_thresh and angle_thresh")
+            raise ValueError(f"{who}: the loose mode needs valid_3d, kp2d_thresh and angle_thresh")
         if tuple(valid_3d.shape) != (B,) or tuple(kp2d_thresh.shape) != (44,) or tuple(angle_thresh.shape) != (24,):
-            raise ValueError("val_loss: valid_3d (B), kp2d_thresh (44), angle_thresh (24)")
+            raise ValueError(f"{who}: valid_3d (B), kp2d_thresh (44), angle_thresh (24)")
+    if len(weights) != 5:
+        raise ValueError(f"{who}: five weights (2D, 3D, global_orient, body_pose, betas)")
+    return B, is_rotmat
+
+
+def _val_loss_structs(ins, weights, loose, loose_weight, valid_3d, kp2d_thresh, angle_thresh, pelvis_id, is_rotmat):
+    """(thmr_val_loss_desc, thmr_val_loss_in) of checked inputs."""
+    w = [float(x) for x in weights]
+    desc = _cabi.ValLossDesc(*w, float(loose_weight), int(pelvis_id), _cabi.VAL_LOSS_LOOSE if loose else _cabi.VAL_LOSS_PLAIN, is_rotmat, 0)
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    return desc, _cabi.ValLossIn(*[ptr(t) for t in ins], ptr(valid_3d), ptr(kp2d_thresh), ptr(angle_thresh))
+
+
+def val_loss(pred_kp2d, pred_kp3d, pred_rotmat, pred_betas, gt_kp2d, gt_kp3d, gt_pose, gt_betas, has_global_orient, has_body_pose,
+             has_betas, weights, loose=False, loose_weight=0.0, valid_3d=None, kp2d_thresh=None, angle_thresh=None, pelvis_id=39,
+             taps=True, running=None, workspace=None, losses=None, out=None):
+    """thmr_val_loss: compute_loss (tokenhmr.py:190-277) for B items.  pred_kp2d (B,44,2), pred_kp3d (B,44,3), pred_rotmat (B,24,3,3),
+    pred_betas (B,10), gt_kp2d (B,44,3), gt_kp3d (B,44,4), gt_pose (B,72) axis-angle or (B,24,3,3) matrices, gt_betas (B,10), has_* (B);
+    weights: the five LOSS_WEIGHTS in the order 2D, 3D, global_orient, body_pose, betas.  loose: valid_3d (B), kp2d_thresh (44),
+    angle_thresh (24).  Returns a dict of device tensors: 'losses' (6, the reference's dict order), 'per_item' (B,5) and — loose with
+    taps — VAL_LOSS_TAPS.  running: a (7) float64 device tensor that the call adds its six losses and a count of 1 to.  out: a dict of preallocated
+    tensors for 'per_item' and the taps (a caller that must not allocate); what it lacks is allocated.  No host synchronisation; nothing
+    is written into an input."""
+    ins = [pred_kp2d, pred_kp3d, pred_rotmat, pred_betas, gt_kp2d, gt_kp3d, gt_pose, gt_betas, has_global_orient, has_body_pose, has_betas]
+    _req(workspace, losses)
+    B, is_rotmat = _val_loss_inputs("val_loss", ins, loose, valid_3d, kp2d_thresh, angle_thresh, weights)
     if running is not None and not (running.is_cuda and running.dtype == torch.float64 and running.shape == (7,) and running.is_contiguous()):
         raise ValueError("val_loss: running is a contiguous (7) float64 CUDA tensor")
-    if len(weights) != 5:
-        raise ValueError("val_loss: five weights (2D, 3D, global_orient, body_pose, betas)")
     dev = pred_kp2d.device
     new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)      # noqa: E731
-    res = {"losses": losses if losses is not None else new(6), "per_item": new(B, 5)}
+
+    def pick(k, *shape):
+        t = out.get(k) if out is not None else None
+        if t is None:
+            return new(*shape)
+        _req(t)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"val_loss: out['{k}'] is {shape}, got {tuple(t.shape)}")
+        return t
+
+    res = {"losses": losses if losses is not None else new(6), "per_item": pick("per_item", B, 5)}
     if res["losses"].shape != (6,):
         raise ValueError("val_loss: losses is a (6) tensor")
     if loose and taps:
-        res.update({k: new(B) if k == "has_betas_used" else new(B, 44 if "2d" in k or "3d" in k else 24) for k in VAL_LOSS_TAPS})
+        res.update({k: pick(k, B) if k == "has_betas_used" else pick(k, B, 44 if "2d" in k or "3d" in k else 24) for k in VAL_LOSS_TAPS})
     need = _cabi.VAL_LOSS_WS_PER_ITEM * B
     if workspace is None:
         workspace = new(need)
     elif workspace.numel() < need:
         raise ValueError(f"val_loss: the workspace holds {workspace.numel()} floats, {need} are needed")
-    w = [float(x) for x in weights]
-    desc = _cabi.ValLossDesc(*w, float(loose_weight), int(pelvis_id), _cabi.VAL_LOSS_LOOSE if loose else _cabi.VAL_LOSS_PLAIN, is_rotmat, 0)
+    desc, cin = _val_loss_structs(ins, weights, loose, loose_weight, valid_3d, kp2d_thresh, angle_thresh, pelvis_id, is_rotmat)
     ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-    cin = _cabi.ValLossIn(*[ptr(t) for t in ins], ptr(valid_3d), ptr(kp2d_thresh), ptr(angle_thresh))
     cout = _cabi.ValLossOut(**{k: ptr(res.get(k)) for k in _cabi.VAL_LOSS_OUT_FIELDS if k != "running"}, running=ptr(running))
     with torch.cuda.device(dev):
         _check(_L().thmr_val_loss(C.byref(desc), C.byref(cin), B, C.byref(cout), _p(workspace), _s(pred_kp2d)))
+    return res
+
+
+# ---- its gradient (csrc/loss.hip) ----
+LOSS_GRAD_SLOTS = ("kp2d", "kp3d", "joints", "cam", "rotmat", "betas")          # header: THMR_LOSS_GRAD_*, in slot order
+
+
+def val_loss_grad(pred_kp2d, pred_kp3d, pred_rotmat, pred_betas, gt_kp2d, gt_kp3d, gt_pose, gt_betas, has_global_orient, has_body_pose,
+                  has_betas, weights, loose=False, loose_weight=0.0, valid_3d=None, kp2d_thresh=None, angle_thresh=None, pelvis_id=39,
+                  pred_cam=None, focal_length=5000.0, image_size=256.0, want=None, out=None):
+    """thmr_val_loss_grad: the gradient of val_loss's total (a sum over the B items) — inputs, weights and mode as val_loss takes them.
+    Returns a dict of device tensors keyed by LOSS_GRAD_SLOTS: 'kp2d' (B,44,2), 'kp3d' (B,44,3), 'rotmat' (B,24,3,3), 'betas' (B,10) — the
+    plain partial derivatives by the four predictions — and, with pred_cam (B,3), 'joints' (B,44,3) = 'kp3d' + the projection's adjoint
+    of 'kp2d' (what the body model's backward takes) and 'cam' (B,3).  want: the slots to compute (default: every slot the arguments
+    allow); out: a dict of preallocated tensors to write into.  One launch, no host synchronisation."""
+    ins = [pred_kp2d, pred_kp3d, pred_rotmat, pred_betas, gt_kp2d, gt_kp3d, gt_pose, gt_betas, has_global_orient, has_body_pose, has_betas]
+    B, is_rotmat = _val_loss_inputs("val_loss_grad", ins, loose, valid_3d, kp2d_thresh, angle_thresh, weights)
+    _req(pred_cam)
+    if pred_cam is not None and tuple(pred_cam.shape) != (B, 3):
+        raise ValueError(f"val_loss_grad: pred_cam is (B,3), got {tuple(pred_cam.shape)}")
+    if want is None:
+        want = [k for k in LOSS_GRAD_SLOTS if pred_cam is not None or k not in ("joints", "cam")]
+    unknown = [k for k in want if k not in LOSS_GRAD_SLOTS]
+    if unknown or not want:
+        raise ValueError(f"val_loss_grad: want names slots of {LOSS_GRAD_SLOTS}, at least one; got {list(want)}")
+    if pred_cam is None and ("joints" in want or "cam" in want):
+        raise ValueError("val_loss_grad: 'joints' and 'cam' need pred_cam")
+    shapes = {"kp2d": (B, 44, 2), "kp3d": (B, 44, 3), "joints": (B, 44, 3), "cam": (B, 3), "rotmat": (B, 24, 3, 3), "betas": (B, 10)}
+    dev = pred_kp2d.device
+    res = {}
+    for k in want:
+        t = out.get(k) if out is not None else None
+        if t is None:
+            t = torch.empty(shapes[k], device=dev, dtype=torch.float32)
+        _req(t)
+        if tuple(t.shape) != shapes[k]:
+            raise ValueError(f"val_loss_grad: out['{k}'] is {shapes[k]}, got {tuple(t.shape)}")
+        res[k] = t
+    desc, cin = _val_loss_structs(ins, weights, loose, loose_weight, valid_3d, kp2d_thresh, angle_thresh, pelvis_id, is_rotmat)
+    table = (C.c_void_p * _cabi.LOSS_GRAD_SLOTS)(*[res[k].data_ptr() if k in res else None for k in LOSS_GRAD_SLOTS])
+    with torch.cuda.device(dev):
+        _check(_L().thmr_val_loss_grad(C.byref(desc), C.byref(cin), _p(pred_cam), float(focal_length), float(image_size), B, table,
+                                       _s(pred_kp2d)))
     return res
 
 

@@ -38,10 +38,7 @@ class _SmplFn(torch.autograd.Function):
         g_verts, g_joints = (None if g is None else g.to(m.device, torch.float32).contiguous() for g in (g_verts, g_joints))
         g_pose = torch.empty_like(pose) if ctx.needs_input_grad[1] else None
         g_betas = torch.empty_like(betas) if ctx.needs_input_grad[2] else None
-        with torch.cuda.device(m.device):
-            st = C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream)
-            m._check(m.lib.thmr_smpl_backward(m.h, _p(pose), 1 if ctx.pose2rot else 0, _p(betas), B, _p(g_verts), _p(g_joints), _p(g_pose),
-                                              _p(g_betas), st), "thmr_smpl_backward")
+        m._backward(pose, ctx.pose2rot, betas, B, g_verts, g_joints, g_pose, g_betas)
         return None, g_pose, g_betas, None
 
 
@@ -98,5 +95,13 @@ class SMPL(_cabi.Handle):
             self._check(self.lib.thmr_smpl_forward(self.h, _p(pose), 1 if pose2rot else 0, _p(betas), B, _p(verts), _p(joints), st),
                         "thmr_smpl_forward")
         return verts, joints
+
+    def _backward(self, pose, pose2rot, betas, B, g_verts, g_joints, g_pose, g_betas):
+        """One thmr_smpl_backward call on the current stream (B <= max_batch, contiguous float32 tensors of this device, enable_grad()
+        done): a None gradient input is zeros, a None output is not computed."""
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._check(self.lib.thmr_smpl_backward(self.h, _p(pose), 1 if pose2rot else 0, _p(betas), B, _p(g_verts), _p(g_joints),
+                                                    _p(g_pose), _p(g_betas), st), "thmr_smpl_backward")
 
     __call__ = forward
