@@ -685,6 +685,58 @@ int thmr_val_loss_grad(const thmr_val_loss_desc* desc, const thmr_val_loss_in* i
  * Refused before any HIP call: a null buffer, rows < 1, x_dev not 16-byte aligned. */
 #define THMR_TOKEN_CE_WS_PER_ROW 1
 int thmr_op_token_ce(const float* x_dev, const int32_t* target_dev, int32_t rows, float* out_dev, float* workspace_dev, void* stream);
+/* The HMR pose and shape discriminator and the adversarial terms built on it (csrc/discriminator.hip): Discriminator
+ * (tokenhmr/lib/models/discriminator.py:4-99) as tokenhmr.py uses it — loss_adv (:392-394), loss_fake and loss_real (:357-362).  fp32
+ * throughout, but for the shape branch (165 multiply-adds per item, accumulated in fp64: column 23 is one short, badly conditioned chain
+ * per item, which the loss's gradient multiplies by out - target).  New symbols under ABI 5: no struct or signature changed.  STATELESS: no handle; the weights are one device block of
+ * THMR_DISC_WEIGHT_FLOATS floats that the caller holds, 16-byte aligned, in a layout of this library's own (the transposed copies the
+ * backward streams are made once, when the block is written; nothing here updates a weight).  The block: these tensors in this order,
+ * each starting at a multiple of 64 floats —
+ *   D_conv1.weight^T (9,32) | D_conv1.bias (32) | D_conv2.weight^T (32,32) | D_conv2.weight (32,32) | D_conv2.bias (32) |
+ *   D_conv1.weight (32,9) | pose_out.j.weight as row j (23,32) | pose_out.j.bias (23) | betas_fc1.weight (10,10) | .bias (10) |
+ *   betas_fc2.weight (5,10) | .bias (5) | betas_out.weight (5) | .bias (1) |
+ *   fc1 (1024, THMR_DISC_KPAD): D_alljoints_fc1.weight with column j * 32 + c holding the reference's column c * 23 + j (it flattens
+ *       channel-major, :91) and columns 736 .. 767 zero | D_alljoints_fc1.bias (1024) | the first 736 columns of fc1 transposed (736,1024) |
+ *   D_alljoints_fc2.weight (1024,1024) | .bias (1024) | its transpose (1024,1024) | D_alljoints_out.weight (1024) | .bias (1).
+ * poses_dev: (B,23,3,3) with pose_stride floats between items (>= 207; 216 for the body_pose view of a (B,24,3,3) buffer, which needs no
+ * copy); read as scalars, 4-byte alignment suffices.  betas_dev: (B,10).  out (B,25): columns 0..22 the per-joint heads (:77-81), 23 the
+ * shape branch (:84-88), 24 the all-joints branch (:91-96).
+ * The loss is L(target) = sum_{b,c} (out[b][c] - target)^2 / loss_div: loss_div = the batch size the loss is a mean over (:358,393), 0 = B
+ * (a caller that splits a batch over several calls passes the whole batch's size and adds the calls' values).
+ * bufs_host: a table in HOST memory of THMR_DISC_SLOTS device pointers, indexed by THMR_DISC_*:
+ *   OUT         (B,25)        forward: required; backward: optional
+ *   LOSS        one float     optional: L(target), summed in fp64 in a fixed order
+ *   GRAD_POSES  (B,23,3,3)    backward only: d/d poses, contiguous, written in full
+ *   GRAD_BETAS  (B,10)        backward only: d/d betas; either gradient may be NULL and is then not computed, not both
+ *   WORKSPACE   THMR_DISC_WS_PER_ITEM x B floats, 16-byte aligned, required; every word that is read was written earlier in the same
+ *               call, so it needs no initialisation (the zero columns of fc1's padded operand included)
+ * thmr_disc_forward: four launches on `stream`, five with LOSS: the per-joint front, shape branch and heads (one workgroup per item);
+ * two skinny GEMMs with bias + ReLU that stream the wide weights once (K = 736 is padded to THMR_DISC_KPAD); the read-out (one wave per
+ * item); the loss sum.
+ * thmr_disc_backward: the gradient of sum(out * grad_out) with grad_out_or_null (B,25) given, else of L(target), by the INPUTS (there
+ * is no gradient by the weights).  It keeps no activations between calls: it runs the forward again into the workspace — so it needs no
+ * preceding forward, and OUT / LOSS of the same call are that forward's, bit-equal to thmr_disc_forward's — then two skinny GEMMs on the
+ * transposed weights (the first with the ReLU mask as its epilogue) and the front's backward: eight launches, nine with LOSS.  ReLU's
+ * derivative is torch's, zero at z <= 0.  Without GRAD_POSES the wide layers are only run when OUT or LOSS is asked for.
+ * Both: no float atomics, no allocation, no host synchronisation; two runs are bit-equal and a captured call replays like the eager one.
+ * Refused before any HIP call (THMR_ERR_INVALID, message in thmr_last_error(NULL)): a null weights_dev, poses_dev, betas_dev or table; a
+ * null WORKSPACE; forward without OUT; backward with GRAD_POSES and GRAD_BETAS both NULL; B outside [1, THMR_DISC_MAX_BATCH]; loss_div < 0;
+ * pose_stride < 207; weights_dev or WORKSPACE not 16-byte aligned (their rows are read as float4); a target that is not finite where it
+ * is read (LOSS given, or backward without grad_out_or_null). */
+#define THMR_DISC_OUT 0
+#define THMR_DISC_LOSS 1
+#define THMR_DISC_GRAD_POSES 2
+#define THMR_DISC_GRAD_BETAS 3
+#define THMR_DISC_WORKSPACE 4
+#define THMR_DISC_SLOTS 5
+#define THMR_DISC_MAX_BATCH 256
+#define THMR_DISC_KPAD 768
+#define THMR_DISC_WEIGHT_FLOATS 3644480
+#define THMR_DISC_WS_PER_ITEM 5665
+int thmr_disc_forward(const float* weights_dev, const float* poses_dev, int64_t pose_stride, const float* betas_dev, int32_t B,
+                      int32_t loss_div, double target, float** bufs_host, void* stream);
+int thmr_disc_backward(const float* weights_dev, const float* poses_dev, int64_t pose_stride, const float* betas_dev,
+                       const float* grad_out_or_null, int32_t B, int32_t loss_div, double target, float** bufs_host, void* stream);
 
 /* Evaluation metrics right after the hot path — stateless, all buffers device-side.
  * Replaces compute_similarity_transform / eval_pose and the arithmetic of Evaluator.__call__

@@ -55,6 +55,9 @@ VAL_LOSS_PLAIN, VAL_LOSS_LOOSE = 0, 1
 VAL_LOSS_WS_PER_ITEM, TOKEN_CE_WS_PER_ROW = 5, 1
 # thmr_val_loss_grad (header: THMR_LOSS_GRAD_*): the slots of its host table of device pointers
 LOSS_GRAD_KP2D, LOSS_GRAD_KP3D, LOSS_GRAD_JOINTS, LOSS_GRAD_CAM, LOSS_GRAD_ROTMAT, LOSS_GRAD_BETAS, LOSS_GRAD_SLOTS = 0, 1, 2, 3, 4, 5, 6
+# thmr_disc_forward / thmr_disc_backward (header: THMR_DISC_*): the slots of their host table of device pointers, and the sizes
+DISC_OUT, DISC_LOSS, DISC_GRAD_POSES, DISC_GRAD_BETAS, DISC_WORKSPACE, DISC_SLOTS = 0, 1, 2, 3, 4, 5
+DISC_MAX_BATCH, DISC_KPAD, DISC_WEIGHT_FLOATS, DISC_WS_PER_ITEM = 256, 768, 3644480, 5665
 VAL_LOSS_IN_FIELDS = ["pred_keypoints_2d", "pred_keypoints_3d", "pred_rotmat", "pred_betas", "gt_keypoints_2d", "gt_keypoints_3d", "gt_pose",
                       "gt_betas", "has_global_orient", "has_body_pose", "has_betas", "valid_3d", "kp2d_thresh", "angle_thresh"]
 VAL_LOSS_OUT_FIELDS = ["losses", "per_item", "kp2d_err", "angle_err", "valid2d", "weak2d", "valid_rot", "weak_rot", "conf2d_used",

@@ -505,6 +505,50 @@ struct ReconLossArgs {
 int launch_recon_loss(ReconLossArgs& a, hipStream_t s);
 // out[0] = mean over rows of logsumexp(x_r) - x_r[target_r], x (rows, 2048); row_loss: rows floats of workspace
 int launch_token_ce(const float* x, const int32_t* target, int rows, float* out, float* row_loss, hipStream_t s);
+// discriminator.hip: the HMR pose / shape discriminator (tokenhmr/lib/models/discriminator.py), forward and the gradient by its inputs.
+// The weight block, as float offsets: the blocks below in this order, each starting at a multiple of 64 floats (include/tokenhmr_hip.h
+// states the same list; tokenhmr_amd/discriminator.py writes it).  "_t" = the transposed copy the other direction streams.
+constexpr int64_t disc_up(int64_t x) { return (x + 63) & ~int64_t(63); }
+struct DiscWeights {
+    static constexpr int64_t conv1_t = 0;                               // (9,32)      D_conv1.weight^T
+    static constexpr int64_t conv1_b = disc_up(conv1_t + 9 * 32);            // (32)
+    static constexpr int64_t conv2_t = disc_up(conv1_b + 32);                // (32,32)     D_conv2.weight^T
+    static constexpr int64_t conv2 = disc_up(conv2_t + 32 * 32);             // (32,32)     D_conv2.weight
+    static constexpr int64_t conv2_b = disc_up(conv2 + 32 * 32);             // (32)
+    static constexpr int64_t conv1 = disc_up(conv2_b + 32);                  // (32,9)      D_conv1.weight
+    static constexpr int64_t pose_out_w = disc_up(conv1 + 32 * 9);           // (23,32)     pose_out.j.weight, row j
+    static constexpr int64_t pose_out_b = disc_up(pose_out_w + 23 * 32);     // (23)
+    static constexpr int64_t betas_fc1_w = disc_up(pose_out_b + 23);         // (10,10)
+    static constexpr int64_t betas_fc1_b = disc_up(betas_fc1_w + 100);       // (10)
+    static constexpr int64_t betas_fc2_w = disc_up(betas_fc1_b + 10);        // (5,10)
+    static constexpr int64_t betas_fc2_b = disc_up(betas_fc2_w + 50);        // (5)
+    static constexpr int64_t betas_out_w = disc_up(betas_fc2_b + 5);         // (5)
+    static constexpr int64_t betas_out_b = disc_up(betas_out_w + 5);         // (1)
+    static constexpr int64_t fc1 = disc_up(betas_out_b + 1);                 // (1024,768)  D_alljoints_fc1.weight, column j * 32 + c = its c * 23 + j; 736.. zero
+    static constexpr int64_t fc1_b = disc_up(fc1 + 1024 * 768);              // (1024)
+    static constexpr int64_t fc1_t = disc_up(fc1_b + 1024);                  // (736,1024)  the first 736 columns of fc1, transposed
+    static constexpr int64_t fc2 = disc_up(fc1_t + 736 * 1024);              // (1024,1024) D_alljoints_fc2.weight
+    static constexpr int64_t fc2_b = disc_up(fc2 + 1024 * 1024);             // (1024)
+    static constexpr int64_t fc2_t = disc_up(fc2_b + 1024);                  // (1024,1024) its transpose
+    static constexpr int64_t out_w = disc_up(fc2_t + 1024 * 1024);           // (1024)      D_alljoints_out.weight
+    static constexpr int64_t out_b = disc_up(out_w + 1024);                  // (1)
+    static constexpr int64_t total = disc_up(out_b + 1);
+};
+constexpr int kDiscKpad = 768;                                    // fc1's K, 736 padded to the skinny GEMM's 64-deep step
+struct DiscArgs {
+    const float *w, *poses, *betas;       // the weight block; (B,23,3,3) with pose_stride floats between items; (B,10)
+    const float* grad_out;                // (B,25) or null: then d loss / d out = 2 (out - target) / div
+    int64_t pose_stride;
+    float *out, *loss;                    // (B,25); one float or null
+    float *grad_poses, *grad_betas;       // (B,23,3,3), (B,10): backward only, either may be null
+    float *h, *a1, *a2, *dz2, *dz1, *dh, *partial;      // workspace: (B,768) (B,1024) x 4 (B,768) (B)
+    float target, div;                    // the loss's target (0 or 1) and divisor (the batch size the loss is a mean over)
+    int B, want_out;                      // want_out: the caller reads `out` of a backward (else the wide layers may be skipped)
+};
+int launch_disc_forward(const DiscArgs& a, hipStream_t s);
+int launch_disc_backward(const DiscArgs& a, hipStream_t s);
+// gemm_skinny.hip: C = resid[m][n] > 0 ? acc : 0 — the reverse product of a Linear + ReLU, masked by the forward's output
+int launch_gemm_skinny_relu_mask(const GemmArgs& a, hipStream_t s);
 // body_model.hip: SMPL and SMPL-H on one set of kernels (prep -> blend GEMM -> skin).  One-time, per model: Jt (nj,3) / Jsd (nj,3,10) from
 // the joint regressor (launch_body_jreg), dirsT (20670 x kx) = [shapedirs | the first npf rows of posedirs | 0]^T (launch_body_build_dirs)
 int launch_body_jreg(const float* Jreg, const float* vt, const float* sd, float* Jt, float* Jsd, int nj, hipStream_t s);

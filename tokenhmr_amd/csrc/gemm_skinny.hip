@@ -13,6 +13,10 @@
 
 namespace {
 
+// An epilogue of this file only (not a GemmEpi, not offered through thmr_op_gemm): C = resid[m][n] > 0 ? acc : 0, no bias — the reverse
+// product dX = dY . W of a Linear whose INPUT came out of a ReLU, masked by that ReLU's output (torch's derivative: zero at z <= 0).
+constexpr int EPI_SKINNY_RELU_MASK = 100;
+
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs a) {
     __shared__ __attribute__((aligned(16))) float red[4][4][64][4];   // [wave][mtile][lane][reg]
@@ -74,11 +78,15 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs a) {
     const int n = n0 + l15;
     if (n < a.N) {
         float bias = 0.f;
-        if constexpr (EPI != EPI_NONE) bias = a.bias[n];
+        if constexpr (EPI != EPI_NONE && EPI != EPI_SKINNY_RELU_MASK) bias = a.bias[n];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int m = m0 + mt * 16 + g * 4 + r;   // D layout 16x16: row = 4*(lane>>4) + reg, col = lane&15
-            if (m < a.M) a.C[(int64_t)m * a.ldc + n] = gemm_epilogue<EPI>(a, v[r], bias, m, n);
+            if constexpr (EPI == EPI_SKINNY_RELU_MASK) {
+                if (m < a.M) a.C[(int64_t)m * a.ldc + n] = a.resid[(int64_t)m * a.ldr + n] > 0.f ? v[r] : 0.f;
+            } else {
+                if (m < a.M) a.C[(int64_t)m * a.ldc + n] = gemm_epilogue<EPI>(a, v[r], bias, m, n);
+            }
         }
     }
 }
@@ -100,5 +108,12 @@ int launch_gemm_skinny(const GemmArgs& a, int epi, hipStream_t s) {
         default: return -1;
     }
 #undef THMR_SK_CASE
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_gemm_skinny_relu_mask(const GemmArgs& a, hipStream_t s) {
+    if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % 64) != 0 || !a.resid) return -1;
+    if ((a.lda % 4) != 0 || (a.ldw % 4) != 0) return -1;
+    hipLaunchKernelGGL((gemm_skinny_kernel<EPI_SKINNY_RELU_MASK>), dim3((a.N + 15) / 16, (a.M + 63) / 64), dim3(256), 0, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

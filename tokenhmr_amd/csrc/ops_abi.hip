@@ -753,6 +753,57 @@ int thmr_op_token_ce(const float* x, const int32_t* target, int32_t rows, float*
     return 0;
 }
 
+// ---- the pose / shape discriminator and its gradient by the inputs (stateless; csrc/discriminator.hip) ----
+static_assert(DiscWeights::total == THMR_DISC_WEIGHT_FLOATS && kDiscKpad == THMR_DISC_KPAD, "the header states the weight block's size");
+static_assert(THMR_DISC_WS_PER_ITEM == 2 * THMR_DISC_KPAD + 4 * 1024 + 32 + 1, "the header states the workspace");
+
+// What both calls refuse, without the entry point's name in front; fills the inputs and the workspace's regions when the arguments pass.
+static const char* disc_prepare(DiscArgs& a, const float* weights, const float* poses, int64_t pose_stride, const float* betas, int32_t B,
+                                int32_t loss_div, float** bufs) {
+    if (!weights || !poses || !betas || !bufs) return "null weights, poses, betas or buffer table";
+    float* ws = bufs[THMR_DISC_WORKSPACE];
+    if (!ws) return "null workspace";
+    if (B < 1 || B > THMR_DISC_MAX_BATCH) return "1 <= B <= THMR_DISC_MAX_BATCH (256) is required";
+    if (loss_div < 0) return "loss_div >= 0 is required (0 = B)";
+    if (pose_stride < 207) return "pose_stride >= 207 is required";
+    if (reinterpret_cast<uintptr_t>(weights) % 16 != 0 || reinterpret_cast<uintptr_t>(ws) % 16 != 0)
+        return "the weight block and the workspace must be 16-byte aligned";
+    a.w = weights; a.poses = poses; a.betas = betas; a.pose_stride = pose_stride; a.B = B;
+    a.div = (float)(loss_div > 0 ? loss_div : B);
+    const size_t n = (size_t)B;
+    a.h = ws; a.a1 = a.h + n * THMR_DISC_KPAD; a.a2 = a.a1 + n * 1024; a.dz2 = a.a2 + n * 1024; a.dz1 = a.dz2 + n * 1024;
+    a.dh = a.dz1 + n * 1024;
+    float* own_out = a.dh + n * THMR_DISC_KPAD;
+    a.partial = own_out + n * 32;
+    a.want_out = bufs[THMR_DISC_OUT] != nullptr;
+    a.out = a.want_out ? bufs[THMR_DISC_OUT] : own_out;
+    a.loss = bufs[THMR_DISC_LOSS];
+    return nullptr;
+}
+
+int thmr_disc_forward(const float* weights, const float* poses, int64_t pose_stride, const float* betas, int32_t B, int32_t loss_div,
+                      double target, float** bufs, void* stream) {
+    DiscArgs a{};
+    if (const char* why = disc_prepare(a, weights, poses, pose_stride, betas, B, loss_div, bufs)) return fail(THMR_ERR_INVALID, std::string("disc_forward: ") + why);
+    if (!a.want_out) return fail(THMR_ERR_INVALID, "disc_forward: the OUT slot is null");
+    if (a.loss && !std::isfinite(target)) return fail(THMR_ERR_INVALID, "disc_forward: the target must be finite");
+    a.target = (float)target;
+    LAUNCH_OK(launch_disc_forward(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int thmr_disc_backward(const float* weights, const float* poses, int64_t pose_stride, const float* betas, const float* grad_out, int32_t B,
+                       int32_t loss_div, double target, float** bufs, void* stream) {
+    DiscArgs a{};
+    if (const char* why = disc_prepare(a, weights, poses, pose_stride, betas, B, loss_div, bufs)) return fail(THMR_ERR_INVALID, std::string("disc_backward: ") + why);
+    a.grad_poses = bufs[THMR_DISC_GRAD_POSES]; a.grad_betas = bufs[THMR_DISC_GRAD_BETAS]; a.grad_out = grad_out;
+    if (!a.grad_poses && !a.grad_betas) return fail(THMR_ERR_INVALID, "disc_backward: the GRAD_POSES and GRAD_BETAS slots are both null");
+    if ((a.loss || !grad_out) && !std::isfinite(target)) return fail(THMR_ERR_INVALID, "disc_backward: the target must be finite");
+    a.target = (float)target;
+    LAUNCH_OK(launch_disc_backward(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 // ---- evaluation metrics (stateless) ----
 int thmr_eval_pose(const float* pred_j, const float* gt_j, int32_t nj, int32_t gt_stride, const int32_t* kp, int32_t nkp,
                    int32_t pelvis_ind, int32_t pelvis_mode, const float* pred_v, const float* gt_v, int32_t nv, int32_t B,

@@ -11,7 +11,11 @@ head's outputs:
 
     losses, grads = vloss.value_and_grad(batch, output, body_model=smpl_model)      # d loss / d (global_orient, body_pose, betas, pred_cam)
 
-There is no backward above the head; the optimisers and the discriminator terms are not built.
+With a tokenhmr_amd.discriminator.Discriminator the generator's adversarial term (tokenhmr.py:392-394) joins both:
+
+    losses, grads = vloss.value_and_grad(batch, output, body_model=smpl_model, discriminator=D)      # + losses['loss_gen']
+
+There is no backward above the head, no gradient by the discriminator's own weights, and the optimisers are not built.
 
 Deliberate departure: the reference's LOOSE_SUP branch writes into the batch (keypoints_2d[:, :, -1], keypoints_3d[:, :, -1],
 has_smpl_params['betas']; :223, :227, :240).  Nothing in `batch` is modified here; what the reference would have written is returned in
@@ -67,6 +71,7 @@ class ValidationLoss:
         if missing:
             raise KeyError(f"cfg.LOSS_WEIGHTS lacks {missing}")
         self.weights = [float(lw[k]) for k in _WEIGHT_KEYS]
+        self.adversarial_weight = float(lw["ADVERSARIAL"]) if "ADVERSARIAL" in lw else 0.0      # tokenhmr.py:394; read by value_and_grad only
         model = _node(cfg, "MODEL")
         get = model.get if hasattr(model, "get") else (lambda k, d=None: getattr(model, k, d))
         self.loose_sup = bool(get("LOOSE_SUP", False))
@@ -168,7 +173,8 @@ class ValidationLoss:
             b["value"].update({k: f(B) if k == "has_betas_used" else f(B, 44 if "2d" in k or "3d" in k else 24) for k in ops.VAL_LOSS_TAPS})
         return b
 
-    def value_and_grad(self, batch, output, body_model=None, train=False, focal_length=5000.0, image_size=256.0):
+    def value_and_grad(self, batch, output, body_model=None, train=False, focal_length=5000.0, image_size=256.0, discriminator=None,
+                       adversarial_weight=None):
         """-> (losses, grads).  `losses` is what __call__ sets as output['losses'], from the same thmr_val_loss call on the same arguments
         (bit-equal to it); the running means of get_metrics_dict() count __call__ only.  The total is a SUM over the items, as the
         reference's: nothing is divided by the batch size.
@@ -180,7 +186,13 @@ class ValidationLoss:
         torch.add per summed tensor; on the current stream, without synchronisation, and after the first call at a batch size without
         allocations beyond prepare()'s own copies (capturable once body_model.enable_grad() has run; prepare() uploads valid_3d from
         the host in the loose branch, which a capture refuses).  The returned tensors are buffers of this object, overwritten by the
-        next call at that batch size on that device."""
+        next call at that batch size on that device.
+        discriminator (a tokenhmr_amd.discriminator.Discriminator; default None: not a launch or a bit changes): the generator's term of
+        training_step (tokenhmr.py:392-394).  `losses` then also holds 'loss_gen' = ((D(body_pose, betas) - 1)^2).sum() / B, 'loss' is
+        compute_loss + w loss_gen, and w d loss_gen is added into the 'body_pose' and 'betas' gradients ('global_orient' and 'pred_cam'
+        get none); w = adversarial_weight, by default cfg.LOSS_WEIGHTS.ADVERSARIAL where the config has it, else 0.  One
+        thmr_disc_backward call per chunk of the discriminator's max_batch, on body_pose as the stride-216 view of the joined
+        rotation matrices (no copy), and three torch.add."""
         a = self.prepare(batch, output, train)
         loose = a.pop("loose")
         dev, B = a["pred_kp2d"].device, a["pred_kp2d"].shape[0]
@@ -201,7 +213,12 @@ class ValidationLoss:
                           loose_weight=self.loose_weight, valid_3d=a["valid_3d"], kp2d_thresh=st["kp2d"] if loose else None,
                           angle_thresh=st["angle"] if loose else None, pelvis_id=self.pelvis_id, pred_cam=cam, focal_length=focal_length,
                           image_size=image_size, want=want, out=b)
+        if discriminator is not None:
+            losses = self._adversarial(discriminator, adversarial_weight, a, b, losses, output)
         if body_model is None:
+            if discriminator is not None:
+                b["rotmat"][:, 1:].add_(b["adv_poses"], alpha=b["adv_w"])
+                b["betas"].add_(b["adv_betas"], alpha=b["adv_w"])
             return losses, {"pred_keypoints_2d": b["kp2d"], "pred_keypoints_3d": b["kp3d"], "global_orient": b["rotmat"][:, :1],
                             "body_pose": b["rotmat"][:, 1:], "betas": b["betas"]}
         with torch.no_grad():
@@ -211,8 +228,30 @@ class ValidationLoss:
                                      b["bm_rotmat"][i:i + n], b["bm_betas"][i:i + n])
             torch.add(b["bm_rotmat"], b["rotmat"], out=b["total_rotmat"])
             torch.add(b["bm_betas"], b["betas"], out=b["total_betas"])
+            if discriminator is not None:
+                b["total_rotmat"][:, 1:].add_(b["adv_poses"], alpha=b["adv_w"])
+                b["total_betas"].add_(b["adv_betas"], alpha=b["adv_w"])
         return losses, {"global_orient": b["total_rotmat"][:, :1], "body_pose": b["total_rotmat"][:, 1:], "betas": b["total_betas"],
                         "pred_cam": b["cam"]}
+
+    def _adversarial(self, discriminator, weight, a, b, losses, output):
+        """loss_gen and its gradient by body_pose and betas into b['adv_*']; -> the losses dict with 'loss_gen' and the new total."""
+        dev, B = a["pred_betas"].device, a["pred_betas"].shape[0]
+        if discriminator.device != dev:
+            raise ValueError(f"the discriminator lives on {discriminator.device}, the loss's inputs on {dev}")
+        w = self.adversarial_weight if weight is None else float(weight)
+        if "adv_poses" not in b:
+            f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)      # noqa: E731
+            b.update(adv_poses=f(B, 23, 3, 3), adv_betas=f(B, 10), adv_loss=f(()), adv_chunk=f(()), adv_total=f(()))
+        b["adv_w"] = w
+        with torch.no_grad():
+            discriminator._chunks(a["pred_rotmat"][:, 1:], a["pred_betas"], target=1.0, want_loss=True, want_poses=True, want_betas=True,
+                                  bufs={"loss": b["adv_loss"], "chunk_loss": b["adv_chunk"], "grad_poses": b["adv_poses"],
+                                        "grad_betas": b["adv_betas"]})
+            torch.add(losses["loss"], b["adv_loss"], alpha=w, out=b["adv_total"])          # tokenhmr.py:394
+        losses = dict(losses, loss=b["adv_total"], loss_gen=b["adv_loss"])
+        output["losses"] = losses
+        return losses
 
     def reset(self):
         for st in self._dev.values():

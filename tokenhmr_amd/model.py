@@ -140,15 +140,18 @@ class TokenHMR:
             self.body_model = SMPL(self._smpl_constants, max_batch=self.max_batch, device=self.device).enable_grad()
         return self.body_model
 
-    def loss_value_and_grad(self, batch, output, train=False, body_model=None):
+    def loss_value_and_grad(self, batch, output, train=False, body_model=None, discriminator=None, adversarial_weight=None):
         """compute_loss and its gradient by the head's outputs -> (losses, grads): `losses` as compute_loss sets output['losses'], `grads`
         with 'global_orient' (B,1,3,3), 'body_pose' (B,23,3,3), 'betas' (B,10) and 'pred_cam' (B,3) — the total derivative of the summed
         loss through the projection and the body model (ValidationLoss.value_and_grad; buffers, overwritten by the next call at that
         batch size).  `output` is what forward() returned.  There is no backward past the head: the ViT, the decoder and the tokenizer
-        stay inference only.  The body model is built from the SMPL constants on first use."""
+        stay inference only.  The body model is built from the SMPL constants on first use.
+        discriminator / adversarial_weight: ValidationLoss.value_and_grad's — with a tokenhmr_amd.discriminator.Discriminator, `losses` also
+        holds 'loss_gen', 'loss' is compute_loss + w loss_gen (tokenhmr.py:392-394) and the 'body_pose' and 'betas' gradients carry the
+        term; without one nothing changes."""
         F, S = self._projection()
         return self._loss_module().value_and_grad(batch, output, body_model=self._grad_body_model(body_model), train=train, focal_length=F,
-                                                  image_size=S)
+                                                  image_size=S, discriminator=discriminator, adversarial_weight=adversarial_weight)
 
     def _head_output(self, pred_smpl_params, pred_cam):
         """The engine's own tail on a head's outputs: Engine.lbs_forward -> the part of forward()'s dict that compute_loss reads."""
@@ -160,14 +163,19 @@ class TokenHMR:
         return {"pred_cam": cam, "pred_cam_t": cam_t, "pred_smpl_params": {"global_orient": R[:, :1], "body_pose": R[:, 1:], "betas": betas},
                 "pred_keypoints_3d": joints, "pred_keypoints_2d": kp2d}
 
-    def head_loss(self, batch, pred_smpl_params, pred_cam, train=False, body_model=None):
+    def head_loss(self, batch, pred_smpl_params, pred_cam, train=False, body_model=None, discriminator=None, adversarial_weight=None):
         """compute_loss of a head's outputs under torch autograd: pred_smpl_params {'global_orient' (B,1,3,3), 'body_pose' (B,23,3,3),
         'betas' (B,10)} and pred_cam (B,3) -> the 0-dim total.  Forward: Engine.lbs_forward and thmr_val_loss, the engine's own tail and
         the existing value.  When grad is enabled and an input requires it, the total carries a graph whose backward is
-        loss_value_and_grad's chain (once differentiable; an input that needs no gradient gets None).  Otherwise the plain path."""
+        loss_value_and_grad's chain (once differentiable; an input that needs no gradient gets None).  Otherwise the plain path.
+        With a discriminator the total is compute_loss + w loss_gen, as loss_value_and_grad's, on either path."""
         ins = (pred_smpl_params["global_orient"], pred_smpl_params["body_pose"], pred_smpl_params["betas"], pred_cam)
         if torch.is_grad_enabled() and any(t.requires_grad for t in ins):
-            return _HeadLossFn.apply(self, batch, bool(train), self._grad_body_model(body_model), *ins)
+            return _HeadLossFn.apply(self, batch, bool(train), self._grad_body_model(body_model), discriminator, adversarial_weight, *ins)
+        if discriminator is not None:
+            out = self._head_output(pred_smpl_params, pred_cam)
+            return self.loss_value_and_grad(batch, out, train=train, body_model=body_model, discriminator=discriminator,
+                                            adversarial_weight=adversarial_weight)[0]["loss"].clone()
         return self.compute_loss(batch, self._head_output(pred_smpl_params, pred_cam), train=train)
 
     def validation_step(self, batch, batch_idx=0, dataloader_idx=0):
@@ -214,13 +222,14 @@ class _HeadLossFn(torch.autograd.Function):
     """TokenHMR.head_loss with a graph: the value and the four gradients come out of one loss_value_and_grad call in forward()."""
 
     @staticmethod
-    def forward(ctx, model, batch, train, body_model, go, bp, betas, cam):
+    def forward(ctx, model, batch, train, body_model, discriminator, adversarial_weight, go, bp, betas, cam):
         ctx.set_materialize_grads(False)
         out = model._head_output({"global_orient": go, "body_pose": bp, "betas": betas}, cam)
-        losses, grads = model.loss_value_and_grad(batch, out, train=train, body_model=body_model)
+        losses, grads = model.loss_value_and_grad(batch, out, train=train, body_model=body_model, discriminator=discriminator,
+                                                  adversarial_weight=adversarial_weight)
         # the gradients are buffers of the loss module: this graph keeps copies of those it will hand out
         keep = [grads[k].reshape(t.shape).clone() if need else None
-                for k, t, need in zip(("global_orient", "body_pose", "betas", "pred_cam"), (go, bp, betas, cam), ctx.needs_input_grad[4:])]
+                for k, t, need in zip(("global_orient", "body_pose", "betas", "pred_cam"), (go, bp, betas, cam), ctx.needs_input_grad[6:])]
         ctx.which = [g is not None for g in keep]
         ctx.save_for_backward(*[g for g in keep if g is not None])
         return losses["loss"].clone()
@@ -231,8 +240,8 @@ class _HeadLossFn(torch.autograd.Function):
         saved = iter(ctx.saved_tensors)
         grads = [next(saved) if have else None for have in ctx.which]
         if g_total is None:
-            return (None,) * 8
-        return (None, None, None, None) + tuple(None if g is None else g * g_total for g in grads)
+            return (None,) * 10
+        return (None,) * 6 + tuple(None if g is None else g * g_total for g in grads)
 
 
 def _cat_outputs(outs):

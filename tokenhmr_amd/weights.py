@@ -237,6 +237,35 @@ def make_synthetic_tokenizer(cfg: HMRConfig = RELEASE, seed: int = 0):
     return sd
 
 
+def discriminator_spec():
+    """Ordered (name, shape) of every tensor of the reference's Discriminator (tokenhmr/lib/models/discriminator.py:12-49): its
+    state_dict's key names; the two 1x1 convolutions keep their 4-D weights."""
+    S = [("D_conv1.weight", (32, 9, 1, 1)), ("D_conv1.bias", (32,)), ("D_conv2.weight", (32, 32, 1, 1)), ("D_conv2.bias", (32,))]
+    for j in range(23):
+        S += [(f"pose_out.{j}.weight", (1, 32)), (f"pose_out.{j}.bias", (1,))]
+    for name, o, i in (("betas_fc1", 10, 10), ("betas_fc2", 5, 10), ("betas_out", 1, 5), ("D_alljoints_fc1", 1024, 736),
+                       ("D_alljoints_fc2", 1024, 1024), ("D_alljoints_out", 1, 1024)):
+        S += [(name + ".weight", (o, i)), (name + ".bias", (o,))]
+    return S
+
+
+def make_synthetic_discriminator(seed: int = 0, style: str = "init"):
+    """Seeded Discriminator state_dict (reference key names).  style "init": weights U(-a, a) with Xavier's a = sqrt(6 / (fan_in +
+    fan_out)), as the reference initialises them (discriminator.py:15-48); the biases, which it zeroes, are 0.1 * randn here — a zero
+    bias would hide every bias bug.  The 23 per-joint heads are 23 different draws."""
+    if style != "init":
+        raise ValueError(f"unknown weight style '{style}'")
+    g = torch.Generator(device="cpu").manual_seed(3000 + seed)
+    sd = OrderedDict()
+    for name, shape in discriminator_spec():
+        if name.endswith(".bias"):
+            sd[name] = 0.1 * torch.randn(shape, generator=g, dtype=torch.float32)
+        else:
+            a = math.sqrt(6.0 / (shape[0] + shape[1]))          # 1x1 kernels: the receptive field is 1
+            sd[name] = (torch.rand(shape, generator=g, dtype=torch.float32) * 2 - 1) * a
+    return sd
+
+
 def checksum(sd) -> float:
     """Cheap fingerprint so golden fixtures can detect a weight-generator drift."""
     acc = 0.0
