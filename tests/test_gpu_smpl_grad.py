@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import rotation_cases as RC
 import stage_bounds as SB
 from tests import guarded as G
 
@@ -393,9 +394,9 @@ def test_gpu_aa_to_rotmat_backward(built_lib, cuda_dev, n):
     aa = torch.from_numpy(0.8 * rng.standard_normal((n, 3))).float()
     gR = torch.from_numpy(rng.standard_normal((n, 3, 3))).float()
 
-    def truth(dtype):
+    def truth(dtype, fn=O.batch_rodrigues):
         t = aa.to(dtype).clone().requires_grad_(True)
-        return torch.autograd.grad((O.batch_rodrigues(t) * gR.to(dtype)).sum(), t)[0]
+        return torch.autograd.grad((fn(t) * gR.to(dtype)).sum(), t)[0]
 
     x = aa.to(cuda_dev).requires_grad_(True)
     R = ops.aa_to_rotmat(x)
@@ -403,5 +404,9 @@ def test_gpu_aa_to_rotmat_backward(built_lib, cuda_dev, n):
     g, = torch.autograd.grad((R * gR.to(cuda_dev)).sum(), x)
     with torch.no_grad():
         assert ops.aa_to_rotmat(x).grad_fn is None
-    ok, line = SB.check(f"aa_to_rotmat backward, n = {n}:", g.cpu(), truth(torch.float32), truth(torch.float64), MULT)
+    # the fp32 reference is the tighter of the two forms against the SAME truth (tests/test_gpu_rotation_edges.py): the quaternion form the
+    # operator computes (geometry.py:5-44) or the Rodrigues form its adjoint is written from; the bound can only be the earlier one or less
+    r64 = truth(torch.float64)
+    name, r32 = RC.tighter({"rod": truth(torch.float32), "quat": truth(torch.float32, O.aa_to_rotmat)}, r64, 0, n)
+    ok, line = SB.check(f"aa_to_rotmat backward, n = {n} (fp32 reference: {name}):", g.cpu(), r32, r64, MULT)
     assert ok, line

@@ -246,6 +246,35 @@ def test_matrix_and_axis_angle_ground_truth_agree(built_lib, cuda_dev, golden, t
                 assert np.array_equal(a[k], b[k])
 
 
+def test_matrix_and_axis_angle_ground_truth_agree_on_the_edge_sets(built_lib, cuda_dev, thresholds):
+    """The same twins on the rows where the formula is singular: 24 joints x 5 items take ten rows of each axis-angle group of
+    tests/rotation_cases.py (zero, |aa| = 1e-9 ... 1e-2, near pi, 2 pi and 4 pi, single-axis), the NaN row excluded."""
+    import rotation_cases as RC
+    B = 5
+    x, spans = RC.aa_set()
+    rows = torch.cat([x[lo + 3:lo + 13] for lo, hi in spans.values()])
+    assert rows.shape == (B * 24, 3) and torch.isfinite(rows).all()
+    inp = GV.make_inputs(B, 33)
+    inp["gt_pose_aa"] = rows.reshape(B, 72).numpy().copy()
+    for k in ("has_global_orient", "has_body_pose"):           # every row counts
+        inp[k] = np.ones(B, dtype=np.float32)
+    aa = rows.to(cuda_dev).contiguous()
+    R = torch.empty(B * 24, 3, 3, device=cuda_dev)
+    _cabi.check(built_lib.thmr_op_aa_to_rotmat(_p(aa), _p(R), B * 24, None), lib=built_lib)
+    inp["gt_pose_rotmat"] = R.view(B, 24, 3, 3).cpu().numpy()
+    for loose in (False, True):
+        a, b = _np(_device_call(inp, cuda_dev, thresholds, loose)), _np(_device_call(inp, cuda_dev, thresholds, loose, gt="mat"))
+        assert np.isfinite(a["per_item"]).all() and (a["per_item"][:, 2:4] > 0).all()
+        assert np.array_equal(a["per_item"][:, 2:4], b["per_item"][:, 2:4]), "aa_to_rotmat_dev and aa_to_rotmat_kernel no longer agree bit for bit"
+        assert np.array_equal(a["losses"], b["losses"])
+        if loose:
+            d = np.abs(a["angle_err"] - b["angle_err"]).max()
+            print(f"edge sets: angle_err between the two ground truths differs by {d:.2e} rad")
+            assert d <= ANGLE_FLOOR
+            for k in ("valid_rot", "weak_rot", "valid2d", "conf3d_used"):
+                assert np.array_equal(a[k], b[k])
+
+
 # ------------------------------------------------------------------------------------------------ determinism, graph replay
 def test_two_runs_and_a_graph_replay_are_bit_equal(built_lib, cuda_dev, golden, thresholds):
     lib = built_lib
