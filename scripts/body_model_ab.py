@@ -7,10 +7,11 @@
 bits: the same inputs and synthetic constants through library A and the in-tree library, every output compared byte for byte (output
       buffers pre-filled with one pattern, so what a call leaves unwritten compares equal too).  SMPL through thmr_smpl_forward (every
       crops-per-pass regime of launch_lbs and its ragged last group; each case twice, so the arrival counter is re-zeroed), the engine
-      path (thmr_lbs_forward with a camera, thmr_forward) on a depth-1 engine, SMPL-H through thmr_smplh_forward.  Exit status 1 if any
-      byte differs.
-time: thmr_smpl_forward at 1, 64, 512 crops (scripts/lbs_bench.py's call) and thmr_smplh_forward full / folded at 1, 8, 64 poses
-      (scripts/smplh_bench.py's calls), three arms taking turns window by window: A, the in-tree library, and A AGAIN on a second handle,
+      path (thmr_lbs_forward with a camera, thmr_forward) on a depth-1 engine, SMPL-H through thmr_smplh_forward.  The backward through
+      thmr_smpl_backward (matrices and axis-angle) and thmr_smplh_backward (folded and full, both paths reserved on one handle), each at
+      the smallest batch of every crops-per-workgroup value and at one batch with a ragged last group.  Exit status 1 if any byte differs.
+time: thmr_smpl_forward at 1, 64, 512 crops (scripts/lbs_bench.py's call), thmr_smplh_forward full / folded at 1, 8, 64 poses
+      (scripts/smplh_bench.py's calls) and the three backward calls at 64, three arms taking turns window by window: A, the in-tree library, and A AGAIN on a second handle,
       whose distance from the first is the parent's own run-to-run spread; then bench.py's default line from a built checkout of the
       parent, from this tree and from the parent's again.  Exit status 1 unless in every row the in-tree figure lies within that spread
       of the parent's.  The recorded run (profiles/body_model_ab_same_box.json) ended with status 1: 4 of 10 rows outside, three of them
@@ -64,6 +65,14 @@ def smplh_fwd(lib, h, pose, pose2rot, betas, transl, body_only, B, verts, joints
     _cabi.check(lib.thmr_smplh_forward(h, p(pose), pose2rot, p(betas), p(transl), body_only, B, p(verts), p(joints), None), lib=lib)
 
 
+def smpl_bwd(lib, h, pose, pose2rot, betas, B, gV, gJ, gp, gb):
+    _cabi.check(lib.thmr_smpl_backward(h, p(pose), pose2rot, p(betas), B, p(gV), p(gJ), p(gp), p(gb), None), lib=lib)
+
+
+def smplh_bwd(lib, h, pose, pose2rot, betas, transl, body_only, B, gV, gJ, gp, gb, gt):
+    _cabi.check(lib.thmr_smplh_backward(h, p(pose), pose2rot, p(betas), p(transl), body_only, B, p(gV), p(gJ), p(gp), p(gb), p(gt), None), lib=lib)
+
+
 def rotmats(n, g):
     R = torch.linalg.qr(torch.randn(n, 3, 3, generator=g))[0]
     return R * torch.linalg.det(R).sign()[:, None, None]
@@ -95,6 +104,8 @@ def bits(libs, out):
     R = rotmats(BMAX * 24, g).reshape(BMAX, 24, 3, 3).to(DEV)
     aa = (torch.randn(BMAX, 72, generator=g) * 0.7).to(DEV)
     betas = torch.randn(BMAX, 10, generator=g).to(DEV)
+    gV = torch.randn(BMAX, 6890, 3, generator=g).to(DEV)          # the backward rows' output gradients, SMPL's and (the first 256) SMPL-H's
+    gJ = torch.randn(BMAX, 73, 3, generator=g).to(DEV)
     for mname, consts in models:
         hs = [create(lib, consts, BMAX, False) for lib in libs]
         for B, pose2rot in itertools.product([64] if "dup" in mname else [1, 3, 31, 32, 63, 64, 65, 100, 255, 256, 300], (0, 1)):
@@ -105,6 +116,17 @@ def bits(libs, out):
                     smpl_fwd(lib, h, (aa if pose2rot else R)[:B].contiguous(), pose2rot, betas[:B].contiguous(), B, v, j)
                     outs.append((v, j))
                 record(f"smpl {mname} B={B} pose2rot={pose2rot} call={call}", {"verts": (outs[0][0], outs[1][0]), "joints": (outs[0][1], outs[1][1])})
+        # thmr_smpl_backward: the smallest batch of every crops-per-pass value (1 ... 8), and 300 = 37 groups of 8 and a ragged one of 4
+        for lib, h in zip(libs, hs):
+            _cabi.check(lib.thmr_smpl_grad_reserve(h), lib=lib)
+        for B, pose2rot in itertools.product([64] if "dup" in mname else [1, 64, 96, 128, 160, 192, 224, 256, 300], (0, 1)):
+            pose = (aa if pose2rot else R)[:B].contiguous()
+            outs = []
+            for lib, h in zip(libs, hs):
+                gp, gb = torch.full_like(pose, -7.5), torch.full((B, 10), -7.5, device=DEV)
+                smpl_bwd(lib, h, pose, pose2rot, betas[:B].contiguous(), B, gV[:B].contiguous(), gJ[:B, :44].contiguous(), gp, gb)
+                outs.append((gp, gb))
+            record(f"smpl backward {mname} B={B} pose2rot={pose2rot}", {"grad_pose": (outs[0][0], outs[1][0]), "grad_betas": (outs[0][1], outs[1][1])})
         for lib, h in zip(libs, hs):
             lib.thmr_smpl_destroy(h)
 
@@ -149,6 +171,21 @@ def bits(libs, out):
             outs.append((v, j))
         record(f"smplh {'folded' if body_only else 'full'} B={B} transl={wt} betas={wb} joints={wj} pose2rot={pose2rot}",
                {"verts": (outs[0][0], outs[1][0]), "joints": (outs[0][1], outs[1][1])})
+    # thmr_smplh_backward, both paths reserved on one handle: the smallest batch of every poses-per-workgroup value (1, 2, 4, 8), and 255 =
+    # 63 groups of 4 and a ragged one of 3
+    for lib, h in zip(libs, hs):
+        _cabi.check(lib.thmr_smplh_grad_reserve(h, 3), lib=lib)
+    for body_only, B, pose2rot in itertools.product((1, 0), [1, 64, 128, 255, 256], (0, 1)):
+        nj = 22 if body_only else 52
+        pose = (aah[:B, :nj * 3] if pose2rot else Rh[:B, :nj]).contiguous()
+        outs = []
+        for lib, h in zip(libs, hs):
+            grads = [torch.full_like(pose, -7.5), torch.full((B, 10), -7.5, device=DEV), torch.full((B, 3), -7.5, device=DEV)]
+            smplh_bwd(lib, h, pose, pose2rot, hb[:B].contiguous(), transl[:B].contiguous(), body_only, B, gV[:B].contiguous(), gJ[:B].contiguous(),
+                      *grads)
+            outs.append(grads)
+        record(f"smplh backward {'folded' if body_only else 'full'} B={B} pose2rot={pose2rot}",
+               {k: (outs[0][i], outs[1][i]) for i, k in enumerate(("grad_pose", "grad_betas", "grad_transl"))})
     for lib, h in zip(libs, hs):
         lib.thmr_smplh_destroy(h)
 
@@ -202,6 +239,11 @@ def timing(libs, out, reps, iters, parent_tree, steps, warmup):
         betas = torch.randn(B, 10, generator=g).to(DEV)
         v, j = torch.empty(B, 6890, 3, device=DEV), torch.empty(B, 44, 3, device=DEV)
         row("thmr_smpl_forward", B, "us per call", windows({k: (lambda k=k: smpl_fwd(arms[k], hs[k], R, 0, betas, B, v, j)) for k in arms}))
+        if B == 64:
+            for k, lib in arms.items():
+                _cabi.check(lib.thmr_smpl_grad_reserve(hs[k]), lib=lib)
+            gp, gb = torch.empty_like(R), torch.empty_like(betas)
+            row("thmr_smpl_backward", B, "us per call", windows({k: (lambda k=k: smpl_bwd(arms[k], hs[k], R, 0, betas, B, v, j, gp, gb)) for k in arms}))
         for k, lib in arms.items():
             lib.thmr_smpl_destroy(hs[k])
     consts = make_synthetic_smplh(0)
@@ -215,6 +257,14 @@ def timing(libs, out, reps, iters, parent_tree, steps, warmup):
     for B in (1, 8, 64):
         row("thmr_smplh_forward full", B, "us per call", windows({k: (lambda k=k: smplh_fwd(arms[k], hs[k], Rh, 0, hb, None, 0, B, v, j)) for k in arms}))
         row("thmr_smplh_forward folded", B, "us per call", windows({k: (lambda k=k: smplh_fwd(arms[k], hs[k], R22, 0, hb, None, 1, B, v, j)) for k in arms}))
+    # the backward at 64 poses, the forward's last outputs as its output gradients
+    for k, lib in arms.items():
+        _cabi.check(lib.thmr_smplh_grad_reserve(hs[k], 3), lib=lib)
+    gb, gt = torch.empty_like(hb), torch.empty(64, 3, device=DEV)
+    for name, pose, body_only in (("full", Rh, 0), ("folded", R22, 1)):
+        gp = torch.empty_like(pose)
+        row(f"thmr_smplh_backward {name}", 64, "us per call",
+            windows({k: (lambda k=k: smplh_bwd(arms[k], hs[k], pose, 0, hb, None, body_only, 64, v, j, gp, gb, gt)) for k in arms}))
     for k, lib in arms.items():
         lib.thmr_smplh_destroy(hs[k])
 

@@ -217,7 +217,7 @@ def test_smpl_axis_angle_at_zero_and_tiny_poses(built_lib, cuda_dev):
     tests/test_gpu_val_loss_grad.py::_smpl_truth32 takes it (what the validation loss feeds the body model).  A dense vertex gradient is NOT
     added: measured on eight generic poses, gV ~ N(0, 1) puts grad_R of the pose2rot = 0 call, which no rotation kernel touches, at 1.0 ...
     5.4 times the reference's own distance per item (the skin-backward's fp32 sums over 6890 vertices), and that would decide this test.  SMPL-H is left out: both models reach the same two kernels
-    (launch_rodrigues, launch_rodrigues_backward in csrc/ops_abi.hip), and its float64 chain would be a second copy of this test."""
+    (launch_rodrigues, launch_rodrigues_backward through resolve_pose / finish_pose_grad in csrc/body_model_abi.hip), and its float64 chain would be a second copy of this test."""
     from tokenhmr_amd.smpl import SMPL
     from tokenhmr_amd.smpl_assets import make_synthetic_smpl
     smpl = make_synthetic_smpl(seed=0)

@@ -136,7 +136,7 @@ def test_gpu_smplh_backward_every_joint_path(built_lib, cuda_dev, body_only, dup
 
 
 # ------------------------------------------------------------------------------------------------ 3. batch independence, reproducibility
-# launch_smplh_backward_path (tokenhmr_amd/csrc/body_model.hip) walks the forward's poses per workgroup, smplh_poses_per_workgroup: 1 below
+# launch_smplh_backward (tokenhmr_amd/csrc/body_model.hip) walks the forward's poses per workgroup, smplh_poses_per_workgroup: 1 below
 # 64 poses, 2 from 64, 4 from 128, 8 from 256, with the bone matrices double-buffered on c & 1; the blend GEMM's reverse is ONE tile shape
 # (64 rows x 128) and ONE ksplit (38) at every size
 EDGE_BATCHES = (63, 64, 65, 127, 128, 129, 255, 256, 257)
@@ -183,6 +183,24 @@ def test_gpu_smplh_backward_after_an_unrelated_forward(built_lib, cuda_dev, edge
     torch.cuda.synchronize()
     for g, w in zip(got, want):
         assert torch.equal(g, w)
+
+
+def test_gpu_smplh_backward_paths_keep_their_workspaces_apart(built_lib, cuda_dev):
+    """One handle with BOTH paths reserved (two workspaces of one type, BodyGradWorkspace in csrc/abi_util.h): folded, full, folded again at
+    B = max_batch = 3 from axis-angle poses, so each path's own rotation-gradient scratch is in play.  Each result is byte for byte what
+    the same call gives on a fresh handle that reserved that path alone."""
+    c, B = _asset(), 3
+    ins = {body_only: _dev(cuda_dev, *_inputs(B, 81 + body_only, body_only, True)) for body_only in (True, False)}
+    both = _model(c, B, cuda_dev)
+    alone = {True: _model(c, B, cuda_dev, "folded"), False: _model(c, B, cuda_dev, "full")}
+    for step, body_only in enumerate((True, False, True)):
+        got = _backward(both, *ins[body_only], body_only, True)
+        want = _backward(alone[body_only], *ins[body_only], body_only, True)
+        torch.cuda.synchronize()
+        for name, g, w in zip(NAMES, got, want):
+            assert torch.equal(g.view(torch.int32), w.view(torch.int32)), f"call {step} ({'folded' if body_only else 'full'}) {name}"
+    for m in (both, *alone.values()):
+        m.close()
 
 
 # ------------------------------------------------------------------------------------------------ 4. NULL arms, guard bands, refusals

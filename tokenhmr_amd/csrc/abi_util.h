@@ -1,5 +1,6 @@
 // Host-side plumbing shared by the files that own C entry points of include/tokenhmr_hip.h: the engine units (engine.hip,
-// engine_weights.hip, engine_paths.hip: every call that takes a thmr_engine) and ops_abi.hip (the stateless operators).  Host only: no kernel includes this (SmplConsts::derive calls two launchers).
+// engine_weights.hip, engine_paths.hip: every call that takes a thmr_engine), ops_abi.hip (the stateless operators) and body_model_abi.hip
+// (the thmr_smpl / thmr_smplh handles).  Host only: no kernel includes this (the body-model structs call launchers of body_model.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +19,7 @@ int fail(thmr_engine* e, int code, const std::string& msg);
 int fail(int code, const std::string& msg);
 
 // HIP_OK (a HIP call) / LAUNCH_OK (a launch_* helper: 0, -1 = it refused the arguments, else the launch failed) return from the calling
-// function through THMR_FAIL(code, msg), which the including file defines: engine_state.h as fail(e, code, msg), ops_abi.hip as fail(code, msg).
+// function through THMR_FAIL(code, msg), which the including file defines: engine_state.h as fail(e, code, msg), ops_abi.hip and body_model_abi.hip as fail(code, msg).
 #define HIP_OK(call)                                                                          \
     do {                                                                                      \
         hipError_t _e = (call);                                                               \
@@ -75,6 +76,76 @@ struct SmplConsts {
         a.Jt = base + jt; a.Jsd = base + jsd; a.vt = base + vt; a.dirsT = base + dirs; a.W = base + w; a.J19 = base + j19;
         a.parents = iv + kParents; a.extra = iv + kExtra; a.jmap = iv + kJmap; a.update_hips = iv + kUpdateHips;
     }
+};
+
+// thmr_smplh's constant block, the same way (thmr_smplh_desc + what is derived from it once), and the per-batch scratch behind it
+struct SmplhConsts {
+    size_t vt = 0, sd = 0, pd = 0, jr = 0, w = 0, wb = 0, ints = 0, jt = 0, jsd = 0, dirs = 0, dirsb = 0;
+    size_t A = 0, xf = 0, rot = 0, vposed = 0;      // scratch: (B,52,12), (B,480), (B,52,9) for pose2rot, (B,20670)
+    // the int32 block (192 words): parents [0, 52) | extra_verts [64, 85) | fold [128, 180)
+    static constexpr int kParents = 0, kExtra = 64, kFold = 128;
+    static constexpr int HJ = THMR_SMPLH_NJ, HB = THMR_SMPLH_NBODY, HP = THMR_SMPLH_NP;
+
+    size_t lay(size_t off, size_t B) {          // returns the next free offset
+        auto take = [&](size_t& o, size_t n) { o = off; off = align64(off + n); };
+        take(vt, (size_t)NV * 3); take(sd, (size_t)NV * 30); take(pd, (size_t)HP * NV * 3); take(jr, (size_t)HJ * NV);
+        take(w, (size_t)NV * HJ); take(wb, (size_t)NV * THMR_SMPLH_NBODY_PAD);      // wb: the folded path's weights, derived
+        take(ints, 192); take(jt, HJ * 3); take(jsd, HJ * 30);
+        take(dirs, (size_t)NV * 3 * THMR_SMPLH_KX); take(dirsb, (size_t)NV * 3 * THMR_SMPLH_KXB);      // both derived
+        take(A, B * HJ * 12); take(xf, B * THMR_SMPLH_KX); take(rot, B * HJ * 9); take(vposed, B * NV * 3);
+        return off;
+    }
+    // par (52), ext (21) and fold (52) are the caller's validated host copies; the float arrays come from d as it says (k)
+    bool upload(float* base, const thmr_smplh_desc* d, hipMemcpyKind k, const int32_t* par, const int32_t* ext, const int32_t* fold) const {
+        int32_t* iv = reinterpret_cast<int32_t*>(base + ints);
+        auto cp = [](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { return hipMemcpy(dst, src, bytes, kind) == hipSuccess; };
+        return cp(base + vt, d->v_template, sizeof(float) * NV * 3, k) && cp(base + sd, d->shapedirs, sizeof(float) * NV * 30, k) &&
+               cp(base + pd, d->posedirs, sizeof(float) * HP * NV * 3, k) && cp(base + jr, d->J_regressor, sizeof(float) * HJ * NV, k) &&
+               cp(base + w, d->lbs_weights, sizeof(float) * NV * HJ, k) && cp(iv + kParents, par, sizeof(int32_t) * HJ, hipMemcpyHostToDevice) &&
+               cp(iv + kExtra, ext, sizeof(int32_t) * 21, hipMemcpyHostToDevice) && cp(iv + kFold, fold, sizeof(int32_t) * HJ, hipMemcpyHostToDevice);
+    }
+    int derive(float* base, hipStream_t st) const {     // Jt / Jsd, both dirs^T and the folded weights from what upload() copied
+        if (int r = launch_body_jreg(base + jr, base + vt, base + sd, base + jt, base + jsd, HJ, st)) return r;
+        if (int r = launch_body_build_dirs(base + sd, base + pd, base + dirs, (HJ - 1) * 9, THMR_SMPLH_KX, st)) return r;
+        if (int r = launch_body_build_dirs(base + sd, base + pd, base + dirsb, (HB - 1) * 9, THMR_SMPLH_KXB, st)) return r;
+        return launch_smplh_fold_weights(base + w, reinterpret_cast<const int32_t*>(base + ints) + kFold, base + wb, st);
+    }
+    void fill(SmplhArgs& a, float* base) const {        // the constant and scratch pointers of one launch_smplh call
+        const int32_t* iv = reinterpret_cast<const int32_t*>(base + ints);
+        a.Jt = base + jt; a.Jsd = base + jsd; a.vt = base + vt; a.dirsT = base + dirs; a.dirsT_body = base + dirsb; a.W = base + w; a.W_body = base + wb;
+        a.parents = iv + kParents; a.extra = iv + kExtra; a.fold = iv + kFold;
+        a.A = base + A; a.xf = base + xf; a.vposed = base + vposed;
+    }
+};
+
+// The backward's own allocation of a body-model handle (thmr_smpl: one; thmr_smplh: one per path): dirsT transposed (kx, 20672), g_vposed
+// (B, 20672), the bone-matrix partials (B, ga_per_item), the split-K planes (38, B, kx) and, for pose2rot, the rotation matrices' gradient
+// (B, nj, 9).  mem is null until reserve() has succeeded.
+struct BodyGradWorkspace {
+    float* mem = nullptr;
+    size_t dirs = 0, vp = 0, part = 0, planes = 0, rot = 0;
+
+    // 0, THMR_ERR_NOMEM (the allocation) or THMR_ERR_HIP (building dirsK); synchronises the device once.  The current device is the handle's.
+    int reserve(const float* dirsT, size_t kx, size_t ga_per_item, size_t nj, size_t max_batch) {
+        size_t off = 0;
+        auto take = [&](size_t& o, size_t n) { o = off; off = align64(off + n); };
+        take(dirs, kx * THMR_LBS_GK); take(vp, max_batch * THMR_LBS_GK); take(part, max_batch * ga_per_item);
+        take(planes, (size_t)THMR_LBS_GKSPLIT * max_batch * kx); take(rot, max_batch * nj * 9);
+        float* g = nullptr;
+        if (hipMalloc(&g, off * sizeof(float)) != hipSuccess) return THMR_ERR_NOMEM;
+        if (launch_body_build_dirs_k(dirsT, g + dirs, (int)kx, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(g);
+            return THMR_ERR_HIP;
+        }
+        mem = g;
+        return 0;
+    }
+    void fill(BodyGradArgs& g, const float* gV, const float* gJ, bool pose2rot, float* grad_pose, float* grad_betas, float* grad_transl) const {
+        g.gV = gV; g.gJ = gJ; g.dirsK = mem + dirs; g.gvp = mem + vp; g.gApart = mem + part; g.planes = mem + planes;
+        g.grad_rotmat = !grad_pose ? nullptr : (pose2rot ? mem + rot : grad_pose);      // axis-angle: finished from `rot` (finish_pose_grad)
+        g.grad_betas = grad_betas; g.grad_transl = grad_transl;
+    }
+    void release() { if (mem) (void)hipFree(mem); mem = nullptr; }
 };
 
 inline GemmArgs mk(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* resid, int64_t ldr,

@@ -841,6 +841,32 @@ void launch_lbs_prep(const LbsArgs& a, hipStream_t s) {
                        nullptr, a.A, a.xf, a.Jtr, a.cnt, nullptr);
 }
 
+// prep -> blend GEMM (the forward's, recomputed) -> skin-backward -> blend GEMM reversed -> chain-backward: five launches, SMPL's and either
+// SMPL-H path's alike.  `a` is LbsArgs or SmplhArgs; what only one model or path has comes as an argument, null for the other.  cg: crops per
+// skin workgroup, the forward's rule
+template <int NR, int NC, int NSP, int KX, Model M, bool WREG, class Args>
+int launch_body_backward(const Args& a, const BodyGradArgs& g, const float* W, const float* dirsT, const float* J19, const int32_t* jmap,
+                         const int32_t* update_hips, const int32_t* fold, float* Jtr, unsigned* cnt, const float* transl, int cg, hipStream_t s) {
+    const int B = a.B;
+    hipLaunchKernelGGL((prep_kernel<NR, NC, KX, M>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, transl, a.Jt, a.Jsd, a.parents, fold, a.A, a.xf,
+                       Jtr, cnt, nullptr);
+    if (hipGetLastError() != hipSuccess) return -2;
+    if (int r = launch_blend(a.xf, dirsT, a.vt, a.vposed, B, KX, s)) return r;
+    hipLaunchKernelGGL((lbs_skin_backward_kernel<NC, NSP, M, WREG>), dim3(SKB, (B + cg - 1) / cg), dim3(256), 0, s, a.vposed, W, a.A, J19, a.extra,
+                       jmap, update_hips, g.gV, g.gJ, g.gvp, g.gApart, B, cg);
+    if (hipGetLastError() != hipSuccess) return -2;
+    // gx (B x KX) = g_vposed (B x 20672) . dirsK^T: M = B is skinny and N = 224 / 480 is two / four tiles, so K is split THMR_LBS_GKSPLIT = 38
+    // ways (544 = 17 K tiles per slice) to put 76 / 152 workgroups per 64 crops on the chip; ONE tile shape (64 x 128) at every batch size,
+    // so no dispatch switch exists between sizes (every shape sums a slice's K in the same order anyway, gemm_f32.hip)
+    GemmArgs ga{};
+    ga.A = g.gvp; ga.lda = THMR_LBS_GK; ga.W = g.dirsK; ga.ldw = THMR_LBS_GK; ga.M = B; ga.N = KX; ga.K = THMR_LBS_GK;
+    ga.qscale = 1.f;
+    if (int r = launch_gemm_splitk(ga, 12, THMR_LBS_GKSPLIT, g.planes, s)) return r;
+    hipLaunchKernelGGL((lbs_chain_backward_kernel<NR, NC, KX, THMR_LBS_GKSPLIT, M>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, a.Jt, a.Jsd,
+                       a.parents, jmap, update_hips, fold, g.gJ, g.gApart, g.planes, g.grad_rotmat, g.grad_betas, g.grad_transl, B);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 }  // namespace
 
 int launch_body_build_dirs_k(const float* dirsT, float* dirsK, int kx, hipStream_t s) {
@@ -854,55 +880,20 @@ int launch_rodrigues_backward(const float* aa, const float* gR, float* gaa, int 
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// prep -> blend GEMM (the forward's, recomputed) -> skin-backward -> blend GEMM reversed -> chain-backward: five launches
-int launch_lbs_backward(const LbsArgs& a, const LbsGradArgs& g, hipStream_t s) {
-    const int B = a.B;
-    if (B < 1 || (!g.gV && !g.gJ) || (!g.grad_rotmat && !g.grad_betas)) return -1;
-    launch_lbs_prep(a, s);
-    if (int r = launch_blend(a.xf, a.dirsT, a.vt, a.vposed, B, THMR_LBS_KX, s)) return r;
-    const int cg = lbs_crops_per_pass(B);
-    hipLaunchKernelGGL((lbs_skin_backward_kernel<NJ, NJ, SMPL, true>), dim3(SKB, (B + cg - 1) / cg), dim3(256), 0, s, a.vposed, a.W, a.A, a.J19,
-                       a.extra, a.jmap, a.update_hips, g.gV, g.gJ, g.gvp, g.gApart, B, cg);
-    if (hipGetLastError() != hipSuccess) return -2;
-    // gx (B x 224) = g_vposed (B x 20672) . dirsK^T: M = B is skinny and N = 224 is two tiles, so K is split THMR_LBS_GKSPLIT = 38 ways (544
-    // = 17 K tiles per slice) to put 76 workgroups per 64 crops on the chip; ONE tile shape (64 x 128) at every batch size, so no
-    // dispatch switch exists between sizes (every shape sums a slice's K in the same order anyway, gemm_f32.hip)
-    GemmArgs ga{};
-    ga.A = g.gvp; ga.lda = THMR_LBS_GK; ga.W = g.dirsK; ga.ldw = THMR_LBS_GK; ga.M = B; ga.N = THMR_LBS_KX; ga.K = THMR_LBS_GK;
-    ga.qscale = 1.f;
-    if (int r = launch_gemm_splitk(ga, 12, THMR_LBS_GKSPLIT, g.planes, s)) return r;
-    hipLaunchKernelGGL((lbs_chain_backward_kernel<NJ, NJ, THMR_LBS_KX, THMR_LBS_GKSPLIT, SMPL>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas,
-                       a.Jt, a.Jsd, a.parents, a.jmap, a.update_hips, nullptr, g.gJ, g.gApart, g.planes, g.grad_rotmat, g.grad_betas, nullptr, B);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+int launch_lbs_backward(const LbsArgs& a, const BodyGradArgs& g, hipStream_t s) {
+    if (a.B < 1 || (!g.gV && !g.gJ) || (!g.grad_rotmat && !g.grad_betas)) return -1;
+    return launch_body_backward<NJ, NJ, NJ, THMR_LBS_KX, SMPL, true>(a, g, a.W, a.dirsT, a.J19, a.jmap, a.update_hips, nullptr, a.Jtr, a.cnt, nullptr,
+                                                                     lbs_crops_per_pass(a.B), s);
 }
 
-// SMPL-H's backward, either path: the same five launches on the same kernels.  The forward's crops-per-pass rule; the blend GEMM's reverse
-// keeps SMPL's tile (64 x 128) and split (THMR_LBS_GKSPLIT = 38 slices of 17 K tiles) for N = 224 and N = 480 alike: 76 / 152 workgroups
-// per 64 poses
-template <int NC, int NSP, int KX, bool WREG>
-int launch_smplh_backward_path(const SmplhArgs& a, const SmplhGradArgs& g, const float* W, const float* dirsT, hipStream_t s) {
-    const int B = a.B;
-    hipLaunchKernelGGL((prep_kernel<NJH, NC, KX, SMPLH>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, a.transl, a.Jt, a.Jsd, a.parents, a.fold,
-                       a.A, a.xf, nullptr, nullptr, nullptr);
-    if (hipGetLastError() != hipSuccess) return -2;
-    if (int r = launch_blend(a.xf, dirsT, a.vt, a.vposed, B, KX, s)) return r;
-    const int cg = smplh_poses_per_workgroup(B);
-    hipLaunchKernelGGL((lbs_skin_backward_kernel<NC, NSP, SMPLH, WREG>), dim3(SKB, (B + cg - 1) / cg), dim3(256), 0, s, a.vposed, W, a.A, nullptr,
-                       a.extra, nullptr, nullptr, g.gV, g.gJ, g.gvp, g.gApart, B, cg);
-    if (hipGetLastError() != hipSuccess) return -2;
-    GemmArgs ga{};
-    ga.A = g.gvp; ga.lda = THMR_LBS_GK; ga.W = g.dirsK; ga.ldw = THMR_LBS_GK; ga.M = B; ga.N = KX; ga.K = THMR_LBS_GK;
-    ga.qscale = 1.f;
-    if (int r = launch_gemm_splitk(ga, 12, THMR_LBS_GKSPLIT, g.planes, s)) return r;
-    hipLaunchKernelGGL((lbs_chain_backward_kernel<NJH, NC, KX, THMR_LBS_GKSPLIT, SMPLH>), dim3(B), dim3(128), 0, s, a.rotmat, a.betas, a.Jt,
-                       a.Jsd, a.parents, nullptr, nullptr, a.fold, g.gJ, g.gApart, g.planes, g.grad_rotmat, g.grad_betas, g.grad_transl, B);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int launch_smplh_backward(const SmplhArgs& a, const SmplhGradArgs& g, hipStream_t s) {
+int launch_smplh_backward(const SmplhArgs& a, const BodyGradArgs& g, hipStream_t s) {
     if (!a.rotmat || a.B < 1 || (!g.gV && !g.gJ) || (!g.grad_rotmat && !g.grad_betas && !g.grad_transl)) return -1;
-    if (a.body_only) return launch_smplh_backward_path<NBODY, THMR_SMPLH_NBODY_PAD, THMR_SMPLH_KXB, true>(a, g, a.W_body, a.dirsT_body, s);
-    return launch_smplh_backward_path<NJH, NJH, THMR_SMPLH_KX, false>(a, g, a.W, a.dirsT, s);
+    const int cg = smplh_poses_per_workgroup(a.B);
+    if (a.body_only)
+        return launch_body_backward<NJH, NBODY, THMR_SMPLH_NBODY_PAD, THMR_SMPLH_KXB, SMPLH, true>(a, g, a.W_body, a.dirsT_body, nullptr, nullptr, nullptr,
+                                                                                                   a.fold, nullptr, nullptr, a.transl, cg, s);
+    return launch_body_backward<NJH, NJH, NJH, THMR_SMPLH_KX, SMPLH, false>(a, g, a.W, a.dirsT, nullptr, nullptr, nullptr, a.fold, nullptr, nullptr,
+                                                                            a.transl, cg, s);
 }
 
 int launch_rodrigues(const float* aa, float* R, int n, hipStream_t s) {

@@ -571,14 +571,14 @@ int launch_lbs(const LbsArgs& a, hipStream_t s);
 // then skin-backward -> the blend GEMM's reverse (split-K, THMR_LBS_GKSPLIT planes) -> chain-backward.  In `a`: rotmat, betas, the
 // constants and the scratch of launch_lbs (verts, joints, kp2d, cam_t, xv unused).  g_vposed rows are padded to the GEMM's 32-deep K tile.
 constexpr int THMR_LBS_GK = 20672, THMR_LBS_GKSPLIT = 38, THMR_LBS_GA = 27 * 24 * 12;     // K = 32 * 2 * 17 * 19; bone-matrix partials per crop
-struct LbsGradArgs {
-    const float *gV, *gJ;             // (B,6890,3), (B,44,3): either may be null (zeros), not both
-    const float* dirsK;               // (224, 20672) K-contiguous: dirsT transposed, the two pad columns zero (launch_body_build_dirs_k)
-    float *gvp, *gApart, *planes;     // scratch: (B,20672), (B,27,288), (THMR_LBS_GKSPLIT,B,224)
-    float *grad_rotmat, *grad_betas;  // (B,24,3,3), (B,10): either may be null, not both
+struct BodyGradArgs {                 // SMPL and SMPL-H alike (nj = 24 / 52 or 22, kx = 224 / 480 or 224)
+    const float *gV, *gJ;             // (B,6890,3), (B,44 or 73,3): either may be null (zeros), not both
+    const float* dirsK;               // (kx, 20672) K-contiguous: the path's dirsT transposed, the two pad columns zero (launch_body_build_dirs_k)
+    float *gvp, *gApart, *planes;     // scratch: (B,20672), (B,THMR_LBS_GA / THMR_SMPLH_GA / _GA_BODY), (THMR_LBS_GKSPLIT,B,kx)
+    float *grad_rotmat, *grad_betas, *grad_transl;   // (B,nj,3,3), (B,10), (B,3): any may be null, not all; SMPL leaves grad_transl null
 };
 int launch_body_build_dirs_k(const float* dirsT, float* dirsK, int kx, hipStream_t s);
-int launch_lbs_backward(const LbsArgs& a, const LbsGradArgs& g, hipStream_t s);
+int launch_lbs_backward(const LbsArgs& a, const BodyGradArgs& g, hipStream_t s);
 int launch_rodrigues_backward(const float* aa, const float* gR, float* gaa, int n, hipStream_t s);
 // SMPL-H, 52 chain joints (22 body + 2 x 15 hand) and 73 output joints; the folded body-only path works on 22 joints, its weight table
 // padded to 24 columns.  dirsT (20670 x 480) = [shapedirs | posedirs (459) | 0]^T, dirsT_body (20670 x 224) = [shapedirs | the 189 body
@@ -602,10 +602,4 @@ int launch_smplh(const SmplhArgs& a, hipStream_t s);
 // forward's inputs, constants and scratch (verts, joints unused).  A workgroup's gA partial carries one row more than the path has bone
 // matrices: a row of ones, whose translation column is the vertices' share of grad_transl.
 constexpr int THMR_SMPLH_GA = 27 * (THMR_SMPLH_NJ + 1) * 12, THMR_SMPLH_GA_BODY = 27 * (THMR_SMPLH_NBODY + 1) * 12;
-struct SmplhGradArgs {
-    const float *gV, *gJ;             // (B,6890,3), (B,73,3): either may be null (zeros), not both
-    const float* dirsK;               // the path's dirsT transposed, (480 or 224, 20672) (launch_body_build_dirs_k)
-    float *gvp, *gApart, *planes;     // scratch: (B,20672), (B,THMR_SMPLH_GA or _GA_BODY), (THMR_LBS_GKSPLIT,B,480 or 224)
-    float *grad_rotmat, *grad_betas, *grad_transl;   // (B,52 or 22,3,3), (B,10), (B,3): any may be null, not all
-};
-int launch_smplh_backward(const SmplhArgs& a, const SmplhGradArgs& g, hipStream_t s);
+int launch_smplh_backward(const SmplhArgs& a, const BodyGradArgs& g, hipStream_t s);

@@ -1,10 +1,9 @@
-// The stateless C entry points of include/tokenhmr_hip.h: every thmr_op_* operator, the stand-alone body models (thmr_smpl_*, thmr_smplh_*),
-// the loss value and the evaluation metrics.  None of them touches a thmr_engine (engine.hip owns those calls): each validates its
+// The stateless C entry points of include/tokenhmr_hip.h: every thmr_op_* operator, the loss values and the evaluation metrics.  None of
+// them takes a handle (engine.hip owns the thmr_engine calls, body_model_abi.hip the thmr_smpl / thmr_smplh ones): each validates its
 // arguments before any HIP call and then launches what the engine launches, through the same launch_* functions (common.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <map>
 #include <mutex>
 
@@ -339,292 +338,6 @@ int thmr_op_decoder_init(const float* bias, const float* pos, float* x, int32_t 
     if (!bias || !pos || !x) return fail(THMR_ERR_INVALID, "decoder_init: null buffer");
     if (B <= 0 || E <= 0 || (int64_t)B * E > (int64_t)1 << 30) return fail(THMR_ERR_INVALID, "decoder_init: B, E >= 1 and B * E <= 2^30 are required");
     LAUNCH_OK(launch_decoder_init(bias, pos, x, B, E, static_cast<hipStream_t>(stream)));
-    return 0;
-}
-
-// ---- stand-alone SMPL model ----
-struct thmr_smpl {
-    float* mem = nullptr;
-    int max_batch = 0;
-    SmplConsts c;
-    size_t o_A, o_pf, o_Jtr, o_vposed, o_rot, o_joints, o_xv, o_cnt, total;
-    // the backward's own allocation (thmr_smpl_grad_reserve): dirs (224, 20672), g_vposed (B, 20672), the bone-matrix partials (B, 27, 288),
-    // the split-K planes (38, B, 224) and, for pose2rot, the rotation matrices' gradient (B, 24, 9)
-    float* gmem = nullptr;
-    int device = 0;
-    size_t g_dirs, g_vp, g_part, g_planes, g_rot;
-};
-
-int thmr_smpl_create(const thmr_smpl_desc* d, int32_t max_batch, int32_t device, thmr_smpl** out) {
-    if (!d || !out || max_batch < 1) return fail(THMR_ERR_INVALID, "bad argument");
-    *out = nullptr;
-    if (!d->v_template || !d->shapedirs || !d->posedirs || !d->J_regressor || !d->lbs_weights || !d->J19_regressor ||
-        !d->parents || !d->extra_verts || !d->joint_map)
-        return fail(THMR_ERR_INVALID, "thmr_smpl_desc has a null field");
-    HIP_OK(hipSetDevice(device));
-    thmr_smpl* m = new thmr_smpl();
-    m->max_batch = max_batch;
-    m->device = device;
-    size_t off = m->c.lay(0);
-    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
-    const size_t B = (size_t)max_batch;
-    m->o_A = take(B * NJ * 12); m->o_pf = take(B * THMR_LBS_XF); m->o_Jtr = take(B * NJ * 3); m->o_rot = take(B * NJ * 9);
-    m->o_vposed = take(B * NV * 3);
-    m->o_joints = take(B * 132);
-    m->o_xv = take(B * 63); m->o_cnt = take(B);
-    m->total = off;
-    if (hipMalloc(&m->mem, off * sizeof(float)) != hipSuccess) { delete m; return fail(THMR_ERR_NOMEM, "hipMalloc(smpl) failed"); }
-    if (hipMemset(m->mem + m->o_cnt, 0, B * sizeof(float)) != hipSuccess) { thmr_smpl_destroy(m); return fail(THMR_ERR_HIP, "hipMemset(lbs counters) failed"); }
-    // upload() only enqueues its copies: d's arrays and m->c.hips_host are read until the hipDeviceSynchronize() below
-    if (m->c.upload(m->mem, d, d->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, nullptr) != hipSuccess ||
-        m->c.derive(m->mem, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
-        thmr_smpl_destroy(m);
-        return fail(THMR_ERR_HIP, "SMPL constant upload failed");
-    }
-    *out = m;
-    return 0;
-}
-
-void thmr_smpl_destroy(thmr_smpl* m) {
-    if (!m) return;
-    if (m->mem) (void)hipFree(m->mem);
-    if (m->gmem) (void)hipFree(m->gmem);
-    delete m;
-}
-
-int thmr_smpl_forward(thmr_smpl* m, const float* pose, int32_t pose2rot, const float* betas, int32_t B, float* verts,
-                      float* joints, void* stream) {
-    if (!m || !pose || !betas || !verts) return fail(THMR_ERR_INVALID, "null argument");
-    if (B < 1 || B > m->max_batch) return fail(THMR_ERR_INVALID, "batch outside [1, max_batch]");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const float* rot = pose;
-    if (pose2rot) {
-        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * NJ, st));
-        rot = m->mem + m->o_rot;
-    }
-    LbsArgs a{};
-    m->c.fill(a, m->mem);
-    a.rotmat = rot; a.betas = betas;
-    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_pf; a.Jtr = m->mem + m->o_Jtr; a.vposed = m->mem + m->o_vposed; a.xv = m->mem + m->o_xv;
-    a.cnt = reinterpret_cast<unsigned*>(m->mem + m->o_cnt);
-    a.verts = verts; a.joints = joints ? joints : m->mem + m->o_joints;
-    a.focal_over_size = FOCAL / IMG; a.B = B;
-    LAUNCH_OK(launch_lbs(a, st));
-    return 0;
-}
-
-int thmr_smpl_grad_reserve(thmr_smpl* m) {
-    if (!m) return fail(THMR_ERR_INVALID, "smpl_grad_reserve: null handle");
-    if (m->gmem) return 0;
-    HIP_OK(hipSetDevice(m->device));
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
-    const size_t B = (size_t)m->max_batch;
-    m->g_dirs = take((size_t)THMR_LBS_KX * THMR_LBS_GK); m->g_vp = take(B * THMR_LBS_GK); m->g_part = take(B * THMR_LBS_GA);
-    m->g_planes = take((size_t)THMR_LBS_GKSPLIT * B * THMR_LBS_KX); m->g_rot = take(B * NJ * 9);
-    float* g = nullptr;
-    if (hipMalloc(&g, off * sizeof(float)) != hipSuccess) return fail(THMR_ERR_NOMEM, "hipMalloc(smpl backward workspace) failed");
-    if (launch_body_build_dirs_k(m->mem + m->c.dirs, g + m->g_dirs, THMR_LBS_KX, nullptr) != 0 || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(g);
-        return fail(THMR_ERR_HIP, "smpl_grad_reserve: building the transposed blend-shape matrix failed");
-    }
-    m->gmem = g;
-    return 0;
-}
-
-int thmr_smpl_backward(thmr_smpl* m, const float* pose, int32_t pose2rot, const float* betas, int32_t B, const float* grad_verts,
-                       const float* grad_joints, float* grad_pose, float* grad_betas, void* stream) {
-    if (!m || !pose || !betas) return fail(THMR_ERR_INVALID, "smpl_backward: null handle, pose or betas");
-    if (!grad_verts && !grad_joints) return fail(THMR_ERR_INVALID, "smpl_backward: grad_verts and grad_joints are both null");
-    if (!grad_pose && !grad_betas) return fail(THMR_ERR_INVALID, "smpl_backward: grad_pose and grad_betas are both null");
-    if (B < 1 || B > m->max_batch) return fail(THMR_ERR_INVALID, "smpl_backward: batch outside [1, max_batch]");
-    if (pose2rot != 0 && pose2rot != 1) return fail(THMR_ERR_INVALID, "smpl_backward: pose2rot is 0 or 1");
-    if (!m->gmem) return fail(THMR_ERR_INVALID, "smpl_backward: call thmr_smpl_grad_reserve on this handle first");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const float* rot = pose;
-    if (pose2rot) {
-        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * NJ, st));
-        rot = m->mem + m->o_rot;
-    }
-    LbsArgs a{};
-    m->c.fill(a, m->mem);
-    a.rotmat = rot; a.betas = betas;
-    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_pf; a.Jtr = m->mem + m->o_Jtr; a.vposed = m->mem + m->o_vposed;
-    a.cnt = reinterpret_cast<unsigned*>(m->mem + m->o_cnt);
-    a.B = B;
-    LbsGradArgs g{};
-    g.gV = grad_verts; g.gJ = grad_joints; g.dirsK = m->gmem + m->g_dirs;
-    g.gvp = m->gmem + m->g_vp; g.gApart = m->gmem + m->g_part; g.planes = m->gmem + m->g_planes;
-    g.grad_rotmat = !grad_pose ? nullptr : (pose2rot ? m->gmem + m->g_rot : grad_pose);
-    g.grad_betas = grad_betas;
-    LAUNCH_OK(launch_lbs_backward(a, g, st));
-    if (pose2rot && grad_pose) LAUNCH_OK(launch_rodrigues_backward(pose, m->gmem + m->g_rot, grad_pose, B * NJ, st));
-    return 0;
-}
-
-// ---- stand-alone SMPL-H model (csrc/body_model.hip) ----
-struct thmr_smplh {
-    float* mem = nullptr;
-    int max_batch = 0;
-    size_t o_vt, o_sd, o_pd, o_jr, o_w, o_wb, o_int, o_jt, o_jsd, o_dirs, o_dirsb, o_A, o_xf, o_vposed, o_rot, total;
-    // the backward's own allocations (thmr_smplh_grad_reserve), one per path, [0] full and [1] folded: the path's dirs transposed
-    // (kx, 20672), g_vposed (B, 20672), the gA partials (B, 27, (nj + 1) * 12), the split-K planes (38, B, kx) and, for pose2rot, the rotation
-    // matrices' gradient (B, nj, 9)
-    struct Grad { float* mem = nullptr; size_t dirs, vp, part, planes, rot; } grad[2];
-    int device = 0;
-};
-
-static void smplh_fill(const thmr_smplh* m, SmplhArgs& a) {
-    const int32_t* ints = reinterpret_cast<const int32_t*>(m->mem + m->o_int);
-    a.Jt = m->mem + m->o_jt; a.Jsd = m->mem + m->o_jsd;
-    a.parents = ints; a.extra = ints + 64; a.fold = ints + 128;
-    a.vt = m->mem + m->o_vt; a.dirsT = m->mem + m->o_dirs; a.dirsT_body = m->mem + m->o_dirsb; a.W = m->mem + m->o_w; a.W_body = m->mem + m->o_wb;
-    a.A = m->mem + m->o_A; a.xf = m->mem + m->o_xf; a.vposed = m->mem + m->o_vposed;
-}
-
-int thmr_smplh_create(const thmr_smplh_desc* d, int32_t max_batch, int32_t device, thmr_smplh** out) {
-    constexpr int HJ = THMR_SMPLH_NJ, HB = THMR_SMPLH_NBODY, HP = THMR_SMPLH_NP;
-    if (!d || !out || max_batch < 1) return fail(THMR_ERR_INVALID, "bad argument");
-    *out = nullptr;
-    if (!d->v_template || !d->shapedirs || !d->posedirs || !d->J_regressor || !d->lbs_weights || !d->parents || !d->extra_verts)
-        return fail(THMR_ERR_INVALID, "thmr_smplh_desc has a null field");
-    HIP_OK(hipSetDevice(device));
-    int32_t par[HJ], ext[21], fold[HJ];
-    if (d->on_device) {
-        HIP_OK(hipMemcpy(par, d->parents, sizeof(par), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(ext, d->extra_verts, sizeof(ext), hipMemcpyDeviceToHost));
-    } else {
-        memcpy(par, d->parents, sizeof(par));
-        memcpy(ext, d->extra_verts, sizeof(ext));
-    }
-    if (par[0] != -1) return fail(THMR_ERR_INVALID, "thmr_smplh_desc.parents[0] must be -1 (the root)");
-    for (int i = 1; i < HJ; ++i)
-        if (par[i] < 0 || par[i] >= i)
-            return fail(THMR_ERR_INVALID, "thmr_smplh_desc.parents[" + std::to_string(i) + "] = " + std::to_string(par[i]) + " is outside [0, " + std::to_string(i) + ")");
-    for (int k = 0; k < 21; ++k)
-        if (ext[k] < 0 || ext[k] >= NV)
-            return fail(THMR_ERR_INVALID, "thmr_smplh_desc.extra_verts[" + std::to_string(k) + "] = " + std::to_string(ext[k]) + " is outside [0, 6890)");
-    // fold[j]: the body joint whose bone matrix joint j has when every hand rotation is the identity.  parents[i] < i keeps the 22 body
-    // joints a chain of their own and gives fold[j] < 22 by induction (one ascending pass)
-    for (int j = 0; j < HJ; ++j) fold[j] = j < HB ? j : fold[par[j]];
-    thmr_smplh* m = new thmr_smplh();
-    m->max_batch = max_batch;
-    m->device = device;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
-    m->o_vt = take((size_t)NV * 3); m->o_sd = take((size_t)NV * 30); m->o_pd = take((size_t)HP * NV * 3);
-    m->o_jr = take((size_t)HJ * NV); m->o_w = take((size_t)NV * HJ); m->o_wb = take((size_t)NV * THMR_SMPLH_NBODY_PAD);
-    m->o_int = take(192); m->o_jt = take(HJ * 3); m->o_jsd = take(HJ * 30);
-    m->o_dirs = take((size_t)NV * 3 * THMR_SMPLH_KX); m->o_dirsb = take((size_t)NV * 3 * THMR_SMPLH_KXB);
-    const size_t B = (size_t)max_batch;
-    m->o_A = take(B * HJ * 12); m->o_xf = take(B * THMR_SMPLH_KX); m->o_rot = take(B * HJ * 9); m->o_vposed = take(B * NV * 3);
-    m->total = off;
-    if (hipMalloc(&m->mem, off * sizeof(float)) != hipSuccess) { delete m; return fail(THMR_ERR_NOMEM, "hipMalloc(smplh) failed"); }
-    const hipMemcpyKind k = d->on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    auto cp = [&](size_t o, const void* src, size_t bytes) { return hipMemcpy(m->mem + o, src, bytes, k) == hipSuccess; };
-    int32_t* ints = reinterpret_cast<int32_t*>(m->mem + m->o_int);      // parents [0, 52) | extra_verts [64, 85) | fold [128, 180)
-    bool ok = cp(m->o_vt, d->v_template, sizeof(float) * NV * 3) && cp(m->o_sd, d->shapedirs, sizeof(float) * NV * 30) &&
-              cp(m->o_pd, d->posedirs, sizeof(float) * (size_t)HP * NV * 3) && cp(m->o_jr, d->J_regressor, sizeof(float) * HJ * NV) &&
-              cp(m->o_w, d->lbs_weights, sizeof(float) * NV * HJ) &&
-              hipMemcpy(ints, par, sizeof(par), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(ints + 64, ext, sizeof(ext), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(ints + 128, fold, sizeof(fold), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok || launch_body_jreg(m->mem + m->o_jr, m->mem + m->o_vt, m->mem + m->o_sd, m->mem + m->o_jt, m->mem + m->o_jsd, HJ, nullptr) != 0 ||
-        launch_body_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirs, (HJ - 1) * 9, THMR_SMPLH_KX, nullptr) != 0 ||
-        launch_body_build_dirs(m->mem + m->o_sd, m->mem + m->o_pd, m->mem + m->o_dirsb, (HB - 1) * 9, THMR_SMPLH_KXB, nullptr) != 0 ||
-        launch_smplh_fold_weights(m->mem + m->o_w, ints + 128, m->mem + m->o_wb, nullptr) != 0 ||
-        hipDeviceSynchronize() != hipSuccess) {
-        thmr_smplh_destroy(m);
-        return fail(THMR_ERR_HIP, "SMPL-H constant upload failed");
-    }
-    *out = m;
-    return 0;
-}
-
-void thmr_smplh_destroy(thmr_smplh* m) {
-    if (!m) return;
-    if (m->mem) (void)hipFree(m->mem);
-    for (auto& g : m->grad)
-        if (g.mem) (void)hipFree(g.mem);
-    delete m;
-}
-
-int thmr_smplh_forward(thmr_smplh* m, const float* pose, int32_t pose2rot, const float* betas, const float* transl, int32_t body_only,
-                       int32_t B, float* verts, float* joints, void* stream) {
-    if (!m || !pose || !verts) return fail(THMR_ERR_INVALID, "smplh_forward: null argument");
-    if (B < 1 || B > m->max_batch) return fail(THMR_ERR_INVALID, "smplh_forward: batch outside [1, max_batch]");
-    if ((pose2rot != 0 && pose2rot != 1) || (body_only != 0 && body_only != 1))
-        return fail(THMR_ERR_INVALID, "smplh_forward: pose2rot and body_only are 0 or 1");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nj = body_only ? THMR_SMPLH_NBODY : THMR_SMPLH_NJ;
-    const float* rot = pose;
-    if (pose2rot) {
-        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * nj, st));
-        rot = m->mem + m->o_rot;
-    }
-    SmplhArgs a{};
-    smplh_fill(m, a);
-    a.rotmat = rot; a.betas = betas; a.transl = transl;
-    a.verts = verts; a.joints = joints; a.B = B; a.body_only = body_only;
-    LAUNCH_OK(launch_smplh(a, st));
-    return 0;
-}
-
-int thmr_smplh_grad_reserve(thmr_smplh* m, int32_t paths) {
-    if (!m) return fail(THMR_ERR_INVALID, "smplh_grad_reserve: null handle");
-    if (paths < 1 || paths > (THMR_SMPLH_GRAD_FOLDED | THMR_SMPLH_GRAD_FULL))
-        return fail(THMR_ERR_INVALID, "smplh_grad_reserve: paths is THMR_SMPLH_GRAD_FOLDED (1), THMR_SMPLH_GRAD_FULL (2) or both (3)");
-    HIP_OK(hipSetDevice(m->device));
-    for (int folded = 0; folded < 2; ++folded) {
-        thmr_smplh::Grad& g = m->grad[folded];
-        if (!(paths & (folded ? THMR_SMPLH_GRAD_FOLDED : THMR_SMPLH_GRAD_FULL)) || g.mem) continue;
-        const size_t B = (size_t)m->max_batch, kx = folded ? THMR_SMPLH_KXB : THMR_SMPLH_KX, nj = folded ? THMR_SMPLH_NBODY : THMR_SMPLH_NJ;
-        size_t off = 0;
-        auto take = [&](size_t n) { size_t o = off; off = align64(off + n); return o; };
-        g.dirs = take(kx * THMR_LBS_GK); g.vp = take(B * THMR_LBS_GK); g.part = take(B * (folded ? THMR_SMPLH_GA_BODY : THMR_SMPLH_GA));
-        g.planes = take((size_t)THMR_LBS_GKSPLIT * B * kx); g.rot = take(B * nj * 9);
-        float* mem = nullptr;
-        if (hipMalloc(&mem, off * sizeof(float)) != hipSuccess) return fail(THMR_ERR_NOMEM, "hipMalloc(smplh backward workspace) failed");
-        if (launch_body_build_dirs_k(m->mem + (folded ? m->o_dirsb : m->o_dirs), mem + g.dirs, (int)kx, nullptr) != 0 ||
-            hipDeviceSynchronize() != hipSuccess) {
-            (void)hipFree(mem);
-            return fail(THMR_ERR_HIP, "smplh_grad_reserve: building the transposed blend-shape matrix failed");
-        }
-        g.mem = mem;
-    }
-    return 0;
-}
-
-int thmr_smplh_backward(thmr_smplh* m, const float* pose, int32_t pose2rot, const float* betas, const float* transl, int32_t body_only,
-                        int32_t B, const float* grad_verts, const float* grad_joints, float* grad_pose, float* grad_betas,
-                        float* grad_transl, void* stream) {
-    if (!m || !pose) return fail(THMR_ERR_INVALID, "smplh_backward: null handle or pose");
-    if (!grad_verts && !grad_joints) return fail(THMR_ERR_INVALID, "smplh_backward: grad_verts and grad_joints are both null");
-    if (!grad_pose && !grad_betas && !grad_transl) return fail(THMR_ERR_INVALID, "smplh_backward: grad_pose, grad_betas and grad_transl are all null");
-    if (B < 1 || B > m->max_batch) return fail(THMR_ERR_INVALID, "smplh_backward: batch outside [1, max_batch]");
-    if ((pose2rot != 0 && pose2rot != 1) || (body_only != 0 && body_only != 1))
-        return fail(THMR_ERR_INVALID, "smplh_backward: pose2rot and body_only are 0 or 1");
-    const thmr_smplh::Grad& gm = m->grad[body_only];
-    if (!gm.mem)
-        return fail(THMR_ERR_INVALID, body_only ? "smplh_backward: the folded path was not reserved (thmr_smplh_grad_reserve with THMR_SMPLH_GRAD_FOLDED)"
-                                                : "smplh_backward: the full path was not reserved (thmr_smplh_grad_reserve with THMR_SMPLH_GRAD_FULL)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nj = body_only ? THMR_SMPLH_NBODY : THMR_SMPLH_NJ;
-    const float* rot = pose;
-    if (pose2rot) {
-        LAUNCH_OK(launch_rodrigues(pose, m->mem + m->o_rot, B * nj, st));
-        rot = m->mem + m->o_rot;
-    }
-    SmplhArgs a{};
-    smplh_fill(m, a);
-    a.rotmat = rot; a.betas = betas; a.transl = transl; a.B = B; a.body_only = body_only;
-    SmplhGradArgs g{};
-    g.gV = grad_verts; g.gJ = grad_joints; g.dirsK = gm.mem + gm.dirs;
-    g.gvp = gm.mem + gm.vp; g.gApart = gm.mem + gm.part; g.planes = gm.mem + gm.planes;
-    g.grad_rotmat = !grad_pose ? nullptr : (pose2rot ? gm.mem + gm.rot : grad_pose);
-    g.grad_betas = grad_betas; g.grad_transl = grad_transl;
-    LAUNCH_OK(launch_smplh_backward(a, g, st));
-    if (pose2rot && grad_pose) LAUNCH_OK(launch_rodrigues_backward(pose, gm.mem + gm.rot, grad_pose, B * nj, st));
     return 0;
 }
 
