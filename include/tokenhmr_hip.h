@@ -236,7 +236,7 @@ typedef struct thmr_vit_plan_desc {
     int32_t attn;               /* THMR_ATTN_* */
     int32_t bs_blk;             /* 1: fc1 writes fc2's operand in the row-blocked form (fc2 on the 128 x 256 stream) */
     int32_t part2_in_scratch;   /* 1: fc2's partial planes live in the scratch arena (3-4 crops), 0: behind the engine's operand buffers */
-    int32_t tile_opts;          /* GemmArgs::tile_opts of the split3 GEMMs (0 in the shipped library) */
+    int32_t tile_opts;          /* GemmArgs::tile_opts of the split3 GEMMs: bits 0-4 of csrc/gemm_split3_rule.h (0 in the shipped library) */
 } thmr_vit_plan_desc;
 int thmr_debug_vit_plan(const thmr_config* cfg, int32_t vit_gemm_mode, int32_t B, int32_t streams_available, thmr_vit_plan_desc* out);
 

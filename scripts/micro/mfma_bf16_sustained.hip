@@ -1,5 +1,5 @@
 // Micro-benchmark 9 (round 3): what rate does the bf16 matrix pipe SUSTAIN on this part, and what do the LDS reads of a GEMM loop cost it?
-// Context: the split3 GEMM (csrc/gemm_split.hip) keeps the MFMA pipe 74 % busy in cycles, but its counters show the shader clock at
+// Context: the split3 GEMM (csrc/gemm_split16.hip) keeps the MFMA pipe 74 % busy in cycles, but its counters show the shader clock at
 // ~1.53 GHz during the kernel (GRBM_GUI_ACTIVE / duration; the exact-fp32 kernel runs at ~2.16 GHz).  Is that a power ceiling of the
 // matrix pipe itself, or the price of the data movement around it?
 //   hipcc --offload-arch=gfx950 -O3 -o build_ab/mfma_bf16_sustained scripts/micro/mfma_bf16_sustained.hip && build_ab/mfma_bf16_sustained

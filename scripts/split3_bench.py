@@ -1,4 +1,4 @@
-"""fp32 GEMM on the bf16 matrix pipe (csrc/gemm_split.hip: three bf16 pieces per operand, six products, fp32 accumulate) beside the
+"""fp32 GEMM on the bf16 matrix pipe (csrc/gemm_split16.hip; format: csrc/split3_convert.hip: three bf16 pieces per operand, six products, fp32 accumulate) beside the
 exact-fp32 MFMA kernel, on the four ViT-H GEMM shapes of the hot path (vit.py:82-87,104-126) at B crops:
 per shape the time of both kernels with the epilogue the engine uses, the time of converting the A operand, the error of both against
 an fp64 product of the same operands (max over the output of |c - c64| / (|a| . |w|)), and fp32-equivalent TFLOP/s (2 M N K / t).

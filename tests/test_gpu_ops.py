@@ -165,7 +165,7 @@ def test_gemm_ring16(built_lib, cuda_dev, shape):
 
 
 def _split3_ref(x):
-    """numpy restatement of csrc/gemm_split.hip::split3_kernel: h = bf16_rne(x), m = bf16_rne(x - h), l = bf16_rne(x - h - m),
+    """numpy restatement of csrc/split3_convert.hip::split3_kernel: h = bf16_rne(x), m = bf16_rne(x - h), l = bf16_rne(x - h - m),
     laid out [R][K/8][3][8] (uint16 bit patterns)."""
     import numpy as np
 

@@ -340,7 +340,7 @@ def test_gemm_split3_pos_embed_strided(built_lib, cuda_dev, variant):
 #       -> N = 256 * 128 = 32768, K = 96; M = 37 (any M <= 128 is one row tile: 37 keeps it ragged and odd).
 #   persist/128x128/k<S> (the same rule on (tile, K slice) units): K % (32 S) == 0, K / S >= 96, ceil(M / 128) * (N / 128) * S >= 256;
 #       the reduce wants N % 4 == 0 -> S = 2: N = 128 * 128 = 16384, K = 192; S = 4: N = 64 * 128 = 8192, K = 384.
-#   tail (launch_split16_tiles_tail): N % 256 == 0; T = ceil(M / 128) * (N / 256) tiles, T % 8 == 0; an XCD's share q = T / 8 holds at least
+#   tail (split3_rule::choose, csrc/gemm_split3_rule.h): N % 256 == 0; T = ceil(M / 128) * (N / 256) tiles, T % 8 == 0; an XCD's share q = T / 8 holds at least
 #       one full round of 32 and a rest of 1 ... 16 -> q = 33, T = 264 -> M = 37 (one row tile), N = 264 * 256 = 67584, K = 32 is admitted
 #       by the rule; K = 64 is used (two K tiles: the double buffer turns over once).
 RULED_SHAPES = [("persist", (32, 65536, 64)), ("persist", (32, 65536 + 256, 64)),

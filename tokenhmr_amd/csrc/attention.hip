@@ -107,7 +107,7 @@ struct AttnDbg {
 // (crop, head) (batched path); (1, 4): three workgroups of 64 queries each, all staging the same K / V (few crops: B*16
 // workgroups cannot occupy 256 CUs); (1, 12): one 768-thread workgroup, 12 waves of 16 queries, K / V staged once.  Every query
 // is computed by the same instruction sequence in all of them, so the variants are bit-identical.
-// SPLIT: `out` is a split3 operand [B*192][1280/8][3][8] bf16 (gemm_split.hip) instead of fp32 — the same values, each written as three
+// SPLIT: `out` is a split3 operand [B*192][1280/8][3][8] bf16 (split3_convert.hip) instead of fp32 — the same values, each written as three
 // bf16 pieces (a lane's 4 consecutive d are the 8-byte half of the three chunks of one k-group)
 template <int QT, int NW, int DBG = 0, bool SPLIT = false>
 __global__ __launch_bounds__(NW * 64, NW == 12 ? 6 : 2) void vit_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, AttnDbg dbg) {

@@ -58,7 +58,7 @@ struct GemmArgs {
     // grid, copy sp reduces K slice [sp*K/ksplit, (sp+1)*K/ksplit) and stores its RAW partial tile to C + sp*M*ldc (C = the
     // partial-sum buffer part[ksplit][M][N], no epilogue); 0 / 1 = off.
     int ksplit;
-    // split3 GEMM only (gemm_split.hip): c_split != nullptr = the epilogue's result goes out as a split3 operand [M][N/8][3][8] bf16
+    // split3 GEMM only (split3_convert.hip): c_split != nullptr = the epilogue's result goes out as a split3 operand [M][N/8][3][8] bf16
     // (row stride 6 * ldcs bytes; N % 8 == 0) INSTEAD of fp32 C — the next GEMM's A operand without a conversion pass
     void* c_split;
     int64_t ldcs;
@@ -72,10 +72,11 @@ struct GemmArgs {
     //           fp32 tile: 7.5 of the 9.9 us fc1's epilogue costs per tile, profiles/r4e_split3_gemm_b64.jsonl); here 32 lanes write 512
     //           contiguous bytes.  Used for the one operand that only GEMM kernels touch: fc1's GELU output = fc2's A (vit.py:84-87).
     int a_blk, cs_blk;
-    // split3 GEMM, A/B only (experiments build: the engine sets it from THMR_SPLIT3_NARROW8=1 / THMR_SPLIT3_TAIL8=1 at thmr_create): bit 0 = the
-    // 128 x 128 tile on eight waves of 64 x 32 instead of four of 64 x 64, bit 1 = the half-tile tail likewise (round 6: measured slower /
-    // equal, gemm_split.hip); bit 2 = the 128 x 128 tile with round 5's TWO-stage K ring instead of three stages (THMR_SPLIT3_RING3=0);
-    // bit 3 = small 128 x 256 grids keep their copies spread over the K tile (THMR_SPLIT3_FRONT=0).  Same bits either way.
+    // split3 GEMM, A/B only (experiments build: split3_tile_knobs() turns the THMR_SPLIT3_* environment into these bits, for the engine at
+    // thmr_create and for every launch; names and measurements in gemm_split3_rule.h): bit 0 = the 128 x 128 tile on eight waves of 64 x 32
+    // instead of four of 64 x 64, bit 1 = the half-tile tail likewise (round 6: measured slower / equal); bit 2 = the 128 x 128 tile with
+    // round 5's TWO-stage K ring instead of three stages; bit 3 = small 128 x 256 grids keep their copies spread over the K tile; bit 4 = no
+    // half-tile tail.  Same result bits either way.
     int tile_opts;
 };
 
@@ -208,7 +209,7 @@ __device__ __forceinline__ float gemm_epilogue(const GemmArgs& a, float acc, flo
     return v;
 }
 
-// ---- "split3": an fp32 value as three bf16 pieces h + m + l (gemm_split.hip) ----
+// ---- "split3": an fp32 value as three bf16 pieces h + m + l (split3_convert.hip) ----
 // Round-to-nearest-even bf16 of x (any NaN -> 0x7fc0) in integer arithmetic: the form of the stand-alone converter (split3_kernel: weights
 // at load time, ops.split3) and the one the numpy restatement in the tests states.  The producers inside the hot path use split3_pair
 // below (hardware conversion), which differs from it on NaN payloads only.
@@ -381,12 +382,16 @@ int launch_gemm_splitk(const GemmArgs& a, int variant, int ksplit, float* part, 
 // applied by launch_splitk_epilogue / launch_splitk_resid_ln)
 int launch_gemm_ring(const GemmArgs& a, int epi, int ring, int ksplit, float* part, hipStream_t s);   // gemm_f32.hip
 int launch_gemm_ring16(const GemmArgs& a, int epi, hipStream_t s);                // gemm_f32.hip: small M on 16x16x4 tiles (64 x 48)
-// gemm_split.hip: fp32 -> three bf16 pieces ("split3"), and the GEMM over split3 operands on the bf16 matrix pipe (a.A / a.W = split3)
+// split3_convert.hip: fp32 -> three bf16 pieces ("split3")
 int launch_split3(const float* src, int64_t ld_src, void* dst, int64_t ld_dst, int64_t rows, int K, hipStream_t s);
+// gemm_split3_dispatch.hip: the GEMM over split3 operands on the bf16 matrix pipe (a.A / a.W = split3); the tile grid of a launch is
+// split3_rule::choose's (gemm_split3_rule.h)
 int launch_gemm_split3(const GemmArgs& a, int epi, int variant, hipStream_t s);
+struct Split3TileKnobs { int forced_tile, opts; };      // a variant id for every launch that asks for the rule (-1 = none); tile_opts bits
+Split3TileKnobs split3_tile_knobs();                    // experiments build: read from the environment; shipped: {-1, 0}
 // split-K on the split3 big tiles: ksplit copies of the tile grid in one launch, raw partial sums into part[ksplit][M][N]
 int launch_gemm_split3_splitk(const GemmArgs& a, int ksplit, float* part, hipStream_t s);
-// gemm_split_persist.hip: the same product on 256 persistent workgroups (a tile stream per CU, ragged last round split along K with the
+// the same product on 256 persistent workgroups (a tile stream per CU, ragged last round split along K with the
 // accumulators handed over through `ws`; bit-identical to launch_gemm_split3).  mode 0 = fp32 C; 1 / 2 = split3 output (a.c_split) through the
 // LDS transposition / through swapped operand roles.  ws: gemm_split3_persist_ws_bytes() of device memory zeroed once, one launch at a time.
 size_t gemm_split3_persist_ws_bytes();
@@ -403,10 +408,16 @@ void* gemm_split3_persist_op_ws(hipStream_t s);        // zeroed workspace per (
 // one workgroup per tile (wide = 128 x 256 on 8 waves, else 128 x 128 on 4; a.ksplit copies of the grid) or 256 persistent workgroups
 int launch_split16_tiles(const GemmArgs& a, int epi, int shape, hipStream_t s);      // shape 0: 128 x 256 / 8 waves, 1: 128 x 128 / 4 waves, 2: 128 x 128 / 8 waves
 int launch_split16_persist(const GemmArgs& a, int epi, void* ws, bool narrow, hipStream_t s);
-// the wide grid with its ragged last round as 128 x 128 half tiles; 0 launched, 1 = does not apply to this shape (nothing launched), < 0 error
-int launch_split16_tiles_tail(const GemmArgs& a, int epi, int cus, bool tail8, hipStream_t s);
-// small-M split3 GEMM (64x64 tiles, LDS-DMA ring, optional split-K into part[ksplit][M][N] without epilogue)
+// the wide grid with its ragged last round as 128 x 128 half tiles (q tiles per XCD, tail_from of them whole: gemm_split3_rule.h); 0 launched,
+// 1 = no instantiation for this epilogue (nothing launched), < 0 error
+int launch_split16_tiles_tail(const GemmArgs& a, int epi, int q, int tail_from, bool tail8, hipStream_t s);
+#ifdef THMR_EXPERIMENTS
+// gemm_split3_exp.hip: the 32x32x16 kernels that lost their A/B — the per-tile variants (ids 1, 3, 4, 20, 22, 31-37), the stream's modes 10-12,
+// and the small-M split3 GEMM (64x64 tiles, LDS-DMA ring, optional split-K into part[ksplit][M][N] without epilogue)
+int launch_split3_exp_tiles(const GemmArgs& a, int epi, int variant, hipStream_t s);
+int launch_split3_exp_persist(const GemmArgs& a, int epi, int mode, void* ws, hipStream_t s);
 int launch_gemm_split3_ring(const GemmArgs& a, int epi, int ksplit, float* part, hipStream_t s);
+#endif
 // LayerNorm (D = 1280) whose result is written as a split3 operand [rows][D/8][3][8] instead of fp32 (same arithmetic as launch_layernorm)
 int launch_layernorm_split3(const float* x, const float* g, const float* b, void* y_split, int rows, int D, float eps, hipStream_t s);
 int launch_gemm_skinny(const GemmArgs& a, int epi, hipStream_t s);                // gemm_skinny.hip

@@ -190,7 +190,7 @@ static VitKnobs read_knobs() {
     k.split3_small = on("THMR_SPLIT3_SMALL");
     if (on("THMR_SPLIT3_FC2_SPLIT")) k.split3_fc2_split = 1;
     num("THMR_SPLIT3_MIN_B", k.split3_min_b);
-    k.tile_opts = (on("THMR_SPLIT3_NARROW8") ? 1 : 0) | (on("THMR_SPLIT3_TAIL8") ? 2 : 0) | (off("THMR_SPLIT3_RING3") ? 4 : 0) | (off("THMR_SPLIT3_FRONT") ? 8 : 0);
+    k.tile_opts = split3_tile_knobs().opts;
     num("THMR_SPLIT3_PN_MASK", k.pn_mask);
     num("THMR_SPLIT3_PN_MAX", k.pn_max);
     num("THMR_SPLIT3_PN_FILL", k.pn_fill);

@@ -104,7 +104,7 @@ int vit_forward(thmr_engine* e, const float* img, int B, float* feats_out, hipSt
     // What the plan's three paths differ in.  Every step of a block is written ONCE below, in terms of this; which kernel a GEMM or the
     // attention runs, and every split factor, is the plan's.
     //   THMR_VIT_PATH_F32: exact-fp32 MFMA; the operands h and big live in the scratch arena.
-    //   THMR_VIT_PATH_SPLIT3: the four GEMMs as split3 products on the bf16 matrix pipe (csrc/gemm_split.hip); everything else — patch embed,
+    //   THMR_VIT_PATH_SPLIT3: the four GEMMs as split3 products on the bf16 matrix pipe (csrc/gemm_split16.hip); everything else — patch embed,
     //     LayerNorm arithmetic, epilogues — is the fp32 path's.  The LayerNorms, the attention kernel and fc1's GELU epilogue write their
     //     results directly as three bf16 pieces (hs [M][1280], bs [M][5120]): no conversion pass, no fp32 copy of those activations.
     //   THMR_VIT_PATH_SPLIT3_SMALL: EXPERIMENT (experiments library, THMR_SPLIT3_SMALL=1, off by default): a small-batch regime (up to six

@@ -114,7 +114,7 @@ struct thmr_engine : WeightLayout {
     char* split_w = nullptr;          // split3 weight copies: shared, reference-counted, among the engines of one weight arena (engine_weights.hip)
     bool split_w_counted = false;     // this engine holds a reference to the shared copy
     char* split_act = nullptr;
-    // tile streams of the split3 GEMMs (csrc/gemm_split_persist.hip): hand-over slabs + flags, allocated with the split3 weights on a
+    // tile streams of the split3 GEMMs (csrc/gemm_split3_dispatch.hip): hand-over slabs + flags, allocated with the split3 weights on a
     // 256-CU device; s3_persist: run-time state, 1 until a hand-over timeout was recovered (then the per-tile kernels, same results)
     void* s3_ws = nullptr;
     int s3_persist = 1;

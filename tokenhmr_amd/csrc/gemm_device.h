@@ -1,4 +1,4 @@
-// Device helpers shared by the GEMM kernels (gemm_f32.hip: exact-fp32 MFMA tiles; gemm_split.hip: fp32 operands split into three
+// Device helpers shared by the GEMM kernels (gemm_f32.hip: exact-fp32 MFMA tiles; gemm_split16.hip, gemm_split3_exp.hip: fp32 operands split into three
 // bf16 pieces): compile-time loops, the saddr-form LDS-DMA copy, the XCD-aware tile order and the fused-epilogue tile store.
 #pragma once
 #include "common.h"

@@ -1,7 +1,7 @@
 // The split3 GEMM on v_mfma_f32_16x16x32_bf16 — ONE kernel template for both decompositions: one workgroup per tile (any shape, split-K
-// copies of the grid) and 256 persistent workgroups over a tile stream (gemm_split_persist.hip's scheme: a ragged last round split along
+// copies of the grid) and 256 persistent workgroups over a tile stream (the scheme described in gemm_split3_exp.hip: a ragged last round split along
 // K, the accumulators handed from one XCD's workgroup to the next through memory).  Same operand format, same LDS stage image and
-// LDS-DMA staging as gemm_split.hip (vit.py:82-87,104-126 are the products it serves).
+// LDS-DMA staging as the 32x32x16 kernels (format: split3_convert.hip) (vit.py:82-87,104-126 are the products it serves).
 //
 // Why another MFMA shape (scripts/micro/mfma_bf16_sustained.hip, profiles/r4j_mfma_bf16_16x16x32_vs_32x32x16_sustained.log).  The split3
 // GEMMs run at the clock the part grants under 256 CUs of back-to-back bf16 MFMAs (1.4-1.5 GHz, HISTORY.md 11.2), so what counts is
@@ -24,10 +24,7 @@
 // so every read has at least a block (24 MFMAs + the SIMD partner's) to return and a copy a whole K tile to land.
 // Per output element K is summed tile by tile, per tile the six piece products in the order lh hl mm mh hm hh (each over its 32 k inside one
 // MFMA): the same for every instantiation, decomposition and batch size — bit-identical results among them (tests), and NOT bit-identical to
-// the 32x32x16 kernels of gemm_split.hip (another grouping of k inside the MFMA), which are kept in the experiments build for the A/B.
-#include <map>
-#include <mutex>
-
+// the 32x32x16 kernels of gemm_split3_exp.hip (another grouping of k inside the MFMA), which are kept in the experiments build for the A/B.
 #include "common.h"
 #include "gemm_device.h"
 #include "gemm_split_device.h"
@@ -125,7 +122,7 @@ constexpr int split16_lds_bytes() { return NST * (QBM * ROWB + WN * NI * 16 * RO
 // hypothesis that the four-wave form (one wave per SIMD, matrix pipe ~45 % busy at few crops: fc1 at 4 crops = 240 workgroups x 40 K tiles
 // in 62 us = 1.55 us per K tile against 0.7 us of MFMA issue, profiles/r6a_class_profile_small_batches.log) lacks a second wave per SIMD.
 // Measured, it does not: the eight-wave form is 3-6 % SLOWER per call at 3-8 crops and equal as the half-tile tail at 64
-// (profiles/r6d_ab_narrow8_or_tail8_*.json; launch_split3_tiles in gemm_split.hip keeps the four-wave form).  What the few-crop K loop
+// (profiles/r6d_ab_narrow8_or_tail8_*.json; the tile rule in gemm_split3_rule.h keeps the four-wave form).  What the few-crop K loop
 // waits for is its LDS-DMA copies — bytes in flight per CU, not waves (see the NST = 3 ring below).
 // NST = LDS stages of the K ring (round 6).  Two (every instantiation up to round 5): the copies of K tile t + 1 are issued during tile t - 1 and
 // waited for at tile t's barrier — ONE stage (48 KB of a 128 x 128 tile pair, 72 KB of a 128 x 256 one) in flight per CU for about one K-tile
@@ -795,17 +792,13 @@ int launch_split16_tiles(const GemmArgs& a, int epi, int shape, hipStream_t s) {
     }
 }
 
-// The 128 x 256 tiling with its ragged last round as 128 x 128 half tiles (gemm_split16_tail_kernel).  `cus` = compute units of the device.
-// Applies when the tile count divides by the 8 XCDs, an XCD's share q leaves 1 ... cus / 16 tiles after its full rounds and N % 256 == 0;
-// returns 1 (nothing launched) when it does not — the caller then launches the plain grid.
-int launch_split16_tiles_tail(const GemmArgs& a, int epi, int cus, bool tail8, hipStream_t s) {
-    if (a.ksplit > 1 || (a.N % 256) != 0 || cus < 16 || (cus % 8) != 0) return 1;
+// The 128 x 256 tiling with its ragged last round as 128 x 128 half tiles (gemm_split16_tail_kernel): q tiles per XCD, the first tf of them
+// whole.  Where that applies (N % 256 == 0, 8 q tiles, no split-K) and what q and tf are is the tile rule's (gemm_split3_rule.h); returns 1
+// (nothing launched) for an epilogue the tail kernel is not instantiated for.
+int launch_split16_tiles_tail(const GemmArgs& a, int epi, int q, int tf, bool tail8, hipStream_t s) {
     if (a.c_split != nullptr && epi == EPI_BIAS_RESID) return -1;
-    const int tiles_m = (a.M + QBM - 1) / QBM, tiles_n = a.N / 256, T = tiles_m * tiles_n, per = cus / 8;
-    if ((T % 8) != 0) return 1;
-    const int q = T / 8, full = q / per, rem = q - full * per;
-    if (full < 1 || rem < 1 || 2 * rem > per) return 1;
-    const int tf = full * per;
+    const int tiles_m = (a.M + QBM - 1) / QBM, tiles_n = a.N / 256;
+    if (a.ksplit > 1 || (a.N % 256) != 0 || tiles_m * tiles_n != 8 * q || tf < 0 || tf > q) return -1;      // not what the rule hands out
     if (a.a_blk) {
         if (epi == EPI_BIAS_RESID) return launch16_tail<EPI_BIAS_RESID, true>(a, tiles_m, tiles_n, q, tf, tail8, s);
         if (epi == EPI_NONE) return launch16_tail<EPI_NONE, true>(a, tiles_m, tiles_n, q, tf, tail8, s);

@@ -1,20 +1,8 @@
-// fp32 GEMM on the bf16 matrix pipe:  C[M,N] = epilogue(A[M,K] . W[N,K]^T)  with every fp32 operand carried as THREE bf16 pieces.
+// EXPERIMENTS build only (the shipped object of this file is empty): every split3 GEMM kernel on v_mfma_f32_32x32x16_bf16, six MFMAs per
+// 16 k (operand format: split3_convert.hip).  Round 4 replaced them with the 16x16x32 kernels of gemm_split16.hip (another grouping of k
+// inside the MFMA, so equal to rounding only); they stay for the A/B under their variant ids (op_gemm_variants.h).
 //
-// Why: exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, gemm_f32.hip) runs at 1/16 of the bf16 rate on gfx950 (157 vs 2500 TFLOP/s) and the
-// ViT GEMMs of the reference (tokenhmr/lib/models/backbones/vit.py:82-87,104-126) already sit at 0.93 of that peak.  An fp32 number
-// is the exact sum of three bf16 numbers, x = h + m + l (8 + 8 + 8 significand bits, each piece the round-to-nearest bf16 of what
-// the pieces before it left), a product of two bf16 is exact in fp32, and
-//     a.b = hh + (hm + mh) + (mm + hl + lh) + [ml + lm + ll]
-// where the bracket is below 2^-23 of |a.b| — the size of ONE fp32 rounding, which an fp32 dot product of length K commits K times.
-// So six v_mfma_f32_32x32x16_bf16 (fp32 accumulate) per 16 k give an fp32-grade product at 16 / 6 = 2.67 times the matrix rate.
-// This is NOT the product path of the engine (which stays on exact-fp32 MFMA and is bitwise an fmaf chain); it is an op of the C ABI
-// (thmr_op_split3 / thmr_op_gemm_split3) with its own parity tests against an fp64 reference, measured beside the fp32 kernel.
-//
-// Operand format ("split3"): X[R][K] fp32  ->  Xs[R][K/8][3][8] bf16: 8 consecutive k of a row as three adjacent 16-byte chunks
-// (piece h, m, l).  One chunk is exactly one lane's A / B operand of v_mfma_f32_32x32x16_bf16 (8 consecutive k of one row), a row
-// of a 32-deep K tile is 192 contiguous bytes, a row of the matrix is 6 K bytes.
-//
-// Kernel (gfx950): block tile (WM TM 32) x (WN TN 32), 8 waves of 64 x 64 on 128 x 256 by default, ONE workgroup per CU (two LDS
+// Per-tile kernel (gfx950): block tile (WM TM 32) x (WN TN 32), 8 waves of 64 x 64 on 128 x 256 by default, ONE workgroup per CU (two LDS
 // stages of 72 KB), two waves per SIMD.
 //   * staging: global_load_lds_dwordx4, saddr form (gemm_device.h); the LDS image of a stage is chunk-linear (row r = 12 chunks), and
 //     since the LDS side of the copy is lane-linear the bank swizzle is applied to the SOURCE: physical slot p of row r holds logical
@@ -28,106 +16,45 @@
 //       step 1 : MFMAs on fragment set 1; in their shadow the reads of tile kt+1's step-0 fragments and the copies of tile kt+2 into
 //                the buffer everybody just finished reading
 //     so a copy has a whole step (>= 24 MFMAs of this wave plus its SIMD partner's) to land and no fragment read is exposed.
-#include <cstdlib>
-#include <map>
-#include <mutex>
-
+//
+// Stream kernel: the same product (six v_mfma_f32_32x32x16_bf16 per 16 k) as PERSISTENT workgroups
+// over a tile stream.  Same 128 x 256 tile, same 8 waves of 64 x 64, same LDS image and same K loop as gemm_split3_kernel — and the same
+// bits: every output element is ONE accumulator chain over k = 0 ... K-1 in the same order, here too.  What changes is who runs which
+// part of which tile, and when (vit.py:82-87,104-126 are the four products this serves at 32 crops and more).
+//
+// Why (profiles/r3ah_split3_kernel_stats.csv): with one workgroup per tile and one workgroup per CU the four ViT GEMMs of a
+// 64-crop batch have 1440 / 480 / 1920 / 480 tiles for 256 CUs = 5.625 / 1.875 / 7.5 / 1.875 rounds — every one of them idles 6.25 % of
+// the chip in a ragged last round — and every tile pays its own pipeline fill (two K tiles of LDS-DMA latency) and its own epilogue with
+// nothing running underneath (fc1's GELU + split3 epilogue: 812 us against 716 us for the same tiles at the qkv rate).
+//
+// Decomposition.  256 workgroups (one per CU), workgroup b = (xcd = b & 7, lane = b >> 3).  Lane i of the eight XCDs owns the tile list
+// {i, i + 32, i + 64, ...} in the XCD-aware logical order of gemm_device.h::tile_coords — T_i tiles of nk K tiles each = T_i nk steps, cut into
+// eight equal consecutive step ranges, one per XCD.  So the 32 workgroups of an XCD walk 32 NEIGHBOURING tiles (8 x 4: the L2 footprint of
+// gemm_split3_kernel's dispatch order) in lockstep, all with the same range boundaries, and a tile that straddles a boundary is split ALONG K
+// between the same lane of two neighbouring XCDs.
+//
+// The K split keeps the association: the first part (k tiles [0, p)) is computed by XCD x as the FIRST thing it does, its raw fp32
+// accumulators go to a workspace slab (write-through stores) and a flag is published; XCD x + 1 runs the rest (k tiles [p, nk)) as the LAST
+// thing it does, starting from those accumulators instead of zeros — the accumulator chain merely travels through memory, bit for bit.
+// (Summing two independently accumulated halves would be another association: a crop's result would depend on which tile it lands in.)
+// The producer never waits for anybody and the consumer needs the slab some hundred microseconds after it was written, so the spin on the
+// flag is nominal; it is bounded all the same (error word, no hang).  Placement-independent: cdna_hip_programming.md Guideline 16, R1 form
+// (sc1 payload stores, every storing wave drains before a workgroup barrier, one lane publishes; sc1 loads on the consumer).
+//
+// Pipeline.  The two-stage LDS-DMA pipeline runs ACROSS tile boundaries: while the last K tiles of one tile are multiplied the first two K
+// tiles of the next one are already being copied, the epilogue's stores drain under the next tile's MFMAs, and the only exposed cost per
+// tile is the epilogue's own VALU work.  For a split3 OUTPUT (fc1: GELU, then three bf16 pieces per value, 8 consecutive columns per
+// 16-byte chunk) that requires an epilogue that leaves the stage buffers alone: MODE 2 multiplies with the operand ROLES swapped (the MFMA's
+// "A" is the weight fragment), which leaves a lane with one ROW of the output and 4-column groups in its registers, and eight
+// v_permlane32_swap per accumulator turn those into two groups of 8 consecutive columns — no LDS, no barrier.  MODE 1 keeps the LDS
+// transposition of gemm_split3_kernel (coalesced 384-byte row pieces) and pays a pipeline drain + refill per tile for it.
 #include "common.h"
 #include "gemm_device.h"
 #include "gemm_split_device.h"
 
+#ifdef THMR_EXPERIMENTS
+
 namespace {
-
-// X[rows][lds] fp32 -> split3 (row stride ldd fp32-equivalents = 6 ldd bytes); thread = 8 consecutive k of one row
-__global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ src, int64_t lds_, char* __restrict__ dst, int64_t ldd,
-                                                     int64_t rows, int kg) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * kg) return;
-    const int64_t r = idx / kg;
-    const int g = (int)(idx - r * kg);
-    const f32x4* p = reinterpret_cast<const f32x4*>(src + r * lds_ + (int64_t)g * 8);
-    const f32x4 v0 = p[0], v1 = p[1];
-    const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-    uint32_t h[8], m[8], l[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        h[e] = bf16_rne(x[e]);
-        const float r1 = x[e] - __uint_as_float(h[e] << 16);          // exact: the residual of a rounding fits the format
-        m[e] = bf16_rne(r1);
-        const float r2 = r1 - __uint_as_float(m[e] << 16);            // exact
-        l[e] = bf16_rne(r2);
-    }
-    u32x4* o = reinterpret_cast<u32x4*>(dst + r * ldd * 6 + (int64_t)g * 48);
-    o[0] = u32x4{h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
-    o[1] = u32x4{m[0] | (m[1] << 16), m[2] | (m[3] << 16), m[4] | (m[5] << 16), m[6] | (m[7] << 16)};
-    o[2] = u32x4{l[0] | (l[1] << 16), l[2] | (l[3] << 16), l[4] | (l[5] << 16), l[6] | (l[7] << 16)};
-}
-
-// nn.LayerNorm over D = NV * 256 (vit.py:136,144; the arithmetic of rowops.hip::ln_wave_kernel, one wave per row) with the result
-// written as a split3 operand: lane l holds 4 consecutive elements, so lanes 2 j and 2 j + 1 write the two 8-byte halves of the three
-// chunks of k-group j — the fp32 copy of the normalised row is never written.
-template <int NV>
-__global__ __launch_bounds__(256) void ln_split3_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, char* __restrict__ y, int rows, float eps) {
-    constexpr int D = NV * 256;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int lane = threadIdx.x & 63;
-    const float* xr = x + (int64_t)row * D;
-    f32x4 v[NV];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        v[i] = *reinterpret_cast<const f32x4*>(xr + (i * 64 + lane) * 4);
-        sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    }
-    const float mean = wave_sum(sum) * (1.0f / D);
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float d = v[i][e] - mean;
-            sq += d * d;
-        }
-    const float var = wave_sum(sq) * (1.0f / D);
-    const float rstd = 1.0f / sqrtf(var + eps);
-    // The row's split3 image (6 D bytes) is assembled in a wave-private LDS buffer and then written as WHOLE lines: 1024 contiguous
-    // bytes per store instruction.  Written straight from the registers a lane owns the 8-byte half of every third 16-byte chunk, and
-    // such partial-line stores run at 3.8 instead of 6.2 TB/s (scripts/micro/store_patterns.hip, profiles/r4c_store_patterns.jsonl:
-    // 24.8 vs 15.2 us for the 94 MB of a 64-crop operand).
-    __shared__ __attribute__((aligned(16))) char rowbuf[4][D * 6];
-    char* rb = rowbuf[threadIdx.x >> 6];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(beta + c);
-        uint32_t h[4], m[4], l[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float o = (v[i][e] - mean) * rstd * g[e] + b[e];
-            h[e] = bf16_rne(o);
-            const float r1 = o - __uint_as_float(h[e] << 16);
-            m[e] = bf16_rne(r1);
-            const float r2 = r1 - __uint_as_float(m[e] << 16);
-            l[e] = bf16_rne(r2);
-        }
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        char* o8 = rb + (c >> 3) * 48 + (lane & 1) * 8;
-        *reinterpret_cast<u32x2*>(o8) = u32x2{h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
-        *reinterpret_cast<u32x2*>(o8 + 16) = u32x2{m[0] | (m[1] << 16), m[2] | (m[3] << 16)};
-        *reinterpret_cast<u32x2*>(o8 + 32) = u32x2{l[0] | (l[1] << 16), l[2] | (l[3] << 16)};
-    }
-    // wave-private buffer: the wave's own LDS writes are visible to its reads in program order (no barrier)
-    char* yr = y + (int64_t)row * D * 6;
-    constexpr int NCH = D * 6 / 16;                      // 16-byte chunks of the row (480)
-#pragma unroll
-    for (int i = 0; i < (NCH + 63) / 64; ++i) {
-        const int ch = i * 64 + lane;
-        if (ch < NCH) *reinterpret_cast<u32x4*>(yr + ch * 16) = *reinterpret_cast<const u32x4*>(rb + ch * 16);
-    }
-}
 
 // ABL (timing-only experiments, results are garbage): bit0 no copies in the loop, bit1 no per-tile barrier, bit2 no fragment reads.
 // RS: step 0 issues one fragment read every RS-th MFMA (0 = as early as possible: one per MFMA).
@@ -310,7 +237,6 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_split3_kernel(GemmArgs a, i
     store_tile<TM, TN, EPI>(a, acc, bm0 + wm0, bn0 + wn0, lrow, lhalf);
 }
 
-#ifdef THMR_EXPERIMENTS      // kernels that lost their A/B (numbers in the comments): experiments build only
 // ---------------------------------------------------------------------------------------------------------------------
 // Small-M split3 GEMM (few crops: the engine's split3 mode up to six crops) — the ring kernel of gemm_f32.hip on split3 operands:
 // 64 x 64 tiles (2 x 2 waves of 32 x 32), ST-deep LDS ring of 24 KB stages fed by global_load_lds whose completion is tracked with
@@ -581,8 +507,6 @@ int launch_split3_wide(const GemmArgs& a, int epi, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-#endif  // THMR_EXPERIMENTS
-
 template <int WM, int WN, int TM, int TN>
 int launch_split3_cfg(const GemmArgs& a, int epi, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -610,126 +534,358 @@ int launch_split3_cfg(const GemmArgs& a, int epi, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+struct PersistWs {
+    float* part;        // [8 * PG] slabs of P_SLAB floats: slab (x, i) = first part of the tile shared by lane i of XCDs x and x + 1
+    unsigned* flag;     // [8 * PG] 0 / 1, set by the producer, cleared by the consumer (stream order separates launches); [8 * PG] = error word
+};
+
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+
+// MODE 2 epilogue: acc[mi][ni] holds the TRANSPOSED 32 x 32 tile (lane & 31 = row m of the output, registers = columns n:
+// n = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)).  v_permlane32_swap(X = reg j of column block g, Y = reg j of block g + 1) exchanges X's upper
+// 32 lanes with Y's lower 32: afterwards lanes 0-31 hold columns 8 h ... 8 h + 7 of blocks (g, g + 1) = 16 g' + 0 ... 7 and lanes 32-63
+// columns 16 g' + 8 ... 15.  Then bias + activation + split3 per value and three 16-byte stores (48 contiguous bytes) per group.
+template <int TM, int TN, int EPI>
+__device__ __forceinline__ void store_tile_split3_swapped(const GemmArgs& a, f32x16 (&acc)[TM][TN], int m0, int n0, int lane) {
+    const int lrow = lane & 31, lhalf = lane >> 5;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+        const int m = m0 + mi * 32 + lrow;
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) {
+#pragma unroll
+            for (int gp = 0; gp < 2; ++gp) {
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const u32x2_t sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[mi][ni][8 * gp + j]),
+                                                                       __float_as_uint(acc[mi][ni][8 * gp + 4 + j]), false, false);
+                    v[j] = __uint_as_float(sw.x);
+                    v[4 + j] = __uint_as_float(sw.y);
+                }
+                const int n = n0 + ni * 32 + gp * 16 + lhalf * 8;
+                float bias[8];
+                if constexpr (EPI != EPI_NONE) {
+                    const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.bias + n), b1 = *reinterpret_cast<const f32x4*>(a.bias + n + 4);
+                    bias[0] = b0[0]; bias[1] = b0[1]; bias[2] = b0[2]; bias[3] = b0[3];
+                    bias[4] = b1[0]; bias[5] = b1[1]; bias[6] = b1[2]; bias[7] = b1[3];
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) bias[u] = 0.f;
+                }
+                if constexpr (EPI == EPI_BIAS_GELU) {
+#pragma unroll
+                    for (int u = 0; u < 8; u += 2) {
+                        const f32x2 gl = gelu_erf2(f32x2{v[u] + bias[u], v[u + 1] + bias[u + 1]});
+                        v[u] = gl.x;
+                        v[u + 1] = gl.y;
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = gemm_epilogue<EPI>(a, v[u], bias[u], m, n + u);
+                }
+                uint32_t H[4], M[4], L[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) split3_pair(v[2 * u], v[2 * u + 1], H[u], M[u], L[u]);
+                char* cb = reinterpret_cast<char*>(a.c_split);
+                const bool blk = a.cs_blk != 0;
+                *reinterpret_cast<u32x4*>(cb + split3_chunk_off(a.ldcs, m, n >> 3, 0, blk)) = u32x4{H[0], H[1], H[2], H[3]};
+                *reinterpret_cast<u32x4*>(cb + split3_chunk_off(a.ldcs, m, n >> 3, 1, blk)) = u32x4{M[0], M[1], M[2], M[3]};
+                *reinterpret_cast<u32x4*>(cb + split3_chunk_off(a.ldcs, m, n >> 3, 2, blk)) = u32x4{L[0], L[1], L[2], L[3]};
+            }
+        }
+    }
+}
+
+// MODE: 0 = fp32 output (store_tile), pipeline continuous across tiles
+//       1 = split3 output through the LDS transposition (store_tile_split3): pipeline drained and refilled per tile
+//       2 = split3 output with swapped operand roles + v_permlane32_swap: pipeline continuous
+// ABLK: A is a row-blocked split3 operand (GemmArgs::a_blk; see gemm_split3_kernel)
+template <int EPI, int MODE, bool ABLK = false>
+__global__ __launch_bounds__(512) void gemm_split3_persist_kernel(GemmArgs a, int tiles_m, int tiles_n, PersistWs ws) {
+    constexpr int NW = 8, WN = 4, TM = 2, TN = 2;
+    constexpr bool SWAP = MODE == 2, CONT = MODE != 1;
+    constexpr int A_Q = PBM * SLOTS / 64, B_Q = PBN * SLOTS / 64;
+    constexpr int A_P = A_Q / NW, B_P = B_Q / NW, NP = A_P + B_P;      // 3 + 6 copies per wave and K tile
+    constexpr int A_STAGE = PBM * ROWB, B_STAGE = PBN * ROWB;
+    static_assert(2 * (A_STAGE + B_STAGE) <= 160 * 1024, "LDS");
+
+    __shared__ __attribute__((aligned(16))) char smem[2 * (A_STAGE + B_STAGE)];
+    char* As = smem;
+    char* Bs = smem + 2 * A_STAGE;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm0 = (wave / WN) * TM * 32;
+    const int wn0 = (wave % WN) * TN * 32;
+    const int lrow = lane & 31, lhalf = lane >> 5;
+
+    // ---- this workgroup's step range of its lane's tile list, as segments: [first part of a shared tile] [whole tiles] [rest of a shared tile]
+    const int xcd = blockIdx.x & 7, ln = blockIdx.x >> 3;
+    const int nk = a.K / SBK;
+    const int T = (tiles_m * tiles_n - ln + PG - 1) / PG;              // >= 8 (launcher)
+    const int S0 = (int)((int64_t)xcd * T * nk / 8), S1 = (int)((int64_t)(xcd + 1) * T * nk / 8);
+    const int j0 = S0 / nk, k0 = S0 - j0 * nk;
+    const int j1 = (S1 - 1) / nk, k1 = S1 - j1 * nk;
+    const int has_pre = k1 < nk ? 1 : 0, has_post = k0 > 0 ? 1 : 0;    // a range is >= nk steps long, so the two are never the same tile
+    const int jf0 = j0 + has_post, nfull = max(j1 - has_pre - jf0 + 1, 0);
+    const int nseg = has_pre + nfull + has_post;
+    // segment n -> tile j of the lane's list, K tiles [kb, ke), kind 0 whole / 1 first part (store the accumulators) / 2 rest (load them)
+    auto seg_of = [&](int n, int& j, int& kb, int& ke, int& kind) {
+        const int m = n - has_pre;
+        if (has_pre && n == 0) { j = j1; kb = 0; ke = k1; kind = 1; }
+        else if (m < nfull) { j = jf0 + m; kb = 0; ke = nk; kind = 0; }
+        else { j = j0; kb = k0; ke = nk; kind = 2; }
+    };
+    auto tile_of = [&](int j, int& bm0, int& bn0) {
+        int tm, tn;
+        tile_coords(tiles_m, tiles_n, j * PG + ln, tm, tn);
+        bm0 = __builtin_amdgcn_readfirstlane(tm * PBM);              // wave-uniform by construction (blockIdx and kernel arguments only)
+        bn0 = __builtin_amdgcn_readfirstlane(tn * PBN);
+    };
+
+    // ---- copies (M % 128 == 0 and N % 256 == 0: no clamping, the lane offsets are the same for every tile)
+    const int64_t arow = a.lda * 6, wrow = a.ldw * 6;
+    uint32_t Aoff[A_P], Woff[B_P];
+#pragma unroll
+    for (int i = 0; i < A_P; ++i) {
+        const int c = (wave + i * NW) * 64 + lane;
+        if constexpr (ABLK) {
+            Aoff[i] = (uint32_t)(c / 384) * (uint32_t)(a.lda * 192) + (uint32_t)(c % 384) * 16u;       // linear within a 32-row block
+        } else {
+            const int row = c / SLOTS, slot = c - row * SLOTS;
+            Aoff[i] = (uint32_t)row * (uint32_t)arow + (uint32_t)((slot + SLOTS - ((row >> 2) & 3)) % SLOTS) * 16u;
+        }
+    }
+    constexpr int A_KSTEP = ABLK ? SLOTS * 512 : ROWB;               // bytes a K tile advances the A source by
+#pragma unroll
+    for (int i = 0; i < B_P; ++i) {
+        const int c = (wave + i * NW) * 64 + lane, row = c / SLOTS, slot = c - row * SLOTS;
+        Woff[i] = (uint32_t)row * (uint32_t)wrow + (uint32_t)((slot + SLOTS - ((row >> 2) & 3)) % SLOTS) * 16u;
+    }
+    // fetch cursor: the K tile the NEXT copy brings in (two ahead of the multiply), wave-uniform
+    int fn = 0, fk = 0, fke = 0;
+    const char *fA = nullptr, *fW = nullptr;
+    auto fetch_seg = [&](int n) {
+        int j, kb, ke, kind, bm0, bn0;
+        seg_of(n, j, kb, ke, kind);
+        tile_of(j, bm0, bn0);
+        fk = kb;
+        fke = ke;
+        fA = reinterpret_cast<const char*>(a.A) + (int64_t)bm0 * arow + (int64_t)kb * A_KSTEP;
+        fW = reinterpret_cast<const char*>(a.W) + (int64_t)bn0 * wrow + (int64_t)kb * ROWB;
+    };
+    auto fetch_advance = [&]() {
+        if (fk + 1 < fke) { ++fk; fA += A_KSTEP; fW += ROWB; }
+        else if (CONT && fn + 1 < nseg) fetch_seg(++fn);
+        // else: past the end (of the segment in MODE 1): the last K tile is copied again, into a buffer nobody reads any more
+    };
+    auto dma_piece = [&](int buf, int p) {
+        if (p < A_P) dma16_saddr(fA, Aoff[p], lds_addr_b(As + buf * A_STAGE + (wave + p * NW) * 1024));
+        else dma16_saddr(fW, Woff[p - A_P], lds_addr_b(Bs + buf * B_STAGE + (wave + (p - A_P) * NW) * 1024));
+    };
+
+    // ---- fragments (as gemm_split3_kernel)
+    uint32_t fo[2][3];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc)
+            fo[s][pc] = (uint32_t)lrow * ROWB + (uint32_t)((((2 * s + lhalf) * 3 + pc) + ((lrow >> 2) & 3)) % SLOTS) * 16u;
+    const char* Afr = As + wm0 * ROWB;
+    const char* Bfr = Bs + wn0 * ROWB;
+    uint32_t foa[2][3];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) foa[s][pc] = ABLK ? (uint32_t)(((2 * s + lhalf) * 3 + pc) * 512 + lrow * 16) : fo[s][pc];
+    bf16x8 af[2][TM][3], bf[2][TN][3];
+    constexpr int NR = 3 * (TM + TN);
+    auto read_one = [&](int buf, int s, int set, int r) {
+        if (r < 3 * TM) {
+            const int mi = r / 3, pc = r % 3;
+            af[set][mi][pc] = *reinterpret_cast<const bf16x8*>(Afr + buf * A_STAGE + mi * 32 * ROWB + foa[s][pc]);
+        } else {
+            const int q = r - 3 * TM, ni = q / 3, pc = q % 3;
+            bf[set][ni][pc] = *reinterpret_cast<const bf16x8*>(Bfr + buf * B_STAGE + ni * 32 * ROWB + fo[s][pc]);
+        }
+    };
+    f32x16 acc[TM][TN];
+    constexpr int G = NPROD * TM * TN;
+    static_assert(NR + NP <= G, "tile too small for the staging interleave");
+
+    // one K tile out of buffer `buf` (gemm_split3_kernel's schedule): step 0's MFMAs over fragment set 0 with the reads of step 1's
+    // fragments in their shadow; barrier; step 1's MFMAs with the reads of the next K tile's first fragments (other buffer) and the copies of
+    // the K tile after next (into this buffer) in their shadow
+    auto ktile = [&](auto bufc) {
+        constexpr int buf = decltype(bufc){};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (s == 1) {
+                __builtin_amdgcn_sched_barrier(0);
+                dma_wait_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int p = 0; p < NPROD; ++p)
+#pragma unroll
+                for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                    for (int ni = 0; ni < TN; ++ni) {
+                        const int idx = (p * TM + mi) * TN + ni;
+                        if constexpr (SWAP)
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[s][ni][piece_w(p)], af[s][mi][piece_a(p)], acc[mi][ni], 0, 0, 0);
+                        else
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s][mi][piece_a(p)], bf[s][ni][piece_w(p)], acc[mi][ni], 0, 0, 0);
+                        bool any = false;
+                        if (s == 0) {
+                            if (idx < NR) { read_one(buf, 1, 1, idx); any = true; }
+                        } else {
+                            if (idx < NR) { read_one(buf ^ 1, 0, 0, idx); any = true; }
+                            else if (idx - NR < NP) { dma_piece(buf, idx - NR); any = true; }
+                        }
+                        if (any) __builtin_amdgcn_sched_barrier(0);
+                    }
+        }
+        fetch_advance();
+    };
+
+    // fill: the first two K tiles of segment n into buffers 0 / 1, tile 0's first fragments into set 0
+    auto fill = [&](int n) {
+        fetch_seg(n);
+        fn = n;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) dma_piece(0, p);
+        fetch_advance();
+#pragma unroll
+        for (int p = 0; p < NP; ++p) dma_piece(1, p);
+        fetch_advance();
+        dma_wait_barrier();
+#pragma unroll
+        for (int r = 0; r < NR; ++r) read_one(0, 0, 0, r);
+    };
+
+    static_assert((int64_t)P_NWG * P_SLAB * 4 < (int64_t(1) << 31), "slab offsets are 32-bit");
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(ws.part, 0, P_NWG * P_SLAB * 4, 0x00020000);
+    const uint32_t slab_lane = (uint32_t)(wave * (TM * TN * 4) * 1024 + lane * 16);     // a wave's 16 chunk rows of 1 KiB each
+    int pub_pending = 0;         // the slab's stores are issued; the flag goes out after the next K tile's barrier (every wave drained)
+    int par = 0;                 // buffer of the next K tile
+    auto after_tile = [&]() {
+        if (pub_pending) {
+            if (tid == 0) __hip_atomic_store(ws.flag + xcd * PG + ln, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pub_pending = 0;
+        }
+    };
+
+    if constexpr (CONT) fill(0);
+    for (int n = 0; n < nseg; ++n) {
+        int j, kb, ke, kind, bm0, bn0;
+        seg_of(n, j, kb, ke, kind);
+        tile_of(j, bm0, bn0);
+        if constexpr (!CONT) {
+            fill(n);
+            par = 0;
+        }
+        if (kind == 2) {
+            // the accumulators of k tiles [0, kb) from lane ln of the previous XCD: one thread polls one word, then sc1 loads
+            if (tid == 0) {
+                unsigned spins = 0;
+                unsigned* f = ws.flag + (xcd - 1) * PG + ln;
+                while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+                    __builtin_amdgcn_s_sleep(2);
+                    if (++spins > (1u << 22)) {                        // ~0.5 s: report, never hang
+                        __hip_atomic_store(ws.flag + P_NWG, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        break;
+                    }
+                }
+                __hip_atomic_store(f, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // re-armed for the next launch (stream order)
+            }
+            asm volatile("s_barrier" ::: "memory");
+            const uint32_t base = (uint32_t)((xcd - 1) * PG + ln) * (uint32_t)(P_SLAB * 4) + slab_lane;
+#pragma unroll
+            for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, base + (uint32_t)(((mi * TN + ni) * 4 + q) * 1024), 0, 16);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) acc[mi][ni][q * 4 + c] = __uint_as_float(r[c]);
+                    }
+        } else {
+#pragma unroll
+            for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
+        }
+
+        int cnt = ke - kb;
+        if (cnt > 0 && par) { ktile(IntC<1>{}); after_tile(); --cnt; par = 0; }
+        for (; cnt >= 2; cnt -= 2) {
+            ktile(IntC<0>{});
+            after_tile();
+            ktile(IntC<1>{});
+            after_tile();
+        }
+        if (cnt) { ktile(IntC<0>{}); after_tile(); par = 1; }
+
+        if (kind == 1) {
+            // raw accumulators -> slab (xcd, ln), write-through; published after the next K tile's barrier
+            const uint32_t base = (uint32_t)(xcd * PG + ln) * (uint32_t)(P_SLAB * 4) + slab_lane;
+#pragma unroll
+            for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const u32x4 v = {__float_as_uint(acc[mi][ni][q * 4]), __float_as_uint(acc[mi][ni][q * 4 + 1]),
+                                         __float_as_uint(acc[mi][ni][q * 4 + 2]), __float_as_uint(acc[mi][ni][q * 4 + 3])};
+                        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, base + (uint32_t)(((mi * TN + ni) * 4 + q) * 1024), 0, 16);
+                    }
+            pub_pending = 1;
+        } else if constexpr (MODE == 0) {
+            store_tile<TM, TN, EPI>(a, acc, bm0 + wm0, bn0 + wn0, lrow, lhalf);
+        } else if constexpr (MODE == 2) {
+            store_tile_split3_swapped<TM, TN, EPI>(a, acc, bm0 + wm0, bn0 + wn0, lane);
+        } else {
+            constexpr int WT = TN * 32 + 4;
+            static_assert(NW * TM * 32 * WT * 4 <= 2 * (A_STAGE + B_STAGE), "transpose tile does not fit the stage buffers");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the copies past the segment's end have landed
+            __syncthreads();                                           // every wave is done with the stage buffers
+            store_tile_split3<TM, TN, EPI>(a, acc, reinterpret_cast<float*>(smem) + wave * (TM * 32 * WT), bm0 + wm0, bn0 + wn0, lane);
+            __syncthreads();                                           // ... and with the transpose tiles, before the next fill
+        }
+        if constexpr (!CONT) {
+            if (pub_pending) {                                         // MODE 1 has no next K tile to hide behind: drain and publish now
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                after_tile();
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // no LDS-DMA write may outlive the workgroup's LDS allocation
+    if (pub_pending) {                                                 // (a first part is never a range's last segment; kept for safety)
+        __syncthreads();
+        after_tile();
+    }
+}
+
+template <int EPI, int MODE, bool ABLK = false>
+int launch_persist_cfg(const GemmArgs& a, const PersistWs& ws, hipStream_t s) {
+    const int tiles_m = a.M / PBM, tiles_n = a.N / PBN;
+    hipLaunchKernelGGL((gemm_split3_persist_kernel<EPI, MODE, ABLK>), dim3(P_NWG), dim3(512), 0, s, a, tiles_m, tiles_n, ws);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 }  // namespace
 
-int launch_split3(const float* src, int64_t ld_src, void* dst, int64_t ld_dst, int64_t rows, int K, hipStream_t s) {
-    if (rows <= 0 || K <= 0 || (K % 8) != 0 || (ld_src % 4) != 0 || (ld_dst % 8) != 0 || ld_dst < K) return -1;
-    const int kg = K / 8;
-    const int64_t n = rows * kg;
-    hipLaunchKernelGGL(split3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, ld_src, reinterpret_cast<char*>(dst), ld_dst,
-                       rows, kg);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int launch_layernorm_split3(const float* x, const float* g, const float* b, void* y_split, int rows, int D, float eps, hipStream_t s) {
-    if (rows <= 0 || D != 1280) return -1;
-    hipLaunchKernelGGL(ln_split3_kernel<5>, dim3((rows + 3) / 4), dim3(256), 0, s, x, g, b, reinterpret_cast<char*>(y_split), rows, eps);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-static int launch_split3_tiles(const GemmArgs& a, int epi, int variant, hipStream_t s);
-
-// a.A / a.W point at split3 operands (lda / ldw = their row strides in fp32-equivalents, i.e. 6 lda bytes); C, bias, resid are fp32.
-// variant: -1 = rule below   0 = 8 waves of 64x64 on 128x256   2 = 4 waves of 64x64 on 128x128   6 = 8 waves of 64x32 on 128x128   8 = 4 waves on 128x128, three-stage K ring   5 / 7 = 128x256 with the
-// ragged last round as half tiles on 4 / 8 waves   (experiments build: 1 = 4 waves of 64x128 on 128x256, ...)
-int launch_gemm_split3(const GemmArgs& a, int epi, int variant, hipStream_t s) {
-    if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % SBK) != 0 || (a.lda % 8) != 0 || (a.ldw % 8) != 0) return -1;
-    if (a.lda * 6 * 256 >= (int64_t(1) << 32) || a.ldw * 6 * 256 >= (int64_t(1) << 32)) return -1;     // 32-bit lane offsets within a tile
-    if (a.cs_out != nullptr || a.ksplit > 1) return -1;
-    if (a.c_split != nullptr && ((a.N % 8) != 0 || (a.ldcs % 8) != 0 || a.ldcs < a.N || epi == EPI_BIAS_RESID)) return -1;
-    return launch_split3_tiles(a, epi, variant, s);
-}
-
-// Split-K on the split3 big tiles (the mode's 3 ... 31 crops: the N = 1280 GEMMs have 25-240 tiles of 128 x 256): `ksplit` copies of the tile
-// grid in ONE launch, copy sp reducing K slice sp into part[sp][M][N] (raw fp32 partial tiles, no epilogue), summed in a fixed order by the
-// residual + LayerNorm kernel that follows proj / fc2 anyway.  Tile by the same rule over tiles * ksplit (bit-identical either way).
-int launch_gemm_split3_splitk(const GemmArgs& a0, int ksplit, float* part, hipStream_t s) {
-    if (ksplit < 2 || part == nullptr) return -1;
-    if (a0.M <= 0 || a0.N <= 0 || a0.K <= 0 || (a0.K % (SBK * ksplit)) != 0 || (a0.lda % 8) != 0 || (a0.ldw % 8) != 0) return -1;
-    if (a0.lda * 6 * 256 >= (int64_t(1) << 32) || a0.ldw * 6 * 256 >= (int64_t(1) << 32) || a0.cs_out != nullptr || a0.c_split != nullptr) return -1;
-    GemmArgs a = a0;
-    a.ksplit = ksplit;
-    a.C = part; a.ldc = a.N;
-    a.bias = nullptr; a.resid = nullptr; a.ldr = 0;
-    return launch_split3_tiles(a, EPI_NONE, -1, s);
-}
-
-// compute units of the current device (cached per device)
-static int device_cus() {
-    static std::mutex mu;
-    static std::map<int, int> cache;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(dev);
-    if (it != cache.end()) return it->second;
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cache[dev] = n;
-    return n;
-}
-
-static int launch_split3_tiles(const GemmArgs& a, int epi, int variant, hipStream_t s) {
-    static const int forced = [] { const char* e = thmr_knob("THMR_SPLIT3_TILE"); return e ? atoi(e) : -1; }();     // A/B knob (0 / 2)
-    if (variant < 0 && forced >= 0) variant = forced;
-    bool by_rule = false;
-    if (variant < 0) {
-        // the tiles are bit-identical (same K order per element), so the choice is purely a matter of time:
-        // 128 x 256 (8 waves) unless the whole grid of 128 x 128 tiles still fits ONE round of 256 CUs (the N = 1280 GEMMs at 16 crops, and
-        // at 7-8 crops with their K split two ways: 240 workgroups instead of 120).  A rounds x tile-time model over both shapes (a
-        // 128 x 128 tile takes 0.55 of a 128 x 256 one) was tried and is worse wherever it differs — 640 vs 669 crops/s at 15 crops, 665 vs
-        // 707 at 48: a partly filled last round of big tiles costs less than a full round (profiles/r3ae_split3_tile_rule_ab.log)
-        const long ks = a.ksplit > 1 ? a.ksplit : 1;
-        const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) * ks;
-        // round 6: the 128 x 128 tile on EIGHT waves of 64 x 32 (variant 6; gemm_split16.hip) was built to put two waves on every SIMD where
-        // that tile is what runs (few crops) and measured SLOWER than the four-wave form, same box, interleaved, whole path
-        // (profiles/r6d_ab_narrow8_*): +5.9 % per call at 4 crops (fc2 +0.19 ms, fc1 +0.14, qkv +0.12 of 8.1), +3.7 % at 8 (fc2 +0.42), +2.9 % at 3,
-        // +3.2 % at 5, +0.6 % at 16.  The few-crop K loop is not short of waves: it waits for its LDS-DMA copies (one 48 KB stage in flight per
-        // CU against a 1.5 us loaded round trip = the 1.55 us per K tile measured), and eight waves add barrier cost without adding bytes
-        // in flight.  Kept as variant 6 / THMR_SPLIT3_NARROW8=1 (bit-identical, tested).
-        static const bool narrow8 = [] { const char* e = thmr_knob("THMR_SPLIT3_NARROW8"); return e && e[0] == '1'; }();
-        // round 6: the four-wave 128 x 128 tile with a THREE-stage K ring (variant 8: two stages of copies in flight per CU)
-        static const int ring3 = [] { const char* e = thmr_knob("THMR_SPLIT3_RING3"); return e ? atoi(e) : -1; }();
-        const bool r3 = ring3 >= 0 ? ring3 != 0 : !(a.tile_opts & 4);
-        const bool n8 = narrow8 || (a.tile_opts & 1);
-        variant = t128 <= 256 ? (n8 ? (r3 ? 9 : 6) : r3 ? 8 : 2) : 0;
-        by_rule = true;
-    }
-    if ((by_rule && variant == 0) || variant == 5 || variant == 7) {
-        // round 5: the 128 x 256 grid with its ragged last round as 128 x 128 half tiles, where that applies (fc1 of a 64-crop batch: 1920
-        // tiles = 7.5 rounds of 256 CUs; gemm_split16.hip gemm_split16_tail_kernel).  Bit-identical to the plain grid.  THMR_SPLIT3_TAIL=0
-        // (experiments build) switches it off for the A/B; variant 5 asks for it explicitly and fails if the shape does not qualify.
-        static const bool tail_off = [] { const char* e = thmr_knob("THMR_SPLIT3_TAIL"); return e && e[0] == '0'; }();
-        // round 6: the half tiles on all eight waves (64 x 32 wave tiles) instead of four = variant 7 / THMR_SPLIT3_TAIL8=1: measured equal
-        // (fc1 +0.09 ms of 22.1 per 64-crop step, whole step +0.1 %: profiles/r6d_ab_narrow8_or_tail8_b64.json); round 5's form stays
-        static const bool tail8 = [] { const char* e = thmr_knob("THMR_SPLIT3_TAIL8"); return e && e[0] == '1'; }();
-        if (variant == 5 || variant == 7 || !tail_off) {
-            const int r = launch_split16_tiles_tail(a, epi, device_cus(), variant == 7 ? true : (tail8 || (a.tile_opts & 2)), s);
-            if (r <= 0) return r;                 // launched, or failed
-            if (variant == 5 || variant == 7) return -1;          // does not apply to this shape
-        }
-        if (variant == 5 || variant == 7) return -1;
-    }
-    if (by_rule && variant == 0 && !(a.tile_opts & 8) && !a.a_blk) {
-        // round 6: a 128 x 256 grid of at most two rounds issues every copy of a K tile right behind the barrier (gemm_split16.hip FRONT): its
-        // period is the weights' round trip, not the MFMA time.  Same box, per call (profiles/r6o_*): fc2 at 32 crops (240 tiles) 10.83 -> 10.38
-        // ms, fc1 / fc2 at 16 crops -0.12 / -0.16, fc1 at 8 -0.08; equal at 64 crops (not used there: more rounds); the three-stage
-        // 128 x 128 tile LOSES with it (12 copies in a row stall its one wave per SIMD: +0.1 ... +0.26 ms per class at 4 / 8 crops)
-        const long ks = a.ksplit > 1 ? a.ksplit : 1;
-        if ((long)((a.M + 127) / 128) * ((a.N + 255) / 256) * ks <= 512) variant = 10;
-    }
+// the one-workgroup-per-tile variants of launch_gemm_split3 that run a kernel of this file; -1 for any other id
+int launch_split3_exp_tiles(const GemmArgs& a, int epi, int variant, hipStream_t s) {
     switch (variant) {
-        // round 4: the product kernels multiply on v_mfma_f32_16x16x32_bf16 (gemm_split16.hip); the 32x32x16 kernels of this file are the
-        // experiments build's variants 20 / 22 (and 1, 4, 3x below) — another grouping of k inside the MFMA, so equal to rounding only
-        case 0: return launch_split16_tiles(a, epi, 0, s);
-        case 2: return launch_split16_tiles(a, epi, 1, s);
-        case 6: return launch_split16_tiles(a, epi, 2, s);
-        case 8: return launch_split16_tiles(a, epi, 3, s);
-        case 9: return launch_split16_tiles(a, epi, 4, s);
-        case 10: return launch_split16_tiles(a, epi, 5, s);
-        case 11: return launch_split16_tiles(a, epi, 6, s);
-#ifdef THMR_EXPERIMENTS
-        case 20: return launch_split3_cfg<2, 4, 2, 2>(a, epi, s);
+        case 20: return launch_split3_cfg<2, 4, 2, 2>(a, epi, s);      // the product tiles until round 4: 128 x 256 on 8 waves, 128 x 128 on 4
         case 22: return launch_split3_cfg<2, 2, 2, 2>(a, epi, s);
         case 1: return launch_split3_cfg<2, 2, 2, 4>(a, epi, s);    // 4 waves of 64 x 128: 3 % slower (r3v)
         case 4: return launch_split3_wide(a, epi, s);               // 256 x 256, 4 waves of 128 x 128, 16-deep stages: the same rate (r3ak)
@@ -740,12 +896,43 @@ static int launch_split3_tiles(const GemmArgs& a, int epi, int variant, hipStrea
         case 32: return epi == EPI_NONE ? launch_split3_abl<2, 4, 2, 2, 2, 0>(a, s) : -1;
         case 34: return epi == EPI_NONE ? launch_split3_abl<2, 4, 2, 2, 4, 0>(a, s) : -1;
         case 37: return epi == EPI_NONE ? launch_split3_abl<2, 4, 2, 2, 7, 0>(a, s) : -1;
-#endif
         default: return -1;
     }
 }
 
-#ifdef THMR_EXPERIMENTS
+// modes 10 (fp32 output) / 11 (split3 output through LDS) / 12 (split3 output, swapped roles) of launch_gemm_split3_persist, which has
+// checked gemm_split3_persist_ok(a) and the workspace
+int launch_split3_exp_persist(const GemmArgs& a, int epi, int mode, void* ws_mem, hipStream_t s) {
+    mode -= 10;
+    if ((mode == 0) != (a.c_split == nullptr) || mode < 0 || mode > 2 || (a.M % PBM) != 0) return -1;      // (the 32x32x16 kernels: whole row tiles only)
+    // the 32x32x16 kernels of this file keep round 4's 0 / 1 flags (set by the producer, cleared by the consumer); the product kernel leaves
+    // epochs in them: zero the flag words (not the control words) first
+    if (hipMemsetAsync(reinterpret_cast<char*>(ws_mem) + (size_t)P_NWG * P_SLAB * 4, 0, P_NWG * sizeof(unsigned), s) != hipSuccess) return -2;
+    if (a.c_split != nullptr && epi == EPI_BIAS_RESID) return -1;
+    PersistWs ws;
+    ws.part = reinterpret_cast<float*>(ws_mem);
+    ws.flag = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws_mem) + (size_t)P_NWG * P_SLAB * 4);
+    if (a.a_blk) {      // row-blocked A (fc2's operand): bias + residual, or no epilogue
+        if (mode != 0) return -1;
+        if (epi == EPI_BIAS_RESID) return launch_persist_cfg<EPI_BIAS_RESID, 0, true>(a, ws, s);
+        if (epi == EPI_NONE) return launch_persist_cfg<EPI_NONE, 0, true>(a, ws, s);
+        return -1;
+    }
+#define THMR_PERSIST_CASE(E, MD) \
+    if (epi == E && mode == MD) return launch_persist_cfg<E, MD>(a, ws, s);
+    THMR_PERSIST_CASE(EPI_NONE, 0)
+    THMR_PERSIST_CASE(EPI_BIAS, 0)
+    THMR_PERSIST_CASE(EPI_BIAS_RESID, 0)
+    THMR_PERSIST_CASE(EPI_BIAS_QSCALE, 0)
+    THMR_PERSIST_CASE(EPI_BIAS_GELU, 0)
+    THMR_PERSIST_CASE(EPI_BIAS_GELU, 2)
+    THMR_PERSIST_CASE(EPI_NONE, 2)
+    THMR_PERSIST_CASE(EPI_BIAS_GELU, 1)      // split3 output through the LDS transposition: 796 vs 784 us on the fc1 shape (profiles/r4a_split3_gemm_persistent_b64.jsonl)
+    THMR_PERSIST_CASE(EPI_NONE, 1)
+#undef THMR_PERSIST_CASE
+    return -1;
+}
+
 // small-M split3 GEMM: 64x64 tiles on a 4-deep LDS-DMA ring; ksplit > 1 writes raw partial sums to part[ksplit][M][N] and applies NO
 // epilogue (launch_splitk_resid_ln / launch_splitk_epilogue then do)
 int launch_gemm_split3_ring(const GemmArgs& a, int epi, int ksplit, float* part, hipStream_t s) {
@@ -775,4 +962,5 @@ int launch_gemm_split3_ring(const GemmArgs& a, int epi, int ksplit, float* part,
 #undef THMR_SRING_CASE
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+
 #endif  // THMR_EXPERIMENTS

@@ -1,5 +1,6 @@
-// Device helpers shared by the split3 GEMM kernels (gemm_split.hip: one workgroup per tile; gemm_split_persist.hip: persistent workgroups
-// over a tile stream): the operand-format constants, the transposing split3 epilogue and the order of the six piece products.
+// Shared by the split3 GEMM files (gemm_split16.hip: the product kernels; gemm_split3_exp.hip: the 32x32x16 kernels of the experiments
+// build; gemm_split3_dispatch.hip: their host side): the operand-format constants (format: split3_convert.hip), the geometry of the tile
+// stream's workspace, the transposing split3 epilogue and the order of the six piece products.
 #pragma once
 #include "common.h"
 #include "gemm_device.h"
@@ -12,6 +13,12 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int SBK = 32;                     // K tile, fp32 elements
 constexpr int SLOTS = SBK / 8 * 3;          // 16-byte chunks per row and K tile
 constexpr int ROWB = SLOTS * 16;            // 192 bytes
+
+// the tile stream (256 persistent workgroups; gemm_split3_persist_ws_bytes / _ok and the stream kernels)
+constexpr int PG = 32;                                     // stream lanes (workgroups) per XCD
+constexpr int PBM = 128, PBN = 256;
+constexpr int P_SLAB = PBM * PBN;                          // floats of one raw accumulator tile (128 KB)
+constexpr int P_NWG = 8 * PG;
 
 template <int N>
 __device__ __forceinline__ void wait_vm_barrier() {

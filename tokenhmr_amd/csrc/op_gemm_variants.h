@@ -43,7 +43,7 @@ constexpr auto kOpGemmF32 = [] {
     return t;
 }();
 
-// ---- thmr_op_gemm_split3 / ..._out_split3: split3 operands (gemm_split16.hip; experiments: gemm_split.hip, gemm_split_persist.hip)
+// ---- thmr_op_gemm_split3 / ..._out_split3: split3 operands (gemm_split16.hip; experiments: gemm_split3_exp.hip)
 constexpr OpGemmRow kOpGemmS3[] = {
     //code kind                      sub ks  fp32 C    split3 C    exp    blk_a
     {-1,  THMR_GEMM_S3_TILE,          -1, 1, {kS3,      kS3Out},    false, false},     // the engine's rule

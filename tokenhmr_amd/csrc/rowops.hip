@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(GemmArgs a, const 
 //   x_new = resid + (sum_s part[s] + bias);  y = LayerNorm(x_new)        one wave per row, D = NV*256
 // ST > 0: the split factor is a compile-time constant, so all ST*NV partial loads of a lane are issued before the first add
 // (the engine's factor 4: 8.8 -> ~5 us at 192 rows, where the kernel is one dependent-load chain per wave); ST = 0: runtime S.
-// SPLIT: y is a split3 operand [rows][D/8][3][8] bf16 (gemm_split.hip) instead of fp32 — the same values as three bf16 pieces each
+// SPLIT: y is a split3 operand [rows][D/8][3][8] bf16 (split3_convert.hip) instead of fp32 — the same values as three bf16 pieces each
 template <int NV, int ST, bool SPLIT = false>
 __global__ __launch_bounds__(256) void splitk_resid_ln_kernel(const float* __restrict__ part, int S, int64_t mn,
                                                               const float* __restrict__ bias, const float* resid, float* xout,

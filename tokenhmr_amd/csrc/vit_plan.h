@@ -5,8 +5,9 @@
 //     sizes, so a crop's result does not depend on the batch it rides in within a range (batch invariance).
 //   * The DECOMPOSITION (one workgroup per tile, the 128 x 256 tile stream, the 128 x 128 tile stream, split K through the stream) decides
 //     only time: all are bit-identical for one split factor.
-// Every batch-size or tile-count threshold of that dispatch lives here; the shape predicates stay with the kernels
-// (gemm_split_persist.hip), and what a launcher decides internally (launch_gemm's cost model, launch_gemm_split3's mixed grid) is its own.
+// Every batch-size or tile-count threshold of that dispatch lives here; the shape predicates stay with the launchers
+// (gemm_split3_dispatch.hip).  Which tile grid a one-workgroup-per-tile split3 launch then runs on is the second rule, a pure host function
+// as well: split3_rule::choose in gemm_split3_rule.h.  (launch_gemm's cost model for the exact-fp32 kernels is still its own.)
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -58,8 +59,8 @@ struct VitKnobs {
     bool split3_small = false;        // THMR_SPLIT3_SMALL=1: the split3 mode also serves up to six crops (ring kernel on split3 operands) — measured SLOWER
     int split3_fc2_split = kSplit3Fc2Split;   // THMR_SPLIT3_FC2_SPLIT=1: fc2 of the split3 mode unsplit from 5 crops on
     int split3_min_b = 0;             // THMR_SPLIT3_MIN_B=<n>: the smallest batch the split3 mode serves (0 = kSplit3LowMinB)
-    int tile_opts = 0;                // GemmArgs::tile_opts of the split3 GEMMs (THMR_SPLIT3_NARROW8=1 -> 1, THMR_SPLIT3_TAIL8=1 -> 2, THMR_SPLIT3_RING3=0 -> 4, THMR_SPLIT3_FRONT=0 -> 8)
-    // persistent split3 GEMM = the 128 x 256 tile stream (csrc/gemm_split_persist.hip; bit-identical to the one-workgroup-per-tile kernel, so
+    int tile_opts = 0;                // GemmArgs::tile_opts of the split3 GEMMs (the bits of gemm_split3_rule.h, from split3_tile_knobs())
+    // persistent split3 GEMM = the 128 x 256 tile stream (csrc/gemm_split16.hip; bit-identical to the one-workgroup-per-tile kernel, so
     // purely a matter of time).  THMR_SPLIT3_PERSIST=0: no stream of either width (the engine's run-time copy also drops to 0 after a
     // recovered hand-over timeout)
     int persist = 1;
@@ -106,7 +107,7 @@ using VitPlan = thmr_vit_plan_desc;   // the plan IS what thmr_debug_vit_plan re
 namespace vit_plan_detail {
 
 inline GemmChoice choice(int kind, int ksplit = 1) { return GemmChoice{kind, ksplit}; }
-// shape-only GemmArgs for the predicates of gemm_split_persist.hip: row-major operands of leading dimension K, optional split3 output
+// shape-only GemmArgs for the predicates of gemm_split3_dispatch.hip: row-major operands of leading dimension K, optional split3 output
 inline GemmArgs shape(int M, int N, int K, int ksplit = 1, int ldcs = 0) {
     GemmArgs a{};
     a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldc = N; a.ldr = N; a.ldcs = ldcs; a.ksplit = ksplit;

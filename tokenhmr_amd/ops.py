@@ -124,7 +124,7 @@ SPLIT3_VARIANT = {"auto": -1, "128x256/w8": 0, "tail": 5,        # tail: the 128
                       # s3: the four-wave tile with a three-stage K ring
                                    # round 6: the 128x128 tile / the tail's half tiles on eight waves of 64x32 (measured slower / equal: not the rule's choice)
                    "128x256/w4": 1, "128x128/w4": 2, "256x256/w4": 4, "ring": 100, "ring/k2": 101, "ring/k4": 102, "auto/k2": 202, "auto/k4": 204,
-                  # 256 persistent workgroups over a tile stream (csrc/gemm_split_persist.hip; M % 32 == 0, N % 256 == 0, >= 256 tiles):
+                  # 256 persistent workgroups over a tile stream (csrc/gemm_split16.hip; host side csrc/gemm_split3_dispatch.hip; M % 32 == 0, N % 256 == 0, >= 256 tiles):
                   # fp32 output / split3 output through the LDS transposition / split3 output through swapped operand roles
                   "persist": 300, "persist/swap": 302, "persist/128x128": 320, "persist/128x128/k2": 322, "persist/128x128/k4": 324,      # 320: the stream over 128x128 tiles, three-stage ring (round 6)
                   # round-4 first versions on v_mfma_f32_32x32x16_bf16 (the product kernels moved to 16x16x32, csrc/gemm_split16.hip): experiments build
@@ -133,7 +133,7 @@ SPLIT3_VARIANT = {"auto": -1, "128x256/w8": 0, "tail": 5,        # tail: the 128
                   "exp/reads-every-2nd": 3, "abl/no-copies": 31, "abl/no-barrier": 32, "abl/no-reads": 34, "abl/none": 37}
 
 
-# variants that exist only in the experiments build (measured slower or timing-only; csrc/gemm_split.hip, gemm_split_persist.hip): asking
+# variants that exist only in the experiments build (measured slower or timing-only; csrc/gemm_split3_exp.hip): asking
 # for one of them routes THAT call to libtokenhmr_hip_exp.so
 SPLIT3_EXP_ONLY = {"128x128/w4/s3/front", "128x128/w8", "128x128/w8/s3", "tail/w8", "128x256/w4", "256x256/w4", "ring", "ring/k2", "ring/k4", "exp/reads-every-2nd", "abl/no-copies",
                    "abl/no-barrier", "abl/no-reads", "abl/none", "old/128x256/w8", "old/128x128/w4", "old/persist", "old/persist/lds", "old/persist/swap"}
@@ -145,7 +145,7 @@ def _L_for(exp_only):
 
 def split3(x, out=None):
     """fp32 (R,K) -> the "split3" operand of gemm_split3: every element as three bf16 pieces h + m + l, laid out [R][K/8][3][8]
-    (returned as an int16 tensor of shape (R, K/8, 3, 8); see csrc/gemm_split.hip).  K % 8 == 0.  `x` may be row-strided (ld_src = its row
+    (returned as an int16 tensor of shape (R, K/8, 3, 8); see csrc/split3_convert.hip).  K % 8 == 0.  `x` may be row-strided (ld_src = its row
     stride, a multiple of 4); `out`: write into this (R, K/8, 3, 8) operand, which may be a view of a wider one (ld_dst, `_ld_s3`)."""
     R, K = x.shape
     ld_src = _ld(x, "x", 4)
